@@ -14,6 +14,11 @@ timed steps.
   python bench.py --gpus 1 --steps 10 --warmup 2
   python bench.py --gpus N ...        (no launcher: the script starts its N ranks itself, spawn_ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything beside the headline: the per-kernel HIP
+events and the roofline, the CPU baselines and the whole-frame check against the CPU oracle, `sustained`, `two_frames_in_flight`,
+`abi_path`, the warm BVH build; for N > 1 the other scheduler variants, the extra legs and every variant's parity check.
+--dump-outputs DIR writes the framebuffer of the last timed step (rank 0's, un-clamped float32) as DIR/framebuffer.npy.
 """
 import argparse
 import json
@@ -638,7 +643,14 @@ def main():
     ap.add_argument("--weak-tris", type=int, default=10_000_000, help="weak_soup: triangles per tile (= per rank)")
     ap.add_argument("--config4-width", type=int, default=1900)
     ap.add_argument("--config4-height", type=int, default=1080)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (see the module docstring); "
+                                                        "the --no-* options above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's framebuffer (rank 0's, un-clamped) as DIR/framebuffer.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.inproc_ranks > 1:
+        ap.error("--dump-outputs: --inproc-ranks is a diagnostic without a timed path to dump")
     if args.inproc_ranks > 1:
         if int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.gpus != 1:
             print("bench.py: --inproc-ranks is a one-process, one-GPU mode", file=sys.stderr)
@@ -717,7 +729,7 @@ def main():
     build_ms = sum(a.info()["build_ms"] for a in tracer.backend.adapter_cache.values()) if on_gpu else 0.0
     # the figure above is the process's FIRST build (code objects load, rocPRIM initialises: ~8 ms of it); the same mesh built again
     build_ms_warm = None
-    if on_gpu and world == 1 and n_dom == 1 and args.harness == "native":
+    if args.full and on_gpu and world == 1 and n_dom == 1 and args.harness == "native":
         from gravit_amd.adapter import HipMeshAdapter
         again = HipMeshAdapter(scene.meshes[0])
         build_ms_warm = again.info()["build_ms"]
@@ -753,23 +765,24 @@ def main():
     settle_frames = 26 if (on_gpu and world == 1 and n_dom > 1 and args.harness == "native") else 0
     for _ in range(settle_frames):
         frame()
-    # One GPU: the warm-up frames are bracketed kernel class by kernel class (closest hit, long rays, any hit) to find the DOMINANT class; the timed
+    # --full, one GPU: the warm-up frames are bracketed kernel class by kernel class (closest hit, long rays, any hit) to find the DOMINANT class; the timed
     # steps then carry HIP events around that class only -- every event pair is a few microseconds of the stream, inside a frame of under a
     # millisecond -- and the other classes are measured in a separate pass of K frames BEHIND the timed region.  Several ranks: all three
-    # classes in the timed steps (the per-rank rooflines use them).
+    # classes in the timed steps (the per-rank rooflines use them).  A plain run carries no events.
     warm_st = None
-    if on_gpu and world == 1 and args.warmup > 0:
+    if args.full and on_gpu and world == 1 and args.warmup > 0:
         capi.stats_reset()
         capi.profile(2)
     for _ in range(args.warmup):
         frame()
     barrier()
     if on_gpu:
-        if world == 1 and args.warmup > 0:
+        if args.full and world == 1 and args.warmup > 0:
             warm_st = capi.stats()
         capi.stats_reset()
-        # HIP events on the launch stream around the traversal kernels (2: closest hit, long rays, any hit; 3 / 4: closest / any hit only)
-        capi.profile(2 if warm_st is None else (3 if warm_st["ms_closest"] >= warm_st["ms_any"] else 4))
+        if args.full:
+            # HIP events on the launch stream around the traversal kernels (2: closest hit, long rays, any hit; 3 / 4: closest / any hit only)
+            capi.profile(2 if warm_st is None else (3 if warm_st["ms_closest"] >= warm_st["ms_any"] else 4))
     else:
         tracer.backend.rays_closest = tracer.backend.rays_any = 0
     per_frame, sums = [], {"rays_closest": 0, "rays_any": 0, "rays_sent": 0, "rounds": 0, "chains": 0, "host_syncs": 0, "bytes_sent": 0}
@@ -785,11 +798,14 @@ def main():
         raw_stats.append(tracer.frame_stats if keep_raw else frame_stats())
     barrier()
     t1 = time.perf_counter()
+    if args.dump_outputs and rank == 0:  # before anything else renders into the framebuffer (the --full passes and variants re-use the tracer)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "framebuffer.npy"), np.asarray(tracer.backend.framebuffer(False), np.float32))
     for fs in raw_stats:
         for k, v in (fs.as_dict() if hasattr(fs, "as_dict") else fs).items():
             sums[k] = sums.get(k, 0) + v
     st = capi.stats() if on_gpu else {}
-    if on_gpu:
+    if on_gpu and args.full:
         capi.profile(False)
     kernel_ms_source = "HIP events over the timed steps"
     if warm_st is not None:  # the classes that were not bracketed in the timed steps: a separate pass of K frames behind the timed region, all classes bracketed
@@ -835,7 +851,7 @@ def main():
 
     # N > 1: every variant and leg is VERIFIED in the same invocation -- rank 0 renders the variant's scene once more with a one-rank tracer of its own
     # (no communicator) and compares the composited framebuffer bit for bit, and the rays traced (summed over the ranks) with the one-rank counts
-    do_parity = world > 1 and not args.no_parity and not args.fake_comm
+    do_parity = world > 1 and args.full and not args.no_parity and not args.fake_comm
     parity_bad = []  # names of the variants / legs whose image or ray counts differ: the line is still printed, rank 0 leaves with status 4
     ref_cache = {}
     skip_known_user = int(dict(o.split("=") for o in args.opt).get("skip_known", 0))
@@ -862,10 +878,10 @@ def main():
         return par
 
     variants = None
-    if world > 1 and on_gpu and args.harness == "native":
+    if args.full and world > 1 and on_gpu and args.harness == "native":
         capi.set_option("frame_timing", 1)  # the variants and the extra legs carry the per-phase breakdown (five more event calls per exchange); `value` above ran without
     legs_error = None  # the first secondary measurement that failed (LegFailed): what is behind it is skipped, the line is still printed
-    if world > 1 and not args.single_variant:
+    if args.full and world > 1 and not args.single_variant:
         variants = {}
         primary = "image_replicated" if image_split else ("domain_bsp" if args.bsp else "domain_async")
         todo = [("domain_async", "domain", False), ("domain_bsp", "domain", True)] + ([("image_replicated", "image", False)] if args.harness == "native" else [])
@@ -924,7 +940,7 @@ def main():
     # N > 1, two more keys of the same line (never `value`): BASELINE configs[3] -- the 8-bunny grid under the Domain scheduler, the
     # configuration BASELINE.json names for the scaling curve -- and the weak-scaling soup (N tiles of 10 M triangles each)
     extra = {}
-    if world > 1 and not args.no_extra_legs and not args.single_variant and legs_error is None:
+    if args.full and world > 1 and not args.no_extra_legs and not args.single_variant and legs_error is None:
         from gravit_amd.layouts import NORMALS_SMOOTH
 
         def extra_legs():
@@ -1051,7 +1067,7 @@ def main():
             legs_error = str(e)
 
     if rank == 0:
-        gpu_fb = tracer.backend.framebuffer(False) if (on_gpu and world == 1 and n_dom == 1) else None  # before the extra legs reuse the backend
+        gpu_fb = tracer.backend.framebuffer(False) if (args.full and on_gpu and world == 1 and n_dom == 1) else None  # before the extra legs reuse the backend
         n_tris_local = max(m.tris.shape[0] for m in scene.meshes)
         b_ray = algorithmic_bytes_per_ray(n_tris_local)
         out = {
@@ -1117,10 +1133,10 @@ def main():
                                         "traced summed over the ranks against the one-rank counts; weak_soup: deposit counts (details: each variant's `parity`)",
                              "bit_exact": (not parity_bad and bool(checked)) if do_parity else None, "failed": parity_bad,
                              "variants": {k: {kk: v.get(kk) for kk in ("bit_exact", "rays_equal", "deposits_equal", "max_abs_diff", "lit_pixels") if kk in v} for k, v in checked.items()},
-                             "skipped": None if do_parity else ("--no-parity" if args.no_parity else "--fake-comm")}
+                             "skipped": None if do_parity else ("no --full" if not args.full else "--no-parity" if args.no_parity else "--fake-comm")}
         if legs_error is not None:
             out["legs_error"] = legs_error  # a secondary measurement failed in the ray exchange; it and what was behind it are missing, `value` was measured before
-        if on_gpu:
+        if args.full and on_gpu:
             dom = "closest" if st["ms_closest"] >= st["ms_any"] else "any"
             if warm_st is not None:  # the class that was bracketed in the timed steps
                 dom = "closest" if warm_st["ms_closest"] >= warm_st["ms_any"] else "any"
@@ -1164,28 +1180,28 @@ def main():
                                                                   "triangle_tests": vs["tri_tests_per_ray"], "sample_rays": int(len(rr))}
                 except Exception as e:
                     out["roofline"]["visits_per_primary_ray"] = "failed: %r" % (e,)
-        if on_gpu and world == 1 and n_dom == 1 and args.harness == "native" and not args.no_sustained:
+        if args.full and on_gpu and world == 1 and n_dom == 1 and args.harness == "native" and not args.no_sustained:
             try:
                 out["sustained"] = sustained(frame, rays_total / args.steps)
             except Exception as e:
                 out["sustained"] = {"failed": repr(e)}
-        if on_gpu and world == 1 and n_dom == 1 and args.harness == "native" and not args.no_abi_path:
+        if args.full and on_gpu and world == 1 and n_dom == 1 and args.harness == "native" and not args.no_abi_path:
             try:
                 out["two_frames_in_flight"] = two_frames_in_flight(scene, args.steps, rays_total / args.steps)
             except Exception as e:
                 out["two_frames_in_flight"] = {"failed": repr(e)}
-        if on_gpu and world == 1 and n_dom == 1 and not args.no_abi_path:
+        if args.full and on_gpu and world == 1 and n_dom == 1 and not args.no_abi_path:
             try:
                 out["abi_path"] = abi_path(scene, tracer, capi, np)
             except Exception as e:
                 out["abi_path"] = {"failed": repr(e)}
-        if on_gpu and world == 1 and n_dom == 1 and not args.no_cpu_baseline:
+        if args.full and on_gpu and world == 1 and n_dom == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(scene, args.cpu_row_stride, host_cores(), gpu_fb=gpu_fb, parity_out=out,
                                                    adapter=tracer.backend.adapter(0) if args.harness == "native" else None)
             except Exception as e:  # the checker is optional for the measurement itself
                 out["cpu_baseline"] = {"value": None, "unit": "Mrays/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
-        if world > 1 and not args.no_cpu_baseline:
+        if args.full and world > 1 and not args.no_cpu_baseline:
             # the CPU column of the N > 1 line: the same one-GPU workload (the un-cut soup, the whole film) on rank 0's host cores while the other ranks wait at
             # the last barrier; rank 0's own one-rank render of that scene (the image variant's reference) is compared with the CPU oracle's frame on the way
             try:

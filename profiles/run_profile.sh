@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-abi-path --no-sustained $@"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-abi-path --no-sustained $@"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $REPO/bench.py $ARGS > $OUT/bench_trace.log 2>&1
 # (TA_* counters abort rocprofv3 on this pool -- signal 6, the pass then runs into its timeout: gpurun_out/pmc_q0_ta, round 3 -- so the
 # vector-memory path is read through the TCP counters: tag look-ups, requests to L2, latencies, stall cycles)

@@ -8,6 +8,7 @@ Fixtures are DATA (inputs and expected outputs), never reference source text:
   ref_simple.ppm, ref_bunny.ppm  the reference's own golden images (Test/CTESTtest/data/), copied as they are
   bunny.obj                      the reference's data/geom/bunny.obj (input of the bunny golden)
   bun_zipper.npz                 vertices/faces of data/geom/bunny/reconstruction/bun_zipper.ply (config 2 input)
+  bun_zipper.ply.xz              that PLY file itself, xz-compressed (the PLY reader must reproduce bun_zipper.npz from it)
   ref_vectors.json               known answers produced by the REFERENCE's own code (Shade, Light, generateNormals,
                                  RayPacketIntersection, RandEngine, Mesh::addFace, struct sizes) through oracle/ref_shim.cpp
   oracle_vectors.npz             outputs of the pinned CPU oracle on seeded inputs (per-ray hits on bunny.obj, framebuffer
@@ -19,6 +20,7 @@ Fixtures are DATA (inputs and expected outputs), never reference source text:
 import ctypes as C
 import hashlib
 import json
+import lzma
 import os
 import shutil
 import sys
@@ -83,6 +85,8 @@ def main():
     shutil.copyfile(os.path.join(REF, "data/geom/bunny.obj"), os.path.join(HERE, "bunny.obj"))
     v, t = scenes.read_ply(os.path.join(REF, "data/geom/bunny/reconstruction/bun_zipper.ply"))
     np.savez_compressed(os.path.join(HERE, "bun_zipper.npz"), verts=v, tris=t)
+    with open(os.path.join(REF, "data/geom/bunny/reconstruction/bun_zipper.ply"), "rb") as f:
+        open(os.path.join(HERE, "bun_zipper.ply.xz"), "wb").write(lzma.compress(f.read(), preset=9 | lzma.PRESET_EXTREME))
 
     out = {"sizes": {"ray": ref.ref_sizeof_ray(), "material": ref.ref_sizeof_material(), "box3d": ref.ref_sizeof_box3d()},
            "ray_epsilon": float(ref.ref_ray_epsilon())}

@@ -118,7 +118,7 @@ def test_bench_script_multi_rank_branch_under_gloo(tmp_path):
     for r in range(2):
         e = dict(env, RANK=str(r), LOCAL_RANK=str(r))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--harness", "checker", "--tris", "20000",
-                                       "--width", "96", "--height", "54", "--steps", "2", "--warmup", "1", "--weak-tris", "8000", "--config4-width", "95", "--config4-height", "54"],
+                                       "--width", "96", "--height", "54", "--steps", "2", "--warmup", "1", "--weak-tris", "8000", "--config4-width", "95", "--config4-height", "54", "--full"],
                                       env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs[0][1][-2000:] + outs[1][1][-2000:]
@@ -160,7 +160,7 @@ def test_bench_script_fails_loudly_when_a_variant_image_differs(tmp_path):
     import sys
 
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--harness", "checker", "--tris", "20000", "--width", "96", "--height", "54",
-                        "--steps", "1", "--warmup", "0", "--no-extra-legs", "--no-cpu-baseline"], env=dict(_clean_env(), GVT_BENCH_BREAK_PARITY="domain_bsp"), capture_output=True, text=True, timeout=300)
+                        "--steps", "1", "--warmup", "0", "--no-extra-legs", "--no-cpu-baseline", "--full"], env=dict(_clean_env(), GVT_BENCH_BREAK_PARITY="domain_bsp"), capture_output=True, text=True, timeout=300)
     assert p.returncode == 4, p.stderr[-3000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["value"] > 0 and j["parity"]["bit_exact"] is False and j["parity"]["failed"] == ["domain_bsp"]
@@ -182,7 +182,7 @@ def test_bench_script_keeps_its_line_when_a_secondary_leg_fails(tmp_path):
     for r in range(2):
         e = dict(env, RANK=str(r), LOCAL_RANK=str(r))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--harness", "checker", "--tris", "20000",
-                                       "--width", "96", "--height", "54", "--steps", "1", "--warmup", "0", "--weak-tris", "8000", "--config4-width", "95", "--config4-height", "54"],
+                                       "--width", "96", "--height", "54", "--steps", "1", "--warmup", "0", "--weak-tris", "8000", "--config4-width", "95", "--config4-height", "54", "--full"],
                                       env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs[0][1][-2000:] + outs[1][1][-2000:]
@@ -208,7 +208,7 @@ def test_bench_script_starts_its_own_ranks_when_no_launcher_did(tmp_path):
     import sys
 
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--harness", "checker", "--tris", "20000", "--width", "96", "--height", "54",
-                        "--steps", "1", "--warmup", "0", "--no-extra-legs"], env=_clean_env(), capture_output=True, text=True, timeout=300)
+                        "--steps", "1", "--warmup", "0", "--no-extra-legs", "--full"], env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line, rank 0's"
@@ -227,3 +227,37 @@ def test_bench_script_launcher_reports_a_failing_rank(tmp_path):
     assert p.returncode != 0
     assert "a rank left with status" in p.stderr
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_script_plain_run_times_only_and_dumps_its_frame(tmp_path, gpus):
+    """A plain run (no --full) is the headline alone: `--steps` timed steps, the line's headline keys, none of the extra measurements or checks;
+    --dump-outputs writes the framebuffer of the last timed step, which is the checker's image of the same scene (one rank: the Image scheduler;
+    two: rank 0's composite of the Domain scheduler), and a second run with the same arguments writes the same bytes."""
+    import json
+    import subprocess
+    import sys
+
+    from gravit_amd.layouts import NORMALS_FLAT
+
+    sc = scenes.soup_scene(20000, 96, 54) if gpus == 1 else scenes.soup_domains_scene(20000, 2, 96, 54)
+    ref_fb, _ = oracle_render(sc, NORMALS_FLAT)
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--harness", "checker", "--tris", "20000", "--width", "96", "--height", "54",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], env=_clean_env(), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "Mrays/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert not {"roofline", "cpu_baseline", "sustained", "abi_path", "two_frames_in_flight", "variants", "config4_bunny_grid", "weak_soup"} & set(j)
+        if gpus > 1:
+            assert j["parity"]["skipped"] == "no --full" and j["parity"]["bit_exact"] is None
+        assert sorted(os.listdir(d)) == ["framebuffer.npy"]
+        fb = np.load(d / "framebuffer.npy")
+        assert fb.dtype == np.float32 and fb.shape == (54, 96, 4)
+        dumps.append(fb)
+    assert (fb[..., 3] > 0).sum() > 100
+    assert np.array_equal(dumps[0], dumps[1]) and np.array_equal(dumps[0], np.asarray(ref_fb, np.float32).reshape(54, 96, 4))

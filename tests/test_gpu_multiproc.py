@@ -70,7 +70,7 @@ def test_bench_script_starts_its_ranks_and_exchanges_over_the_rccl_leg(hip, tmp_
     """plain `python bench.py --gpus 2` (no launcher): the script starts two ranks, each builds the library's communicator and every variant
     and extra leg runs its exchanges through ncclSend / ncclRecv / ncclReduce (stand-in transport; --same-gpu: both ranks on device 0)."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-gpu", "--tris", "200000", "--weak-tris", "100000", "--width", "480", "--height", "270",
-                        "--config4-width", "380", "--config4-height", "216", "--steps", "2", "--warmup", "1"], cwd=ROOT, env=rank_env(tmp_path), stdout=subprocess.PIPE,
+                        "--config4-width", "380", "--config4-height", "216", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, env=rank_env(tmp_path), stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -1040,6 +1040,34 @@ def test_camera_rectangle_edge_cases(hip, case):
     assert sum(r[1]["rays_closest"] for r in res.values()) == std.rays_closest and sum(r[1]["rays_sent"] for r in res.values()) == std.rays_sent
 
 
+def test_bench_script_one_gpu_plain_and_full(hip, tmp_path):
+    """bench.py --gpus 1 at a reduced size: a plain run is the headline alone (`--steps` timed steps, no roofline, CPU baseline or other extra key);
+    --full adds them, the whole-frame check against the CPU oracle included.  Both dump the last timed step's framebuffer, and both dumps are the CPU
+    oracle's image of the same scene, bit for bit."""
+    import json
+    import subprocess
+    import sys
+
+    from tests.conftest import ROOT
+    ref_fb, _ = oracle_render(scenes.soup_scene(200000, 480, 270), NORMALS_FLAT)
+    extra = {"roofline", "cpu_baseline", "sustained", "abi_path", "two_frames_in_flight", "parity"}
+    for full in (False, True):
+        d = tmp_path / ("full" if full else "plain")
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--tris", "200000", "--width", "480", "--height", "270", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)] + (["--full"] if full else []), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
+        j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert j["steps"] == 3 and j["value"] > 0 and j["ms_per_step"] > 0 and j["unit"] == "Mrays/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        if full:
+            assert extra <= set(j) and j["roofline"]["frac"] > 0 and j["parity"]["bit_exact"] is True and j["cpu_baseline"]["value"] > 0, {k: j.get(k) for k in extra}
+        else:
+            assert not extra & set(j)
+        fb = np.load(d / "framebuffer.npy")
+        assert fb.dtype == np.float32 and fb.shape == (270, 480, 4) and (fb[..., 3] > 0).sum() > 1000
+        assert np.array_equal(fb, np.asarray(ref_fb, np.float32).reshape(270, 480, 4)), "plain" if not full else "full"
+
+
 @pytest.mark.parametrize("launcher", ["torch.distributed.run", "none"])
 def test_bench_script_native_multi_process_plumbing(hip, tmp_path, launcher):
     """bench.py's N > 1 branch with the NATIVE harness, two processes on this one GPU: RCCL refuses two ranks on one device, so
@@ -1059,7 +1087,7 @@ def test_bench_script_native_multi_process_plumbing(hip, tmp_path, launcher):
     pre = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)] if launcher != "none" else [sys.executable]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(pre + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-gpu", "--fake-comm", "--tris", "200000", "--weak-tris", "100000", "--width", "480", "--height", "270",
-                              "--steps", "2", "--warmup", "1"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                              "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["value"] > 0 and j["config"]["harness"] == "native" and j["roofline"]["frac"] > 0

@@ -258,8 +258,9 @@ def test_rccl_stand_in_of_the_multi_process_tests_builds_and_covers_the_librarys
 
 def test_read_ply_ascii_binary_and_colors(tmp_path):
     """scenes.read_ply_full against tiny committed PLY files in the three encodings PlyReader.cpp:54-176 takes through ply.c; colours only when the
-    vertex element has more than five properties (PlyReader.cpp:123), as /255 floats; the reference's bun_zipper.ply (where the GraviT tree is present)
+    vertex element has more than five properties (PlyReader.cpp:123), as /255 floats; the reference's bun_zipper.ply (committed xz-compressed)
     reproduces the committed bun_zipper.npz."""
+    import lzma
     import os
 
     from gravit_amd import scenes
@@ -286,11 +287,13 @@ def test_read_ply_ascii_binary_and_colors(tmp_path):
                     b"property list uchar int vertex_indices\nend_header\n0 0 0\n1 0 0\n1 1 0\n3 0 1 7\n")
     with pytest.raises(ValueError):
         scenes.read_ply(str(oob))
-    ref = "/root/reference/data/geom/bunny/reconstruction/bun_zipper.ply"
-    if os.path.exists(ref):
-        z = np.load(os.path.join(GOLDEN, "bun_zipper.npz"))
-        v, t = scenes.read_ply(ref)
-        keys = list(z.keys())
-        vk = [k for k in keys if z[k].dtype.kind == "f" and z[k].ndim == 2][0]
-        tk = [k for k in keys if z[k].dtype.kind in "iu" and z[k].ndim == 2][0]
-        assert np.array_equal(v, z[vk]) and np.array_equal(t, z[tk].astype(np.int32))
+    ref = tmp_path / "bun_zipper.ply"
+    with lzma.open(os.path.join(GOLDEN, "bun_zipper.ply.xz")) as f:
+        ref.write_bytes(f.read())
+    z = np.load(os.path.join(GOLDEN, "bun_zipper.npz"))
+    v, t = scenes.read_ply(str(ref))
+    keys = list(z.keys())
+    vk = [k for k in keys if z[k].dtype.kind == "f" and z[k].ndim == 2][0]
+    tk = [k for k in keys if z[k].dtype.kind in "iu" and z[k].ndim == 2][0]
+    assert len(v) == 35947 and len(t) == 69451
+    assert np.array_equal(v, z[vk]) and np.array_equal(t, z[tk].astype(np.int32))

@@ -6,7 +6,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq 1 $reps); do
   for spec in "$@"; do
     lib=${spec%%:*}; opts=""; [ "$lib" != "$spec" ] && opts=${spec#*:}
-    args=""; for kv in ${opts//,/ }; do args="$args --opt $kv"; done
+    args="--full"; for kv in ${opts//,/ }; do args="$args --opt $kv"; done
     GVT_HIP_LIB=$PWD/$lib python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-abi-path --no-sustained $args > gpurun_out/ab/ab.log 2>&1
     python - "$spec" <<'PY'
 import json, sys

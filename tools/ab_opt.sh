@@ -2,7 +2,7 @@
 # A/B of library options on the benchmark frame (per-kernel HIP events of bench.py): bash tools/ab_opt.sh "opt=v[,opt=v]" ["opt=v" ...]
 mkdir -p gpurun_out/ab
 for o in "$@"; do
-  args=""; for kv in ${o//,/ }; do args="$args --opt $kv"; done
+  args="--full"; for kv in ${o//,/ }; do args="$args --opt $kv"; done
   python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-abi-path --no-sustained $args > gpurun_out/ab/ab.log 2>&1
   python - <<PY
 import json

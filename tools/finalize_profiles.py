@@ -1,4 +1,4 @@
-"""After tools/refresh_profiles.sh + profiles/run_profile.sh + a plain `python bench.py > gpurun_out/bench_final.log` on the GPU box: copies the kept summaries into
+"""After tools/refresh_profiles.sh + profiles/run_profile.sh + a `python bench.py --full` line saved as bench_final.log beside their outputs on the GPU box: copies the kept summaries into
 profiles/, runs tools/collect_profiles.py, stores the bench line as profiles/<tag>_bench.json and rewrites the hash / headline references in DESIGN.md and
 profiles/README.md.   python tools/finalize_profiles.py [tag=r06]"""
 import csv, glob, json, os, re, shutil, subprocess, sys

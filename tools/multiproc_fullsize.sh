@@ -1,5 +1,5 @@
 #!/bin/bash
-# The N > 1 bench line at FULL size on ONE GPU box (VERDICT r5 #1c): `python bench.py --gpus N --same-gpu` -- the script starts its N ranks itself, every rank a process
+# The N > 1 bench line at FULL size on ONE GPU box (VERDICT r5 #1c): `python bench.py --gpus N --same-gpu --full` -- the script starts its N ranks itself, every rank a process
 # on device 0, the library's RCCL leg over the stand-in transport tests/fake_rccl (RCCL refuses two ranks on a device) -- 10 M-triangle soup cut into N tiles, the
 # replicated Image scheduler on the un-cut soup, config 4 at 1900x1080, N weak tiles of 10 M triangles each, per-variant parity against rank 0's one-rank render,
 # the CPU baseline on rank 0.  Records the wall time against the driver's 600 s limit.  The pool allows 6 processes on the card at once: N <= 6 here.
@@ -13,10 +13,10 @@ export GVT_HIP_RCCL_LIB=$REPO/tests/fake_rccl/libfakerccl.so TMPDIR=/tmp/mpf_$$ 
 mkdir -p $TMPDIR
 OUT=gpurun_out/${TAG}_multiproc_fullsize_$N
 t0=$(date +%s)
-timeout -k 10 900 python3 bench.py --gpus $N --same-gpu "$@" > $OUT.json 2> $OUT.err
+timeout -k 10 900 python3 bench.py --gpus $N --same-gpu --full "$@" > $OUT.json 2> $OUT.err
 rc=$?
 t1=$(date +%s)
-echo "bench.py --gpus $N --same-gpu $@: exit status $rc, wall $((t1 - t0)) s" | tee $OUT.txt
+echo "bench.py --gpus $N --same-gpu --full $@: exit status $rc, wall $((t1 - t0)) s" | tee $OUT.txt
 python3 - $OUT.json >> $OUT.txt <<'PY'
 import json, sys
 lines = [l for l in open(sys.argv[1]) if l.startswith("{")]

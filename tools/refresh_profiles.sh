@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/refresh_$TAG
 mkdir -p $OUT
 cd $REPO
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench.log 2>&1 && grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
+python3 bench.py --full --steps 20 --warmup 3 > $OUT/bench.log 2>&1 && grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 python3 tools/tail_probe.py any > $OUT/tail_fit.txt 2>&1
 python3 tools/bench_configs.py roofline=1 > $OUT/configs.txt 2>&1
 python3 bench.py --domains 8 --steps 20 --warmup 3 > $OUT/domains8.log 2>&1

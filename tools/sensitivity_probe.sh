@@ -2,7 +2,7 @@
 # How much does k_trace's time move per extra L1 look-up and per extra vector instruction of a node step?  (profiles/r04_node32_estimate.txt:
 # a 32-byte node trades -2 look-ups for ~+55 instructions per step; this measures both slopes on the benchmark launch instead of assuming them.)
 #   build (here, no GPU needed):  bash tools/sensitivity_probe.sh build     -> tools/libgvt_hip_probe_{C0,L1,L2,L4,V32,V64}.so from a patched COPY of csrc/
-#   run   (GPU box):              bash tools/sensitivity_probe.sh run       -> gpurun_out/sensitivity.txt
+#   run   (GPU box):              bash tools/sensitivity_probe.sh run       -> $OUT_DIR/sensitivity.txt (OUT_DIR: default out/)
 # The shipped sources are not touched: the patch below is applied to a scratch copy.
 #   L<n>: n extra `global_load_lds` dword loads of the node's own line per node step (destination LDS: no registers, the line is the one the
 #         node fetch brings anyway -> no extra HBM / L2 traffic, only n x 64 more look-ups in the L1's tag pipe per wave step; a node fetch is 4 x 64)
@@ -55,15 +55,16 @@ EOF
   done
   exit 0
 fi
-mkdir -p gpurun_out
-OUT=gpurun_out/sensitivity.txt
+OUT_DIR=${OUT_DIR:-out}
+mkdir -p $OUT_DIR
+OUT=$OUT_DIR/sensitivity.txt
 : > $OUT
 for v in shipped C0 L1 L2 L4 V32 V64 shipped; do
   lib=gravit_amd/libgvt_hip.so
   [ $v != shipped ] && lib=tools/libgvt_hip_probe_$v.so
   echo "== $v" >> $OUT
-  GVT_HIP_LIB=$ROOT/$lib python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-abi-path --no-sustained > gpurun_out/sens_$v.log 2>&1
-  python3 - gpurun_out/sens_$v.log >> $OUT <<'EOF'
+  GVT_HIP_LIB=$ROOT/$lib python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-abi-path --no-sustained > $OUT_DIR/sens_$v.log 2>&1
+  python3 - $OUT_DIR/sens_$v.log >> $OUT <<'EOF'
 import json, sys
 j = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 print(json.dumps({"ms_per_step": j["ms_per_step"], "roofline": j["roofline"], "kernels": j.get("kernel_ms_per_step") or j.get("launch_ms")}))
