@@ -102,6 +102,31 @@ class HipMeshAdapter:
                 "bbox_hi": list(i.bbox_hi), "build_ms": i.build_ms, "max_leaf": i.max_leaf, "bytes_nodes": i.bytes_nodes, "bytes_tris": i.bytes_tris,
                 "packet": int(i.packet), "sah_inner": float(i.sah_inner)}
 
+    def update_vertices(self, verts, normals=None):
+        """gvt_hip_mesh_update_vertices: new positions for the same triangles, the tree refitted in place (every pointer a tracer borrowed
+        stays valid).  verts / normals: (nV, 3) float32 -- numpy on the host, or torch tensors on this mesh's GPU (no host round trip).
+        normals=None: regenerated as at create.  Returns the device time of the update in ms."""
+        ms = C.c_float(0.0)
+        if hasattr(verts, "data_ptr"):  # a torch tensor: the device path
+            if not verts.is_cuda or (normals is not None and not normals.is_cuda):
+                raise ValueError("update_vertices: torch tensors must be on the GPU (pass numpy arrays for host data)")
+            import torch
+
+            v = verts.detach().to(torch.float32).contiguous().reshape(-1, 3)
+            nrm = None if normals is None else normals.detach().to(torch.float32).contiguous().reshape(-1, 3)
+            torch.cuda.current_stream(v.device).synchronize()  # (the tensors are written on torch's stream, the update runs on the library's)
+            rc = self.lib.gvt_hip_mesh_update_vertices(self.h, C.c_void_p(v.data_ptr()), C.c_size_t(v.shape[0]),
+                                                       None if nrm is None else C.c_void_p(nrm.data_ptr()), C.c_uint32(1), C.byref(ms))
+            capi.check(rc, "gvt_hip_mesh_update_vertices")
+            self.verts = v.cpu().numpy()
+        else:
+            v = capi.f32(verts, (-1, 3))
+            nrm = None if normals is None else capi.f32(normals, (-1, 3))
+            capi.check(self.lib.gvt_hip_mesh_update_vertices(self.h, capi.ptr(v), C.c_size_t(len(v)), capi.ptr(nrm), C.c_uint32(0), C.byref(ms)),
+                       "gvt_hip_mesh_update_vertices")
+            self.verts = v
+        return float(ms.value)
+
     def normals(self):
         out = np.zeros((len(self.verts), 3), np.float32)
         capi.check(self.lib.gvt_hip_mesh_get_normals(self.h, capi.ptr(out)), "gvt_hip_mesh_get_normals")
@@ -242,6 +267,13 @@ class TopLevel:
             self.h = None
 
     __del__ = close
+
+    def update(self, inst_lo, inst_hi):
+        """gvt_hip_top_update: new instance boxes for the same set (the order and the top BVH rebuilt in place)."""
+        lo = capi.f32(inst_lo, (-1, 3))
+        hi = capi.f32(inst_hi, (-1, 3))
+        capi.check(self.lib.gvt_hip_top_update(self.h, capi.ptr(lo), capi.ptr(hi), C.c_size_t(len(lo))), "gvt_hip_top_update")
+        self.lo, self.hi = lo, hi
 
     def order(self):
         out = np.zeros(self.n, np.int32)

@@ -16,21 +16,21 @@ ABI_VERSION = 6  # GVT_HIP_ABI_VERSION of include/gvt_hip.h this file mirrors (t
 
 SYMBOLS = [
     "gvt_hip_init", "gvt_hip_set_stream", "gvt_hip_synchronize", "gvt_hip_last_error",
-    "gvt_hip_mesh_create", "gvt_hip_mesh_destroy", "gvt_hip_trace_ex", "gvt_hip_mesh_get_info", "gvt_hip_mesh_get_normals",
+    "gvt_hip_mesh_create", "gvt_hip_mesh_destroy", "gvt_hip_trace_ex", "gvt_hip_mesh_get_info", "gvt_hip_mesh_get_normals", "gvt_hip_mesh_update_vertices",
     "gvt_hip_trace", "gvt_hip_intersect", "gvt_hip_occluded",
     "gvt_hip_queue_create", "gvt_hip_queue_destroy", "gvt_hip_queue_reserve", "gvt_hip_queue_clear", "gvt_hip_queue_size",
     "gvt_hip_queue_append", "gvt_hip_queue_append_flags", "gvt_hip_abi_version", "gvt_hip_queue_export", "gvt_hip_trace_queue", "gvt_hip_trace_queue_sink",
     "gvt_hip_camera_generate",
     "gvt_hip_camera_generate_tiled",
     "gvt_hip_camera_filter",
-    "gvt_hip_top_create", "gvt_hip_top_destroy", "gvt_hip_top_order", "gvt_hip_shuffle", "gvt_hip_queue_sizes",
+    "gvt_hip_top_create", "gvt_hip_top_destroy", "gvt_hip_top_order", "gvt_hip_top_update", "gvt_hip_shuffle", "gvt_hip_queue_sizes",
     "gvt_hip_fb_create", "gvt_hip_fb_destroy", "gvt_hip_fb_clear", "gvt_hip_fb_download", "gvt_hip_fb_device_ptr",
     "gvt_hip_fb_write_ppm_bytes",
     "gvt_hip_profile", "gvt_hip_stats_read", "gvt_hip_stats_reset", "gvt_hip_set_option", "gvt_hip_is_experiments_build", "gvt_hip_counters_peek", "gvt_hip_visit_stats", "gvt_hip_wide_visit_stats", "gvt_hip_mesh_download_nodes", "gvt_hip_mesh_download_wide", "gvt_hip_mesh_download_clusters", "gvt_hip_mesh_upload_nodes", "gvt_hip_marked_visit_stats", "gvt_hip_image_frame",
     "gvt_hip_math_probe", "gvt_hip_ctx_create", "gvt_hip_ctx_make_current", "gvt_hip_ctx_destroy",
     "gvt_hip_comm_unique_id", "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_hub_abort", "gvt_hip_hub_destroy", "gvt_hip_comm_create_local",
     "gvt_hip_comm_destroy", "gvt_hip_comm_rank", "gvt_hip_comm_world", "gvt_hip_comm_count", "gvt_hip_comm_reserved_cus", "gvt_hip_comm_set_deadline_ms", "gvt_hip_comm_selftest",
-    "gvt_hip_tracer_create", "gvt_hip_tracer_destroy", "gvt_hip_tracer_set_camera", "gvt_hip_tracer_set_domains", "gvt_hip_tracer_frame",
+    "gvt_hip_tracer_create", "gvt_hip_tracer_destroy", "gvt_hip_tracer_set_camera", "gvt_hip_tracer_set_transforms", "gvt_hip_tracer_set_domains", "gvt_hip_tracer_frame",
 ]
 
 

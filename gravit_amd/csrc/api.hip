@@ -371,7 +371,41 @@ extern "C" void gvt_hip_mesh_destroy(gvt_hip_mesh *M) {
   if (g_ctx.ready) hipStreamSynchronize(g_ctx.stream);
   hipFree(M->d_verts); hipFree(M->d_tris); hipFree(M->d_normals); hipFree(M->d_vcolors); hipFree(M->d_materials);
   hipFree(M->d_face_mat); hipFree(M->d_nodes); hipFree(M->d_tri); hipFree(M->d_slot_of); hipFree(M->d_nodes4); hipFree(M->d_nodes4c); hipFree(M->d_nodes4q); hipFree(M->d_triq);
+  refit_tables_free(M);
   delete M;
+}
+
+// Animated meshes: new positions, the same topology.  The vertices (and the normals, given or regenerated on the device) are copied into the
+// mesh's own arrays and every layout is refitted in place (lbvh.hip refit_lbvh): no pointer a tracer or context borrowed changes.
+extern "C" int gvt_hip_mesh_update_vertices(gvt_hip_mesh *M, const float *verts, size_t nV, const float *vnormals, uint32_t flags, float *ms_out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!M) { set_error("mesh_update_vertices: null mesh"); return GVT_HIP_ERR_INVALID; }
+  if (flags & ~GVT_HIP_UPDATE_DEVICE) { set_error("mesh_update_vertices: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
+  if (nV != M->nV) { set_error("mesh_update_vertices: %zu vertices given, the mesh has %zu (topology changes need a new mesh)", nV, M->nV); return GVT_HIP_ERR_INVALID; }
+  if (nV && !verts) { set_error("mesh_update_vertices: null vertex array"); return GVT_HIP_ERR_INVALID; }
+  if (M->d_nodes4q || M->d_triq) { set_error("mesh_update_vertices: meshes built with the quad layouts (knob quad) cannot be refitted; create a new mesh"); return GVT_HIP_ERR_INVALID; }
+  Ctx &C = g_ctx;
+  hipStream_t st = C.stream;
+  const hipMemcpyKind kind = (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (nV) {
+    HIPCHK(hipMemcpyAsync(M->d_verts, verts, sizeof(float) * 3 * nV, kind, st));
+    if (vnormals) HIPCHK(hipMemcpyAsync(M->d_normals, vnormals, sizeof(float) * 3 * nV, kind, st));
+  }
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); set_error("mesh_update_vertices: hipEventCreate failed"); return GVT_HIP_ERR_DEVICE; }
+  int rc = hipEventRecord(e0, st) == hipSuccess ? 0 : GVT_HIP_ERR_DEVICE;
+  if (!rc && nV && !vnormals) rc = regen_normals(M); // EmbreeMeshAdapter.cpp:129, as at create
+  if (!rc) rc = refit_lbvh(M);
+  float ms = 0.f;
+  if (!rc && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
+    set_error("mesh_update_vertices: %s", hipGetErrorString(hipGetLastError()));
+    rc = GVT_HIP_ERR_DEVICE;
+  }
+  hipStreamSynchronize(st);
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (!rc && ms_out) *ms_out = ms;
+  return rc;
 }
 
 extern "C" int gvt_hip_mesh_get_info(const gvt_hip_mesh *M, gvt_hip_mesh_info *o) {
@@ -856,6 +890,7 @@ extern "C" int gvt_hip_mesh_upload_nodes(gvt_hip_mesh *M, const void *in, size_t
   if (!M || !in || n_nodes != M->nNodes) { set_error("mesh_upload_nodes: null argument or n_nodes != %zu", M ? M->nNodes : (size_t)0); return GVT_HIP_ERR_INVALID; }
   HIPCHK(hipStreamSynchronize(g_ctx.stream));
   if (n_nodes) HIPCHK(hipMemcpy(M->d_nodes, in, n_nodes * sizeof(BvhNode), hipMemcpyHostToDevice));
+  hipFree(M->d_range2); M->d_range2 = nullptr; // (a refit derives the new tree's ranges)
   return 0;
 }
 extern "C" int gvt_hip_marked_visit_stats(gvt_hip_mesh *M, const float *org, const float *dir, size_t n, float tnear, const unsigned char *marks, uint32_t *counts) {

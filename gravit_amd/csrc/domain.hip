@@ -1009,6 +1009,28 @@ extern "C" int gvt_hip_tracer_set_camera(gvt_hip_tracer *R, const gvt_hip_camera
   return 0;
 }
 
+// Rigid motion: the instance matrices of the next frame.  The tracer's copies and the minv / normi rows of its per-instance table (d_insts) are
+// replaced, ordered on the calling context's stream.  What else the tracer derived at create -- `surfaces` (the meshes' packet_ok) and the timed
+// routes -- is a speed guess only: images never depend on it.
+extern "C" int gvt_hip_tracer_set_transforms(gvt_hip_tracer *R, const float *m, const float *minv, const float *normi, size_t n_inst) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!R || (n_inst && (!m || !minv || !normi))) { set_error("tracer_set_transforms: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (n_inst != R->n_inst) { set_error("tracer_set_transforms: %zu instances given, the tracer has %zu", n_inst, R->n_inst); return GVT_HIP_ERR_INVALID; }
+  if (!n_inst) return 0;
+  static_assert(offsetof(WaveInst, minv) == 0 && offsetof(WaveInst, normi) == sizeof(Mat4), "WaveInst: minv and normi lead the record");
+  const size_t row = sizeof(Mat4) + sizeof(Mat3);
+  std::vector<unsigned char> rows(row * n_inst);
+  for (size_t i = 0; i < n_inst; i++) {
+    std::memcpy(rows.data() + row * i, minv + 16 * i, sizeof(Mat4));
+    std::memcpy(rows.data() + row * i + sizeof(Mat4), normi + 9 * i, sizeof(Mat3));
+  }
+  hipStream_t st = gctx().stream;
+  HIPCHK(hipMemcpy2DAsync(R->d_insts, sizeof(WaveInst), rows.data(), row, row, n_inst, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  R->m.assign(m, m + 16 * n_inst); R->minv.assign(minv, minv + 16 * n_inst); R->normi.assign(normi, normi + 9 * n_inst);
+  return 0;
+}
+
 // mpiInstanceMap (DomainTracer.h:115-144): owner[i] = rank that holds instance i's data.  comm == NULL: one rank (Image scheduler).
 extern "C" int gvt_hip_tracer_set_domains(gvt_hip_tracer *R, const int32_t *owner, gvt_hip_comm *comm) {
   if (!R) { set_error("tracer_set_domains: null"); return GVT_HIP_ERR_INVALID; }

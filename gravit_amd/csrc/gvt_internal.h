@@ -195,6 +195,11 @@ struct gvt_hip_mesh {
   float build_ms = 0.f;
   float sah_inner = 0.f;      // sum over the inner nodes of area(node) / area(root)
   bool packet_ok = false;     // coherent lists over this mesh are traversed a packet per wave (k_packet)
+  // refit tables (gvt_hip_mesh_update_vertices), allocated by the first update: meshes that are never updated cost nothing
+  uint2 *d_range2 = nullptr;  // slot range [first, end) of every binary node's subtree
+  uint2 *d_range4 = nullptr;  // ... of every 4-wide node's subtree
+  unsigned *d_vlist = nullptr;  // normal regeneration: the corners (3 * face + corner) of every vertex, vertex by vertex in face order
+  unsigned *d_vstart = nullptr; // ... vertex v's corners are d_vlist[d_vstart[v] .. d_vstart[v + 1])
 };
 
 struct gvt_hip_queue {
@@ -306,6 +311,9 @@ int trav_overflow_fetch_async();
 int trav_overflow_result();
 int build_nodes4(gvt_hip_mesh *M); // lazily, when the wide4 option is on
 int build_nodes4c(gvt_hip_mesh *M); // the cluster layout of the 4-wide nodes (on demand: tracers with several instances / ranks)
+int refit_lbvh(gvt_hip_mesh *M); // every layout the mesh holds, refitted in place to its current d_verts (gvt_hip_mesh_update_vertices)
+int regen_normals(gvt_hip_mesh *M); // d_normals from d_verts, bit-identical to the host's generate_normals (api.hip)
+void refit_tables_free(gvt_hip_mesh *M);
 int sort_pairs_u32(unsigned *keys_in, unsigned *keys_out, unsigned *vals_in, unsigned *vals_out, size_t n, int end_bit);
 // trace.hip
 int queue_reserve(gvt_hip_queue *q, size_t cap);

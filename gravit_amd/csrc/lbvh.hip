@@ -423,6 +423,50 @@ __device__ inline float slot_area(const Slot4 &c) {
   const float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
   return dx * dy + dy * dz + dz * dx;
 }
+// The 64-byte compressed 4-wide node of slots c[0..n): child boxes quantised outwards to 8 bits on a per-node grid (verified in double against the
+// very expression the traversal decodes with), references in w[10..13].  ONE definition for the build (k_collapse4) and the refit (k_refit4):
+// identical boxes give identical words.
+__device__ __forceinline__ void quantise4(const Slot4 (&c)[4], int n, uint32_t (&w)[16]) {
+#pragma unroll
+  for (int k = 0; k < 16; k++) w[k] = 0u;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    float o = c[0].lo[a], h = c[0].hi[a];
+#pragma unroll
+    for (int s = 1; s < 4; s++) if (s < n) { o = fminf(o, c[s].lo[a]); h = fmaxf(h, c[s].hi[a]); }
+    int k2 = 0;
+    (void)frexpf((h - o) * (1.0f / 255.0f), &k2);
+    int e = k2 + 127;
+    e = e < 1 ? 1 : (e > 254 ? 254 : e);
+    uint32_t ql = 0, qh = 0;
+    for (;;) {
+      const float scale = __int_as_float(e << 23);
+      bool ok = true;
+      ql = 0; qh = 0;
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        if (s >= n || !ok) break;
+        int l = (int)floorf(ldexpf(c[s].lo[a] - o, 127 - e)); // (/ scale, a power of two: the same correctly rounded quotient in one instruction)
+        l = l < 0 ? 0 : (l > 255 ? 255 : l);
+        while (l > 0 && (double)o + (double)l * (double)scale > (double)c[s].lo[a]) l--;
+        int u = (int)ceilf(ldexpf(c[s].hi[a] - o, 127 - e));
+        u = u < 0 ? 0 : u;
+        while (u <= 255 && (double)o + (double)u * (double)scale < (double)c[s].hi[a]) u++;
+        if (u > 255) { ok = false; break; }
+        ql |= (uint32_t)l << (8 * s); qh |= (uint32_t)u << (8 * s);
+      }
+      if (ok || e >= 254) break;
+      e++;
+    }
+#pragma unroll
+    for (int s = 0; s < 4; s++) if (s >= n) ql |= 255u << (8 * s); // unused slots: an inverted box (lo plane 255, hi plane 0) that no ray enters
+    w[a] = __float_as_uint(o);
+    w[a == 0 ? 3 : 13 + a] = (uint32_t)e << 23; // the grid step 2^(e-127) as a float: w0.w (x), w3.z (y), w3.w (z)
+    w[4 + 2 * a] = ql; w[5 + 2 * a] = qh;
+  }
+#pragma unroll
+  for (int s = 0; s < 4; s++) w[10 + s] = (uint32_t)(s < n ? c[s].ref : GVT_EMPTY_REF);
+}
 // Level `level` of the collapse: its frontier size is levels[level], written by the launch before; the host launches several levels back to
 // back with grids sized by a bound (4^level, at most every node) and reads the sizes once per batch -- a level used to cost a counter
 // reset, a launch, a copy and a host synchronisation (14 levels at 10 M triangles).
@@ -490,47 +534,8 @@ __global__ __launch_bounds__(GVT_COLLAPSE_BLOCK, 4) void k_collapse4( // (4 wave
 #pragma unroll
   for (int s = 0; s < 4; s++)
     if (s < n && c[s].ref >= 0) { fout[slot] = c[s].ref; c[s].ref = (int)(base_in + n_in + slot); slot++; }
-  // quantise (outwards, verified in double against the very expression the traversal decodes with)
   uint32_t w[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) w[k] = 0u;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    float o = c[0].lo[a], h = c[0].hi[a];
-#pragma unroll
-    for (int s = 1; s < 4; s++) if (s < n) { o = fminf(o, c[s].lo[a]); h = fmaxf(h, c[s].hi[a]); }
-    int k2 = 0;
-    (void)frexpf((h - o) * (1.0f / 255.0f), &k2);
-    int e = k2 + 127;
-    e = e < 1 ? 1 : (e > 254 ? 254 : e);
-    uint32_t ql = 0, qh = 0;
-    for (;;) {
-      const float scale = __int_as_float(e << 23);
-      bool ok = true;
-      ql = 0; qh = 0;
-#pragma unroll
-      for (int s = 0; s < 4; s++) {
-        if (s >= n || !ok) break;
-        int l = (int)floorf(ldexpf(c[s].lo[a] - o, 127 - e)); // (/ scale, a power of two: the same correctly rounded quotient in one instruction)
-        l = l < 0 ? 0 : (l > 255 ? 255 : l);
-        while (l > 0 && (double)o + (double)l * (double)scale > (double)c[s].lo[a]) l--;
-        int u = (int)ceilf(ldexpf(c[s].hi[a] - o, 127 - e));
-        u = u < 0 ? 0 : u;
-        while (u <= 255 && (double)o + (double)u * (double)scale < (double)c[s].hi[a]) u++;
-        if (u > 255) { ok = false; break; }
-        ql |= (uint32_t)l << (8 * s); qh |= (uint32_t)u << (8 * s);
-      }
-      if (ok || e >= 254) break;
-      e++;
-    }
-#pragma unroll
-    for (int s = 0; s < 4; s++) if (s >= n) ql |= 255u << (8 * s); // unused slots: an inverted box (lo plane 255, hi plane 0) that no ray enters
-    w[a] = __float_as_uint(o);
-    w[a == 0 ? 3 : 13 + a] = (uint32_t)e << 23; // the grid step 2^(e-127) as a float: w0.w (x), w3.z (y), w3.w (z)
-    w[4 + 2 * a] = ql; w[5 + 2 * a] = qh;
-  }
-#pragma unroll
-  for (int s = 0; s < 4; s++) w[10 + s] = (uint32_t)(s < n ? c[s].ref : GVT_EMPTY_REF);
+  quantise4(c, n, w);
   uint4 *dst = nodes4 + (size_t)GVT_NODE4_F4 * (base_in + i);
   dst[0] = make_uint4(w[0], w[1], w[2], w[3]); dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
   dst[2] = make_uint4(w[8], w[9], w[10], w[11]); dst[3] = make_uint4(w[12], w[13], w[14], w[15]);
@@ -935,11 +940,19 @@ __global__ __launch_bounds__(256) void k_cluster_emit(const uint4 *__restrict__ 
 }
 } // namespace
 
+static std::mutex g_nodes4c_lock; // (tracers of several contexts -- threads -- may be created over one mesh at the same time)
+static int cluster_layout(gvt_hip_mesh *M, uint4 *dst);
 int build_nodes4c(gvt_hip_mesh *M) {
-  static std::mutex once; // (tracers of several contexts -- threads -- may be created over one mesh at the same time)
-  std::lock_guard<std::mutex> lock(once);
+  std::lock_guard<std::mutex> lock(g_nodes4c_lock);
   if (M->d_nodes4c || !M->d_nodes4 || !M->nNodes4 || M->levels4.empty()) return 0;
   if (M->levels4.size() > (size_t)GVT_COLLAPSE_LEVELS || M->nNodes4 >= ((size_t)1 << 26)) return 0; // (the wave-per-ray traversals walk nodes4 then)
+  int rc = dalloc(&M->d_nodes4c, (size_t)GVT_NODE4_F4 * M->nNodes4);
+  if (!rc) rc = cluster_layout(M, M->d_nodes4c);
+  if (rc) { hipFree(M->d_nodes4c); M->d_nodes4c = nullptr; if (!*gvt_hip_last_error()) set_error("cluster layout: device allocation failed"); }
+  return rc;
+}
+// nodes4 in cluster order into dst (the build's allocation, or the same array again after a refit: the topology, hence every position, is unchanged)
+static int cluster_layout(gvt_hip_mesh *M, uint4 *dst) {
   Ctx &C = gctx();
   hipStream_t st = C.stream;
   const unsigned n4 = (unsigned)M->nNodes4;
@@ -955,14 +968,13 @@ int build_nodes4c(gvt_hip_mesh *M) {
   size_t tb = 0;
   int rc = dalloc(&w, n4);
   if (!rc) rc = dalloc(&pos, n4);
-  if (!rc) rc = dalloc(&M->d_nodes4c, (size_t)GVT_NODE4_F4 * n4);
   if (!rc && rocprim::exclusive_scan(nullptr, tb, w, pos, 0u, (size_t)n4, rocprim::plus<unsigned>(), st) != hipSuccess) rc = GVT_HIP_ERR_DEVICE;
   if (!rc && hipMalloc(&tmp, tb ? tb : 16) != hipSuccess) rc = GVT_HIP_ERR_DEVICE;
   uint4 root[4];
   if (!rc) {
     k_cluster_weight<<<(n4 + 255) / 256, 256, 0, st>>>(M->d_nodes4, n4, T, w);
     hipError_t e = rocprim::exclusive_scan(tmp, tb, w, pos, 0u, (size_t)n4, rocprim::plus<unsigned>(), st);
-    if (e == hipSuccess) { k_cluster_emit<<<(n4 + 255) / 256, 256, 0, st>>>(M->d_nodes4, n4, T, pos, M->d_nodes4c); e = hipGetLastError(); }
+    if (e == hipSuccess) { k_cluster_emit<<<(n4 + 255) / 256, 256, 0, st>>>(M->d_nodes4, n4, T, pos, dst); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(root, M->d_nodes4, 64, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { set_error("cluster layout: %s", hipGetErrorString(e)); rc = GVT_HIP_ERR_DEVICE; }
@@ -974,7 +986,7 @@ int build_nodes4c(gvt_hip_mesh *M) {
     M->root_entry4c = (int)mask; // (the root's cluster starts at slot 0)
   }
   hipFree(w); hipFree(pos); hipFree(tmp);
-  if (rc) { hipFree(M->d_nodes4c); M->d_nodes4c = nullptr; if (!*gvt_hip_last_error()) set_error("cluster layout: device allocation failed"); }
+  if (rc && !*gvt_hip_last_error()) set_error("cluster layout: device allocation failed");
   return rc;
 }
 
@@ -1009,4 +1021,266 @@ int wide_root_marks(gvt_hip_mesh *M, int width, unsigned char *d_marks, size_t *
   hipFree(fa); hipFree(fb); hipFree(cnt);
   if (n_wide) *n_wide = total;
   return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// In-place refit (gvt_hip_mesh_update_vertices): new vertex positions, the same tree.  Every binary and every 4-wide node covers a contiguous range of
+// triangle slots (Karras' ranges survive the collapses), and the build computes every node box as the union of the slot-order triangle boxes over that
+// range (k_node_boxes*, the range-union table).  So once each node's range is known -- derived on the first update, 8 bytes per node -- every node refits
+// on its own from a fresh range-union table: no atomics, no level-by-level launches.  The queries do not depend on the tree, and min / max are exact:
+// unchanged vertices give the build's bytes back, and any vertices give the hits of a fresh build.
+namespace {
+__device__ inline uint2 child_range(int ref, const uint2 *__restrict__ rng) {
+  if (ref >= 0) return rng[ref];
+  const unsigned code = (unsigned)~ref;
+  return make_uint2(code >> 3, (code >> 3) + (code & 7u));
+}
+// slot range of every binary node: the first slot of its leftmost leaf, the end of its rightmost one (k_emit_nodes: child 0 precedes child 1)
+__global__ __launch_bounds__(256) void k_range2(const BvhNode *__restrict__ nodes, unsigned n, uint2 *__restrict__ rng) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int r = __float_as_int(nodes[i].n3.x);
+  while (r >= 0) r = __float_as_int(nodes[r].n3.x);
+  const unsigned first = (unsigned)~r >> 3;
+  r = __float_as_int(nodes[i].n3.y);
+  while (r >= 0) r = __float_as_int(nodes[r].n3.y);
+  const unsigned code = (unsigned)~r;
+  rng[i] = make_uint2(first, (code >> 3) + (code & 7u));
+}
+__device__ inline void refs4(const uint4 *__restrict__ nd, int r[4]) {
+  const uint4 w2 = nd[2], w3 = nd[3];
+  r[0] = (int)w2.z; r[1] = (int)w2.w; r[2] = (int)w3.x; r[3] = (int)w3.y;
+}
+// ... of every 4-wide node of one breadth-first level, from its children's (the level below done first).  A node's slots are NOT in range order -- k_collapse4
+// puts the right half of an expanded child at the end -- so the range is the min / max over all of them.
+__global__ __launch_bounds__(256) void k_range4(const uint4 *__restrict__ nodes4, unsigned begin, unsigned cnt, uint2 *__restrict__ rng) {
+  const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= cnt) return;
+  const unsigned i = begin + k;
+  int r[4];
+  refs4(nodes4 + (size_t)GVT_NODE4_F4 * i, r);
+  uint2 out = make_uint2(0xffffffffu, 0u);
+  for (int s = 0; s < 4; s++) {
+    if (r[s] == GVT_EMPTY_REF) continue;
+    const uint2 q = child_range(r[s], rng);
+    out.x = min(out.x, q.x); out.y = max(out.y, q.y);
+  }
+  rng[i] = out;
+}
+// the slots rewritten in place: the primID from the slot itself, the same float operations as k_emit_tris; the slot-order boxes on the way
+__global__ __launch_bounds__(256) void k_refit_tris(const float *__restrict__ verts, const int *__restrict__ tris, unsigned n, float4 *__restrict__ out,
+                                                    float4 *__restrict__ slo, float4 *__restrict__ shi) {
+  const unsigned s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const int p = __float_as_int(out[4 * s].w);
+  const int a = tris[3 * p], b = tris[3 * p + 1], c = tris[3 * p + 2];
+  const V3 v0 = ld3(verts + 3 * a), v1 = ld3(verts + 3 * b), v2 = ld3(verts + 3 * c);
+  slo[s] = make_float4(fminf(v0.x, fminf(v1.x, v2.x)), fminf(v0.y, fminf(v1.y, v2.y)), fminf(v0.z, fminf(v1.z, v2.z)), 0.f);
+  shi[s] = make_float4(fmaxf(v0.x, fmaxf(v1.x, v2.x)), fmaxf(v0.y, fmaxf(v1.y, v2.y)), fmaxf(v0.z, fmaxf(v1.z, v2.z)), 0.f);
+  const V3 e1 = sub3(v0, v1), e2 = sub3(v2, v0);
+  out[4 * s + 0] = make_float4(v0.x, v0.y, v0.z, __int_as_float(p));
+  out[4 * s + 1] = make_float4(e1.x, e1.y, e1.z, v1.x);
+  out[4 * s + 2] = make_float4(e2.x, e2.y, e2.z, v1.y);
+  out[4 * s + 3] = make_float4(v1.z, v2.x, v2.y, v2.z);
+}
+// binary nodes: both child boxes from the table, padded as k_emit_nodes pads them; the references stay
+__global__ __launch_bounds__(256) void k_refit2(BvhNode *__restrict__ nodes, unsigned n, const uint2 *__restrict__ rng, BoxLevels T,
+                                                const float *__restrict__ scene) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pad = scene[7];
+  BvhNode nd = nodes[i];
+  const uint2 ra = child_range(__float_as_int(nd.n3.x), rng), rb = child_range(__float_as_int(nd.n3.y), rng);
+  float4 al, ah, bl, bh;
+  node_box_from_table(ra.x, ra.y, T, al, ah);
+  node_box_from_table(rb.x, rb.y, T, bl, bh);
+  nd.n0 = make_float4(al.x - pad, ah.x + pad, al.y - pad, ah.y + pad);
+  nd.n1 = make_float4(bl.x - pad, bh.x + pad, bl.y - pad, bh.y + pad);
+  nd.n2 = make_float4(al.z - pad, ah.z + pad, bl.z - pad, bh.z + pad);
+  nodes[i] = nd;
+}
+// 4-wide nodes: the padded child boxes (the binary nodes' floats: the same table, the same pad) re-quantised by k_collapse4's quantiser
+__global__ __launch_bounds__(256) void k_refit4(uint4 *__restrict__ nodes4, unsigned n4, const uint2 *__restrict__ rng, BoxLevels T,
+                                                const float *__restrict__ scene) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float pad = scene[7];
+  uint4 *nd = nodes4 + (size_t)GVT_NODE4_F4 * i;
+  int r[4];
+  refs4(nd, r);
+  Slot4 c[4];
+  int n = 0;
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    c[s].ref = r[s];
+    for (int k = 0; k < 3; k++) { c[s].lo[k] = 0.f; c[s].hi[k] = 0.f; }
+    if (r[s] == GVT_EMPTY_REF) continue;
+    n = s + 1;
+    const uint2 q = child_range(r[s], rng);
+    float4 l, h;
+    node_box_from_table(q.x, q.y, T, l, h);
+    c[s].lo[0] = l.x - pad; c[s].lo[1] = l.y - pad; c[s].lo[2] = l.z - pad;
+    c[s].hi[0] = h.x + pad; c[s].hi[1] = h.y + pad; c[s].hi[2] = h.z + pad;
+  }
+  uint32_t w[16];
+  quantise4(c, n, w);
+  nd[0] = make_uint4(w[0], w[1], w[2], w[3]); nd[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  nd[2] = make_uint4(w[8], w[9], w[10], w[11]); nd[3] = make_uint4(w[12], w[13], w[14], w[15]);
+}
+
+// normal regeneration (Mesh::generateNormals, api.hip generate_normals): every vertex sums the unit normals of its faces in FACE order -- the corner
+// list, sorted by vertex with a stable radix sort, keeps it -- then normalises.  The same V3 operations, no contraction: bit-identical to the host loop.
+__global__ __launch_bounds__(256) void k_corner_keys(const int *__restrict__ tris, unsigned n3, unsigned *__restrict__ keys, unsigned *__restrict__ vals) {
+  const unsigned j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n3) return;
+  keys[j] = (unsigned)tris[j];
+  vals[j] = j;
+}
+// vstart[v] = first position of vertex v in the sorted corner list (vertices without faces: an empty range)
+__global__ __launch_bounds__(256) void k_vstart(const unsigned *__restrict__ skeys, unsigned n3, unsigned nV, unsigned *__restrict__ vstart) {
+  const unsigned j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n3) return;
+  const unsigned k = skeys[j];
+  const unsigned from = j ? skeys[j - 1] + 1u : 0u;
+  for (unsigned v = from; v <= k && (j == 0 || skeys[j - 1] != k); v++) vstart[v] = j;
+  if (j == n3 - 1) for (unsigned v = k + 1; v <= nV; v++) vstart[v] = n3;
+}
+__global__ __launch_bounds__(256) void k_vnormals(const float *__restrict__ verts, const int *__restrict__ tris, const unsigned *__restrict__ list,
+                                                  const unsigned *__restrict__ vstart, unsigned nV, float *__restrict__ normals) {
+  const unsigned v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nV) return;
+  float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
+  const unsigned e1 = vstart[v + 1];
+  for (unsigned e = vstart[v]; e < e1; e++) {
+    const unsigned f = list[e] / 3u;
+    const int I = tris[3 * f], J = tris[3 * f + 1], K = tris[3 * f + 2];
+    const V3 a = ld3(verts + 3 * I), b = ld3(verts + 3 * J), c = ld3(verts + 3 * K);
+    const V3 u = sub3(b, a), w = sub3(c, a);
+    V3 n;
+    n.x = u.y * w.z - u.z * w.y;
+    n.y = u.z * w.x - u.x * w.z;
+    n.z = u.x * w.y - u.y * w.x;
+    n = norm3(n);
+    d0 += n.x; d1 += n.y; d2 += n.z;
+  }
+  const V3 n = norm3(mk3(d0, d1, d2));
+  normals[3 * v] = n.x; normals[3 * v + 1] = n.y; normals[3 * v + 2] = n.z;
+}
+} // namespace
+
+void refit_tables_free(gvt_hip_mesh *M) {
+  hipFree(M->d_range2); hipFree(M->d_range4); hipFree(M->d_vlist); hipFree(M->d_vstart);
+  M->d_range2 = M->d_range4 = nullptr;
+  M->d_vlist = M->d_vstart = nullptr;
+}
+
+int regen_normals(gvt_hip_mesh *M) {
+  Ctx &C = gctx();
+  hipStream_t st = C.stream;
+  const unsigned nV = (unsigned)M->nV, n3 = (unsigned)(3 * M->nT);
+  if (!nV) return 0;
+  if (!M->d_vstart) { // once per mesh: the corner list
+    unsigned *keys = nullptr, *skeys = nullptr, *vals = nullptr;
+    int rc = dalloc(&M->d_vstart, (size_t)nV + 1);
+    if (!rc) rc = dalloc(&M->d_vlist, n3);
+    if (!rc) rc = dalloc(&keys, n3);
+    if (!rc) rc = dalloc(&skeys, n3);
+    if (!rc) rc = dalloc(&vals, n3);
+    int bits = 1;
+    while (bits < 32 && (nV - 1u) >> bits) bits++;
+    if (!rc) {
+      hipError_t e = hipMemsetAsync(M->d_vstart, 0, sizeof(unsigned) * ((size_t)nV + 1), st);
+      if (e != hipSuccess) { set_error("normals: %s", hipGetErrorString(e)); rc = GVT_HIP_ERR_DEVICE; }
+    }
+    if (!rc && n3) {
+      k_corner_keys<<<(n3 + 255) / 256, 256, 0, st>>>(M->d_tris, n3, keys, vals);
+      rc = sort_pairs_u32(keys, skeys, vals, M->d_vlist, n3, bits); // (LSD radix sort: stable, so a vertex's corners stay in face order)
+      if (!rc) k_vstart<<<(n3 + 255) / 256, 256, 0, st>>>(skeys, n3, nV, M->d_vstart);
+    }
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) { set_error("normals: corner list: %s", hipGetErrorString(hipGetLastError())); rc = GVT_HIP_ERR_DEVICE; }
+    hipFree(keys); hipFree(skeys); hipFree(vals);
+    if (rc) { hipFree(M->d_vlist); hipFree(M->d_vstart); M->d_vlist = nullptr; M->d_vstart = nullptr; return rc; }
+  }
+  k_vnormals<<<(nV + 255) / 256, 256, 0, st>>>(M->d_verts, M->d_tris, M->d_vlist, M->d_vstart, nV, M->d_normals);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int refit_lbvh(gvt_hip_mesh *M) {
+  Ctx &C = gctx();
+  hipStream_t st = C.stream;
+  const unsigned n = (unsigned)M->nT;
+  if (n == 0 || !M->d_nodes) return 0;
+  const unsigned B = 256, G = (n + B - 1) / B;
+  float4 *slo = nullptr, *shi = nullptr;
+  float *d_scene = nullptr;
+  unsigned long long *sah_acc = nullptr, sah_host = 0ull;
+  float *h_scene = (float *)(C.h_pinned + 32);
+  float pad = 0.f;
+  BuildArena A;
+  BoxLevels T;
+  int rc = 0;
+#define OK(x) do { if ((rc = (x)) != 0) goto done; } while (0)
+#define HOK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { set_error("refit: %s: %s", #x, hipGetErrorString(_e)); rc = GVT_HIP_ERR_DEVICE; goto done; } } while (0)
+  A.cap = 2 * sizeof(float4) * ((size_t)n + 1) + 4 * sizeof(float4) * ((size_t)n / 31 + 64 * GVT_BOX_LEVELS) + 16 * 256 + 4096;
+  A.base = (char *)scratch_get(21, A.cap);
+  if (!A.base) return GVT_HIP_ERR_DEVICE;
+  OK(A.take(&slo, n)); OK(A.take(&shi, n)); OK(A.take(&d_scene, 8)); OK(A.take(&sah_acc, 1));
+  k_refit_tris<<<G, B, 0, st>>>(M->d_verts, M->d_tris, n, M->d_tri, slo, shi);
+  OK(build_box_levels(slo, shi, n, A, T, st));
+  {
+    unsigned cnt = n;
+    for (int l = 1; l < T.n_levels; l++) cnt = (cnt + 31u) / 32u;
+    k_scene_box<<<1, 64, 0, st>>>(T.lo[T.n_levels - 1], T.hi[T.n_levels - 1], cnt, d_scene); // (min / max: the build's box, whatever the order)
+  }
+  HOK(hipMemcpyAsync(h_scene, d_scene, 8 * sizeof(float), hipMemcpyDeviceToHost, st));
+  if ((int)n <= M->leaf_max) { // one node (k_single_node, as built: its pad comes from the host)
+    HOK(hipStreamSynchronize(st));
+    pad = h_scene[7];
+    k_single_node<<<1, 64, 0, st>>>(slo, shi, n, pad, M->d_nodes);
+  } else {
+    const unsigned nn = (unsigned)M->nNodes;
+    if (!M->d_range2) { OK(dalloc(&M->d_range2, nn)); k_range2<<<(nn + B - 1) / B, B, 0, st>>>(M->d_nodes, nn, M->d_range2); }
+    k_refit2<<<(nn + B - 1) / B, B, 0, st>>>(M->d_nodes, nn, M->d_range2, T, d_scene);
+  }
+  if (M->d_nodes4 && M->nNodes4) {
+    const unsigned n4 = (unsigned)M->nNodes4;
+    if (!M->d_range4) { // once: level by level from the deepest (the breadth-first array: levels4)
+      OK(dalloc(&M->d_range4, n4));
+      unsigned end = n4;
+      for (size_t l = M->levels4.size(); l-- > 0;) {
+        const unsigned cnt = M->levels4[l], begin = end - cnt;
+        if (cnt) k_range4<<<(cnt + B - 1) / B, B, 0, st>>>(M->d_nodes4, begin, cnt, M->d_range4);
+        end = begin;
+      }
+      if (end != 0) { set_error("refit: the 4-wide level sizes do not add up to %u nodes", n4); rc = GVT_HIP_ERR_DEVICE; goto done; }
+    }
+    k_refit4<<<(n4 + B - 1) / B, B, 0, st>>>(M->d_nodes4, n4, M->d_range4, T, d_scene);
+  }
+  HOK(hipGetLastError());
+  if (M->d_nodes4c) { // the cluster layout again, into its own array (the same permutation: the topology is unchanged)
+    std::lock_guard<std::mutex> lock(g_nodes4c_lock);
+    OK(cluster_layout(M, M->d_nodes4c));
+  }
+  HOK(hipStreamSynchronize(st));
+  for (int k = 0; k < 3; k++) { M->lo[k] = h_scene[k]; M->hi[k] = h_scene[3 + k]; }
+  { // the packet statistic, as at build
+    const float ex = M->hi[0] - M->lo[0], ey = M->hi[1] - M->lo[1], ez = M->hi[2] - M->lo[2];
+    const float ra = ex * ey + ey * ez + ez * ex;
+    M->sah_inner = 0.f; M->packet_ok = false;
+    if (ra > 0.f && M->nNodes > 1) {
+      HOK(hipMemsetAsync(sah_acc, 0, sizeof(unsigned long long), st));
+      k_sah_sum<<<(unsigned)std::min<size_t>(2048, (M->nNodes + 255) / 256), 256, 0, st>>>(M->d_nodes, (unsigned)M->nNodes, 1.f / ra, sah_acc);
+      HOK(hipMemcpyAsync(&sah_host, sah_acc, sizeof sah_host, hipMemcpyDeviceToHost, st));
+      HOK(hipStreamSynchronize(st));
+      M->sah_inner = 1.f + (float)((double)sah_host / 65536.0);
+      M->packet_ok = M->sah_inner <= (float)C.packet_sah_max;
+    }
+  }
+done:
+  hipStreamSynchronize(st);
+  if (A.cap > ((size_t)1 << 30)) scratch_release(21);
+  return rc;
+#undef OK
+#undef HOK
 }

@@ -456,23 +456,42 @@ struct TopBuild {
 };
 } // namespace
 
-extern "C" gvt_hip_top *gvt_hip_top_create(const float *inst_lo, const float *inst_hi, size_t n) {
-  if (ensure_init()) return nullptr;
-  if (!inst_lo || !inst_hi) { set_error("top_create: null boxes"); return nullptr; }
-  gvt_hip_top *T = new gvt_hip_top();
-  T->n = n;
+// the order, the host copies and the device records of the boxes and of the top BVH (create, and update into the same arrays)
+namespace {
+struct TopRecords {
+  std::vector<float4> lo, hi, nlo, nhi;
+};
+void top_records(gvt_hip_top *T, const float *inst_lo, const float *inst_hi, size_t n, TopRecords &R) {
   TopBuild B{ inst_lo, inst_hi, {}, {}, {} };
   B.set.resize(n);
   for (size_t i = 0; i < n; i++) B.set[i] = (int)i;
   if (n) B.build(0, (int)n);
   T->order = B.sorted;
   T->h_lo.assign(inst_lo, inst_lo + 3 * n); T->h_hi.assign(inst_hi, inst_hi + 3 * n);
-  std::vector<float4> lo(n ? n : 1), hi(n ? n : 1);
+  R.lo.assign(n ? n : 1, float4{}); R.hi.assign(n ? n : 1, float4{});
   for (size_t k = 0; k < n; k++) {
     int q = T->order[k];
-    lo[k] = make_float4(inst_lo[3 * q], inst_lo[3 * q + 1], inst_lo[3 * q + 2], __builtin_bit_cast(float, q));
-    hi[k] = make_float4(inst_hi[3 * q], inst_hi[3 * q + 1], inst_hi[3 * q + 2], 0.f);
+    R.lo[k] = make_float4(inst_lo[3 * q], inst_lo[3 * q + 1], inst_lo[3 * q + 2], __builtin_bit_cast(float, q));
+    R.hi[k] = make_float4(inst_hi[3 * q], inst_hi[3 * q + 1], inst_hi[3 * q + 2], 0.f);
   }
+  const size_t nn = B.nodes.size();
+  R.nlo.resize(nn); R.nhi.resize(nn);
+  for (size_t k = 0; k < nn; k++) {
+    const TopNode &N = B.nodes[k];
+    R.nlo[k] = make_float4(N.lo[0], N.lo[1], N.lo[2], __builtin_bit_cast(float, N.left));
+    R.nhi[k] = make_float4(N.hi[0], N.hi[1], N.hi[2], __builtin_bit_cast(float, N.right));
+  }
+}
+} // namespace
+
+extern "C" gvt_hip_top *gvt_hip_top_create(const float *inst_lo, const float *inst_hi, size_t n) {
+  if (ensure_init()) return nullptr;
+  if (!inst_lo || !inst_hi) { set_error("top_create: null boxes"); return nullptr; }
+  gvt_hip_top *T = new gvt_hip_top();
+  T->n = n;
+  TopRecords R;
+  top_records(T, inst_lo, inst_hi, n, R);
+  const std::vector<float4> &lo = R.lo, &hi = R.hi;
   bool ok = hipMalloc((void **)&T->d_lo, sizeof(float4) * (n ? n : 1)) == hipSuccess &&
             hipMalloc((void **)&T->d_hi, sizeof(float4) * (n ? n : 1)) == hipSuccess &&
             hipMalloc((void **)&T->d_hist, sizeof(unsigned) * (n ? n : 1)) == hipSuccess &&
@@ -483,21 +502,39 @@ extern "C" gvt_hip_top *gvt_hip_top_create(const float *inst_lo, const float *in
     ok = hipMemcpy(T->d_lo, lo.data(), sizeof(float4) * n, hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(T->d_hi, hi.data(), sizeof(float4) * n, hipMemcpyHostToDevice) == hipSuccess;
   }
-  if (ok && !B.nodes.empty()) { // the tree itself, for larger sets (gvt_device.h top_nearest)
-    const size_t nn = B.nodes.size();
-    std::vector<float4> nlo(nn), nhi(nn);
-    for (size_t k = 0; k < nn; k++) {
-      const TopNode &N = B.nodes[k];
-      nlo[k] = make_float4(N.lo[0], N.lo[1], N.lo[2], __builtin_bit_cast(float, N.left));
-      nhi[k] = make_float4(N.hi[0], N.hi[1], N.hi[2], __builtin_bit_cast(float, N.right));
-    }
-    ok = hipMalloc((void **)&T->d_nlo, sizeof(float4) * nn) == hipSuccess && hipMalloc((void **)&T->d_nhi, sizeof(float4) * nn) == hipSuccess &&
-         hipMemcpy(T->d_nlo, nlo.data(), sizeof(float4) * nn, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(T->d_nhi, nhi.data(), sizeof(float4) * nn, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && !R.nlo.empty()) { // the tree itself, for larger sets (gvt_device.h top_nearest); room for the largest tree n boxes can give (updates)
+    const size_t nn = R.nlo.size(), room = std::max(nn, 2 * n - 1);
+    ok = hipMalloc((void **)&T->d_nlo, sizeof(float4) * room) == hipSuccess && hipMalloc((void **)&T->d_nhi, sizeof(float4) * room) == hipSuccess &&
+         hipMemcpy(T->d_nlo, R.nlo.data(), sizeof(float4) * nn, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(T->d_nhi, R.nhi.data(), sizeof(float4) * nn, hipMemcpyHostToDevice) == hipSuccess;
     T->n_nodes = nn;
   }
   if (!ok) { set_error("top_create: device allocation failed"); gvt_hip_top_destroy(T); return nullptr; }
   return T;
+}
+// Moving instances: the same set, new boxes.  Rebuilt on the host as at create (the reference's BVH), uploaded in place on the calling context's
+// stream: tracers that borrow the top read T->dev() per frame and keep working.
+extern "C" int gvt_hip_top_update(gvt_hip_top *T, const float *inst_lo, const float *inst_hi, size_t n) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!T || !inst_lo || !inst_hi) { set_error("top_update: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (n != T->n) { set_error("top_update: %zu boxes given, the top has %zu instances", n, T->n); return GVT_HIP_ERR_INVALID; }
+  if (!n) return 0;
+  hipStream_t st = gctx().stream;
+  TopRecords R;
+  gvt_hip_top tmp; // (the order and host copies move into T only once the upload is issued)
+  top_records(&tmp, inst_lo, inst_hi, n, R);
+  if (R.nlo.size() > std::max<size_t>(T->n_nodes, 2 * n - 1) || (!R.nlo.empty() && !T->d_nlo)) { set_error("top_update: the tree outgrew its arrays"); return GVT_HIP_ERR_DEVICE; }
+  HIPCHK(hipStreamSynchronize(st)); // (the host vectors below are copied from pageable memory)
+  HIPCHK(hipMemcpyAsync(T->d_lo, R.lo.data(), sizeof(float4) * n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(T->d_hi, R.hi.data(), sizeof(float4) * n, hipMemcpyHostToDevice, st));
+  if (!R.nlo.empty()) {
+    HIPCHK(hipMemcpyAsync(T->d_nlo, R.nlo.data(), sizeof(float4) * R.nlo.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(T->d_nhi, R.nhi.data(), sizeof(float4) * R.nhi.size(), hipMemcpyHostToDevice, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  T->order.swap(tmp.order); T->h_lo.swap(tmp.h_lo); T->h_hi.swap(tmp.h_hi);
+  T->n_nodes = R.nlo.size();
+  return 0;
 }
 extern "C" void gvt_hip_top_destroy(gvt_hip_top *T) {
   if (!T) return;

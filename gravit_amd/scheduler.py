@@ -278,6 +278,37 @@ class NativeTracer:
                              cam.samples, cam.depth, cam.jitter)
         capi.check(self.lib.gvt_hip_tracer_set_camera(self.h, C.byref(pod)), "gvt_hip_tracer_set_camera")
 
+    def set_transforms(self, m, minv, normi):
+        """gvt_hip_tracer_set_transforms: the next frame's instance matrices (rigid motion)."""
+        import ctypes as C
+
+        m, minv, normi = capi.f32(m, (-1, 16)), capi.f32(minv, (-1, 16)), capi.f32(normi, (-1, 9))
+        capi.check(self.lib.gvt_hip_tracer_set_transforms(self.h, capi.ptr(m), capi.ptr(minv), capi.ptr(normi), C.c_size_t(len(m))),
+                   "gvt_hip_tracer_set_transforms")
+
+    def update_scene(self, scene):
+        """The next frame of an animation: `scene` has this tracer's topology (instances, their meshes, the meshes' triangles) and new vertices,
+        instance boxes (scenes.instance_bbox), transforms or camera.  Changed meshes are refitted in place (normals as given, else regenerated),
+        the top-level set and the tracer's matrices replaced; the same tracer, queues and framebuffer render the next frame."""
+        old = self.scene
+        if scene.n_inst != old.n_inst or list(scene.inst_mesh) != list(old.inst_mesh) or len(scene.meshes) != len(old.meshes):
+            raise ValueError("update_scene: the instance set differs (create a new tracer)")
+        for a, b in zip(old.meshes, scene.meshes):
+            if a.tris.shape != b.tris.shape or len(a.verts) != len(b.verts) or not np.array_equal(a.tris, b.tris):
+                raise ValueError("update_scene: a mesh's topology differs (create a new mesh and tracer)")
+        B = self.backend
+        for mi, ad in B.adapter_cache.items():
+            mesh = scene.meshes[mi]
+            verts = capi.f32(mesh.verts, (-1, 3))
+            if np.array_equal(verts.view(np.uint32), ad.verts.view(np.uint32)) and mesh.vnormals is old.meshes[mi].vnormals:
+                continue
+            ad.update_vertices(verts, mesh.vnormals)
+        B.top.update(scene.inst_lo, scene.inst_hi)
+        self.set_transforms(scene.m, scene.minv, scene.normi)
+        self.set_camera(scene.camera)
+        self.scene = scene
+        B.scene = scene
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.gvt_hip_tracer_destroy(self.h)

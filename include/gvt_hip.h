@@ -135,6 +135,18 @@ int gvt_hip_mesh_get_info(const gvt_hip_mesh *, gvt_hip_mesh_info *);
 /* vertex normals in use (device -> host copy), nV*3 floats */
 int gvt_hip_mesh_get_normals(const gvt_hip_mesh *, float *out);
 
+/* ---- animated meshes: in-place refit ----
+ * New vertex positions for a mesh whose topology stays (triangles, materials and colours are kept).  nV must be the mesh's vertex count.
+ * Afterwards the mesh behaves exactly like gvt_hip_mesh_create on the new vertices -- the same hits, shading inputs and mesh_info box --
+ * but keeps its tree's topology and node counts: the node boxes are refitted, not rebuilt.  Every device pointer the mesh holds stays
+ * valid, so tracers and contexts that borrow it keep working; the caller serialises the update against frames that use the mesh.
+ * vnormals == NULL: regenerated (on the device, bit-identical to the host generation at create).  The call is ordered on the calling
+ * context's stream and returns when it is done.  ms_out (may be NULL): device time of the update after the upload.  Meshes built with the
+ * quad layouts (experiments build) are refused. */
+#define GVT_HIP_UPDATE_DEVICE 1u /* verts / vnormals are device pointers on the mesh's device (in situ: no host round trip) */
+int gvt_hip_mesh_update_vertices(gvt_hip_mesh *, const float *verts /* nV*3 */, size_t nV, const float *vnormals /* nV*3 or NULL */,
+                                 uint32_t flags, float *ms_out);
+
 /* ---- Adapter::trace (Adapter.h:82-84; EmbreeMeshAdapter.cpp:625-660) ----
  * rays[begin,end) are traced (end==0 -> n_rays, EmbreeMeshAdapter.cpp:642) and updated in place like the
  * reference's rayList (t, and origin/direction/w/depth/type on a bounce).  rays_out receives every
@@ -206,6 +218,9 @@ int gvt_hip_camera_generate_tiled(gvt_hip_queue *q, const float eye[3], const fl
 gvt_hip_top *gvt_hip_top_create(const float *inst_lo, const float *inst_hi, size_t n_inst);
 void gvt_hip_top_destroy(gvt_hip_top *);
 int gvt_hip_top_order(const gvt_hip_top *, int32_t *order_out /* n_inst */);
+/* New instance boxes (n_inst as at create): the order, the device boxes and the top BVH are rebuilt in place; tracers borrowing the top
+ * see them at their next frame. */
+int gvt_hip_top_update(gvt_hip_top *, const float *inst_lo, const float *inst_hi, size_t n_inst);
 /* shuffleRays(rays, from): consumes q_in (also when it fails: q_in is then cleared, its rays are lost); a ray whose next instance is i is advanced
  * (origin += dir * t * 0.95f) and appended to queues[i] -- unless keep_mask!=NULL and keep_mask[i]==0
  * (Tracer<DomainScheduler>::shuffleDropRays, DomainTracer.h:148-183); SHADOW rays that hit no further
@@ -276,6 +291,8 @@ gvt_hip_tracer *gvt_hip_tracer_create(gvt_hip_top *, gvt_hip_mesh *const *meshes
                                       int normal_mode, const gvt_hip_camera *cam, gvt_hip_fb *fb);
 void gvt_hip_tracer_destroy(gvt_hip_tracer *);
 int gvt_hip_tracer_set_camera(gvt_hip_tracer *, const gvt_hip_camera *cam);
+/* Rigid motion: the next frame's instance matrices (n_inst as at create), replacing the tracer's copies (stream-ordered). */
+int gvt_hip_tracer_set_transforms(gvt_hip_tracer *, const float *m /* n_inst*16 */, const float *minv, const float *normi /* n_inst*9 */, size_t n_inst);
 /* mpiInstanceMap (DomainTracer.h:115-144): owner[i] = rank holding instance i.  comm == NULL (or never called): one rank, Image scheduler. */
 int gvt_hip_tracer_set_domains(gvt_hip_tracer *, const int32_t *owner /* n_inst */, gvt_hip_comm *comm);
 #define GVT_HIP_FRAME_BSP 1          /* Domain: trace until the local queues are dry, then exchange (Tracer<DomainScheduler>); default:
