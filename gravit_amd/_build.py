@@ -1,5 +1,6 @@
-"""Build libgvt_hip.so (the C-ABI adapter library) and libgvt_hip_exp.so (the same sources with -DGVT_EXPERIMENTS: every
-variant that was measured and lost behind its knob, for the knob sweeps and probes) for gfx950 with hipcc, in-tree.
+"""Build libgvt_hip.so (the C-ABI adapter library) and libgvt_hip_exp.so (the same sources with -DGVT_EXPERIMENTS, which only
+lets gvt_hip_set_option move the tuned constants away from their measured-best values, for the knob sweeps and probes) for
+gfx950 with hipcc, in-tree.
 
 hipcc cross-compiles without a GPU; the built .so is git-ignored but travels with the tree to
 the GPU box.  -ffp-contract=off is part of the contract: the parity-critical arithmetic must not
@@ -18,15 +19,12 @@ LIB_EXP = os.path.join(HERE, "libgvt_hip_exp.so")
 SOURCES = ["api.hip", "lbvh.hip", "trace.hip", "sched.hip", "domain.hip"]
 
 
-def _headers(experiments):
-    """Every header / include a translation unit may pull in: csrc/*.h, csrc/*.inc, include/*.h (+ csrc/experiments/* for the
-    experiments build) -- the same set source_hash() hashes, so a stale object can never carry a fresh hash."""
+def _headers():
+    """Every header / include a translation unit may pull in: csrc/*.h, csrc/*.inc, include/*.h -- the same set source_hash()
+    hashes, so a stale object can never carry a fresh hash."""
     inc = os.path.join(os.path.dirname(HERE), "include")
     out = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".h", ".inc"))]
     out += [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f.endswith(".h")]
-    if experiments:
-        exp = os.path.join(CSRC, "experiments")
-        out += [os.path.join(exp, f) for f in sorted(os.listdir(exp)) if f.endswith((".h", ".inc"))]
     return out
 
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-Wall",
@@ -77,7 +75,7 @@ def build(force=False, verbose=False, experiments=False):
     if experiments:
         extra = extra + ["-DGVT_EXPERIMENTS"]
     cc = hipcc()
-    hdrs = _headers(experiments)
+    hdrs = _headers()
     objs = []
     procs = []
     for s in SOURCES:

@@ -232,8 +232,9 @@ extern "C" int gvt_hip_stats_reset(void) {
 
 // ---- tuning knobs: one table.  `shipped`: the knob is part of the product's surface -- a switch of behaviour (the reference's hop-by-hop
 // shuffle rule, the sink, the list order), a budget (memory, chunk sizes, round sizes) or a test hook.  The others have ONE measured-best
-// value (DESIGN.md / EXPERIMENTS.md); they can be moved only in the experiments build of the library (libgvt_hip_exp.so), where the knob
-// sweeps run; the shipped library answers GVT_HIP_ERR_INVALID when one of them is switched away from its default.
+// value (DESIGN.md / EXPERIMENTS.md): tuned constants, and a few alternative arms that both builds carry (wave_single = 0, lean_frame = 0 ...);
+// they can be moved only in the experiments build of the library (libgvt_hip_exp.so), where the knob sweeps run; the shipped library answers
+// GVT_HIP_ERR_INVALID when one of them is switched away from its default.  Variants that lost everywhere have no knob: their code is gone.
 namespace {
 struct KnobDef { const char *name; int Knobs::*field; int lo, hi; bool shipped; };
 const KnobDef g_knobs[] = {
@@ -255,15 +256,10 @@ const KnobDef g_knobs[] = {
   { "inline_kb", &Knobs::inline_kb, 0, 1024, true },          { "comm_cus", &Knobs::comm_cus, 0, 128, true },
   { "comm_stream", &Knobs::comm_stream, 0, 1, true },         { "spec_ticks", &Knobs::spec_ticks, 0, 1, true },
   { "finish_clusters", &Knobs::finish_clusters, 0, 1, true }, { "hop_local", &Knobs::hop_local, 0, 3, true },
-  // experiments build only: the alternative was measured and lost, or the value is a tuned constant
-  { "trav_kernel", &Knobs::trav_kernel, 0, 1, false },        { "wide4", &Knobs::wide4, 0, 1, false },
-  { "coop_fetch", &Knobs::coop_fetch, 0, 1, false },          { "fused", &Knobs::fused, 0, 1, false },
-  { "quad", &Knobs::quad, 0, 1, false },
-  { "quad_inner_min", &Knobs::quad_inner_min, 1, 16, false }, { "quad_refill_min", &Knobs::quad_refill_min, 1, 16, false },
-  { "blocks_per_cu_quad", &Knobs::blocks_per_cu_quad, 1, 8, false },
+  // experiments build only: a tuned constant, or an alternative arm that was measured and lost
   { "blocks_per_cu", &Knobs::blocks_per_cu, 1, 8, false },    { "blocks_per_cu_closest", &Knobs::blocks_per_cu_closest, 0, 8, false },
   { "refill_min", &Knobs::refill_min, 1, 64, false },         { "inner_min", &Knobs::inner_min, 1, 64, false },
-  { "share", &Knobs::share, 0, 3, false },                    { "share_min_rays", &Knobs::share_min_rays, 0, 1 << 30, false },
+  { "share", &Knobs::share, 0, 1, false },                    { "share_min_rays", &Knobs::share_min_rays, 0, 1 << 30, false },
   { "sort_gather", &Knobs::sort_gather, 0, 1, false },        { "sort_bits", &Knobs::sort_bits, 8, 32, false },
   { "long_steps_drain", &Knobs::long_steps_drain, 0, 1 << 20, false }, { "long_save", &Knobs::long_save, 0, 1, false },
   { "lean_frame", &Knobs::lean_frame, 0, 1, false },          { "report_poll", &Knobs::report_poll, 0, 1, false },
@@ -272,7 +268,6 @@ const KnobDef g_knobs[] = {
   { "top_lds", &Knobs::top_lds, 0, 1, false },                { "camera_tile", &Knobs::camera_tile, 0, 8, false },
   { "abi_pipe_min", &Knobs::abi_pipe_min, 0, 1 << 30, false },
   { "shadow_cls_lo", &Knobs::shadow_cls_lo, 0, 255, false },  { "shadow_cls_shift", &Knobs::shadow_cls_shift, 0, 6, false },
-  { "fused1", &Knobs::fused1, 0, 1, false },                  { "fused1_min_rays", &Knobs::fused1_min_rays, 0, 1 << 30, false },
 };
 } // namespace
 
@@ -370,7 +365,7 @@ extern "C" void gvt_hip_mesh_destroy(gvt_hip_mesh *M) {
   if (!M) return;
   if (g_ctx.ready) hipStreamSynchronize(g_ctx.stream);
   hipFree(M->d_verts); hipFree(M->d_tris); hipFree(M->d_normals); hipFree(M->d_vcolors); hipFree(M->d_materials);
-  hipFree(M->d_face_mat); hipFree(M->d_nodes); hipFree(M->d_tri); hipFree(M->d_slot_of); hipFree(M->d_nodes4); hipFree(M->d_nodes4c); hipFree(M->d_nodes4q); hipFree(M->d_triq);
+  hipFree(M->d_face_mat); hipFree(M->d_nodes); hipFree(M->d_tri); hipFree(M->d_slot_of); hipFree(M->d_nodes4); hipFree(M->d_nodes4c);
   refit_tables_free(M);
   delete M;
 }
@@ -383,7 +378,6 @@ extern "C" int gvt_hip_mesh_update_vertices(gvt_hip_mesh *M, const float *verts,
   if (flags & ~GVT_HIP_UPDATE_DEVICE) { set_error("mesh_update_vertices: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
   if (nV != M->nV) { set_error("mesh_update_vertices: %zu vertices given, the mesh has %zu (topology changes need a new mesh)", nV, M->nV); return GVT_HIP_ERR_INVALID; }
   if (nV && !verts) { set_error("mesh_update_vertices: null vertex array"); return GVT_HIP_ERR_INVALID; }
-  if (M->d_nodes4q || M->d_triq) { set_error("mesh_update_vertices: meshes built with the quad layouts (knob quad) cannot be refitted; create a new mesh"); return GVT_HIP_ERR_INVALID; }
   Ctx &C = g_ctx;
   hipStream_t st = C.stream;
   const hipMemcpyKind kind = (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;

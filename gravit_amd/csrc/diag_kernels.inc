@@ -1,10 +1,9 @@
-// diag_kernels.inc -- included by trace.hip inside its anonymous namespace.  NOT the hot path: the per-ray visit-count diagnostic
-// (gvt_hip_visit_stats) and, in the experiments build only (-DGVT_EXPERIMENTS), the first version of the traversal (one 64-ray batch
-// per wave over the binary LBVH, no refill): the `trav_kernel=0` baseline.
-template <bool ANY, bool COUNT = false>
-__device__ inline bool traverse(const Trav &T, V3 O, V3 D, float tnear, int *__restrict__ lds /* &stack[0][tid] */, int *__restrict__ spill,
-                                float &best_t, int &best_prim, float &best_u, float &best_v, unsigned *cnt = nullptr,
-                                const unsigned char *__restrict__ marks = nullptr /* COUNT: cnt[3] counts the visits of marked nodes */) {
+// diag_kernels.inc -- included by trace.hip inside its anonymous namespace.  NOT the hot path: the per-ray visit-count diagnostics
+// (gvt_hip_visit_stats, gvt_hip_wide_visit_stats), one 64-ray batch per wave over the binary LBVH.
+// closest-hit traversal of the binary nodes, counting: cnt[0] inner-node visits, cnt[1] leaf visits, cnt[2] triangle tests, cnt[3] visits of marked nodes
+__device__ inline void traverse_count(const Trav &T, V3 O, V3 D, float tnear, int *__restrict__ lds /* &stack[0][tid] */, int *__restrict__ spill,
+                                      float &best_t, int &best_prim, float &best_u, float &best_v, unsigned *cnt,
+                                      const unsigned char *__restrict__ marks = nullptr) {
   // reciprocal direction for the slab test only (never feeds a result)
   float dx = fabsf(D.x) < 1e-30f ? copysignf(1e-30f, D.x) : D.x;
   float dy = fabsf(D.y) < 1e-30f ? copysignf(1e-30f, D.y) : D.y;
@@ -15,7 +14,7 @@ __device__ inline bool traverse(const Trav &T, V3 O, V3 D, float tnear, int *__r
   int cur = 0;
   for (;;) {
     if (cur >= 0) {
-      if (COUNT) { cnt[0]++; if (marks && marks[cur]) cnt[3]++; }
+      cnt[0]++; if (marks && marks[cur]) cnt[3]++;
       const BvhNode *nd = T.nodes + cur;
       const float4 n0 = nd->n0, n1 = nd->n1, n2 = nd->n2, n3 = nd->n3;
       float a0 = __builtin_fmaf(n0.x, ix, -ox), a1 = __builtin_fmaf(n0.y, ix, -ox);
@@ -28,7 +27,7 @@ __device__ inline bool traverse(const Trav &T, V3 O, V3 D, float tnear, int *__r
       c0 = __builtin_fmaf(n2.z, iz, -oz); c1 = __builtin_fmaf(n2.w, iz, -oz);
       float tn1 = fmaxf(fmaxf(fminf(a0, a1), fminf(b0, b1)), fmaxf(fminf(c0, c1), 0.f));
       float tf1 = fminf(fminf(fmaxf(a0, a1), fmaxf(b0, b1)), fmaxf(c0, c1)) * 1.0000004f;
-      const float lim = ANY ? GVT_FLT_MAX : cull_bound(best_t);
+      const float lim = cull_bound(best_t);
       const bool h0 = (tn0 <= tf0) && (tn0 <= lim);
       const bool h1 = (tn1 <= tf1) && (tn1 <= lim);
       const int r0 = __float_as_int(n3.x), r1 = __float_as_int(n3.y);
@@ -50,12 +49,11 @@ __device__ inline bool traverse(const Trav &T, V3 O, V3 D, float tnear, int *__r
     } else {
       const unsigned code = (unsigned)~cur;
       const unsigned first = code >> 3, ntri = code & 7u;
-      if (COUNT) { cnt[1]++; cnt[2] += ntri; }
+      cnt[1]++; cnt[2] += ntri;
       for (unsigned k = 0; k < ntri; k++) {
         const float4 t0 = T.tris[4 * (first + k)], t1 = T.tris[4 * (first + k) + 1], t2 = T.tris[4 * (first + k) + 2];
         float t, u, v;
         if (tri_test(O, D, mk3(t0.x, t0.y, t0.z), mk3(t1.x, t1.y, t1.z), mk3(t2.x, t2.y, t2.z), tnear, t, u, v)) {
-          if (ANY) return true;
           const int prim = __float_as_int(t0.w);
           if (best_prim < 0 || t < best_t || (t == best_t && prim < best_prim)) { best_t = t; best_prim = prim; best_u = u; best_v = v; }
         }
@@ -65,7 +63,6 @@ __device__ inline bool traverse(const Trav &T, V3 O, V3 D, float tnear, int *__r
       cur = (sp < TRAV_STACK) ? lds[sp * TRAV_BLOCK] : spill[sp - TRAV_STACK];
     }
   }
-  return false;
 }
 
 // wave-level work fetch: 64 rays per grab; every wave leaves as soon as the counter passes n
@@ -74,33 +71,6 @@ __device__ inline unsigned fetch_batch(unsigned *counter) {
   if (lane_id() == 0) base = atomicAdd(counter, 64u);
   return (unsigned)__builtin_amdgcn_readfirstlane((int)base);
 }
-
-#ifdef GVT_EXPERIMENTS
-template <bool XFORM>
-__global__ __launch_bounds__(TRAV_BLOCK) void k_closest(RayPlanes q, const unsigned *__restrict__ idx, unsigned n, Mat4 minv, Trav T,
-                                                         float tnear, gvt_hip_hit *__restrict__ hits, unsigned *counter, int *spill_base) {
-  __shared__ int stack[TRAV_STACK * TRAV_BLOCK];
-  int *lds = &stack[threadIdx.x];
-  int *spill = spill_base + (size_t)(blockIdx.x * TRAV_BLOCK + threadIdx.x) * TRAV_SPILL;
-  for (;;) {
-    const unsigned base = fetch_batch(counter);
-    if (base >= n) break;
-    const unsigned j = base + lane_id();
-    if (j < n) {
-      const unsigned i = idx ? idx[j] : j;
-      const float4 a = q.p0[i], b = q.p1[i];
-      V3 O = mk3(a.x, a.y, a.z), D = mk3(b.x, b.y, b.z);
-      if (XFORM) { O = xfm_point(minv, O); D = xfm_vector(minv, D); }
-      float bt = GVT_FLT_MAX, bu = 0.f, bv = 0.f;
-      int bp = -1;
-      if (T.nodes) traverse<false>(T, O, D, tnear, lds, spill, bt, bp, bu, bv);
-      gvt_hip_hit h; h.t = bt; h.prim = bp; h.u = bu; h.v = bv;
-      hits[j] = h;
-    }
-  }
-}
-
-#endif // GVT_EXPERIMENTS
 
 // diagnostic: how many nodes would a W-wide collapse of the tree make this ray visit?  marks[k] = binary node k is the root of a
 // W-wide node (lbvh.hip wide_root_marks: the very collapse rule of build_nodes4, run for width W); a wide node is visited exactly
@@ -120,7 +90,7 @@ __global__ __launch_bounds__(TRAV_BLOCK) void k_wide_visit_stats(RayPlanes q, un
         const float4 a = q.p0[j], b = q.p1[j];
         float bt = GVT_FLT_MAX, bu, bv;
         int bp = -1;
-        traverse<false, true>(T, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), tnear, lds, spill, bt, bp, bu, bv, c, marks);
+        traverse_count(T, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), tnear, lds, spill, bt, bp, bu, bv, c, marks);
       }
       out[j] = c[3];
     }
@@ -144,40 +114,9 @@ __global__ __launch_bounds__(TRAV_BLOCK) void k_visit_stats(RayPlanes q, unsigne
         const float4 a = q.p0[j], b = q.p1[j];
         float bt = GVT_FLT_MAX, bu, bv;
         int bp = -1;
-        traverse<false, true>(T, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), tnear, lds, spill, bt, bp, bu, bv, c);
+        traverse_count(T, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), tnear, lds, spill, bt, bp, bu, bv, c);
       }
       out[3 * j] = c[0]; out[3 * j + 1] = c[1]; out[3 * j + 2] = c[2];
     }
   }
 }
-
-#ifdef GVT_EXPERIMENTS
-// MODE 0: flags[j] = occluded.  MODE 1: un-occluded rays of q are appended to `out` (moved_rays).
-template <bool XFORM, int MODE>
-__global__ __launch_bounds__(TRAV_BLOCK) void k_any(RayPlanes q, unsigned n, Mat4 minv, Trav T, float tnear, int *__restrict__ flags,
-                                                     RayPlanes out, unsigned *out_count, unsigned *counter, int *spill_base) {
-  __shared__ int stack[TRAV_STACK * TRAV_BLOCK];
-  int *lds = &stack[threadIdx.x];
-  int *spill = spill_base + (size_t)(blockIdx.x * TRAV_BLOCK + threadIdx.x) * TRAV_SPILL;
-  for (;;) {
-    const unsigned base = fetch_batch(counter);
-    if (base >= n) break;
-    const unsigned j = base + lane_id();
-    bool survive = false;
-    if (j < n) {
-      const float4 a = q.p0[j], b = q.p1[j];
-      V3 O = mk3(a.x, a.y, a.z), D = mk3(b.x, b.y, b.z);
-      if (XFORM) { O = xfm_point(minv, O); D = xfm_vector(minv, D); }
-      float bt = GVT_FLT_MAX, bu, bv;
-      int bp = -1;
-      const bool occ = T.nodes ? traverse<true>(T, O, D, tnear, lds, spill, bt, bp, bu, bv) : false;
-      if (MODE == 0) flags[j] = occ ? 1 : 0;
-      survive = !occ;
-    }
-    if (MODE == 1) {
-      const unsigned slot = wave_alloc(out_count, survive);
-      if (survive) { out.p0[slot] = q.p0[j]; out.p1[slot] = q.p1[j]; out.p2[slot] = q.p2[j]; out.p3[slot] = q.p3[j]; if (out.p4) out.p4[slot] = 0u; store_no_known(out, slot); }
-    }
-  }
-}
-#endif // GVT_EXPERIMENTS

@@ -835,7 +835,6 @@ struct gvt_hip_tracer {
   std::vector<uint8_t> owned;
   gvt_hip_comm *comm = nullptr; // borrowed
   int rank = 0, world = 1;
-  bool all_quad = true; // every local mesh carries the quad-per-ray layouts
   // device tables
   WaveInst *d_insts = nullptr;
   // per-round tables in ONE pinned block / ONE device block (a single host-to-device copy per round): segments, queue descriptors, mask
@@ -973,9 +972,8 @@ extern "C" gvt_hip_tracer *gvt_hip_tracer_create(gvt_hip_top *T, gvt_hip_mesh *c
     if (!M->d_nodes4 && M->nNodes) ok = build_nodes4(M) == 0; // the merged kernels traverse the 4-wide layout
     // the cluster layout for k_finish (small rounds: several instances or ranks); knob finish_clusters = 0: the plain 4-wide nodes
     if (ok && C.finish_clusters && C.finish_rays > 0 && n_inst > 1 && M->d_nodes4) ok = build_nodes4c(M) == 0; // (once per mesh, under its own lock)
-    I.nodes4 = M->d_nodes4; I.tris = M->d_tri; I.nodes4q = M->d_nodes4q; I.trisq = M->d_triq;
+    I.nodes4 = M->d_nodes4; I.tris = M->d_tri;
     I.nodes4c = C.finish_clusters ? M->d_nodes4c : nullptr; I.root_entry4c = M->root_entry4c;
-    if (M->nNodes && !(M->d_nodes4q && M->d_triq)) R->all_quad = false;
     I.mv.slots = M->d_tri; I.mv.slot_of = M->d_slot_of; I.mv.verts = M->d_verts; I.mv.tris = M->d_tris; I.mv.normals = M->d_normals; I.mv.vcolors = M->d_vcolors;
     I.mv.materials = M->d_materials; I.mv.n_mat = (unsigned)M->nMat; I.mv.face_mat = M->d_face_mat; I.mv.mat = M->mesh_mat;
   }
@@ -1155,7 +1153,7 @@ int local_chain(gvt_hip_tracer *R, const std::vector<size_t> *extra_in, uint64_t
   // gvt_hip_tracer_frame; knob hop_local; not with the known-miss shortcut, whose list is kept by the shuffle kernels)
   P.hop = R->hop_now == 1 ? 1 : R->hop_now == 2 ? 2 : 0;
   P.hop_owner = R->world > 1 ? R->d_owner : nullptr; P.hop_rank = R->rank;
-  WaveSet W{ R->d_segs, R->d_insts, n_seg, R->all_quad ? 1 : 0, (int)nI };
+  WaveSet W{ R->d_segs, R->d_insts, n_seg, (int)nI };
   if (C.finish_rays > 0 && N <= (size_t)C.finish_rays && P.sink.fb && !count_on_device && !exact) R->fin_eligible = true;
   if (R->fin_limit > 0 && N <= (size_t)R->fin_limit && P.sink.fb && !count_on_device && !exact) {
     // a small round: ONE launch follows every ray to its end on this rank (finish_kernel.inc); what remains are rays in other ranks' queues
@@ -1282,7 +1280,7 @@ int round_report(gvt_hip_tracer *R, bool exchange, uint64_t *syncs, bool chain_e
       P.normal_mode = R->normal_mode; P.seed = 0; P.n_lights = (int)R->lights.size(); P.update_in_place = 0; P.carried_rng = 1;
       P.sink = TermSink{};
       P.sink.top = R->top->dev(); P.sink.from = -1; P.sink.fb = R->fb->d_rgba; P.sink.n_pix = (unsigned)(R->fb->w * R->fb->h);
-      WaveSet W{ R->d_spec_segs, R->d_insts, n_own, R->all_quad ? 1 : 0, (int)nI };
+      WaveSet W{ R->d_spec_segs, R->d_insts, n_own, (int)nI };
       // (the launch's grid: persistent waves pull rays from a counter, any size is correct; sized for twice what this rank's rounds have held lately, so that
       //  ranks sharing one device -- in-process ranks -- do not each claim all of it for a few hundred rays)
       const size_t grid_rays = std::min<size_t>((size_t)C.finish_rays, std::max<size_t>(1024, 2 * R->spec_recent_rays));

@@ -265,44 +265,6 @@ __device__ inline unsigned block_alloc(unsigned *counter, bool want, unsigned *s
   return sh[1] + woff + lanes_below(mask);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Quad-cooperative fetch of 64-byte records (BVH nodes, triangle slots).
-// A wave whose 64 lanes each read their own 64-byte record with 4 x global_load_dwordx4 spends 4 x 64 L1 tag
-// look-ups on 64 cache lines; the vector L1 is then the busiest unit of the traversal kernel (TCP busy 82 %).
-// Here the 4 lanes of a quad fetch the quad's 4 records together -- instruction j reads record j, lane k its 16-byte
-// piece k, so a quad touches ONE line per instruction -- and transpose the pieces with DPP quad permutes (two
-// butterfly stages, VALU only).  Measured on MI355X (tools/gather_bench.hip, dependent node chase, L2-resident set):
-// 110 -> 202 G records/s.  Every lane of the wave must call it (EXEC all ones); `want` = this lane needs its record.
-// ---------------------------------------------------------------------------------------------
-template <int CTRL> __device__ inline int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
-template <int CTRL> __device__ inline float dpp_f(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)); }
-
-template <int XOR_CTRL> __device__ inline void quad_xchg(float &a, float &b, bool upper) {
-  const float send = upper ? a : b;      // the lower lane of the pair keeps a and gives b away, the upper one the reverse
-  const float recv = dpp_f<XOR_CTRL>(send);
-  a = upper ? recv : a;
-  b = upper ? b : recv;
-}
-template <int XOR_CTRL> __device__ inline void quad_xchg4(float4 &a, float4 &b, bool upper) {
-  quad_xchg<XOR_CTRL>(a.x, b.x, upper); quad_xchg<XOR_CTRL>(a.y, b.y, upper);
-  quad_xchg<XOR_CTRL>(a.z, b.z, upper); quad_xchg<XOR_CTRL>(a.w, b.w, upper);
-}
-
-__device__ inline void quad_fetch64(const float4 *__restrict__ base, unsigned rec, bool want, float4 &r0, float4 &r1, float4 &r2, float4 &r3) {
-  const unsigned k = lane_id() & 3u;
-  const int w = want ? 1 : 0;
-  float4 p0 = make_float4(0.f, 0.f, 0.f, 0.f), p1 = p0, p2 = p0, p3 = p0;
-  { const unsigned r = (unsigned)dpp_i<0x00>((int)rec); if (dpp_i<0x00>(w)) p0 = base[(size_t)r * 4 + k]; }
-  { const unsigned r = (unsigned)dpp_i<0x55>((int)rec); if (dpp_i<0x55>(w)) p1 = base[(size_t)r * 4 + k]; }
-  { const unsigned r = (unsigned)dpp_i<0xAA>((int)rec); if (dpp_i<0xAA>(w)) p2 = base[(size_t)r * 4 + k]; }
-  { const unsigned r = (unsigned)dpp_i<0xFF>((int)rec); if (dpp_i<0xFF>(w)) p3 = base[(size_t)r * 4 + k]; }
-  // lane k holds piece k of records 0..3; lane j needs pieces 0..3 of record j: a 4x4 transpose inside the quad
-  const bool odd = (k & 1u) != 0u, hi = (k & 2u) != 0u;
-  quad_xchg4<0xB1>(p0, p1, odd); quad_xchg4<0xB1>(p2, p3, odd); // quad_perm [1,0,3,2]
-  quad_xchg4<0x4E>(p0, p2, hi);  quad_xchg4<0x4E>(p1, p3, hi);  // quad_perm [2,3,0,1]
-  r0 = p0; r1 = p1; r2 = p2; r3 = p3;
-}
-
 // ---- top-level instance test (BVH::intersect + RayPacketIntersection), shared by the shuffle kernels and k_trace's sink ----
 // RayPacket.h fastmin/fastmax: (a<b)?a:b / (a>b)?a:b
 __device__ inline float fmin_ref(float a, float b) { return (a < b) ? a : b; }

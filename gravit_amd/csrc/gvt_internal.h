@@ -23,15 +23,11 @@ struct PendingEvent {
 #define SHADOW_CLASSES 8
 #define SHADOW_CLS_WORD 24
 struct Knobs {
-  int trav_kernel = 1;   // 1 = persistent waves with lane refill (k_trace), 0 = one 64-ray batch at a time (k_closest/k_any)
   int blocks_per_cu = 4; // k_trace grid: resident 256-thread blocks per CU
   int blocks_per_cu_closest = 5; // ... for closest-hit launches (0: blocks_per_cu); 5: 0.528 vs 0.554 ms per 1 M rays (4) and 0.552 (6); any-hit: 4 is best (5: 0.50 vs 0.40)
   int refill_min = 16;   // k_trace: idle lanes needed before a refill
   int inner_min = 32;    // k_trace: the inner-node loop is left once fewer lanes than this still descend
-  int coop_fetch = 0;    // k_trace: quad-cooperative 64-byte fetches (DPP transpose) instead of 4 loads per lane
-  int wide4 = 1;         // k_trace: traverse the compressed 4-wide collapse (64-B nodes, four 8-bit child boxes per fetch)
-  int share = 1;         // k_trace drain-phase work sharing, bit 0: any-hit launches (0.66 vs 0.80 ms per 1 M shadow rays), bit 1: closest-hit
-                         // launches (no gain: the pending subtrees of a closest-hit ray are mostly pruned by its eventual hit)
+  int share = 1;         // k_trace drain-phase work sharing in any-hit launches (0.66 vs 0.80 ms per 1 M shadow rays)
   int share_min_rays = 131072; // ... only in launches of at least this many rays (15 K shadow rays: the hand-off costs more than the tail it trims)
   int sort_rays = 0;     // Morton-sort the rays of a list before traversal (pays on incoherent lists; camera rays arrive in 8x8 tiles and the shuffle keeps list order)
   int sort_gather = 0;   // after sorting, traverse a contiguous object-space copy (o,d) of the rays
@@ -41,15 +37,9 @@ struct Knobs {
                          // Measured (10 M soup, 1 M rays): 72 shortens the closest launch 0.519 -> 0.504 ms but k_long_closest grows 0.044 -> 0.094
   int long_save = 1;     // parked rays carry their pending stack and go on from it (0: they start again at the root with their best hit as the bound)
   int long_min_rays = 65536; // ... only in launches of at least this many rays (small launches have no tail to speak of)
-  int fused = 0;         // scheduler rounds: closest hit + shade + first-light shadow rays in one kernel (k_fused) instead of three launches.
-                         // Measured 2.4x SLOWER than the three launches (EXPERIMENTS.md): shading inside the persistent kernel is latency-exposed
   int packet = 1;        // scheduler rounds: camera rays in tile order (and their direct-mapped shadow rays) traversed a packet of 64 per wave (k_packet): 0 never,
                          // 1 on meshes the builder found packet-friendly (gvt_hip_mesh::packet_ok), 2 always.  4-10 % faster on surfaces (bun_zipper, the hall),
                          // 2.5x-20x SLOWER on the random soups (EXPERIMENTS.md): hence the per-mesh choice
-  int fused1 = 0;        // experiments build: one-instance depth-1 frames with one point / ambient light and a Lambert mesh material run the whole adapter call in ONE
-                         // launch (k_frame1: closest hit -> lean shade -> the lane goes on with its shadow ray -> deposit).  Bit-exact, and SLOWER: 1.19-1.27 ms per
-                         // benchmark frame against 0.94 for the three launches (EXPERIMENTS.md round 5): closest-hit and any-hit work co-resident costs more than the tails
-  int fused1_min_rays = 65536; // ... in launches of at least this many rays
   int shadow_order = 1;  // single-mesh rounds with one light: the shadow rays are listed by the step count of their primaries' tiles, the longest first (shade.inc);
                          // 0: in arrival order.  The any-hit launch's drain is then left to short rays: 0.318 -> 0.281 ms in tools/order_probe.py
   int shadow_cls_lo = 24, shadow_cls_shift = 3; // ... class of a 64-ray tile = (node steps of its longest primary - lo) >> shift, clamped to 0..7 (tuned constants)
@@ -100,12 +90,7 @@ struct Knobs {
   int camera_tile = 8;   // gvt_hip_image_frame: camera rays listed in 8x8-pixel tiles (0: pixel-major like generateRays)
   int top_ordered = 1;   // shuffle: order-preserving, deterministic slots (<= 64 destinations) instead of arrival-order atomics
   int top_lds = 1;       // shuffle kernels: aggregate destination counters in LDS per 1024-thread block
-  int quad = 0;          // experiments build: four lanes per ray (k_traceq, experiments/quad_kernel.inc) instead of one (k_trace); meshes created while it
-                         // is set carry the quad layouts.  Measured 1.5x slower on the 10 M soup (VALU bound: 16 rays per wave), EXPERIMENTS.md
   int leaf_max = 2;      // triangles per leaf at mesh build (1..4): closest hit on the 10 M soup 0.51 ms (2) vs 0.57 ms (4)
-  int quad_inner_min = 8; // k_traceq: the node loop is left once fewer quads than this still descend
-  int quad_refill_min = 4; // k_traceq: idle quads needed before a refill
-  int blocks_per_cu_quad = 8; // k_traceq grid: resident 256-thread blocks per CU
 };
 
 struct Ctx : Knobs {
@@ -133,8 +118,6 @@ struct Ctx : Knobs {
   // light list of the last trace call (uploaded only when it changes)
   std::vector<unsigned char> lights_cached;
   const void *lights_cached_dst = nullptr;
-  std::vector<unsigned char> frame1_cached; // k_frame1's shading constants as last uploaded (trace.hip)
-  const void *frame1_cached_dst = nullptr;
   // staging queues of gvt_hip_trace (host RayVector in / out)
   gvt_hip_queue *abi_qin = nullptr, *abi_qout = nullptr;
   std::vector<Ctx *> abi_lanes; // contexts of the pipelined host path's lanes (api.hip trace_pipelined), created on first use
@@ -187,8 +170,6 @@ struct gvt_hip_mesh {
   uint4 *d_nodes4c = nullptr; // the same nodes in CLUSTER order for the wave-per-ray traversals (build_nodes4c, lbvh.hip): every even-level node followed by its
                               // inner children; references out of a cluster = (slot of the even node << 4) | mask of its inner children.  Built on demand
   int root_entry4c = 0;       // ... the root's reference in that form
-  uint4 *d_nodes4q = nullptr; // the same nodes laid out for the quad-per-ray traversal: piece s = child s (quad_kernel.inc)
-  float4 *d_triq = nullptr;   // leaf blocks, transposed (lbvh.hip k_emit_trisq)
   int leaf_max = 2;           // triangles per leaf this mesh was built with
   size_t nLeaves = 0;
   float lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
@@ -293,23 +274,22 @@ struct WaveInst { // per instance (Adapter::trace arguments m / minv / normi + t
   const uint4 *nodes4;
   const float4 *tris;
   const uint4 *nodes4c;  // cluster layout for the wave-per-ray traversals (null: not built; they walk nodes4 then)
-  const uint4 *nodes4q;  // quad layouts (null: the mesh was built without them)
-  const float4 *trisq;
   MeshView mv;
 };
 struct WaveSet {
   const WaveSeg *segs;
   const WaveInst *insts;
   int n_seg;
-  int quad_ok; // every instance that can be traced here carries the quad layouts (nodes4q / trisq)
-  int n_inst;  // rows of `insts` (0: unknown; the kernels then read the tables from global memory)
+  // rows of `insts` (0: unknown; the kernels then read the tables from global memory).  Kept at offset 24, not packed beside n_seg: with one
+  // 16-byte load for both words the merged any-hit k_trace spilled two more scalar registers and a frame of 8 domains took 0.4 % longer
+  alignas(8) int n_inst;
 };
 
 // lbvh.hip
 int build_lbvh(gvt_hip_mesh *M);
 int trav_overflow_fetch_async();
 int trav_overflow_result();
-int build_nodes4(gvt_hip_mesh *M); // lazily, when the wide4 option is on
+int build_nodes4(gvt_hip_mesh *M); // the 4-wide layout: build_lbvh makes it; the traversal launches build it on first use where a mesh has none
 int build_nodes4c(gvt_hip_mesh *M); // the cluster layout of the 4-wide nodes (on demand: tracers with several instances / ranks)
 int refit_lbvh(gvt_hip_mesh *M); // every layout the mesh holds, refitted in place to its current d_verts (gvt_hip_mesh_update_vertices)
 int regen_normals(gvt_hip_mesh *M); // d_normals from d_verts, bit-identical to the host's generate_normals (api.hip)

@@ -324,8 +324,7 @@ __global__ __launch_bounds__(256) void k_emit_nodes(int n_inner, const unsigned 
                                                     const float4 *__restrict__ slo, const float4 *__restrict__ shi,
                                                     const float4 *__restrict__ ilo, const float4 *__restrict__ ihi,
                                                     const int *__restrict__ child_l, const int *__restrict__ child_r, const int *__restrict__ rfirst,
-                                                    const int *__restrict__ rlast, const float *__restrict__ scene, BvhNode *__restrict__ nodes, int leaf_max,
-                                                    unsigned *__restrict__ leaf_of) {
+                                                    const int *__restrict__ rlast, const float *__restrict__ scene, BvhNode *__restrict__ nodes, int leaf_max) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_inner || !live[i]) return;
   const float pad = scene[7];
@@ -342,10 +341,6 @@ __global__ __launch_bounds__(256) void k_emit_nodes(int n_inner, const unsigned 
   nodes[newidx[i]] = nd;
   // (no leaf counter: the emitted nodes form a binary tree, so it has one leaf more than nodes -- counting them here took one atomic per
   // wave on a single word, half of this kernel's 1.8 ms at 10 M triangles)
-  if (!leaf_of) return;
-  // every sorted triangle learns its leaf (first slot, count): the transposed leaf blocks of k_emit_trisq are laid out per leaf
-  if (r0 < 0) { const unsigned code = (unsigned)~r0; for (unsigned k = 0; k < (code & 7u); k++) leaf_of[(code >> 3) + k] = code; }
-  if (r1 < 0) { const unsigned code = (unsigned)~r1; for (unsigned k = 0; k < (code & 7u); k++) leaf_of[(code >> 3) + k] = code; }
 }
 
 __global__ __launch_bounds__(256) void k_emit_tris(const float *__restrict__ verts, const int *__restrict__ tris, const unsigned *__restrict__ sorted,
@@ -369,27 +364,6 @@ __global__ __launch_bounds__(256) void k_emit_tris(const float *__restrict__ ver
   out[4 * s + 2] = make_float4(e2.x, e2.y, e2.z, v1.y);
   out[4 * s + 3] = make_float4(v1.z, v2.x, v2.y, v2.z);
   slot_of[p] = s;
-}
-
-// Leaf blocks for the quad-per-ray traversal (quad_kernel.inc): the n <= 4 triangles of a leaf occupy n x 64 B starting at slot
-// `first`, TRANSPOSED -- piece i (0: v0|prim, 1: e1, 2: e2, 3: Ng) of triangle k at float4 index 4*first + i*n + k -- so that the
-// lanes of a quad, lane k testing triangle k, read n consecutive 16-byte pieces (one or two cache lines) per load instruction
-// instead of n different lines.  Same float operations as k_emit_tris: bit-identical operands.
-__global__ __launch_bounds__(256) void k_emit_trisq(const float *__restrict__ verts, const int *__restrict__ tris, const unsigned *__restrict__ sorted,
-                                                    const unsigned *__restrict__ leaf_of, unsigned n, float4 *__restrict__ out) {
-  unsigned s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
-  const unsigned code = leaf_of[s], first = code >> 3, cnt = code & 7u, k = s - first;
-  unsigned p = sorted[s];
-  int a = tris[3 * p], b = tris[3 * p + 1], c = tris[3 * p + 2];
-  V3 v0 = ld3(verts + 3 * a), v1 = ld3(verts + 3 * b), v2 = ld3(verts + 3 * c);
-  V3 e1 = sub3(v0, v1), e2 = sub3(v2, v0);
-  V3 Ng = cross3(e1, e2);
-  float4 *blk = out + (size_t)4 * first;
-  blk[0 * cnt + k] = make_float4(v0.x, v0.y, v0.z, __int_as_float((int)p));
-  blk[1 * cnt + k] = make_float4(e1.x, e1.y, e1.z, 0.f);
-  blk[2 * cnt + k] = make_float4(e2.x, e2.y, e2.z, 0.f);
-  blk[3 * cnt + k] = make_float4(Ng.x, Ng.y, Ng.z, 0.f);
 }
 
 // n <= leaf_max: one node, child0 = the only leaf, child1 = empty leaf behind an inverted box
@@ -474,7 +448,7 @@ __device__ __forceinline__ void quantise4(const Slot4 (&c)[4], int n, uint32_t (
 #define GVT_COLLAPSE_LEVELS 96
 __global__ __launch_bounds__(GVT_COLLAPSE_BLOCK, 4) void k_collapse4( // (4 waves per SIMD = two 512-thread blocks per CU: 128 registers; unbounded the compiler took 132 and ONE block was resident)
     const BvhNode *__restrict__ nodes, const int *__restrict__ fin, unsigned *__restrict__ levels, int level,
-                                                                  int *__restrict__ fout, uint4 *__restrict__ nodes4, uint4 *__restrict__ nodes4q) {
+                                                                  int *__restrict__ fout, uint4 *__restrict__ nodes4) {
   const unsigned n_in = levels[level];
   if (blockIdx.x * blockDim.x >= n_in) return; // (block-uniform)
   unsigned base_in = 0;
@@ -539,18 +513,6 @@ __global__ __launch_bounds__(GVT_COLLAPSE_BLOCK, 4) void k_collapse4( // (4 wave
   uint4 *dst = nodes4 + (size_t)GVT_NODE4_F4 * (base_in + i);
   dst[0] = make_uint4(w[0], w[1], w[2], w[3]); dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
   dst[2] = make_uint4(w[8], w[9], w[10], w[11]); dst[3] = make_uint4(w[12], w[13], w[14], w[15]);
-  if (nodes4q) {
-    // the same node for the quad-per-ray traversal: piece s (16 B) is all lane s of a quad needs of child s --
-    //   x = ref_s, y = (lo.x, lo.y, lo.z, hi.x) bytes, z = (hi.y, hi.z) bytes | grid step of axis s as the upper half of its float
-    //   (a power of two: the lower 16 bits are zero), w = grid origin of axis s (s < 3)
-    const uint32_t step[3] = { w[3], w[14], w[15] };
-    uint4 *dq = nodes4q + (size_t)GVT_NODE4_F4 * (base_in + i);
-    for (int s = 0; s < 4; s++) {
-      const uint32_t lx = (w[4] >> (8 * s)) & 0xffu, hx = (w[5] >> (8 * s)) & 0xffu, ly = (w[6] >> (8 * s)) & 0xffu, hy = (w[7] >> (8 * s)) & 0xffu,
-                     lz = (w[8] >> (8 * s)) & 0xffu, hz = (w[9] >> (8 * s)) & 0xffu;
-      dq[s] = make_uint4(w[10 + s], lx | (ly << 8) | (lz << 16) | (hx << 24), hy | (hz << 8) | (s < 3 ? (step[s] & 0xffff0000u) : 0u), s < 3 ? w[s] : 0u);
-    }
-  }
 }
 
 // Marks the binary nodes that become roots of W-wide nodes under k_collapse4's rule (start from the two children, replace the inner
@@ -668,9 +630,8 @@ int build_lbvh(gvt_hip_mesh *M) {
 
   float4 *plo = nullptr, *phi = nullptr, *slo = nullptr, *shi = nullptr, *ilo = nullptr, *ihi = nullptr;
   unsigned long long *keys = nullptr, *keys2 = nullptr;
-  unsigned *vals = nullptr, *sorted = nullptr, *live = nullptr, *newidx = nullptr, *leaf_of = nullptr;
+  unsigned *vals = nullptr, *sorted = nullptr, *live = nullptr, *newidx = nullptr;
   const int leaf_max = C.leaf_max < 1 ? 1 : (C.leaf_max > 4 ? 4 : C.leaf_max);
-  const bool want_q = C.quad != 0; // the quad-per-ray layouts (nodes4q + transposed leaf blocks)
   M->leaf_max = leaf_max;
   int *cl = nullptr, *cr = nullptr, *rf = nullptr, *rl = nullptr;
   void *tmp = nullptr, *tmp2 = nullptr;
@@ -719,7 +680,6 @@ int build_lbvh(gvt_hip_mesh *M) {
   mark("scene box");
   OK(dalloc(&M->d_tri, (size_t)4 * n));
   OK(dalloc(&M->d_slot_of, n));
-  if (want_q) { OK(A.take(&leaf_of, n)); OK(dalloc(&M->d_triq, (size_t)4 * n)); }
 
   if ((int)n <= leaf_max) {
     OK(dalloc(&M->d_nodes, 1));
@@ -737,12 +697,6 @@ int build_lbvh(gvt_hip_mesh *M) {
     k_tri_bounds<<<G, B, 0, st>>>(M->d_verts, M->d_tris, n, tlo, thi);
     k_single_node<<<1, 64, 0, st>>>(tlo, thi, n, pad, M->d_nodes);
     k_emit_tris<<<G, B, 0, st>>>(M->d_verts, M->d_tris, sorted, n, M->d_tri, M->d_slot_of, nullptr, nullptr);
-    if (want_q) {
-      std::vector<unsigned> lo_(n, (unsigned)~leaf_ref(0u, n));
-      HOK(hipMemcpyAsync(leaf_of, lo_.data(), sizeof(unsigned) * n, hipMemcpyHostToDevice, st));
-      HOK(hipStreamSynchronize(st));
-      k_emit_trisq<<<G, B, 0, st>>>(M->d_verts, M->d_tris, sorted, leaf_of, n, M->d_triq);
-    }
   } else {
     OK(A.take(&keys, n)); OK(A.take(&keys2, n)); OK(A.take(&vals, n)); OK(A.take(&sorted, n));
     k_morton<<<G, B, 0, st>>>(M->d_verts, M->d_tris, n, d_scene, key_bits, keys, vals);
@@ -781,11 +735,10 @@ int build_lbvh(gvt_hip_mesh *M) {
     M->nNodes = (size_t)C.h_pinned[40] + C.h_pinned[41];
     OK(dalloc(&M->d_nodes, M->nNodes));
     M->nLeaves = M->nNodes + 1;
-    k_emit_nodes<<<(n_inner + B - 1) / B, B, 0, st>>>(n_inner, live, newidx, slo, shi, ilo, ihi, cl, cr, rf, rl, d_scene, M->d_nodes, leaf_max, leaf_of);
-    if (want_q) k_emit_trisq<<<G, B, 0, st>>>(M->d_verts, M->d_tris, sorted, leaf_of, n, M->d_triq);
+    k_emit_nodes<<<(n_inner + B - 1) / B, B, 0, st>>>(n_inner, live, newidx, slo, shi, ilo, ihi, cl, cr, rf, rl, d_scene, M->d_nodes, leaf_max);
     mark("emit nodes + slots");
   }
-  if (gctx().wide4 || want_q) OK(build_nodes4(M, &A)); // the traversal layout; counted in the build time
+  OK(build_nodes4(M, &A)); // the traversal layout; counted in the build time
   mark("4-wide collapse");
   { // packet-friendly?  (a surface: a few dozen inner nodes on a random line, whatever the triangle count; a soup: N^(1/3) of them)
     const float ex = M->hi[0] - M->lo[0], ey = M->hi[1] - M->lo[1], ez = M->hi[2] - M->lo[2];
@@ -827,7 +780,7 @@ int sort_pairs_u32(unsigned *keys_in, unsigned *keys_out, unsigned *vals_in, uns
   return 0;
 }
 
-// Compressed 4-wide collapse of the emitted binary tree (the traversal layout of k_trace's wide4 variant)
+// Compressed 4-wide collapse of the emitted binary tree (the traversal layout of k_trace and the wave-per-ray kernels)
 static int build_nodes4(gvt_hip_mesh *M, BuildArena *A) {
   if (M->d_nodes4 || !M->nNodes) return 0;
   // k_trace addresses a node by a 32-bit BYTE offset (index << 6, trace_lane.inc): 2^26 nodes is the layout's limit (a mesh of ~130 M triangles)
@@ -837,7 +790,6 @@ static int build_nodes4(gvt_hip_mesh *M, BuildArena *A) {
   int *fa = nullptr, *fb = nullptr;
   unsigned *cnt = nullptr;
   int rc = dalloc(&M->d_nodes4, (size_t)GVT_NODE4_F4 * M->nNodes);
-  if (!rc && M->d_triq) rc = dalloc(&M->d_nodes4q, (size_t)GVT_NODE4_F4 * M->nNodes);
   if (A) { // called from build_lbvh: the frontier arrays out of the build's arena
     if (!rc) rc = A->take(&fa, M->nNodes);
     if (!rc) rc = A->take(&fb, M->nNodes);
@@ -867,7 +819,7 @@ static int build_nodes4(gvt_hip_mesh *M, BuildArena *A) {
       for (; level < batch_end; level++) {
         // a level holds at most 4^level nodes (a node has at most four children) and at most every node
         const size_t bound = level >= 16 ? M->nNodes : std::min<size_t>(M->nNodes, (size_t)1 << (2 * level));
-        k_collapse4<<<(unsigned)((bound + GVT_COLLAPSE_BLOCK - 1) / GVT_COLLAPSE_BLOCK), GVT_COLLAPSE_BLOCK, 0, st>>>(M->d_nodes, fa, cnt, level, fb, M->d_nodes4, M->d_nodes4q);
+        k_collapse4<<<(unsigned)((bound + GVT_COLLAPSE_BLOCK - 1) / GVT_COLLAPSE_BLOCK), GVT_COLLAPSE_BLOCK, 0, st>>>(M->d_nodes, fa, cnt, level, fb, M->d_nodes4);
         int *t = fa; fa = fb; fb = t;
       }
       e = hipGetLastError();
@@ -887,7 +839,7 @@ static int build_nodes4(gvt_hip_mesh *M, BuildArena *A) {
     }
   }
   if (!A) { hipFree(fa); hipFree(fb); hipFree(cnt); }
-  if (rc) { hipFree(M->d_nodes4); M->d_nodes4 = nullptr; hipFree(M->d_nodes4q); M->d_nodes4q = nullptr; }
+  if (rc) { hipFree(M->d_nodes4); M->d_nodes4 = nullptr; }
   return rc;
 }
 int build_nodes4(gvt_hip_mesh *M) { return build_nodes4(M, nullptr); }

@@ -133,14 +133,6 @@ __device__ inline bool shade(const MatEval &m, const RayRec &ray, V3 N, const gv
   return true;
 }
 
-#ifdef GVT_EXPERIMENTS
-// out-of-line copies for k_fused: the shading code runs once per ray, the traversal loop thousands of times -- keeping it a call
-// keeps its registers out of the loop's allocation
-__device__ __attribute__((noinline)) bool shade_call(const MatEval &m, const RayRec &ray, V3 N, const gvt_hip_light &L, V3 lightPos, V3 &out) {
-  return shade(m, ray, N, L, lightPos, out);
-}
-#endif
-
 // CosWeightedRandomHemisphereDirection2 (EmbreeMeshAdapter.cpp:289-318)
 __device__ inline V3 cos_weighted_dir(V3 n, uint32_t &seed) {
   float Xi1 = gvt_fastrand01(seed);

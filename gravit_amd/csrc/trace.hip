@@ -18,9 +18,7 @@
 // k_trace in one paragraph: a wave pulls index ranges from a device counter (an exit every wave reaches), refills lanes whose ray has finished
 // while the others go on, alternates a tight loop over the compressed 4-wide nodes with a leaf phase, keeps its traversal stacks in LDS
 // (stack[level][lane]: lane-contiguous, bank conflict free) and compacts survivors per wave (__ballot + mbcnt, one atomic per >= 64 rays).
-// Compiled only with -DGVT_EXPERIMENTS (libgvt_hip_exp.so, the library the knob sweeps and probes run against): experiments/ -- the
-// first-version kernels (trav_kernel=0), the binary-node and quad-cooperative-fetch arms of k_trace (wide4=0, coop_fetch=1), k_fused,
-// k_packet, k_traceq (four lanes per ray).  EXPERIMENTS.md lists what was measured on the way.
+// EXPERIMENTS.md lists the variants that were measured on the way and lost; their code is in the history.
 #include "gvt_internal.h"
 
 #ifndef TRAV_BLOCK
@@ -50,13 +48,9 @@ struct Trav {
   const uint4 *__restrict__ nodes4;  // compressed 4-wide collapse (64 B per node) or null
 };
 
-#include "diag_kernels.inc" // visit counts (+ the first-version kernels in the experiments build)
+#include "diag_kernels.inc" // visit counts
 
 #include "trace_lane.inc" // the lane-per-ray traversal
-
-#ifdef GVT_EXPERIMENTS
-#include "experiments/quad_kernel.inc" // k_traceq: four lanes per ray (measured slower: VALU bound, EXPERIMENTS.md)
-#endif
 
 #include "trace_wave.inc" // the wave-per-ray traversal
 
@@ -65,14 +59,6 @@ struct Trav {
 #include "shade.inc" // Shade(), lights, the bounce direction, k_shade
 
 #include "finish_kernel.inc" // k_finish: a small round in one launch, every ray followed to its end on this rank
-
-#ifdef GVT_EXPERIMENTS
-#include "experiments/fused_lean.inc" // k_frame1: closest hit + Lambert / point-light shade + shadow ray + deposit of a one-instance depth-1 frame in ONE launch (measured slower, EXPERIMENTS.md; knob `fused1`)
-#endif
-
-#ifdef GVT_EXPERIMENTS
-#include "experiments/fused_kernel.inc" // k_fused: the one-kernel closest + shade + shadow variant (measured slower, EXPERIMENTS.md; knob `fused`)
-#endif
 
 #include "convert.inc" // layout conversions at the ABI boundary, ray sort keys, the small bookkeeping kernels of a trace call
 
@@ -84,19 +70,12 @@ int trav_grid(size_t n) {
   return (int)(need < (size_t)C.trav_blocks ? (need ? need : 1) : (size_t)C.trav_blocks);
 }
 
-template <bool ANY, bool XFORM, int MODE, typename... Args> void launch_trace(bool have_nodes4, int grid, hipStream_t st, RayPlanes q, const unsigned *idx, unsigned n, Mat4 minv, Args... args) {
+template <bool ANY, bool XFORM, int MODE, typename... Args> void launch_trace(int grid, hipStream_t st, RayPlanes q, const unsigned *idx, unsigned n, Mat4 minv, Args... args) {
   // k_trace never reads the matrix's bottom row (an instance matrix is affine); it carries the direction transform's `translation x 0` terms there instead
   // (xfm_vector: m[12..14] * 0.0f, kept for parity with glm's mat4 * vec4(d, 0)): kernel arguments live in SCALAR registers, where the products computed on
   // the device sat in three vector registers for the whole launch -- spilled to scratch in the shipped closest-hit kernel
   minv.m[3] = minv.m[12] * 0.0f; minv.m[7] = minv.m[13] * 0.0f; minv.m[11] = minv.m[14] * 0.0f;
-#ifdef GVT_EXPERIMENTS
-  if (!(gctx().wide4 && have_nodes4)) { // the uncompressed binary nodes
-    if (gctx().coop_fetch) k_trace<ANY, XFORM, MODE, true, false><<<grid, TRAV_BLOCK, 0, st>>>(q, idx, n, minv, args...);
-    else k_trace<ANY, XFORM, MODE, false, false><<<grid, TRAV_BLOCK, 0, st>>>(q, idx, n, minv, args...);
-    return;
-  }
-#endif
-  k_trace<ANY, XFORM, MODE, false, true><<<grid, TRAV_BLOCK, 0, st>>>(q, idx, n, minv, args...); // a mesh without 4-wide nodes has no triangles: every ray retires as a miss
+  k_trace<ANY, XFORM, MODE><<<grid, TRAV_BLOCK, 0, st>>>(q, idx, n, minv, args...); // a mesh without 4-wide nodes has no triangles: every ray retires as a miss
 }
 
 // scratch of a closest-hit launch's parked rays: n records, then LONG_SAVE stack entries for each of the first LONG_STK_CAP of them
@@ -118,19 +97,6 @@ int trav_grid2(size_t n, bool closest = false) {
   if (want > (size_t)C.trav_blocks) want = (size_t)C.trav_blocks;
   return (int)(need < want ? (need ? need : 1) : want);
 }
-
-#ifdef GVT_EXPERIMENTS
-// k_traceq: 64 rays in flight per 256-thread block
-int quad_grid(size_t n) {
-  Ctx &C = gctx();
-  size_t want = (size_t)C.n_cu * (size_t)C.blocks_per_cu_quad;
-  size_t need = (n + 63) / 64;
-  if (want > (size_t)C.trav_blocks) want = (size_t)C.trav_blocks;
-  return (int)(need < want ? (need ? need : 1) : want);
-}
-// (32-bit byte offsets into the node and leaf-block arrays: meshes beyond 2^26 triangles keep the one-lane-per-ray kernels)
-inline bool quad_usable(const gvt_hip_mesh *M) { return gctx().quad && gctx().trav_kernel == 1 && M->d_nodes4q && M->d_triq && M->nT < ((size_t)1 << 26) && M->nNodes4 < ((size_t)1 << 26); }
-#endif
 
 } // namespace
 
@@ -188,13 +154,12 @@ int launch_closest(gvt_hip_mesh *M, RayPlanes q, const unsigned *idx, size_t n, 
                    gvt_hip_hit *d_hits, bool counter_is_zero) {
   if (!n) return 0;
   Ctx &C = gctx();
-  if (gctx().wide4 && !M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
-  const bool have_nodes4 = M->d_nodes4 != nullptr;
+  if (!M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
   Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
   unsigned *counter = C.d_counters + 0;
   if (!counter_is_zero) HIPCHK(hipMemsetAsync(C.d_counters, 0, 5 * sizeof(unsigned), C.stream));
   LongQ LQ{};
-  if (C.trav_kernel == 1 && C.wide4 && have_nodes4 && C.long_steps > 0 && n >= (size_t)C.long_min_rays) { // long rays are parked and traversed a wave per ray
+  if (M->d_nodes4 && C.long_steps > 0 && n >= (size_t)C.long_min_rays) { // long rays are parked and traversed a wave per ray
     LQ.recs = (LongRec *)scratch_get(15, long_scratch_bytes(n));
     if (!LQ.recs) return GVT_HIP_ERR_DEVICE;
     LQ.count = C.d_counters + 3;
@@ -203,20 +168,8 @@ int launch_closest(gvt_hip_mesh *M, RayPlanes q, const unsigned *idx, size_t n, 
   {
     ProfScope ps(KC_CLOSEST);
     RayPlanes none{};
-#ifdef GVT_EXPERIMENTS
-    if (quad_usable(M)) {
-      TravQ TQ{ M->d_nodes4q, M->d_triq };
-      if (xform) k_traceq<false, true, 0><<<quad_grid(n), 256, 0, C.stream>>>(q, idx, (unsigned)n, minv, TQ, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.quad_refill_min, C.quad_inner_min, nullptr, TermSink{}, LQ);
-      else k_traceq<false, false, 0><<<quad_grid(n), 256, 0, C.stream>>>(q, idx, (unsigned)n, minv, TQ, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.quad_refill_min, C.quad_inner_min, nullptr, TermSink{}, LQ);
-    } else if (C.trav_kernel != 1) {
-      if (xform) k_closest<true><<<trav_grid(n), TRAV_BLOCK, 0, C.stream>>>(q, idx, (unsigned)n, minv, T, tnear, d_hits, counter, C.d_spill);
-      else k_closest<false><<<trav_grid(n), TRAV_BLOCK, 0, C.stream>>>(q, idx, (unsigned)n, minv, T, tnear, d_hits, counter, C.d_spill);
-    } else
-#endif
-    {
-      if (xform) launch_trace<false, true, 0>(have_nodes4, trav_grid2(n, true), C.stream, q, idx, (unsigned)n, minv, T, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
-      else launch_trace<false, false, 0>(have_nodes4, trav_grid2(n, true), C.stream, q, idx, (unsigned)n, minv, T, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
-    }
+    if (xform) launch_trace<false, true, 0>(trav_grid2(n, true), C.stream, q, idx, (unsigned)n, minv, T, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
+    else launch_trace<false, false, 0>(trav_grid2(n, true), C.stream, q, idx, (unsigned)n, minv, T, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
   }
   if (LQ.steps) {
     {
@@ -237,7 +190,7 @@ int launch_closest(gvt_hip_mesh *M, RayPlanes q, const unsigned *idx, size_t n, 
 int launch_visit_stats(gvt_hip_mesh *M, RayPlanes q, size_t n, float tnear, unsigned *d_out) {
   if (!n) return 0;
   Ctx &C = gctx();
-  if (gctx().wide4 && !M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
+  if (!M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
   Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
   unsigned *counter = C.d_counters + 0;
   HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), C.stream));
@@ -260,28 +213,15 @@ int launch_wide_visit_stats(gvt_hip_mesh *M, RayPlanes q, size_t n, float tnear,
 int launch_any_flags(gvt_hip_mesh *M, RayPlanes q, size_t n, bool xform, const Mat4 &minv, float tnear, int *d_flags) {
   if (!n) return 0;
   Ctx &C = gctx();
-  if (gctx().wide4 && !M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
-  const bool have_nodes4 = M->d_nodes4 != nullptr;
+  if (!M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
   Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
   unsigned *counter = C.d_counters + 0;
   HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), C.stream));
   RayPlanes none{};
   {
     ProfScope ps(KC_ANY);
-#ifdef GVT_EXPERIMENTS
-    if (quad_usable(M)) {
-      TravQ TQ{ M->d_nodes4q, M->d_triq };
-      if (xform) k_traceq<true, true, 0><<<quad_grid(n), 256, 0, C.stream>>>(q, nullptr, (unsigned)n, minv, TQ, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.quad_refill_min, C.quad_inner_min, nullptr, TermSink{}, LongQ{});
-      else k_traceq<true, false, 0><<<quad_grid(n), 256, 0, C.stream>>>(q, nullptr, (unsigned)n, minv, TQ, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.quad_refill_min, C.quad_inner_min, nullptr, TermSink{}, LongQ{});
-    } else if (C.trav_kernel != 1) {
-      if (xform) k_any<true, 0><<<trav_grid(n), TRAV_BLOCK, 0, C.stream>>>(q, (unsigned)n, minv, T, tnear, d_flags, none, nullptr, counter, C.d_spill);
-      else k_any<false, 0><<<trav_grid(n), TRAV_BLOCK, 0, C.stream>>>(q, (unsigned)n, minv, T, tnear, d_flags, none, nullptr, counter, C.d_spill);
-    } else
-#endif
-    {
-      if (xform) launch_trace<true, true, 0>(have_nodes4, trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{});
-      else launch_trace<true, false, 0>(have_nodes4, trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{});
-    }
+    if (xform) launch_trace<true, true, 0>(trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{});
+    else launch_trace<true, false, 0>(trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{});
   }
   HIPCHK(hipGetLastError());
   C.stats.rays_any += n;
@@ -333,11 +273,6 @@ int trace_core(gvt_hip_mesh *M, RayPlanes in, size_t n, uint64_t index_base, gvt
   const unsigned *idx = nullptr;
   unsigned *next = d_idx_a;
   int pass = 0;
-#ifdef GVT_EXPERIMENTS
-  const bool persistent = C.trav_kernel == 1;
-#else
-  const bool persistent = true;
-#endif
   while (n_active) { // while (validRayLeft) :465
     int rc;
     if (C.sort_rays && n_active >= 8192) { // ray sorting: traverse in Morton order of the object-space origin
@@ -373,7 +308,7 @@ int trace_core(gvt_hip_mesh *M, RayPlanes in, size_t n, uint64_t index_base, gvt
     A.in = in; A.idx = idx; A.n = (unsigned)n_active; A.index_base = index_base; A.hits = d_hits;
     A.first_pass = (pass == 0); A.carried_rng = P.carried_rng; A.out = outp; A.out_count = out->d_count; A.shadow = shadow; A.shadow_count = c_shadow;
     A.next_idx = next; A.next_count = c_next; A.lights = d_lights; A.normi = P.normi; A.normal_mode = P.normal_mode;
-    A.n_lights = nL; A.seed = P.seed; A.zero_word = persistent ? C.d_counters + 0 : nullptr;
+    A.n_lights = nL; A.seed = P.seed; A.zero_word = C.d_counters + 0;
     A.sink = P.sink; A.update_in_place = P.update_in_place;
     A.n_dev = nullptr; A.W = WaveSet{}; A.out_from = nullptr; A.shadow_inst = nullptr; A.shadow_stride = 0;
     {
@@ -382,58 +317,27 @@ int trace_core(gvt_hip_mesh *M, RayPlanes in, size_t n, uint64_t index_base, gvt
     }
     HIPCHK(hipGetLastError());
     C.stats.rays_shaded += n_active;
-    // traceShadowRays :364-385.  With the persistent kernel the shadow-ray count stays on the device (the kernel reads
-    // it, the grid does not depend on it); the host learns the counts of the pass in ONE read-back afterwards.
-    unsigned n_shadow = 0, n_next = 0;
+    // traceShadowRays :364-385.  The shadow-ray count stays on the device (the persistent kernel reads it, the grid does not depend on it);
+    // the host learns the counts of the pass in ONE read-back afterwards.
     const size_t shadow_ub = n_active * (size_t)nL;
-    if (persistent) {
-      if (shadow_ub) {
-        Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-        unsigned *counter = C.d_counters + 0; // zeroed by k_shade
-        {
-          ProfScope ps(KC_ANY);
-#ifdef GVT_EXPERIMENTS
-          if (quad_usable(M))
-            k_traceq<true, true, 1><<<quad_grid(shadow_ub), 256, 0, st>>>(shadow, nullptr, 0u, P.minv, TravQ{ M->d_nodes4q, M->d_triq }, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count, counter,
-                                                                          C.d_spill, C.quad_refill_min, C.quad_inner_min, c_shadow, P.sink, LongQ{});
-          else
-#endif
-          launch_trace<true, true, 1>(M->d_nodes4 != nullptr, trav_grid2(shadow_ub), st, shadow, nullptr, 0u, P.minv, T, GVT_RAY_EPSILON, nullptr, nullptr, outp,
-                                                                               out->d_count, counter, C.d_spill, C.refill_min, C.inner_min, c_shadow, C.share, (unsigned)C.share_min_rays, P.sink, LongQ{});
-        }
-        HIPCHK(hipGetLastError());
-        C.stats.launches_any++;
+    if (shadow_ub) {
+      Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
+      unsigned *counter = C.d_counters + 0; // zeroed by k_shade
+      {
+        ProfScope ps(KC_ANY);
+        launch_trace<true, true, 1>(trav_grid2(shadow_ub), st, shadow, nullptr, 0u, P.minv, T, GVT_RAY_EPSILON, nullptr, nullptr, outp,
+                                    out->d_count, counter, C.d_spill, C.refill_min, C.inner_min, c_shadow, C.share, (unsigned)C.share_min_rays, P.sink, LongQ{});
       }
-      HIPCHK(hipMemcpyAsync(C.h_pinned, c_shadow, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(C.h_pinned + 2, out->d_count, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      if ((rc = trav_overflow_fetch_async())) return rc;
-      HIPCHK(hipStreamSynchronize(st));
-      if ((rc = trav_overflow_result())) return rc;
-      n_shadow = C.h_pinned[0]; n_next = C.h_pinned[1];
-      C.stats.rays_any += n_shadow;
+      HIPCHK(hipGetLastError());
+      C.stats.launches_any++;
     }
-#ifdef GVT_EXPERIMENTS
-    else { // trav_kernel=0: the first-version kernels size their grid from the host-known count
-      HIPCHK(hipMemcpyAsync(C.h_pinned, c_shadow, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      n_shadow = C.h_pinned[0]; n_next = C.h_pinned[1];
-      if (n_shadow) {
-        Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-        unsigned *counter = C.d_counters + 0;
-        HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), st));
-        {
-          ProfScope ps(KC_ANY);
-          k_any<true, 1><<<trav_grid(n_shadow), TRAV_BLOCK, 0, st>>>(shadow, n_shadow, P.minv, T, GVT_RAY_EPSILON, nullptr, outp, out->d_count, counter,
-                                                                      C.d_spill);
-        }
-        HIPCHK(hipGetLastError());
-        C.stats.rays_any += n_shadow;
-        C.stats.launches_any++;
-      }
-      HIPCHK(hipMemcpyAsync(C.h_pinned + 2, out->d_count, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-#endif
+    HIPCHK(hipMemcpyAsync(C.h_pinned, c_shadow, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(C.h_pinned + 2, out->d_count, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if ((rc = trav_overflow_fetch_async())) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = trav_overflow_result())) return rc;
+    const unsigned n_shadow = C.h_pinned[0], n_next = C.h_pinned[1];
+    C.stats.rays_any += n_shadow;
     n_active = n_next;
     idx = next;
     next = (next == d_idx_a) ? d_idx_b : d_idx_a;
@@ -514,11 +418,7 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
   // SHADOW_CLASSES regions of `cls_stride` slots; not for packets (no per-ray step counts) nor small rounds (a wave per ray)
   const bool by_class_wanted = single && single->mesh->d_nodes4 && C.shadow_order && nL == 1 && n >= (size_t)C.shadow_order_min_rays && n > (size_t)C.small_rays &&
                         C.long_steps > 0 && n >= (size_t)C.long_min_rays &&
-                        !((C.packet == 2 || (C.packet == 1 && single->mesh->packet_ok && n >= (size_t)C.packet_min_rays)) && single->coherent)
-#ifdef GVT_EXPERIMENTS
-                        && !quad_usable(single->mesh) // (k_traceq walks the shadow list as one contiguous run counted by c[1])
-#endif
-      ;
+                        !((C.packet == 2 || (C.packet == 1 && single->mesh->packet_ok && n >= (size_t)C.packet_min_rays)) && single->coherent);
   const size_t cls_stride = (n + 63) & ~(size_t)63;
   // (every region has room for the whole list -- 8 x 64 bytes per ray: 0.5 GB at the benchmark's 1.04 M rays; beyond 8 GiB the list stays in arrival order)
   // The ordering is an optimisation whose results do not depend on it: it must never make a frame fail that fits without it.  A device that cannot
@@ -620,34 +520,6 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
       // ... the CLOSEST hit, that is.  Shadow rays as packets lost on both surfaces they were measured on (bun_zipper any hit 0.162 -> 0.189 ms, the hall
       // 1.23 -> 1.33: an any-hit packet goes on until its LAST ray is occluded or through): under the per-mesh choice they stay a lane per ray; 2 forces both
       const bool pkt_any = pkt && C.packet == 2;
-#ifdef GVT_EXPERIMENTS
-      // the whole adapter call in ONE launch (experiments/fused_lean.inc; measured 1.19-1.27 ms per benchmark frame against 0.94 for the three launches) where the frame is the simple case: one instance in the scene, camera rays, depth 1, one
-      // point / ambient light, a Lambert mesh material, the terminal sink on
-      const bool lean1 = C.fused1 && !pkt && single->coherent && pass == 0 && passes == 1 && have4 && !small1 && nL == 1 && lights_host[0].type != GVT_HIP_LIGHT_AREA &&
-                         P.sink.fb && P.sink.top.n_inst == 1 && !M->d_vcolors && !M->d_face_mat && M->mesh_mat.type == 0 && n >= (size_t)C.fused1_min_rays;
-      if (lean1) {
-        ProfScope ps(KC_CLOSEST);
-        Frame1Shade K;
-        std::memset(&K, 0, sizeof K);
-        K.normi = single->normi; K.kd[0] = M->mesh_mat.kd[0]; K.kd[1] = M->mesh_mat.kd[1]; K.kd[2] = M->mesh_mat.kd[2]; K.normal_mode = P.normal_mode;
-        K.slot_of = M->d_slot_of; K.tri_idx = M->d_tris; K.normals = M->d_normals; K.p3 = single->planes.p3; K.light = lights_host[0]; K.fb = P.sink.fb; K.n_pix = P.sink.n_pix;
-        Frame1Shade *d_K = (Frame1Shade *)scratch_get(22, sizeof K);
-        if (!d_K) return GVT_HIP_ERR_DEVICE;
-        if (C.frame1_cached_dst != d_K || C.frame1_cached.size() != sizeof K || std::memcmp(C.frame1_cached.data(), &K, sizeof K) != 0) { // (uploaded when it changes: steady-state frames skip it)
-          C.frame1_cached.assign((const unsigned char *)&K, (const unsigned char *)&K + sizeof K);
-          C.frame1_cached_dst = d_K;
-          HIPCHK(hipMemcpyAsync(d_K, C.frame1_cached.data(), sizeof K, hipMemcpyHostToDevice, st));
-          HIPCHK(hipStreamSynchronize(st)); // pageable source
-        }
-        Frame1Args F;
-        F.p0 = single->planes.p0; F.p1 = single->planes.p1; F.n = (unsigned)n; F.n_dev = n_dev; F.minv = single->minv; F.nodes4 = M->d_nodes4; F.tris = M->d_tri;
-        F.tnear = GVT_RAY_EPSILON; F.counter = c + 0; F.spill_base = C.d_spill; F.refill_min = C.refill_min; F.inner_min = C.inner_min; F.shade = d_K;
-        k_frame1<<<trav_grid2(n, true), TRAV_BLOCK, 0, st>>>(F);
-        HIPCHK(hipGetLastError());
-        C.stats.launches_closest++;
-        continue;
-      }
-#endif
       if (pkt) {
         ProfScope ps(KC_CLOSEST);
         LongQ LP{ d_long, c + 3, nullptr, 0u, 0, 0 };
@@ -659,17 +531,9 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
         ProfScope ps(KC_CLOSEST);
         k_long_seed<<<blocks_for(n), 256, 0, st>>>(d_long, c + 3, idx, (unsigned)n, n_dev);
         k_long_closest<true><<<small_grid, 256, 0, st>>>(single->planes, d_long, c + 3, single->minv, TS, GVT_RAY_EPSILON, d_hits, c + 4);
-      }
-#ifdef GVT_EXPERIMENTS
-      else if (quad_usable(M)) {
+      } else {
         ProfScope ps(KC_CLOSEST);
-        k_traceq<false, true, 0><<<quad_grid(n), 256, 0, st>>>(single->planes, idx, (unsigned)n, single->minv, TravQ{ M->d_nodes4q, M->d_triq }, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
-                                                             c + 0, C.d_spill, C.quad_refill_min, C.quad_inner_min, n_dev, TermSink{}, LQ);
-      }
-#endif
-      else {
-        ProfScope ps(KC_CLOSEST);
-        launch_trace<false, true, 0>(have4, trav_grid2(n, true), st, single->planes, idx, (unsigned)n, single->minv, TS, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
+        launch_trace<false, true, 0>(trav_grid2(n, true), st, single->planes, idx, (unsigned)n, single->minv, TS, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
                                      c + 0, C.d_spill, C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
       }
       if (LQ.steps && !small1 && !pkt) {
@@ -706,20 +570,13 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
           k_packet<true><<<blocks_for(shadow_cap), 256, 0, st>>>(shadow, (unsigned)shadow_cap, nullptr, single->minv, TS, GVT_RAY_EPSILON, nullptr, d_shadow_inst, outp, out->d_count,
                                                                sk, LongQ{}, d_retry, c + 6, (unsigned long long *)(c + 18), c + 9);
           // rays of packets that bailed out: one lane per ray (an empty list costs a few microseconds)
-          launch_trace<true, true, 1>(have4, trav_grid2(4096), st, shadow, d_retry, 0u, single->minv, TS, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
+          launch_trace<true, true, 1>(trav_grid2(4096), st, shadow, d_retry, 0u, single->minv, TS, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
                                       c + 0, C.d_spill, C.refill_min, C.inner_min, c + 6, C.share, (unsigned)C.share_min_rays, sk, LongQ{});
-        } else
-#ifdef GVT_EXPERIMENTS
-        if (quad_usable(M) && !small1)
-          k_traceq<true, true, 1><<<quad_grid(shadow_cap), 256, 0, st>>>(shadow, nullptr, 0u, single->minv, TravQ{ M->d_nodes4q, M->d_triq }, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                                                       c + 0, C.d_spill, C.quad_refill_min, C.quad_inner_min, c + 1, sk, LongQ{});
-        else
-#endif
-        if (small1) k_wave_any<false><<<(int)std::min<size_t>((shadow_cap + 3) / 4, (size_t)C.n_cu * 3), 256, 0, st>>>(shadow, c + 1, single->minv, TS, GVT_RAY_EPSILON, outp, out->d_count, c + 0, sk, MultiSrc{});
+        } else if (small1) k_wave_any<false><<<(int)std::min<size_t>((shadow_cap + 3) / 4, (size_t)C.n_cu * 3), 256, 0, st>>>(shadow, c + 1, single->minv, TS, GVT_RAY_EPSILON, outp, out->d_count, c + 0, sk, MultiSrc{});
         else {
           MultiSrc by{};
           if (by_class) { by.cls_cnt = c + SHADOW_CLS_WORD; by.cls_stride = (unsigned)cls_stride; by.cls_total = c + 1; }
-          launch_trace<true, true, 1>(have4, trav_grid2(shadow_cap), st, shadow, nullptr, 0u, single->minv, TS, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
+          launch_trace<true, true, 1>(trav_grid2(shadow_cap), st, shadow, nullptr, 0u, single->minv, TS, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
                                       c + 0, C.d_spill, C.refill_min, C.inner_min, by_class ? nullptr : c + 1, C.share, (unsigned)C.share_min_rays, sk, LongQ{}, by);
         }
       }
@@ -728,33 +585,6 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
       C.stats.launches_any++;
       continue;
     }
-#ifdef GVT_EXPERIMENTS
-    if (C.fused && P.sink.fb) {
-      // one launch: closest hit, shade, the first light's shadow rays, terminal rule (k_fused); lights 1.. through the list
-      FusedArgs F;
-      F.W = W; F.idx = idx; F.n = (unsigned)n; F.n_dev = n_dev; F.lights = d_lights; F.n_lights = nL; F.normal_mode = P.normal_mode;
-      F.first_pass = (pass == 0); F.seed = P.seed; F.out = outp; F.out_count = out->d_count; F.out_from = d_out_from;
-      F.shadow = shadow; F.shadow_count = c + 1; F.shadow_inst = d_shadow_inst; F.next_idx = next; F.next_count = c_next; F.sink = P.sink;
-      F.counter = c + 0; F.spill_base = C.d_spill; F.refill_min = C.refill_min; F.inner_min = C.inner_min;
-      F.tot = (unsigned long long *)(c + 16); F.tnear = GVT_RAY_EPSILON;
-      {
-        ProfScope ps(KC_CLOSEST);
-        k_fused<<<trav_grid2(n), TRAV_BLOCK, 0, st>>>(F);
-      }
-      if (nL > 1) {
-        k_set_u32<<<1, 64, 0, st>>>(c + 0, 0u); // the work counter of the launch that follows
-        ProfScope ps(KC_ANY);
-        MultiSrc MA{ W, d_shadow_inst, d_out_from, nullptr };
-        k_trace<true, true, 1, false, true, true><<<trav_grid2(n * (size_t)(nL - 1)), TRAV_BLOCK, 0, st>>>(shadow, nullptr, 0u, id, T, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                                                                                       c + 0, C.d_spill, C.refill_min, C.inner_min, c + 1, C.share, (unsigned)C.share_min_rays,
-                                                                                                       P.sink, LongQ{}, MA);
-        C.stats.launches_any++;
-      }
-      HIPCHK(hipGetLastError());
-      C.stats.launches_closest++;
-      continue;
-    }
-#endif
     LongQ LQ{};
     if (use_long) { LQ.recs = d_long; LQ.count = c + 3; long_limits(LQ, n); }
     MultiSrc MS{ W, nullptr, nullptr, nullptr };
@@ -771,19 +601,11 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
       ProfScope ps(KC_CLOSEST);
       k_long_seed<<<blocks_for(n), 256, 0, st>>>(d_long, c + 3, idx, (unsigned)n, n_dev);
       k_long_closest<true, true><<<small_grid, 256, 0, st>>>(none, d_long, c + 3, id, T, GVT_RAY_EPSILON, d_hits, c + 4, W, nullptr, pass > 0 ? d_hop : nullptr);
-    }
-#ifdef GVT_EXPERIMENTS
-    else if (C.quad && W.quad_ok) {
+    } else {
       ProfScope ps(KC_CLOSEST);
-      k_traceq<false, true, 0, true><<<quad_grid(n), 256, 0, st>>>(none, idx, (unsigned)n, id, TravQ{}, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
-                                                                 c + 0, C.d_spill, C.quad_refill_min, C.quad_inner_min, n_dev, TermSink{}, LQ, MS);
-    }
-#endif
-    else {
-      ProfScope ps(KC_CLOSEST);
-      k_trace<false, true, 0, false, true, true><<<trav_grid2(n, true), TRAV_BLOCK, 0, st>>>(none, idx, (unsigned)n, id, T, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
-                                                                                      c + 0, C.d_spill, C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays,
-                                                                                      d_hop ? P.sink : TermSink{}, LQ, MS);
+      k_trace<false, true, 0, true><<<trav_grid2(n, true), TRAV_BLOCK, 0, st>>>(none, idx, (unsigned)n, id, T, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
+                                                                          c + 0, C.d_spill, C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays,
+                                                                          d_hop ? P.sink : TermSink{}, LQ, MS);
     }
     if (use_long && !small && !pktm) {
       ProfScope ps(KC_LONG);
@@ -813,15 +635,9 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
       MultiSrc MA{ W, d_shadow_inst, d_out_from, direct ? (unsigned long long *)(c + 18) : nullptr };
       if (d_hop && P.sink.fb && P.hop == 2) { MA.hop_owner = P.hop_owner; MA.hop_rank = P.hop_rank; MA.hop_tot = hop_tot; } // (an un-occluded shadow ray goes on the same way -- not in the early mode: 1.372 -> 1.340 ms on the soup tiles without)
       if (small) k_wave_any<true><<<(int)std::min<size_t>((shadow_cap + 3) / 4, (size_t)C.n_cu * 3), 256, 0, st>>>(shadow, c + 1, id, T, GVT_RAY_EPSILON, outp, out->d_count, c + 0, P.sink, MA);
-#ifdef GVT_EXPERIMENTS
-      else if (C.quad && W.quad_ok)
-        k_traceq<true, true, 1, true><<<quad_grid(shadow_cap), 256, 0, st>>>(shadow, nullptr, direct ? (unsigned)shadow_cap : 0u, id, TravQ{}, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                                                           c + 0, C.d_spill, C.quad_refill_min, C.quad_inner_min, direct ? (direct_dev ? nd0 : nullptr) : c + 1, P.sink, LongQ{}, MA);
-#endif
-      else
-      k_trace<true, true, 1, false, true, true><<<trav_grid2(shadow_cap), TRAV_BLOCK, 0, st>>>(shadow, nullptr, direct ? (unsigned)shadow_cap : 0u, id, T, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                                                                              c + 0, C.d_spill, C.refill_min, C.inner_min, direct ? (direct_dev ? nd0 : nullptr) : c + 1, C.share, (unsigned)C.share_min_rays,
-                                                                                              P.sink, LongQ{}, MA);
+      else k_trace<true, true, 1, true><<<trav_grid2(shadow_cap), TRAV_BLOCK, 0, st>>>(shadow, nullptr, direct ? (unsigned)shadow_cap : 0u, id, T, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
+                                                                                 c + 0, C.d_spill, C.refill_min, C.inner_min, direct ? (direct_dev ? nd0 : nullptr) : c + 1, C.share,
+                                                                                 (unsigned)C.share_min_rays, P.sink, LongQ{}, MA);
     }
     HIPCHK(hipGetLastError());
     C.stats.launches_closest++;

@@ -205,7 +205,7 @@ struct MultiSrc {
   int hop_early;               // 1: only while the wave still has rays to fetch (a ray that goes on during the drain would stretch the launch's tail: it is left to the next round)
   unsigned long long *hop_tot; // the traces hops add (closest-hit traces, like the rounds they replace); any hit: non-null = hops on
 };
-template <bool ANY, bool XFORM, int MODE, bool COOP, bool W4, bool MULTI = false>
+template <bool ANY, bool XFORM, int MODE, bool MULTI = false>
 __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSEST)) void k_trace(RayPlanes q, const unsigned *__restrict__ idx, unsigned n, Mat4 minv, Trav T, float tnear,
                                                        gvt_hip_hit *__restrict__ hits, int *__restrict__ flags, RayPlanes out, unsigned *out_count,
                                                        unsigned *counter, int *spill_base, int refill_min, int inner_min, const unsigned *__restrict__ n_dev, int share, unsigned share_min, TermSink sink, LongQ LQ,
@@ -214,9 +214,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
   // dynamic ranges of `dyn` rays from the counter.  chunk is a fraction of a wave's fair share (3/8 for closest-hit launches, whose
   // per-ray cost varies most, 5/8 for any-hit; measured at 1 M rays: 96/128/160 rays -> 0.542/0.549/0.579 ms closest, 0.400/0.400/0.384
   // any), never less than one wave's width; dyn is 1/16 of the share, at least 64 (32: the counter word saturates).
-#ifdef GVT_EXPERIMENTS
-  if (!ANY && (share & 2)) LQ.steps = 0; // closest-hit drain sharing (a rejected variant) and parking both go after a launch's last rays: one at a time
-#endif
   // (refill_min / inner_min / share stay kernel arguments in the shipped library too, although only the experiments build can move them: as
   // compile-time constants they cost 1.5 % of the any-hit launch -- 0.3555 against 0.3500 ms, the register allocation changes)
   const unsigned n_waves_total = gridDim.x * (unsigned)(TRAV_BLOCK / 64);
@@ -281,13 +278,11 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
   unsigned j = 0;
   V3 O = mk3(0, 0, 0), D = mk3(0, 0, 1);
   RaySlab S = make_slab(0.f, 0.f, 0.f, 0.f, 0.f, 0.f);
-  float ox = 0, oy = 0, oz = 0; // O * inv_d as such: only the binary-tree variants (W4 false) read it
   float bt = GVT_FLT_MAX, bu = 0.f, bv = 0.f, bden = 1.f; // bu, bv: un-divided U, V of the best hit; bden its |den|
   int bp = -1, sp = 0, cur = TRAV_DONE;
   int sb = 0;           // bottom of this lane's stack window [sb, sp): entries below sb were given away to helper lanes
-  bool sharing = false; // wave-uniform: some ray of this wave is being traversed by more than one lane
+  bool sharing = false; // wave-uniform (any hit): some ray of this wave is being traversed by more than one lane
   int drain_iters = 0;  // wave-uniform: outer iterations since the wave's work range ran dry
-  int donor_lane = -1;  // helper: the lane it took its subtree from (to follow that lane's best hit)
   int nsteps = 0;       // closest hit: inner steps of this lane's ray; beyond LQ.steps the ray is parked for k_long_closest (nsteps = -1 from then on)
 #define KT_PARKED (nsteps < 0)
   const uint4 *nodes4_l = T.nodes4; // MULTI: this lane's ray's instance
@@ -389,11 +384,10 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
             const float dy = fabsf(D.y) < 1e-30f ? copysignf(1e-30f, D.y) : D.y;
             const float dz = fabsf(D.z) < 1e-30f ? copysignf(1e-30f, D.z) : D.z;
             const float ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz;
-            ox = O.x * ix; oy = O.y * iy; oz = O.z * iz;
-            S = make_slab(ix, iy, iz, ox, oy, oz);
+            S = make_slab(ix, iy, iz, O.x * ix, O.y * iy, O.z * iz);
             bt = GVT_FLT_MAX; bu = 0.f; bv = 0.f; bden = 1.f; bp = -1;
-            sp = 0; sb = 0; donor_lane = -1; nsteps = 0;
-            cur = (MULTI ? (nodes4_l != nullptr) : (W4 ? (T.nodes4 != nullptr) : (T.nodes != nullptr))) ? 0 : TRAV_DONE;
+            sp = 0; sb = 0; nsteps = 0;
+            cur = (MULTI ? nodes4_l : T.nodes4) != nullptr ? 0 : TRAV_DONE;
             active = true;
           }
         }
@@ -404,15 +398,12 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
       }
     }
     if (nidle == 64) break; // nothing left in flight and nothing left to fetch
-    // ---- drain phase: work sharing inside the wave.  Once the work counter is exhausted, a wave used to finish at the pace of
-    //      its slowest ray (measured: up to 536 more inner steps at ~2.5 K cycles each while 63 lanes idle -- the fixed ~0.5 ms of
-    //      every launch).  Now an idle lane takes the BOTTOM entry (the largest pending subtree) of a busy lane's stack together with a
-    //      copy of its ray and best hit, and traverses that subtree as a helper; results are merged when lanes of a ray retire.
-#ifdef GVT_EXPERIMENTS
-    const bool share_on = ANY ? (share & 1) != 0 : (share & 2) != 0;
-#else
-    const bool share_on = ANY && (share & 1) != 0; // sharing for closest hit lost (EXPERIMENTS.md): compiled into the experiments build only
-#endif
+    // ---- drain phase of an any-hit launch: work sharing inside the wave.  Once the work counter is exhausted, a wave used to finish at
+    //      the pace of its slowest ray (measured: up to 536 more inner steps at ~2.5 K cycles each while 63 lanes idle -- the fixed ~0.5 ms
+    //      of every launch).  Now an idle lane takes the BOTTOM entry (the largest pending subtree) of a busy lane's stack together with a
+    //      copy of its ray, and traverses that subtree as a helper; an occluder found by any lane of a ray ends them all when they retire.
+    //      (Sharing for closest hit lost, EXPERIMENTS.md: the pending subtrees of a closest-hit ray are mostly pruned by its eventual hit.)
+    const bool share_on = ANY && (share & 1) != 0;
     // ... but only once the wave has been draining for KT_SHARE_DELAY iterations: where shadow rays are short -- surface meshes: they leave or are
     // occluded within a few steps -- a wave's drain is over before then and never pays for the pairing (bun_zipper 0.557 -> 0.514 ms per
     // frame, bunny.conf 0.338 -> 0.291, the 8-bunny grid 0.502 -> 0.459 without sharing); in a dense soup the drain is a hundred steps long
@@ -424,31 +415,24 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
       const unsigned wave_tid0 = threadIdx.x & ~63u;
       for (int pairs = 0; idle_m && don_m && pairs < 16; pairs++) {
         const int h = __ffsll((long long)idle_m) - 1, d = __ffsll((long long)don_m) - 1;
-        // the bottom entry = the largest pending subtree.  For the closest hit those are the far siblings near the root, which the
-        // owner's eventual hit usually prunes: helpers therefore keep pulling the donor's current best distance (below).
+        // the bottom entry = the largest pending subtree
         const int sbd = __shfl(sb, d);
         const unsigned gj = (unsigned)__shfl((int)j, d);
         const float gOx = __shfl(O.x, d), gOy = __shfl(O.y, d), gOz = __shfl(O.z, d);
         const float gDx = __shfl(D.x, d), gDy = __shfl(D.y, d), gDz = __shfl(D.z, d);
-        const float gox = __shfl(ox, d), goy = __shfl(oy, d), goz = __shfl(oz, d);
         RaySlab gS;
         gS.ix = __shfl(S.ix, d); gS.iy = __shfl(S.iy, d); gS.iz = __shfl(S.iz, d);
         gS.ox = (f2){ __shfl(S.ox.x, d), __shfl(S.ox.y, d) }; gS.oy = (f2){ __shfl(S.oy.x, d), __shfl(S.oy.y, d) }; gS.oz = (f2){ __shfl(S.oz.x, d), __shfl(S.oz.y, d) };
-        const float gbt = __shfl(bt, d), gbu = __shfl(bu, d), gbv = __shfl(bv, d), gbden = __shfl(bden, d);
         const int gbp = __shfl(bp, d);
         const int ginst = __shfl(inst_l, d);
-        const unsigned ggidx = (unsigned)__shfl((int)gidx, d);
         if ((int)lane_id() == h) {
-          if (MULTI) { inst_l = ginst; gidx = ggidx; nodes4_l = MS.W.insts[ginst].nodes4; tris_l = MS.W.insts[ginst].tris; }
+          if (MULTI) { inst_l = ginst; nodes4_l = MS.W.insts[ginst].nodes4; tris_l = MS.W.insts[ginst].tris; }
           const unsigned tid_d = wave_tid0 + (unsigned)d;
           cur = (sbd < TRAV_STACK) ? stack[sbd * TRAV_BLOCK + tid_d]
                                    : spill_base[((size_t)blockIdx.x * TRAV_BLOCK + tid_d) * TRAV_SPILL + (sbd - TRAV_STACK)];
           j = gj; O = mk3(gOx, gOy, gOz); D = mk3(gDx, gDy, gDz);
-          S = gS; ox = gox; oy = goy; oz = goz;
-          bt = gbt; bu = gbu; bv = gbv; bden = gbden; bp = gbp; // the donor's best so far: a pruning bound, merged idempotently later
+          S = gS; bp = gbp;
           sp = 0; sb = 0;
-          donor_lane = d;
-          nsteps = 0; // a fresh share of the ray: not the step count / parked state of the lane's previous ray
           active = true;
         }
         if ((int)lane_id() == d) sb++;
@@ -460,13 +444,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
 #if GVT_STAMP == 1
     { unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_refill += t_ - t_mark; t_mark = t_; n_outer_it++; }
 #endif
-    if (!ANY && sharing) { // helpers follow their donor's best hit: a closer hit found by the owner prunes the helper's subtree too
-      const int dl = donor_lane >= 0 ? donor_lane : (int)lane_id();
-      const unsigned dj = (unsigned)__shfl((int)j, dl);
-      const float dt = __shfl(bt, dl), du = __shfl(bu, dl), dv = __shfl(bv, dl), dd = __shfl(bden, dl);
-      const int dp = __shfl(bp, dl);
-      if (active && donor_lane >= 0 && dj == j && dp >= 0 && (bp < 0 || dt < bt || (dt == bt && dp < bp))) { bt = dt; bp = dp; bu = du; bv = dv; bden = dd; }
-    }
     // ---- inner nodes: the lanes holding one descend level by level in a tight loop; the loop is left as soon as
     //      fewer than inner_min lanes still descend (the others wait at a leaf, have finished, or are idle), so that
     //      both this loop and the dearer leaf phase below run at high lane utilisation.
@@ -478,50 +455,43 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
     const float lim2 = fminf(cull_bound(bt), 3.40282326e38f);
     while (im) {
       const bool at_inner = cur >= 0;
-      if (W4) {
-        if (at_inner) { // one 64-byte fetch decides four children (8-bit boxes on the node's own grid)
-          float tn[4];
-          int rr[4];
-          bool entered[4];
-          // (node address from a 32-bit byte offset: one shift, and the load takes base + offset -- the builder refuses trees of 2^26 nodes or more)
-          node4_test<ANY>((const uint4 *)((const char *)(MULTI ? nodes4_l : T.nodes4) + ((unsigned)cur << 6)), S, GVT_FLT_MAX, tn, rr, ANY ? entered : nullptr);
+      if (at_inner) { // one 64-byte fetch decides four children (8-bit boxes on the node's own grid)
+        float tn[4];
+        int rr[4];
+        bool entered[4];
+        // (node address from a 32-bit byte offset: one shift, and the load takes base + offset -- the builder refuses trees of 2^26 nodes or more)
+        node4_test<ANY>((const uint4 *)((const char *)(MULTI ? nodes4_l : T.nodes4) + ((unsigned)cur << 6)), S, GVT_FLT_MAX, tn, rr, ANY ? entered : nullptr);
 #define KT_ENTERED(K) (ANY ? entered[K] : (tn[K] <= lim2)) // (closest hit: tn / rr are sorted below, the flags are not)
-          if (!ANY) { // nearest first; for any-hit the order does not matter
+        if (!ANY) { // nearest first; for any-hit the order does not matter
 #define GVT_CE(A, B) { const bool sw_ = tn[B] < tn[A]; const float ta_ = sw_ ? tn[B] : tn[A], tb_ = sw_ ? tn[A] : tn[B]; \
-                       const int ra_ = sw_ ? rr[B] : rr[A], rb_ = sw_ ? rr[A] : rr[B]; tn[A] = ta_; tn[B] = tb_; rr[A] = ra_; rr[B] = rb_; }
-            GVT_CE(0, 1) GVT_CE(2, 3) GVT_CE(0, 2) GVT_CE(1, 3) GVT_CE(1, 2)
+                     const int ra_ = sw_ ? rr[B] : rr[A], rb_ = sw_ ? rr[A] : rr[B]; tn[A] = ta_; tn[B] = tb_; rr[A] = ra_; rr[B] = rb_; }
+          GVT_CE(0, 1) GVT_CE(2, 3) GVT_CE(0, 2) GVT_CE(1, 3) GVT_CE(1, 2)
 #undef GVT_CE
-          }
-          // push the hit children farthest first (closest hit: sorted), continue with the first hit one
-          int nxt = TRAV_DONE;
-          bool have = false;
-          if (sp + 3 <= TRAV_STACK) { // room for three entries in the LDS part: no bounds checks, no spill path
-#pragma unroll
-            for (int c4 = 3; c4 >= 0; c4--) {
-              if (KT_ENTERED(c4)) {
-                if (have) { lds[sp * TRAV_BLOCK] = nxt; sp++; }
-                nxt = rr[c4]; have = true;
-              }
-            }
-          } else {
-#pragma unroll
-            for (int c4 = 3; c4 >= 0; c4--) {
-              if (KT_ENTERED(c4)) {
-                if (have) KT_PUSH(nxt)
-                nxt = rr[c4]; have = true;
-              }
-            }
-          }
-          if (have) cur = nxt;
-          else KT_POP()
-#undef KT_ENTERED
         }
+        // push the hit children farthest first (closest hit: sorted), continue with the first hit one
+        int nxt = TRAV_DONE;
+        bool have = false;
+        if (sp + 3 <= TRAV_STACK) { // room for three entries in the LDS part: no bounds checks, no spill path
+#pragma unroll
+          for (int c4 = 3; c4 >= 0; c4--) {
+            if (KT_ENTERED(c4)) {
+              if (have) { lds[sp * TRAV_BLOCK] = nxt; sp++; }
+              nxt = rr[c4]; have = true;
+            }
+          }
+        } else {
+#pragma unroll
+          for (int c4 = 3; c4 >= 0; c4--) {
+            if (KT_ENTERED(c4)) {
+              if (have) KT_PUSH(nxt)
+              nxt = rr[c4]; have = true;
+            }
+          }
+        }
+        if (have) cur = nxt;
+        else KT_POP()
+#undef KT_ENTERED
       }
-#ifdef GVT_EXPERIMENTS
-      else {
-#include "experiments/binary_node_arm.inc"
-      }
-#endif
 #if GVT_STAMP == 1
       n_inner_it++; n_inner_lanes += (unsigned long long)__popcll(ballot64(at_inner));
 #endif
@@ -541,11 +511,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
       const bool at_leaf = cur < 0 && cur != TRAV_DONE;
 #if GVT_STAMP == 1
       n_leaf_lanes += (unsigned long long)__popcll(ballot64(at_leaf));
-#endif
-#ifdef GVT_EXPERIMENTS
-      if (COOP) {
-#include "experiments/coop_leaf_arm.inc"
-      } else
 #endif
       if (at_leaf) {
         const unsigned code = (unsigned)~cur;
@@ -593,7 +558,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
       const bool retire_now = RETIRE_BATCH == 0 || share_now || nfin_w + nidle_w >= (exhausted ? 64 : refill_min);
       if (!retire_now) continue;
     }
-    if (sharing) { // lanes of one ray: the last one to finish carries the merged result, the others fold theirs into a partner
+    if (sharing) { // lanes of one ray (any hit): the last one to finish carries the merged result, the others fold theirs into a partner
       const unsigned long long FM = ballot64(active && cur == TRAV_DONE);
       unsigned long long fm = FM;
       while (fm) {
@@ -606,16 +571,11 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
         bool merged_occluded = false;
         while (src) {
           const int sidx = __ffsll((long long)src) - 1;
-          const float st = __shfl(bt, sidx), su = __shfl(bu, sidx), sv = __shfl(bv, sidx), sd = __shfl(bden, sidx);
-          const int spr = __shfl(bp, sidx);
-          const bool spk = __shfl(nsteps, sidx) < 0;
-          if (!ANY && (int)lane_id() == tgt && spk) nsteps = -1; // a lane that gave up on its share: the whole ray goes to k_long_closest
-          if (ANY) { if (spr >= 0) merged_occluded = true; }
-          else if ((int)lane_id() == tgt && spr >= 0 && (bp < 0 || st < bt || (st == bt && spr < bp))) { bt = st; bp = spr; bu = su; bv = sv; bden = sd; }
+          if (__shfl(bp, sidx) >= 0) merged_occluded = true;
           if ((int)lane_id() == sidx) active = false; // folded into tgt: retires without writing
           src &= src - 1;
         }
-        if (ANY && merged_occluded && ((G >> lane_id()) & 1ull) && active) { bp = 0; cur = TRAV_DONE; } // one occluder ends the whole group
+        if (merged_occluded && ((G >> lane_id()) & 1ull) && active) { bp = 0; cur = TRAV_DONE; } // one occluder ends the whole group
         fm &= ~Gf;
       }
     }
@@ -648,10 +608,9 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
             const float dy = fabsf(D.y) < 1e-30f ? copysignf(1e-30f, D.y) : D.y;
             const float dz = fabsf(D.z) < 1e-30f ? copysignf(1e-30f, D.z) : D.z;
             const float ix = 1.0f / dx, iy = 1.0f / dy, iz = 1.0f / dz;
-            ox = O.x * ix; oy = O.y * iy; oz = O.z * iz;
-            S = make_slab(ix, iy, iz, ox, oy, oz);
+            S = make_slab(ix, iy, iz, O.x * ix, O.y * iy, O.z * iz);
             bt = GVT_FLT_MAX; bu = 0.f; bv = 0.f; bden = 1.f; bp = -1;
-            sp = 0; sb = 0; donor_lane = -1; nsteps = 0;
+            sp = 0; sb = 0; nsteps = 0;
             cur = nodes4_l != nullptr ? 0 : TRAV_DONE; // (an instance without a tree: a miss at once -- the next retirement looks further)
             hopped = true;
           }
@@ -682,7 +641,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
           const unsigned slot = base + lanes_below(pm);
           LongRec R; R.j = j; R.i = MULTI ? gidx : (idx ? idx[j] : j); R.bt = bt; R.bp = bp; R.bu = bu; R.bv = bv; R.bden = bden; R.ns = 0u;
           const int depth = sp - sb;
-          if (LQ.stk && !sharing && depth > 0 && depth <= LONG_SAVE && slot < LQ.stk_cap) { // a shared ray's windows are not one stack: it starts again
+          if (LQ.stk && depth > 0 && depth <= LONG_SAVE && slot < LQ.stk_cap) {
             int *dst = LQ.stk + (size_t)slot * LONG_SAVE;
             for (int k = 0; k < depth; k++) dst[k] = (sb + k < TRAV_STACK) ? lds[(sb + k) * TRAV_BLOCK] : KT_SPILL(sb + k - TRAV_STACK);
             R.ns = (unsigned)depth;

@@ -141,8 +141,7 @@ int gvt_hip_mesh_get_normals(const gvt_hip_mesh *, float *out);
  * but keeps its tree's topology and node counts: the node boxes are refitted, not rebuilt.  Every device pointer the mesh holds stays
  * valid, so tracers and contexts that borrow it keep working; the caller serialises the update against frames that use the mesh.
  * vnormals == NULL: regenerated (on the device, bit-identical to the host generation at create).  The call is ordered on the calling
- * context's stream and returns when it is done.  ms_out (may be NULL): device time of the update after the upload.  Meshes built with the
- * quad layouts (experiments build) are refused. */
+ * context's stream and returns when it is done.  ms_out (may be NULL): device time of the update after the upload. */
 #define GVT_HIP_UPDATE_DEVICE 1u /* verts / vnormals are device pointers on the mesh's device (in situ: no host round trip) */
 int gvt_hip_mesh_update_vertices(gvt_hip_mesh *, const float *verts /* nV*3 */, size_t nV, const float *vnormals /* nV*3 or NULL */,
                                  uint32_t flags, float *ms_out);
@@ -417,12 +416,13 @@ int gvt_hip_math_probe(int kind, const float *in, size_t n, float *out);
  *                                                by events (also GVT_HIP_COMM_STREAM in the environment); default 0: on the compute stream, large payloads beside it
  *                "abi_lanes" / "abi_chunk"     gvt_hip_trace on a host RayVector: pipeline lanes (0: one shot), rays per chunk
  *   test hook    "inject_fail_tick"
- * Everything else -- the tuned constants of the kernels (refill / phase thresholds, grid sizes, drain sharing ...) and the variants that were
- * measured and lost ("trav_kernel" = 0, "wide4" = 0, "coop_fetch", "fused", "packet", "quad", merged kernels for one queue, compacted shadow
- * slots, non-lean frames, camera rays in generateRays' pixel-major order ("camera_tile" = 0) ...: EXPERIMENTS.md) -- can be moved only in the experiments build of the library (libgvt_hip_exp.so,
- * -DGVT_EXPERIMENTS), where the knob sweeps run; the shipped library answers GVT_HIP_ERR_INVALID when one of them is switched away from its default. */
+ * Everything else -- the tuned constants of the kernels (refill / phase thresholds, grid sizes, drain sharing ...) and the alternative arms that
+ * were measured and lost but stay in the code (merged kernels for one queue, compacted shadow slots, non-lean frames, camera rays in
+ * generateRays' pixel-major order ("camera_tile" = 0) ...: EXPERIMENTS.md) -- can be moved only in the experiments build of the library
+ * (libgvt_hip_exp.so, -DGVT_EXPERIMENTS), where the knob sweeps run; the shipped library answers GVT_HIP_ERR_INVALID when one of them is
+ * switched away from its default.  Any other name is an unknown option in both builds. */
 int gvt_hip_set_option(const char *name, int value);
-/* 1 in the experiments build (every variant behind its knob), 0 in the shipped library */
+/* 1 in the experiments build (the tuned constants movable), 0 in the shipped library */
 int gvt_hip_is_experiments_build(void);
 /* diagnostic: the calling thread's context counter words (32) after a stream synchronisation; [3] = rays the last closest-hit launch
    parked for k_long_closest, [8] = traversal overflow flags */

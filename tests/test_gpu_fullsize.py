@@ -81,8 +81,7 @@ def test_bounded_sample_bit_exact_against_oracle(soup):
 
 def test_traversal_layouts_agree_at_full_size(soup, hip):
     """The default path (compressed 4-wide nodes, long rays parked and finished a wave per ray) and the same without parking return the
-    same hit records for every primary ray of the frame, bit for bit -- and the default launch really parked rays.  (The first-version
-    kernel over the binary tree: tests/experiment_cases.py, against the experiments build.)"""
+    same hit records for every primary ray of the frame, bit for bit -- and the default launch really parked rays."""
     sc, tr = soup
     ad = next(iter(tr.backend.adapter_cache.values()))
     rays = oracle_camera_rays(sc)

@@ -633,8 +633,8 @@ def test_round_results_do_not_depend_on_knobs(hip, opts):
     """The round chain under every knob of the shipped library -- a wave per ray for small rounds or never, k_finish or rounds (over the cluster layout of the
     nodes, the default, or over the plain 4-wide nodes), exact
     growth, no terminal sink, the known-miss shortcut (against the checker's restatement of it) -- returns the oracle's image on a multi-domain depth-2 frame, on config 4
-    and on a soup (the variants that lost -- merged kernels for one queue, compacted shadow slots, non-lean frames, k_fused / k_packet /
-    k_traceq -- tests/experiment_cases.py, against the experiments build)."""
+    and on a soup (the alternative arms that lost -- merged kernels for one queue, compacted shadow slots, non-lean frames --
+    tests/experiment_cases.py, against the experiments build)."""
     for sc, mode, tol in ((config5(192, 4), NORMALS_FLAT, 1e-5), (scenes.bunny_grid_scene(width=380, height=216), NORMALS_SMOOTH, 0.0),
                           (scenes.soup_scene(100_000, 160, 90), NORMALS_FLAT, 0.0)):
         ref, st = oracle_render(sc, mode, nthreads=8, rule="shortcut" if opts.get("skip_known", 0) else "strict")

@@ -69,8 +69,8 @@ def test_closest_and_any_hit_match_oracle(hip, name):
                                   dict(leaf_max=1), dict(leaf_max=4, long_steps=4, long_min_rays=0), dict(leaf_max=3)])
 def test_results_do_not_depend_on_tuning_knobs(hip, opts):
     """Every knob of the shipped library that touches the adapter call -- sorting, parking threshold, sink, list order, leaf size -- returns
-    the same bits (the tuned constants -- refill / phase thresholds, grid sizes, drain sharing -- and the variants that lost can be moved
-    in the experiments build only: tests/experiment_cases.py sweeps them there)."""
+    the same bits (the tuned constants -- refill / phase thresholds, grid sizes, drain sharing -- can be moved in the experiments build
+    only: tests/experiment_cases.py sweeps them there)."""
     sc = scenes.soup_scene(150_000, 160, 90)
     mesh = sc.meshes[0]
     om = orc.Mesh(mesh.verts, mesh.tris, mesh_mat=mesh.material)

@@ -34,7 +34,7 @@ for f in glob.glob(out + "/pmc_*/**/*counter_collection.csv", recursive=True):
         e[0] += float(r["Counter_Value"] or 0); e[1] += 1
 res = {}
 for k, cs in pmc.items():
-    if not k.startswith(("k_trace", "k_packet", "k_long", "k_shade", "k_wave_any", "k_frame1", "k_finish")): continue
+    if not k.startswith(("k_trace", "k_packet", "k_long", "k_shade", "k_wave_any", "k_finish")): continue
     e = {c: v[0] / max(1, v[1]) for c, v in cs.items()}   # per launch
     e["launches_counted"] = max(v[1] for v in cs.values())
     if k in dur: e["avg_launch_us_trace_pass"] = sum(dur[k]) / len(dur[k]) / 1e3; e["launches_trace_pass"] = len(dur[k])

@@ -20,7 +20,7 @@ def run(opts, frames=4):
 configs = []
 for bb in (3, 4, 5, 6):
     for (r, i) in ((8, 20), (16, 32), (24, 40), (32, 48)):
-        configs.append(dict(trav_kernel=1, blocks_per_cu=bb, refill_min=r, inner_min=i, share=1))
+        configs.append(dict(blocks_per_cu=bb, refill_min=r, inner_min=i, share=1))
 res = {}
 for rnd in range(2):
     for c in configs:
