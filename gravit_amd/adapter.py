@@ -327,3 +327,92 @@ def camera_generate(q, cam, tile=0):
         q.h, capi.ptr(capi.f32(cam.eye, 3)), capi.ptr(capi.f32(cam.focus, 3)), capi.ptr(capi.f32(cam.up, 3)), C.c_float(cam.fov),
         C.c_int(cam.width), C.c_int(cam.height), C.c_int(cam.samples), C.c_int(cam.depth), C.c_float(cam.jitter), C.c_int(tile)),
         "gvt_hip_camera_generate_tiled")
+
+
+class TransferFunction:
+    """gvt::render::data::primitives::TransferFunction (TransferFunction.{h,cpp}): colour rows (x r g b), opacity rows (x a) and the value
+    range that maps onto them.  The 256-entry resampling and the opacity correction happen in the library (gvt_hip_volume_set_transfer)."""
+
+    def __init__(self, cmap, omap, value_range=(0.0, 1.0)):
+        self.cmap = capi.f32(cmap, (-1, 4))
+        self.omap = capi.f32(omap, (-1, 2))
+        self.value_range = (float(value_range[0]), float(value_range[1]))
+
+    @staticmethod
+    def read_map(path, width):
+        """GraviT's .cmap / .omap format (TransferFunction::load, :91-115): a count, then that many rows of `width` numbers."""
+        tok = open(path).read().split()
+        if not tok:
+            raise ValueError("%s: empty map" % path)
+        n = int(tok[0])
+        if n < 0 or len(tok) < 1 + n * width:
+            raise ValueError("%s: %d rows of %d promised, %d numbers present" % (path, n, width, len(tok) - 1))
+        return np.array([float(v) for v in tok[1:1 + n * width]], np.float32).reshape(n, width)
+
+    @classmethod
+    def from_files(cls, cmap_path, omap_path, value_range=(0.0, 1.0)):
+        return cls(cls.read_map(cmap_path, 4), cls.read_map(omap_path, 2), value_range)
+
+
+class HipVolumeAdapter:
+    """A volume brick on the device (gvt_hip_volume): the counterpart of the reference's volume adapters (OSPRayAdapter, PVolAdapter).
+    `brick` is a scenes.Brick (or a scenes.VolumeData: the whole grid as one brick); its data may also be a torch tensor on the GPU."""
+
+    def __init__(self, brick, sampling_rate=1.0, skip=True):
+        self.lib = capi.load()
+        if hasattr(brick, "global_counts"):
+            counts, offset, gcounts = brick.counts, brick.offset, brick.global_counts
+        else:
+            counts = brick.counts
+            offset, gcounts = np.zeros(3, np.int32), counts
+        data = brick.data
+        flags = 0 if skip else capi.VOLUME_NO_SKIP
+        if hasattr(data, "data_ptr") and data.is_cuda:  # a torch tensor on the device
+            if not data.is_contiguous() or str(data.dtype) != "torch.float32":
+                raise ValueError("HipVolumeAdapter: a device tensor must be contiguous float32")
+            self._data = data
+            src = C.c_void_p(data.data_ptr())
+            flags |= capi.VOLUME_DEVICE
+        elif hasattr(data, "data_ptr"):  # a torch tensor in host memory
+            self._data = capi.f32(data.numpy())
+            src = capi.ptr(self._data)
+        else:
+            self._data = capi.f32(data)
+            src = capi.ptr(self._data)
+        self.counts = np.ascontiguousarray(counts, np.int32)
+        self.offset = np.ascontiguousarray(offset, np.int32)
+        self.global_counts = np.ascontiguousarray(gcounts, np.int32)
+        self.origin = capi.f32(brick.origin, 3)
+        self.spacing = capi.f32(brick.spacing, 3)
+        self.sampling_rate = float(sampling_rate)
+        self.h = C.c_void_p(self.lib.gvt_hip_volume_create(src, capi.ptr(self.counts), capi.ptr(self.origin), capi.ptr(self.spacing),
+                                                           capi.ptr(self.offset), capi.ptr(self.global_counts), self.sampling_rate, flags))
+        if not self.h:
+            raise capi.GvtHipError("gvt_hip_volume_create: " + capi.last_error())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gvt_hip_volume_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_transfer(self, tf):
+        capi.check(self.lib.gvt_hip_volume_set_transfer(self.h, capi.ptr(tf.cmap), len(tf.cmap), capi.ptr(tf.omap), len(tf.omap),
+                                                         tf.value_range[0], tf.value_range[1]), "gvt_hip_volume_set_transfer")
+
+    def info(self):
+        i = capi.VolumeInfo()
+        capi.check(self.lib.gvt_hip_volume_get_info(self.h, C.byref(i)), "gvt_hip_volume_get_info")
+        return i.as_dict()
+
+    def trace(self, rays, m, minv, begin=0, end=0):
+        """OSPRayAdapter::trace: every ray of rays[begin, end) comes back marched through the brick, with its flags."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        n_in = (end or len(rays)) - begin
+        out = np.zeros(max(n_in, 0), RAY_DTYPE)
+        n_out = C.c_size_t(0)
+        capi.check(self.lib.gvt_hip_volume_trace(self.h, capi.ptr(rays), C.c_size_t(len(rays)), C.c_size_t(begin), C.c_size_t(end), capi.ptr(out),
+                                                 C.c_size_t(len(out)), C.byref(n_out), capi.ptr(capi.f32(m, 16)), capi.ptr(capi.f32(minv, 16))),
+                   "gvt_hip_volume_trace")
+        return out[:n_out.value]

@@ -31,6 +31,8 @@ SYMBOLS = [
     "gvt_hip_comm_unique_id", "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_hub_abort", "gvt_hip_hub_destroy", "gvt_hip_comm_create_local",
     "gvt_hip_comm_destroy", "gvt_hip_comm_rank", "gvt_hip_comm_world", "gvt_hip_comm_count", "gvt_hip_comm_reserved_cus", "gvt_hip_comm_set_deadline_ms", "gvt_hip_comm_selftest",
     "gvt_hip_tracer_create", "gvt_hip_tracer_destroy", "gvt_hip_tracer_set_camera", "gvt_hip_tracer_set_transforms", "gvt_hip_tracer_set_domains", "gvt_hip_tracer_frame",
+    "gvt_hip_volume_create", "gvt_hip_volume_destroy", "gvt_hip_volume_get_info", "gvt_hip_volume_set_transfer", "gvt_hip_volume_trace",
+    "gvt_hip_shuffle_volume", "gvt_hip_volume_frame",
 ]
 
 
@@ -58,6 +60,20 @@ class FrameStats(C.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
+
+class VolumeInfo(C.Structure):
+    _fields_ = [("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3), ("dt", C.c_float), ("value_min", C.c_float), ("value_max", C.c_float),
+                ("blocks", C.c_int32 * 3), ("pad", C.c_float), ("n_blocks", C.c_uint64), ("n_blocks_empty", C.c_uint64),
+                ("samples_marched", C.c_uint64), ("samples_gathered", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("box_lo", "box_hi", "blocks") else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+# volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
+RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10
+VOLUME_OPAQUE_A = 0.99
+VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
 
 FRAME_BSP, FRAME_NO_COMPOSITE, FRAME_FULL_REDUCE, FRAME_IMAGE = 1, 2, 4, 8
 
@@ -87,13 +103,15 @@ def load():
         for s in SYMBOLS:
             getattr(lib, s)  # AttributeError if the ABI is incomplete
         lib.gvt_hip_last_error.restype = C.c_char_p
+        lib.gvt_hip_volume_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
+        lib.gvt_hip_volume_set_transfer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
         for f in ("gvt_hip_mesh_create", "gvt_hip_queue_create", "gvt_hip_top_create", "gvt_hip_fb_create", "gvt_hip_fb_device_ptr", "gvt_hip_ctx_create",
-                  "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_comm_create_local", "gvt_hip_tracer_create"):
+                  "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_comm_create_local", "gvt_hip_tracer_create", "gvt_hip_volume_create"):
             getattr(lib, f).restype = C.c_void_p
         for f in ("gvt_hip_mesh_destroy", "gvt_hip_queue_destroy", "gvt_hip_top_destroy", "gvt_hip_fb_destroy", "gvt_hip_ctx_destroy", "gvt_hip_hub_abort",
-                  "gvt_hip_hub_destroy", "gvt_hip_comm_destroy", "gvt_hip_tracer_destroy"):
+                  "gvt_hip_hub_destroy", "gvt_hip_comm_destroy", "gvt_hip_tracer_destroy", "gvt_hip_volume_destroy"):
             getattr(lib, f).restype = None
             getattr(lib, f).argtypes = [C.c_void_p]
         _lib = lib
@@ -166,5 +184,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

@@ -1,0 +1,670 @@
+// volume.hip -- volume domains: scalar bricks rendered with a transfer function.
+//   gvt_hip_volume_create / _set_transfer   Volume + TransferFunction (render/data/primitives/Volume.h, TransferFunction.cpp:40-72)
+//   k_volume_march                          the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp)
+//   k_vol_classify / _scan / _scatter       AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391)
+//   gvt_hip_volume_frame                    Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks
+// The contract (lattice, ownership, evaluation order, flags) is stated in include/gvt_hip.h; tests/volume_checker.py restates it in numpy.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "gvt_internal.h"
+
+struct gvt_hip_volume {
+  int n[3] = { 0, 0, 0 }, off[3] = { 0, 0, 0 };
+  float go[3] = { 0, 0, 0 }, sp[3] = { 1, 1, 1 };
+  float rate = 1.f, dt = 1.f;
+  float lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 }; // the brick's vertex box, object space
+  int skip = 1;
+  float vmin = 0.f, vmax = 0.f;
+  int nb[3] = { 0, 0, 0 };
+  std::vector<float> bmin, bmax; // per macro cell: value range of its vertices
+  std::vector<uint8_t> bnan;     // ... and whether one of them is NaN
+  uint64_t n_empty = 0;
+  bool has_tf = false;
+  float tf_lo = 0.f, tf_hi = 1.f;
+  float *d_vox = nullptr;
+  float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
+  uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
+  unsigned long long *d_stats = nullptr; // samples marched, samples gathered
+};
+
+namespace {
+
+#define VOL_BLOCK 256
+#define VOL_STEP 32          // samples a lane marches between two refill decisions of its wave
+#define VOL_REFILL_MIN 16    // a wave fetches new rays once at least this many of its lanes are idle (or all of them)
+#define VOL_K_MAX 1073741824.f
+#define VOL_MAX_SAMPLES (1 << 22) // lattice positions one visit of a brick walks at most (only reached by rays whose |d| is far below the spacing)
+#define VOL_DEST_MAX 256
+
+struct VolDev {
+  const float *vox;
+  const float4 *tf;
+  const uint8_t *mc;
+  int nx, ny, nz, ox, oy, oz, nbx, nby;
+  float gox, goy, goz, sx, sy, sz, dt;
+  float lo[3], hi[3];
+  float vlo, vspan;
+  int skip;
+};
+
+// slab test of the ray o + t d against [lo, hi] in the contract's fixed form (the march and the shuffle; tests/volume_checker.py restates
+// it): an axis with d == 0 keeps the whole line or none of it.  Miss: tn > tf.
+__device__ inline void vol_slab(const float lo[3], const float hi[3], const float o[3], const float d[3], float &tn, float &tf) {
+  tn = -INFINITY; tf = INFINITY;
+  for (int a = 0; a < 3; a++) {
+    if (d[a] == 0.f) {
+      if (o[a] < lo[a] || o[a] > hi[a]) { tn = INFINITY; tf = -INFINITY; }
+      continue;
+    }
+    const float inv = 1.f / d[a];
+    float t0 = (lo[a] - o[a]) * inv, t1 = (hi[a] - o[a]) * inv;
+    if (t0 > t1) { const float s = t0; t0 = t1; t1 = s; }
+    tn = fmaxf(tn, t0); tf = fminf(tf, t1);
+  }
+}
+
+// first lattice index k >= 0 with k * dt > t; -1: none below VOL_K_MAX
+__device__ inline int vol_first_after(float t, float dt) {
+  if (!(t >= 0.f)) return 0;
+  const float q = floorf(t / dt);
+  if (!(q < VOL_K_MAX)) return -1;
+  int k = (int)q;
+  while ((float)k * dt <= t) k++;
+  while (k > 0 && (float)(k - 1) * dt > t) k--;
+  return k;
+}
+
+// the global cell of lattice sample k: is it the brick's?  c = the cell relative to the brick, f = the fractions inside it
+__device__ inline bool vol_cell(const VolDev &V, const float o[3], const float d[3], int k, int c[3], float f[3]) {
+  const float t = (float)k * V.dt;
+  const float g[3] = { ((o[0] + d[0] * t) - V.gox) / V.sx, ((o[1] + d[1] * t) - V.goy) / V.sy, ((o[2] + d[2] * t) - V.goz) / V.sz };
+  const int off[3] = { V.ox, V.oy, V.oz }, n[3] = { V.nx, V.ny, V.nz };
+  bool own = true;
+  for (int a = 0; a < 3; a++) {
+    const float fl = floorf(g[a]);
+    f[a] = g[a] - fl;
+    own = own && fl >= (float)off[a] && fl <= (float)(off[a] + n[a] - 2); // (false for NaN)
+    c[a] = own ? (int)fl - off[a] : 0;
+  }
+  return own;
+}
+
+__device__ inline float lerp_(float a, float b, float f) { return a + f * (b - a); }
+
+// One lane per ray, persistent waves with lane refill: a lane that finishes its ray takes the next one of the queue (one atomic per wave
+// and refill).  Rays are updated in place.
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                            unsigned long long *__restrict__ stats) {
+  bool active = false, exhausted = false;
+  unsigned idx = 0;
+  float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
+  int k = 0, k_hi = -1, k_last = -1;
+  bool seen = false;
+  unsigned long long n_marched = 0, n_gathered = 0;
+  for (;;) {
+    const unsigned long long idle = ballot64(!active);
+    if (idle && !exhausted && (__popcll(idle) >= VOL_REFILL_MIN || idle == ballot64(true))) {
+      const unsigned slot = wave_alloc(work, !active);
+      if (ballot64(!active && slot >= n)) exhausted = true; // (wave-uniform)
+      if (!active && slot < n) {
+        idx = slot;
+        active = true;
+        const float4 a = q.p0[idx], b = q.p1[idx], c = q.p2[idx];
+        const V3 oo = xfm_point(minv, mk3(a.x, a.y, a.z)), dd = xfm_vector(minv, mk3(b.x, b.y, b.z));
+        o[0] = oo.x; o[1] = oo.y; o[2] = oo.z; d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
+        C[0] = c.x; C[1] = c.y; C[2] = c.z;
+        A = q.p3[idx].z;
+        float tn, tf;
+        vol_slab(V.lo, V.hi, o, d, tn, tf);
+        const int k_prog = vol_first_after(a.w, V.dt);
+        k = 0;
+        k_hi = -1;
+        if (tn <= tf && tf >= 0.f && tf < INFINITY && k_prog >= 0) {
+          const float qlo = floorf(tn / V.dt), qhi = floorf(tf / V.dt);
+          if (qlo < VOL_K_MAX) {
+            k = max(k_prog, qlo > 1.f ? (int)qlo - 1 : 0);
+            k_hi = qhi < VOL_K_MAX ? (int)qhi + 1 : (int)VOL_K_MAX;
+            k_hi = min(k_hi, k + VOL_MAX_SAMPLES);
+          }
+        }
+        k_last = -1;
+        seen = false;
+      }
+    }
+    if (!ballot64(active)) break;
+    if (active) {
+      bool done = false;
+      for (int s = 0; s < VOL_STEP; s++) {
+        if (k > k_hi) { done = true; break; }
+        int c[3];
+        float f[3];
+        if (!vol_cell(V, o, d, k, c, f)) {
+          if (seen) { done = true; break; } // a brick's samples along a line are contiguous: the rest belongs to others
+          k++;
+          continue;
+        }
+        seen = true;
+        k_last = k;
+        n_marched++;
+        const int bi = ((c[2] >> 3) * V.nby + (c[1] >> 3)) * V.nbx + (c[0] >> 3);
+        if (V.skip && !V.mc[bi]) {
+          // an empty macro cell adds +0 per sample: jump to the last sample still inside it -- verified, so exact whatever the estimate
+          // (per axis the cells move monotonically with k: two samples in one block have every sample between them in it too)
+          const int cb[3] = { c[0] >> 3, c[1] >> 3, c[2] >> 3 };
+          const int off[3] = { V.ox, V.oy, V.oz }, nn[3] = { V.nx, V.ny, V.nz };
+          const float go[3] = { V.gox, V.goy, V.goz }, sp[3] = { V.sx, V.sy, V.sz };
+          float te = INFINITY;
+          for (int a = 0; a < 3; a++) {
+            if (d[a] == 0.f) continue;
+            const int gv = d[a] > 0.f ? off[a] + min(8 * cb[a] + 8, nn[a] - 1) : off[a] + 8 * cb[a];
+            te = fminf(te, ((go[a] + (float)gv * sp[a]) - o[a]) / d[a]);
+          }
+          const float qj = floorf(te / V.dt);
+          if (qj < VOL_K_MAX && qj > (float)(k + 1)) {
+            const int kj = min((int)qj, k_hi);
+            int cj[3];
+            float fj[3];
+            if (kj > k + 1 && vol_cell(V, o, d, kj, cj, fj) && (cj[0] >> 3) == cb[0] && (cj[1] >> 3) == cb[1] && (cj[2] >> 3) == cb[2]) {
+              n_marched += (unsigned long long)(kj - k);
+              k_last = kj;
+              k = kj;
+            }
+          }
+          k++;
+          continue;
+        }
+        n_gathered++;
+        const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny;
+        const float *p = V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
+        const float v000 = p[0], v100 = p[1], v010 = p[sy], v110 = p[sy + 1];
+        const float v001 = p[sz], v101 = p[sz + 1], v011 = p[sz + sy], v111 = p[sz + sy + 1];
+        const float c00 = lerp_(v000, v100, f[0]), c10 = lerp_(v010, v110, f[0]);
+        const float c01 = lerp_(v001, v101, f[0]), c11 = lerp_(v011, v111, f[0]);
+        const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
+        const float v = lerp_(c0, c1, f[2]);
+        const float pos = fminf(fmaxf((v - V.vlo) / V.vspan, 0.f), 1.f) * 255.f;
+        const int i0 = min((int)pos, 254);
+        const float w = pos - (float)i0;
+        const float4 e0 = V.tf[i0], e1 = V.tf[i0 + 1];
+        const float r = lerp_(e0.x, e1.x, w), g = lerp_(e0.y, e1.y, w), b = lerp_(e0.z, e1.z, w), al = lerp_(e0.w, e1.w, w);
+        const float fr = (1.f - A) * al;
+        C[0] = C[0] + fr * r; C[1] = C[1] + fr * g; C[2] = C[2] + fr * b;
+        A = A + fr;
+        k++;
+        if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
+      }
+      if (done) {
+        float4 a = q.p0[idx];
+        if (k_last >= 0) a.w = (float)k_last * V.dt;
+        q.p0[idx] = a;
+        q.p2[idx] = make_float4(C[0], C[1], C[2], q.p2[idx].w);
+        float4 e = q.p3[idx];
+        const int flag = A >= GVT_HIP_VOLUME_OPAQUE_A ? GVT_HIP_RAY_OPAQUE : GVT_HIP_RAY_BOUNDARY;
+        e.y = __int_as_float(__float_as_int(e.y) | flag);
+        e.z = A;
+        q.p3[idx] = e;
+        active = false;
+      }
+    }
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    n_marched += __shfl_xor(n_marched, s);
+    n_gathered += __shfl_xor(n_gathered, s);
+  }
+  if (lane_id() == 0 && n_marched) { atomicAdd(&stats[0], n_marched); atomicAdd(&stats[1], n_gathered); }
+}
+
+// ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
+// its first slot, so the queues keep the order of the list they were filled from.
+__device__ inline int vol_next(const TopDev &T, int from, const float o[3], const float d[3], float t_min) {
+  float p = t_min;
+  if (from >= 0) { // progress = the exit of the source box (world space, the test below): it grows strictly from hop to hop
+    for (int j = 0; j < T.n_inst; j++) {
+      const float4 lo = T.blo[j], hi = T.bhi[j];
+      if (__float_as_int(lo.w) != from) continue;
+      const float l[3] = { lo.x, lo.y, lo.z }, h[3] = { hi.x, hi.y, hi.z };
+      float tn;
+      vol_slab(l, h, o, d, tn, p);
+    }
+  }
+  int next = -1;
+  float best = INFINITY;
+  for (int j = 0; j < T.n_inst; j++) { // in the top's order: equal entries resolve to the first
+    const float4 lo = T.blo[j], hi = T.bhi[j];
+    const int inst = __float_as_int(lo.w);
+    if (inst == from) continue;
+    const float l[3] = { lo.x, lo.y, lo.z }, h[3] = { hi.x, hi.y, hi.z };
+    float tn, tf;
+    vol_slab(l, h, o, d, tn, tf);
+    if (tn <= tf && tf > p && (next < 0 || tn < best)) { next = inst; best = tn; }
+  }
+  return next;
+}
+
+__global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigned n, TopDev T, int n_dest, int from, int *__restrict__ next_out,
+                                                            unsigned *__restrict__ blk_cnt, float *__restrict__ fb, unsigned n_pix) {
+  __shared__ unsigned sh[VOL_DEST_MAX];
+  for (int j = threadIdx.x; j < n_dest; j += VOL_BLOCK) sh[j] = 0u;
+  __syncthreads();
+  const unsigned i = blockIdx.x * VOL_BLOCK + threadIdx.x;
+  int next = -1;
+  if (i < n) {
+    const float4 a = q.p0[i], b = q.p1[i], e = q.p3[i];
+    const float o[3] = { a.x, a.y, a.z }, d[3] = { b.x, b.y, b.z };
+    const int depth = __float_as_int(e.y);
+    bool deposit = false;
+    if (from < 0) next = vol_next(T, -1, o, d, a.w); // camera rays: no deposit where they meet no brick
+    else if (depth & GVT_HIP_RAY_OPAQUE) deposit = true;
+    else if (depth & GVT_HIP_RAY_BOUNDARY) {
+      next = vol_next(T, from, o, d, a.w);
+      deposit = next < 0; // EXTERNAL: the ray leaves the volume
+    }
+    if (deposit && fb) {
+      const unsigned id = (unsigned)__float_as_int(e.x);
+      if (id < n_pix) {
+        const float4 c = q.p2[i];
+        float *px = fb + (size_t)4 * id;
+        atomicAdd(px + 0, c.x); atomicAdd(px + 1, c.y); atomicAdd(px + 2, c.z); atomicAdd(px + 3, e.z);
+      }
+    }
+    next_out[i] = next;
+  }
+  unsigned long long todo = ballot64(next >= 0);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int dd = __shfl(next, leader);
+    const unsigned long long m = ballot64(next == dd);
+    if ((int)lane_id() == leader) atomicAdd(&sh[dd], (unsigned)__popcll(m));
+    todo &= ~m;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < n_dest; j += VOL_BLOCK) blk_cnt[(size_t)j * gridDim.x + blockIdx.x] = sh[j];
+}
+
+// one block per destination: exclusive scan of its per-block counts, offset by the queue's fill; totals[j] = the rays it receives
+__global__ __launch_bounds__(VOL_BLOCK) void k_vol_scan(unsigned *__restrict__ blk_cnt, unsigned n_blk, const QueueDesc *__restrict__ queues,
+                                                        unsigned *__restrict__ totals) {
+  __shared__ unsigned sh_w[VOL_BLOCK / 64];
+  __shared__ unsigned sh_run, sh_start;
+  const int j = blockIdx.x;
+  unsigned *row = blk_cnt + (size_t)j * n_blk;
+  if (threadIdx.x == 0) { sh_run = *queues[j].count; sh_start = sh_run; }
+  __syncthreads();
+  for (unsigned b0 = 0; b0 < n_blk; b0 += VOL_BLOCK) {
+    const unsigned b = b0 + threadIdx.x;
+    const unsigned v = b < n_blk ? row[b] : 0u;
+    unsigned incl = v;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if ((int)lane_id() >= o) incl += u; }
+    if (lane_id() == 63) sh_w[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    unsigned woff = 0;
+    for (unsigned w = 0; w < (threadIdx.x >> 6); w++) woff += sh_w[w];
+    const unsigned run = sh_run;
+    if (b < n_blk) row[b] = run + woff + incl - v;
+    __syncthreads();
+    if (threadIdx.x == VOL_BLOCK - 1) sh_run = run + woff + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) totals[j] = sh_run - sh_start;
+}
+
+// fresh (camera rays): they start with no colour, no opacity and no flags
+__global__ __launch_bounds__(VOL_BLOCK) void k_vol_scatter(RayPlanes q, unsigned n, const int *__restrict__ next_in, const unsigned *__restrict__ blk_base,
+                                                           const QueueDesc *__restrict__ queues, int n_dest, int fresh, unsigned *__restrict__ overflow) {
+  __shared__ unsigned sh[(VOL_BLOCK / 64) * VOL_DEST_MAX]; // rays of wave w for destination j
+  for (int x = threadIdx.x; x < (VOL_BLOCK / 64) * n_dest; x += VOL_BLOCK) sh[x] = 0u;
+  __syncthreads();
+  const unsigned i = blockIdx.x * VOL_BLOCK + threadIdx.x;
+  const int next = i < n ? next_in[i] : -1;
+  unsigned local = 0;
+  unsigned long long todo = ballot64(next >= 0);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int dd = __shfl(next, leader);
+    const unsigned long long m = ballot64(next == dd);
+    if ((int)lane_id() == leader) sh[(threadIdx.x >> 6) * n_dest + dd] = (unsigned)__popcll(m);
+    if (next == dd) local = lanes_below(m);
+    todo &= ~m;
+  }
+  __syncthreads();
+  if (next < 0) return;
+  for (unsigned w = 0; w < (threadIdx.x >> 6); w++) local += sh[w * n_dest + next];
+  local += blk_base[(size_t)next * gridDim.x + blockIdx.x];
+  RayRec r = load_ray(q, i);
+  r.depth &= ~GVT_HIP_RAY_BOUNDARY;
+  if (fresh) { r.c = mk3(0.f, 0.f, 0.f); r.w = 0.f; r.depth = 0; }
+  const QueueDesc Q = queues[next];
+  if (local < Q.cap) store_ray(make_planes(Q.planes, Q.cap), local, r);
+  else atomicOr(overflow, 1u);
+}
+
+inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
+
+VolDev vol_dev(const gvt_hip_volume *Vh) {
+  VolDev V;
+  V.vox = Vh->d_vox; V.tf = Vh->d_tf; V.mc = Vh->d_mc;
+  V.nx = Vh->n[0]; V.ny = Vh->n[1]; V.nz = Vh->n[2]; V.ox = Vh->off[0]; V.oy = Vh->off[1]; V.oz = Vh->off[2];
+  V.nbx = Vh->nb[0]; V.nby = Vh->nb[1];
+  V.gox = Vh->go[0]; V.goy = Vh->go[1]; V.goz = Vh->go[2]; V.sx = Vh->sp[0]; V.sy = Vh->sp[1]; V.sz = Vh->sp[2]; V.dt = Vh->dt;
+  for (int a = 0; a < 3; a++) { V.lo[a] = Vh->lo[a]; V.hi[a] = Vh->hi[a]; }
+  V.vlo = Vh->tf_lo; V.vspan = Vh->tf_hi - Vh->tf_lo;
+  V.skip = Vh->skip;
+  return V;
+}
+
+// the march of q's rays through brick Vh, in place, on the context's stream (no host wait)
+int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
+  if (!q->size) return 0;
+  Ctx &C = gctx();
+  unsigned *work = (unsigned *)scratch_get(20, sizeof(unsigned));
+  if (!work) return GVT_HIP_ERR_DEVICE;
+  HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
+  Mat4 M;
+  for (int k = 0; k < 16; k++) M.m[k] = minv[k];
+  const unsigned blocks = std::min(blocks_of(q->size), (unsigned)(std::max(C.n_cu, 1) * 8));
+  k_volume_march<<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// consumes q_in; one host wait (two where a destination queue has to grow to its exact need first)
+int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb) {
+  Ctx &C = gctx();
+  hipStream_t st = C.stream;
+  const size_t n = q_in->size, nI = T->n;
+  if (!n) return 0;
+  const unsigned n_blk = blocks_of(n);
+  int *d_next = (int *)scratch_get(6, sizeof(int) * n);
+  unsigned *d_blk = (unsigned *)scratch_get(14, sizeof(unsigned) * (nI ? nI : 1) * n_blk);
+  unsigned *d_ovf = (unsigned *)scratch_get(22, sizeof(unsigned));
+  if (!d_next || !d_blk || !d_ovf) return GVT_HIP_ERR_DEVICE;
+  bool roomy = true;
+  for (size_t i = 0; i < nI; i++) {
+    if ((int)i == from) continue;
+    if (nI <= 16 && queues[i]->cap < queues[i]->size + n) { // few bricks: worst-case room, so that the round has one host wait
+      int rc = queue_reserve(queues[i], queues[i]->size + n);
+      if (rc) return rc;
+    }
+    if (queues[i]->cap < queues[i]->size + n) roomy = false;
+  }
+  QueueDesc *desc = (QueueDesc *)T->h_qdesc;
+  auto upload_desc = [&]() -> int {
+    for (size_t i = 0; i < nI; i++) { desc[i].planes = queues[i]->d_planes; desc[i].cap = queues[i]->cap; desc[i].count = queues[i]->d_count; desc[i].keep = 1u; }
+    if (nI) HIPCHK(hipMemcpyAsync(T->d_qdesc, desc, sizeof(QueueDesc) * nI, hipMemcpyHostToDevice, st));
+    T->qdesc_uploaded.clear(); // (the asynchronous mesh shuffle's upload cache no longer describes d_qdesc)
+    return 0;
+  };
+  int rc;
+  if ((rc = upload_desc())) return rc;
+  HIPCHK(hipMemsetAsync(d_ovf, 0, sizeof(unsigned), st));
+  const RayPlanes P = make_planes(q_in->d_planes, q_in->cap);
+  {
+    ProfScope ps(KC_SHUFFLE);
+    k_vol_classify<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, T->dev(), (int)nI, from, d_next, d_blk, fb ? fb->d_rgba : nullptr,
+                                                fb ? (unsigned)(fb->w * fb->h) : 0u);
+    if (nI) k_vol_scan<<<(unsigned)nI, VOL_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, T->d_hist);
+  }
+  HIPCHK(hipGetLastError());
+  if (!roomy) { // exact growth: the totals first (the scan's bases depend only on the counts, which do not move before the scatter)
+    HIPCHK(hipMemcpyAsync(T->h_hist, T->d_hist, sizeof(unsigned) * nI, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < nI; i++)
+      if (T->h_hist[i] && (rc = queue_reserve(queues[i], queues[i]->size + T->h_hist[i]))) return rc;
+    if ((rc = upload_desc())) return rc;
+  }
+  {
+    ProfScope ps(KC_SHUFFLE);
+    k_vol_scatter<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, d_next, d_blk, (const QueueDesc *)T->d_qdesc, (int)nI, from < 0 ? 1 : 0, d_ovf);
+  }
+  HIPCHK(hipGetLastError());
+  if (nI) HIPCHK(hipMemcpyAsync(T->h_hist, T->d_hist, sizeof(unsigned) * nI, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(C.h_pinned + 13, d_ovf, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (C.h_pinned[13]) { set_error("shuffle_volume: a destination queue overflowed"); return GVT_HIP_ERR_DEVICE; }
+  for (size_t i = 0; i < nI; i++) {
+    if (!T->h_hist[i]) continue;
+    queues[i]->size += T->h_hist[i];
+    if ((rc = set_device_u32(queues[i]->d_count, (unsigned)queues[i]->size))) return rc;
+  }
+  q_in->size = 0; // rays.clear(), TracerBase.h:411
+  HIPCHK(hipMemsetAsync(q_in->d_count, 0, sizeof(unsigned), st));
+  return 0;
+}
+
+// TransferFunction::DeviceCommit's resampling (TransferFunction.cpp:40-72): the positions x in double rounded to float, the interpolation in
+// float; rows of W floats (x first)
+template <int W>
+bool resample(const float *map, int nrow, float out[256][W - 1]) {
+  int i0 = 0, i1 = 1;
+  const float xmin = map[0], xmax = map[(size_t)(nrow - 1) * W];
+  for (int i = 0; i < 256; i++) {
+    float x = xmin + (i / (255.0)) * (xmax - xmin);
+    if (x > xmax) x = xmax;
+    while (map[(size_t)i1 * W] < x) i0++, i1++;
+    const float dx = (x - map[(size_t)i0 * W]) / (map[(size_t)i1 * W] - map[(size_t)i0 * W]);
+    for (int c = 1; c < W; c++) {
+      const float a = map[(size_t)i0 * W + c], b = map[(size_t)i1 * W + c];
+      out[i][c - 1] = a + dx * (b - a);
+      if (!std::isfinite(out[i][c - 1])) return false;
+    }
+  }
+  return true;
+}
+
+} // namespace
+
+extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int counts[3], const float origin[3], const float spacing[3], const int offset[3],
+                                                 const int global_counts[3], float sampling_rate, int flags) {
+  if (ensure_init()) return nullptr;
+  if (!samples || !counts || !origin || !spacing || !offset || !global_counts) { set_error("volume_create: null argument"); return nullptr; }
+  if (flags & ~(GVT_HIP_VOLUME_DEVICE | GVT_HIP_VOLUME_NO_SKIP)) { set_error("volume_create: unknown flag bits %d", flags); return nullptr; }
+  if (!(sampling_rate > 0.f) || !std::isfinite(sampling_rate)) { set_error("volume_create: sampling_rate %g is not positive", (double)sampling_rate); return nullptr; }
+  size_t total = 1;
+  for (int a = 0; a < 3; a++) {
+    if (counts[a] < 2 || global_counts[a] < 2) { set_error("volume_create: counts must be at least 2 per axis (axis %d)", a); return nullptr; }
+    if (!(spacing[a] > 0.f) || !std::isfinite(spacing[a]) || !std::isfinite(origin[a])) { set_error("volume_create: spacing of axis %d is not positive and finite", a); return nullptr; }
+    if (offset[a] < 0 || (long long)offset[a] + counts[a] > (long long)global_counts[a]) {
+      set_error("volume_create: the brick's vertices [%d, %d) of axis %d lie outside its global grid of %d", offset[a], offset[a] + counts[a], a, global_counts[a]);
+      return nullptr;
+    }
+    if (global_counts[a] >= (1 << 24)) { set_error("volume_create: global grid too large on axis %d", a); return nullptr; }
+    total *= (size_t)counts[a];
+  }
+  if (total >= 0xffffffffull) { set_error("volume_create: brick of %zu vertices is too large", total); return nullptr; }
+  gvt_hip_volume *V = new gvt_hip_volume();
+  for (int a = 0; a < 3; a++) {
+    V->n[a] = counts[a]; V->off[a] = offset[a]; V->go[a] = origin[a]; V->sp[a] = spacing[a];
+    V->lo[a] = origin[a] + (float)offset[a] * spacing[a];
+    V->hi[a] = origin[a] + (float)(offset[a] + counts[a] - 1) * spacing[a];
+    V->nb[a] = (counts[a] - 1 + 7) / 8;
+  }
+  V->rate = sampling_rate;
+  V->dt = std::min(std::min(spacing[0], spacing[1]), spacing[2]) / sampling_rate;
+  V->skip = (flags & GVT_HIP_VOLUME_NO_SKIP) ? 0 : 1;
+  const size_t n_blocks = (size_t)V->nb[0] * V->nb[1] * V->nb[2];
+  std::vector<float> host;
+  const float *h = samples;
+  bool ok = hipMalloc((void **)&V->d_vox, sizeof(float) * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
+            hipMalloc((void **)&V->d_stats, 2 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMemset(V->d_stats, 0, 2 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess;
+  if (ok && (flags & GVT_HIP_VOLUME_DEVICE)) {
+    host.resize(total);
+    ok = hipMemcpy(host.data(), samples, sizeof(float) * total, hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(V->d_vox, samples, sizeof(float) * total, hipMemcpyDeviceToDevice) == hipSuccess;
+    h = host.data();
+  } else if (ok) {
+    ok = hipMemcpy(V->d_vox, samples, sizeof(float) * total, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) { set_error("volume_create: device allocation or copy failed"); gvt_hip_volume_destroy(V); return nullptr; }
+  // macro cells: the value range of the vertices of their (up to) 8^3 cells.  A vertex is a corner of the cells of its block and, on a
+  // block boundary, of the block below too
+  V->bmin.assign(n_blocks, INFINITY); V->bmax.assign(n_blocks, -INFINITY); V->bnan.assign(n_blocks, 0);
+  V->vmin = INFINITY; V->vmax = -INFINITY;
+  const size_t nx = counts[0], ny = counts[1], nz = counts[2];
+  for (size_t z = 0; z < nz; z++) {
+    const size_t bz0 = z ? (z - 1) / 8 : 0, bz1 = std::min(z / 8, (size_t)V->nb[2] - 1);
+    for (size_t y = 0; y < ny; y++) {
+      const size_t by0 = y ? (y - 1) / 8 : 0, by1 = std::min(y / 8, (size_t)V->nb[1] - 1);
+      for (size_t x = 0; x < nx; x++) {
+        const size_t bx0 = x ? (x - 1) / 8 : 0, bx1 = std::min(x / 8, (size_t)V->nb[0] - 1);
+        const float v = h[(z * ny + y) * nx + x];
+        const bool nan = v != v;
+        if (!nan) { V->vmin = std::min(V->vmin, v); V->vmax = std::max(V->vmax, v); }
+        for (size_t bz = bz0; bz <= bz1; bz++)
+          for (size_t by = by0; by <= by1; by++)
+            for (size_t bx = bx0; bx <= bx1; bx++) {
+              const size_t b = (bz * V->nb[1] + by) * V->nb[0] + bx;
+              if (nan) V->bnan[b] = 1;
+              else { V->bmin[b] = std::min(V->bmin[b], v); V->bmax[b] = std::max(V->bmax[b], v); }
+            }
+      }
+    }
+  }
+  return V;
+}
+
+extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
+  if (!V) return;
+  if (gctx().ready) hipStreamSynchronize(gctx().stream);
+  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_stats);
+  delete V;
+}
+
+extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap, int nc, const float *omap, int no, float value_lo, float value_hi) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !cmap || !omap) { set_error("volume_set_transfer: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (nc < 2 || no < 2) { set_error("volume_set_transfer: a map needs at least 2 entries (colour %d, opacity %d)", nc, no); return GVT_HIP_ERR_INVALID; }
+  if (!(value_lo < value_hi) || !std::isfinite(value_lo) || !std::isfinite(value_hi)) {
+    set_error("volume_set_transfer: value range [%g, %g] is empty", (double)value_lo, (double)value_hi);
+    return GVT_HIP_ERR_INVALID;
+  }
+  for (int i = 1; i < nc; i++)
+    if (!(cmap[4 * i] >= cmap[4 * (i - 1)])) { set_error("volume_set_transfer: colour map x decreases at entry %d", i); return GVT_HIP_ERR_INVALID; }
+  for (int i = 1; i < no; i++)
+    if (!(omap[2 * i] >= omap[2 * (i - 1)])) { set_error("volume_set_transfer: opacity map x decreases at entry %d", i); return GVT_HIP_ERR_INVALID; }
+  float col[256][3], op[256][1];
+  if (!resample<4>(cmap, nc, col) || !resample<2>(omap, no, op)) {
+    set_error("volume_set_transfer: a map resamples to a non-finite entry (a repeated x hit exactly)");
+    return GVT_HIP_ERR_INVALID;
+  }
+  std::vector<float4> tf(256);
+  for (int i = 0; i < 256; i++) {
+    const float a = (float)(1.0 - std::pow(1.0 - (double)op[i][0], 1.0 / (double)V->rate)); // opacity correction, rounded once
+    if (!std::isfinite(a)) { set_error("volume_set_transfer: opacity %g at entry %d cannot be corrected", (double)op[i][0], i); return GVT_HIP_ERR_INVALID; }
+    tf[i] = make_float4(col[i][0], col[i][1], col[i][2], a);
+  }
+  // macro-cell table: a block may be skipped when every table entry its values can reach -- one entry of margin either side for the
+  // rounding of the interpolation -- has a == 0: its samples then add exactly +0
+  const size_t nbk = V->bmin.size();
+  std::vector<uint8_t> mc(nbk);
+  const double span = (double)value_hi - (double)value_lo;
+  auto entry = [&](float v) {
+    double p = ((double)v - value_lo) / span;
+    p = p < 0 ? 0 : (p > 1 ? 1 : p);
+    return (int)std::floor(p * 255.0);
+  };
+  uint64_t empty = 0;
+  for (size_t b = 0; b < nbk; b++) {
+    int e0 = 0, e1 = 255;
+    if (V->bmin[b] <= V->bmax[b]) { e0 = V->bnan[b] ? 0 : std::max(0, entry(V->bmin[b]) - 1); e1 = std::min(255, entry(V->bmax[b]) + 2); }
+    float amax = 0.f;
+    for (int e = e0; e <= e1; e++) amax = std::max(amax, tf[e].w);
+    mc[b] = amax > 0.f ? 1 : 0;
+    empty += mc[b] ? 0 : 1;
+  }
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
+  HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(V->d_mc, mc.data(), nbk, hipMemcpyHostToDevice));
+  V->tf_lo = value_lo; V->tf_hi = value_hi; V->n_empty = empty; V->has_tf = true;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_get_info(gvt_hip_volume *V, gvt_hip_volume_info *out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !out) { set_error("volume_get_info: null"); return GVT_HIP_ERR_INVALID; }
+  unsigned long long s[2] = { 0, 0 };
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(s, V->d_stats, sizeof(s), hipMemcpyDeviceToHost));
+  gvt_hip_volume_info I{};
+  for (int a = 0; a < 3; a++) { I.box_lo[a] = V->lo[a]; I.box_hi[a] = V->hi[a]; I.blocks[a] = V->nb[a]; }
+  I.dt = V->dt; I.value_min = V->vmin; I.value_max = V->vmax;
+  I.n_blocks = V->bmin.size(); I.n_blocks_empty = V->has_tf ? V->n_empty : 0;
+  I.samples_marched = s[0]; I.samples_gathered = s[1];
+  *out = I;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_trace(gvt_hip_volume *V, const gvt_hip_ray *rays, size_t n, size_t begin, size_t end, gvt_hip_ray *rays_out, size_t cap,
+                                    size_t *n_out, const float m[16], const float minv[16]) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !n_out || !m || !minv || (n && !rays)) { set_error("volume_trace: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (end == 0) end = n;
+  if (begin > end || end > n) { set_error("volume_trace: bad range [%zu, %zu) of %zu rays", begin, end, n); return GVT_HIP_ERR_INVALID; }
+  if (!V->has_tf) { set_error("volume_trace: the volume has no transfer function (gvt_hip_volume_set_transfer)"); return GVT_HIP_ERR_INVALID; }
+  const size_t cnt = end - begin;
+  *n_out = cnt;
+  if (cnt > cap) { set_error("volume_trace: %zu rays, capacity %zu", cnt, cap); return GVT_HIP_ERR_CAPACITY; }
+  if (!cnt) return 0;
+  if (!rays_out) { set_error("volume_trace: null rays_out"); return GVT_HIP_ERR_INVALID; }
+  Ctx &C = gctx();
+  if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
+  if (!C.abi_qin || !C.abi_qout) return GVT_HIP_ERR_DEVICE;
+  gvt_hip_queue *q = C.abi_qin; // (the context's staging list of gvt_hip_trace)
+  int rc;
+  if ((rc = gvt_hip_queue_clear(q))) return rc;
+  if ((rc = gvt_hip_queue_append_flags(q, rays + begin, cnt, GVT_HIP_APPEND_KEEP_STATE))) return rc; // (bytes 64..79 pass through untouched)
+  if ((rc = volume_march(V, q, minv))) return rc;
+  size_t got = 0;
+  if ((rc = gvt_hip_queue_export(q, rays_out, cap, &got, 0))) return rc;
+  *n_out = got;
+  return gvt_hip_queue_clear(q);
+}
+
+extern "C" int gvt_hip_shuffle_volume(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!T || !q_in || (T->n && !queues)) { set_error("shuffle_volume: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (T->n > VOL_DEST_MAX) { set_error("shuffle_volume: %zu bricks, at most %d", T->n, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
+  if (from >= (int)T->n) { set_error("shuffle_volume: source %d of %zu bricks", from, T->n); return GVT_HIP_ERR_INVALID; }
+  for (size_t i = 0; i < T->n; i++)
+    if (!queues[i] || (queues[i] == q_in && (int)i != from)) { set_error("shuffle_volume: queue %zu is null or aliases q_in", i); return GVT_HIP_ERR_INVALID; }
+  return shuffle_volume_impl(T, q_in, from, queues, fb);
+}
+
+extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                                    gvt_hip_queue *const *queues, gvt_hip_fb *fb, uint64_t *adapter_calls) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!T || !cam || !fb || (n_inst && (!volumes || !m || !minv || !queues)) || T->n != n_inst) {
+    set_error("volume_frame: null or inconsistent argument");
+    return GVT_HIP_ERR_INVALID;
+  }
+  if (n_inst > VOL_DEST_MAX) { set_error("volume_frame: %zu bricks, at most %d", n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
+  for (size_t i = 0; i < n_inst; i++)
+    if (!volumes[i] || !queues[i] || !volumes[i]->has_tf) { set_error("volume_frame: brick %zu has no volume, queue or transfer function", i); return GVT_HIP_ERR_INVALID; }
+  Ctx &C = gctx();
+  if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
+  if (!C.abi_qin || !C.abi_qout) return GVT_HIP_ERR_DEVICE;
+  gvt_hip_queue *q_cam = C.abi_qout; // (a staging list of the context: the camera's rays before they are distributed)
+  int rc;
+  if ((rc = gvt_hip_fb_clear(fb))) return rc;                                                  // clearBuffer :142
+  for (size_t i = 0; i < n_inst; i++) if ((rc = gvt_hip_queue_clear(queues[i]))) return rc;
+  // generateRays :137, then every camera ray into the brick it enters first.  The origins stay at the eye (gvt_hip_camera_filter would advance
+  // them into the first box): a ray keeps one sample lattice from start to end
+  if ((rc = gvt_hip_camera_generate_tiled(q_cam, cam->eye, cam->focus, cam->up, cam->fov, cam->width, cam->height, cam->samples, 0,
+                                          cam->jitter_window_size, 8))) return rc;
+  if ((rc = shuffle_volume_impl(T, q_cam, -1, queues, fb))) return rc;
+  uint64_t calls = 0;
+  for (;;) {                                                                                   // :159-259
+    int target = -1;
+    size_t cnt = 0;
+    for (size_t i = 0; i < n_inst; i++)
+      if (queues[i]->size > cnt) { cnt = queues[i]->size; target = (int)i; }
+    if (target < 0) break;
+    if ((rc = volume_march(volumes[target], queues[target], minv + 16 * (size_t)target))) return rc;
+    calls++;
+    if ((rc = shuffle_volume_impl(T, queues[target], target, queues, fb))) return rc;       // shuffleRays(moved_rays, instTarget) :252
+  }
+  if (adapter_calls) *adapter_calls = calls;
+  return 0;
+}

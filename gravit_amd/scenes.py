@@ -520,3 +520,115 @@ def load_conf(path, geom_dirs=None, width=None, height=None):
     lights = np.concatenate(lights) if lights else np.zeros(0, LIGHT_DTYPE)
     return _assemble(meshes, inst_mesh, mats, np.ascontiguousarray(lights, LIGHT_DTYPE), camera,
                      "%s[%s]" % (os.path.basename(path), sched))
+
+
+# ------------------------------------------------------------------ volumes (render/data/primitives/Volume.h; data/vol/*.bov)
+@dataclass
+class VolumeData:
+    """A scalar grid: data[z, y, x] (x fastest, the BOV order), the position of vertex 0 and the vertex spacing."""
+
+    data: np.ndarray  # (nz, ny, nx) f32
+    origin: np.ndarray = field(default_factory=lambda: np.zeros(3, F))
+    spacing: np.ndarray = field(default_factory=lambda: np.ones(3, F))
+
+    @property
+    def counts(self):
+        nz, ny, nx = self.data.shape
+        return np.array([nx, ny, nz], np.int32)
+
+
+@dataclass
+class Brick:
+    """One brick of a VolumeData (gvt_hip_volume_create's arguments): the vertices [offset, offset + counts) of the global grid, and the
+    box they span in the volume's own space."""
+
+    data: np.ndarray  # (counts[2], counts[1], counts[0]) f32
+    offset: np.ndarray  # (3,) i32, x y z
+    global_counts: np.ndarray
+    origin: np.ndarray  # the GLOBAL grid's vertex 0
+    spacing: np.ndarray
+    lo: np.ndarray
+    hi: np.ndarray
+
+    @property
+    def counts(self):
+        nz, ny, nx = self.data.shape
+        return np.array([nx, ny, nz], np.int32)
+
+
+_BOV_TYPES = {"FLOAT": "f4", "DOUBLE": "f8", "INT": "i4", "UCHAR": "u1", "BYTE": "u1", "SHORT": "i2", "CHAR": "i1"}
+
+
+def read_bov(path):
+    """A Brick-Of-Values file (data/vol/*.bov): the header's keys and the data as f32 (z, y, x); FLOAT, INT and UCHAR (and their kin) are read,
+    non-float types converted on the host.  DATA_FILE is relative to the header."""
+    hdr = {}
+    for line in open(path):
+        if ":" in line:
+            k, v = line.split(":", 1)
+            hdr[k.strip().upper()] = v.strip()
+    nx, ny, nz = (int(v) for v in hdr["DATA_SIZE"].split()[:3])
+    fmt = hdr.get("DATA_FORMAT", "FLOAT").upper()
+    if fmt not in _BOV_TYPES:
+        raise ValueError("%s: unsupported DATA_FORMAT %s" % (path, fmt))
+    endian = ">" if hdr.get("DATA_ENDIAN", "LITTLE").upper().startswith("B") else "<"
+    dt = np.dtype(endian + _BOV_TYPES[fmt]) if _BOV_TYPES[fmt] != "u1" else np.dtype("u1")
+    raw = os.path.join(os.path.dirname(os.path.abspath(path)), hdr["DATA_FILE"])
+    a = np.fromfile(raw, dt, nx * ny * nz)
+    if a.size != nx * ny * nz:
+        raise ValueError("%s: %d values, the header promises %d" % (raw, a.size, nx * ny * nz))
+    origin = np.array([float(v) for v in hdr.get("BRICK_ORIGIN", "0 0 0").split()[:3]], F)
+    size = np.array([float(v) for v in hdr.get("BRICK_SIZE", "%d %d %d" % (nx - 1, ny - 1, nz - 1)).split()[:3]], F)
+    spacing = (size / np.array([nx - 1, ny - 1, nz - 1], F)).astype(F)
+    return hdr, VolumeData(np.ascontiguousarray(a.astype(F).reshape(nz, ny, nx)), origin, spacing)
+
+
+def sphere_volume(n):
+    """data/vol/sphere-like: a radial density on n^3 vertices, 1 at the centre falling linearly to 0 at half the width and beyond."""
+    c = (n - 1) / 2.0
+    x = (np.arange(n, dtype=np.float64) - c) / c
+    r = np.sqrt(x[None, None, :] ** 2 + x[None, :, None] ** 2 + x[:, None, None] ** 2)
+    return VolumeData(np.ascontiguousarray(np.clip(1.0 - r, 0.0, 1.0).astype(F)))
+
+
+def noise_volume(n, seed=0, cell=8):
+    """Smooth value noise on n^3 vertices in [0, 1]: random values on a coarse lattice (one per `cell` vertices) interpolated linearly, an
+    axis at a time (slab by slab along z, so that 512^3 fits in a few GB)."""
+    rng = np.random.default_rng(seed)
+    m = (n - 1) // cell + 2
+    coarse = rng.random((m, m, m), dtype=np.float32)
+    pos = np.arange(n, dtype=np.float64) / cell
+    i0 = np.minimum(pos.astype(np.int64), m - 2)
+    w = (pos - i0).astype(F)
+    a = coarse[:, :, i0] * (1 - w) + coarse[:, :, i0 + 1] * w        # (m, m, n)
+    a = a[:, i0, :] * (1 - w)[None, :, None] + a[:, i0 + 1, :] * w[None, :, None]  # (m, n, n)
+    out = np.empty((n, n, n), F)
+    for z in range(n):
+        out[z] = a[i0[z]] * (1 - w[z]) + a[i0[z] + 1] * w[z]
+    return VolumeData(out)
+
+
+def _cuts(n_vertices, parts):
+    cells = n_vertices - 1
+    if not 1 <= parts <= cells:
+        raise ValueError("cannot cut %d cells into %d bricks" % (cells, parts))
+    return [k * cells // parts for k in range(parts + 1)]
+
+
+def split_volume(vol, bx, by, bz):
+    """Bricks of bx * by * bz: the cells cut evenly per axis, neighbours sharing one layer of vertices; every cell is owned by exactly one
+    brick.  Order: x fastest.  Boxes in the volume's own space, computed as gvt_hip_volume_create computes them (f32)."""
+    cnt = vol.counts
+    cx, cy, cz = _cuts(int(cnt[0]), bx), _cuts(int(cnt[1]), by), _cuts(int(cnt[2]), bz)
+    org, sp = np.asarray(vol.origin, F), np.asarray(vol.spacing, F)
+    out = []
+    for k in range(bz):
+        for j in range(by):
+            for i in range(bx):
+                off = np.array([cx[i], cy[j], cz[k]], np.int32)
+                end = np.array([cx[i + 1], cy[j + 1], cz[k + 1]], np.int32)  # last vertex
+                d = np.ascontiguousarray(vol.data[off[2]:end[2] + 1, off[1]:end[1] + 1, off[0]:end[0] + 1])
+                lo = (org + off.astype(F) * sp).astype(F)
+                hi = (org + end.astype(F) * sp).astype(F)
+                out.append(Brick(d, off, cnt.copy(), org, sp, lo, hi))
+    return out

@@ -555,3 +555,57 @@ class DomainTracer:
         if self.rank != 0 or not download:
             return None
         return B.framebuffer(True).reshape(cam.height, cam.width, 4)
+
+
+class VolumeTracer:
+    """Tracer<ImageScheduler> over the bricks of one volume instance (gvt_hip_volume_frame): bricks = scenes.split_volume(...) (or one
+    VolumeData), m = the instance's matrix (None: identity).  The world box of a brick is its box under m (scenes.instance_bbox)."""
+
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True):
+        import ctypes as C
+
+        from .adapter import HipVolumeAdapter
+        from .scenes import instance_bbox, instance_matrices, mat_translate_scale
+
+        bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
+        self.camera = camera
+        self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
+        self.minv = instance_matrices(self.m)[0]
+        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip) for b in bricks]
+        for a in self.adapters:
+            a.set_transfer(tf)
+        boxes = []
+        for b in bricks:
+            lo = b.lo if hasattr(b, "lo") else np.asarray(b.origin, np.float32)
+            hi = b.hi if hasattr(b, "hi") else (np.asarray(b.origin, np.float32) + (b.counts - 1).astype(np.float32) * np.asarray(b.spacing, np.float32)).astype(np.float32)
+            boxes.append(instance_bbox(self.m, lo, hi))
+        self.inst_lo = np.array([b[0] for b in boxes], np.float32)
+        self.inst_hi = np.array([b[1] for b in boxes], np.float32)
+        self.n_inst = len(bricks)
+        self.top = TopLevel(self.inst_lo, self.inst_hi)
+        self.queues = [RayQueue() for _ in range(self.n_inst)]
+        self.fb = FrameBuffer(camera.width, camera.height)
+        self.calls = 0
+        self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
+
+    def frame(self):
+        import ctypes as C
+
+        cam = self.camera
+        pod = capi.CameraPod((C.c_float * 3)(*cam.eye), (C.c_float * 3)(*cam.focus), (C.c_float * 3)(*cam.up), cam.fov, cam.width, cam.height,
+                             cam.samples, cam.depth, cam.jitter)
+        m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
+        minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
+        calls = C.c_uint64(0)
+        capi.check(capi.load().gvt_hip_volume_frame(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                    C.byref(pod), self._arr(self.queues), self.fb.h, C.byref(calls)), "gvt_hip_volume_frame")
+        self.calls = calls.value
+        return self
+
+    def framebuffer(self, clamp=False):
+        return self.fb.download(clamp)
+
+    def stats(self):
+        infos = [a.info() for a in self.adapters]
+        return {"adapter_calls": self.calls, "samples_marched": sum(i["samples_marched"] for i in infos),
+                "samples_gathered": sum(i["samples_gathered"] for i in infos)}

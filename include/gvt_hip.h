@@ -324,6 +324,63 @@ typedef struct gvt_hip_frame_stats {
  * (Domain) the composite: the sum of the ranks' float framebuffers on rank 0 (IceTComposite.cpp:84-101).  Collective under a comm. */
 int gvt_hip_tracer_frame(gvt_hip_tracer *, int flags, gvt_hip_frame_stats *stats);
 
+/* ---- volume domains: Volume + TransferFunction (render/data/primitives/Volume.h, TransferFunction.{h,cpp}), the volume adapters'
+ *      trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp) and the volume branch of shuffleRays
+ *      (algorithm/TracerBase.h:344-391) ----
+ * A volume is one brick of a global scalar grid of global_counts vertices, x fastest (BOV order).  `origin` is the position of the GLOBAL
+ * grid's vertex 0 and `spacing` its vertex spacing, in the volume's own (object) space; `offset` is the brick's first vertex in global indices
+ * and the brick owns the cells [offset, offset + counts - 1) per axis, so neighbouring bricks share one layer of vertices.  A whole volume is
+ * the brick with offset 0 and counts = global_counts.
+ * Samples lie on ONE lattice per ray: t_k = k * dt from the ray's origin, which stays fixed, with dt = min(spacing) / sampling_rate; t is the
+ * ray's own parameter (object space = minv * world, the direction not normalised, so t means the same in both).  A sample belongs to the brick
+ * that owns its global cell floor((p - origin) / spacing), whatever the bricking.  Per sample, in this order: trilinear interpolation of the
+ * cell's 8 vertices; the 256-entry table at clamp((v - lo) / (hi - lo), 0, 1) * 255, linear between two entries; front-to-back compositing
+ * f = (1 - A) * a, C += f * c, A += f.  The ray carries its state: color = the premultiplied C, w = A, t_min = t of the last lattice sample
+ * marched (the next brick goes on after it), depth = the flags.  A ray stops with GVT_HIP_RAY_OPAQUE once A >= GVT_HIP_VOLUME_OPAQUE_A, else
+ * it leaves the brick with GVT_HIP_RAY_BOUNDARY.  A visit of one brick walks at most 2^22 lattice positions. */
+#define GVT_HIP_RAY_OPAQUE 0x2            /* actor/ORays.h */
+#define GVT_HIP_RAY_BOUNDARY 0x4
+#define GVT_HIP_RAY_EXTERNAL_BOUNDARY 0x10
+#define GVT_HIP_VOLUME_OPAQUE_A 0.99f     /* early ray termination */
+#define GVT_HIP_VOLUME_DEVICE 1           /* create: `samples` is device memory (default: host) */
+#define GVT_HIP_VOLUME_NO_SKIP 2          /* create: interpolate every sample (no macro-cell skipping; the results are the same bits) */
+typedef struct gvt_hip_volume gvt_hip_volume;
+gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int counts[3], const float origin[3], const float spacing[3], const int offset[3],
+                                      const int global_counts[3], float sampling_rate, int flags);
+void gvt_hip_volume_destroy(gvt_hip_volume *);
+typedef struct gvt_hip_volume_info {
+  float box_lo[3], box_hi[3]; /* the brick's vertices in the volume's own space */
+  float dt;                   /* lattice step */
+  float value_min, value_max; /* range of the brick's samples */
+  int32_t blocks[3];          /* macro cells (8^3 cells each) per axis */
+  float pad;
+  uint64_t n_blocks, n_blocks_empty; /* macro cells, and those whose table maximum (corrected opacity over the block's value range) is 0 */
+  uint64_t samples_marched;   /* lattice samples the brick owned along the rays marched so far, skipped ones included */
+  uint64_t samples_gathered;  /* ... of which were interpolated (8 voxel reads each); the others lay in empty macro cells */
+} gvt_hip_volume_info;
+int gvt_hip_volume_get_info(gvt_hip_volume *, gvt_hip_volume_info *); /* synchronises */
+/* TransferFunction: cmap rows (x r g b), omap rows (x a), each resampled to 256 entries as TransferFunction::DeviceCommit does
+ * (TransferFunction.cpp:40-72); the opacity corrected on the host, a' = 1 - (1 - a)^(1 / sampling_rate) in double; the macro-cell table
+ * rebuilt.  [value_lo, value_hi] maps onto the table.  At least 2 rows each, x not decreasing, value_lo < value_hi. */
+int gvt_hip_volume_set_transfer(gvt_hip_volume *, const float *cmap, int nc, const float *omap, int no, float value_lo, float value_hi);
+/* OSPRayAdapter::trace on a host RayVector: rays[begin, end) (end == 0: n) are marched through the brick (m is the instance's matrix, minv
+ * its inverse; the march needs minv only) and every one of them comes back in rays_out with its flags and state.  cap too small:
+ * GVT_HIP_ERR_CAPACITY, *n_out = the count needed, nothing marched. */
+int gvt_hip_volume_trace(gvt_hip_volume *, const gvt_hip_ray *rays, size_t n, size_t begin, size_t end, gvt_hip_ray *rays_out, size_t cap,
+                         size_t *n_out, const float m[16], const float minv[16]);
+/* shuffleRays, volume branch, PRIMARY rays (TracerBase.h:344-391), order-preserving; consumes q_in (which may be queues[from]).
+ * from >= 0: a RAY_OPAQUE ray deposits; a RAY_BOUNDARY ray goes on to the next brick -- the nearest box (entry distance, ties in the top's
+ * order) other than `from` whose exit lies beyond the exit of box `from` -- with the flag cleared, or, with none, becomes EXTERNAL and
+ * deposits.  from < 0 (camera rays): every ray goes to the nearest box whose exit lies beyond its t_min, starting with C = 0, A = 0 and
+ * depth 0; a ray that meets none is dropped.  A deposit adds (color, w) = (C, A) to the pixel: the colour is already premultiplied (the
+ * reference adds color * w); deposits are float atomics, so the sums are bit-reproducible only with one ray per pixel.  At most 256 bricks. */
+int gvt_hip_shuffle_volume(gvt_hip_top *, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb);
+/* Tracer<ImageScheduler> over volume bricks: clearBuffer, the camera's rays into the brick each enters first (gvt_hip_shuffle_volume, from
+ * -1), then until every queue is empty: march the fullest queue (first strictly largest), shuffle.  One host wait per round;
+ * *adapter_calls = the marches. */
+int gvt_hip_volume_frame(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m /* n_inst*16 */, const float *minv, size_t n_inst,
+                         const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, uint64_t *adapter_calls);
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

@@ -1,0 +1,93 @@
+"""Volume frame timing (not bench.py): a 1080p frame of scenes.noise_volume at 256^3 and 512^3, as one brick and as 8 bricks, through
+gvt_hip_volume_frame.  Reports ms per frame (host clock around frames that end in a synchronisation), lattice samples per second, and the
+voxel bytes per sample by the algorithmic count (8 reads of 4 bytes per interpolated sample, none for samples in skipped macro cells).
+Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (k_volume_march); counters in a run of their own.
+
+  python tools/volume_bench.py [--sizes 256 512] [--steps 10] [--warmup 2] [--json OUT]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from gravit_amd import _build, capi, scenes  # noqa: E402
+from gravit_amd.adapter import TransferFunction  # noqa: E402
+from gravit_amd.scheduler import VolumeTracer  # noqa: E402
+
+F = np.float32
+CMAPS = os.path.join(ROOT, "tests", "golden", "colormaps")
+
+
+def transfer(kind):
+    """"thin": opacity rising linearly to 0.03 -- rays cross the whole grid, every sample is interpolated; "spikes": GraviT's
+    fivespikes.omap -- opaque only around 0.9, most macro cells skipped."""
+    rd = TransferFunction.read_map
+    cmap = rd(os.path.join(CMAPS, "CoolWarm.cmap"), 4)
+    if kind == "thin":
+        return TransferFunction(cmap, np.array([[0.0, 0.0], [1.0, 0.03]], F), (0.0, 1.0))
+    return TransferFunction(cmap, rd(os.path.join(CMAPS, "fivespikes.omap"), 2), (0.0, 1.0))
+
+
+def camera():
+    return scenes.Camera((1.45, 1.1, 1.9), (0.5, 0.5, 0.5), (0.0, 1.0, 0.0), float(F(40.0 * np.pi / 180.0)), 1920, 1080)
+
+
+def run(n, split, steps, warmup, rate, kind):
+    vol = scenes.noise_volume(n, seed=1)
+    vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
+    t0 = time.time()
+    tr = VolumeTracer(bricks, camera(), transfer(kind), sampling_rate=rate)
+    setup = time.time() - t0
+    for _ in range(warmup):
+        tr.frame()
+    s0 = tr.stats()
+    capi.synchronize()
+    times = []
+    for _ in range(steps):
+        t = time.perf_counter()
+        tr.frame()
+        capi.synchronize()
+        times.append((time.perf_counter() - t) * 1e3)
+    s1 = tr.stats()
+    marched = (s1["samples_marched"] - s0["samples_marched"]) / steps
+    gathered = (s1["samples_gathered"] - s0["samples_gathered"]) / steps
+    ms = float(np.median(times))
+    fb = tr.framebuffer(False)
+    return {"n": n, "tf": kind, "bricks": int(np.prod(split)), "split": list(split), "sampling_rate": rate, "ms_median": round(ms, 3),
+            "ms_min": round(min(times), 3), "ms_max": round(max(times), 3), "adapter_calls": tr.calls,
+            "samples_per_frame": int(marched), "samples_interpolated": int(gathered), "gsamples_per_s": round(marched / ms / 1e6, 3),
+            "voxel_bytes_per_sample": round(32.0 * gathered / max(marched, 1), 2), "voxel_bytes_per_frame_mb": round(32.0 * gathered / 1e6, 1),
+            "lit_pixels": int((fb[..., 3] > 0).sum()), "setup_s": round(setup, 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rate", type=float, default=1.0)
+    ap.add_argument("--tf", nargs="+", default=["thin", "spikes"])
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    capi.init(0)
+    out = {"source_hash": _build.source_hash(), "width": 1920, "height": 1080, "runs": []}
+    for n in a.sizes:
+        for kind in a.tf:
+            for split in ((1, 1, 1), (2, 2, 2)):
+                r = run(n, split, a.steps, a.warmup, a.rate, kind)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
