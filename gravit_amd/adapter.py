@@ -401,10 +401,36 @@ class HipVolumeAdapter:
         capi.check(self.lib.gvt_hip_volume_set_transfer(self.h, capi.ptr(tf.cmap), len(tf.cmap), capi.ptr(tf.omap), len(tf.omap),
                                                          tf.value_range[0], tf.value_range[1]), "gvt_hip_volume_set_transfer")
 
+    def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
+        """Volume::SetIsovalues / SetSlices: isovalues, then planes (nx, ny, nz, d) in the volume's own space, rendered shaded inside the
+        march with one opacity.  Nothing given: the surfaces are cleared."""
+        iso = capi.f32(isovalues, -1)
+        pl = capi.f32(slices, -1).reshape(len(slices), 4)
+        capi.check(self.lib.gvt_hip_volume_set_surfaces(self.h, capi.ptr(iso), len(iso), capi.ptr(pl), len(pl), float(opacity)),
+                   "gvt_hip_volume_set_surfaces")
+
+    def set_lights(self, lights, ka=0.4, kd=0.6):
+        """The lights of the surfaces: a LIGHT_DTYPE array (position, color) or a sequence of (position, colour) pairs, world space;
+        directional, from the position towards the origin (OSPRayAdapter.cpp:245-295).  ka / kd: that adapter's material."""
+        if isinstance(lights, np.ndarray) and lights.dtype.names:
+            pos, col = capi.f32(lights["position"], (-1, 3)), capi.f32(lights["color"], (-1, 3))
+        else:
+            lights = list(lights)
+            pos = capi.f32([l[0] for l in lights], -1).reshape(len(lights), 3)
+            col = capi.f32([l[1] for l in lights], -1).reshape(len(lights), 3)
+        capi.check(self.lib.gvt_hip_volume_set_lights(self.h, capi.ptr(pos), capi.ptr(col), len(pos), float(ka), float(kd)),
+                   "gvt_hip_volume_set_lights")
+
     def info(self):
         i = capi.VolumeInfo()
         capi.check(self.lib.gvt_hip_volume_get_info(self.h, C.byref(i)), "gvt_hip_volume_get_info")
         return i.as_dict()
+
+    def crossings(self):
+        """Surfaces composited by this brick's marches so far."""
+        n = C.c_uint64(0)
+        capi.check(self.lib.gvt_hip_volume_get_crossings(self.h, C.byref(n)), "gvt_hip_volume_get_crossings")
+        return n.value
 
     def trace(self, rays, m, minv, begin=0, end=0):
         """OSPRayAdapter::trace: every ray of rays[begin, end) comes back marched through the brick, with its flags."""

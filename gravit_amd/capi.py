@@ -33,6 +33,7 @@ SYMBOLS = [
     "gvt_hip_tracer_create", "gvt_hip_tracer_destroy", "gvt_hip_tracer_set_camera", "gvt_hip_tracer_set_transforms", "gvt_hip_tracer_set_domains", "gvt_hip_tracer_frame",
     "gvt_hip_volume_create", "gvt_hip_volume_destroy", "gvt_hip_volume_get_info", "gvt_hip_volume_set_transfer", "gvt_hip_volume_trace",
     "gvt_hip_shuffle_volume", "gvt_hip_volume_frame",
+    "gvt_hip_volume_set_surfaces", "gvt_hip_volume_set_lights", "gvt_hip_volume_get_crossings",
 ]
 
 
@@ -72,6 +73,8 @@ class VolumeInfo(C.Structure):
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10
+RAY_SIDES = 0x20  # the ray's t field holds the surface sides of the sample in t_min
+VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
 
@@ -105,6 +108,8 @@ def load():
         lib.gvt_hip_last_error.restype = C.c_char_p
         lib.gvt_hip_volume_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
         lib.gvt_hip_volume_set_transfer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float]
+        lib.gvt_hip_volume_set_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]
+        lib.gvt_hip_volume_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
         for f in ("gvt_hip_mesh_create", "gvt_hip_queue_create", "gvt_hip_top_create", "gvt_hip_fb_create", "gvt_hip_fb_device_ptr", "gvt_hip_ctx_create",

@@ -26,7 +26,14 @@ struct gvt_hip_volume {
   float *d_vox = nullptr;
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
   uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
-  unsigned long long *d_stats = nullptr; // samples marched, samples gathered
+  unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered
+  // surfaces (gvt_hip_volume_set_surfaces / _set_lights): with n_iso + n_pl > 0 the march is k_volume_march_surf
+  int n_iso = 0, n_pl = 0, n_lights = 0;
+  float iso[GVT_HIP_VOLUME_MAX_SURFACES] = {}, plane[GVT_HIP_VOLUME_MAX_SURFACES][4] = {};
+  float surf_alpha = 1.f, ka = 0.4f, kd = 0.6f;
+  float lpos[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {}, lcol[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {};
+  std::vector<uint8_t> h_mc;     // host copy of d_mc
+  uint32_t *d_cells = nullptr;   // per macro cell, for the surface march: skip bit and isovalue sides (rebuilt by set_transfer and set_surfaces)
 };
 
 namespace {
@@ -216,6 +223,241 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes 
   if (lane_id() == 0 && n_marched) { atomicAdd(&stats[0], n_marched); atomicAdd(&stats[1], n_gathered); }
 }
 
+// ---- surfaces in the march: isovalues and slice planes, shaded (the contract: include/gvt_hip.h; tests/volume_surface_checker.py).
+// The table is wave-uniform and travels by value (kernel arguments, read with scalar loads); per lane the march adds the side mask of
+// the previous sample, the lattice index the carried mask belongs to and, at a crossing only, the gradient.
+struct SurfDev {
+  float iso[GVT_HIP_VOLUME_MAX_SURFACES];
+  float4 plane[GVT_HIP_VOLUME_MAX_SURFACES];                                // (nx, ny, nz, d), object space; bit n_iso + j
+  float ldir[GVT_HIP_VOLUME_MAX_LIGHTS][3], lcol[GVT_HIP_VOLUME_MAX_LIGHTS][3]; // unit directions in object space, colours
+  const uint32_t *cells; // per macro cell: bit 16 = its samples may go uninterpolated, bits 0..15 = their isovalue sides
+  int n_iso, n_pl, n_lights;
+  float alpha, ka, kd;
+};
+#define VOL_CELL_SKIP 0x10000u
+
+__device__ inline void vol_point(const VolDev &V, const float o[3], const float d[3], int k, float p[3]) {
+  const float t = (float)k * V.dt;
+  p[0] = o[0] + d[0] * t; p[1] = o[1] + d[1] * t; p[2] = o[2] + d[2] * t;
+}
+
+__device__ inline unsigned surf_plane_sides(const SurfDev &S, const float p[3]) {
+  unsigned m = 0u;
+  for (int j = 0; j < S.n_pl; j++) {
+    const float4 P = S.plane[j];
+    if ((P.x * p[0] + P.y * p[1]) + P.z * p[2] >= P.w) m |= 1u << (S.n_iso + j);
+  }
+  return m;
+}
+
+// May the samples k+1 .. kj of a ray go unvisited as far as the planes are concerned?  Only if every plane's field at k and at kj has the
+// same sign and lies further from zero than twice a bound on its evaluation error (about 6 roundings of the terms below; 2^-18 leaves a
+// factor 8): the exact field is linear in t, so every sample between them then evaluates to the same side.
+__device__ inline bool surf_planes_clear(const VolDev &V, const SurfDev &S, const float o[3], const float d[3], int k, int kj) {
+  float pa[3], pb[3];
+  vol_point(V, o, d, k, pa);
+  vol_point(V, o, d, kj, pb);
+  const float T = (float)kj * V.dt;
+  const float ext[3] = { fabsf(o[0]) + fabsf(d[0]) * T, fabsf(o[1]) + fabsf(d[1]) * T, fabsf(o[2]) + fabsf(d[2]) * T };
+  bool clear = true;
+  for (int j = 0; j < S.n_pl; j++) {
+    const float4 P = S.plane[j];
+    const float ma = ((P.x * pa[0] + P.y * pa[1]) + P.z * pa[2]) - P.w, mb = ((P.x * pb[0] + P.y * pb[1]) + P.z * pb[2]) - P.w;
+    const float e2 = (((fabsf(P.x) * ext[0] + fabsf(P.y) * ext[1]) + fabsf(P.z) * ext[2]) + fabsf(P.w)) * (2.f / 262144.f);
+    clear = clear && ((ma > e2 && mb > e2) || (ma < -e2 && mb < -e2)); // (false for NaN)
+  }
+  return clear;
+}
+
+// the table's colour at value v: the sample's own look-up, opacity in .w
+__device__ inline float4 vol_lookup(const VolDev &V, float v) {
+  const float pos = fminf(fmaxf((v - V.vlo) / V.vspan, 0.f), 1.f) * 255.f;
+  const int i0 = min((int)pos, 254);
+  const float w = pos - (float)i0;
+  const float4 e0 = V.tf[i0], e1 = V.tf[i0 + 1];
+  return make_float4(lerp_(e0.x, e1.x, w), lerp_(e0.y, e1.y, w), lerp_(e0.z, e1.z, w), lerp_(e0.w, e1.w, w));
+}
+
+// one crossed surface of base colour c and (unnormalised) normal g, composited in front of the sample
+__device__ inline void surf_composite(const SurfDev &S, float4 c, const float g[3], float C[3], float &A) {
+  float rgb[3] = { c.x, c.y, c.z };
+  if (S.n_lights > 0) {
+    float sum[3] = { 0.f, 0.f, 0.f };
+    const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+    if (len > 0.f) { // (false for NaN)
+      const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
+      for (int j = 0; j < S.n_lights; j++) {
+        const float ndl = fabsf((n[0] * S.ldir[j][0] + n[1] * S.ldir[j][1]) + n[2] * S.ldir[j][2]);
+        for (int a = 0; a < 3; a++) sum[a] = sum[a] + S.lcol[j][a] * ndl;
+      }
+    }
+    for (int a = 0; a < 3; a++) rgb[a] = rgb[a] * (S.ka + S.kd * sum[a]);
+  }
+  const float f = (1.f - A) * S.alpha;
+  C[0] = C[0] + f * rgb[0]; C[1] = C[1] + f * rgb[1]; C[2] = C[2] + f * rgb[2];
+  A = A + f;
+}
+
+// k_volume_march with surfaces (launched only for volumes that have some): the same lanes, refill and lattice; per sample the side mask,
+// at a crossing the shaded surfaces before the sample's own contribution.  prev < 0: no previous sample.
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                 unsigned long long *__restrict__ stats) {
+  bool active = false, exhausted = false;
+  unsigned idx = 0;
+  float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
+  int k = 0, k_hi = -1, k_last = -1, k_carry = -1, prev = -1;
+  bool seen = false;
+  unsigned long long n_marched = 0, n_gathered = 0;
+  unsigned n_crossed = 0;
+  for (;;) {
+    const unsigned long long idle = ballot64(!active);
+    if (idle && !exhausted && (__popcll(idle) >= VOL_REFILL_MIN || idle == ballot64(true))) {
+      const unsigned slot = wave_alloc(work, !active);
+      if (ballot64(!active && slot >= n)) exhausted = true; // (wave-uniform)
+      if (!active && slot < n) {
+        idx = slot;
+        active = true;
+        const float4 a = q.p0[idx], b = q.p1[idx], c = q.p2[idx], e = q.p3[idx];
+        const V3 oo = xfm_point(minv, mk3(a.x, a.y, a.z)), dd = xfm_vector(minv, mk3(b.x, b.y, b.z));
+        o[0] = oo.x; o[1] = oo.y; o[2] = oo.z; d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
+        C[0] = c.x; C[1] = c.y; C[2] = c.z;
+        A = e.z;
+        float tn, tf;
+        vol_slab(V.lo, V.hi, o, d, tn, tf);
+        const int k_prog = vol_first_after(a.w, V.dt);
+        k = 0;
+        k_hi = -1;
+        if (tn <= tf && tf >= 0.f && tf < INFINITY && k_prog >= 0) {
+          const float qlo = floorf(tn / V.dt), qhi = floorf(tf / V.dt);
+          if (qlo < VOL_K_MAX) {
+            k = max(k_prog, qlo > 1.f ? (int)qlo - 1 : 0);
+            k_hi = qhi < VOL_K_MAX ? (int)qhi + 1 : (int)VOL_K_MAX;
+            k_hi = min(k_hi, k + VOL_MAX_SAMPLES);
+          }
+        }
+        k_last = -1;
+        seen = false;
+        // the sides of the sample in t_min count only for the sample right after it
+        const bool carried = (__float_as_int(e.y) & GVT_HIP_RAY_SIDES) != 0;
+        prev = carried ? ((int)c.w & 0xffff) : -1;
+        k_carry = carried ? k_prog : -1;
+      }
+    }
+    if (!ballot64(active)) break;
+    if (active) {
+      bool done = false;
+      for (int s = 0; s < VOL_STEP; s++) {
+        if (k > k_hi) { done = true; break; }
+        int c[3];
+        float f[3];
+        if (!vol_cell(V, o, d, k, c, f)) {
+          if (seen) { done = true; break; }
+          k++;
+          continue;
+        }
+        if (!seen && k != k_carry) prev = -1;
+        seen = true;
+        k_last = k;
+        n_marched++;
+        float p[3];
+        vol_point(V, o, d, k, p);
+        const unsigned pl = surf_plane_sides(S, p);
+        const int bi = ((c[2] >> 3) * V.nby + (c[1] >> 3)) * V.nbx + (c[0] >> 3);
+        const unsigned cell = V.skip ? S.cells[bi] : 0u;
+        if ((cell & VOL_CELL_SKIP) && (prev < 0 || prev == (int)((cell & 0xffffu) | pl))) {
+          // nothing to composite here and no crossing: the sample goes uninterpolated, and so do those after it in this macro cell
+          // as long as no plane can change sides among them (the isovalue sides are the cell's)
+          prev = (int)((cell & 0xffffu) | pl);
+          const int cb[3] = { c[0] >> 3, c[1] >> 3, c[2] >> 3 };
+          const int off[3] = { V.ox, V.oy, V.oz }, nn[3] = { V.nx, V.ny, V.nz };
+          const float go[3] = { V.gox, V.goy, V.goz }, sp[3] = { V.sx, V.sy, V.sz };
+          float te = INFINITY;
+          for (int a = 0; a < 3; a++) {
+            if (d[a] == 0.f) continue;
+            const int gv = d[a] > 0.f ? off[a] + min(8 * cb[a] + 8, nn[a] - 1) : off[a] + 8 * cb[a];
+            te = fminf(te, ((go[a] + (float)gv * sp[a]) - o[a]) / d[a]);
+          }
+          const float qj = floorf(te / V.dt);
+          if (qj < VOL_K_MAX && qj > (float)(k + 1)) {
+            const int kj = min((int)qj, k_hi);
+            int cj[3];
+            float fj[3];
+            if (kj > k + 1 && vol_cell(V, o, d, kj, cj, fj) && (cj[0] >> 3) == cb[0] && (cj[1] >> 3) == cb[1] && (cj[2] >> 3) == cb[2] &&
+                surf_planes_clear(V, S, o, d, k, kj)) {
+              n_marched += (unsigned long long)(kj - k);
+              k_last = kj;
+              k = kj;
+            }
+          }
+          k++;
+          continue;
+        }
+        n_gathered++;
+        const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny;
+        const float *vp = V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
+        const float v000 = vp[0], v100 = vp[1], v010 = vp[sy], v110 = vp[sy + 1];
+        const float v001 = vp[sz], v101 = vp[sz + 1], v011 = vp[sz + sy], v111 = vp[sz + sy + 1];
+        const float c00 = lerp_(v000, v100, f[0]), c10 = lerp_(v010, v110, f[0]);
+        const float c01 = lerp_(v001, v101, f[0]), c11 = lerp_(v011, v111, f[0]);
+        const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
+        const float v = lerp_(c0, c1, f[2]);
+        unsigned sides = pl;
+        for (int i = 0; i < S.n_iso; i++)
+          if (v >= S.iso[i]) sides |= 1u << i;
+        unsigned crossed = prev < 0 ? 0u : (sides ^ (unsigned)prev);
+        prev = (int)sides;
+        if (crossed) {
+          while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+            const int i = __ffs((int)crossed) - 1;
+            crossed &= crossed - 1u;
+            n_crossed++;
+            if (i < S.n_iso) {
+              const float g[3] = { lerp_(lerp_(v100 - v000, v110 - v010, f[1]), lerp_(v101 - v001, v111 - v011, f[1]), f[2]) / V.sx,
+                                   lerp_(lerp_(v010 - v000, v110 - v100, f[0]), lerp_(v011 - v001, v111 - v101, f[0]), f[2]) / V.sy,
+                                   lerp_(lerp_(v001 - v000, v101 - v100, f[0]), lerp_(v011 - v010, v111 - v110, f[0]), f[1]) / V.sz };
+              surf_composite(S, vol_lookup(V, S.iso[i]), g, C, A);
+            } else {
+              const float4 P = S.plane[i - S.n_iso];
+              const float g[3] = { P.x, P.y, P.z };
+              surf_composite(S, vol_lookup(V, v), g, C, A);
+            }
+          }
+          if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
+        }
+        const float4 tc = vol_lookup(V, v);
+        const float fr = (1.f - A) * tc.w;
+        C[0] = C[0] + fr * tc.x; C[1] = C[1] + fr * tc.y; C[2] = C[2] + fr * tc.z;
+        A = A + fr;
+        k++;
+        if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
+      }
+      if (done) {
+        float4 a = q.p0[idx];
+        float4 cc = q.p2[idx], e = q.p3[idx];
+        int flag = A >= GVT_HIP_VOLUME_OPAQUE_A ? GVT_HIP_RAY_OPAQUE : GVT_HIP_RAY_BOUNDARY;
+        if (k_last >= 0) { // (prev = the sides of sample k_last)
+          a.w = (float)k_last * V.dt;
+          cc.w = (float)prev;
+          flag |= GVT_HIP_RAY_SIDES;
+        }
+        q.p0[idx] = a;
+        q.p2[idx] = make_float4(C[0], C[1], C[2], cc.w);
+        e.y = __int_as_float(__float_as_int(e.y) | flag);
+        e.z = A;
+        q.p3[idx] = e;
+        active = false;
+      }
+    }
+  }
+  unsigned long long n_cr = n_crossed;
+  for (int s = 32; s >= 1; s >>= 1) {
+    n_marched += __shfl_xor(n_marched, s);
+    n_gathered += __shfl_xor(n_gathered, s);
+    n_cr += __shfl_xor(n_cr, s);
+  }
+  if (lane_id() == 0 && n_marched) { atomicAdd(&stats[0], n_marched); atomicAdd(&stats[1], n_gathered); if (n_cr) atomicAdd(&stats[2], n_cr); }
+}
+
 // ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
 // its first slot, so the queues keep the order of the list they were filled from.
 __device__ inline int vol_next(const TopDev &T, int from, const float o[3], const float d[3], float t_min) {
@@ -354,6 +596,48 @@ VolDev vol_dev(const gvt_hip_volume *Vh) {
   return V;
 }
 
+// the surface march's by-value block.  The lights' directions are computed here, on the host, in float32: -position as a vector through
+// minv (xfm_vector's order), divided by its length sqrt((x*x + y*y) + z*z); a light whose length is 0 or not finite shines from nowhere (0)
+SurfDev surf_dev(const gvt_hip_volume *Vh, const Mat4 &minv) {
+  SurfDev S{};
+  S.n_iso = Vh->n_iso; S.n_pl = Vh->n_pl; S.n_lights = Vh->n_lights;
+  S.alpha = Vh->surf_alpha; S.ka = Vh->ka; S.kd = Vh->kd;
+  S.cells = Vh->d_cells;
+  for (int i = 0; i < Vh->n_iso; i++) S.iso[i] = Vh->iso[i];
+  for (int i = 0; i < Vh->n_pl; i++) S.plane[i] = make_float4(Vh->plane[i][0], Vh->plane[i][1], Vh->plane[i][2], Vh->plane[i][3]);
+  for (int j = 0; j < Vh->n_lights; j++) {
+    const V3 l = xfm_vector(minv, mk3(-Vh->lpos[j][0], -Vh->lpos[j][1], -Vh->lpos[j][2]));
+    const float len = sqrtf((l.x * l.x + l.y * l.y) + l.z * l.z);
+    const bool ok = len > 0.f && std::isfinite(len);
+    S.ldir[j][0] = ok ? l.x / len : 0.f; S.ldir[j][1] = ok ? l.y / len : 0.f; S.ldir[j][2] = ok ? l.z / len : 0.f;
+    for (int a = 0; a < 3; a++) S.lcol[j][a] = Vh->lcol[j][a];
+  }
+  return S;
+}
+
+// the surface march's per-cell words: a macro cell's samples may go uninterpolated when the transfer function leaves it empty (h_mc) and
+// no isovalue lies within its value range widened by 2^-18 of its magnitude (the trilinear interpolant's rounding stays far inside: three
+// nested lerps are off by a few 2^-24 of the largest vertex); the word then carries the isovalue sides all its samples have
+int upload_cells(gvt_hip_volume *V) {
+  const size_t nbk = V->bmin.size();
+  std::vector<uint32_t> cells(nbk, 0u);
+  if (V->has_tf)
+    for (size_t b = 0; b < nbk; b++) {
+      if (V->h_mc[b] || (V->n_iso && (V->bnan[b] || !(V->bmin[b] <= V->bmax[b])))) continue;
+      const double lo = V->bmin[b], hi = V->bmax[b], mg = std::max(std::fabs(lo), std::fabs(hi)) / 262144.0 + 1e-37;
+      uint32_t w = VOL_CELL_SKIP;
+      for (int i = 0; i < V->n_iso; i++) {
+        const double c = V->iso[i];
+        if (c < lo - mg) w |= 1u << i;        // every sample >= c
+        else if (!(c > hi + mg)) { w = 0u; break; }
+      }
+      cells[b] = w;
+    }
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the table)
+  HIPCHK(hipMemcpy(V->d_cells, cells.data(), sizeof(uint32_t) * nbk, hipMemcpyHostToDevice));
+  return 0;
+}
+
 // the march of q's rays through brick Vh, in place, on the context's stream (no host wait)
 int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
   if (!q->size) return 0;
@@ -364,7 +648,10 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = minv[k];
   const unsigned blocks = std::min(blocks_of(q->size), (unsigned)(std::max(C.n_cu, 1) * 8));
-  k_volume_march<<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+  if (Vh->n_iso + Vh->n_pl > 0)
+    k_volume_march_surf<<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+  else
+    k_volume_march<<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -487,8 +774,9 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int
   std::vector<float> host;
   const float *h = samples;
   bool ok = hipMalloc((void **)&V->d_vox, sizeof(float) * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
-            hipMalloc((void **)&V->d_stats, 2 * sizeof(unsigned long long)) == hipSuccess &&
-            hipMemset(V->d_stats, 0, 2 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess;
+            hipMalloc((void **)&V->d_stats, 3 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMemset(V->d_stats, 0, 3 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
+            hipMalloc((void **)&V->d_cells, sizeof(uint32_t) * n_blocks) == hipSuccess;
   if (ok && (flags & GVT_HIP_VOLUME_DEVICE)) {
     host.resize(total);
     ok = hipMemcpy(host.data(), samples, sizeof(float) * total, hipMemcpyDeviceToHost) == hipSuccess &&
@@ -528,7 +816,7 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int
 extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
-  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_stats);
+  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats);
   delete V;
 }
 
@@ -578,6 +866,52 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(V->d_mc, mc.data(), nbk, hipMemcpyHostToDevice));
   V->tf_lo = value_lo; V->tf_hi = value_hi; V->n_empty = empty; V->has_tf = true;
+  V->h_mc.swap(mc);
+  return upload_cells(V);
+}
+
+extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isovalues, int n_iso, const float *slices, int n_slices, float opacity) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || (n_iso > 0 && !isovalues) || (n_slices > 0 && !slices)) { set_error("volume_set_surfaces: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (n_iso < 0 || n_slices < 0 || n_iso > GVT_HIP_VOLUME_MAX_SURFACES || n_slices > GVT_HIP_VOLUME_MAX_SURFACES || n_iso + n_slices > GVT_HIP_VOLUME_MAX_SURFACES) {
+    set_error("volume_set_surfaces: %d isovalues and %d slices, at most %d surfaces", n_iso, n_slices, GVT_HIP_VOLUME_MAX_SURFACES);
+    return GVT_HIP_ERR_INVALID;
+  }
+  if (!(opacity > 0.f && opacity <= 1.f)) { set_error("volume_set_surfaces: opacity %g is not in (0, 1]", (double)opacity); return GVT_HIP_ERR_INVALID; }
+  for (int i = 0; i < n_iso; i++)
+    if (isovalues[i] != isovalues[i]) { set_error("volume_set_surfaces: isovalue %d is NaN", i); return GVT_HIP_ERR_INVALID; }
+  for (int i = 0; i < n_slices; i++) {
+    const float *p = slices + 4 * i;
+    const bool finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]);
+    if (!finite || (p[0] == 0.f && p[1] == 0.f && p[2] == 0.f)) { set_error("volume_set_surfaces: slice %d has a zero or non-finite plane", i); return GVT_HIP_ERR_INVALID; }
+  }
+  V->n_iso = n_iso; V->n_pl = n_slices; V->surf_alpha = opacity;
+  for (int i = 0; i < n_iso; i++) V->iso[i] = isovalues[i];
+  for (int i = 0; i < n_slices; i++)
+    for (int a = 0; a < 4; a++) V->plane[i][a] = slices[4 * i + a];
+  return V->has_tf ? upload_cells(V) : 0;
+}
+
+extern "C" int gvt_hip_volume_set_lights(gvt_hip_volume *V, const float *positions, const float *colours, int n, float ka, float kd) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || (n > 0 && (!positions || !colours))) { set_error("volume_set_lights: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (n < 0 || n > GVT_HIP_VOLUME_MAX_LIGHTS) { set_error("volume_set_lights: %d lights, at most %d", n, GVT_HIP_VOLUME_MAX_LIGHTS); return GVT_HIP_ERR_INVALID; }
+  if (!std::isfinite(ka) || !std::isfinite(kd)) { set_error("volume_set_lights: ka %g, kd %g", (double)ka, (double)kd); return GVT_HIP_ERR_INVALID; }
+  for (int i = 0; i < 3 * n; i++)
+    if (!std::isfinite(positions[i]) || !std::isfinite(colours[i])) { set_error("volume_set_lights: light %d is not finite", i / 3); return GVT_HIP_ERR_INVALID; }
+  V->n_lights = n; V->ka = ka; V->kd = kd;
+  for (int j = 0; j < n; j++)
+    for (int a = 0; a < 3; a++) { V->lpos[j][a] = positions[3 * j + a]; V->lcol[j][a] = colours[3 * j + a]; }
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_get_crossings(gvt_hip_volume *V, uint64_t *crossings_rendered) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !crossings_rendered) { set_error("volume_get_crossings: null"); return GVT_HIP_ERR_INVALID; }
+  unsigned long long s = 0;
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(&s, V->d_stats + 2, sizeof(s), hipMemcpyDeviceToHost));
+  *crossings_rendered = s;
   return 0;
 }
 

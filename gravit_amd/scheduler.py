@@ -602,10 +602,21 @@ class VolumeTracer:
         self.calls = calls.value
         return self
 
+    def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
+        """The volume's isosurfaces and slice planes (object space), on every brick."""
+        for a in self.adapters:
+            a.set_surfaces(isovalues, slices, opacity)
+        return self
+
+    def set_lights(self, lights, ka=0.4, kd=0.6):
+        for a in self.adapters:
+            a.set_lights(lights, ka, kd)
+        return self
+
     def framebuffer(self, clamp=False):
         return self.fb.download(clamp)
 
     def stats(self):
         infos = [a.info() for a in self.adapters]
-        return {"adapter_calls": self.calls, "samples_marched": sum(i["samples_marched"] for i in infos),
+        return {"adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
                 "samples_gathered": sum(i["samples_gathered"] for i in infos)}

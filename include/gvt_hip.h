@@ -381,6 +381,50 @@ int gvt_hip_shuffle_volume(gvt_hip_top *, gvt_hip_queue *q_in, int from, gvt_hip
 int gvt_hip_volume_frame(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m /* n_inst*16 */, const float *minv, size_t n_inst,
                          const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, uint64_t *adapter_calls);
 
+/* ---- surfaces of a volume: Volume::SetIsovalues / SetSlices (Volume.h:96-100,128-132) as OSPRayAdapter hands them to its renderer
+ *      (OSPRayAdapter.cpp:70-86), with the lights that exist only for them (:245-295) ----
+ * Up to GVT_HIP_VOLUME_MAX_SURFACES surfaces, indexed i: the n_iso isovalues in the order given, then the n_slices planes (nx, ny, nz, d),
+ * object space.  Each is the zero set of a field sampled at the ray's lattice positions p_k = o + (k * dt) * d (per axis o + d * t with
+ * t = (float)k * dt, as the march's own position):
+ *   isovalue c_i: side_i(k) = (v_k >= c_i), v_k the sample's trilinear value;  plane: side_i(k) = ((nx*p.x + ny*p.y) + nz*p.z >= d).
+ * A comparison with NaN is false.  sides(k) = the mask of those bits (bit i = surface i).
+ * A CROSSING of surface i is detected AT sample k when the brick owns k, the ray marched k - 1, and side_i(k) != side_i(k - 1).  "Marched":
+ * earlier in this visit, or k - 1 is the sample in the ray's t_min and the ray carries its sides: the flag GVT_HIP_RAY_SIDES in depth, and
+ * sides(k - 1) as a float in the ray's t field (bytes 44..47; an integer in [0, 65535]).  The carried sides count only if the brick's first
+ * owned sample is exactly the first lattice sample after t_min; otherwise (no flag: camera rays, whose depth the shuffle from -1 zeroes; a
+ * gap between bricks) the first owned sample has no previous one and detects nothing.  A surface is thus rendered at the sample after it, at
+ * most one lattice step behind: everything that shades it belongs to the brick that owns that sample, so the bricking cannot change the image.
+ * A march that owned a sample writes sides(last sample) into t and sets the flag; one that owned none leaves t and the flag as they came.
+ * RENDERING at sample k, before the sample's own contribution, if any surface is crossed: for each crossed surface in index order while
+ * A < GVT_HIP_VOLUME_OPAQUE_A:
+ *   c = the table's rgb (the sample's look-up, opacity ignored) at c_i for an isovalue, at v_k for a plane;
+ *   g = for a plane (nx, ny, nz); for an isovalue the gradient of the trilinear interpolant in the sample's cell, with lerp(a, b, f) =
+ *       a + f * (b - a) and f the sample's fractions:
+ *         g.x = lerp(lerp(v100 - v000, v110 - v010, f.y), lerp(v101 - v001, v111 - v011, f.y), f.z) / spacing.x
+ *         g.y = lerp(lerp(v010 - v000, v110 - v100, f.x), lerp(v011 - v001, v111 - v101, f.x), f.z) / spacing.y
+ *         g.z = lerp(lerp(v001 - v000, v101 - v100, f.x), lerp(v011 - v010, v111 - v110, f.x), f.y) / spacing.z
+ *   with lights: len = sqrt((g.x*g.x + g.y*g.y) + g.z*g.z); S = (0, 0, 0); if len > 0 (false for NaN): n = g / len and per light j in order
+ *       ndl = |(n.x*l.x + n.y*l.y) + n.z*l.z|, S = S + colour_j * ndl; rgb = c * (ka + kd * S) per channel.  Without lights: rgb = c.
+ *   f = (1 - A) * opacity; C = C + f * rgb; A = A + f.  No clamp.
+ * If A >= GVT_HIP_VOLUME_OPAQUE_A after that, the ray stops with GVT_HIP_RAY_OPAQUE and the sample's own contribution is not added; t_min
+ * records k either way.  A sample without a crossing is the plain march's.
+ * LIGHTS: GraviT's positions and colours, world space.  The direction of light j is -position_j, taken to object space as a vector
+ * through the instance's minv (m[r]*x + m[4+r]*y) + (m[8+r]*z + m[12+r]*0) and divided by its length sqrt((x*x + y*y) + z*z), on the HOST in
+ * float32 at every march (length 0 or not finite: direction 0).  This equals world-space shading for rigid motions and uniform scales only.
+ * Skipping: a macro cell is jumped only where no crossing can hide (no isovalue within its value range, no plane among the samples jumped,
+ * not at a sample whose sides differ from the previous one's); the bits are those of GVT_HIP_VOLUME_NO_SKIP, the rays' t field included. */
+#define GVT_HIP_RAY_SIDES 0x20            /* depth: the ray's t field holds sides(sample in t_min) (actor/ORays.h uses 0x1..0x10) */
+#define GVT_HIP_VOLUME_MAX_SURFACES 16
+#define GVT_HIP_VOLUME_MAX_LIGHTS 8
+/* 0 isovalues and 0 slices clear the surfaces (the plain march again).  NaN isovalue, zero or non-finite plane, opacity outside (0, 1],
+ * more than 16 surfaces: GVT_HIP_ERR_INVALID, the volume unchanged.  Rebuilds the per-cell skip table, as _set_transfer does. */
+int gvt_hip_volume_set_surfaces(gvt_hip_volume *, const float *isovalues, int n_iso, const float *slices /* n_slices*4 */, int n_slices, float opacity);
+/* n = 0: no lights (rgb = c).  More than GVT_HIP_VOLUME_MAX_LIGHTS or a non-finite value: GVT_HIP_ERR_INVALID.  The OSPRay adapter's
+ * material is ka = 0.4, kd = 0.6. */
+int gvt_hip_volume_set_lights(gvt_hip_volume *, const float *positions /* n*3 */, const float *colours /* n*3 */, int n, float ka, float kd);
+/* surfaces composited by the marches of this volume so far (gvt_hip_volume_info keeps its layout); synchronises */
+int gvt_hip_volume_get_crossings(gvt_hip_volume *, uint64_t *crossings_rendered);
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

@@ -4,6 +4,8 @@ voxel bytes per sample by the algorithmic count (8 reads of 4 bytes per interpol
 Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (k_volume_march); counters in a run of their own.
 
   python tools/volume_bench.py [--sizes 256 512] [--steps 10] [--warmup 2] [--json OUT]
+  python tools/volume_bench.py --surfaces    the "thin" frames plain, with two isovalues the field never reaches (the per-sample cost of
+                                             the side test alone) and with two it does (opacity 0.3, one light), each against the plain frame
 """
 import argparse
 import json
@@ -38,12 +40,18 @@ def camera():
     return scenes.Camera((1.45, 1.1, 1.9), (0.5, 0.5, 0.5), (0.0, 1.0, 0.0), float(F(40.0 * np.pi / 180.0)), 1920, 1080)
 
 
-def run(n, split, steps, warmup, rate, kind):
-    vol = scenes.noise_volume(n, seed=1)
-    vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
+SURFACE_MODES = {"plain": None, "never": (2.0, 3.0), "reached": (0.4, 0.6)}  # noise_volume lies in [0, 1]
+
+
+def run(n, split, steps, warmup, rate, kind, vol=None, surfaces=None):
+    if vol is None:
+        vol = scenes.noise_volume(n, seed=1)
+        vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
     bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
     t0 = time.time()
     tr = VolumeTracer(bricks, camera(), transfer(kind), sampling_rate=rate)
+    if surfaces:
+        tr.set_surfaces(surfaces, (), 0.3).set_lights([((3.0, 4.0, 5.0), (1.0, 1.0, 1.0))])
     setup = time.time() - t0
     for _ in range(warmup):
         tr.frame()
@@ -60,6 +68,10 @@ def run(n, split, steps, warmup, rate, kind):
     gathered = (s1["samples_gathered"] - s0["samples_gathered"]) / steps
     ms = float(np.median(times))
     fb = tr.framebuffer(False)
+    if surfaces:
+        return {"n": n, "tf": kind, "bricks": int(np.prod(split)), "isovalues": list(surfaces), "ms_median": round(ms, 3), "ms_min": round(min(times), 3),
+                "ms_max": round(max(times), 3), "samples_per_frame": int(marched), "samples_interpolated": int(gathered),
+                "crossings_per_frame": int((s1["crossings_rendered"] - s0["crossings_rendered"]) / steps), "lit_pixels": int((fb[..., 3] > 0).sum())}
     return {"n": n, "tf": kind, "bricks": int(np.prod(split)), "split": list(split), "sampling_rate": rate, "ms_median": round(ms, 3),
             "ms_min": round(min(times), 3), "ms_max": round(max(times), 3), "adapter_calls": tr.calls,
             "samples_per_frame": int(marched), "samples_interpolated": int(gathered), "gsamples_per_s": round(marched / ms / 1e6, 3),
@@ -75,10 +87,23 @@ def main():
     ap.add_argument("--rate", type=float, default=1.0)
     ap.add_argument("--tf", nargs="+", default=["thin", "spikes"])
     ap.add_argument("--json")
+    ap.add_argument("--surfaces", action="store_true")
     a = ap.parse_args()
     capi.init(0)
     out = {"source_hash": _build.source_hash(), "width": 1920, "height": 1080, "runs": []}
-    for n in a.sizes:
+    for n in a.sizes if a.surfaces else ():
+        vol = scenes.noise_volume(n, seed=1)
+        vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
+        for split in ((1, 1, 1), (2, 2, 2)):
+            base = None
+            for mode, iso in SURFACE_MODES.items():
+                r = run(n, split, a.steps, a.warmup, a.rate, "thin", vol, iso)
+                r["mode"] = mode
+                base = r["ms_median"] if mode == "plain" else base
+                r["vs_plain"] = round(r["ms_median"] / base, 3)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    for n in () if a.surfaces else a.sizes:
         for kind in a.tf:
             for split in ((1, 1, 1), (2, 2, 2)):
                 r = run(n, split, a.steps, a.warmup, a.rate, kind)
