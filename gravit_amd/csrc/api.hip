@@ -657,9 +657,8 @@ static int trace_pipelined(Ctx &C, gvt_hip_mesh *M, gvt_hip_ray *rays, size_t be
     LC->profile = 0;
     const gvt_hip_stats before = LC->stats;
     int rc = 0;
-    if (!LC->abi_qin) { LC->abi_qin = gvt_hip_queue_create(0); LC->abi_qout = gvt_hip_queue_create(0); }
+    if (!staging_queues(*LC)) rc = GVT_HIP_ERR_DEVICE;
     gvt_hip_queue *qin = LC->abi_qin, *qout = LC->abi_qout;
-    if (!qin || !qout) rc = GVT_HIP_ERR_DEVICE;
     while (!rc && !err.load()) {
       const size_t k = next.fetch_add(1);
       if (k >= n_chunks) break;
@@ -735,9 +734,8 @@ extern "C" int gvt_hip_trace_ex(gvt_hip_mesh *M, gvt_hip_ray *rays, size_t n_ray
     rc = trace_pipelined(C, M, rays, begin, n, rays_out, cap, n_out, P, lights, n_lights, write_back, &fell_back);
     if (!fell_back) return rc;
   }
-  if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
+  if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
   gvt_hip_queue *qin = C.abi_qin, *qout = C.abi_qout;
-  if (!qin || !qout) return GVT_HIP_ERR_DEVICE;
   if ((rc = gvt_hip_queue_clear(qin)) || (rc = gvt_hip_queue_clear(qout))) return rc;
   if ((rc = gvt_hip_queue_append_flags(qin, rays + begin, n, GVT_HIP_APPEND_KEEP_STATE))) return rc; // bytes 64..79 pass through (a forwarded ray is a copy of all 80 bytes); this path never reads them
   if ((rc = queue_reserve(qout, n * (1 + n_lights)))) return rc;

@@ -265,6 +265,21 @@ __device__ inline unsigned block_alloc(unsigned *counter, bool want, unsigned *s
   return sh[1] + woff + lanes_below(mask);
 }
 
+// The lanes of a wave grouped by destination (dest < 0: none): f(d, m, leader) runs once per distinct destination d, in the order of
+// each one's first lane, with m = the mask of d's lanes (popcount: their number, lanes_below(m): a lane's rank among them) and
+// leader = the first of them.  Reached by the whole wave; f is wave-uniform code.
+template <class F>
+__device__ __forceinline__ void wave_by_dest(int dest, F f) {
+  unsigned long long todo = ballot64(dest >= 0);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int d = __shfl(dest, leader);
+    const unsigned long long m = ballot64(dest == d);
+    f(d, m, leader);
+    todo &= ~m;
+  }
+}
+
 // ---- top-level instance test (BVH::intersect + RayPacketIntersection), shared by the shuffle kernels and k_trace's sink ----
 // RayPacket.h fastmin/fastmax: (a<b)?a:b / (a>b)?a:b
 __device__ inline float fmin_ref(float a, float b) { return (a < b) ? a : b; }

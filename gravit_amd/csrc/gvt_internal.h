@@ -129,6 +129,11 @@ struct Ctx : Knobs {
 Ctx &gctx();
 void set_error(const char *fmt, ...);
 int ensure_init();
+// the context's staging queues (abi_qin, abi_qout), created on first use; false: they could not be created
+inline bool staging_queues(Ctx &C) {
+  if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
+  return C.abi_qin && C.abi_qout;
+}
 void *scratch_get(int slot, size_t bytes); // grow-only; contents NOT preserved on growth
 void scratch_release(int slot); // gives a slot's memory back (after a synchronisation of the context's stream)
 

@@ -134,16 +134,11 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_top_classify(RaySrc S, unsigned n
     next_out[i] = next;
     t_out[i] = ret_t;
   }
-  unsigned long long todo = ballot64(next >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int d = __shfl(next, leader);
-    const unsigned long long m = ballot64(next == d);
+  wave_by_dest(next, [&](int d, unsigned long long m, int leader) {
     if ((int)lane_id() == leader) {
       if (use_lds) atomicAdd(&sh_cnt[d], (unsigned)__popcll(m)); else atomicAdd(&hist[d], (unsigned)__popcll(m));
     }
-    todo &= ~m;
-  }
+  });
   if (use_lds) {
     __syncthreads();
     for (int d = threadIdx.x; d < n_inst; d += TOP_BLOCK) {
@@ -153,39 +148,7 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_top_classify(RaySrc S, unsigned n
   }
 }
 
-// Ordered mode (few destinations): exclusive scan of the per-block counts of one destination, offset by the queue's fill,
-// so that the scatter can place every ray at a slot that depends only on its index in the input list -- queues keep the order
-// of the list they were filled from (camera rays stay in pixel order; no sort is needed in front of the traversal) and the
-// result of a shuffle is deterministic.  One block per destination.
-__global__ __launch_bounds__(TOP_BLOCK) void k_top_scan(unsigned *__restrict__ blk_cnt, unsigned n_blk, const QueueDesc *__restrict__ queues,
-                                                        unsigned *__restrict__ totals) {
-  __shared__ unsigned sh_w[TOP_BLOCK / 64];
-  __shared__ unsigned sh_run;
-  const int d = blockIdx.x;
-  unsigned *row = blk_cnt + (size_t)d * n_blk;
-  __shared__ unsigned sh_start;
-  if (threadIdx.x == 0) { sh_run = *queues[d].count; sh_start = sh_run; }
-  __syncthreads();
-  for (unsigned b0 = 0; b0 < n_blk; b0 += TOP_BLOCK) {
-    const unsigned b = b0 + threadIdx.x;
-    const unsigned v = b < n_blk ? row[b] : 0u;
-    unsigned incl = v;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if ((int)lane_id() >= o) incl += u; }
-    if (lane_id() == 63) sh_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned woff = 0;
-    for (unsigned w = 0; w < (threadIdx.x >> 6); w++) woff += sh_w[w];
-    const unsigned run = sh_run;
-    if (b < n_blk) row[b] = run + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == TOP_BLOCK - 1) sh_run = run + woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    if (queues[d].keep) *queues[d].count = sh_run;
-    if (totals) totals[d] = sh_run - sh_start;
-  }
-}
+#include "ordered_scan.inc" // k_dest_scan: ordered mode, every block's first slot per destination
 
 __global__ __launch_bounds__(TOP_BLOCK) void k_top_scatter(RaySrc S, unsigned n, const int *__restrict__ next_in, const float *__restrict__ t_in,
                                                            const QueueDesc *__restrict__ queues, int n_inst, float *__restrict__ fb, unsigned n_pix,
@@ -220,11 +183,7 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_top_scatter(RaySrc S, unsigned n,
     if (next >= 0 && !queues[next].keep) next = -1; // shuffleDropRays: not this rank's domain
   }
   unsigned local = 0; // use_lds: offset inside the block's share of the destination; else: final slot
-  unsigned long long todo = ballot64(next >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int d = __shfl(next, leader);
-    const unsigned long long m = ballot64(next == d);
+  wave_by_dest(next, [&](int d, unsigned long long m, int leader) {
     unsigned base = 0;
     if (blk_base) {
       if ((int)lane_id() == leader) sh[(threadIdx.x >> 6) * n_inst + d] = (unsigned)__popcll(m);
@@ -233,8 +192,7 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_top_scatter(RaySrc S, unsigned n,
       base = __shfl(base, leader);
     }
     if (next == d) local = base + lanes_below(m);
-    todo &= ~m;
-  }
+  });
   if (blk_base) {
     __syncthreads();
     if (next >= 0) {
@@ -578,7 +536,7 @@ static int shuffle_impl(gvt_hip_top *T, const RaySrc &in, size_t n, int from, gv
     }
     if (queues[i]->cap < queues[i]->size + n) roomy = false;
   }
-  const bool scan_totals = d_blk && roomy; // ordered mode: k_top_scan leaves the totals in d_hist, no atomics and no memset needed
+  const bool scan_totals = d_blk && roomy; // ordered mode: k_dest_scan leaves the totals in d_hist, no atomics and no memset needed
   if (nI && !scan_totals) HIPCHK(hipMemsetAsync(T->d_hist, 0, sizeof(unsigned) * nI, st));
   {
     ProfScope ps(KC_SHUFFLE);
@@ -603,7 +561,7 @@ static int shuffle_impl(gvt_hip_top *T, const RaySrc &in, size_t n, int from, gv
   T->qdesc_uploaded.clear(); // (the asynchronous shuffle's upload cache no longer describes d_qdesc)
   {
     ProfScope ps(KC_SHUFFLE);
-    if (d_blk) k_top_scan<<<(unsigned)nI, TOP_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, scan_totals ? T->d_hist : nullptr);
+    if (d_blk) k_dest_scan<TOP_BLOCK><<<(unsigned)nI, TOP_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, scan_totals ? T->d_hist : nullptr);
     const size_t lds = d_blk ? sizeof(unsigned) * nI * (TOP_BLOCK / 64) : (use_lds ? 2 * sizeof(unsigned) * nI : 0);
     k_top_scatter<<<n_blk, TOP_BLOCK, lds, st>>>(in, (unsigned)n, d_next, d_t, (const QueueDesc *)T->d_qdesc, (int)nI, fb ? fb->d_rgba : nullptr,
                                                fb ? (unsigned)(fb->w * fb->h) : 0u, use_lds, d_blk);
@@ -724,7 +682,7 @@ static int shuffle_async_src(gvt_hip_top *T, const RaySrc &S, size_t n_ub, const
     ProfScope ps(KC_SHUFFLE);
     k_top_classify<<<n_blk, TOP_BLOCK, use_lds ? sizeof(unsigned) * nI : 0, st>>>(S, (unsigned)n_ub, T->dev(), (int)nI, from, d_next, d_t, nullptr, use_lds, d_blk,
                                                                                 n_dev, from_arr, C.skip_known);
-    if (d_blk) k_top_scan<<<(unsigned)nI, TOP_BLOCK, 0, st>>>(d_blk, n_blk, qd, nullptr);
+    if (d_blk) k_dest_scan<TOP_BLOCK><<<(unsigned)nI, TOP_BLOCK, 0, st>>>(d_blk, n_blk, qd, nullptr);
     const size_t lds = d_blk ? sizeof(unsigned) * nI * (TOP_BLOCK / 64) : (use_lds ? 2 * sizeof(unsigned) * nI : 0);
     k_top_scatter<<<n_blk, TOP_BLOCK, lds, st>>>(S, (unsigned)n_ub, d_next, d_t, qd, (int)nI, fb ? fb->d_rgba : nullptr,
                                                fb ? (unsigned)(fb->w * fb->h) : 0u, use_lds, d_blk, n_dev, d_overflow);

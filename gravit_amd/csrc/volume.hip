@@ -1,11 +1,14 @@
 // volume.hip -- volume domains: scalar bricks rendered with a transfer function.
 //   gvt_hip_volume_create / _set_transfer   Volume + TransferFunction (render/data/primitives/Volume.h, TransferFunction.cpp:40-72)
-//   k_volume_march                          the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp)
-//   k_vol_classify / _scan / _scatter       AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391)
+//   k_volume_march / k_volume_march_surf    the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp): two
+//                                           entry points of one body, volume_march_body<SURF> (SURF: isovalues and slice planes)
+//   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
+//                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
 //   gvt_hip_volume_frame                    Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks
 // The contract (lattice, ownership, evaluation order, flags) is stated in include/gvt_hip.h; tests/volume_checker.py restates it in numpy.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "gvt_internal.h"
@@ -27,7 +30,7 @@ struct gvt_hip_volume {
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
   uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
   unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered
-  // surfaces (gvt_hip_volume_set_surfaces / _set_lights): with n_iso + n_pl > 0 the march is k_volume_march_surf
+  // surfaces (gvt_hip_volume_set_surfaces / _set_lights): with n_iso + n_pl > 0 the march is k_volume_march_surf (volume_march_body<true>)
   int n_iso = 0, n_pl = 0, n_lights = 0;
   float iso[GVT_HIP_VOLUME_MAX_SURFACES] = {}, plane[GVT_HIP_VOLUME_MAX_SURFACES][4] = {};
   float surf_alpha = 1.f, ka = 0.4f, kd = 0.6f;
@@ -100,129 +103,6 @@ __device__ inline bool vol_cell(const VolDev &V, const float o[3], const float d
 
 __device__ inline float lerp_(float a, float b, float f) { return a + f * (b - a); }
 
-// One lane per ray, persistent waves with lane refill: a lane that finishes its ray takes the next one of the queue (one atomic per wave
-// and refill).  Rays are updated in place.
-__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
-                                                            unsigned long long *__restrict__ stats) {
-  bool active = false, exhausted = false;
-  unsigned idx = 0;
-  float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
-  int k = 0, k_hi = -1, k_last = -1;
-  bool seen = false;
-  unsigned long long n_marched = 0, n_gathered = 0;
-  for (;;) {
-    const unsigned long long idle = ballot64(!active);
-    if (idle && !exhausted && (__popcll(idle) >= VOL_REFILL_MIN || idle == ballot64(true))) {
-      const unsigned slot = wave_alloc(work, !active);
-      if (ballot64(!active && slot >= n)) exhausted = true; // (wave-uniform)
-      if (!active && slot < n) {
-        idx = slot;
-        active = true;
-        const float4 a = q.p0[idx], b = q.p1[idx], c = q.p2[idx];
-        const V3 oo = xfm_point(minv, mk3(a.x, a.y, a.z)), dd = xfm_vector(minv, mk3(b.x, b.y, b.z));
-        o[0] = oo.x; o[1] = oo.y; o[2] = oo.z; d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
-        C[0] = c.x; C[1] = c.y; C[2] = c.z;
-        A = q.p3[idx].z;
-        float tn, tf;
-        vol_slab(V.lo, V.hi, o, d, tn, tf);
-        const int k_prog = vol_first_after(a.w, V.dt);
-        k = 0;
-        k_hi = -1;
-        if (tn <= tf && tf >= 0.f && tf < INFINITY && k_prog >= 0) {
-          const float qlo = floorf(tn / V.dt), qhi = floorf(tf / V.dt);
-          if (qlo < VOL_K_MAX) {
-            k = max(k_prog, qlo > 1.f ? (int)qlo - 1 : 0);
-            k_hi = qhi < VOL_K_MAX ? (int)qhi + 1 : (int)VOL_K_MAX;
-            k_hi = min(k_hi, k + VOL_MAX_SAMPLES);
-          }
-        }
-        k_last = -1;
-        seen = false;
-      }
-    }
-    if (!ballot64(active)) break;
-    if (active) {
-      bool done = false;
-      for (int s = 0; s < VOL_STEP; s++) {
-        if (k > k_hi) { done = true; break; }
-        int c[3];
-        float f[3];
-        if (!vol_cell(V, o, d, k, c, f)) {
-          if (seen) { done = true; break; } // a brick's samples along a line are contiguous: the rest belongs to others
-          k++;
-          continue;
-        }
-        seen = true;
-        k_last = k;
-        n_marched++;
-        const int bi = ((c[2] >> 3) * V.nby + (c[1] >> 3)) * V.nbx + (c[0] >> 3);
-        if (V.skip && !V.mc[bi]) {
-          // an empty macro cell adds +0 per sample: jump to the last sample still inside it -- verified, so exact whatever the estimate
-          // (per axis the cells move monotonically with k: two samples in one block have every sample between them in it too)
-          const int cb[3] = { c[0] >> 3, c[1] >> 3, c[2] >> 3 };
-          const int off[3] = { V.ox, V.oy, V.oz }, nn[3] = { V.nx, V.ny, V.nz };
-          const float go[3] = { V.gox, V.goy, V.goz }, sp[3] = { V.sx, V.sy, V.sz };
-          float te = INFINITY;
-          for (int a = 0; a < 3; a++) {
-            if (d[a] == 0.f) continue;
-            const int gv = d[a] > 0.f ? off[a] + min(8 * cb[a] + 8, nn[a] - 1) : off[a] + 8 * cb[a];
-            te = fminf(te, ((go[a] + (float)gv * sp[a]) - o[a]) / d[a]);
-          }
-          const float qj = floorf(te / V.dt);
-          if (qj < VOL_K_MAX && qj > (float)(k + 1)) {
-            const int kj = min((int)qj, k_hi);
-            int cj[3];
-            float fj[3];
-            if (kj > k + 1 && vol_cell(V, o, d, kj, cj, fj) && (cj[0] >> 3) == cb[0] && (cj[1] >> 3) == cb[1] && (cj[2] >> 3) == cb[2]) {
-              n_marched += (unsigned long long)(kj - k);
-              k_last = kj;
-              k = kj;
-            }
-          }
-          k++;
-          continue;
-        }
-        n_gathered++;
-        const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny;
-        const float *p = V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
-        const float v000 = p[0], v100 = p[1], v010 = p[sy], v110 = p[sy + 1];
-        const float v001 = p[sz], v101 = p[sz + 1], v011 = p[sz + sy], v111 = p[sz + sy + 1];
-        const float c00 = lerp_(v000, v100, f[0]), c10 = lerp_(v010, v110, f[0]);
-        const float c01 = lerp_(v001, v101, f[0]), c11 = lerp_(v011, v111, f[0]);
-        const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
-        const float v = lerp_(c0, c1, f[2]);
-        const float pos = fminf(fmaxf((v - V.vlo) / V.vspan, 0.f), 1.f) * 255.f;
-        const int i0 = min((int)pos, 254);
-        const float w = pos - (float)i0;
-        const float4 e0 = V.tf[i0], e1 = V.tf[i0 + 1];
-        const float r = lerp_(e0.x, e1.x, w), g = lerp_(e0.y, e1.y, w), b = lerp_(e0.z, e1.z, w), al = lerp_(e0.w, e1.w, w);
-        const float fr = (1.f - A) * al;
-        C[0] = C[0] + fr * r; C[1] = C[1] + fr * g; C[2] = C[2] + fr * b;
-        A = A + fr;
-        k++;
-        if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
-      }
-      if (done) {
-        float4 a = q.p0[idx];
-        if (k_last >= 0) a.w = (float)k_last * V.dt;
-        q.p0[idx] = a;
-        q.p2[idx] = make_float4(C[0], C[1], C[2], q.p2[idx].w);
-        float4 e = q.p3[idx];
-        const int flag = A >= GVT_HIP_VOLUME_OPAQUE_A ? GVT_HIP_RAY_OPAQUE : GVT_HIP_RAY_BOUNDARY;
-        e.y = __int_as_float(__float_as_int(e.y) | flag);
-        e.z = A;
-        q.p3[idx] = e;
-        active = false;
-      }
-    }
-  }
-  for (int s = 32; s >= 1; s >>= 1) {
-    n_marched += __shfl_xor(n_marched, s);
-    n_gathered += __shfl_xor(n_gathered, s);
-  }
-  if (lane_id() == 0 && n_marched) { atomicAdd(&stats[0], n_marched); atomicAdd(&stats[1], n_gathered); }
-}
-
 // ---- surfaces in the march: isovalues and slice planes, shaded (the contract: include/gvt_hip.h; tests/volume_surface_checker.py).
 // The table is wave-uniform and travels by value (kernel arguments, read with scalar loads); per lane the march adds the side mask of
 // the previous sample, the lattice index the carried mask belongs to and, at a crossing only, the gradient.
@@ -234,6 +114,7 @@ struct SurfDev {
   int n_iso, n_pl, n_lights;
   float alpha, ka, kd;
 };
+struct NoSurf {}; // what the plain march has in SurfDev's place: nothing (its scalar registers are full without the table)
 #define VOL_CELL_SKIP 0x10000u
 
 __device__ inline void vol_point(const VolDev &V, const float o[3], const float d[3], int k, float p[3]) {
@@ -298,14 +179,101 @@ __device__ inline void surf_composite(const SurfDev &S, float4 c, const float g[
   A = A + f;
 }
 
-// k_volume_march with surfaces (launched only for volumes that have some): the same lanes, refill and lattice; per sample the side mask,
-// at a crossing the shaded surfaces before the sample's own contribution.  prev < 0: no previous sample.
-__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
-                                                                 unsigned long long *__restrict__ stats) {
+// ---- the steps of the march.  Each is parity critical (the checkers compare bit for bit) and exists once.
+
+// ray (a = origin | t_min, b = direction) into the brick's object space, and the lattice range k .. k_hi its visit walks (k_hi < k:
+// none).  Returns the first lattice index after t_min.
+__device__ __forceinline__ int vol_ray_range(const VolDev &V, const Mat4 &minv, float4 a, float4 b, float o[3], float d[3], int &k, int &k_hi) {
+  const V3 oo = xfm_point(minv, mk3(a.x, a.y, a.z)), dd = xfm_vector(minv, mk3(b.x, b.y, b.z));
+  o[0] = oo.x; o[1] = oo.y; o[2] = oo.z; d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
+  float tn, tf;
+  vol_slab(V.lo, V.hi, o, d, tn, tf);
+  const int k_prog = vol_first_after(a.w, V.dt);
+  k = 0;
+  k_hi = -1;
+  if (tn <= tf && tf >= 0.f && tf < INFINITY && k_prog >= 0) {
+    const float qlo = floorf(tn / V.dt), qhi = floorf(tf / V.dt);
+    if (qlo < VOL_K_MAX) {
+      k = max(k_prog, qlo > 1.f ? (int)qlo - 1 : 0);
+      k_hi = qhi < VOL_K_MAX ? (int)qhi + 1 : (int)VOL_K_MAX;
+      k_hi = min(k_hi, k + VOL_MAX_SAMPLES);
+    }
+  }
+  return k_prog;
+}
+
+// Sample k lies in cell c, whose macro cell needs no interpolation: the last sample kj > k + 1 still inside that macro cell, or k where
+// there is none.  Verified, so exact whatever the estimate (per axis the cells move monotonically with k: two samples in one block
+// have every sample between them in it too).
+__device__ __forceinline__ int vol_jump_target(const VolDev &V, const float o[3], const float d[3], int k, int k_hi, const int c[3]) {
+  const int cb[3] = { c[0] >> 3, c[1] >> 3, c[2] >> 3 };
+  const int off[3] = { V.ox, V.oy, V.oz }, nn[3] = { V.nx, V.ny, V.nz };
+  const float go[3] = { V.gox, V.goy, V.goz }, sp[3] = { V.sx, V.sy, V.sz };
+  float te = INFINITY;
+  for (int a = 0; a < 3; a++) {
+    if (d[a] == 0.f) continue;
+    const int gv = d[a] > 0.f ? off[a] + min(8 * cb[a] + 8, nn[a] - 1) : off[a] + 8 * cb[a];
+    te = fminf(te, ((go[a] + (float)gv * sp[a]) - o[a]) / d[a]);
+  }
+  const float qj = floorf(te / V.dt);
+  if (qj < VOL_K_MAX && qj > (float)(k + 1)) {
+    const int kj = min((int)qj, k_hi);
+    int cj[3];
+    float fj[3];
+    if (kj > k + 1 && vol_cell(V, o, d, kj, cj, fj) && (cj[0] >> 3) == cb[0] && (cj[1] >> 3) == cb[1] && (cj[2] >> 3) == cb[2]) return kj;
+  }
+  return k;
+}
+
+// the eight vertices of cell c and the trilinear value at the fractions f
+struct VolCorners { float v000, v100, v010, v110, v001, v101, v011, v111; };
+__device__ __forceinline__ float vol_gather(const VolDev &V, const int c[3], const float f[3], VolCorners &G) {
+  const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny;
+  const float *p = V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
+  G.v000 = p[0]; G.v100 = p[1]; G.v010 = p[sy]; G.v110 = p[sy + 1];
+  G.v001 = p[sz]; G.v101 = p[sz + 1]; G.v011 = p[sz + sy]; G.v111 = p[sz + sy + 1];
+  const float c00 = lerp_(G.v000, G.v100, f[0]), c10 = lerp_(G.v010, G.v110, f[0]);
+  const float c01 = lerp_(G.v001, G.v101, f[0]), c11 = lerp_(G.v011, G.v111, f[0]);
+  const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
+  return lerp_(c0, c1, f[2]);
+}
+
+// the sample of value v, front to back
+__device__ __forceinline__ void vol_accumulate(const VolDev &V, float v, float C[3], float &A) {
+  const float4 tc = vol_lookup(V, v);
+  const float fr = (1.f - A) * tc.w;
+  C[0] = C[0] + fr * tc.x; C[1] = C[1] + fr * tc.y; C[2] = C[2] + fr * tc.z;
+  A = A + fr;
+}
+
+// the ray leaves the brick: t_min = its last sample here (k_last < 0: it had none), colour, opacity and flags; with surfaces the sides
+// of that sample too
+template <bool SURF>
+__device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, unsigned idx, int k_last, const float C[3], float A, int prev) {
+  float4 a = q.p0[idx];
+  int flag = A >= GVT_HIP_VOLUME_OPAQUE_A ? GVT_HIP_RAY_OPAQUE : GVT_HIP_RAY_BOUNDARY;
+  if (k_last >= 0) a.w = (float)k_last * V.dt;
+  q.p0[idx] = a;
+  float cw = q.p2[idx].w;
+  if constexpr (SURF)
+    if (k_last >= 0) { cw = (float)prev; flag |= GVT_HIP_RAY_SIDES; } // (prev = the sides of sample k_last)
+  q.p2[idx] = make_float4(C[0], C[1], C[2], cw);
+  float4 e = q.p3[idx];
+  e.y = __int_as_float(__float_as_int(e.y) | flag);
+  e.z = A;
+  q.p3[idx] = e;
+}
+
+// One lane per ray, persistent waves with lane refill: a lane that finishes its ray takes the next one of the queue (one atomic per wave
+// and refill).  Rays are updated in place.  SURF (volumes that have surfaces): per sample the side mask, at a crossing the shaded
+// surfaces before the sample's own contribution.  prev < 0: no previous sample.
+template <bool SURF>
+__device__ __forceinline__ void volume_march_body(const VolDev &V, const std::conditional_t<SURF, SurfDev, NoSurf> &S, RayPlanes q, unsigned n, const Mat4 &minv,
+                                                  unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
   bool active = false, exhausted = false;
   unsigned idx = 0;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
-  int k = 0, k_hi = -1, k_last = -1, k_carry = -1, prev = -1;
+  int k = 0, k_hi = -1, k_last = -1, k_carry = -1, prev = -1; // (k_carry, prev, n_crossed: SURF only)
   bool seen = false;
   unsigned long long n_marched = 0, n_gathered = 0;
   unsigned n_crossed = 0;
@@ -318,29 +286,16 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfD
         idx = slot;
         active = true;
         const float4 a = q.p0[idx], b = q.p1[idx], c = q.p2[idx], e = q.p3[idx];
-        const V3 oo = xfm_point(minv, mk3(a.x, a.y, a.z)), dd = xfm_vector(minv, mk3(b.x, b.y, b.z));
-        o[0] = oo.x; o[1] = oo.y; o[2] = oo.z; d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
+        const int k_prog = vol_ray_range(V, minv, a, b, o, d, k, k_hi);
         C[0] = c.x; C[1] = c.y; C[2] = c.z;
         A = e.z;
-        float tn, tf;
-        vol_slab(V.lo, V.hi, o, d, tn, tf);
-        const int k_prog = vol_first_after(a.w, V.dt);
-        k = 0;
-        k_hi = -1;
-        if (tn <= tf && tf >= 0.f && tf < INFINITY && k_prog >= 0) {
-          const float qlo = floorf(tn / V.dt), qhi = floorf(tf / V.dt);
-          if (qlo < VOL_K_MAX) {
-            k = max(k_prog, qlo > 1.f ? (int)qlo - 1 : 0);
-            k_hi = qhi < VOL_K_MAX ? (int)qhi + 1 : (int)VOL_K_MAX;
-            k_hi = min(k_hi, k + VOL_MAX_SAMPLES);
-          }
-        }
         k_last = -1;
         seen = false;
-        // the sides of the sample in t_min count only for the sample right after it
-        const bool carried = (__float_as_int(e.y) & GVT_HIP_RAY_SIDES) != 0;
-        prev = carried ? ((int)c.w & 0xffff) : -1;
-        k_carry = carried ? k_prog : -1;
+        if constexpr (SURF) { // the sides of the sample in t_min count only for the sample right after it
+          const bool carried = (__float_as_int(e.y) & GVT_HIP_RAY_SIDES) != 0;
+          prev = carried ? ((int)c.w & 0xffff) : -1;
+          k_carry = carried ? k_prog : -1;
+        }
       }
     }
     if (!ballot64(active)) break;
@@ -351,100 +306,78 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfD
         int c[3];
         float f[3];
         if (!vol_cell(V, o, d, k, c, f)) {
-          if (seen) { done = true; break; }
+          if (seen) { done = true; break; } // a brick's samples along a line are contiguous: the rest belongs to others
           k++;
           continue;
         }
-        if (!seen && k != k_carry) prev = -1;
+        if constexpr (SURF)
+          if (!seen && k != k_carry) prev = -1;
         seen = true;
         k_last = k;
         n_marched++;
-        float p[3];
-        vol_point(V, o, d, k, p);
-        const unsigned pl = surf_plane_sides(S, p);
         const int bi = ((c[2] >> 3) * V.nby + (c[1] >> 3)) * V.nbx + (c[0] >> 3);
-        const unsigned cell = V.skip ? S.cells[bi] : 0u;
-        if ((cell & VOL_CELL_SKIP) && (prev < 0 || prev == (int)((cell & 0xffffu) | pl))) {
-          // nothing to composite here and no crossing: the sample goes uninterpolated, and so do those after it in this macro cell
-          // as long as no plane can change sides among them (the isovalue sides are the cell's)
-          prev = (int)((cell & 0xffffu) | pl);
-          const int cb[3] = { c[0] >> 3, c[1] >> 3, c[2] >> 3 };
-          const int off[3] = { V.ox, V.oy, V.oz }, nn[3] = { V.nx, V.ny, V.nz };
-          const float go[3] = { V.gox, V.goy, V.goz }, sp[3] = { V.sx, V.sy, V.sz };
-          float te = INFINITY;
-          for (int a = 0; a < 3; a++) {
-            if (d[a] == 0.f) continue;
-            const int gv = d[a] > 0.f ? off[a] + min(8 * cb[a] + 8, nn[a] - 1) : off[a] + 8 * cb[a];
-            te = fminf(te, ((go[a] + (float)gv * sp[a]) - o[a]) / d[a]);
-          }
-          const float qj = floorf(te / V.dt);
-          if (qj < VOL_K_MAX && qj > (float)(k + 1)) {
-            const int kj = min((int)qj, k_hi);
-            int cj[3];
-            float fj[3];
-            if (kj > k + 1 && vol_cell(V, o, d, kj, cj, fj) && (cj[0] >> 3) == cb[0] && (cj[1] >> 3) == cb[1] && (cj[2] >> 3) == cb[2] &&
-                surf_planes_clear(V, S, o, d, k, kj)) {
-              n_marched += (unsigned long long)(kj - k);
-              k_last = kj;
-              k = kj;
-            }
+        // Plain: an empty macro cell adds +0 per sample.  SURF: nothing to composite there and no crossing either, as long as no plane
+        // can change sides among the samples (the isovalue sides are the cell's).  The sample goes uninterpolated, and so do those
+        // after it in this macro cell
+        unsigned pl = 0u;
+        bool skip;
+        if constexpr (SURF) {
+          float p[3];
+          vol_point(V, o, d, k, p);
+          pl = surf_plane_sides(S, p);
+          const unsigned cell = V.skip ? S.cells[bi] : 0u;
+          skip = (cell & VOL_CELL_SKIP) && (prev < 0 || prev == (int)((cell & 0xffffu) | pl));
+          if (skip) prev = (int)((cell & 0xffffu) | pl);
+        } else {
+          skip = V.skip && !V.mc[bi];
+        }
+        if (skip) {
+          const int kj = vol_jump_target(V, o, d, k, k_hi, c);
+          bool jump = kj > k;
+          if constexpr (SURF) jump = jump && surf_planes_clear(V, S, o, d, k, kj);
+          if (jump) {
+            n_marched += (unsigned long long)(kj - k);
+            k_last = kj;
+            k = kj;
           }
           k++;
           continue;
         }
         n_gathered++;
-        const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny;
-        const float *vp = V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
-        const float v000 = vp[0], v100 = vp[1], v010 = vp[sy], v110 = vp[sy + 1];
-        const float v001 = vp[sz], v101 = vp[sz + 1], v011 = vp[sz + sy], v111 = vp[sz + sy + 1];
-        const float c00 = lerp_(v000, v100, f[0]), c10 = lerp_(v010, v110, f[0]);
-        const float c01 = lerp_(v001, v101, f[0]), c11 = lerp_(v011, v111, f[0]);
-        const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
-        const float v = lerp_(c0, c1, f[2]);
-        unsigned sides = pl;
-        for (int i = 0; i < S.n_iso; i++)
-          if (v >= S.iso[i]) sides |= 1u << i;
-        unsigned crossed = prev < 0 ? 0u : (sides ^ (unsigned)prev);
-        prev = (int)sides;
-        if (crossed) {
-          while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
-            const int i = __ffs((int)crossed) - 1;
-            crossed &= crossed - 1u;
-            n_crossed++;
-            if (i < S.n_iso) {
-              const float g[3] = { lerp_(lerp_(v100 - v000, v110 - v010, f[1]), lerp_(v101 - v001, v111 - v011, f[1]), f[2]) / V.sx,
-                                   lerp_(lerp_(v010 - v000, v110 - v100, f[0]), lerp_(v011 - v001, v111 - v101, f[0]), f[2]) / V.sy,
-                                   lerp_(lerp_(v001 - v000, v101 - v100, f[0]), lerp_(v011 - v010, v111 - v110, f[0]), f[1]) / V.sz };
-              surf_composite(S, vol_lookup(V, S.iso[i]), g, C, A);
-            } else {
-              const float4 P = S.plane[i - S.n_iso];
-              const float g[3] = { P.x, P.y, P.z };
-              surf_composite(S, vol_lookup(V, v), g, C, A);
+        VolCorners G;
+        const float v = vol_gather(V, c, f, G);
+        if constexpr (SURF) {
+          unsigned sides = pl;
+          for (int i = 0; i < S.n_iso; i++)
+            if (v >= S.iso[i]) sides |= 1u << i;
+          unsigned crossed = prev < 0 ? 0u : (sides ^ (unsigned)prev);
+          prev = (int)sides;
+          if (crossed) {
+            const float v000 = G.v000, v100 = G.v100, v010 = G.v010, v110 = G.v110, v001 = G.v001, v101 = G.v101, v011 = G.v011, v111 = G.v111;
+            while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+              const int i = __ffs((int)crossed) - 1;
+              crossed &= crossed - 1u;
+              n_crossed++;
+              if (i < S.n_iso) {
+                const float g[3] = { lerp_(lerp_(v100 - v000, v110 - v010, f[1]), lerp_(v101 - v001, v111 - v011, f[1]), f[2]) / V.sx,
+                                     lerp_(lerp_(v010 - v000, v110 - v100, f[0]), lerp_(v011 - v001, v111 - v101, f[0]), f[2]) / V.sy,
+                                     lerp_(lerp_(v001 - v000, v101 - v100, f[0]), lerp_(v011 - v010, v111 - v110, f[0]), f[1]) / V.sz };
+                surf_composite(S, vol_lookup(V, S.iso[i]), g, C, A);
+              } else {
+                const float4 P = S.plane[i - S.n_iso];
+                const float g[3] = { P.x, P.y, P.z };
+                surf_composite(S, vol_lookup(V, v), g, C, A);
+              }
             }
+            if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
           }
-          if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
         }
-        const float4 tc = vol_lookup(V, v);
-        const float fr = (1.f - A) * tc.w;
-        C[0] = C[0] + fr * tc.x; C[1] = C[1] + fr * tc.y; C[2] = C[2] + fr * tc.z;
-        A = A + fr;
+        vol_accumulate(V, v, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }
       if (done) {
-        float4 a = q.p0[idx];
-        float4 cc = q.p2[idx], e = q.p3[idx];
-        int flag = A >= GVT_HIP_VOLUME_OPAQUE_A ? GVT_HIP_RAY_OPAQUE : GVT_HIP_RAY_BOUNDARY;
-        if (k_last >= 0) { // (prev = the sides of sample k_last)
-          a.w = (float)k_last * V.dt;
-          cc.w = (float)prev;
-          flag |= GVT_HIP_RAY_SIDES;
-        }
-        q.p0[idx] = a;
-        q.p2[idx] = make_float4(C[0], C[1], C[2], cc.w);
-        e.y = __int_as_float(__float_as_int(e.y) | flag);
-        e.z = A;
-        q.p3[idx] = e;
+        vol_write_back<SURF>(V, q, idx, k_last, C, A, prev);
         active = false;
       }
     }
@@ -453,9 +386,25 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfD
   for (int s = 32; s >= 1; s >>= 1) {
     n_marched += __shfl_xor(n_marched, s);
     n_gathered += __shfl_xor(n_gathered, s);
-    n_cr += __shfl_xor(n_cr, s);
+    if constexpr (SURF) n_cr += __shfl_xor(n_cr, s);
   }
-  if (lane_id() == 0 && n_marched) { atomicAdd(&stats[0], n_marched); atomicAdd(&stats[1], n_gathered); if (n_cr) atomicAdd(&stats[2], n_cr); }
+  if (lane_id() == 0 && n_marched) {
+    atomicAdd(&stats[0], n_marched);
+    atomicAdd(&stats[1], n_gathered);
+    if constexpr (SURF)
+      if (n_cr) atomicAdd(&stats[2], n_cr);
+  }
+}
+
+// The two entry points.  The plain one does not receive SurfDev: the table is about 600 bytes of kernel arguments, and its scalar
+// registers are full as it is.
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                            unsigned long long *__restrict__ stats) {
+  volume_march_body<false>(V, NoSurf{}, q, n, minv, work, stats);
+}
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                 unsigned long long *__restrict__ stats) {
+  volume_march_body<true>(V, S, q, n, minv, work, stats);
 }
 
 // ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
@@ -513,44 +462,14 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigne
     }
     next_out[i] = next;
   }
-  unsigned long long todo = ballot64(next >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int dd = __shfl(next, leader);
-    const unsigned long long m = ballot64(next == dd);
+  wave_by_dest(next, [&](int dd, unsigned long long m, int leader) {
     if ((int)lane_id() == leader) atomicAdd(&sh[dd], (unsigned)__popcll(m));
-    todo &= ~m;
-  }
+  });
   __syncthreads();
   for (int j = threadIdx.x; j < n_dest; j += VOL_BLOCK) blk_cnt[(size_t)j * gridDim.x + blockIdx.x] = sh[j];
 }
 
-// one block per destination: exclusive scan of its per-block counts, offset by the queue's fill; totals[j] = the rays it receives
-__global__ __launch_bounds__(VOL_BLOCK) void k_vol_scan(unsigned *__restrict__ blk_cnt, unsigned n_blk, const QueueDesc *__restrict__ queues,
-                                                        unsigned *__restrict__ totals) {
-  __shared__ unsigned sh_w[VOL_BLOCK / 64];
-  __shared__ unsigned sh_run, sh_start;
-  const int j = blockIdx.x;
-  unsigned *row = blk_cnt + (size_t)j * n_blk;
-  if (threadIdx.x == 0) { sh_run = *queues[j].count; sh_start = sh_run; }
-  __syncthreads();
-  for (unsigned b0 = 0; b0 < n_blk; b0 += VOL_BLOCK) {
-    const unsigned b = b0 + threadIdx.x;
-    const unsigned v = b < n_blk ? row[b] : 0u;
-    unsigned incl = v;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(incl, o); if ((int)lane_id() >= o) incl += u; }
-    if (lane_id() == 63) sh_w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned woff = 0;
-    for (unsigned w = 0; w < (threadIdx.x >> 6); w++) woff += sh_w[w];
-    const unsigned run = sh_run;
-    if (b < n_blk) row[b] = run + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == VOL_BLOCK - 1) sh_run = run + woff + incl;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) totals[j] = sh_run - sh_start;
-}
+#include "ordered_scan.inc" // k_dest_scan: every block's first slot per destination; totals[j] = the rays it receives
 
 // fresh (camera rays): they start with no colour, no opacity and no flags
 __global__ __launch_bounds__(VOL_BLOCK) void k_vol_scatter(RayPlanes q, unsigned n, const int *__restrict__ next_in, const unsigned *__restrict__ blk_base,
@@ -561,15 +480,10 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_scatter(RayPlanes q, unsigned
   const unsigned i = blockIdx.x * VOL_BLOCK + threadIdx.x;
   const int next = i < n ? next_in[i] : -1;
   unsigned local = 0;
-  unsigned long long todo = ballot64(next >= 0);
-  while (todo) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const int dd = __shfl(next, leader);
-    const unsigned long long m = ballot64(next == dd);
+  wave_by_dest(next, [&](int dd, unsigned long long m, int leader) {
     if ((int)lane_id() == leader) sh[(threadIdx.x >> 6) * n_dest + dd] = (unsigned)__popcll(m);
     if (next == dd) local = lanes_below(m);
-    todo &= ~m;
-  }
+  });
   __syncthreads();
   if (next < 0) return;
   for (unsigned w = 0; w < (threadIdx.x >> 6); w++) local += sh[w * n_dest + next];
@@ -676,9 +590,11 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
     }
     if (queues[i]->cap < queues[i]->size + n) roomy = false;
   }
+  // keep = 0: k_dest_scan reads a queue's count word and leaves it alone.  The host writes the new fills below, once the scatter has
+  // reported no overflow (k_vol_scatter does not read keep: every brick of the top is a destination here)
   QueueDesc *desc = (QueueDesc *)T->h_qdesc;
   auto upload_desc = [&]() -> int {
-    for (size_t i = 0; i < nI; i++) { desc[i].planes = queues[i]->d_planes; desc[i].cap = queues[i]->cap; desc[i].count = queues[i]->d_count; desc[i].keep = 1u; }
+    for (size_t i = 0; i < nI; i++) { desc[i].planes = queues[i]->d_planes; desc[i].cap = queues[i]->cap; desc[i].count = queues[i]->d_count; desc[i].keep = 0u; }
     if (nI) HIPCHK(hipMemcpyAsync(T->d_qdesc, desc, sizeof(QueueDesc) * nI, hipMemcpyHostToDevice, st));
     T->qdesc_uploaded.clear(); // (the asynchronous mesh shuffle's upload cache no longer describes d_qdesc)
     return 0;
@@ -691,7 +607,7 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
     ProfScope ps(KC_SHUFFLE);
     k_vol_classify<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, T->dev(), (int)nI, from, d_next, d_blk, fb ? fb->d_rgba : nullptr,
                                                 fb ? (unsigned)(fb->w * fb->h) : 0u);
-    if (nI) k_vol_scan<<<(unsigned)nI, VOL_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, T->d_hist);
+    if (nI) k_dest_scan<VOL_BLOCK><<<(unsigned)nI, VOL_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, T->d_hist);
   }
   HIPCHK(hipGetLastError());
   if (!roomy) { // exact growth: the totals first (the scan's bases depend only on the counts, which do not move before the scatter)
@@ -943,8 +859,7 @@ extern "C" int gvt_hip_volume_trace(gvt_hip_volume *V, const gvt_hip_ray *rays, 
   if (!cnt) return 0;
   if (!rays_out) { set_error("volume_trace: null rays_out"); return GVT_HIP_ERR_INVALID; }
   Ctx &C = gctx();
-  if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
-  if (!C.abi_qin || !C.abi_qout) return GVT_HIP_ERR_DEVICE;
+  if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
   gvt_hip_queue *q = C.abi_qin; // (the context's staging list of gvt_hip_trace)
   int rc;
   if ((rc = gvt_hip_queue_clear(q))) return rc;
@@ -977,8 +892,7 @@ extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volum
   for (size_t i = 0; i < n_inst; i++)
     if (!volumes[i] || !queues[i] || !volumes[i]->has_tf) { set_error("volume_frame: brick %zu has no volume, queue or transfer function", i); return GVT_HIP_ERR_INVALID; }
   Ctx &C = gctx();
-  if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
-  if (!C.abi_qin || !C.abi_qout) return GVT_HIP_ERR_DEVICE;
+  if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
   gvt_hip_queue *q_cam = C.abi_qout; // (a staging list of the context: the camera's rays before they are distributed)
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;                                                  // clearBuffer :142
