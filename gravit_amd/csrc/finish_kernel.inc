@@ -59,27 +59,26 @@ __device__ __forceinline__ void uni_ray(RayRec &r) {
   r.km[0] = uni(r.km[0]); r.km[1] = uni(r.km[1]); r.km[2] = uni(r.km[2]);
 }
 
-// closest hit / any hit of ONE ray by a whole wave: wave_closest_run / wave_any_run (trace.hip), from the root
+// closest hit / any hit of ONE ray by a whole wave, from the root: the two layouts' instantiations of wave_run / wave_any_run (trace_wave.inc)
 #define FIN_CAP 384           // lists of 640 entries: 10 KiB of LDS per wave, 16 waves per CU = 4 per SIMD (128 VGPRs, 50 spilled outside the traversal loops).  Round 6, against
 #define FIN_PHYS (FIN_CAP + 256) // k_long_closest's 768 entries / 12 waves per CU: --domains 8 1.477 -> 1.458 ms (3 alternated pairs): a step waits for memory more than for issue
                               // slots (profiles/r06_finish_clusters.txt).  Lists of 256 entries (24 waves per CU, 84 VGPRs) were slower, 0.53 vs 0.47 ms on the 8-tile soup's 25 K hops
-// (nodes4c != null: the instance carries the cluster layout -- two levels per memory round trip, trace_wave.inc wave_closest_run_c)
+// (nodes4c != null, wave-uniform: the instance carries the cluster layout -- two levels per memory round trip, trace_wave.inc)
 template <int CAP, int PHYS>
 __device__ inline void wave_closest(const uint4 *__restrict__ nodes4, const uint4 *__restrict__ nodes4c, int root_entry, const float4 *__restrict__ tris, V3 O, V3 D, float tnear,
-                                    volatile int *s_ref, volatile float *s_tn, volatile int *l_ref, volatile float *l_tn, float &bt, int &bp, float &bu, float &bv, float &bden,
-                                    unsigned *ovf_word) {
+                                    const WaveLists &L, float &bt, int &bp, float &bu, float &bv, float &bden, unsigned *ovf_word) {
   bt = GVT_FLT_MAX; bu = 0.f; bv = 0.f; bden = 1.f; bp = -1;
-  if (lane_id() == 0) { s_ref[0] = nodes4c ? root_entry : 0; s_tn[0] = 0.f; }
+  if (lane_id() == 0) { L.s_ref[0] = nodes4c ? root_entry : 0; L.s_tn[0] = 0.f; }
   __builtin_amdgcn_wave_barrier();
-  if (nodes4c) wave_closest_run_c<CAP, PHYS>(nodes4c, tris, O, D, slab_of(O, D), tnear, s_ref, s_tn, l_ref, l_tn, 1, 0, bt, bp, bu, bv, bden, ovf_word);
-  else wave_closest_run<CAP, PHYS>(nodes4, tris, O, D, slab_of(O, D), tnear, s_ref, s_tn, l_ref, l_tn, nodes4 ? 1 : 0, 0, bt, bp, bu, bv, bden, ovf_word);
+  if (nodes4c) wave_run<false, true, CAP, PHYS>(nodes4c, tris, O, D, slab_of(O, D), tnear, L, 1, 0, bt, bp, bu, bv, bden, ovf_word);
+  else wave_run<false, false, CAP, PHYS>(nodes4, tris, O, D, slab_of(O, D), tnear, L, nodes4 ? 1 : 0, 0, bt, bp, bu, bv, bden, ovf_word);
   bt = uni(bt); bp = uni(bp); bu = uni(bu); bv = uni(bv); bden = uni(bden); // (the wave's reduction left the same values in every lane)
 }
 template <int CAP, int PHYS>
 __device__ inline bool wave_any(const uint4 *__restrict__ nodes4, const uint4 *__restrict__ nodes4c, int root_entry, const float4 *__restrict__ tris, V3 O, V3 D, float tnear,
                                 volatile int *s_ref, volatile int *l_ref, unsigned *ovf_word) {
-  if (nodes4c) return wave_any_run_c<CAP, PHYS>(nodes4c, root_entry, tris, O, D, slab_of(O, D), tnear, s_ref, l_ref, ovf_word);
-  return wave_any_run<CAP, PHYS>(nodes4, tris, O, D, slab_of(O, D), tnear, s_ref, l_ref, ovf_word);
+  if (nodes4c) return wave_any_run<true, CAP, PHYS>(nodes4c, root_entry, tris, O, D, slab_of(O, D), tnear, s_ref, l_ref, ovf_word);
+  return wave_any_run<false, CAP, PHYS>(nodes4, 0, tris, O, D, slab_of(O, D), tnear, s_ref, l_ref, ovf_word);
 }
 
 __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves per SIMD = the 16 waves per CU the LDS lists allow (unbounded: 230 VGPRs, 2 per SIMD; 3 per SIMD: 156)
@@ -93,6 +92,7 @@ __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves pe
   volatile float *s_tn = s_tn_all[wv];
   volatile int *l_ref = l_ref_all[wv];
   volatile float *l_tn = l_tn_all[wv];
+  const WaveLists L = { s_ref, s_tn, l_ref, l_tn };
   if (A.valid && !*A.valid) return;
   const unsigned n_rays = A.n_dev ? *A.n_dev : A.n;
   if (blockIdx.x == 0 && A.count_ptr)
@@ -115,11 +115,7 @@ __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves pe
     } else next = top_nearest(ra, rb, A.top, from, ret_t);
     next = uni(next); ret_t = uni(ret_t);
     if (next < 0) {
-      if (lane == 0 && r.type == 1 && len3(r.c) > 0.f && (unsigned)r.id < A.n_pix) {
-        const V3 cw = scl3(r.c, r.w);
-        float *px = A.fb + (size_t)4 * (unsigned)r.id;
-        atomicAdd(px + 0, cw.x); atomicAdd(px + 1, cw.y); atomicAdd(px + 2, cw.z); atomicAdd(px + 3, 1.f);
-      }
+      if (lane == 0) deposit_shadow(A.fb, A.n_pix, r.type, r.c, r.w, (unsigned)r.id);
       return 0;
     }
     if (!walked) r.o = uni(add3(r.o, scl3(r.d, ret_t * 0.95f))); // :393
@@ -133,12 +129,7 @@ __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves pe
     return 2;
   };
   for (;;) {
-    unsigned g = 0;
-    if (first) { first = false; g = blockIdx.x * 4u + (unsigned)wv; }
-    else {
-      if (lane == 0) g = atomicAdd(A.counter, 1u);
-      g = (unsigned)__builtin_amdgcn_readfirstlane((int)g) + gridDim.x * 4u;
-    }
+    const unsigned g = wave_ticket(first, A.counter, wv);
     if (g >= n_rays) break;
     const WaveSeg sg = A.W.segs[wave_find_seg(A.W, g)];
     RayRec r = load_ray(make_planes(sg.planes, sg.cap), g - sg.begin);
@@ -149,7 +140,7 @@ __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves pe
       const WaveInst *wi = A.W.insts + inst;
       float bt, bu, bv, bden;
       int bp;
-      wave_closest<FIN_CAP, FIN_PHYS>(wi->nodes4, wi->nodes4c, wi->root_entry4c, wi->tris, xfm_point(wi->minv, r.o), xfm_vector(wi->minv, r.d), GVT_RAY_EPSILON, s_ref, s_tn, l_ref, l_tn, bt, bp, bu, bv, bden, A.trav_overflow);
+      wave_closest<FIN_CAP, FIN_PHYS>(wi->nodes4, wi->nodes4c, wi->root_entry4c, wi->tris, xfm_point(wi->minv, r.o), xfm_vector(wi->minv, r.d), GVT_RAY_EPSILON, L, bt, bp, bu, bv, bden, A.trav_overflow);
       n_closest++;
       if (bp < 0) { // miss: forwarded as it is
         int next;
@@ -244,7 +235,7 @@ __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves pe
       r.km[0] = 0u; r.km[1] = 0u; r.km[2] = 0u; // a new straight segment
       uni_ray(r);
     }
-    __builtin_amdgcn_wave_barrier(); // (convergent: the lanes meet again here -- move_on's lane-0 blocks -- not at the loop header's readfirstlane)
+    __builtin_amdgcn_wave_barrier(); // (convergent: the lanes meet again here -- move_on's lane-0 blocks -- not at the loop header's readfirstlane: wave_ticket)
   }
   if (lane == 0 && (n_closest || n_any)) { atomicAdd(A.tot + 0, (unsigned long long)n_closest); atomicAdd(A.tot + 1, (unsigned long long)n_any); }
 }

@@ -280,6 +280,16 @@ __device__ __forceinline__ void wave_by_dest(int dest, F f) {
   }
 }
 
+// shuffleRays' terminal deposit (TracerBase.h:396-400 -> IceTComposite::localAdd): a SHADOW ray (type 1) that carries colour and has no instance
+// ahead of it adds colour * weight and one count to its pixel.  The caller decides that nothing lies ahead; any other ray just ends.
+__device__ __forceinline__ void deposit_shadow(float *fb, unsigned n_pix, int type, V3 c, float w, unsigned id) {
+  if (type == 1 && len3(c) > 0.f && id < n_pix) {
+    const V3 cw = scl3(c, w);
+    float *px = fb + (size_t)4 * id;
+    atomicAdd(px + 0, cw.x); atomicAdd(px + 1, cw.y); atomicAdd(px + 2, cw.z); atomicAdd(px + 3, 1.f);
+  }
+}
+
 // ---- top-level instance test (BVH::intersect + RayPacketIntersection), shared by the shuffle kernels and k_trace's sink ----
 // RayPacket.h fastmin/fastmax: (a<b)?a:b / (a>b)?a:b
 __device__ inline float fmin_ref(float a, float b) { return (a < b) ? a : b; }

@@ -845,7 +845,7 @@ static int build_nodes4(gvt_hip_mesh *M, BuildArena *A) {
 int build_nodes4(gvt_hip_mesh *M) { return build_nodes4(M, nullptr); }
 
 // ------------------------------------------------------------------------------------------------
-// The CLUSTER layout of the 4-wide nodes, for the traversals that give a ray a whole wave (k_finish: trace_wave.inc wave_closest_run_c / wave_any_run_c).
+// The CLUSTER layout of the 4-wide nodes, for the traversals that give a ray a whole wave (k_finish: trace_wave.inc wave_run<.., CLUSTER>).
 // Such a traversal is a chain of dependent node fetches, one per level of the tree (the wave opens its ray's whole frontier per step): ~12 steps of a microsecond
 // each for a tile of a million triangles.  Here every node of an EVEN level is followed in memory by its inner children (odd level), and a reference to an even
 // node carries, in its low four bits, which of its children are inner nodes: (slot << 4) | mask.  A step then fetches a node AND its children at once -- the

@@ -173,13 +173,7 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_top_scatter(RaySrc S, unsigned n,
     if (next >= 0) {
       const float t_adv = t_in[i];
       if (t_adv >= 0.f) r.o = add3(r.o, scl3(r.d, t_adv * 0.95f)); // TracerBase.h:393 (< 0: k_top_classify has walked the ray through known misses)
-    } else if (fb && r.type == 1 && len3(r.c) > 0.f) { // TracerBase.h:396-400 -> localAdd
-      if ((unsigned)r.id < n_pix) {
-        const V3 c = scl3(r.c, r.w);
-        float *px = fb + (size_t)4 * (unsigned)r.id;
-        atomicAdd(px + 0, c.x); atomicAdd(px + 1, c.y); atomicAdd(px + 2, c.z); atomicAdd(px + 3, 1.f);
-      }
-    }
+    } else if (fb) deposit_shadow(fb, n_pix, r.type, r.c, r.w, (unsigned)r.id);
     if (next >= 0 && !queues[next].keep) next = -1; // shuffleDropRays: not this rank's domain
   }
   unsigned local = 0; // use_lds: offset inside the block's share of the destination; else: final slot

@@ -290,11 +290,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, 4) void k_shade(ShadeArgs A, MeshView 
       const float4 a = make_float4(r.o.x, r.o.y, r.o.z, r.t_min), b = make_float4(r.d.x, r.d.y, r.d.z, r.t_max);
       if (top_nearest(a, b, A.sink.top, inst, ret_t) < 0) {
         forward = false;
-        if (r.type == 1 && len3(r.c) > 0.f && (unsigned)r.id < A.sink.n_pix) {
-          const V3 cw = scl3(r.c, r.w);
-          float *px = A.sink.fb + (size_t)4 * (unsigned)r.id;
-          atomicAdd(px + 0, cw.x); atomicAdd(px + 1, cw.y); atomicAdd(px + 2, cw.z); atomicAdd(px + 3, 1.f);
-        }
+        deposit_shadow(A.sink.fb, A.sink.n_pix, r.type, r.c, r.w, (unsigned)r.id);
       }
     }
     const unsigned slot = block_alloc(A.out_count, forward, &sh_alloc[0]);

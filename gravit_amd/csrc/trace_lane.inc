@@ -107,6 +107,17 @@ __device__ __forceinline__ void node4_test(const uint4 *__restrict__ nd, const R
 #undef GVT_Q2
 }
 
+// tn / rr of the four children by ascending distance (a 5-compare network; equal distances keep their order, a miss -- GVT_FLT_MAX -- sorts last)
+__device__ __forceinline__ void sort4(float (&tn)[4], int (&rr)[4]) {
+  auto ce = [&](int a, int b) {
+    const bool sw = tn[b] < tn[a];
+    const float ta = sw ? tn[b] : tn[a], tb = sw ? tn[a] : tn[b];
+    const int ra = sw ? rr[b] : rr[a], rb = sw ? rr[a] : rr[b];
+    tn[a] = ta; tn[b] = tb; rr[a] = ra; rr[b] = rb;
+  };
+  ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2);
+}
+
 __device__ __forceinline__ int *kt_spill_ptr(int *spill_base, int k) {
   unsigned t = threadIdx.x;
   asm volatile("" : "+v"(t));
@@ -157,15 +168,7 @@ __device__ inline void flush_pending(volatile unsigned *pend, int n_pend, const 
         float ret_t;
         go_on = top_nearest(a, b, K.top, from, ret_t) >= 0;
       }
-      if (!go_on) {
-        const V3 col = mk3(c.x, c.y, c.z);
-        const unsigned id = (unsigned)__float_as_int(d.x);
-        if (__float_as_int(d.w) == 1 && len3(col) > 0.f && id < K.n_pix) { // TracerBase.h:396-400 -> IceTComposite::localAdd
-          const V3 cw = scl3(col, d.z);
-          float *px = K.fb + (size_t)4 * id;
-          atomicAdd(px + 0, cw.x); atomicAdd(px + 1, cw.y); atomicAdd(px + 2, cw.z); atomicAdd(px + 3, 1.f);
-        }
-      }
+      if (!go_on) deposit_shadow(K.fb, K.n_pix, __float_as_int(d.w), mk3(c.x, c.y, c.z), d.z, (unsigned)__float_as_int(d.x));
     }
     const unsigned long long m = ballot64(go_on);
     if (m) {
@@ -462,12 +465,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
         // (node address from a 32-bit byte offset: one shift, and the load takes base + offset -- the builder refuses trees of 2^26 nodes or more)
         node4_test<ANY>((const uint4 *)((const char *)(MULTI ? nodes4_l : T.nodes4) + ((unsigned)cur << 6)), S, GVT_FLT_MAX, tn, rr, ANY ? entered : nullptr);
 #define KT_ENTERED(K) (ANY ? entered[K] : (tn[K] <= lim2)) // (closest hit: tn / rr are sorted below, the flags are not)
-        if (!ANY) { // nearest first; for any-hit the order does not matter
-#define GVT_CE(A, B) { const bool sw_ = tn[B] < tn[A]; const float ta_ = sw_ ? tn[B] : tn[A], tb_ = sw_ ? tn[A] : tn[B]; \
-                     const int ra_ = sw_ ? rr[B] : rr[A], rb_ = sw_ ? rr[A] : rr[B]; tn[A] = ta_; tn[B] = tb_; rr[A] = ra_; rr[B] = rb_; }
-          GVT_CE(0, 1) GVT_CE(2, 3) GVT_CE(0, 2) GVT_CE(1, 3) GVT_CE(1, 2)
-#undef GVT_CE
-        }
+        if (!ANY) sort4(tn, rr); // nearest first; for any-hit the order does not matter
         // push the hit children farthest first (closest hit: sorted), continue with the first hit one
         int nxt = TRAV_DONE;
         bool have = false;

@@ -1011,6 +1011,61 @@ def test_random_scenes_through_the_native_schedulers(hip, seed):
         assert sum(r[1]["rays_closest"] for r in res.values()) == std.rays_closest and sum(r[1]["rays_sent"] for r in res.values()) == std.rays_sent
 
 
+def _coincident_deck_scene(n_inst):
+    """300 small triangles scattered around a deck of 1,500 coincident copies of one triangle (primIDs 300..1799), one mesh; a 32x32 film aimed at the
+    deck, one point light on the camera's side, depth 1.  n_inst = 2: a second instance of the mesh beside the first, off the film -- a mesh with
+    several instances gets the cluster layout, which a one-instance scene never builds."""
+    from gravit_amd.layouts import default_material, point_light
+    rng = np.random.default_rng(77)
+    ctr = rng.uniform([0.20, 0.30, 0.20], [0.46, 0.56, 0.70], (300, 1, 3))
+    one = np.array([[0.30, 0.40, 0.45], [0.36, 0.40, 0.45], [0.33, 0.46, 0.45]])
+    v = np.concatenate([ctr + rng.uniform(-0.005, 0.005, (300, 3, 3)), np.broadcast_to(one, (1500, 3, 3))]).reshape(-1, 3).astype(np.float32)
+    t = np.arange(len(v), dtype=np.int32).reshape(-1, 3)
+    mesh = scenes.MeshData(v, t, default_material(kd=(0.7, 0.6, 0.5)))
+    mats = [scenes.mat_translate_scale((0.4 * i, 0.0, 0.0), (1.0, 1.0, 1.0)) for i in range(n_inst)]
+    cam = scenes.Camera(eye=(0.33, 0.42, 1.5), focus=(0.33, 0.42, 0.45), up=(0.0, 1.0, 0.0), fov=0.115, width=32, height=32, depth=1)
+    return scenes._assemble([mesh], [0] * n_inst, mats, point_light((0.6, 0.7, 1.2)), cam, "coincident deck x%d" % n_inst), 300
+
+
+@pytest.mark.parametrize("n_inst", [1, 2])
+def test_wave_lists_throttle_on_coincident_triangles(hip, n_inst):
+    """The wave-per-ray traversal (trace_wave.inc wave_run) with its lists FULL: 1,500 coincident triangles are some 750 leaves at one distance, none of which
+    the cull can drop, so a ray that meets the deck has hundreds of entries pending at once -- more than the lists' CAP allows a node step to add to (k_finish:
+    384, k_long_closest / k_wave_any: 512): the steps are throttled, leaves are taken while nodes still wait.  Shadow rays start on the deck and enter every one
+    of its boxes again.  Through k_long_closest + k_wave_any from the root (small_rays), k_finish over the cluster layout (two instances; one instance: no
+    cluster layout is built) and over the plain nodes, and k_long_closest resuming rays parked after two steps: the oracle's image with tolerance 0, the
+    oracle's ray counts, the lowest coincident primID for every ray that hits the deck, and no list overflow reported."""
+    from gravit_amd.adapter import HipMeshAdapter
+    from tests.helpers import oracle_camera_rays, oracle_meshes
+
+    sc, first_coincident = _coincident_deck_scene(n_inst)
+    ref, st = oracle_render(sc, NORMALS_FLAT, nthreads=8)
+    rays = oracle_camera_rays(sc)
+    h_ref = oracle_meshes(sc)[0].intersect(rays["origin"], rays["direction"])  # (instance 0: the identity transform)
+    on_deck = h_ref["prim"] >= first_coincident
+    assert on_deck.sum() > 100 and (h_ref["prim"][on_deck] == first_coincident).all()  # the premise: the film sees the deck, the oracle reports its first copy
+    for opts in (dict(small_rays=1 << 30, finish_rays=0), dict(finish_rays=1 << 30), dict(finish_rays=1 << 30, finish_clusters=0),
+                 dict(long_steps=2, long_min_rays=0, small_rays=0, finish_rays=0)):
+        try:
+            for k, v in opts.items():
+                hip.set_option(k, v)
+            tr = NativeTracer(sc, NORMALS_FLAT)
+            fb = tr().framebuffer(True)
+            print(opts, "max colour difference", float(np.abs(fb[..., :3] - ref[..., :3]).max()), "rays", tr.stats["rays_closest"], tr.stats["rays_any"],
+                  "oracle", st.rays_closest, st.rays_any, "overflow word", hip.counters_peek()[8])
+            assert np.abs(fb[..., :3] - ref[..., :3]).max() <= 0.0 and np.array_equal(fb[..., 3], ref[..., 3]), opts
+            assert tr.stats["rays_closest"] == st.rays_closest and tr.stats["rays_any"] == st.rays_any, opts
+            assert hip.counters_peek()[8] == 0, opts
+            tr.close()
+            ad = HipMeshAdapter(sc.meshes[0], NORMALS_FLAT)
+            h = ad.intersect(rays["origin"], rays["direction"])
+            assert (h["prim"][on_deck] == first_coincident).all() and np.array_equal(h["prim"], h_ref["prim"]), opts
+            assert np.array_equal(h["t"].view(np.uint32), h_ref["t"].view(np.uint32)), opts
+            assert hip.counters_peek()[8] == 0, opts
+        finally:
+            hip.set_option("defaults", 0)
+
+
 @pytest.mark.parametrize("case", ["partly_off_film", "box_behind_the_eye_plane", "nothing_in_view", "jitter_window"])
 def test_camera_rectangle_edge_cases(hip, case):
     """The camera filter enumerates only the film rectangle the (kept) instances' boxes project onto (sched.hip camera_keep_rect).
