@@ -50,8 +50,8 @@ static int ctx_setup(Ctx &C, int device) {
   C.trav_blocks = std::max(C.n_cu, C.n_cu * 32 / (trav_block_threads() / 64)); // at most 8 waves per SIMD, whatever the block size
   const size_t spill_ints = (size_t)C.trav_blocks * trav_block_threads() * trav_spill_ints_per_thread();
   HIPCHK(hipMalloc((void **)&C.d_spill, spill_ints * sizeof(int)));
-  HIPCHK(hipMalloc((void **)&C.d_counters, 64 * sizeof(unsigned)));
-  HIPCHK(hipMemset(C.d_counters, 0, 64 * sizeof(unsigned)));
+  HIPCHK(hipMalloc((void **)&C.d_counters, CW_COUNT * sizeof(unsigned)));
+  HIPCHK(hipMemset(C.d_counters, 0, CW_COUNT * sizeof(unsigned)));
   HIPCHK(hipHostMalloc((void **)&C.h_pinned, 64 * sizeof(unsigned), hipHostMallocDefault));
   std::memset(C.h_pinned, 0, 64 * sizeof(unsigned));
   C.ready = true;
@@ -130,7 +130,7 @@ extern "C" void gvt_hip_ctx_destroy(gvt_hip_ctx *c) {
     for (Ctx *L : C->abi_lanes) gvt_hip_ctx_destroy((gvt_hip_ctx *)L);
     C->abi_lanes.clear();
     hipSetDevice(C->device);
-    for (int k = 0; k < 24; k++) if (C->scratch[k]) hipFree(C->scratch[k]);
+    for (int k = 0; k < SCRATCH_COUNT; k++) if (C->scratch[k]) hipFree(C->scratch[k]);
     hipFree(C->d_spill); hipFree(C->d_counters); hipHostFree(C->h_pinned);
     hipStreamDestroy(C->own_stream);
   }
@@ -154,7 +154,7 @@ extern "C" int gvt_hip_synchronize(void) {
   return 0;
 }
 
-void *scratch_get(int slot, size_t bytes) {
+void *scratch_get(ScratchSlot slot, size_t bytes) {
   Ctx &C = g_ctx;
   if (bytes <= C.scratch_bytes[slot] && C.scratch[slot]) return C.scratch[slot];
   hipStreamSynchronize(C.stream);
@@ -167,7 +167,7 @@ void *scratch_get(int slot, size_t bytes) {
   return C.scratch[slot];
 }
 
-void scratch_release(int slot) {
+void scratch_release(ScratchSlot slot) {
   Ctx &C = g_ctx;
   if (!C.scratch[slot]) return;
   hipStreamSynchronize(C.stream);
@@ -493,7 +493,7 @@ extern "C" int gvt_hip_queue_append_flags(gvt_hip_queue *q, const gvt_hip_ray *r
   if (rc) return rc;
   const gvt_hip_ray *d_src = rays;
   if (!src_on_device) {
-    void *stage = scratch_get(0, sizeof(gvt_hip_ray) * n);
+    void *stage = scratch_get(SCR_GENERAL, sizeof(gvt_hip_ray) * n);
     if (!stage) return GVT_HIP_ERR_DEVICE;
     HIPCHK(hipMemcpyAsync(stage, rays, sizeof(gvt_hip_ray) * n, hipMemcpyHostToDevice, C.stream));
     d_src = (const gvt_hip_ray *)stage;
@@ -515,7 +515,7 @@ extern "C" int gvt_hip_queue_export(gvt_hip_queue *q, gvt_hip_ray *dst, size_t c
   Ctx &C = g_ctx;
   gvt_hip_ray *d_dst = dst;
   if (!dst_on_device) {
-    d_dst = (gvt_hip_ray *)scratch_get(0, sizeof(gvt_hip_ray) * q->size);
+    d_dst = (gvt_hip_ray *)scratch_get(SCR_GENERAL, sizeof(gvt_hip_ray) * q->size);
     if (!d_dst) return GVT_HIP_ERR_DEVICE;
   }
   int rc = convert_planes_to_aos(make_planes(q->d_planes, q->cap), 0, q->size, d_dst);
@@ -756,8 +756,8 @@ extern "C" int gvt_hip_trace_ex(gvt_hip_mesh *M, gvt_hip_ray *rays, size_t n_ray
 // ---- rtcIntersect / rtcOccluded equivalents on object-space rays ----
 static int stage_od(const float *org, const float *dir, size_t n, RayPlanes &planes) {
   Ctx &C = g_ctx;
-  float *d_org = (float *)scratch_get(2, sizeof(float) * 6 * n);
-  float4 *d_pl = (float4 *)scratch_get(3, sizeof(float4) * 2 * n);
+  float *d_org = (float *)scratch_get(SCR_SHADOW, sizeof(float) * 6 * n);
+  float4 *d_pl = (float4 *)scratch_get(SCR_IDX_A, sizeof(float4) * 2 * n);
   if (!d_org || !d_pl) return GVT_HIP_ERR_DEVICE;
   float *d_dir = d_org + 3 * n;
   HIPCHK(hipMemcpyAsync(d_org, org, sizeof(float) * 3 * n, hipMemcpyHostToDevice, C.stream));
@@ -774,7 +774,7 @@ extern "C" int gvt_hip_intersect(gvt_hip_mesh *M, const float *org, const float 
   RayPlanes pl;
   int rc = stage_od(org, dir, n, pl);
   if (rc) return rc;
-  gvt_hip_hit *d_hits = (gvt_hip_hit *)scratch_get(0, sizeof(gvt_hip_hit) * n);
+  gvt_hip_hit *d_hits = (gvt_hip_hit *)scratch_get(SCR_GENERAL, sizeof(gvt_hip_hit) * n);
   if (!d_hits) return GVT_HIP_ERR_DEVICE;
   Mat4 id{};
   if ((rc = launch_closest(M, pl, nullptr, n, false, id, tnear, d_hits))) return rc;
@@ -792,7 +792,7 @@ extern "C" int gvt_hip_occluded(gvt_hip_mesh *M, const float *org, const float *
   RayPlanes pl;
   int rc = stage_od(org, dir, n, pl);
   if (rc) return rc;
-  int *d_flags = (int *)scratch_get(0, sizeof(int) * n);
+  int *d_flags = (int *)scratch_get(SCR_GENERAL, sizeof(int) * n);
   if (!d_flags) return GVT_HIP_ERR_DEVICE;
   Mat4 id{};
   if ((rc = launch_any_flags(M, pl, n, false, id, tnear, d_flags))) return rc;
@@ -811,7 +811,7 @@ extern "C" int gvt_hip_visit_stats(gvt_hip_mesh *M, const float *org, const floa
   RayPlanes pl;
   int rc = stage_od(org, dir, n, pl);
   if (rc) return rc;
-  unsigned *d_out = (unsigned *)scratch_get(0, 3 * n * sizeof(unsigned));
+  unsigned *d_out = (unsigned *)scratch_get(SCR_GENERAL, 3 * n * sizeof(unsigned));
   if (!d_out) return GVT_HIP_ERR_DEVICE;
   if ((rc = launch_visit_stats(M, pl, n, tnear, d_out))) return rc;
   HIPCHK(hipMemcpyAsync(counts, d_out, 3 * n * sizeof(unsigned), hipMemcpyDeviceToHost, C.stream));
@@ -831,7 +831,7 @@ extern "C" int gvt_hip_wide_visit_stats(gvt_hip_mesh *M, const float *org, const
   int rc = wide_root_marks(M, width, d_marks, &nw);
   RayPlanes pl;
   if (!rc) rc = stage_od(org, dir, n, pl);
-  unsigned *d_out = rc ? nullptr : (unsigned *)scratch_get(0, n * sizeof(unsigned));
+  unsigned *d_out = rc ? nullptr : (unsigned *)scratch_get(SCR_GENERAL, n * sizeof(unsigned));
   if (!rc && !d_out) rc = GVT_HIP_ERR_DEVICE;
   if (!rc) rc = launch_wide_visit_stats(M, pl, n, tnear, d_marks, d_out);
   if (!rc && hipMemcpyAsync(counts, d_out, n * sizeof(unsigned), hipMemcpyDeviceToHost, C.stream) != hipSuccess) rc = GVT_HIP_ERR_DEVICE;
@@ -895,7 +895,7 @@ extern "C" int gvt_hip_marked_visit_stats(gvt_hip_mesh *M, const float *org, con
   int rc = hipMemcpy(d_marks, marks, M->nNodes, hipMemcpyHostToDevice) == hipSuccess ? 0 : GVT_HIP_ERR_DEVICE;
   RayPlanes pl;
   if (!rc) rc = stage_od(org, dir, n, pl);
-  unsigned *d_out = rc ? nullptr : (unsigned *)scratch_get(0, n * sizeof(unsigned));
+  unsigned *d_out = rc ? nullptr : (unsigned *)scratch_get(SCR_GENERAL, n * sizeof(unsigned));
   if (!rc && !d_out) rc = GVT_HIP_ERR_DEVICE;
   if (!rc) rc = launch_wide_visit_stats(M, pl, n, tnear, d_marks, d_out);
   if (!rc && hipMemcpyAsync(counts, d_out, n * sizeof(unsigned), hipMemcpyDeviceToHost, C.stream) != hipSuccess) rc = GVT_HIP_ERR_DEVICE;
@@ -906,12 +906,13 @@ extern "C" int gvt_hip_marked_visit_stats(gvt_hip_mesh *M, const float *org, con
 }
 
 int debug_stamps(unsigned long long *out, int reset);
-// diagnostic: the launching context's counter words (work counters, parked-ray count [3], overflow flags [8]), after a synchronisation
+// diagnostic: the launching context's counter words 0..CW_PEEK-1 (enum CounterWord), after a synchronisation
 extern "C" int gvt_hip_counters_peek(uint32_t out[32]) {
+  static_assert(CW_PEEK == 32, "the ABI's array");
   Ctx &C = gctx();
   if (!out || !C.d_counters) { set_error("counters_peek: null"); return GVT_HIP_ERR_INVALID; }
   HIPCHK(hipStreamSynchronize(C.stream));
-  HIPCHK(hipMemcpy(out, C.d_counters, 32 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, C.d_counters, CW_PEEK * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 extern "C" int gvt_hip_is_experiments_build(void) {

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_math_probe(int kind, const float *__res
 __global__ void k_set_u32(unsigned *p, unsigned v) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = v; }
 // start of a trace call: moved_rays count := its current size, work counter / shadow count / next count := 0 (one launch, not three memsets)
 __global__ void k_trace_begin(unsigned *out_count, unsigned out_size, unsigned *counters) {
-  if (blockIdx.x == 0 && threadIdx.x < 5) counters[threadIdx.x] = 0u; // work counter, shadow count, next count, parked rays, their work counter
+  if (blockIdx.x == 0 && threadIdx.x < 5) counters[threadIdx.x] = 0u; // CW_WORK, CW_SHADOW, CW_BOUNCE_A, CW_LONG, CW_LONG_WORK
   if (blockIdx.x == 0 && threadIdx.x == 5) *out_count = out_size;
 }
 

@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void k_round_report(unsigned *const *__restric
   }
   if (threadIdx.x == 0) { sh_out = 0; sh_local = 0; }
   if (chain_end) { // the launch chain in front left its k_wave_end to this kernel: last pass's shadow rays into the frame total, traced queues cleared
-    if (threadIdx.x == 0) { unsigned long long *tot = (unsigned long long *)(counters + 16); tot[1] += counters[1]; }
+    if (threadIdx.x == 0) { cw_totals(counters)[TOT_ANY] += counters[CW_SHADOW]; }
     for (int i = threadIdx.x; i < n_inst; i += blockDim.x)
       if (chain_mask[i]) *count_ptr[i] = 0u;
   }
@@ -609,14 +609,14 @@ __global__ __launch_bounds__(256) void k_round_report(unsigned *const *__restric
     }
   }
   if (threadIdx.x == 0) {
-    tail[0] = counters[16]; tail[1] = counters[17]; tail[2] = counters[18]; tail[3] = counters[19];
-    tail[4] = counters[8]; tail[5] = overflow[0];
+    tail[0] = counters[CW_TOT_CLOSEST]; tail[1] = counters[CW_TOT_CLOSEST + 1]; tail[2] = counters[CW_TOT_ANY]; tail[3] = counters[CW_TOT_ANY + 1];
+    tail[4] = counters[CW_TRAV_OVF]; tail[5] = overflow[0];
     for (int k = 0; k < 4; k++) tail[6 + k] = (unsigned)bb[k];
-    tail[10] = counters[9]; // packets handed over by k_packet
-    tail[11] = counters[20] + counters[3]; // closest-hit rays parked for k_long_closest so far this frame (earlier launches + the last one)
+    tail[10] = counters[CW_PACKETS]; // packets handed over by k_packet
+    tail[11] = counters[CW_LONG_FRAME] + counters[CW_LONG]; // closest-hit rays parked for k_long_closest so far this frame (earlier launches + the last one)
     tail[12] = 0u;
     tail[13] = (speculative && spec) ? spec[SPEC_N] : 0u;
-    counters[0] = 0u;       // the work counter of the next small chain (k_finish starts from 0 without a memset in front)
+    counters[CW_WORK] = 0u; // the work counter of the next small chain (k_finish starts from 0 without a memset in front)
     if (spec) { // does the tick behind this one need the host?  (a pair's payload beyond the inline area, or this rank's error)
       unsigned slow = err_code ? 1u : 0u;
       for (int p = 0; p < world; p++) if (p != rank && ann[p * msg_ints + 1] > 0 && ann[p * msg_ints + 10] == 0) slow = 1u;
@@ -811,8 +811,8 @@ __global__ __launch_bounds__(256) void k_publish(const int *__restrict__ ann_in,
 __global__ void k_zero_totals(unsigned *c, unsigned *ovf, int fb_w, int fb_h, unsigned *const *__restrict__ count_ptr = nullptr, int n_inst = 0) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_inst; i += gridDim.x * blockDim.x) *count_ptr[i] = 0u;
   if (blockIdx.x) return;
-  if (threadIdx.x < 4) c[16 + threadIdx.x] = 0u;
-  if (threadIdx.x == 4) { *ovf = 0u; c[9] = 0u; c[0] = 0u; ovf[10] = 0u; ovf[11] = 0u; ovf[12] = 0u; c[3] = 0u; c[20] = 0u; }
+  if (threadIdx.x < 4) c[CW_TOT_CLOSEST + threadIdx.x] = 0u; // both 64-bit totals
+  if (threadIdx.x == 4) { *ovf = 0u; c[CW_PACKETS] = 0u; c[CW_WORK] = 0u; ovf[10] = 0u; ovf[11] = 0u; ovf[12] = 0u; c[CW_LONG] = 0u; c[CW_LONG_FRAME] = 0u; }
   if (threadIdx.x == 5) { int *bb = (int *)(ovf + 4); bb[0] = fb_w; bb[1] = fb_h; bb[2] = 0; bb[3] = 0; }
 }
 } // namespace
@@ -974,8 +974,7 @@ extern "C" gvt_hip_tracer *gvt_hip_tracer_create(gvt_hip_top *T, gvt_hip_mesh *c
     if (ok && C.finish_clusters && C.finish_rays > 0 && n_inst > 1 && M->d_nodes4) ok = build_nodes4c(M) == 0; // (once per mesh, under its own lock)
     I.nodes4 = M->d_nodes4; I.tris = M->d_tri;
     I.nodes4c = C.finish_clusters ? M->d_nodes4c : nullptr; I.root_entry4c = M->root_entry4c;
-    I.mv.slots = M->d_tri; I.mv.slot_of = M->d_slot_of; I.mv.verts = M->d_verts; I.mv.tris = M->d_tris; I.mv.normals = M->d_normals; I.mv.vcolors = M->d_vcolors;
-    I.mv.materials = M->d_materials; I.mv.n_mat = (unsigned)M->nMat; I.mv.face_mat = M->d_face_mat; I.mv.mat = M->mesh_mat;
+    I.mv = mesh_view(M);
   }
   R->round_bytes = (sizeof(WaveSeg) + sizeof(QueueDesc)) * n1 + ((n1 + 15) & ~(size_t)15);
   ok = ok && hipMalloc((void **)&R->d_insts, sizeof(WaveInst) * n1) == hipSuccess && hipMalloc(&R->d_round, R->round_bytes) == hipSuccess &&
@@ -1140,7 +1139,7 @@ int local_chain(gvt_hip_tracer *R, const std::vector<size_t> *extra_in, uint64_t
   // one-queue scene: same pointers, same bound)
   for (size_t k = (size_t)n_seg; k < (nI ? nI : 1); k++) std::memset(&R->h_segs[k], 0, sizeof(WaveSeg));
   if ((rc = round_tables_upload(R, st))) return rc;
-  int *d_from = (int *)scratch_get(17, sizeof(int) * bound);
+  int *d_from = (int *)scratch_get(SCR_OUT_FROM, sizeof(int) * bound);
   if (!d_from) return GVT_HIP_ERR_DEVICE;
   TraceParams P{};
   P.normal_mode = R->normal_mode; P.seed = 0; P.n_lights = nL; P.update_in_place = 0; P.carried_rng = 1;
@@ -1177,22 +1176,25 @@ int local_chain(gvt_hip_tracer *R, const std::vector<size_t> *extra_in, uint64_t
   }
   const bool single = one.mesh != nullptr;
   // several queues straight from the camera filter: the segments' lengths and beginnings from the count words (in the chain's first kernel)
-  const unsigned *n_dev0 = (count_on_device && !single) ? C.d_counters + 22 : nullptr;
+  ChainOpts O;
+  O.d_count_ptr = R->d_count_ptr; O.d_mask = R->d_mask; O.n_inst = (int)nI;
+  O.defer_end = defer_end && single;
+  O.n_dev0_multi = (count_on_device && !single) ? C.d_counters + CW_MERGED_N : nullptr;
   // several queues of camera rays in tile order, every traced mesh packet-friendly (or packets forced): the merged closest-hit launch walks packets too
   // (launches of a few hundred thousand rays over small meshes lose with packets -- 4 K waves, each a long serial walk: bunny.conf 0.243 -> 0.254 ms, the
   // 8-bunny grid 0.368 -> 0.407 -- where the hall cut into 8 slabs, 4.2 M camera rays, gains: 7.57 -> 7.25 ms; hence packet_min_rays)
-  bool multi_packets = !single && !P.hop && fresh_from_camera && C.camera_tile == 8 && (C.packet == 2 || (C.packet == 1 && N >= (size_t)C.packet_min_rays));
-  for (int k = 0; k < n_seg && multi_packets; k++) {
+  O.multi_packets = !single && !P.hop && fresh_from_camera && C.camera_tile == 8;
+  for (int k = 0; k < n_seg && O.multi_packets; k++) {
     const gvt_hip_mesh *Mk = R->meshes[R->h_segs[k].inst];
-    multi_packets = Mk && Mk->d_nodes4 && (C.packet == 2 || Mk->packet_ok);
+    O.multi_packets = Mk && Mk->d_nodes4 && walks_packets(C, Mk, N);
   }
   // every mesh of the round a plain LAMBERT one (no vertex colours, no per-face materials): with depth 1 and no area light the merged chain shades with k_shade's lean instantiation too
-  bool simple_meshes = !single;
-  for (int k = 0; k < n_seg && simple_meshes; k++) {
+  O.simple_meshes = !single;
+  for (int k = 0; k < n_seg && O.simple_meshes; k++) {
     const gvt_hip_mesh *Mk = R->meshes[R->h_segs[k].inst];
-    simple_meshes = Mk && !Mk->d_vcolors && !Mk->d_face_mat && Mk->mesh_mat.type == 0;
+    O.simple_meshes = Mk && plain_lambert(Mk);
   }
-  if ((rc = wave_trace_chain(W, N, passes, R->q_moved, d_from, P, R->lights.data(), single ? &one : nullptr, R->d_count_ptr, R->d_mask, (int)nI, defer_end && single, n_dev0, multi_packets, simple_meshes))) return rc;
+  if ((rc = wave_trace_chain(W, N, passes, R->q_moved, d_from, P, R->lights.data(), single ? &one : nullptr, O))) return rc;
   // one instance in the whole scene and the terminal rule applied inside the kernels: nothing can have moved
   if (exact) {
     if ((rc = shuffle_exact(R->top, R->q_moved, single ? nullptr : d_from, single ? one.inst : -1, R->queues.data(), R->fb))) return rc;

@@ -237,5 +237,5 @@ __global__ __launch_bounds__(256, 4) void k_finish(FinishArgs A) { // 4 waves pe
     }
     __builtin_amdgcn_wave_barrier(); // (convergent: the lanes meet again here -- move_on's lane-0 blocks -- not at the loop header's readfirstlane: wave_ticket)
   }
-  if (lane == 0 && (n_closest || n_any)) { atomicAdd(A.tot + 0, (unsigned long long)n_closest); atomicAdd(A.tot + 1, (unsigned long long)n_any); }
+  if (lane == 0 && (n_closest || n_any)) { atomicAdd(A.tot + TOT_CLOSEST, (unsigned long long)n_closest); atomicAdd(A.tot + TOT_ANY, (unsigned long long)n_any); }
 }

@@ -18,6 +18,32 @@
 #define GVT_FLT_MAX 3.402823466e+38f
 #define GVT_FLT_EPSILON 1.192092896e-07f
 
+// The words of a context's device counter array (Ctx::d_counters, gvt_internal.h), for host code and kernels alike.  The numbering is fixed:
+// gvt_hip_counters_peek shows words 0..CW_PEEK-1 and k_trace_begin / launch_closest zero CW_WORK..CW_LONG_WORK as one run.
+enum CounterWord {
+  CW_WORK = 0,         // work counter of the traversal launch in flight (k_trace's `counter`); reset: k_trace_begin, k_wave_pass_begin, k_shade (zero_word), k_round_report
+  CW_SHADOW = 1,       // shadow rays of the pass; reset: k_trace_begin / trace_core per pass, k_wave_pass_begin
+  CW_BOUNCE_A = 2,     // bounce list counts, alternating by pass (cw_bounce); reset: k_wave_pass_begin (both at pass 0, the current one afterwards),
+  CW_BOUNCE_B = 5,     //   k_trace_begin / trace_core per pass (A only: trace_core reads the count back)
+  CW_LONG = 3,         // closest-hit rays parked for k_long_closest; reset: k_trace_begin, k_wave_pass_begin, k_zero_totals
+  CW_LONG_WORK = 4,    // k_long_closest's work counter (its `counter`); reset: k_trace_begin, k_wave_pass_begin
+  CW_PKT_RETRY = 6,    // shadow rays of any-hit packets that bailed out (k_packet<true>); reset: k_wave_pass_begin
+  CW_TRAV_OVF = 8,     // set when a traversal stack would have exceeded its LDS levels + spill entries; reset: trav_overflow_result, after reporting it
+  CW_PACKETS = 9,      // packets handed over by k_packet; reset: k_zero_totals, k_cam1_count
+  CW_TOT_CLOSEST = 16, // the frame's 64-bit ray totals, closest (words 16-17) and any (18-19): cw_totals()[TOT_CLOSEST], [TOT_ANY];
+  CW_TOT_ANY = 18,     //   reset: k_zero_totals, k_cam1_count
+  CW_LONG_FRAME = 20,  // rays parked so far this frame, without the last launch's; reset: k_zero_totals, k_cam1_count
+  CW_MERGED_N = 22,    // length of a merged list only the device knows (k_wave_pass_begin writes it from the count words); never reset, written before it is read
+  CW_SHADOW_CLS = 24,  // SHADOW_CLASSES class counts of the ordered shadow list (shade.inc); reset: k_wave_pass_begin
+  CW_PEEK = 32,        // words gvt_hip_counters_peek copies out
+  CW_COUNT = 64        // words allocated
+};
+enum { TOT_CLOSEST = 0, TOT_ANY = 1 }; // the pair of 64-bit totals at CW_TOT_CLOSEST, as cw_totals() sees it
+__host__ __device__ inline unsigned long long *cw_totals(unsigned *c) { return (unsigned long long *)(c + CW_TOT_CLOSEST); }
+__host__ __device__ inline int cw_bounce(int pass) { return (pass & 1) ? CW_BOUNCE_B : CW_BOUNCE_A; } // the list pass `pass` WRITES (and pass + 1 reads)
+static_assert(CW_TOT_ANY == CW_TOT_CLOSEST + 2 && CW_LONG_FRAME == CW_TOT_ANY + 2, "k_cam1_count clears the totals and the parked total as one run of five words");
+static_assert(CW_LONG_WORK == 4 && CW_BOUNCE_A < 5 && CW_LONG < 5, "k_trace_begin / launch_closest zero words 0..4 as one run");
+
 struct V3 {
   float x, y, z;
 };

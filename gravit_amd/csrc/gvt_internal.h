@@ -19,9 +19,34 @@ struct PendingEvent {
 
 // tuning knobs (gvt_hip_set_option); results never depend on them.  "defaults" restores this initial state.
 // the shadow list of a single-mesh round in SHADOW_CLASSES regions (class = how long the primaries of a 64-ray tile took), their ray counts in the
-// context's counter words SHADOW_CLS_WORD.. (reset with the pass's other counters)
+// context's counter words CW_SHADOW_CLS.. (gvt_device.h; reset with the pass's other counters)
 #define SHADOW_CLASSES 8
-#define SHADOW_CLS_WORD 24
+static_assert(CW_SHADOW_CLS + SHADOW_CLASSES <= CW_PEEK, "the class counts are read through gvt_hip_counters_peek");
+static_assert(CW_SHADOW_CLS + SHADOW_CLASSES <= CW_COUNT && CW_PEEK <= CW_COUNT, "every named counter word lies inside the allocation");
+
+// The context's grow-only scratch buffers (Ctx::scratch, scratch_get).  A buffer belongs to ONE use per call chain in flight on the context's stream; the
+// sharing that exists is between calls that never overlap, and is listed here.
+enum ScratchSlot {
+  SCR_GENERAL,     // the per-call general buffer: the hit records of a trace call / a round's chain / gvt_hip_intersect, gvt_hip_occluded's flags, the visit-count
+                   // diagnostics' output, gvt_hip_math_probe's values, the AoS staging of queue import / export (api.hip)
+  SCR_SHADOW,      // a pass's shadow-ray list (trace.hip); the origin | direction upload of the object-space queries (api.hip stage_od)
+  SCR_IDX_A,       // the two bounce index lists of a chain, alternating by pass; A also: the query rays' planes (api.hip stage_od)
+  SCR_IDX_B,
+  SCR_LIGHTS,      // the device copy of the light list (Ctx::lights_cached_dst)
+  SCR_NEXT_INST,   // shuffles: every ray's next instance (sched.hip, volume.hip); the clamped framebuffer copy (sched.hip)
+  SCR_NEXT_T,      // shuffles: ... and its entry distance (sched.hip)
+  SCR_SORT_KEYS_IN, SCR_SORT_KEYS_OUT, SCR_SORT_VALS_IN, SCR_SORT_VALS_OUT, // ray sort (knob sort_rays)
+  SCR_SORT_TEMP, SCR_SORT_GATHER, // rocPRIM's temporary storage (lbvh.hip sort_pairs_u32) | the sorted rays' object-space copy (knob sort_gather)
+  SCR_BLOCK_COUNTS,// per-block destination counts of the ordered shuffles and the camera filter (sched.hip, volume.hip)
+  SCR_LONG,        // parked closest-hit rays and their saved stacks (long_scratch_bytes)
+  SCR_SHADOW_INST, SCR_OUT_FROM, // a round's chain: instance of every shadow ray | source instance of every ray it appends (domain.hip local_chain)
+  SCR_PKT_RETRY,   // shadow rays of any-hit packets that bailed out
+  SCR_STEPS,       // node steps per primary, for the class-ordered shadow list (knob shadow_order)
+  SCR_VOL_WORK, SCR_VOL_OVF, // the volume march's work counter and overflow flag (volume.hip)
+  SCR_BUILD,       // the builder's and the refit's temporaries (lbvh.hip); released again beyond 1 GiB
+  SCR_HOP,         // merged chains with hops: the instance every ray is in now
+  SCRATCH_COUNT
+};
 struct Knobs {
   int blocks_per_cu = 4; // k_trace grid: resident 256-thread blocks per CU
   int blocks_per_cu_closest = 5; // ... for closest-hit launches (0: blocks_per_cu); 5: 0.528 vs 0.554 ms per 1 M rays (4) and 0.552 (6); any-hit: 4 is best (5: 0.50 vs 0.40)
@@ -109,12 +134,12 @@ struct Ctx : Knobs {
   int cu_reserved = 0;   // compute units masked away from the context's stream for a communicator's own stream (knob comm_cus)
   int trav_blocks = 0;
   int *d_spill = nullptr;
-  unsigned *d_counters = nullptr; // small array of device counters (work fetch, temps)
+  unsigned *d_counters = nullptr; // CW_COUNT device counter words (enum CounterWord, gvt_device.h)
   // pinned host scratch for small read-backs
   unsigned *h_pinned = nullptr;
   // grow-only device scratch arenas (never freed inside hot calls)
-  void *scratch[24] = { nullptr };
-  size_t scratch_bytes[24] = { 0 };
+  void *scratch[SCRATCH_COUNT] = { nullptr };
+  size_t scratch_bytes[SCRATCH_COUNT] = { 0 };
   // light list of the last trace call (uploaded only when it changes)
   std::vector<unsigned char> lights_cached;
   const void *lights_cached_dst = nullptr;
@@ -134,8 +159,8 @@ inline bool staging_queues(Ctx &C) {
   if (!C.abi_qin) { C.abi_qin = gvt_hip_queue_create(0); C.abi_qout = gvt_hip_queue_create(0); }
   return C.abi_qin && C.abi_qout;
 }
-void *scratch_get(int slot, size_t bytes); // grow-only; contents NOT preserved on growth
-void scratch_release(int slot); // gives a slot's memory back (after a synchronisation of the context's stream)
+void *scratch_get(ScratchSlot slot, size_t bytes); // grow-only; contents NOT preserved on growth
+void scratch_release(ScratchSlot slot); // gives a slot's memory back (after a synchronisation of the context's stream)
 
 #define HIPCHK(expr)                                                                              \
   do {                                                                                            \
@@ -323,15 +348,26 @@ struct WaveSingle { // the launch has ONE segment: its queue planes and instance
   const unsigned *n_dev; // the first pass's ray count lives in device memory (the queue's count word; n_total is only its bound)
   int pass0_begun;       // the producer of the queue (k_cam1_scatter) has already done k_wave_pass_begin's pass-0 resets
 };
-// defer_end: the caller's next kernel (k_round_report) does k_wave_end's work
-// n_dev0_multi (merged kernels): device word holding the length of the merged list where only the device knows it; n_total is then a bound
+// what a round's chain is told beyond its rays; the defaults are "nothing of the kind"
+struct ChainOpts {
+  unsigned *const *d_count_ptr = nullptr; // the count words of the rank's queues by instance, and which of them this round traces: k_wave_end clears those
+  const unsigned char *d_mask = nullptr;
+  int n_inst = 0;
+  bool defer_end = false;                 // the caller's next kernel (k_round_report) does k_wave_end's work
+  const unsigned *n_dev0_multi = nullptr; // merged kernels: device word holding the length of the merged list where only the device knows it; n_total is then a bound
+  bool multi_packets = false;             // merged kernels, first pass: the queues hold camera rays in tile order over packet-friendly meshes -- closest hits through k_packet_multi
+  bool simple_meshes = false;             // merged kernels: every traced mesh is a plain_lambert one
+};
 int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue *out, int *d_out_from, const TraceParams &P,
-                     const gvt_hip_light *lights_host, const WaveSingle *single, unsigned *const *d_count_ptr, const unsigned char *d_mask, int n_inst,
-                     bool defer_end = false, const unsigned *n_dev0_multi = nullptr, bool multi_packets = false, bool simple_meshes = false);
-// multi_packets (merged kernels, first pass): the queues hold camera rays in tile order over packet-friendly meshes -- closest hits through k_packet_multi
+                     const gvt_hip_light *lights_host, const WaveSingle *single, const ChainOpts &O);
 int finish_round(const WaveSet &W, size_t n_total, const TraceParams &P, const gvt_hip_light *lights_host, const void *d_qdesc, const int *d_owner, int rank,
                  unsigned *d_queue_overflow, unsigned *const *d_count_ptr, const unsigned char *d_mask, const unsigned *spec_words = nullptr);
 bool finish_lights_resident(const gvt_hip_light *lights_host, int nL); // the context's device copy of the light list is this list (trace.hip)
+// the per-round decisions the chains and the tracer (domain.hip local_chain: only it has a round's host meshes) share
+MeshView mesh_view(const gvt_hip_mesh *M);
+bool walks_packets(const Ctx &C, const gvt_hip_mesh *M, size_t n); // a coherent list of n rays (bound) over M is traversed a packet per wave (knob packet)
+bool plain_lambert(const gvt_hip_mesh *M);                         // a LAMBERT mesh material, no vertex colours, no per-face materials: k_shade's LEAN instantiation may shade it
+bool no_area_light(const gvt_hip_light *lights, int nL);
 int convert_aos_to_planes(const gvt_hip_ray *d_src, size_t n, RayPlanes dst, size_t dst_off, bool keep_state);
 int convert_planes_to_aos(RayPlanes src, size_t src_off, size_t n, gvt_hip_ray *d_dst);
 int convert_od_to_planes(const float *d_org, const float *d_dir, size_t n, RayPlanes dst);

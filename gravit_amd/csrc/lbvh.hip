@@ -662,7 +662,7 @@ int build_lbvh(gvt_hip_mesh *M) {
     const size_t per_tri = 6 * sizeof(float4) + 2 * sizeof(unsigned long long) + 9 * sizeof(unsigned) + 4 * sizeof(int); // (+ k_node_boxes_chunk's spine lists)
     const size_t levels = 4 * sizeof(float4) * ((size_t)n / 31 + 64 * GVT_BOX_LEVELS);
     A.cap = per_tri * ((size_t)n + 1) + levels + tb_sort + tb_scan + 64 * 256 + 4096;
-    A.base = (char *)scratch_get(21, A.cap);
+    A.base = (char *)scratch_get(SCR_BUILD, A.cap);
     if (!A.base) { rc = GVT_HIP_ERR_DEVICE; goto done; }
   }
   mark("arena");
@@ -761,7 +761,7 @@ int build_lbvh(gvt_hip_mesh *M) {
   }
 done:
   hipStreamSynchronize(st);
-  if (A.cap > ((size_t)1 << 30)) scratch_release(21); // a large scene's temporaries are not kept
+  if (A.cap > ((size_t)1 << 30)) scratch_release(SCR_BUILD); // a large scene's temporaries are not kept
   hipEventDestroy(e0); hipEventDestroy(e1);
   return rc;
 #undef OK
@@ -774,7 +774,7 @@ int sort_pairs_u32(unsigned *keys_in, unsigned *keys_out, unsigned *vals_in, uns
   Ctx &C = gctx();
   size_t tb = 0;
   HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, C.stream));
-  void *tmp = scratch_get(12, tb ? tb : 16);
+  void *tmp = scratch_get(SCR_SORT_TEMP, tb ? tb : 16);
   if (!tmp) return GVT_HIP_ERR_DEVICE;
   HIPCHK(rocprim::radix_sort_pairs(tmp, tb, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, C.stream));
   return 0;
@@ -1175,7 +1175,7 @@ int refit_lbvh(gvt_hip_mesh *M) {
 #define OK(x) do { if ((rc = (x)) != 0) goto done; } while (0)
 #define HOK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { set_error("refit: %s: %s", #x, hipGetErrorString(_e)); rc = GVT_HIP_ERR_DEVICE; goto done; } } while (0)
   A.cap = 2 * sizeof(float4) * ((size_t)n + 1) + 4 * sizeof(float4) * ((size_t)n / 31 + 64 * GVT_BOX_LEVELS) + 16 * 256 + 4096;
-  A.base = (char *)scratch_get(21, A.cap);
+  A.base = (char *)scratch_get(SCR_BUILD, A.cap);
   if (!A.base) return GVT_HIP_ERR_DEVICE;
   OK(A.take(&slo, n)); OK(A.take(&shi, n)); OK(A.take(&d_scene, 8)); OK(A.take(&sah_acc, 1));
   k_refit_tris<<<G, B, 0, st>>>(M->d_verts, M->d_tris, n, M->d_tri, slo, shi);
@@ -1231,7 +1231,7 @@ int refit_lbvh(gvt_hip_mesh *M) {
   }
 done:
   hipStreamSynchronize(st);
-  if (A.cap > ((size_t)1 << 30)) scratch_release(21);
+  if (A.cap > ((size_t)1 << 30)) scratch_release(SCR_BUILD);
   return rc;
 #undef OK
 #undef HOK

@@ -232,8 +232,8 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_cam1_count(CamArgs A, unsigned n,
     for (int w = 0; w < TOP_BLOCK / 64; w++) tot += sh_w[w];
     blk_cnt[blockIdx.x] = tot;
   }
-  if (blockIdx.x == 0 && threadIdx.x < 5) c[16 + threadIdx.x] = 0u; // the frame's ray totals and parked-ray total (k_zero_totals)
-  if (blockIdx.x == 0 && threadIdx.x == 4) { *ovf = 0u; c[9] = 0u; }
+  if (blockIdx.x == 0 && threadIdx.x < 5) c[CW_TOT_CLOSEST + threadIdx.x] = 0u; // the frame's ray totals and parked-ray total, CW_TOT_CLOSEST..CW_LONG_FRAME (k_zero_totals)
+  if (blockIdx.x == 0 && threadIdx.x == 4) { *ovf = 0u; c[CW_PACKETS] = 0u; }
 }
 __global__ __launch_bounds__(TOP_BLOCK) void k_cam1_scatter(CamArgs A, unsigned n, TopDev top, const unsigned *__restrict__ blk_cnt, QueueDesc Q,
                                                             unsigned *__restrict__ overflow, unsigned *__restrict__ c, unsigned *__restrict__ moved_count) {
@@ -266,10 +266,10 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_cam1_scatter(CamArgs A, unsigned 
     unsigned total = base;
     for (int w = 0; w < TOP_BLOCK / 64; w++) total += sh_w[w];
     *Q.count = total;
-    unsigned long long *tot = (unsigned long long *)(c + 16); // k_wave_pass_begin, pass 0 (trace.hip)
-    *moved_count = 0u; c[2] = 0u; c[5] = 0u; tot[0] += total;
-    c[0] = 0u; c[1] = 0u; c[3] = 0u; c[4] = 0u; c[6] = 0u;
-    for (int k = 0; k < SHADOW_CLASSES; k++) c[SHADOW_CLS_WORD + k] = 0u;
+    unsigned long long *tot = cw_totals(c); // k_wave_pass_begin, pass 0 (trace.hip)
+    *moved_count = 0u; c[CW_BOUNCE_A] = 0u; c[CW_BOUNCE_B] = 0u; tot[TOT_CLOSEST] += total;
+    c[CW_WORK] = 0u; c[CW_SHADOW] = 0u; c[CW_LONG] = 0u; c[CW_LONG_WORK] = 0u; c[CW_PKT_RETRY] = 0u;
+    for (int k = 0; k < SHADOW_CLASSES; k++) c[CW_SHADOW_CLS + k] = 0u;
   }
 }
 
@@ -505,15 +505,15 @@ static int shuffle_impl(gvt_hip_top *T, const RaySrc &in, size_t n, int from, gv
   Ctx &C = gctx();
   if (!n) return 0;
   hipStream_t st = C.stream;
-  int *d_next = (int *)scratch_get(6, sizeof(int) * n);
-  float *d_t = (float *)scratch_get(7, sizeof(float) * n);
+  int *d_next = (int *)scratch_get(SCR_NEXT_INST, sizeof(int) * n);
+  float *d_t = (float *)scratch_get(SCR_NEXT_T, sizeof(float) * n);
   if (!d_next || !d_t) return GVT_HIP_ERR_DEVICE;
   const size_t nI = T->n;
   const int use_lds = (C.top_lds && nI > 0 && nI <= 4096) ? 1 : 0; // LDS counters per destination; beyond that straight to the global ones
   const unsigned n_blk = blocks_for(n, TOP_BLOCK);
   unsigned *d_blk = nullptr; // ordered mode: [destination][block] counts, then base slots
   if (C.top_ordered && use_lds && nI <= GVT_TOP_ORDERED_MAX) {
-    d_blk = (unsigned *)scratch_get(14, sizeof(unsigned) * nI * n_blk);
+    d_blk = (unsigned *)scratch_get(SCR_BLOCK_COUNTS, sizeof(unsigned) * nI * n_blk);
     if (!d_blk) return GVT_HIP_ERR_DEVICE;
   }
   // When every kept queue already has room for all n rays the scatter is launched right behind the classification and the
@@ -630,7 +630,7 @@ int camera_one_instance_async(gvt_hip_top *T, const gvt_hip_camera *cam, int til
   }
   if (!n_list) n_list = 1; // (nothing in view: one empty position, so that the kernels still publish the counts and do the resets)
   const unsigned n_blk = blocks_for(n_list, TOP_BLOCK);
-  unsigned *d_blk = (unsigned *)scratch_get(14, sizeof(unsigned) * n_blk);
+  unsigned *d_blk = (unsigned *)scratch_get(SCR_BLOCK_COUNTS, sizeof(unsigned) * n_blk);
   if (!d_blk) return GVT_HIP_ERR_DEVICE;
   QueueDesc Q{ q->d_planes, q->cap, q->d_count, 1u };
   {
@@ -647,15 +647,15 @@ static int shuffle_async_src(gvt_hip_top *T, const RaySrc &S, size_t n_ub, const
   Ctx &C = gctx();
   if (!n_ub) return 0;
   hipStream_t st = C.stream;
-  int *d_next = (int *)scratch_get(6, sizeof(int) * n_ub);
-  float *d_t = (float *)scratch_get(7, sizeof(float) * n_ub);
+  int *d_next = (int *)scratch_get(SCR_NEXT_INST, sizeof(int) * n_ub);
+  float *d_t = (float *)scratch_get(SCR_NEXT_T, sizeof(float) * n_ub);
   if (!d_next || !d_t) return GVT_HIP_ERR_DEVICE;
   const size_t nI = T->n;
   const int use_lds = (C.top_lds && nI > 0 && nI <= 4096) ? 1 : 0;
   const unsigned n_blk = blocks_for(n_ub, TOP_BLOCK);
   unsigned *d_blk = nullptr;
   if (C.top_ordered && use_lds && nI <= GVT_TOP_ORDERED_MAX) {
-    d_blk = (unsigned *)scratch_get(14, sizeof(unsigned) * nI * n_blk);
+    d_blk = (unsigned *)scratch_get(SCR_BLOCK_COUNTS, sizeof(unsigned) * nI * n_blk);
     if (!d_blk) return GVT_HIP_ERR_DEVICE;
   }
   const QueueDesc *qd = (const QueueDesc *)d_qdesc;
@@ -801,7 +801,7 @@ extern "C" int gvt_hip_fb_download(gvt_hip_fb *F, float *rgba, int clamp) {
   if (!F || !rgba) { set_error("fb_download: null"); return GVT_HIP_ERR_INVALID; }
   Ctx &C = gctx();
   const size_t n4 = (size_t)F->w * F->h;
-  float *tmp = (float *)scratch_get(6, sizeof(float) * 4 * n4);
+  float *tmp = (float *)scratch_get(SCR_NEXT_INST, sizeof(float) * 4 * n4);
   if (!tmp) return GVT_HIP_ERR_DEVICE;
   k_fb_clamp<<<blocks_for(n4), 256, 0, C.stream>>>(F->d_rgba, tmp, n4, clamp);
   HIPCHK(hipGetLastError());

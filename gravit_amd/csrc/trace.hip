@@ -11,9 +11,10 @@
 //   finish_kernel.inc  k_finish: a small scheduler round in one launch, every ray followed to its end on this rank
 //   convert.inc        80-byte Ray AoS <-> planes, ray sort keys, bookkeeping kernels;  diag_kernels.inc: the visit-count diagnostic
 // and this file keeps the host side:
+//   closest_step, any_step, shade_args, chain_bufs, ...   the steps every chain is made of, each written once
 //   trace_core         one Adapter::trace call: closest -> shade -> any per pass, one read-back per pass
-//   wave_trace_chain   the same chain for a whole scheduler ROUND (all non-empty local queues at once, MULTI kernel variants), ray counts in
-//                      device memory, no host round trip;  finish_round: k_finish
+//   wave_trace_chain   the same chain for a whole scheduler ROUND, ray counts in device memory, no host round trip: single_pass (one non-empty
+//                      local queue: the single-mesh kernels) or merged_pass (all of them at once: the MULTI variants);  finish_round: k_finish
 //
 // k_trace in one paragraph: a wave pulls index ranges from a device counter (an exit every wave reaches), refills lanes whose ray has finished
 // while the others go on, alternates a tight loop over the compressed 4-wide nodes with a leaf phase, keeps its traversal stacks in LDS
@@ -70,22 +71,25 @@ int trav_grid(size_t n) {
   return (int)(need < (size_t)C.trav_blocks ? (need ? need : 1) : (size_t)C.trav_blocks);
 }
 
-template <bool ANY, bool XFORM, int MODE, typename... Args> void launch_trace(int grid, hipStream_t st, RayPlanes q, const unsigned *idx, unsigned n, Mat4 minv, Args... args) {
+template <bool ANY, bool XFORM, int MODE, bool MULTI = false, typename... Args> void launch_trace(int grid, hipStream_t st, RayPlanes q, const unsigned *idx, unsigned n, Mat4 minv, Args... args) {
   // k_trace never reads the matrix's bottom row (an instance matrix is affine); it carries the direction transform's `translation x 0` terms there instead
   // (xfm_vector: m[12..14] * 0.0f, kept for parity with glm's mat4 * vec4(d, 0)): kernel arguments live in SCALAR registers, where the products computed on
   // the device sat in three vector registers for the whole launch -- spilled to scratch in the shipped closest-hit kernel
   minv.m[3] = minv.m[12] * 0.0f; minv.m[7] = minv.m[13] * 0.0f; minv.m[11] = minv.m[14] * 0.0f;
-  k_trace<ANY, XFORM, MODE><<<grid, TRAV_BLOCK, 0, st>>>(q, idx, n, minv, args...); // a mesh without 4-wide nodes has no triangles: every ray retires as a miss
+  k_trace<ANY, XFORM, MODE, MULTI><<<grid, TRAV_BLOCK, 0, st>>>(q, idx, n, minv, args...); // a mesh without 4-wide nodes has no triangles: every ray retires as a miss
 }
 
 // scratch of a closest-hit launch's parked rays: n records, then LONG_SAVE stack entries for each of the first LONG_STK_CAP of them
 static size_t long_scratch_bytes(size_t n) { return sizeof(LongRec) * n + sizeof(int) * LONG_SAVE * (size_t)LONG_STK_CAP; }
-static void long_limits(LongQ &LQ, size_t n) {
+static LongQ long_queue(LongRec *recs, size_t n) { // k_trace parks its long rays in recs[0, n), counted in CW_LONG
   Ctx &C = gctx();
+  LongQ LQ{};
+  LQ.recs = recs; LQ.count = C.d_counters + CW_LONG;
   LQ.steps = C.long_steps_override > 0 ? C.long_steps_override : C.long_steps;
   LQ.steps_drain = C.long_steps_drain > 0 && C.long_steps_drain < LQ.steps ? C.long_steps_drain : LQ.steps;
   LQ.stk = C.long_save ? (int *)(LQ.recs + n) : nullptr;
   LQ.stk_cap = LONG_STK_CAP;
+  return LQ;
 }
 
 // persistent-wave kernel: fewer, longer-lived waves so that every lane is refilled several times
@@ -114,14 +118,14 @@ int debug_stamps(unsigned long long *out, int reset) {
 // queued behind the traversal launches on the stream; read after the caller's next synchronisation through trav_overflow_result()
 int trav_overflow_fetch_async() {
   Ctx &C = gctx();
-  HIPCHK(hipMemcpyAsync(C.h_pinned + 8, C.d_counters + TRAV_OVF_WORD, sizeof(unsigned), hipMemcpyDeviceToHost, C.stream));
+  HIPCHK(hipMemcpyAsync(C.h_pinned + 8, C.d_counters + CW_TRAV_OVF, sizeof(unsigned), hipMemcpyDeviceToHost, C.stream));
   return 0;
 }
 int trav_overflow_result() {
   Ctx &C = gctx();
   if (!C.h_pinned[8]) return 0;
   C.h_pinned[8] = 0;
-  hipMemsetAsync(C.d_counters + TRAV_OVF_WORD, 0, sizeof(unsigned), C.stream);
+  hipMemsetAsync(C.d_counters + CW_TRAV_OVF, 0, sizeof(unsigned), C.stream);
   set_error("BVH traversal stack overflow (more than %d pending entries for one ray): results of this call are incomplete", TRAV_STACK + TRAV_SPILL);
   return GVT_HIP_ERR_DEVICE;
 }
@@ -150,37 +154,179 @@ int convert_od_to_planes(const float *d_org, const float *d_dir, size_t n, RayPl
   return 0;
 }
 
+// ---- the steps the launch chains below are made of ----
+MeshView mesh_view(const gvt_hip_mesh *M) {
+  MeshView mv;
+  mv.slots = M->d_tri; mv.slot_of = M->d_slot_of; mv.verts = M->d_verts; mv.tris = M->d_tris; mv.normals = M->d_normals; mv.vcolors = M->d_vcolors;
+  mv.materials = M->d_materials; mv.n_mat = (unsigned)M->nMat; mv.face_mat = M->d_face_mat; mv.mat = M->mesh_mat;
+  return mv;
+}
+// knob packet: 0 never, 1 the mesh's own choice (gvt_hip_mesh::packet_ok) in launches of at least packet_min_rays, 2 always
+bool walks_packets(const Ctx &C, const gvt_hip_mesh *M, size_t n) { return C.packet == 2 || (C.packet == 1 && M->packet_ok && n >= (size_t)C.packet_min_rays); }
+bool plain_lambert(const gvt_hip_mesh *M) { return !M->d_vcolors && !M->d_face_mat && M->mesh_mat.type == 0; }
+bool no_area_light(const gvt_hip_light *lights, int nL) { return std::all_of(lights, lights + nL, [](const gvt_hip_light &l) { return l.type != GVT_HIP_LIGHT_AREA; }); }
+
+// The light list rarely changes between calls: the context keeps a device copy (SCR_LIGHTS) and the host bytes it was made from.
+static bool lights_cached_at(const Ctx &C, const void *dst, const gvt_hip_light *lights_host, int nL) {
+  const size_t bytes = sizeof(gvt_hip_light) * (size_t)nL;
+  return C.lights_cached_dst == dst && C.lights_cached.size() == bytes && std::memcmp(C.lights_cached.data(), lights_host, bytes) == 0;
+}
+// the context's device copy of the light list is this list: a launch may use it without a copy
+bool finish_lights_resident(const gvt_hip_light *lights_host, int nL) {
+  Ctx &C = gctx();
+  return !nL || (C.scratch[SCR_LIGHTS] && lights_cached_at(C, C.scratch[SCR_LIGHTS], lights_host, nL));
+}
+// ... uploaded when it (or its scratch buffer) changed; may_upload = false: it must be resident already (no upload, no synchronisation in here)
+static int lights_on_device(const gvt_hip_light *lights_host, int nL, gvt_hip_light **d_lights, bool may_upload = true) {
+  Ctx &C = gctx();
+  *d_lights = (gvt_hip_light *)scratch_get(SCR_LIGHTS, sizeof(gvt_hip_light) * (nL > 0 ? nL : 1));
+  if (!*d_lights) return GVT_HIP_ERR_DEVICE;
+  if (!nL || lights_cached_at(C, *d_lights, lights_host, nL)) return 0;
+  if (!may_upload) { set_error("finish_round: a speculative launch needs the light list resident"); return GVT_HIP_ERR_INVALID; }
+  const size_t bytes = sizeof(gvt_hip_light) * (size_t)nL;
+  C.lights_cached.assign((const unsigned char *)lights_host, (const unsigned char *)lights_host + bytes);
+  C.lights_cached_dst = *d_lights;
+  HIPCHK(hipMemcpyAsync(*d_lights, C.lights_cached.data(), bytes, hipMemcpyHostToDevice, C.stream));
+  HIPCHK(hipStreamSynchronize(C.stream)); // pageable source: finish the copy before the cached bytes can change
+  return 0;
+}
+
+// The scratch a chain over n rays needs whatever its kernels: hits, the pass's shadow list, the two bounce index lists, the lights.
+struct ChainBufs {
+  gvt_hip_hit *hits; unsigned *idx_a, *idx_b; gvt_hip_light *lights;
+  size_t shadow_cap; RayPlanes shadow; // shadow rays a pass can emit, and their list: shadow_cap slots, or ordered_slots
+  unsigned char *steps;                // non-null: the class-ordered list was asked for and granted
+};
+// ordered_slots != 0: the class-ordered shadow list of that many slots (8 x 64 bytes per ray: 0.5 GB at the benchmark's 1.04 M rays) and the step counts it is
+// ordered by.  The ordering is an optimisation whose results do not depend on it: it must never make a frame fail that fits without it.  A device that
+// cannot give the 8x list falls back to arrival order with the plain list, for this context from then on (no allocation attempt per frame).
+static int chain_bufs(ChainBufs &B, size_t n, int nL, const gvt_hip_light *lights_host, size_t ordered_slots = 0) {
+  Ctx &C = gctx();
+  B.hits = (gvt_hip_hit *)scratch_get(SCR_GENERAL, sizeof(gvt_hip_hit) * n);
+  B.shadow_cap = n * (size_t)(nL > 0 ? nL : 1);
+  size_t slots = ordered_slots ? ordered_slots : B.shadow_cap;
+  float4 *d_shadow = (float4 *)scratch_get(SCR_SHADOW, sizeof(float4) * 4 * slots);
+  B.steps = (ordered_slots && d_shadow) ? (unsigned char *)scratch_get(SCR_STEPS, n) : nullptr;
+  if (ordered_slots && (!d_shadow || !B.steps)) {
+    (void)hipGetLastError(); // (the failed hipMalloc's sticky-less error)
+    C.shadow_order_denied = true;
+    B.steps = nullptr;
+    slots = B.shadow_cap;
+    d_shadow = (float4 *)scratch_get(SCR_SHADOW, sizeof(float4) * 4 * slots);
+  }
+  B.idx_a = (unsigned *)scratch_get(SCR_IDX_A, sizeof(unsigned) * n);
+  B.idx_b = (unsigned *)scratch_get(SCR_IDX_B, sizeof(unsigned) * n);
+  if (!B.hits || !d_shadow || !B.idx_a || !B.idx_b) return GVT_HIP_ERR_DEVICE;
+  B.shadow = make_planes(d_shadow, slots);
+  B.shadow.p4 = nullptr; B.shadow.p5 = nullptr; // shadow rays carry no stream and no list
+  return lights_on_device(lights_host, nL, &B.lights);
+}
+
+// Ray sorting (knob sort_rays): *idx becomes the list's first n entries (of a list of at most n_cap) in the order of k_ray_keys' key -- direction octant, then
+// the Morton cell of the object-space origin in M's box.  n_dev: the length where only the device knows it (the unused entries sort last).
+static int sort_ray_list(const gvt_hip_mesh *M, RayPlanes q, const unsigned **idx, size_t n, size_t n_cap, const Mat4 &minv, const unsigned *n_dev = nullptr) {
+  Ctx &C = gctx();
+  unsigned *k_in = (unsigned *)scratch_get(SCR_SORT_KEYS_IN, sizeof(unsigned) * n_cap), *k_out = (unsigned *)scratch_get(SCR_SORT_KEYS_OUT, sizeof(unsigned) * n_cap);
+  unsigned *v_in = (unsigned *)scratch_get(SCR_SORT_VALS_IN, sizeof(unsigned) * n_cap), *v_out = (unsigned *)scratch_get(SCR_SORT_VALS_OUT, sizeof(unsigned) * n_cap);
+  if (!k_in || !k_out || !v_in || !v_out) return GVT_HIP_ERR_DEVICE;
+  const float ex = M->hi[0] - M->lo[0], ey = M->hi[1] - M->lo[1], ez = M->hi[2] - M->lo[2];
+  const float3 blo = make_float3(M->lo[0], M->lo[1], M->lo[2]);
+  const float3 inv = make_float3(ex > 0 ? 1.f / ex : 0.f, ey > 0 ? 1.f / ey : 0.f, ez > 0 ? 1.f / ez : 0.f);
+  {
+    ProfScope ps(KC_SORT);
+    k_ray_keys<<<blocks_for(n), 256, 0, C.stream>>>(q, *idx, (unsigned)n, minv, blo, inv, k_in, v_in, C.sort_bits, n_dev);
+    if (int rc = sort_pairs_u32(k_in, k_out, v_in, v_out, n, C.sort_bits)) return rc;
+  }
+  HIPCHK(hipGetLastError());
+  *idx = v_out;
+  return 0;
+}
+
+// Where a traversal step's rays and geometry come from: one mesh (q, minv, T; W empty) or a round's segments (MULTI kernels: W; q, minv, T empty).
+struct TraceSrc { RayPlanes q; Mat4 minv; Trav T; WaveSet W; TermSink sink; MultiSrc MS; const int *hop; }; // hop: MultiSrc::hop_inst for the wave-per-ray kernels
+enum StepMode { BY_LANES, BY_PACKETS, BY_WAVES }; // k_trace (+ its parked rays a wave each) | k_packet (+ the packets that bailed out) | a wave per ray (small launches)
+static int wave_grid(size_t n) { return (int)std::min<size_t>((n + 3) / 4, (size_t)gctx().n_cu * 3); }
+
+// The closest-hit step over idx[0, n) (null: the identity; n_dev: the count where only the device knows it) into d_hits.  LQ.steps != 0: k_trace parks long rays;
+// d_long: the parked-ray records (BY_PACKETS and BY_WAVES use them whatever LQ says).  `later_pass`: a merged chain's bounce pass (the rays' hops are read).
+template <bool XFORM, bool MULTI>
+static void closest_step(StepMode mode, const TraceSrc &S, const unsigned *idx, size_t n, const unsigned *n_dev, float tnear, gvt_hip_hit *d_hits, const LongQ &LQ,
+                         LongRec *d_long, bool later_pass = false) {
+  Ctx &C = gctx();
+  hipStream_t st = C.stream;
+  unsigned *c = C.d_counters;
+  const int tail_grid = C.n_cu * 3; // 48 KiB of LDS per block
+  RayPlanes none{};
+  if (mode == BY_PACKETS) {
+    ProfScope ps(KC_CLOSEST);
+    LongQ LP{ d_long, c + CW_LONG, nullptr, 0u, 0, 0 };
+    if constexpr (MULTI) k_packet_multi<<<blocks_for(n), 256, 0, st>>>(S.W, (unsigned)n, n_dev, tnear, d_hits, LP, c + CW_PACKETS);
+    else k_packet<false><<<blocks_for(n), 256, 0, st>>>(S.q, (unsigned)n, n_dev, S.minv, S.T, tnear, d_hits, nullptr, none, nullptr, TermSink{}, LP, nullptr, nullptr, nullptr, c + CW_PACKETS);
+    k_long_closest<XFORM, MULTI><<<tail_grid, 256, 0, st>>>(S.q, d_long, c + CW_LONG, S.minv, S.T, tnear, d_hits, c + CW_LONG_WORK, S.W); // packets that bailed out
+  } else if (mode == BY_WAVES) {
+    ProfScope ps(KC_CLOSEST);
+    k_long_seed<<<blocks_for(n), 256, 0, st>>>(d_long, c + CW_LONG, idx, (unsigned)n, n_dev);
+    k_long_closest<XFORM, MULTI><<<wave_grid(n), 256, 0, st>>>(S.q, d_long, c + CW_LONG, S.minv, S.T, tnear, d_hits, c + CW_LONG_WORK, S.W, nullptr, later_pass ? S.hop : nullptr);
+  } else {
+    {
+      ProfScope ps(KC_CLOSEST);
+      launch_trace<false, XFORM, 0, MULTI>(trav_grid2(n, true), st, S.q, idx, (unsigned)n, S.minv, S.T, tnear, d_hits, nullptr, none, nullptr, c + CW_WORK, C.d_spill,
+                                           C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LQ, S.MS);
+    }
+    if (LQ.steps) {
+      ProfScope ps(KC_LONG);
+      k_long_closest<XFORM, MULTI><<<tail_grid, 256, 0, st>>>(S.q, LQ.recs, LQ.count, S.minv, S.T, tnear, d_hits, c + CW_LONG_WORK, S.W, LQ.stk, S.hop);
+    }
+  }
+}
+
+// The any-hit step over the shadow list S.q: un-occluded rays are appended to `out` or end in S.sink.  BY_LANES: idx / n / n_dev as k_trace takes them (n = 0: the
+// count is *n_dev), the grid sized for grid_rays;  BY_WAVES: the list's first CW_SHADOW rays.  (Any-hit packets are the single-mesh chain's own: any_packets.)
+template <bool MULTI>
+static void any_step(StepMode mode, const TraceSrc &S, const unsigned *idx, size_t grid_rays, unsigned n, const unsigned *n_dev, RayPlanes out, unsigned *out_count) {
+  Ctx &C = gctx();
+  unsigned *c = C.d_counters;
+  ProfScope ps(KC_ANY);
+  if (mode == BY_WAVES) k_wave_any<MULTI><<<wave_grid(grid_rays), 256, 0, C.stream>>>(S.q, c + CW_SHADOW, S.minv, S.T, GVT_RAY_EPSILON, out, out_count, c + CW_WORK, S.sink, S.MS);
+  else launch_trace<true, true, 1, MULTI>(trav_grid2(grid_rays), C.stream, S.q, idx, n, S.minv, S.T, GVT_RAY_EPSILON, nullptr, nullptr, out, out_count, c + CW_WORK, C.d_spill,
+                                          C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{}, S.MS);
+}
+
+// The fields of ShadeArgs every chain sets alike (the rest is zero); the caller adds its source (in or W), and what else differs.
+static ShadeArgs shade_args(const ChainBufs &B, const unsigned *idx, size_t n, int pass, const unsigned *n_dev, unsigned *next, unsigned *c_next, RayPlanes outp,
+                            unsigned *out_count, const TraceParams &P) {
+  unsigned *c = gctx().d_counters;
+  ShadeArgs A{};
+  A.idx = idx; A.n = (unsigned)n; A.hits = B.hits; A.first_pass = (pass == 0); A.carried_rng = 1; A.out = outp; A.out_count = out_count;
+  A.shadow = B.shadow; A.shadow_count = c + CW_SHADOW; A.next_idx = next; A.next_count = c_next; A.lights = B.lights; A.normi = P.normi; A.normal_mode = P.normal_mode;
+  A.n_lights = P.n_lights; A.seed = P.seed; A.zero_word = c + CW_WORK; A.sink = P.sink; A.n_dev = n_dev;
+  return A;
+}
+
+// The shade step over A.n rays; lean: k_shade's LEAN instantiation (shade.inc; the callers' conditions)
+template <bool MULTI>
+static void shade_step(const ShadeArgs &A, const MeshView &mv, bool lean = false) {
+  ProfScope ps(KC_SHADE);
+  if (lean) k_shade<MULTI, true><<<blocks_for(A.n, SHADE_BLOCK), SHADE_BLOCK, 0, gctx().stream>>>(A, mv);
+  else k_shade<MULTI><<<blocks_for(A.n, SHADE_BLOCK), SHADE_BLOCK, 0, gctx().stream>>>(A, mv);
+}
+
 int launch_closest(gvt_hip_mesh *M, RayPlanes q, const unsigned *idx, size_t n, bool xform, const Mat4 &minv, float tnear,
                    gvt_hip_hit *d_hits, bool counter_is_zero) {
   if (!n) return 0;
   Ctx &C = gctx();
   if (!M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
-  Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-  unsigned *counter = C.d_counters + 0;
-  if (!counter_is_zero) HIPCHK(hipMemsetAsync(C.d_counters, 0, 5 * sizeof(unsigned), C.stream));
+  if (!counter_is_zero) HIPCHK(hipMemsetAsync(C.d_counters, 0, (CW_LONG_WORK + 1) * sizeof(unsigned), C.stream)); // CW_WORK .. CW_LONG_WORK
   LongQ LQ{};
   if (M->d_nodes4 && C.long_steps > 0 && n >= (size_t)C.long_min_rays) { // long rays are parked and traversed a wave per ray
-    LQ.recs = (LongRec *)scratch_get(15, long_scratch_bytes(n));
-    if (!LQ.recs) return GVT_HIP_ERR_DEVICE;
-    LQ.count = C.d_counters + 3;
-    long_limits(LQ, n);
+    LongRec *recs = (LongRec *)scratch_get(SCR_LONG, long_scratch_bytes(n));
+    if (!recs) return GVT_HIP_ERR_DEVICE;
+    LQ = long_queue(recs, n);
   }
-  {
-    ProfScope ps(KC_CLOSEST);
-    RayPlanes none{};
-    if (xform) launch_trace<false, true, 0>(trav_grid2(n, true), C.stream, q, idx, (unsigned)n, minv, T, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
-    else launch_trace<false, false, 0>(trav_grid2(n, true), C.stream, q, idx, (unsigned)n, minv, T, tnear, d_hits, nullptr, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
-  }
-  if (LQ.steps) {
-    {
-      ProfScope ps(KC_LONG);
-      {
-        const int grid = C.n_cu * 3; // 48 KiB of LDS per block
-        if (xform) k_long_closest<true><<<grid, 256, 0, C.stream>>>(q, LQ.recs, LQ.count, minv, T, tnear, d_hits, C.d_counters + 4, WaveSet{}, LQ.stk);
-        else k_long_closest<false><<<grid, 256, 0, C.stream>>>(q, LQ.recs, LQ.count, minv, T, tnear, d_hits, C.d_counters + 4, WaveSet{}, LQ.stk);
-      }
-    }
-  }
+  TraceSrc S{};
+  S.q = q; S.minv = minv; S.T = Trav{ M->d_nodes, M->d_tri, M->d_nodes4 };
+  if (xform) closest_step<true, false>(BY_LANES, S, idx, n, nullptr, tnear, d_hits, LQ, LQ.recs);
+  else closest_step<false, false>(BY_LANES, S, idx, n, nullptr, tnear, d_hits, LQ, LQ.recs);
   HIPCHK(hipGetLastError());
   C.stats.rays_closest += n;
   C.stats.launches_closest++;
@@ -192,7 +338,7 @@ int launch_visit_stats(gvt_hip_mesh *M, RayPlanes q, size_t n, float tnear, unsi
   Ctx &C = gctx();
   if (!M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
   Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-  unsigned *counter = C.d_counters + 0;
+  unsigned *counter = C.d_counters + CW_WORK;
   HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), C.stream));
   k_visit_stats<<<trav_grid(n), TRAV_BLOCK, 0, C.stream>>>(q, (unsigned)n, T, tnear, d_out, counter, C.d_spill);
   HIPCHK(hipGetLastError());
@@ -203,7 +349,7 @@ int launch_wide_visit_stats(gvt_hip_mesh *M, RayPlanes q, size_t n, float tnear,
   if (!n) return 0;
   Ctx &C = gctx();
   Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-  unsigned *counter = C.d_counters + 0;
+  unsigned *counter = C.d_counters + CW_WORK;
   HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), C.stream));
   k_wide_visit_stats<<<trav_grid(n), TRAV_BLOCK, 0, C.stream>>>(q, (unsigned)n, T, tnear, d_marks, d_out, counter, C.d_spill);
   HIPCHK(hipGetLastError());
@@ -215,7 +361,7 @@ int launch_any_flags(gvt_hip_mesh *M, RayPlanes q, size_t n, bool xform, const M
   Ctx &C = gctx();
   if (!M->d_nodes4) { int rc4 = build_nodes4(M); if (rc4) return rc4; }
   Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-  unsigned *counter = C.d_counters + 0;
+  unsigned *counter = C.d_counters + CW_WORK;
   HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), C.stream));
   RayPlanes none{};
   {
@@ -238,60 +384,27 @@ int trace_core(gvt_hip_mesh *M, RayPlanes in, size_t n, uint64_t index_base, gvt
   if (!n) return 0;
   hipStream_t st = C.stream;
   const int nL = P.n_lights;
-  // scratch: hits, rng, shadow queue, two index lists, lights
-  gvt_hip_hit *d_hits = (gvt_hip_hit *)scratch_get(0, sizeof(gvt_hip_hit) * n);
-  const size_t shadow_cap = n * (size_t)(nL > 0 ? nL : 1);
-  float4 *d_shadow = (float4 *)scratch_get(2, sizeof(float4) * 4 * shadow_cap);
-  unsigned *d_idx_a = (unsigned *)scratch_get(3, sizeof(unsigned) * n);
-  unsigned *d_idx_b = (unsigned *)scratch_get(4, sizeof(unsigned) * n);
-  gvt_hip_light *d_lights = (gvt_hip_light *)scratch_get(5, sizeof(gvt_hip_light) * (nL > 0 ? nL : 1));
-  if (!d_hits || !d_shadow || !d_idx_a || !d_idx_b || !d_lights) return GVT_HIP_ERR_DEVICE;
-  { // the light list rarely changes between calls: upload only when it (or its scratch buffer) did
-    std::vector<unsigned char> &cached = C.lights_cached;
-    const void *&cached_dst = C.lights_cached_dst;
-    const size_t bytes = sizeof(gvt_hip_light) * (size_t)nL;
-    if (nL && (cached_dst != d_lights || cached.size() != bytes || std::memcmp(cached.data(), lights_host, bytes) != 0)) {
-      cached.assign((const unsigned char *)lights_host, (const unsigned char *)lights_host + bytes);
-      cached_dst = d_lights;
-      HIPCHK(hipMemcpyAsync(d_lights, cached.data(), bytes, hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st)); // pageable source: finish the copy before `cached` can change
-    }
-  }
-  RayPlanes shadow = make_planes(d_shadow, shadow_cap);
-  shadow.p4 = nullptr; shadow.p5 = nullptr; // shadow rays carry no stream and no list
+  ChainBufs B;
+  int rc = chain_bufs(B, n, nL, lights_host);
+  if (rc) return rc;
   RayPlanes outp = make_planes(out->d_planes, out->cap);
-  unsigned *c_shadow = C.d_counters + 1, *c_next = C.d_counters + 2;
-  k_trace_begin<<<1, 64, 0, st>>>(out->d_count, (unsigned)out->size, C.d_counters); // c_shadow, c_next, work counter
-
-  MeshView mv;
-  mv.slots = M->d_tri; mv.slot_of = M->d_slot_of; mv.verts = M->d_verts; mv.tris = M->d_tris; mv.normals = M->d_normals; mv.vcolors = M->d_vcolors;
-  mv.materials = M->d_materials; mv.n_mat = (unsigned)M->nMat; mv.face_mat = M->d_face_mat;
-  mv.mat = M->mesh_mat;
+  unsigned *c = C.d_counters;
+  static_assert(CW_BOUNCE_A == CW_SHADOW + 1, "the pass's two counts are reset and read back as one run");
+  k_trace_begin<<<1, 64, 0, st>>>(out->d_count, (unsigned)out->size, c); // CW_WORK .. CW_LONG_WORK
+  const MeshView mv = mesh_view(M);
+  TraceSrc SA{}; // the shadow rays' any-hit step
+  SA.q = B.shadow; SA.minv = P.minv; SA.T = Trav{ M->d_nodes, M->d_tri, M->d_nodes4 }; SA.sink = P.sink;
 
   size_t n_active = n;
   const size_t out_size0 = out->size;
   const unsigned *idx = nullptr;
-  unsigned *next = d_idx_a;
+  unsigned *next = B.idx_a;
   int pass = 0;
   while (n_active) { // while (validRayLeft) :465
-    int rc;
-    if (C.sort_rays && n_active >= 8192) { // ray sorting: traverse in Morton order of the object-space origin
-      unsigned *k_in = (unsigned *)scratch_get(8, sizeof(unsigned) * n), *k_out = (unsigned *)scratch_get(9, sizeof(unsigned) * n);
-      unsigned *v_in = (unsigned *)scratch_get(10, sizeof(unsigned) * n), *v_out = (unsigned *)scratch_get(11, sizeof(unsigned) * n);
-      if (!k_in || !k_out || !v_in || !v_out) return GVT_HIP_ERR_DEVICE;
-      const float ex = M->hi[0] - M->lo[0], ey = M->hi[1] - M->lo[1], ez = M->hi[2] - M->lo[2];
-      const float3 blo = make_float3(M->lo[0], M->lo[1], M->lo[2]);
-      const float3 inv = make_float3(ex > 0 ? 1.f / ex : 0.f, ey > 0 ? 1.f / ey : 0.f, ez > 0 ? 1.f / ez : 0.f);
-      {
-        ProfScope ps(KC_SORT);
-        k_ray_keys<<<blocks_for(n_active), 256, 0, st>>>(in, idx, (unsigned)n_active, P.minv, blo, inv, k_in, v_in, C.sort_bits);
-        if ((rc = sort_pairs_u32(k_in, k_out, v_in, v_out, n_active, C.sort_bits))) return rc;
-      }
-      HIPCHK(hipGetLastError());
-      idx = v_out;
-    }
+    // ray sorting: traverse in Morton order of the object-space origin
+    if (C.sort_rays && n_active >= 8192 && (rc = sort_ray_list(M, in, &idx, n_active, n, P.minv))) return rc;
     if (idx && C.sort_rays && C.sort_gather && n_active >= 8192) {
-      float4 *od = (float4 *)scratch_get(13, sizeof(float4) * 2 * n);
+      float4 *od = (float4 *)scratch_get(SCR_SORT_GATHER, sizeof(float4) * 2 * n);
       if (!od) return GVT_HIP_ERR_DEVICE;
       {
         ProfScope ps(KC_SORT);
@@ -299,39 +412,25 @@ int trace_core(gvt_hip_mesh *M, RayPlanes in, size_t n, uint64_t index_base, gvt
       }
       HIPCHK(hipGetLastError());
       RayPlanes sorted{ od, od + n, nullptr, nullptr, nullptr };
-      rc = launch_closest(M, sorted, nullptr, n_active, false, P.minv, GVT_RAY_EPSILON, d_hits, pass == 0);
+      rc = launch_closest(M, sorted, nullptr, n_active, false, P.minv, GVT_RAY_EPSILON, B.hits, pass == 0);
     } else
-      rc = launch_closest(M, in, idx, n_active, true, P.minv, GVT_RAY_EPSILON, d_hits, pass == 0);
+      rc = launch_closest(M, in, idx, n_active, true, P.minv, GVT_RAY_EPSILON, B.hits, pass == 0);
     if (rc) return rc;
-    if (pass > 0) HIPCHK(hipMemsetAsync(c_shadow, 0, 2 * sizeof(unsigned), st)); // c_shadow, c_next adjacent (pass 0: k_trace_begin)
-    ShadeArgs A{};
-    A.in = in; A.idx = idx; A.n = (unsigned)n_active; A.index_base = index_base; A.hits = d_hits;
-    A.first_pass = (pass == 0); A.carried_rng = P.carried_rng; A.out = outp; A.out_count = out->d_count; A.shadow = shadow; A.shadow_count = c_shadow;
-    A.next_idx = next; A.next_count = c_next; A.lights = d_lights; A.normi = P.normi; A.normal_mode = P.normal_mode;
-    A.n_lights = nL; A.seed = P.seed; A.zero_word = C.d_counters + 0;
-    A.sink = P.sink; A.update_in_place = P.update_in_place;
-    A.n_dev = nullptr; A.W = WaveSet{}; A.out_from = nullptr; A.shadow_inst = nullptr; A.shadow_stride = 0;
-    {
-      ProfScope ps(KC_SHADE);
-      k_shade<false><<<blocks_for(n_active, SHADE_BLOCK), SHADE_BLOCK, 0, st>>>(A, mv);
-    }
+    if (pass > 0) HIPCHK(hipMemsetAsync(c + CW_SHADOW, 0, 2 * sizeof(unsigned), st)); // CW_SHADOW, CW_BOUNCE_A (pass 0: k_trace_begin)
+    ShadeArgs A = shade_args(B, idx, n_active, pass, nullptr, next, c + CW_BOUNCE_A, outp, out->d_count, P);
+    A.in = in; A.index_base = index_base; A.carried_rng = P.carried_rng; A.update_in_place = P.update_in_place;
+    shade_step<false>(A, mv);
     HIPCHK(hipGetLastError());
     C.stats.rays_shaded += n_active;
     // traceShadowRays :364-385.  The shadow-ray count stays on the device (the persistent kernel reads it, the grid does not depend on it);
     // the host learns the counts of the pass in ONE read-back afterwards.
     const size_t shadow_ub = n_active * (size_t)nL;
     if (shadow_ub) {
-      Trav T{ M->d_nodes, M->d_tri, M->d_nodes4 };
-      unsigned *counter = C.d_counters + 0; // zeroed by k_shade
-      {
-        ProfScope ps(KC_ANY);
-        launch_trace<true, true, 1>(trav_grid2(shadow_ub), st, shadow, nullptr, 0u, P.minv, T, GVT_RAY_EPSILON, nullptr, nullptr, outp,
-                                    out->d_count, counter, C.d_spill, C.refill_min, C.inner_min, c_shadow, C.share, (unsigned)C.share_min_rays, P.sink, LongQ{});
-      }
+      any_step<false>(BY_LANES, SA, nullptr, shadow_ub, 0u, c + CW_SHADOW, outp, out->d_count); // (the work counter: zeroed by k_shade)
       HIPCHK(hipGetLastError());
       C.stats.launches_any++;
     }
-    HIPCHK(hipMemcpyAsync(C.h_pinned, c_shadow, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(C.h_pinned, c + CW_SHADOW, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(C.h_pinned + 2, out->d_count, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     if ((rc = trav_overflow_fetch_async())) return rc;
     HIPCHK(hipStreamSynchronize(st));
@@ -340,7 +439,7 @@ int trace_core(gvt_hip_mesh *M, RayPlanes in, size_t n, uint64_t index_base, gvt
     C.stats.rays_any += n_shadow;
     n_active = n_next;
     idx = next;
-    next = (next == d_idx_a) ? d_idx_b : d_idx_a;
+    next = (next == B.idx_a) ? B.idx_b : B.idx_a;
     pass++;
     if (n_active) { // a further pass (bounces): room for everything IT can emit -- a forward or nL shadow rays per ray -- behind what is there
       out->size = C.h_pinned[2];
@@ -358,7 +457,7 @@ extern "C" int gvt_hip_math_probe(int kind, const float *in, size_t n, float *ou
   if (kind < 0 || kind > 2 || (n && (!in || !out)) || n > 0xffffffffull) { set_error("math_probe: bad argument"); return GVT_HIP_ERR_INVALID; }
   if (!n) return 0;
   Ctx &C = gctx();
-  float *d = (float *)scratch_get(0, sizeof(float) * 2 * n);
+  float *d = (float *)scratch_get(SCR_GENERAL, sizeof(float) * 2 * n);
   if (!d) return GVT_HIP_ERR_DEVICE;
   HIPCHK(hipMemcpyAsync(d, in, sizeof(float) * n, hipMemcpyHostToDevice, C.stream));
   k_math_probe<<<blocks_for(n), 256, 0, C.stream>>>(kind, d, (unsigned)n, d + n);
@@ -371,9 +470,6 @@ extern "C" int gvt_hip_math_probe(int kind, const float *in, size_t n, float *ou
 // ------------------------------------------------------------------------------------------------
 // Merged launch chain of one scheduler round (gvt_internal.h "wave"): closest hit -> shade -> any hit over the rays of all local
 // queues at once, `passes` times (bounces), WITHOUT any host round trip: later passes read their ray count from device memory.
-// Device counters of the context (d_counters): [0] work counter, [1] shadow rays of the pass, [2] / [5] bounce list counts
-// (alternating), [3] parked long rays, [4] their work counter, [8] stack overflow flag, [16..19] two 64-bit ray totals
-// (closest, any) accumulated over the frame and read back with the queue sizes.
 // ------------------------------------------------------------------------------------------------
 namespace {
 // segs (pass 0 of a merged chain whose queues were filled by the camera filter without a read-back; the host uploaded the segments with
@@ -387,263 +483,182 @@ __global__ void k_wave_pass_begin(unsigned *c, int pass, unsigned n_host, unsign
     for (int k = 0; k < n_seg; k++) { const unsigned n = *count_ptr[segs[k].inst]; segs[k].begin = run; segs[k].n = n; run += n; }
     *const_cast<unsigned *>(n_dev0) = run;
   }
-  unsigned long long *tot = (unsigned long long *)(c + 16);
-  const int cur = (pass & 1) ? 5 : 2, prev = (pass & 1) ? 2 : 5;
-  if (pass == 0) { *out_count = 0u; c[2] = 0u; c[5] = 0u; tot[0] += n_dev0 ? *n_dev0 : n_host; }
-  else { tot[1] += c[1]; tot[0] += c[prev]; c[cur] = 0u; }
-  c[20] += c[3]; // rays parked by the launch before (the frame's total: the tracer adapts its parking threshold to it)
-  c[0] = 0u; c[1] = 0u; c[3] = 0u; c[4] = 0u; c[6] = 0u;
-  for (int k = 0; k < SHADOW_CLASSES; k++) c[SHADOW_CLS_WORD + k] = 0u; // the shadow list's class counts (shade.inc)
+  unsigned long long *tot = cw_totals(c);
+  const int cur = cw_bounce(pass), prev = cw_bounce(pass + 1);
+  if (pass == 0) { *out_count = 0u; c[CW_BOUNCE_A] = 0u; c[CW_BOUNCE_B] = 0u; tot[TOT_CLOSEST] += n_dev0 ? *n_dev0 : n_host; }
+  else { tot[TOT_ANY] += c[CW_SHADOW]; tot[TOT_CLOSEST] += c[prev]; c[cur] = 0u; }
+  c[CW_LONG_FRAME] += c[CW_LONG]; // rays parked by the launch before (the frame's total: the tracer adapts its parking threshold to it)
+  c[CW_WORK] = 0u; c[CW_SHADOW] = 0u; c[CW_LONG] = 0u; c[CW_LONG_WORK] = 0u; c[CW_PKT_RETRY] = 0u;
+  for (int k = 0; k < SHADOW_CLASSES; k++) c[CW_SHADOW_CLS + k] = 0u; // the shadow list's class counts (shade.inc)
 }
 // end of a round's chain: the last pass's shadow rays into the frame total; and the traced queues' clear() (count words of the
 // queues whose mask byte is set) in the same launch
 __global__ void k_wave_end(unsigned *c, unsigned *const *__restrict__ count_ptr, const unsigned char *__restrict__ mask, int n_inst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) { unsigned long long *tot = (unsigned long long *)(c + 16); tot[1] += c[1]; }
+  if (i == 0) cw_totals(c)[TOT_ANY] += c[CW_SHADOW];
   if (count_ptr && i < n_inst && mask[i]) *count_ptr[i] = 0u;
 }
 } // namespace
 
+// what the passes of a round's chain share, whichever kernels they use
+struct Chain {
+  size_t n; int passes; // rays of pass 0 (or their bound): what every launch is sized by
+  const TraceParams &P; const gvt_hip_light *lights_host; gvt_hip_queue *out; RayPlanes outp;
+  ChainBufs B;
+  int *d_shadow_inst;   // instance of every shadow ray (merged kernels; any-hit packets: < 0 marks an empty slot)
+  LongRec *d_long;
+  bool use_long, small; // k_trace parks long rays | a wave per ray (see k_long_seed)
+  const unsigned *nd0;  // pass 0's ray count where only the device knows it
+};
+// a pass's ray count on the device (null: K.n), its list (null: the identity), the bounce list it writes and that list's count word
+struct Pass { int pass; const unsigned *n_dev, *idx; unsigned *next, *c_next; };
+
+// shadow rays as packets (single-mesh chains, knob packet = 2): the direct-mapped list a packet of 64 per wave, then the rays of packets that bailed out a
+// lane per ray (an empty list costs a few microseconds)
+static int any_packets(const Chain &K, const TraceSrc &S) {
+  Ctx &C = gctx();
+  unsigned *c = C.d_counters;
+  unsigned *d_retry = (unsigned *)scratch_get(SCR_PKT_RETRY, sizeof(unsigned) * K.B.shadow_cap);
+  if (!d_retry) return GVT_HIP_ERR_DEVICE;
+  ProfScope ps(KC_ANY);
+  k_packet<true><<<blocks_for(K.B.shadow_cap), 256, 0, C.stream>>>(S.q, (unsigned)K.B.shadow_cap, nullptr, S.minv, S.T, GVT_RAY_EPSILON, nullptr, K.d_shadow_inst, K.outp, K.out->d_count,
+                                                                 S.sink, LongQ{}, d_retry, c + CW_PKT_RETRY, cw_totals(c) + TOT_ANY, c + CW_PACKETS);
+  launch_trace<true, true, 1>(trav_grid2(4096), C.stream, S.q, d_retry, 0u, S.minv, S.T, GVT_RAY_EPSILON, nullptr, nullptr, K.outp, K.out->d_count, c + CW_WORK, C.d_spill,
+                              C.refill_min, C.inner_min, c + CW_PKT_RETRY, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{});
+  return 0;
+}
+
+// One segment (a single non-empty local queue, e.g. the one-domain benchmark): the single-mesh kernels -- no segment lookup and no per-ray table loads at a
+// refill -- with the same device-side counts.  Its own: bounce sorting, packets for the shadow rays, the class-ordered shadow list (cls_stride slots per class).
+static int single_pass(const Chain &K, Pass p, const WaveSingle &W1, size_t cls_stride) {
+  Ctx &C = gctx();
+  unsigned *c = C.d_counters;
+  gvt_hip_mesh *M = W1.mesh;
+  const size_t n = K.n;
+  const int nL = K.P.n_lights;
+  const bool have4 = M->d_nodes4 != nullptr, by_class = K.B.steps != nullptr;
+  // ray sorting where it should pay (knob sort_rays, off by default: measured, profiles/r06_sort_cfg5.txt): a BOUNCE list -- secondary rays in their parents'
+  // order, i.e. neighbours in the list leave neighbouring surface points in unrelated directions -- is reordered by direction octant, then the Morton cell of the
+  // ray's origin (k_ray_keys) before the closest-hit launch; the pass's shadow rays inherit the order (k_shade allocates their slots in list order).  The list's
+  // length lives on the device: all n entries of the bound are sorted, the unused ones with the largest key
+  if (C.sort_rays && p.pass > 0 && n >= 8192 && have4)
+    if (int rc = sort_ray_list(M, W1.planes, &p.idx, n, n, W1.minv, p.n_dev)) return rc;
+  TraceSrc S{};
+  S.q = W1.planes; S.minv = W1.minv; S.T = Trav{ M->d_nodes, M->d_tri, M->d_nodes4 };
+  LongQ LQ{};
+  if (K.use_long && have4) LQ = long_queue(K.d_long, n);
+  LQ.steps_out = K.B.steps;
+  const bool small1 = K.small && have4;
+  // a coherent list (camera rays in 8x8 tiles, straight from the filter) over a mesh the builder found packet-friendly (walks_packets): a wave walks the tree
+  // ONCE for 64 rays (k_packet) -- the reference chooses its packet width per build as well (EmbreeMeshAdapter.cpp:50-74)
+  const bool pkt = walks_packets(C, M, n) && W1.coherent && p.pass == 0 && have4 && !small1;
+  // ... the CLOSEST hit, that is.  Shadow rays as packets lost on both surfaces they were measured on (bun_zipper any hit 0.162 -> 0.189 ms, the hall
+  // 1.23 -> 1.33: an any-hit packet goes on until its LAST ray is occluded or through): under the per-mesh choice they stay a lane per ray; 2 forces both
+  const bool pkt_any = pkt && C.packet == 2;
+  closest_step<true, false>(pkt ? BY_PACKETS : small1 ? BY_WAVES : BY_LANES, S, p.idx, n, p.n_dev, GVT_RAY_EPSILON, K.B.hits, LQ, K.d_long);
+  ShadeArgs A = shade_args(K.B, p.idx, n, p.pass, p.n_dev, p.next, p.c_next, K.outp, K.out->d_count, K.P);
+  A.in = W1.planes; A.normi = W1.normi; A.sink.from = W1.inst;
+  if (pkt_any) { A.shadow_inst = K.d_shadow_inst; A.shadow_stride = (unsigned)n; } // shadow rays in the primaries' order: packets again
+  A.steps = K.B.steps; A.cls_cnt = by_class ? c + CW_SHADOW_CLS : nullptr; A.cls_stride = (unsigned)cls_stride; A.cls_lo = C.shadow_cls_lo; A.cls_shift = C.shadow_cls_shift;
+  // the simple frame (k_shade's LEAN instantiation): camera rays of the scene's only instance, depth 1, no area light, a LAMBERT mesh material
+  const bool lean_shade = W1.coherent && p.pass == 0 && K.passes == 1 && K.P.sink.fb && K.P.sink.top.n_inst == 1 && nL >= 1 && plain_lambert(M) && no_area_light(K.lights_host, nL);
+  shade_step<false>(A, mesh_view(M), lean_shade);
+  if (!nL) return 0;
+  TraceSrc SA = S;
+  SA.q = K.B.shadow; SA.sink = A.sink;
+  if (pkt_any) return any_packets(K, SA);
+  if (by_class) { SA.MS.cls_cnt = c + CW_SHADOW_CLS; SA.MS.cls_stride = (unsigned)cls_stride; SA.MS.cls_total = c + CW_SHADOW; }
+  any_step<false>(small1 ? BY_WAVES : BY_LANES, SA, nullptr, K.B.shadow_cap, 0u, by_class ? nullptr : c + CW_SHADOW, K.outp, K.out->d_count);
+  return 0;
+}
+
+// Several segments: the MULTI kernels.  Their own: hops (d_hop), direct-mapped shadow slots, the source instance of every ray appended (d_out_from).
+static void merged_pass(const Chain &K, const Pass &p, const WaveSet &W, const ChainOpts &O, int *d_hop, int *d_out_from) {
+  Ctx &C = gctx();
+  unsigned *c = C.d_counters;
+  const TraceParams &P = K.P;
+  const size_t n = K.n;
+  const int nL = P.n_lights;
+  TraceSrc S{};
+  S.W = W; S.MS.W = W; S.hop = d_hop;
+  if (d_hop) {
+    S.sink = P.sink;
+    S.MS.hop_inst = d_hop; S.MS.hop_read = p.pass > 0; S.MS.hop_owner = P.hop_owner; S.MS.hop_rank = P.hop_rank; S.MS.hop_tot = cw_totals(c) + TOT_CLOSEST; S.MS.hop_early = P.hop == 1 ? 1 : 0;
+  }
+  LongQ LQ{};
+  if (K.use_long) LQ = long_queue(K.d_long, n);
+  // the round's queues hold camera rays in tile order, over packet-friendly meshes only: the closest hits a packet of 64 rays per wave
+  const bool pktm = O.multi_packets && p.pass == 0 && !K.small && p.idx == nullptr;
+  closest_step<true, true>(pktm ? BY_PACKETS : K.small ? BY_WAVES : BY_LANES, S, p.idx, n, p.n_dev, GVT_RAY_EPSILON, K.B.hits, LQ, K.d_long, p.pass > 0);
+  ShadeArgs A = shade_args(K.B, p.idx, n, p.pass, p.n_dev, p.next, p.c_next, K.outp, K.out->d_count, P);
+  A.W = W; A.out_from = d_out_from; A.shadow_inst = K.d_shadow_inst; A.hop_inst = d_hop;
+  const bool direct = C.shadow_direct && p.pass == 0 && !K.small; // later passes and small rounds hold few rays: compacted slots
+  // (k_shade marks every slot below the stride -- the bound -- empty or taken; with one light the list is as long as the traced one,
+  // and where only the device knows that length the any-hit launch stops there instead of skipping empty slots up to the bound)
+  const bool direct_dev = direct && K.nd0 != nullptr && nL == 1;
+  A.shadow_stride = direct ? (unsigned)n : 0u;
+  // (k_shade's LEAN instantiation for the merged chain: depth 1, no area light, plain LAMBERT meshes; a missing ray still walks the instances ahead of it)
+  const bool lean_multi = O.simple_meshes && p.pass == 0 && K.passes == 1 && nL >= 1 && no_area_light(K.lights_host, nL);
+  shade_step<true>(A, MeshView{}, lean_multi);
+  if (!nL) return;
+  TraceSrc SA{};
+  SA.q = K.B.shadow; SA.sink = P.sink;
+  SA.MS = MultiSrc{ W, K.d_shadow_inst, d_out_from, direct ? cw_totals(c) + TOT_ANY : nullptr };
+  // (an un-occluded shadow ray goes on the same way -- not in the early mode: 1.372 -> 1.340 ms on the soup tiles without)
+  if (d_hop && P.sink.fb && P.hop == 2) { SA.MS.hop_owner = P.hop_owner; SA.MS.hop_rank = P.hop_rank; SA.MS.hop_tot = cw_totals(c) + TOT_CLOSEST; }
+  if (K.small) any_step<true>(BY_WAVES, SA, nullptr, K.B.shadow_cap, 0u, nullptr, K.outp, K.out->d_count);
+  else any_step<true>(BY_LANES, SA, nullptr, K.B.shadow_cap, direct ? (unsigned)K.B.shadow_cap : 0u, direct ? (direct_dev ? K.nd0 : nullptr) : c + CW_SHADOW, K.outp, K.out->d_count);
+}
+
 int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue *out, int *d_out_from, const TraceParams &P,
-                     const gvt_hip_light *lights_host, const WaveSingle *single, unsigned *const *d_count_ptr, const unsigned char *d_mask, int n_inst,
-                     bool defer_end, const unsigned *n_dev0_multi, bool multi_packets, bool simple_meshes) {
+                     const gvt_hip_light *lights_host, const WaveSingle *single, const ChainOpts &O) {
   Ctx &C = gctx();
   if (!n_total) return 0;
   hipStream_t st = C.stream;
   const int nL = P.n_lights;
   const size_t n = n_total;
-  gvt_hip_hit *d_hits = (gvt_hip_hit *)scratch_get(0, sizeof(gvt_hip_hit) * n);
-  const size_t shadow_cap = n * (size_t)(nL > 0 ? nL : 1);
   // a single-mesh round with one light: the shadow rays listed by how long their primaries' tiles took, the longest first (knob shadow_order; shade.inc) --
   // SHADOW_CLASSES regions of `cls_stride` slots; not for packets (no per-ray step counts) nor small rounds (a wave per ray)
   const bool by_class_wanted = single && single->mesh->d_nodes4 && C.shadow_order && nL == 1 && n >= (size_t)C.shadow_order_min_rays && n > (size_t)C.small_rays &&
-                        C.long_steps > 0 && n >= (size_t)C.long_min_rays &&
-                        !((C.packet == 2 || (C.packet == 1 && single->mesh->packet_ok && n >= (size_t)C.packet_min_rays)) && single->coherent);
+                               C.long_steps > 0 && n >= (size_t)C.long_min_rays && !(walks_packets(C, single->mesh, n) && single->coherent);
   const size_t cls_stride = (n + 63) & ~(size_t)63;
-  // (every region has room for the whole list -- 8 x 64 bytes per ray: 0.5 GB at the benchmark's 1.04 M rays; beyond 8 GiB the list stays in arrival order)
-  // The ordering is an optimisation whose results do not depend on it: it must never make a frame fail that fits without it.  A device that cannot
-  // give the 8x list falls back to arrival order with the plain n-slot list, for this context from then on (no allocation attempt per frame).
-  bool by_class = by_class_wanted && !C.shadow_order_denied && cls_stride * SHADOW_CLASSES * 64 <= ((size_t)8 << 30);
-  size_t shadow_slots = by_class ? cls_stride * SHADOW_CLASSES : shadow_cap;
+  // (every region has room for the whole list; beyond 8 GiB the list stays in arrival order -- and after one refusal: chain_bufs)
+  const size_t ordered_slots = (by_class_wanted && !C.shadow_order_denied && cls_stride * SHADOW_CLASSES * 64 <= ((size_t)8 << 30)) ? cls_stride * SHADOW_CLASSES : 0;
+  const size_t shadow_slots = ordered_slots ? ordered_slots : n * (size_t)(nL > 0 ? nL : 1);
   if (shadow_slots >= 0xffffffffull) { set_error("round: %zu shadow slots exceed the 32-bit slot counters", shadow_slots); return GVT_HIP_ERR_INVALID; }
-  float4 *d_shadow = (float4 *)scratch_get(2, sizeof(float4) * 4 * shadow_slots);
-  unsigned char *d_steps = (by_class && d_shadow) ? (unsigned char *)scratch_get(19, n) : nullptr;
-  if (by_class && (!d_shadow || !d_steps)) {
-    (void)hipGetLastError(); // (the failed hipMalloc's sticky-less error)
-    C.shadow_order_denied = true;
-    by_class = false;
-    d_steps = nullptr;
-    shadow_slots = shadow_cap;
-    d_shadow = (float4 *)scratch_get(2, sizeof(float4) * 4 * shadow_slots);
-  }
-  unsigned *d_idx_a = (unsigned *)scratch_get(3, sizeof(unsigned) * n);
-  unsigned *d_idx_b = (unsigned *)scratch_get(4, sizeof(unsigned) * n);
-  gvt_hip_light *d_lights = (gvt_hip_light *)scratch_get(5, sizeof(gvt_hip_light) * (nL > 0 ? nL : 1));
-  int *d_shadow_inst = (int *)scratch_get(16, sizeof(int) * shadow_cap);
-  LongRec *d_long = (LongRec *)scratch_get(15, long_scratch_bytes(n));
-  if (!d_hits || !d_shadow || !d_idx_a || !d_idx_b || !d_lights || !d_shadow_inst || !d_long) return GVT_HIP_ERR_DEVICE;
-  {
-    std::vector<unsigned char> &cached = C.lights_cached;
-    const void *&cached_dst = C.lights_cached_dst;
-    const size_t bytes = sizeof(gvt_hip_light) * (size_t)nL;
-    if (nL && (cached_dst != d_lights || cached.size() != bytes || std::memcmp(cached.data(), lights_host, bytes) != 0)) {
-      cached.assign((const unsigned char *)lights_host, (const unsigned char *)lights_host + bytes);
-      cached_dst = d_lights;
-      HIPCHK(hipMemcpyAsync(d_lights, cached.data(), bytes, hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st)); // pageable source: finish the copy before `cached` can change (first frame only)
-    }
-  }
+  Chain K{ n, passes, P, lights_host, out, make_planes(out->d_planes, out->cap) };
+  int rc = chain_bufs(K.B, n, nL, lights_host, ordered_slots);
+  if (rc) return rc;
+  K.d_shadow_inst = (int *)scratch_get(SCR_SHADOW_INST, sizeof(int) * K.B.shadow_cap);
+  K.d_long = (LongRec *)scratch_get(SCR_LONG, long_scratch_bytes(n));
+  if (!K.d_shadow_inst || !K.d_long) return GVT_HIP_ERR_DEVICE;
   // hops (MultiSrc, trace_lane.inc): in a merged chain a ray that leaves its instance without a hit goes on into the next instance of this rank inside the launch;
   // d_hop[virtual index] = the instance it is in now (-1: its segment's), for the kernels behind (k_long_closest, k_shade, the next pass's refill)
   int *d_hop = nullptr;
   if (!single && P.hop && P.sink.fb) {
-    d_hop = (int *)scratch_get(23, sizeof(int) * n);
+    d_hop = (int *)scratch_get(SCR_HOP, sizeof(int) * n);
     if (!d_hop) return GVT_HIP_ERR_DEVICE;
     HIPCHK(hipMemsetAsync(d_hop, 0xff, sizeof(int) * n, st));
   }
-  unsigned long long *hop_tot = (unsigned long long *)(C.d_counters + 16); // (the chain's closest-hit total: k_wave_pass_begin)
-  RayPlanes shadow = make_planes(d_shadow, shadow_slots);
-  shadow.p4 = nullptr; shadow.p5 = nullptr;
-  RayPlanes outp = make_planes(out->d_planes, out->cap);
-  RayPlanes none{};
   unsigned *c = C.d_counters;
-  Trav T{};
-  Mat4 id{};
-  const bool use_long = C.long_steps > 0 && n >= (size_t)C.long_min_rays;
-  const bool small = n <= (size_t)C.small_rays; // a wave per ray (see k_long_seed)
-  const int small_grid = (int)std::min<size_t>((n + 3) / 4, (size_t)C.n_cu * 3);
+  K.use_long = C.long_steps > 0 && n >= (size_t)C.long_min_rays;
+  K.small = n <= (size_t)C.small_rays;
   // pass 0's ray count where only the device knows it (the chain straight behind the camera filter): the single queue's count word, or
   // the word the caller's segment kernel left the merged list's length in (n_total is then the bound the launches are sized by)
-  const unsigned *nd0 = single ? single->n_dev : n_dev0_multi;
+  K.nd0 = single ? single->n_dev : O.n_dev0_multi;
   for (int pass = 0; pass < passes; pass++) {
-    const unsigned *n_dev = pass ? c + ((pass & 1) ? 2 : 5) : nd0; // count written by the previous pass's k_shade
-    const unsigned *idx = pass ? ((pass & 1) ? d_idx_a : d_idx_b) : nullptr;    // its bounce list
-    unsigned *next = (pass & 1) ? d_idx_b : d_idx_a;
-    unsigned *c_next = c + ((pass & 1) ? 5 : 2);
+    unsigned *const lists[2] = { K.B.idx_a, K.B.idx_b };
+    // (the count written by the previous pass's k_shade and its bounce list)
+    const Pass p{ pass, pass ? c + cw_bounce(pass - 1) : K.nd0, pass ? lists[(pass - 1) & 1] : nullptr, lists[pass & 1], c + cw_bounce(pass) };
     if (!(pass == 0 && single && single->pass0_begun))
-      k_wave_pass_begin<<<1, 64, 0, st>>>(c, pass, (unsigned)n, out->d_count, nd0, (pass == 0 && n_dev0_multi && !single) ? const_cast<WaveSeg *>(W.segs) : nullptr, W.n_seg, d_count_ptr);
-    // ray sorting where it should pay (knob sort_rays, off by default: measured, profiles/r06_sort_cfg5.txt): a BOUNCE list -- secondary rays in their parents'
-    // order, i.e. neighbours in the list leave neighbouring surface points in unrelated directions -- is reordered by direction octant, then the Morton cell of the
-    // ray's origin (k_ray_keys) before the closest-hit launch; the pass's shadow rays inherit the order (k_shade allocates their slots in list order).  The list's
-    // length lives on the device: all n entries of the bound are sorted, the unused ones with the largest key
-    if (C.sort_rays && pass > 0 && single && n >= 8192 && single->mesh->d_nodes4) {
-      gvt_hip_mesh *Ms = single->mesh;
-      unsigned *k_in = (unsigned *)scratch_get(8, sizeof(unsigned) * n), *k_out = (unsigned *)scratch_get(9, sizeof(unsigned) * n);
-      unsigned *v_in = (unsigned *)scratch_get(10, sizeof(unsigned) * n), *v_out = (unsigned *)scratch_get(11, sizeof(unsigned) * n);
-      if (!k_in || !k_out || !v_in || !v_out) return GVT_HIP_ERR_DEVICE;
-      const float ex = Ms->hi[0] - Ms->lo[0], ey = Ms->hi[1] - Ms->lo[1], ez = Ms->hi[2] - Ms->lo[2];
-      const float3 blo = make_float3(Ms->lo[0], Ms->lo[1], Ms->lo[2]);
-      const float3 inv = make_float3(ex > 0 ? 1.f / ex : 0.f, ey > 0 ? 1.f / ey : 0.f, ez > 0 ? 1.f / ez : 0.f);
-      int rc_s;
-      {
-        ProfScope ps(KC_SORT);
-        k_ray_keys<<<blocks_for(n), 256, 0, st>>>(single->planes, idx, (unsigned)n, single->minv, blo, inv, k_in, v_in, C.sort_bits, n_dev);
-        if ((rc_s = sort_pairs_u32(k_in, k_out, v_in, v_out, n, C.sort_bits))) return rc_s;
-      }
-      HIPCHK(hipGetLastError());
-      idx = v_out;
-    }
-    if (single) {
-      // one segment (a single non-empty local queue, e.g. the one-domain benchmark): the single-mesh kernels -- no segment lookup and
-      // no per-ray table loads at a refill -- with the same device-side counts
-      gvt_hip_mesh *M = single->mesh;
-      const bool have4 = M->d_nodes4 != nullptr;
-      Trav TS{ M->d_nodes, M->d_tri, M->d_nodes4 };
-      LongQ LQ{};
-      if (use_long && have4) { LQ.recs = d_long; LQ.count = c + 3; long_limits(LQ, n); }
-      LQ.steps_out = by_class ? d_steps : nullptr;
-      const bool small1 = small && have4;
-      // a coherent list (camera rays in 8x8 tiles, straight from the filter) over a mesh the builder found packet-friendly (gvt_hip_mesh::packet_ok;
-      // knob packet: 0 never, 1 the mesh's own choice, 2 always): a wave walks the tree ONCE for 64 rays (k_packet) -- the reference chooses its packet
-      // width per build as well (EmbreeMeshAdapter.cpp:50-74)
-      const bool pkt = (C.packet == 2 || (C.packet == 1 && M->packet_ok && n >= (size_t)C.packet_min_rays)) && single->coherent && pass == 0 && have4 && !small1;
-      // ... the CLOSEST hit, that is.  Shadow rays as packets lost on both surfaces they were measured on (bun_zipper any hit 0.162 -> 0.189 ms, the hall
-      // 1.23 -> 1.33: an any-hit packet goes on until its LAST ray is occluded or through): under the per-mesh choice they stay a lane per ray; 2 forces both
-      const bool pkt_any = pkt && C.packet == 2;
-      if (pkt) {
-        ProfScope ps(KC_CLOSEST);
-        LongQ LP{ d_long, c + 3, nullptr, 0u, 0, 0 };
-        k_packet<false><<<blocks_for(n), 256, 0, st>>>(single->planes, (unsigned)n, n_dev, single->minv, TS, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
-                                                     TermSink{}, LP, nullptr, nullptr, nullptr, c + 9);
-        k_long_closest<true><<<C.n_cu * 3, 256, 0, st>>>(single->planes, d_long, c + 3, single->minv, TS, GVT_RAY_EPSILON, d_hits, c + 4); // packets that bailed out
-      } else
-      if (small1) {
-        ProfScope ps(KC_CLOSEST);
-        k_long_seed<<<blocks_for(n), 256, 0, st>>>(d_long, c + 3, idx, (unsigned)n, n_dev);
-        k_long_closest<true><<<small_grid, 256, 0, st>>>(single->planes, d_long, c + 3, single->minv, TS, GVT_RAY_EPSILON, d_hits, c + 4);
-      } else {
-        ProfScope ps(KC_CLOSEST);
-        launch_trace<false, true, 0>(trav_grid2(n, true), st, single->planes, idx, (unsigned)n, single->minv, TS, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
-                                     c + 0, C.d_spill, C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, TermSink{}, LQ);
-      }
-      if (LQ.steps && !small1 && !pkt) {
-        ProfScope ps(KC_LONG);
-        k_long_closest<true><<<C.n_cu * 3, 256, 0, st>>>(single->planes, d_long, c + 3, single->minv, TS, GVT_RAY_EPSILON, d_hits, c + 4, WaveSet{}, LQ.stk);
-      }
-      ShadeArgs A{};
-      A.in = single->planes; A.idx = idx; A.n = (unsigned)n; A.index_base = 0; A.hits = d_hits;
-      A.first_pass = (pass == 0); A.carried_rng = 1; A.out = outp; A.out_count = out->d_count; A.shadow = shadow; A.shadow_count = c + 1;
-      A.next_idx = next; A.next_count = c_next; A.lights = d_lights; A.normi = single->normi; A.normal_mode = P.normal_mode;
-      A.n_lights = nL; A.seed = P.seed; A.zero_word = c + 0;
-      A.sink = P.sink; A.sink.from = single->inst; A.update_in_place = 0;
-      A.n_dev = n_dev; A.W = WaveSet{}; A.out_from = nullptr; A.shadow_inst = nullptr; A.shadow_stride = 0;
-      if (pkt_any) { A.shadow_inst = d_shadow_inst; A.shadow_stride = (unsigned)n; } // shadow rays in the primaries' order: packets again
-      A.steps = d_steps; A.cls_cnt = by_class ? c + SHADOW_CLS_WORD : nullptr; A.cls_stride = (unsigned)cls_stride; A.cls_lo = C.shadow_cls_lo; A.cls_shift = C.shadow_cls_shift;
-      MeshView mv;
-      mv.slots = M->d_tri; mv.slot_of = M->d_slot_of; mv.verts = M->d_verts; mv.tris = M->d_tris; mv.normals = M->d_normals; mv.vcolors = M->d_vcolors;
-      mv.materials = M->d_materials; mv.n_mat = (unsigned)M->nMat; mv.face_mat = M->d_face_mat; mv.mat = M->mesh_mat;
-      // the simple frame (k_shade's LEAN instantiation): camera rays of the scene's only instance, depth 1, no area light, a LAMBERT mesh material
-      const bool lean_shade = single->coherent && pass == 0 && passes == 1 && P.sink.fb && P.sink.top.n_inst == 1 && nL >= 1 && !M->d_vcolors && !M->d_face_mat &&
-                              M->mesh_mat.type == 0 && !A.update_in_place && std::all_of(lights_host, lights_host + nL, [](const gvt_hip_light &l) { return l.type != GVT_HIP_LIGHT_AREA; });
-      {
-        ProfScope ps(KC_SHADE);
-        if (lean_shade) k_shade<false, true><<<blocks_for(n, SHADE_BLOCK), SHADE_BLOCK, 0, st>>>(A, mv);
-        else k_shade<false><<<blocks_for(n, SHADE_BLOCK), SHADE_BLOCK, 0, st>>>(A, mv);
-      }
-      if (nL) {
-        ProfScope ps(KC_ANY);
-        TermSink sk = P.sink;
-        sk.from = single->inst;
-        if (pkt_any) {
-          unsigned *d_retry = (unsigned *)scratch_get(18, sizeof(unsigned) * shadow_cap);
-          if (!d_retry) return GVT_HIP_ERR_DEVICE;
-          k_packet<true><<<blocks_for(shadow_cap), 256, 0, st>>>(shadow, (unsigned)shadow_cap, nullptr, single->minv, TS, GVT_RAY_EPSILON, nullptr, d_shadow_inst, outp, out->d_count,
-                                                               sk, LongQ{}, d_retry, c + 6, (unsigned long long *)(c + 18), c + 9);
-          // rays of packets that bailed out: one lane per ray (an empty list costs a few microseconds)
-          launch_trace<true, true, 1>(trav_grid2(4096), st, shadow, d_retry, 0u, single->minv, TS, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                      c + 0, C.d_spill, C.refill_min, C.inner_min, c + 6, C.share, (unsigned)C.share_min_rays, sk, LongQ{});
-        } else if (small1) k_wave_any<false><<<(int)std::min<size_t>((shadow_cap + 3) / 4, (size_t)C.n_cu * 3), 256, 0, st>>>(shadow, c + 1, single->minv, TS, GVT_RAY_EPSILON, outp, out->d_count, c + 0, sk, MultiSrc{});
-        else {
-          MultiSrc by{};
-          if (by_class) { by.cls_cnt = c + SHADOW_CLS_WORD; by.cls_stride = (unsigned)cls_stride; by.cls_total = c + 1; }
-          launch_trace<true, true, 1>(trav_grid2(shadow_cap), st, shadow, nullptr, 0u, single->minv, TS, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                      c + 0, C.d_spill, C.refill_min, C.inner_min, by_class ? nullptr : c + 1, C.share, (unsigned)C.share_min_rays, sk, LongQ{}, by);
-        }
-      }
-      HIPCHK(hipGetLastError());
-      C.stats.launches_closest++;
-      C.stats.launches_any++;
-      continue;
-    }
-    LongQ LQ{};
-    if (use_long) { LQ.recs = d_long; LQ.count = c + 3; long_limits(LQ, n); }
-    MultiSrc MS{ W, nullptr, nullptr, nullptr };
-    if (d_hop) { MS.hop_inst = d_hop; MS.hop_read = pass > 0; MS.hop_owner = P.hop_owner; MS.hop_rank = P.hop_rank; MS.hop_tot = hop_tot; MS.hop_early = P.hop == 1 ? 1 : 0; }
-    // the round's queues hold camera rays in tile order, over packet-friendly meshes only: the closest hits a packet of 64 rays per wave
-    const bool pktm = multi_packets && pass == 0 && !small && idx == nullptr;
-    if (pktm) {
-      ProfScope ps(KC_CLOSEST);
-      LongQ LP{ d_long, c + 3, nullptr, 0u, 0, 0 };
-      k_packet_multi<<<blocks_for(n), 256, 0, st>>>(W, (unsigned)n, n_dev, GVT_RAY_EPSILON, d_hits, LP, c + 9);
-      k_long_closest<true, true><<<C.n_cu * 3, 256, 0, st>>>(none, d_long, c + 3, id, T, GVT_RAY_EPSILON, d_hits, c + 4, W); // packets that bailed out
-    } else
-    if (small) {
-      ProfScope ps(KC_CLOSEST);
-      k_long_seed<<<blocks_for(n), 256, 0, st>>>(d_long, c + 3, idx, (unsigned)n, n_dev);
-      k_long_closest<true, true><<<small_grid, 256, 0, st>>>(none, d_long, c + 3, id, T, GVT_RAY_EPSILON, d_hits, c + 4, W, nullptr, pass > 0 ? d_hop : nullptr);
-    } else {
-      ProfScope ps(KC_CLOSEST);
-      k_trace<false, true, 0, true><<<trav_grid2(n, true), TRAV_BLOCK, 0, st>>>(none, idx, (unsigned)n, id, T, GVT_RAY_EPSILON, d_hits, nullptr, none, nullptr,
-                                                                          c + 0, C.d_spill, C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays,
-                                                                          d_hop ? P.sink : TermSink{}, LQ, MS);
-    }
-    if (use_long && !small && !pktm) {
-      ProfScope ps(KC_LONG);
-      k_long_closest<true, true><<<C.n_cu * 3, 256, 0, st>>>(none, d_long, c + 3, id, T, GVT_RAY_EPSILON, d_hits, c + 4, W, LQ.stk, d_hop);
-    }
-    ShadeArgs A{};
-    A.in = none; A.idx = idx; A.n = (unsigned)n; A.index_base = 0; A.hits = d_hits;
-    A.first_pass = (pass == 0); A.carried_rng = 1; A.out = outp; A.out_count = out->d_count; A.shadow = shadow; A.shadow_count = c + 1;
-    A.next_idx = next; A.next_count = c_next; A.lights = d_lights; A.normi = P.normi; A.normal_mode = P.normal_mode;
-    A.n_lights = nL; A.seed = P.seed; A.zero_word = c + 0;
-    A.sink = P.sink; A.update_in_place = 0;
-    A.n_dev = n_dev; A.W = W; A.out_from = d_out_from; A.shadow_inst = d_shadow_inst; A.hop_inst = d_hop;
-    const bool direct = C.shadow_direct && pass == 0 && !small; // later passes and small rounds hold few rays: compacted slots
-    // (k_shade marks every slot below the stride -- the bound -- empty or taken; with one light the list is as long as the traced one,
-    // and where only the device knows that length the any-hit launch stops there instead of skipping empty slots up to the bound)
-    const bool direct_dev = direct && nd0 != nullptr && nL == 1;
-    A.shadow_stride = direct ? (unsigned)n : 0u;
-    // (k_shade's LEAN instantiation for the merged chain: depth 1, no area light, plain LAMBERT meshes; a missing ray still walks the instances ahead of it)
-    const bool lean_multi = simple_meshes && pass == 0 && passes == 1 && nL >= 1 && std::all_of(lights_host, lights_host + nL, [](const gvt_hip_light &l) { return l.type != GVT_HIP_LIGHT_AREA; });
-    {
-      ProfScope ps(KC_SHADE);
-      if (lean_multi) k_shade<true, true><<<blocks_for(n, SHADE_BLOCK), SHADE_BLOCK, 0, st>>>(A, MeshView{});
-      else k_shade<true><<<blocks_for(n, SHADE_BLOCK), SHADE_BLOCK, 0, st>>>(A, MeshView{});
-    }
-    if (nL) {
-      ProfScope ps(KC_ANY);
-      MultiSrc MA{ W, d_shadow_inst, d_out_from, direct ? (unsigned long long *)(c + 18) : nullptr };
-      if (d_hop && P.sink.fb && P.hop == 2) { MA.hop_owner = P.hop_owner; MA.hop_rank = P.hop_rank; MA.hop_tot = hop_tot; } // (an un-occluded shadow ray goes on the same way -- not in the early mode: 1.372 -> 1.340 ms on the soup tiles without)
-      if (small) k_wave_any<true><<<(int)std::min<size_t>((shadow_cap + 3) / 4, (size_t)C.n_cu * 3), 256, 0, st>>>(shadow, c + 1, id, T, GVT_RAY_EPSILON, outp, out->d_count, c + 0, P.sink, MA);
-      else k_trace<true, true, 1, true><<<trav_grid2(shadow_cap), TRAV_BLOCK, 0, st>>>(shadow, nullptr, direct ? (unsigned)shadow_cap : 0u, id, T, GVT_RAY_EPSILON, nullptr, nullptr, outp, out->d_count,
-                                                                                 c + 0, C.d_spill, C.refill_min, C.inner_min, direct ? (direct_dev ? nd0 : nullptr) : c + 1, C.share,
-                                                                                 (unsigned)C.share_min_rays, P.sink, LongQ{}, MA);
-    }
+      k_wave_pass_begin<<<1, 64, 0, st>>>(c, pass, (unsigned)n, out->d_count, K.nd0, (pass == 0 && O.n_dev0_multi && !single) ? const_cast<WaveSeg *>(W.segs) : nullptr, W.n_seg, O.d_count_ptr);
+    if (!single) merged_pass(K, p, W, O, d_hop, d_out_from);
+    else if ((rc = single_pass(K, p, *single, cls_stride))) return rc;
     HIPCHK(hipGetLastError());
     C.stats.launches_closest++;
     C.stats.launches_any++;
   }
-  if (!defer_end) k_wave_end<<<(unsigned)((std::max(n_inst, 1) + 255) / 256), 256, 0, st>>>(c, d_count_ptr, d_mask, n_inst); // + queue[instTarget].clear()
+  if (!O.defer_end) k_wave_end<<<(unsigned)((std::max(O.n_inst, 1) + 255) / 256), 256, 0, st>>>(c, O.d_count_ptr, O.d_mask, O.n_inst); // + queue[instTarget].clear()
   HIPCHK(hipGetLastError());
   C.stats.trace_calls++;
   return 0;
@@ -652,47 +667,28 @@ int wave_trace_chain(const WaveSet &W, size_t n_total, int passes, gvt_hip_queue
 // A small round in ONE launch (finish_kernel.inc): the rays of the segments in W are traced, shaded, their shadow rays traced and
 // everything that moves on is followed through this rank's instances; rays for other ranks' instances are appended to their queues
 // (which must have room: n_total * (1 + n_lights * depth) each), everything else ends in the framebuffer.  No shuffle follows.
-// the context's device copy of the light list is this list (finish_round / wave_trace_chain upload it when it changes): a launch may use it without a copy
-bool finish_lights_resident(const gvt_hip_light *lights_host, int nL) {
-  Ctx &C = gctx();
-  const size_t bytes = sizeof(gvt_hip_light) * (size_t)nL;
-  return !nL || (C.lights_cached_dst && C.lights_cached_dst == C.scratch[5] && C.lights_cached.size() == bytes && std::memcmp(C.lights_cached.data(), lights_host, bytes) == 0);
-}
 // spec_words != nullptr: the launch is enqueued ahead of the host's knowledge (domain.hip): n_total is only the bound its grid is sized by, the count is
 // spec_words[2], the launch is void unless spec_words[1]; the light list must be resident already (no upload, no synchronisation in here)
 int finish_round(const WaveSet &W, size_t n_total, const TraceParams &P, const gvt_hip_light *lights_host, const void *d_qdesc, const int *d_owner, int rank,
                  unsigned *d_queue_overflow, unsigned *const *d_count_ptr, const unsigned char *d_mask, const unsigned *spec_words) {
   Ctx &C = gctx();
   if (!n_total) return 0;
-  hipStream_t st = C.stream;
   const int nL = P.n_lights;
-  gvt_hip_light *d_lights = (gvt_hip_light *)scratch_get(5, sizeof(gvt_hip_light) * (nL > 0 ? nL : 1));
-  if (!d_lights) return GVT_HIP_ERR_DEVICE;
-  {
-    std::vector<unsigned char> &cached = C.lights_cached;
-    const void *&cached_dst = C.lights_cached_dst;
-    const size_t bytes = sizeof(gvt_hip_light) * (size_t)nL;
-    if (nL && (cached_dst != d_lights || cached.size() != bytes || std::memcmp(cached.data(), lights_host, bytes) != 0)) {
-      if (spec_words) { set_error("finish_round: a speculative launch needs the light list resident"); return GVT_HIP_ERR_INVALID; }
-      cached.assign((const unsigned char *)lights_host, (const unsigned char *)lights_host + bytes);
-      cached_dst = d_lights;
-      HIPCHK(hipMemcpyAsync(d_lights, cached.data(), bytes, hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-    }
-  }
+  gvt_hip_light *d_lights;
+  if (int rc = lights_on_device(lights_host, nL, &d_lights, spec_words == nullptr)) return rc;
   FinishArgs A;
   A.n_dev = spec_words ? spec_words + 2 : nullptr; A.valid = spec_words ? spec_words + 1 : nullptr;
   A.W = W; A.n = (unsigned)n_total; A.lights = d_lights; A.n_lights = nL; A.normal_mode = P.normal_mode;
   A.top = P.sink.top; A.fb = P.sink.fb; A.n_pix = P.sink.n_pix;
   A.queues = (const QueueDesc *)d_qdesc; A.owner = d_owner; A.rank = rank;
-  A.counter = C.d_counters + 0; A.tot = (unsigned long long *)(C.d_counters + 16);
-  A.queue_overflow = d_queue_overflow; A.trav_overflow = C.d_counters + TRAV_OVF_WORD;
+  A.counter = C.d_counters + CW_WORK; A.tot = cw_totals(C.d_counters); // (FinishArgs::tot: [TOT_CLOSEST], [TOT_ANY])
+  A.queue_overflow = d_queue_overflow; A.trav_overflow = C.d_counters + CW_TRAV_OVF;
   A.seed = P.seed; A.index_base = 0ull; A.skip_known = C.skip_known;
   A.count_ptr = d_count_ptr; A.clear_mask = d_mask; A.n_inst = W.n_inst;
   // (the work counter is 0: the frame's start and every round's report leave it so -- k_zero_totals, k_round_report)
   {
     ProfScope ps(KC_CLOSEST);
-    k_finish<<<(int)std::min<size_t>((n_total + 3) / 4, (size_t)C.n_cu * 4), 256, 0, st>>>(A); // 40 KiB of LDS per block: four blocks per CU
+    k_finish<<<(int)std::min<size_t>((n_total + 3) / 4, (size_t)C.n_cu * 4), 256, 0, C.stream>>>(A); // 40 KiB of LDS per block: four blocks per CU
   }
   HIPCHK(hipGetLastError());
   C.stats.launches_closest++;

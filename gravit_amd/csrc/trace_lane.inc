@@ -19,8 +19,8 @@
 #if GVT_STAMP
 __device__ unsigned long long g_stamp[24];
 #endif
-#define TRAV_OVF_WORD 8 // d_counters[8] of the launching context: set by k_trace / k_long_closest when a traversal stack would have exceeded
-                        // LDS levels + spill entries (k_trace's `counter` is d_counters + 0, k_long_closest's d_counters + 4)
+// CW_TRAV_OVF of the launching context is set by k_trace / k_long_closest when a traversal stack would have exceeded LDS levels + spill entries
+// (k_trace's `counter` is d_counters + CW_WORK, k_long_closest's d_counters + CW_LONG_WORK)
 #ifndef TRAV_CHUNK
 #define TRAV_CHUNK 256
 #endif
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
   {                                                                                   \
     if (sp < TRAV_STACK) { lds[sp * TRAV_BLOCK] = (REF); sp++; }                      \
     else if (sp - TRAV_STACK < TRAV_SPILL) { KT_SPILL(sp - TRAV_STACK) = (REF); sp++; }  \
-    else atomicOr(counter + TRAV_OVF_WORD, 1u); /* reported, never silent */          \
+    else atomicOr(counter + (CW_TRAV_OVF - CW_WORK), 1u); /* reported, never silent */          \
   }
 #define KT_POP()                                                                      \
   {                                                                                   \

@@ -226,7 +226,7 @@ __global__ __launch_bounds__(256) void k_long_closest(RayPlanes q, const LongRec
       ns = __popcll(mi); nl = __popcll(ml);
     } else if (lane == 0) { s_ref[0] = 0; s_tn[0] = 0.f; }
     __builtin_amdgcn_wave_barrier();
-    wave_run<false, false, LONG_CAP, LONG_PHYS>(T.nodes4, T.tris, O, D, S, tnear, WaveLists{ s_ref, s_tn, l_ref, l_tn }, ns, nl, bt, bp, bu, bv, bden, counter + (TRAV_OVF_WORD - 4));
+    wave_run<false, false, LONG_CAP, LONG_PHYS>(T.nodes4, T.tris, O, D, S, tnear, WaveLists{ s_ref, s_tn, l_ref, l_tn }, ns, nl, bt, bp, bu, bv, bden, counter + (CW_TRAV_OVF - CW_LONG_WORK));
     // every lane stores the (same) result: no lane-0-only block at the end of this loop (wave_ticket)
     { gvt_hip_hit h; h.t = bt; h.prim = bp; h.u = (bp >= 0) ? bu / bden : 0.f; h.v = (bp >= 0) ? bv / bden : 0.f; hits[R.j] = h; }
   }
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void k_wave_any(RayPlanes q, const unsigned *_
     } else {
       O = xfm_point(minv, mk3(a.x, a.y, a.z)); D = xfm_vector(minv, mk3(b.x, b.y, b.z));
     }
-    const bool occluded = wave_any_run<false, LONG_CAP, LONG_PHYS>(T.nodes4, 0, T.tris, O, D, slab_of(O, D), tnear, s_ref, l_ref, counter + TRAV_OVF_WORD);
+    const bool occluded = wave_any_run<false, LONG_CAP, LONG_PHYS>(T.nodes4, 0, T.tris, O, D, slab_of(O, D), tnear, s_ref, l_ref, counter + (CW_TRAV_OVF - CW_WORK));
     if (!occluded && lane == 0) { // un-occluded: moved on, or ended here by shuffleRays' terminal rule (TracerBase.h:396-400)
       const float4 c = q.p2[r], d = q.p3[r];
       bool go_on = true;

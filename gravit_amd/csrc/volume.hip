@@ -556,7 +556,7 @@ int upload_cells(gvt_hip_volume *V) {
 int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
   if (!q->size) return 0;
   Ctx &C = gctx();
-  unsigned *work = (unsigned *)scratch_get(20, sizeof(unsigned));
+  unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!work) return GVT_HIP_ERR_DEVICE;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
   Mat4 M;
@@ -577,9 +577,9 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
   const size_t n = q_in->size, nI = T->n;
   if (!n) return 0;
   const unsigned n_blk = blocks_of(n);
-  int *d_next = (int *)scratch_get(6, sizeof(int) * n);
-  unsigned *d_blk = (unsigned *)scratch_get(14, sizeof(unsigned) * (nI ? nI : 1) * n_blk);
-  unsigned *d_ovf = (unsigned *)scratch_get(22, sizeof(unsigned));
+  int *d_next = (int *)scratch_get(SCR_NEXT_INST, sizeof(int) * n);
+  unsigned *d_blk = (unsigned *)scratch_get(SCR_BLOCK_COUNTS, sizeof(unsigned) * (nI ? nI : 1) * n_blk);
+  unsigned *d_ovf = (unsigned *)scratch_get(SCR_VOL_OVF, sizeof(unsigned));
   if (!d_next || !d_blk || !d_ovf) return GVT_HIP_ERR_DEVICE;
   bool roomy = true;
   for (size_t i = 0; i < nI; i++) {
