@@ -22,7 +22,7 @@ struct gvt_hip_volume {
   float vmin = 0.f, vmax = 0.f;
   int nb[3] = { 0, 0, 0 };
   std::vector<float> bmin, bmax; // per macro cell: value range of its vertices
-  std::vector<uint8_t> bnan;     // ... and whether one of them is NaN
+  std::vector<uint8_t> bnan;     // ... and whether one of them is NaN or +-Inf: its samples can evaluate to NaN (Inf - Inf, 0 * Inf)
   uint64_t n_empty = 0;
   bool has_tf = false;
   float tf_lo = 0.f, tf_hi = 1.f;
@@ -332,6 +332,7 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
           skip = V.skip && !V.mc[bi];
         }
         if (skip) {
+          if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the ray arrived opaque: this sample adds +0 and ends it, as any sample does
           const int kj = vol_jump_target(V, o, d, k, k_hi, c);
           bool jump = kj > k;
           if constexpr (SURF) jump = jump && surf_planes_clear(V, S, o, d, k, kj);
@@ -529,6 +530,14 @@ SurfDev surf_dev(const gvt_hip_volume *Vh, const Mat4 &minv) {
   return S;
 }
 
+// Can a sample of macro cell b evaluate to NaN or to +-Inf?  With a vertex that is not finite, or with finite vertices so far apart that
+// b - a overflows inside a lerp (then a + f * Inf is +-Inf, or NaN at f == 0).  Such a sample looks up entry 0 (NaN: fmaxf(NaN, 0) = 0) or
+// entry 255, whatever the range of the block's vertices says
+bool block_is_ranged(const gvt_hip_volume *V, size_t b) { // its samples stay within [bmin, bmax] (but for NaN ones, where bnan is set)
+  return V->bmin[b] <= V->bmax[b] && (double)V->bmax[b] - (double)V->bmin[b] < 3.4e38;
+}
+bool block_is_wild(const gvt_hip_volume *V, size_t b) { return V->bnan[b] || !block_is_ranged(V, b); }
+
 // the surface march's per-cell words: a macro cell's samples may go uninterpolated when the transfer function leaves it empty (h_mc) and
 // no isovalue lies within its value range widened by 2^-18 of its magnitude (the trilinear interpolant's rounding stays far inside: three
 // nested lerps are off by a few 2^-24 of the largest vertex); the word then carries the isovalue sides all its samples have
@@ -537,7 +546,7 @@ int upload_cells(gvt_hip_volume *V) {
   std::vector<uint32_t> cells(nbk, 0u);
   if (V->has_tf)
     for (size_t b = 0; b < nbk; b++) {
-      if (V->h_mc[b] || (V->n_iso && (V->bnan[b] || !(V->bmin[b] <= V->bmax[b])))) continue;
+      if (V->h_mc[b] || (V->n_iso && block_is_wild(V, b))) continue; // (a NaN sample is on the false side of every isovalue)
       const double lo = V->bmin[b], hi = V->bmax[b], mg = std::max(std::fabs(lo), std::fabs(hi)) / 262144.0 + 1e-37;
       uint32_t w = VOL_CELL_SKIP;
       for (int i = 0; i < V->n_iso; i++) {
@@ -715,13 +724,14 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int
         const size_t bx0 = x ? (x - 1) / 8 : 0, bx1 = std::min(x / 8, (size_t)V->nb[0] - 1);
         const float v = h[(z * ny + y) * nx + x];
         const bool nan = v != v;
+        const bool wild = !std::isfinite(v);
         if (!nan) { V->vmin = std::min(V->vmin, v); V->vmax = std::max(V->vmax, v); }
         for (size_t bz = bz0; bz <= bz1; bz++)
           for (size_t by = by0; by <= by1; by++)
             for (size_t bx = bx0; bx <= bx1; bx++) {
               const size_t b = (bz * V->nb[1] + by) * V->nb[0] + bx;
-              if (nan) V->bnan[b] = 1;
-              else { V->bmin[b] = std::min(V->bmin[b], v); V->bmax[b] = std::max(V->bmax[b], v); }
+              if (wild) V->bnan[b] = 1;
+              if (!nan) { V->bmin[b] = std::min(V->bmin[b], v); V->bmax[b] = std::max(V->bmax[b], v); }
             }
       }
     }
@@ -772,7 +782,7 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   uint64_t empty = 0;
   for (size_t b = 0; b < nbk; b++) {
     int e0 = 0, e1 = 255;
-    if (V->bmin[b] <= V->bmax[b]) { e0 = V->bnan[b] ? 0 : std::max(0, entry(V->bmin[b]) - 1); e1 = std::min(255, entry(V->bmax[b]) + 2); }
+    if (block_is_ranged(V, b)) { e0 = V->bnan[b] ? 0 : std::max(0, entry(V->bmin[b]) - 1); e1 = std::min(255, entry(V->bmax[b]) + 2); } // (else: the whole table)
     float amax = 0.f;
     for (int e = e0; e <= e1; e++) amax = std::max(amax, tf[e].w);
     mc[b] = amax > 0.f ? 1 : 0;

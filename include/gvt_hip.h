@@ -337,7 +337,10 @@ int gvt_hip_tracer_frame(gvt_hip_tracer *, int flags, gvt_hip_frame_stats *stats
  * cell's 8 vertices; the 256-entry table at clamp((v - lo) / (hi - lo), 0, 1) * 255, linear between two entries; front-to-back compositing
  * f = (1 - A) * a, C += f * c, A += f.  The ray carries its state: color = the premultiplied C, w = A, t_min = t of the last lattice sample
  * marched (the next brick goes on after it), depth = the flags.  A ray stops with GVT_HIP_RAY_OPAQUE once A >= GVT_HIP_VOLUME_OPAQUE_A, else
- * it leaves the brick with GVT_HIP_RAY_BOUNDARY.  A visit of one brick walks at most 2^22 lattice positions. */
+ * it leaves the brick with GVT_HIP_RAY_BOUNDARY.  A visit of one brick walks at most 2^22 lattice positions.
+ * Samples need not be finite.  lerp(a, b, f) = a + f * (b - a) in float32, so a cell with an Inf vertex (or with finite vertices whose difference
+ * overflows) gives NaN (Inf - Inf, 0 * Inf) or +-Inf samples: NaN looks up entry 0 (clamp is fminf(fmaxf(x, 0), 1)), +Inf entry 255, -Inf entry 0;
+ * macro-cell skipping accounts for them.  A ray that arrives with w >= GVT_HIP_VOLUME_OPAQUE_A marches one owned sample and stops there. */
 #define GVT_HIP_RAY_OPAQUE 0x2            /* actor/ORays.h */
 #define GVT_HIP_RAY_BOUNDARY 0x4
 #define GVT_HIP_RAY_EXTERNAL_BOUNDARY 0x10
