@@ -401,6 +401,33 @@ class HipVolumeAdapter:
         capi.check(self.lib.gvt_hip_volume_set_transfer(self.h, capi.ptr(tf.cmap), len(tf.cmap), capi.ptr(tf.omap), len(tf.omap),
                                                          tf.value_range[0], tf.value_range[1]), "gvt_hip_volume_set_transfer")
 
+    def update_samples(self, data):
+        """gvt_hip_volume_update_samples: the next time step's samples for the same brick, in place (every pointer a tracer borrowed stays
+        valid; transfer function, surfaces and lights are kept).  data: a float32 numpy array of the brick's shape (nz, ny, nx), or a
+        contiguous float32 torch tensor of that shape on the GPU (no host round trip).  Returns the device time of the update in ms."""
+        shape = tuple(int(c) for c in self.counts[::-1])
+        if tuple(data.shape) != shape:
+            raise ValueError("update_samples: data of shape %s, the brick has %s" % (tuple(data.shape), shape))
+        ms = C.c_float(0.0)
+        if hasattr(data, "data_ptr"):  # a torch tensor: the device path
+            import torch
+
+            if not data.is_cuda:
+                raise ValueError("update_samples: torch tensors must be on the GPU (pass numpy arrays for host data)")
+            if not data.is_contiguous() or data.dtype != torch.float32:
+                raise ValueError("update_samples: a device tensor must be contiguous float32")
+            torch.cuda.current_stream(data.device).synchronize()  # (the tensor is written on torch's stream, the update runs on the library's)
+            src, flags = C.c_void_p(data.data_ptr()), 1
+        else:
+            if np.asarray(data).dtype != np.float32:
+                raise ValueError("update_samples: data of dtype %s, the brick holds float32" % np.asarray(data).dtype)
+            data = np.ascontiguousarray(data)
+            src, flags = capi.ptr(data), 0
+        capi.check(self.lib.gvt_hip_volume_update_samples(self.h, src, C.c_size_t(int(np.prod(shape))), C.c_uint32(flags), C.byref(ms)),
+                   "gvt_hip_volume_update_samples")
+        self._data = data
+        return float(ms.value)
+
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
         """Volume::SetIsovalues / SetSlices: isovalues, then planes (nx, ny, nz, d) in the volume's own space, rendered shaded inside the
         march with one opacity.  Nothing given: the surfaces are cleared."""

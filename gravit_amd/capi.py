@@ -34,6 +34,7 @@ SYMBOLS = [
     "gvt_hip_volume_create", "gvt_hip_volume_destroy", "gvt_hip_volume_get_info", "gvt_hip_volume_set_transfer", "gvt_hip_volume_trace",
     "gvt_hip_shuffle_volume", "gvt_hip_volume_frame",
     "gvt_hip_volume_set_surfaces", "gvt_hip_volume_set_lights", "gvt_hip_volume_get_crossings",
+    "gvt_hip_volume_update_samples",
 ]
 
 
@@ -110,6 +111,7 @@ def load():
         lib.gvt_hip_volume_set_transfer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float]
         lib.gvt_hip_volume_set_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]
         lib.gvt_hip_volume_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float]
+        lib.gvt_hip_volume_update_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
         for f in ("gvt_hip_mesh_create", "gvt_hip_queue_create", "gvt_hip_top_create", "gvt_hip_fb_create", "gvt_hip_fb_device_ptr", "gvt_hip_ctx_create",

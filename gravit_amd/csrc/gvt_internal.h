@@ -43,6 +43,7 @@ enum ScratchSlot {
   SCR_PKT_RETRY,   // shadow rays of any-hit packets that bailed out
   SCR_STEPS,       // node steps per primary, for the class-ordered shadow list (knob shadow_order)
   SCR_VOL_WORK, SCR_VOL_OVF, // the volume march's work counter and overflow flag (volume.hip)
+  SCR_VOL_RANGES,  // the macro cells' value ranges of the brick being created or updated, on their way to the host (volume.hip volume_ranges)
   SCR_BUILD,       // the builder's and the refit's temporaries (lbvh.hip); released again beyond 1 GiB
   SCR_HOP,         // merged chains with hops: the instance every ray is in now
   SCRATCH_COUNT

@@ -1,5 +1,6 @@
 // volume.hip -- volume domains: scalar bricks rendered with a transfer function.
 //   gvt_hip_volume_create / _set_transfer   Volume + TransferFunction (render/data/primitives/Volume.h, TransferFunction.cpp:40-72)
+//   k_vol_ranges / k_vol_range_total        the macro cells' value ranges and the brick's, on the device (create and gvt_hip_volume_update_samples)
 //   k_volume_march / k_volume_march_surf    the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp): two
 //                                           entry points of one body, volume_march_body<SURF> (SURF: isovalues and slice planes)
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
@@ -26,6 +27,7 @@ struct gvt_hip_volume {
   uint64_t n_empty = 0;
   bool has_tf = false;
   float tf_lo = 0.f, tf_hi = 1.f;
+  float tf_a[256] = {};          // the table's corrected opacities (d_tf[i].w): what rebuild_tables reads after an update of the samples
   float *d_vox = nullptr;
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
   uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
@@ -497,6 +499,113 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_scatter(RayPlanes q, unsigned
   else atomicOr(overflow, 1u);
 }
 
+
+// ---- macro-cell value ranges.  A macro cell is 8^3 cells = up to 9^3 vertices, clipped at the brick's last vertex; a vertex on a block
+// boundary is a corner of cells on both sides and counts for both blocks.  Per macro cell: the minimum and the maximum of its vertices that
+// are not NaN (none: +Inf and -Inf stay) and whether a vertex is NaN or +-Inf.
+// One block per run of VR_CELLS macro cells along x, for one (by, bz): a wave reads whole rows of the grid, a lane 4 consecutive vertices
+// (one 16-byte load where every row starts 16-byte aligned: nx % 4 == 0, VEC), the block's waves take the run's (up to) 81 rows in turn.
+// Macro cell c of the run is lanes 2c and 2c + 1 and the first vertex of lane 2c + 2 (shuffles), then the waves (LDS); the run's last
+// boundary vertex, x0 + 8 * VR_CELLS, belongs to the next run's lane 0 and is read here one scalar per row.  The alternative, a block
+// per macro cell, reads 9-float row fragments (36 of every 64-byte sector pair); this reads every row of a run once in full and the
+// boundary rows (y or z a multiple of 8) by two blocks: 81 / 64 = 1.27 of the grid's bytes, the second reading mostly from L2.
+// Every output has ONE writer and no atomics.  min and max are exact, so the order of the reduction cannot change a value; ranges are
+// compared as values, so between -0 and +0 either may come out: block_is_ranged, rebuild_tables' entry() and upload_cells use them
+// numerically only.
+#define VR_CELLS 32
+static_assert(8 * VR_CELLS == 4 * 64, "a wave's 64 lanes of 4 vertices cover the run's cells");
+
+struct VRange { float mn, mx; unsigned wild; };
+__device__ inline VRange vr_none() { return VRange{ INFINITY, -INFINITY, 0u }; }
+// NaN is tested for, not left to fminf / fmaxf: it sets the flag and enters neither bound; +-Inf sets the flag and enters
+__device__ inline void vr_add(VRange &r, float v) {
+  const bool nan = v != v;
+  if (!nan) { if (v < r.mn) r.mn = v; if (v > r.mx) r.mx = v; }
+  if (nan || v == INFINITY || v == -INFINITY) r.wild = 1u;
+}
+__device__ inline void vr_merge(VRange &r, const VRange &o) { // (bounds are never NaN)
+  if (o.mn < r.mn) r.mn = o.mn;
+  if (o.mx > r.mx) r.mx = o.mx;
+  r.wild |= o.wild;
+}
+__device__ inline VRange vr_shfl_down(const VRange &r, int d) { return VRange{ __shfl_down(r.mn, d), __shfl_down(r.mx, d), __shfl_down(r.wild, d) }; }
+__device__ inline VRange vr_wave_all(VRange r) { // every lane: the wave's range
+  for (int d = 32; d; d >>= 1) vr_merge(r, VRange{ __shfl_xor(r.mn, d), __shfl_xor(r.mx, d), __shfl_xor(r.wild, d) });
+  return r;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(VOL_BLOCK) void k_vol_ranges(const float *__restrict__ vox, unsigned nx, unsigned ny, unsigned nz, unsigned nbx, unsigned nby,
+                                                          unsigned runs, size_t n_work, float *__restrict__ bmin, float *__restrict__ bmax,
+                                                          uint8_t *__restrict__ bnan) {
+  constexpr int WAVES = VOL_BLOCK / 64;
+  __shared__ float s_mn[WAVES][VR_CELLS], s_mx[WAVES][VR_CELLS], s_emn[WAVES], s_emx[WAVES];
+  __shared__ unsigned s_w[WAVES][VR_CELLS], s_ew[WAVES];
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (size_t id = blockIdx.x; id < n_work; id += gridDim.x) { // (block-uniform)
+    const unsigned run = (unsigned)(id % runs), by = (unsigned)((id / runs) % nby), bz = (unsigned)(id / ((size_t)runs * nby));
+    const unsigned x0 = run * (8u * VR_CELLS), y0 = 8u * by, z0 = 8u * bz;
+    const unsigned ry = min(9u, ny - y0), rz = min(9u, nz - z0), rows = ry * rz;
+    const unsigned x = x0 + 4u * lane;
+    VRange first = vr_none(), all = vr_none(); // the lane's first vertex | all four
+    if (x < nx)
+      for (unsigned r = wave; r < rows; r += WAVES) {
+        const float *row = vox + ((size_t)(z0 + r / ry) * ny + (y0 + r % ry)) * nx;
+        if (VEC) { // nx % 4 == 0 and x % 4 == 0: x + 3 < nx
+          const float4 v = *reinterpret_cast<const float4 *>(row + x);
+          vr_add(first, v.x); vr_add(all, v.y); vr_add(all, v.z); vr_add(all, v.w);
+        } else {
+          vr_add(first, row[x]);
+          for (unsigned i = 1; i < 4u && x + i < nx; i++) vr_add(all, row[x + i]);
+        }
+      }
+    vr_merge(all, first);
+    VRange edge = vr_none(); // the boundary vertex behind the run's last cell: one row per thread (rows <= 81)
+    const unsigned xe = x0 + 8u * VR_CELLS;
+    if (threadIdx.x < rows && xe < nx) vr_add(edge, vox[((size_t)(z0 + threadIdx.x / ry) * ny + (y0 + threadIdx.x % ry)) * nx + xe]);
+    edge = vr_wave_all(edge);
+    VRange cell = all; // even lanes: macro cell lane / 2 of the run, this wave's rows
+    const VRange right = vr_shfl_down(all, 1), corner = vr_shfl_down(first, 2);
+    vr_merge(cell, right);
+    if (lane + 2u < 64u) vr_merge(cell, corner);
+    if (!(lane & 1u)) { s_mn[wave][lane >> 1] = cell.mn; s_mx[wave][lane >> 1] = cell.mx; s_w[wave][lane >> 1] = cell.wild; }
+    if (lane == 0u) { s_emn[wave] = edge.mn; s_emx[wave] = edge.mx; s_ew[wave] = edge.wild; }
+    __syncthreads();
+    const unsigned bx = run * VR_CELLS + threadIdx.x;
+    if (threadIdx.x < VR_CELLS && bx < nbx) { // the one writer of this macro cell
+      VRange r = vr_none();
+      for (int w = 0; w < WAVES; w++) vr_merge(r, VRange{ s_mn[w][threadIdx.x], s_mx[w][threadIdx.x], s_w[w][threadIdx.x] });
+      if (threadIdx.x == VR_CELLS - 1)
+        for (int w = 0; w < WAVES; w++) vr_merge(r, VRange{ s_emn[w], s_emx[w], s_ew[w] });
+      const size_t b = ((size_t)bz * nby + by) * nbx + bx;
+      bmin[b] = r.mn; bmax[b] = r.mx; bnan[b] = (uint8_t)r.wild;
+    }
+    __syncthreads(); // (the next round writes the LDS again)
+  }
+}
+
+// the brick's range from its macro cells' (every vertex lies in one): ONE block of 1024 threads, four independent loads in flight per
+// thread and array (the 262 K macro cells of a 512^3 grid are 64 rounds of them); out[0] = min, out[1] = max
+#define VR_TOTAL_BLOCK 1024
+__global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float *__restrict__ bmin, const float *__restrict__ bmax, size_t n, float *__restrict__ out) {
+  __shared__ float s_mn[VR_TOTAL_BLOCK / 64], s_mx[VR_TOTAL_BLOCK / 64];
+  VRange r = vr_none();
+  size_t i = threadIdx.x;
+  for (; i + 3 * (size_t)VR_TOTAL_BLOCK < n; i += 4 * (size_t)VR_TOTAL_BLOCK) {
+    float lo[4], hi[4];
+    for (int u = 0; u < 4; u++) { lo[u] = bmin[i + u * (size_t)VR_TOTAL_BLOCK]; hi[u] = bmax[i + u * (size_t)VR_TOTAL_BLOCK]; }
+    for (int u = 0; u < 4; u++) vr_merge(r, VRange{ lo[u], hi[u], 0u });
+  }
+  for (; i < n; i += VR_TOTAL_BLOCK) vr_merge(r, VRange{ bmin[i], bmax[i], 0u });
+  r = vr_wave_all(r);
+  if ((threadIdx.x & 63u) == 0u) { s_mn[threadIdx.x >> 6] = r.mn; s_mx[threadIdx.x >> 6] = r.mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < VR_TOTAL_BLOCK / 64; w++) vr_merge(r, VRange{ s_mn[w], s_mx[w], 0u });
+    out[0] = r.mn; out[1] = r.mx;
+  }
+}
+
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
 VolDev vol_dev(const gvt_hip_volume *Vh) {
@@ -559,6 +668,67 @@ int upload_cells(gvt_hip_volume *V) {
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the table)
   HIPCHK(hipMemcpy(V->d_cells, cells.data(), sizeof(uint32_t) * nbk, hipMemcpyHostToDevice));
   return 0;
+}
+
+// bmin / bmax / bnan and vmin / vmax from d_vox (stream-ordered behind whatever wrote it), then one host wait and the download: 9 bytes
+// per macro cell.  The grid itself never comes back to the host
+int volume_ranges(gvt_hip_volume *V) {
+  Ctx &C = gctx();
+  const size_t nbk = (size_t)V->nb[0] * V->nb[1] * V->nb[2];
+  char *d = (char *)scratch_get(SCR_VOL_RANGES, 9 * nbk + 2 * sizeof(float));
+  if (!d) return GVT_HIP_ERR_DEVICE;
+  float *d_min = (float *)d, *d_max = d_min + nbk, *d_tot = d_max + nbk;
+  uint8_t *d_nan = (uint8_t *)(d_tot + 2);
+  const unsigned runs = (unsigned)((V->nb[0] + VR_CELLS - 1) / VR_CELLS);
+  const size_t n_work = (size_t)runs * V->nb[1] * V->nb[2];
+  const unsigned blocks = (unsigned)std::min(n_work, (size_t)1 << 22);
+  {
+    ProfScope ps(KC_BUILD);
+    if (V->n[0] % 4 == 0)
+      k_vol_ranges<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(V->d_vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
+    else
+      k_vol_ranges<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(V->d_vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
+    k_vol_range_total<<<1, VR_TOTAL_BLOCK, 0, C.stream>>>(d_min, d_max, nbk, d_tot);
+  }
+  HIPCHK(hipGetLastError());
+  V->bmin.resize(nbk); V->bmax.resize(nbk); V->bnan.resize(nbk); // (sized at create; an update finds them so)
+  float tot[2] = { 0.f, 0.f };
+  HIPCHK(hipMemcpyAsync(V->bmin.data(), d_min, sizeof(float) * nbk, hipMemcpyDeviceToHost, C.stream));
+  HIPCHK(hipMemcpyAsync(V->bmax.data(), d_max, sizeof(float) * nbk, hipMemcpyDeviceToHost, C.stream));
+  HIPCHK(hipMemcpyAsync(V->bnan.data(), d_nan, nbk, hipMemcpyDeviceToHost, C.stream));
+  HIPCHK(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, C.stream));
+  HIPCHK(hipStreamSynchronize(C.stream));
+  V->vmin = tot[0]; V->vmax = tot[1];
+  return 0;
+}
+
+// the tables that depend on the samples AND the transfer function (gvt_hip_volume_set_transfer, gvt_hip_volume_update_samples): d_mc,
+// n_empty and, through upload_cells, d_cells.  The one statement of the rule: a block may be skipped when every table entry its values
+// can reach -- one entry of margin either side for the rounding of the interpolation -- has a == 0: its samples then add exactly +0
+int rebuild_tables(gvt_hip_volume *V) {
+  const size_t nbk = V->bmin.size();
+  std::vector<uint8_t> mc(nbk);
+  const double value_lo = V->tf_lo, span = (double)V->tf_hi - (double)V->tf_lo;
+  auto entry = [&](float v) {
+    double p = ((double)v - value_lo) / span;
+    p = p < 0 ? 0 : (p > 1 ? 1 : p);
+    return (int)std::floor(p * 255.0);
+  };
+  int above[257]; // above[e] = entries below e with a > 0: "some entry of [e0, e1] has a > 0" is one subtraction per block (a walk over up to
+  above[0] = 0;   // 256 entries per block took 19.7 of a 512^3 update's 20.1 ms, the count 1.7 of 2.0: profiles/volume_update.txt, 3)
+  for (int e = 0; e < 256; e++) above[e + 1] = above[e] + (V->tf_a[e] > 0.f ? 1 : 0);
+  uint64_t empty = 0;
+  for (size_t b = 0; b < nbk; b++) {
+    int e0 = 0, e1 = 255;
+    if (block_is_ranged(V, b)) { e0 = V->bnan[b] ? 0 : std::max(0, entry(V->bmin[b]) - 1); e1 = std::min(255, entry(V->bmax[b]) + 2); } // (else: the whole table)
+    mc[b] = above[e1 + 1] - above[e0] > 0 ? 1 : 0;
+    empty += mc[b] ? 0 : 1;
+  }
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
+  HIPCHK(hipMemcpy(V->d_mc, mc.data(), nbk, hipMemcpyHostToDevice));
+  V->n_empty = empty;
+  V->h_mc.swap(mc);
+  return upload_cells(V);
 }
 
 // the march of q's rays through brick Vh, in place, on the context's stream (no host wait)
@@ -696,46 +866,16 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int
   V->dt = std::min(std::min(spacing[0], spacing[1]), spacing[2]) / sampling_rate;
   V->skip = (flags & GVT_HIP_VOLUME_NO_SKIP) ? 0 : 1;
   const size_t n_blocks = (size_t)V->nb[0] * V->nb[1] * V->nb[2];
-  std::vector<float> host;
-  const float *h = samples;
   bool ok = hipMalloc((void **)&V->d_vox, sizeof(float) * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
             hipMalloc((void **)&V->d_stats, 3 * sizeof(unsigned long long)) == hipSuccess &&
             hipMemset(V->d_stats, 0, 3 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
             hipMalloc((void **)&V->d_cells, sizeof(uint32_t) * n_blocks) == hipSuccess;
-  if (ok && (flags & GVT_HIP_VOLUME_DEVICE)) {
-    host.resize(total);
-    ok = hipMemcpy(host.data(), samples, sizeof(float) * total, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(V->d_vox, samples, sizeof(float) * total, hipMemcpyDeviceToDevice) == hipSuccess;
-    h = host.data();
-  } else if (ok) {
-    ok = hipMemcpy(V->d_vox, samples, sizeof(float) * total, hipMemcpyHostToDevice) == hipSuccess;
-  }
+  // the samples go to the device on the context's stream and the macro cells' ranges are computed there, behind the copy (volume_ranges
+  // ends with a host wait): samples in device memory never touch the host
+  ok = ok && hipMemcpyAsync(V->d_vox, samples, sizeof(float) * total, (flags & GVT_HIP_VOLUME_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                            gctx().stream) == hipSuccess;
   if (!ok) { set_error("volume_create: device allocation or copy failed"); gvt_hip_volume_destroy(V); return nullptr; }
-  // macro cells: the value range of the vertices of their (up to) 8^3 cells.  A vertex is a corner of the cells of its block and, on a
-  // block boundary, of the block below too
-  V->bmin.assign(n_blocks, INFINITY); V->bmax.assign(n_blocks, -INFINITY); V->bnan.assign(n_blocks, 0);
-  V->vmin = INFINITY; V->vmax = -INFINITY;
-  const size_t nx = counts[0], ny = counts[1], nz = counts[2];
-  for (size_t z = 0; z < nz; z++) {
-    const size_t bz0 = z ? (z - 1) / 8 : 0, bz1 = std::min(z / 8, (size_t)V->nb[2] - 1);
-    for (size_t y = 0; y < ny; y++) {
-      const size_t by0 = y ? (y - 1) / 8 : 0, by1 = std::min(y / 8, (size_t)V->nb[1] - 1);
-      for (size_t x = 0; x < nx; x++) {
-        const size_t bx0 = x ? (x - 1) / 8 : 0, bx1 = std::min(x / 8, (size_t)V->nb[0] - 1);
-        const float v = h[(z * ny + y) * nx + x];
-        const bool nan = v != v;
-        const bool wild = !std::isfinite(v);
-        if (!nan) { V->vmin = std::min(V->vmin, v); V->vmax = std::max(V->vmax, v); }
-        for (size_t bz = bz0; bz <= bz1; bz++)
-          for (size_t by = by0; by <= by1; by++)
-            for (size_t bx = bx0; bx <= bx1; bx++) {
-              const size_t b = (bz * V->nb[1] + by) * V->nb[0] + bx;
-              if (wild) V->bnan[b] = 1;
-              if (!nan) { V->bmin[b] = std::min(V->bmin[b], v); V->bmax[b] = std::max(V->bmax[b], v); }
-            }
-      }
-    }
-  }
+  if (volume_ranges(V)) { gvt_hip_volume_destroy(V); return nullptr; }
   return V;
 }
 
@@ -769,31 +909,40 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
     if (!std::isfinite(a)) { set_error("volume_set_transfer: opacity %g at entry %d cannot be corrected", (double)op[i][0], i); return GVT_HIP_ERR_INVALID; }
     tf[i] = make_float4(col[i][0], col[i][1], col[i][2], a);
   }
-  // macro-cell table: a block may be skipped when every table entry its values can reach -- one entry of margin either side for the
-  // rounding of the interpolation -- has a == 0: its samples then add exactly +0
-  const size_t nbk = V->bmin.size();
-  std::vector<uint8_t> mc(nbk);
-  const double span = (double)value_hi - (double)value_lo;
-  auto entry = [&](float v) {
-    double p = ((double)v - value_lo) / span;
-    p = p < 0 ? 0 : (p > 1 ? 1 : p);
-    return (int)std::floor(p * 255.0);
-  };
-  uint64_t empty = 0;
-  for (size_t b = 0; b < nbk; b++) {
-    int e0 = 0, e1 = 255;
-    if (block_is_ranged(V, b)) { e0 = V->bnan[b] ? 0 : std::max(0, entry(V->bmin[b]) - 1); e1 = std::min(255, entry(V->bmax[b]) + 2); } // (else: the whole table)
-    float amax = 0.f;
-    for (int e = e0; e <= e1; e++) amax = std::max(amax, tf[e].w);
-    mc[b] = amax > 0.f ? 1 : 0;
-    empty += mc[b] ? 0 : 1;
-  }
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
   HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(V->d_mc, mc.data(), nbk, hipMemcpyHostToDevice));
-  V->tf_lo = value_lo; V->tf_hi = value_hi; V->n_empty = empty; V->has_tf = true;
-  V->h_mc.swap(mc);
-  return upload_cells(V);
+  for (int i = 0; i < 256; i++) V->tf_a[i] = tf[i].w;
+  V->tf_lo = value_lo; V->tf_hi = value_hi; V->has_tf = true;
+  return rebuild_tables(V);
+}
+
+extern "C" int gvt_hip_volume_update_samples(gvt_hip_volume *V, const float *samples, size_t n_samples, uint32_t flags, float *ms_out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !samples) { set_error("volume_update_samples: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (flags & ~GVT_HIP_UPDATE_DEVICE) { set_error("volume_update_samples: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
+  const size_t total = (size_t)V->n[0] * V->n[1] * V->n[2];
+  if (n_samples != total) {
+    set_error("volume_update_samples: %zu samples given, the brick has %zu (%d x %d x %d; another grid needs a new volume)", n_samples, total, V->n[0], V->n[1], V->n[2]);
+    return GVT_HIP_ERR_INVALID;
+  }
+  hipStream_t st = gctx().stream;
+  HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the samples)
+  HIPCHK(hipMemcpyAsync(V->d_vox, samples, sizeof(float) * total, (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); set_error("volume_update_samples: hipEventCreate failed"); return GVT_HIP_ERR_DEVICE; }
+  int rc = hipEventRecord(e0, st) == hipSuccess ? 0 : GVT_HIP_ERR_DEVICE;
+  if (!rc) rc = volume_ranges(V);
+  if (!rc && V->has_tf) rc = rebuild_tables(V); // (else: built when the transfer function arrives)
+  float ms = 0.f;
+  if (!rc && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
+    set_error("volume_update_samples: %s", hipGetErrorString(hipGetLastError()));
+    rc = GVT_HIP_ERR_DEVICE;
+  }
+  hipStreamSynchronize(st);
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (!rc && ms_out) *ms_out = ms;
+  return rc;
 }
 
 extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isovalues, int n_iso, const float *slices, int n_slices, float opacity) {

@@ -602,6 +602,29 @@ class VolumeTracer:
         self.calls = calls.value
         return self
 
+    @staticmethod
+    def _same_bricking(adapters, bricks):
+        """Helper of update(), not part of the tracer's surface (static so that the check runs without a device): the bricks of another time
+        step as a list, if they are the adapters' bricking (counts and offset per brick; a whole VolumeData has offset 0); ValueError otherwise."""
+        bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
+        if len(bricks) != len(adapters):
+            raise ValueError("VolumeTracer.update: %d bricks given, the tracer has %d" % (len(bricks), len(adapters)))
+        for i, (a, b) in enumerate(zip(adapters, bricks)):
+            counts = np.asarray(b.counts, np.int64)
+            offset = np.asarray(getattr(b, "offset", np.zeros(3)), np.int64)
+            if (counts != a.counts).any() or (offset != a.offset).any():
+                raise ValueError("VolumeTracer.update: brick %d has counts %s at offset %s, the tracer's has %s at %s (another bricking needs a new tracer)"
+                                 % (i, counts.tolist(), offset.tolist(), a.counts.tolist(), a.offset.tolist()))
+        return bricks
+
+    def update(self, bricks):
+        """The next time step: the same bricking of the new data (scenes.split_volume with the same split, or one VolumeData), pushed into
+        the bricks in place (gvt_hip_volume_update_samples).  Transfer function, surfaces, lights, top level, queues and framebuffer stay."""
+        bricks = self._same_bricking(self.adapters, bricks)  # (all of them checked before the first one changes)
+        for a, b in zip(self.adapters, bricks):
+            a.update_samples(b.data)
+        return self
+
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
         """The volume's isosurfaces and slice planes (object space), on every brick."""
         for a in self.adapters:

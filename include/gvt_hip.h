@@ -362,9 +362,31 @@ typedef struct gvt_hip_volume_info {
   uint64_t samples_gathered;  /* ... of which were interpolated (8 voxel reads each); the others lay in empty macro cells */
 } gvt_hip_volume_info;
 int gvt_hip_volume_get_info(gvt_hip_volume *, gvt_hip_volume_info *); /* synchronises */
+/* Time-varying volumes (Volume::SetSamples, Volume.h): the next time step's samples for the same brick, in place.  n_samples must be
+ * counts[0] * counts[1] * counts[2] of the brick as created; flags: 0 (samples in host memory) or GVT_HIP_UPDATE_DEVICE (a device pointer:
+ * no host round trip of the grid).  A null volume, null samples, another n_samples or an unknown flag bit: GVT_HIP_ERR_INVALID, the volume
+ * exactly as it was.
+ * After the call the volume answers exactly like a volume freshly created from these samples with the same geometry, sampling rate and
+ * skip flag and the same set_transfer / set_surfaces / set_lights calls: every ray bit of gvt_hip_volume_trace and gvt_hip_volume_frame,
+ * value_min / value_max and n_blocks / n_blocks_empty.  The macro cells' value ranges are recomputed on the device (the kernel create
+ * itself uses: the minimum and maximum of a cell's vertices that are not NaN, and whether one of them is not finite; a vertex on a block
+ * boundary counts for both blocks) and the skip tables rebuilt from them by the rule of _set_transfer and _set_surfaces.  samples_marched,
+ * samples_gathered and the crossings go on accumulating.  Every device pointer the volume holds stays valid (nothing is re-allocated), so
+ * tracers, tops and queues built around it keep working.  The call waits for the calling context's stream first, as _set_transfer does,
+ * and returns when it is done; the caller serialises it against frames that use the brick.  Before any _set_transfer it is legal: the
+ * tables are then built when the transfer function arrives.  Samples need not be finite (the rules above).
+ * GVT_HIP_ERR_DEVICE (a HIP call failed part way): the samples may already be replaced while ranges and tables are not; the volume is then
+ * undefined until an update succeeds, and may only be updated again or destroyed.
+ * ms_out (may be NULL): time on the context's stream from the end of the upload to the end of the update (ranges, their download, the
+ * tables' rebuild on the host and their upload), as for gvt_hip_mesh_update_vertices. */
+int gvt_hip_volume_update_samples(gvt_hip_volume *, const float *samples, size_t n_samples, uint32_t flags, float *ms_out /* may be NULL */);
 /* TransferFunction: cmap rows (x r g b), omap rows (x a), each resampled to 256 entries as TransferFunction::DeviceCommit does
  * (TransferFunction.cpp:40-72); the opacity corrected on the host, a' = 1 - (1 - a)^(1 / sampling_rate) in double; the macro-cell table
- * rebuilt.  [value_lo, value_hi] maps onto the table.  At least 2 rows each, x not decreasing, value_lo < value_hi. */
+ * rebuilt.  [value_lo, value_hi] maps onto the table.  At least 2 rows each, x not decreasing, value_lo < value_hi.
+ * n_blocks_empty counts the macro cells the table leaves empty (their samples go uninterpolated unless GVT_HIP_VOLUME_NO_SKIP): with
+ * e(v) = floor(clamp((v - value_lo) / (value_hi - value_lo), 0, 1) * 255) in double, a macro cell whose vertices span [min, max] is empty
+ * when no entry in [max(0, e(min) - 1), min(255, e(max) + 2)] has a corrected opacity above 0.  The interval starts at entry 0 when a
+ * vertex of the cell is not finite, and is the whole table when the cell has no vertex that is a number or max - min reaches 3.4e38. */
 int gvt_hip_volume_set_transfer(gvt_hip_volume *, const float *cmap, int nc, const float *omap, int no, float value_lo, float value_hi);
 /* OSPRayAdapter::trace on a host RayVector: rays[begin, end) (end == 0: n) are marched through the brick (m is the instance's matrix, minv
  * its inverse; the march needs minv only) and every one of them comes back in rays_out with its flags and state.  cap too small:

@@ -4,6 +4,12 @@ voxel bytes per sample by the algorithmic count (8 reads of 4 bytes per interpol
 Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (k_volume_march); counters in a run of their own.
 
   python tools/volume_bench.py [--sizes 256 512] [--steps 10] [--warmup 2] [--json OUT]
+  python tools/volume_bench.py --update      time-varying volumes: per grid size, with the samples in host memory and in device memory, the
+                                             wall time of destroy + create + set_transfer (what a new time step cost before
+                                             gvt_hip_volume_update_samples) and of the in-place update, its ms_out and where that goes: the
+                                             range kernels (gvt_hip_profile's build class), ranges + download (an update of a volume without
+                                             a transfer function), the rest = the host table rebuild and its upload.  --recreate-only: the
+                                             first of these alone (it needs nothing the update added, so it also runs on an older tree)
   python tools/volume_bench.py --surfaces    the "thin" frames plain, with two isovalues the field never reaches (the per-sample cost of
                                              the side test alone) and with two it does (opacity 0.3, one light), each against the plain frame
 """
@@ -79,6 +85,58 @@ def run(n, split, steps, warmup, rate, kind, vol=None, surfaces=None):
             "lit_pixels": int((fb[..., 3] > 0).sum()), "setup_s": round(setup, 1)}
 
 
+def med(xs):
+    return round(float(np.median(xs)), 3)
+
+
+def run_update(n, device, steps, warmup, recreate_only):
+    """Two time steps of the n^3 noise grid, pushed alternately into one brick under the sparse table."""
+    from gravit_amd.adapter import HipVolumeAdapter
+
+    data = [scenes.noise_volume(n, seed=s).data for s in (1, 2)]
+    geo = (np.zeros(3, F), np.full(3, F(1.0 / (n - 1)), F))
+    if device:
+        import torch
+
+        data = [torch.from_numpy(d).cuda() for d in data]
+        torch.cuda.synchronize()
+    t = transfer("spikes")
+    out = {"n": n, "samples": "device" if device else "host", "grid_mb": round(4.0 * n ** 3 / 1e6, 1)}
+    ad, wall = None, []
+    for i in range(warmup + steps):  # what a new time step cost without the update: a new brick (a tracer around it not counted)
+        t0 = time.perf_counter()
+        if ad is not None:
+            ad.close()
+        ad = HipVolumeAdapter(scenes.VolumeData(data[i % 2], *geo), 1.0)
+        ad.set_transfer(t)
+        capi.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+    out["recreate_wall_ms"], out["recreate_wall_min_ms"] = med(wall[warmup:]), round(min(wall[warmup:]), 3)
+    out["n_blocks"], out["n_blocks_empty"] = ad.info()["n_blocks"], ad.info()["n_blocks_empty"]
+    if recreate_only:
+        return out
+    bare = HipVolumeAdapter(scenes.VolumeData(data[0], *geo), 1.0)  # no transfer function: its update is ranges + download alone
+    wall, ms, ms_bare, ms_kernel = [], [], [], []
+    for i in range(warmup + steps):  # profiling off: the wall time and both ms_out
+        t0 = time.perf_counter()
+        ms.append(ad.update_samples(data[(i + 1) % 2]))
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms_bare.append(bare.update_samples(data[(i + 1) % 2]))
+    capi.profile(1)
+    for i in range(warmup + steps):  # a pass of its own for the range kernels' event time (the profiling events are not in the times above)
+        k0 = capi.stats()["ms_build"]
+        ad.update_samples(data[(i + 1) % 2])
+        ms_kernel.append(capi.stats()["ms_build"] - k0)
+    capi.profile(0)
+    w = warmup
+    out.update({"update_wall_ms": med(wall[w:]), "update_wall_min_ms": round(min(wall[w:]), 3), "update_ms_out": med(ms[w:]),
+                "range_kernels_ms": med(ms_kernel[w:]), "ranges_and_download_ms": med(ms_bare[w:]),
+                "table_rebuild_ms": med(np.array(ms[w:]) - np.array(ms_bare[w:])),
+                "range_kernel_gbs_of_grid": round(4.0 * n ** 3 / 1e6 / max(float(np.median(ms_kernel[w:])), 1e-9), 1),
+                "recreate_over_update": round(out["recreate_wall_ms"] / max(float(np.median(wall[w:])), 1e-9), 1)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
@@ -88,9 +146,20 @@ def main():
     ap.add_argument("--tf", nargs="+", default=["thin", "spikes"])
     ap.add_argument("--json")
     ap.add_argument("--surfaces", action="store_true")
+    ap.add_argument("--update", action="store_true")
+    ap.add_argument("--recreate-only", action="store_true")
     a = ap.parse_args()
+    if a.update:
+        import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
     capi.init(0)
     out = {"source_hash": _build.source_hash(), "width": 1920, "height": 1080, "runs": []}
+    if a.update:
+        for n in a.sizes:
+            for device in (False, True):
+                r = run_update(n, device, a.steps, a.warmup, a.recreate_only)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+        a.sizes = []
     for n in a.sizes if a.surfaces else ():
         vol = scenes.noise_volume(n, seed=1)
         vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
