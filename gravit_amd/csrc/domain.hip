@@ -38,9 +38,9 @@
 int shuffle_async(gvt_hip_top *T, gvt_hip_queue *q_in, size_t n_ub, const int *from_arr, int from, gvt_hip_queue *const *queues, const uint8_t *keep_mask,
                   gvt_hip_fb *fb, unsigned *d_overflow, const void *d_qdesc);
 int shuffle_exact(gvt_hip_top *T, gvt_hip_queue *q_in, const int *from_arr, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb);
-int camera_one_instance_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt_hip_queue *q, gvt_hip_fb *fb, unsigned *d_overflow, unsigned *d_moved_count);
+int camera_one_instance_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt_hip_queue *q, gvt_hip_fb *fb, unsigned *d_overflow, unsigned *d_moved_count, unsigned *row_rays);
 int camera_filter_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt_hip_queue *const *queues, const uint8_t *keep_mask, unsigned *d_overflow,
-                        size_t first, size_t count, bool rect = false);
+                        size_t first, size_t count, bool rect = false, unsigned *row_rays = nullptr);
 size_t camera_instance_bound(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, size_t inst);
 
 // ------------------------------------------------------------------------------------------------
@@ -876,6 +876,7 @@ struct gvt_hip_tracer {
   int fin_choice = -1;         // -1: probing (frames take the routes in turn), else the route
   int fin_limit = 0;           // the frame in progress: rounds of at most this many rays go through k_finish
   int hop_now = 0;             // the frame in progress: hops (TraceParams::hop)
+  unsigned cam_row_rays = 0;   // the frame in progress: list positions per row of tiles of the camera list its filter enumerated (0: unknown / not in tiles)
   bool fin_eligible = false;   // the frame in progress had a round small enough for k_finish
   unsigned fin_probe = 0;
   double fin_best[6] = { 1e30, 1e30, 1e30, 1e30, 1e30, 1e30 }; // fastest frame seen with each route, ms
@@ -1169,6 +1170,7 @@ int local_chain(gvt_hip_tracer *R, const std::vector<size_t> *extra_in, uint64_t
     if (nI == 1) one.planes.p5 = nullptr; // no other instance a ray could have missed: the list is neither read nor written
     one.mesh = R->meshes[i0]; one.inst = i0;
     one.coherent = (fresh_from_camera && C.camera_tile == 8) ? 1 : 0;
+    one.row_rays = one.coherent ? R->cam_row_rays : 0u;
     one.n_dev = count_on_device ? R->queues[i0]->d_count : nullptr; // present[i0] is then only the bound (the whole camera list)
     one.pass0_begun = pass0_begun ? 1 : 0;
     std::memcpy(one.minv.m, R->minv.data() + 16 * (size_t)i0, 64);
@@ -1474,6 +1476,7 @@ extern "C" int gvt_hip_tracer_frame(gvt_hip_tracer *R, int flags, gvt_hip_frame_
   for (size_t i = 0; i < nI; i++) R->queues[i]->size = 0;
   R->q_moved->size = 0;
   R->sizes_exact = true; R->spec_enqueued_last = false;
+  R->cam_row_rays = 0u;
   bool first_on_device = false; // the queues hold the camera's rays, their sizes are on the device only (R->present: bounds)
   if (!lean) {
     if ((rc = gvt_hip_fb_clear(R->fb))) return rc;
@@ -1483,8 +1486,8 @@ extern "C" int gvt_hip_tracer_frame(gvt_hip_tracer *R, int flags, gvt_hip_frame_
     const size_t n_cam = (size_t)R->cam.width * R->cam.height * R->cam.samples * R->cam.samples;
     const int passes0 = R->cam.depth > 1 ? R->cam.depth : 1;
     if ((rc = queue_reserve(R->queues[0], n_cam * (size_t)(1 + (int)R->lights.size() * passes0)))) return rc; // what local_chain will ask for: no move later
-    if (lean) { if ((rc = camera_one_instance_async(R->top, &R->cam, C.camera_tile, R->queues[0], R->fb, R->d_overflow, R->q_moved->d_count))) return rc; }
-    else if ((rc = camera_filter_async(R->top, &R->cam, C.camera_tile, R->queues.data(), nullptr, R->d_overflow, 0, 0))) return rc;
+    if (lean) { if ((rc = camera_one_instance_async(R->top, &R->cam, C.camera_tile, R->queues[0], R->fb, R->d_overflow, R->q_moved->d_count, &R->cam_row_rays))) return rc; }
+    else if ((rc = camera_filter_async(R->top, &R->cam, C.camera_tile, R->queues.data(), nullptr, R->d_overflow, 0, 0, false, &R->cam_row_rays))) return rc;
     R->present[0] = n_cam;
     R->queues[0]->size = n_cam; // bound of what the device holds (a reallocation would copy at least that)
     if ((rc = local_chain(R, nullptr, &S.chains, true, true, lean, lean))) return rc;
@@ -1520,7 +1523,7 @@ extern "C" int gvt_hip_tracer_frame(gvt_hip_tracer *R, int flags, gvt_hip_frame_
     }
     if (on_device) {
       for (size_t i = 0; i < nI; i++) if (room[i] && (rc = queue_reserve(R->queues[i], room[i]))) return rc;
-      if ((rc = camera_filter_async(R->top, &R->cam, C.camera_tile, R->queues.data(), keep, R->d_overflow, 0, 0, true))) return rc;
+      if ((rc = camera_filter_async(R->top, &R->cam, C.camera_tile, R->queues.data(), keep, R->d_overflow, 0, 0, true, &R->cam_row_rays))) return rc;
       for (size_t i = 0; i < nI; i++) { R->present[i] = room[i]; R->queues[i]->size = room[i]; } // bounds, until the first report
       first_on_device = true;
     } else {

@@ -13,6 +13,7 @@
 #include "../../include/gvt_hip.h"
 #define GVT_MATH_FN __host__ __device__ static inline
 #include "../../include/gvt_math.h"
+#include "xcd_stripes.h"
 
 #define GVT_RAY_EPSILON 1.e-6f   // actor/Ray.cpp:33
 #define GVT_FLT_MAX 3.402823466e+38f
@@ -21,7 +22,8 @@
 // The words of a context's device counter array (Ctx::d_counters, gvt_internal.h), for host code and kernels alike.  The numbering is fixed:
 // gvt_hip_counters_peek shows words 0..CW_PEEK-1 and k_trace_begin / launch_closest zero CW_WORK..CW_LONG_WORK as one run.
 enum CounterWord {
-  CW_WORK = 0,         // work counter of the traversal launch in flight (k_trace's `counter`); reset: k_trace_begin, k_wave_pass_begin, k_shade (zero_word), k_round_report
+  CW_WORK = 0,         // work counter of the traversal launch in flight (k_trace's `counter`); reset: k_trace_begin, k_wave_pass_begin, k_shade (zero_word), k_round_report.
+                       //   Also stripe 0's of the eight the launch over the camera's list draws from (cw_work_stripe): all eight reset by cw_zero_work in k_wave_pass_begin, k_cam1_scatter
   CW_SHADOW = 1,       // shadow rays of the pass; reset: k_trace_begin / trace_core per pass, k_wave_pass_begin
   CW_BOUNCE_A = 2,     // bounce list counts, alternating by pass (cw_bounce); reset: k_wave_pass_begin (both at pass 0, the current one afterwards),
   CW_BOUNCE_B = 5,     //   k_trace_begin / trace_core per pass (A only: trace_core reads the count back)
@@ -36,12 +38,23 @@ enum CounterWord {
   CW_MERGED_N = 22,    // length of a merged list only the device knows (k_wave_pass_begin writes it from the count words); never reset, written before it is read
   CW_SHADOW_CLS = 24,  // SHADOW_CLASSES class counts of the ordered shadow list (shade.inc); reset: k_wave_pass_begin
   CW_PEEK = 32,        // words gvt_hip_counters_peek copies out
-  CW_COUNT = 64        // words allocated
+  CW_WORK_XCD = 64,    // the work counters of stripes 1..7 (xcd_stripes.h), CW_LINE words apart: a 128-byte line each, since every XCD's waves pull on their own
+  CW_LINE = 32,
+  CW_COUNT = CW_WORK_XCD + 7 * CW_LINE // words allocated
 };
+// stripe x's work counter as a word offset from CW_WORK (k_trace knows its `counter` = d_counters + CW_WORK only)
+__host__ __device__ constexpr unsigned cw_work_stripe(unsigned x) { return x ? (unsigned)CW_WORK_XCD - CW_WORK + (x - 1u) * CW_LINE : 0u; }
+// all eight work counters := 0, by one thread of a kernel in front of a launch that draws from all of them -- a striped one, trace.hip stripe_arg -- (c = the context's counter words)
+__device__ inline void cw_zero_work(unsigned *c) {
+#pragma unroll
+  for (unsigned x = 0; x < 8u; x++) c[CW_WORK + cw_work_stripe(x)] = 0u;
+}
 enum { TOT_CLOSEST = 0, TOT_ANY = 1 }; // the pair of 64-bit totals at CW_TOT_CLOSEST, as cw_totals() sees it
 __host__ __device__ inline unsigned long long *cw_totals(unsigned *c) { return (unsigned long long *)(c + CW_TOT_CLOSEST); }
 __host__ __device__ inline int cw_bounce(int pass) { return (pass & 1) ? CW_BOUNCE_B : CW_BOUNCE_A; } // the list pass `pass` WRITES (and pass + 1 reads)
 static_assert(CW_TOT_ANY == CW_TOT_CLOSEST + 2 && CW_LONG_FRAME == CW_TOT_ANY + 2, "k_cam1_count clears the totals and the parked total as one run of five words");
+static_assert(CW_LINE * sizeof(unsigned) == 128 && CW_WORK_XCD % CW_LINE == 0 && CW_WORK + cw_work_stripe(7) < CW_COUNT, "every stripe's work counter has a 128-byte line of its own inside the allocation");
+static_assert(CW_SHADOW_CLS + 8 <= CW_WORK_XCD && CW_PEEK <= CW_WORK_XCD, "no named counter word shares a line with the counters of stripes 1..7 (stripe 0 keeps CW_WORK's)");
 static_assert(CW_LONG_WORK == 4 && CW_BOUNCE_A < 5 && CW_LONG < 5, "k_trace_begin / launch_closest zero words 0..4 as one run");
 
 struct V3 {

@@ -69,6 +69,9 @@ struct Knobs {
   int shadow_order = 1;  // single-mesh rounds with one light: the shadow rays are listed by the step count of their primaries' tiles, the longest first (shade.inc);
                          // 0: in arrival order.  The any-hit launch's drain is then left to short rays: 0.318 -> 0.281 ms in tools/order_probe.py
   int shadow_cls_lo = 24, shadow_cls_shift = 3; // ... class of a 64-ray tile = (node steps of its longest primary - lo) >> shift, clamped to 0..7 (tuned constants)
+  int xcd_stripes = 1;   // the single-mesh k_trace launch over the camera's tile-ordered list (lists without film geometry stay front to back): every XCD's waves draw from a stripe of the ray list of their own -- an eighth of every list row, all stripes going down
+                         // the film together (xcd_stripes.h) --, so that an XCD's L2 holds its columns of the band in flight instead of the whole band; they take from the other
+                         // stripes once their own is used up.  0: the list front to back from one counter.  The order of work only: results never depend on it
   int shadow_order_min_rays = 262144; // ... in launches of at least this many rays (a small launch has no drain worth ordering)
   int packet_min_rays = 524288; // ... and only in launches of at least this many rays (bound): a small launch is a few thousand packets, each a long serial walk
   int packet_sah_max = 128; // meshes created afterwards: packet-friendly when sum(area(inner node)) / area(root) is at most this (lbvh.hip k_sah_sum)
@@ -346,6 +349,7 @@ struct WaveSingle { // the launch has ONE segment: its queue planes and instance
   Mat3 normi;
   int inst;
   int coherent; // the queue holds camera rays in tile order, straight from the filter: packet traversal (k_packet)
+  unsigned row_rays; // ... and one row of tiles across the enumerated film is this many list positions (0: unknown); the stripes' row length (xcd_stripes.h)
   const unsigned *n_dev; // the first pass's ray count lives in device memory (the queue's count word; n_total is only its bound)
   int pass0_begun;       // the producer of the queue (k_cam1_scatter) has already done k_wave_pass_begin's pass-0 resets
 };

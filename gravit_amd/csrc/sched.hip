@@ -268,7 +268,7 @@ __global__ __launch_bounds__(TOP_BLOCK) void k_cam1_scatter(CamArgs A, unsigned 
     *Q.count = total;
     unsigned long long *tot = cw_totals(c); // k_wave_pass_begin, pass 0 (trace.hip)
     *moved_count = 0u; c[CW_BOUNCE_A] = 0u; c[CW_BOUNCE_B] = 0u; tot[TOT_CLOSEST] += total;
-    c[CW_WORK] = 0u; c[CW_SHADOW] = 0u; c[CW_LONG] = 0u; c[CW_LONG_WORK] = 0u; c[CW_PKT_RETRY] = 0u;
+    cw_zero_work(c); c[CW_SHADOW] = 0u; c[CW_LONG] = 0u; c[CW_LONG_WORK] = 0u; c[CW_PKT_RETRY] = 0u;
     for (int k = 0; k < SHADOW_CLASSES; k++) c[CW_SHADOW_CLS + k] = 0u;
   }
 }
@@ -582,13 +582,20 @@ int shuffle_async(gvt_hip_top *T, gvt_hip_queue *q_in, size_t n_ub, const int *f
   S.from_cam = 0;
   return shuffle_async_src(T, S, n_ub, q_in->d_count, from_arr, from, queues, keep_mask, fb, d_overflow, d_qdesc);
 }
+// list positions per row of 8x8 tiles of the list these arguments enumerate (0: not in tiles): what the filters below hand back in *row_rays, for a traversal launch
+// over a queue filled from that list in list order to take as its row length (xcd_stripes.h)
+static unsigned camera_row_rays(const CamArgs &A) {
+  if (A.tile != 8) return 0u;
+  const size_t tiles = A.rect_on ? (size_t)A.rtpr : (size_t)(A.W >> 3);
+  return (unsigned)std::min<size_t>(tiles * 64u * (size_t)(A.samples * A.samples), 0x7fffffffu);
+}
 // generateRays + FilterRaysLocally without a read-back: every kept queue must have room for all W*H*samples^2 rays; the queue counts
 // advance on the device only (the caller's first launch chain reads its ray count from there)
 // [first, first + count) of the generated list (count == 0: all of it): a rank's portion under the multi-rank Image scheduler
 static bool camera_keep_rect(const gvt_hip_top *T, CamArgs &A, const uint8_t *keep_mask);
 // rect: enumerate only the film rectangle the kept instances project onto (the whole list, first == count == 0)
 int camera_filter_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt_hip_queue *const *queues, const uint8_t *keep_mask, unsigned *d_overflow,
-                        size_t first, size_t count, bool rect) {
+                        size_t first, size_t count, bool rect, unsigned *row_rays) {
   const size_t n_all = (size_t)cam->width * cam->height * cam->samples * cam->samples;
   if (n_all > 0xffffffffull) { set_error("camera_filter: more than 2^32 rays"); return GVT_HIP_ERR_INVALID; }
   RaySrc S{};
@@ -600,6 +607,7 @@ int camera_filter_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt
     if (!count) count = n_all - first;
     S.cam.first = (unsigned)first;
   }
+  if (row_rays) *row_rays = first ? 0u : camera_row_rays(S.cam);
   return shuffle_async_src(T, S, count, nullptr, nullptr, -1, queues, keep_mask, nullptr, d_overflow, nullptr);
 }
 // Upper bound of the camera rays that can have instance `inst` as their first domain: the positions of the film rectangle its box
@@ -615,7 +623,7 @@ size_t camera_instance_bound(gvt_hip_top *T, const gvt_hip_camera *cam, int tile
 }
 // clearBuffer + generateRays + FilterRaysLocally for a ONE-instance scene on one rank, with the launch chain's pass-0 resets folded
 // in (k_cam1_count / k_cam1_scatter).  q must have room for all W*H*samples^2 rays; its count lives on the device only.
-int camera_one_instance_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt_hip_queue *q, gvt_hip_fb *fb, unsigned *d_overflow, unsigned *d_moved_count) {
+int camera_one_instance_async(gvt_hip_top *T, const gvt_hip_camera *cam, int tile, gvt_hip_queue *q, gvt_hip_fb *fb, unsigned *d_overflow, unsigned *d_moved_count, unsigned *row_rays) {
   Ctx &C = gctx();
   const size_t n = (size_t)cam->width * cam->height * cam->samples * cam->samples;
   if (!n || n > 0xffffffffull || T->n != 1) { set_error("camera_one_instance: bad arguments"); return GVT_HIP_ERR_INVALID; }
@@ -628,6 +636,7 @@ int camera_one_instance_async(gvt_hip_top *T, const gvt_hip_camera *cam, int til
     if (fb) HIPCHK(hipMemsetAsync(fb->d_rgba, 0, sizeof(float) * 4 * (size_t)fb->w * fb->h, C.stream));
     fb = nullptr;
   }
+  if (row_rays) *row_rays = camera_row_rays(A);
   if (!n_list) n_list = 1; // (nothing in view: one empty position, so that the kernels still publish the counts and do the resets)
   const unsigned n_blk = blocks_for(n_list, TOP_BLOCK);
   unsigned *d_blk = (unsigned *)scratch_get(SCR_BLOCK_COUNTS, sizeof(unsigned) * n_blk);

@@ -243,7 +243,12 @@ static int sort_ray_list(const gvt_hip_mesh *M, RayPlanes q, const unsigned **id
 }
 
 // Where a traversal step's rays and geometry come from: one mesh (q, minv, T; W empty) or a round's segments (MULTI kernels: W; q, minv, T empty).
-struct TraceSrc { RayPlanes q; Mat4 minv; Trav T; WaveSet W; TermSink sink; MultiSrc MS; const int *hop; }; // hop: MultiSrc::hop_inst for the wave-per-ray kernels
+struct TraceSrc { RayPlanes q; Mat4 minv; Trav T; WaveSet W; TermSink sink; MultiSrc MS; const int *hop; unsigned row; }; // hop: MultiSrc::hop_inst for the wave-per-ray kernels; row: the list's row length in rays where it has film geometry (xcd_stripes.h), else 0
+// k_trace's stripe_row for a single-mesh launch over a list of that row length (knob xcd_stripes).  A list without film geometry (row 0: bounce and index lists, shadow
+// lists, the adapter's queries) is handed out front to back: stripes over default rows group the rays as that order already does -- the any-hit launch showed the same
+// L2 counters either way, profiles/xcd_stripes.txt -- and cost a wave up to eight atomics at its end where the one counter costs one.  So only the launch over the camera's
+// coherent list draws from the eight counters, and only the kernels in front of THAT launch (k_wave_pass_begin, k_cam1_scatter) have to zero them all (cw_zero_work).
+static unsigned stripe_arg(unsigned row) { return (gctx().xcd_stripes && row) ? row : XCD_STRIPES_OFF; }
 enum StepMode { BY_LANES, BY_PACKETS, BY_WAVES }; // k_trace (+ its parked rays a wave each) | k_packet (+ the packets that bailed out) | a wave per ray (small launches)
 static int wave_grid(size_t n) { return (int)std::min<size_t>((n + 3) / 4, (size_t)gctx().n_cu * 3); }
 
@@ -271,7 +276,7 @@ static void closest_step(StepMode mode, const TraceSrc &S, const unsigned *idx, 
     {
       ProfScope ps(KC_CLOSEST);
       launch_trace<false, XFORM, 0, MULTI>(trav_grid2(n, true), st, S.q, idx, (unsigned)n, S.minv, S.T, tnear, d_hits, nullptr, none, nullptr, c + CW_WORK, C.d_spill,
-                                           C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LQ, S.MS);
+                                           C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LQ, S.MS, MULTI ? XCD_STRIPES_OFF : stripe_arg(S.row));
     }
     if (LQ.steps) {
       ProfScope ps(KC_LONG);
@@ -289,7 +294,7 @@ static void any_step(StepMode mode, const TraceSrc &S, const unsigned *idx, size
   ProfScope ps(KC_ANY);
   if (mode == BY_WAVES) k_wave_any<MULTI><<<wave_grid(grid_rays), 256, 0, C.stream>>>(S.q, c + CW_SHADOW, S.minv, S.T, GVT_RAY_EPSILON, out, out_count, c + CW_WORK, S.sink, S.MS);
   else launch_trace<true, true, 1, MULTI>(trav_grid2(grid_rays), C.stream, S.q, idx, n, S.minv, S.T, GVT_RAY_EPSILON, nullptr, nullptr, out, out_count, c + CW_WORK, C.d_spill,
-                                          C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{}, S.MS);
+                                          C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{}, S.MS, MULTI ? XCD_STRIPES_OFF : stripe_arg(S.row));
 }
 
 // The fields of ShadeArgs every chain sets alike (the rest is zero); the caller adds its source (in or W), and what else differs.
@@ -366,8 +371,8 @@ int launch_any_flags(gvt_hip_mesh *M, RayPlanes q, size_t n, bool xform, const M
   RayPlanes none{};
   {
     ProfScope ps(KC_ANY);
-    if (xform) launch_trace<true, true, 0>(trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{});
-    else launch_trace<true, false, 0>(trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{});
+    if (xform) launch_trace<true, true, 0>(trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{}, MultiSrc{}, stripe_arg(0u));
+    else launch_trace<true, false, 0>(trav_grid2(n), C.stream, q, nullptr, (unsigned)n, minv, T, tnear, nullptr, d_flags, none, nullptr, counter, C.d_spill, C.refill_min, C.inner_min, nullptr, C.share, (unsigned)C.share_min_rays, TermSink{}, LongQ{}, MultiSrc{}, stripe_arg(0u));
   }
   HIPCHK(hipGetLastError());
   C.stats.rays_any += n;
@@ -488,7 +493,7 @@ __global__ void k_wave_pass_begin(unsigned *c, int pass, unsigned n_host, unsign
   if (pass == 0) { *out_count = 0u; c[CW_BOUNCE_A] = 0u; c[CW_BOUNCE_B] = 0u; tot[TOT_CLOSEST] += n_dev0 ? *n_dev0 : n_host; }
   else { tot[TOT_ANY] += c[CW_SHADOW]; tot[TOT_CLOSEST] += c[prev]; c[cur] = 0u; }
   c[CW_LONG_FRAME] += c[CW_LONG]; // rays parked by the launch before (the frame's total: the tracer adapts its parking threshold to it)
-  c[CW_WORK] = 0u; c[CW_SHADOW] = 0u; c[CW_LONG] = 0u; c[CW_LONG_WORK] = 0u; c[CW_PKT_RETRY] = 0u;
+  cw_zero_work(c); c[CW_SHADOW] = 0u; c[CW_LONG] = 0u; c[CW_LONG_WORK] = 0u; c[CW_PKT_RETRY] = 0u;
   for (int k = 0; k < SHADOW_CLASSES; k++) c[CW_SHADOW_CLS + k] = 0u; // the shadow list's class counts (shade.inc)
 }
 // end of a round's chain: the last pass's shadow rays into the frame total; and the traced queues' clear() (count words of the
@@ -524,7 +529,7 @@ static int any_packets(const Chain &K, const TraceSrc &S) {
   k_packet<true><<<blocks_for(K.B.shadow_cap), 256, 0, C.stream>>>(S.q, (unsigned)K.B.shadow_cap, nullptr, S.minv, S.T, GVT_RAY_EPSILON, nullptr, K.d_shadow_inst, K.outp, K.out->d_count,
                                                                  S.sink, LongQ{}, d_retry, c + CW_PKT_RETRY, cw_totals(c) + TOT_ANY, c + CW_PACKETS);
   launch_trace<true, true, 1>(trav_grid2(4096), C.stream, S.q, d_retry, 0u, S.minv, S.T, GVT_RAY_EPSILON, nullptr, nullptr, K.outp, K.out->d_count, c + CW_WORK, C.d_spill,
-                              C.refill_min, C.inner_min, c + CW_PKT_RETRY, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{});
+                              C.refill_min, C.inner_min, c + CW_PKT_RETRY, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{}, MultiSrc{}, stripe_arg(0u));
   return 0;
 }
 
@@ -545,6 +550,7 @@ static int single_pass(const Chain &K, Pass p, const WaveSingle &W1, size_t cls_
     if (int rc = sort_ray_list(M, W1.planes, &p.idx, n, n, W1.minv, p.n_dev)) return rc;
   TraceSrc S{};
   S.q = W1.planes; S.minv = W1.minv; S.T = Trav{ M->d_nodes, M->d_tri, M->d_nodes4 };
+  S.row = (W1.coherent && p.pass == 0 && !p.idx) ? W1.row_rays : 0u; // the camera's list in tile order; bounce lists have no film geometry
   LongQ LQ{};
   if (K.use_long && have4) LQ = long_queue(K.d_long, n);
   LQ.steps_out = K.B.steps;
@@ -565,7 +571,7 @@ static int single_pass(const Chain &K, Pass p, const WaveSingle &W1, size_t cls_
   shade_step<false>(A, mesh_view(M), lean_shade);
   if (!nL) return 0;
   TraceSrc SA = S;
-  SA.q = K.B.shadow; SA.sink = A.sink;
+  SA.q = K.B.shadow; SA.sink = A.sink; SA.row = 0u;
   if (pkt_any) return any_packets(K, SA);
   if (by_class) { SA.MS.cls_cnt = c + CW_SHADOW_CLS; SA.MS.cls_stride = (unsigned)cls_stride; SA.MS.cls_total = c + CW_SHADOW; }
   any_step<false>(small1 ? BY_WAVES : BY_LANES, SA, nullptr, K.B.shadow_cap, 0u, by_class ? nullptr : c + CW_SHADOW, K.outp, K.out->d_count);

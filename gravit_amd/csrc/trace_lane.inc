@@ -180,6 +180,51 @@ __device__ inline void flush_pending(volatile unsigned *pend, int n_pend, const 
   }
 }
 
+// k_trace's work distribution for the single-mesh launches (see there): the wave's next range [ub, ue) of the list, or ub > ue: nothing is left.  Wave-uniform.
+//   row == XCD_STRIPES_OFF: front to back -- first the wave's static chunk, then `dyn` rays at a time from the one counter;
+//   otherwise the stripes of xcd_stripes.h -- first the wave's static units in its home stripe, then units from that stripe's counter, then from the other stripes'.
+// A function of its own and not inlined: its divisions and 64-bit products otherwise take part in the register allocation of the whole kernel, which the
+// closest-hit instantiation, at its budget of 96, pays for with scratch spills.
+// state: the wave's progress, 0 at first -- bits 0..3: it draws from stripe (home + that) & 7, 8 = every stripe is used up; bit 4: set after the first fetch;
+// bits 5..: static units it has yet to take.  Returns (ub, ue, new state); the caller makes the three words scalar again (readfirstlane).
+template <unsigned frac8> __device__ __noinline__ uint3 kt_fetch(unsigned *counter, unsigned n, unsigned row, unsigned state) {
+  // chunk is a fraction of a wave's fair share (frac8 / 8), never less than one wave's width; dyn is 1/16 of the share, at least 64 (32: the counter word saturates)
+  const unsigned wpb = (unsigned)(TRAV_BLOCK / 64), n_waves_total = gridDim.x * wpb, share_w = n / n_waves_total;
+  const unsigned chunk = max(64u, ((share_w * frac8 / 8u) + 16u) & ~31u), dyn = max(64u, (share_w / 16u) & ~63u);
+  unsigned ub = 1u, ue = 0u;
+  if (row == XCD_STRIPES_OFF) { // KEEP IN STEP with the merged launches' copy of this order in k_trace's refill (chunk, dyn, first_chunk there): knob 0 promises their order
+    unsigned base = 0, len = chunk;
+    if (!(state & 16u)) base = (blockIdx.x * wpb + (threadIdx.x >> 6)) * chunk;
+    else {
+      if (lane_id() == 0) base = atomicAdd(counter, dyn);
+      base = (unsigned)__builtin_amdgcn_readfirstlane((int)base) + n_waves_total * chunk;
+      len = dyn;
+    }
+    if (base < n) { ub = base; ue = min(base + len, n); }
+    return make_uint3(ub, ue, 16u);
+  }
+  const XcdStripeMap SM = xcd_stripe_map(n, dyn, row);
+  const unsigned ks = max(1u, (chunk + dyn / 2u) / dyn), home = blockIdx.x & 7u; // the static part in units
+  unsigned st_steal = state & 15u, st_left = (state & 16u) ? state >> 5 : ks;
+  bool got = false;
+  if (st_left) { // this wave's static units; one beyond the stripe's end: so are the rest
+    const unsigned s = (blockIdx.x >> 3) * wpb + (threadIdx.x >> 6);
+    got = xcd_stripe_unit(SM, home, s * ks + (ks - st_left), &ub, &ue);
+    st_left = got ? st_left - 1u : 0u;
+  }
+  while (!got && st_steal < XCD_STRIPES) {
+    const unsigned x = (home + st_steal) & 7u;
+    unsigned t = 0;
+    if (lane_id() == 0) t = atomicAdd(counter + cw_work_stripe(x), 1u);
+    // (behind the static units of the stripe's own waves: those of the blocks x, x + 8, ... of this grid)
+    t = (unsigned)__builtin_amdgcn_readfirstlane((int)t) + ((gridDim.x + 7u - x) >> 3) * wpb * ks;
+    got = xcd_stripe_unit(SM, x, t, &ub, &ue);
+    if (!got) st_steal++;
+  }
+  if (!got) { ub = 1u; ue = 0u; }
+  return make_uint3(ub, ue, st_steal | 16u | (st_left << 5));
+}
+
 // MULTI (merged launch, gvt_internal.h): closest hit -- ray j is virtual index (idx ? idx[j] : j) of the segment table MS.W; any hit --
 // ray j of q was generated in instance MS.ray_inst[j]; either way the lane takes transform and acceleration structure from
 // MS.W.insts[instance].  out_from receives the source instance of every survivor appended to `out`.
@@ -212,13 +257,19 @@ template <bool ANY, bool XFORM, int MODE, bool MULTI = false>
 __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSEST)) void k_trace(RayPlanes q, const unsigned *__restrict__ idx, unsigned n, Mat4 minv, Trav T, float tnear,
                                                        gvt_hip_hit *__restrict__ hits, int *__restrict__ flags, RayPlanes out, unsigned *out_count,
                                                        unsigned *counter, int *spill_base, int refill_min, int inner_min, const unsigned *__restrict__ n_dev, int share, unsigned share_min, TermSink sink, LongQ LQ,
-                                                       MultiSrc MS = MultiSrc{}) {
-  // Work distribution: wave w first takes the static range [w*chunk, (w+1)*chunk) -- no atomic, see the refill below -- and after that
+                                                       MultiSrc MS = MultiSrc{}, unsigned stripe_row = XCD_STRIPES_OFF) {
+  // Work distribution, stripes off (stripe_row == XCD_STRIPES_OFF; the merged launches always): wave w first takes the static range [w*chunk, (w+1)*chunk) -- no atomic, see the refill below -- and after that
   // dynamic ranges of `dyn` rays from the counter.  chunk is a fraction of a wave's fair share (3/8 for closest-hit launches, whose
   // per-ray cost varies most, 5/8 for any-hit; measured at 1 M rays: 96/128/160 rays -> 0.542/0.549/0.579 ms closest, 0.400/0.400/0.384
   // any), never less than one wave's width; dyn is 1/16 of the share, at least 64 (32: the counter word saturates).
   // (refill_min / inner_min / share stay kernel arguments in the shipped library too, although only the experiments build can move them: as
   // compile-time constants they cost 1.5 % of the any-hit launch -- 0.3555 against 0.3500 ms, the register allocation changes)
+  // Stripes on (single-mesh launches, knob xcd_stripes; stripe_row = the list's row length, 0: none known): the list is handed out in UNITS of `dyn` rays through
+  // the mapping of xcd_stripes.h, a stripe and a work counter (cw_work_stripe) per XCD.  Blocks are dealt to the XCDs round-robin, so a wave's home stripe is
+  // blockIdx.x & 7.  Its static first part, again without an atomic, are the units [s * ks, (s + 1) * ks) of that stripe -- s = its number among the stripe's waves,
+  // ks = chunk in units --; the stripe's counter hands out the units behind those of all its waves.  A wave whose stripe is used up goes on to the next stripe's
+  // counter, and so on round all eight (a grid of fewer than eight blocks reaches the stripes without waves of their own in this way): at most one atomic per
+  // stripe it finds used up, never a wait.  All of it is scalar code in the refill path.
   const unsigned n_waves_total = gridDim.x * (unsigned)(TRAV_BLOCK / 64);
   // glm's mat4 * vec4(d, 0) keeps the terms m[12..14] * 0 (they matter for -0 / inf / NaN only; parity keeps them).  launch_trace computes them on the host and
   // hands them over in the matrix's unused bottom row (m[3], m[7], m[11]): scalar registers, not three vector registers held -- and spilled -- for the whole launch
@@ -277,6 +328,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
   unsigned c_next = 0, c_end = 0; // wave-uniform
   bool exhausted = false;         // wave-uniform
   bool first_chunk = true;        // wave-uniform
+  unsigned st_state = 0;          // wave-uniform, single-mesh launches: where the wave stands in its work distribution (kt_fetch)
   bool active = false;
   unsigned j = 0;
   V3 O = mk3(0, 0, 0), D = mk3(0, 0, 1);
@@ -310,6 +362,21 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
         if (c_next == c_end) {
           // the first chunk of every wave is assigned statically (chunk number = wave number): 4096 waves hitting one counter word at
           // launch would queue for ~45 us (a single word sustains ~90 atomics/us); the dynamic chunks start behind those
+          if constexpr (!MULTI) {
+            const uint3 f = kt_fetch<ANY ? 5u : 3u>(counter, n, stripe_row, st_state);
+            const unsigned ub = (unsigned)__builtin_amdgcn_readfirstlane((int)f.x), ue = (unsigned)__builtin_amdgcn_readfirstlane((int)f.y);
+            st_state = (unsigned)__builtin_amdgcn_readfirstlane((int)f.z);
+            if (ub > ue) {
+              exhausted = true;
+#if GVT_STAMP
+              if (!t_exh) { t_exh = __builtin_amdgcn_s_memtime(); it_exh = n_inner_it; out_exh = n_outer_it; act_exh = 64 - nidle; }
+#endif
+              break;
+            }
+            c_next = ub; c_end = ue;
+            if (ub == ue) continue; // an empty unit (a part shorter than the row's longest): the next one
+          } else { // the merged launches: front to back, inline -- KEEP IN STEP with kt_fetch's XCD_STRIPES_OFF branch (routing them through kt_fetch changes the
+                   // register allocation of the merged kernels, which this change leaves as they were)
           unsigned base = 0;
           unsigned this_chunk = chunk;
           if (first_chunk) {
@@ -329,6 +396,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
           }
           c_next = base;
           c_end = min(base + this_chunk, n);
+          }
         }
         const unsigned take = min(c_end - c_next, (unsigned)nidle);
         const unsigned rank = lanes_below(idle);
