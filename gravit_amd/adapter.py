@@ -356,9 +356,18 @@ class TransferFunction:
 
 class HipVolumeAdapter:
     """A volume brick on the device (gvt_hip_volume): the counterpart of the reference's volume adapters (OSPRayAdapter, PVolAdapter).
-    `brick` is a scenes.Brick (or a scenes.VolumeData: the whole grid as one brick); its data may also be a torch tensor on the GPU."""
+    `brick` is a scenes.Brick (or a scenes.VolumeData: the whole grid as one brick); its data may also be a torch tensor on the GPU.
+    native=False: the data is converted to float32, whatever it was.  native=True: a uint8, int16 or uint16 brick (numpy array or contiguous
+    GPU tensor) is stored at its own width (gvt_hip_volume_create_typed: a vertex's value is (float)v, so transfer functions and isovalues
+    are in the data's units) and answers bit for bit like the float32 brick of the converted data; any other dtype raises ValueError.
+    .voxel_type / .sample_bytes: what the library holds (capi.VOXEL_*, bytes per sample on the device)."""
 
-    def __init__(self, brick, sampling_rate=1.0, skip=True):
+    @staticmethod
+    def dtype_of(data):
+        """The dtype's name, for numpy arrays and torch tensors alike."""
+        return str(data.dtype).replace("torch.", "")
+
+    def __init__(self, brick, sampling_rate=1.0, skip=True, native=False):
         self.lib = capi.load()
         if hasattr(brick, "global_counts"):
             counts, offset, gcounts = brick.counts, brick.offset, brick.global_counts
@@ -367,17 +376,19 @@ class HipVolumeAdapter:
             offset, gcounts = np.zeros(3, np.int32), counts
         data = brick.data
         flags = 0 if skip else capi.VOLUME_NO_SKIP
-        if hasattr(data, "data_ptr") and data.is_cuda:  # a torch tensor on the device
-            if not data.is_contiguous() or str(data.dtype) != "torch.float32":
-                raise ValueError("HipVolumeAdapter: a device tensor must be contiguous float32")
+        if hasattr(data, "data_ptr") and not data.is_cuda:  # a torch tensor in host memory
+            data = data.numpy()
+        self.dtype_name = self.dtype_of(data) if native else "float32"
+        if native and self.dtype_name not in ("uint8", "int16", "uint16"):
+            raise ValueError("HipVolumeAdapter: native=True stores uint8, int16 and uint16 data, not %s (convert it, or pass native=False)" % self.dtype_name)
+        if hasattr(data, "data_ptr"):  # a torch tensor on the device
+            if not data.is_contiguous() or self.dtype_of(data) != self.dtype_name:
+                raise ValueError("HipVolumeAdapter: a device tensor must be contiguous %s" % ("float32" if not native else "uint8, int16 or uint16"))
             self._data = data
             src = C.c_void_p(data.data_ptr())
             flags |= capi.VOLUME_DEVICE
-        elif hasattr(data, "data_ptr"):  # a torch tensor in host memory
-            self._data = capi.f32(data.numpy())
-            src = capi.ptr(self._data)
         else:
-            self._data = capi.f32(data)
+            self._data = np.ascontiguousarray(data, dtype=np.dtype(self.dtype_name))  # (native byte order; float32 unless native)
             src = capi.ptr(self._data)
         self.counts = np.ascontiguousarray(counts, np.int32)
         self.offset = np.ascontiguousarray(offset, np.int32)
@@ -385,10 +396,14 @@ class HipVolumeAdapter:
         self.origin = capi.f32(brick.origin, 3)
         self.spacing = capi.f32(brick.spacing, 3)
         self.sampling_rate = float(sampling_rate)
-        self.h = C.c_void_p(self.lib.gvt_hip_volume_create(src, capi.ptr(self.counts), capi.ptr(self.origin), capi.ptr(self.spacing),
-                                                           capi.ptr(self.offset), capi.ptr(self.global_counts), self.sampling_rate, flags))
+        self.h = C.c_void_p(self.lib.gvt_hip_volume_create_typed(src, capi.VOXEL_TYPES[self.dtype_name], capi.ptr(self.counts), capi.ptr(self.origin),
+                                                                 capi.ptr(self.spacing), capi.ptr(self.offset), capi.ptr(self.global_counts),
+                                                                 self.sampling_rate, flags))
         if not self.h:
-            raise capi.GvtHipError("gvt_hip_volume_create: " + capi.last_error())
+            raise capi.GvtHipError("gvt_hip_volume_create_typed: " + capi.last_error())
+        vt, nb = C.c_int(-1), C.c_size_t(0)
+        capi.check(self.lib.gvt_hip_volume_get_voxel_type(self.h, C.byref(vt), C.byref(nb)), "gvt_hip_volume_get_voxel_type")
+        self.voxel_type, self.sample_bytes = vt.value, nb.value
 
     def close(self):
         if getattr(self, "h", None):
@@ -403,28 +418,30 @@ class HipVolumeAdapter:
 
     def update_samples(self, data):
         """gvt_hip_volume_update_samples: the next time step's samples for the same brick, in place (every pointer a tracer borrowed stays
-        valid; transfer function, surfaces and lights are kept).  data: a float32 numpy array of the brick's shape (nz, ny, nx), or a
-        contiguous float32 torch tensor of that shape on the GPU (no host round trip).  Returns the device time of the update in ms."""
+        valid; transfer function, surfaces and lights are kept).  data: a numpy array of the brick's shape (nz, ny, nx) and of the
+        adapter's dtype (float32; a native adapter's own), or a contiguous torch tensor of that shape and dtype on the GPU (no host round
+        trip); another dtype raises ValueError.  Returns the device time of the update in ms."""
         shape = tuple(int(c) for c in self.counts[::-1])
         if tuple(data.shape) != shape:
             raise ValueError("update_samples: data of shape %s, the brick has %s" % (tuple(data.shape), shape))
         ms = C.c_float(0.0)
+        want = getattr(self, "dtype_name", "float32")
         if hasattr(data, "data_ptr"):  # a torch tensor: the device path
             import torch
 
             if not data.is_cuda:
                 raise ValueError("update_samples: torch tensors must be on the GPU (pass numpy arrays for host data)")
-            if not data.is_contiguous() or data.dtype != torch.float32:
-                raise ValueError("update_samples: a device tensor must be contiguous float32")
+            if not data.is_contiguous() or HipVolumeAdapter.dtype_of(data) != want:
+                raise ValueError("update_samples: a device tensor must be contiguous %s" % want)
             torch.cuda.current_stream(data.device).synchronize()  # (the tensor is written on torch's stream, the update runs on the library's)
             src, flags = C.c_void_p(data.data_ptr()), 1
         else:
-            if np.asarray(data).dtype != np.float32:
-                raise ValueError("update_samples: data of dtype %s, the brick holds float32" % np.asarray(data).dtype)
-            data = np.ascontiguousarray(data)
+            if np.asarray(data).dtype.name != want:
+                raise ValueError("update_samples: data of dtype %s, the brick holds %s" % (np.asarray(data).dtype, want))
+            data = np.ascontiguousarray(data, dtype=np.dtype(want))
             src, flags = capi.ptr(data), 0
-        capi.check(self.lib.gvt_hip_volume_update_samples(self.h, src, C.c_size_t(int(np.prod(shape))), C.c_uint32(flags), C.byref(ms)),
-                   "gvt_hip_volume_update_samples")
+        capi.check(self.lib.gvt_hip_volume_update_samples_typed(self.h, src, self.voxel_type, C.c_size_t(int(np.prod(shape))), C.c_uint32(flags),
+                                                                C.byref(ms)), "gvt_hip_volume_update_samples_typed")
         self._data = data
         return float(ms.value)
 

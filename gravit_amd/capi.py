@@ -35,6 +35,7 @@ SYMBOLS = [
     "gvt_hip_shuffle_volume", "gvt_hip_volume_frame",
     "gvt_hip_volume_set_surfaces", "gvt_hip_volume_set_lights", "gvt_hip_volume_get_crossings",
     "gvt_hip_volume_update_samples",
+    "gvt_hip_volume_create_typed", "gvt_hip_volume_update_samples_typed", "gvt_hip_volume_get_voxel_type",
 ]
 
 
@@ -78,6 +79,8 @@ RAY_SIDES = 0x20  # the ray's t field holds the surface sides of the sample in t
 VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
+VOXEL_F32, VOXEL_U8, VOXEL_I16, VOXEL_U16 = 0, 1, 2, 3  # a volume's voxel type: the samples stay on the device at that width
+VOXEL_TYPES = {"float32": VOXEL_F32, "uint8": VOXEL_U8, "int16": VOXEL_I16, "uint16": VOXEL_U16}  # by numpy / torch dtype name
 
 FRAME_BSP, FRAME_NO_COMPOSITE, FRAME_FULL_REDUCE, FRAME_IMAGE = 1, 2, 4, 8
 
@@ -112,10 +115,13 @@ def load():
         lib.gvt_hip_volume_set_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]
         lib.gvt_hip_volume_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float]
         lib.gvt_hip_volume_update_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.gvt_hip_volume_create_typed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
+        lib.gvt_hip_volume_update_samples_typed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_void_p]
+        lib.gvt_hip_volume_get_voxel_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
         for f in ("gvt_hip_mesh_create", "gvt_hip_queue_create", "gvt_hip_top_create", "gvt_hip_fb_create", "gvt_hip_fb_device_ptr", "gvt_hip_ctx_create",
-                  "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_comm_create_local", "gvt_hip_tracer_create", "gvt_hip_volume_create"):
+                  "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_comm_create_local", "gvt_hip_tracer_create", "gvt_hip_volume_create", "gvt_hip_volume_create_typed"):
             getattr(lib, f).restype = C.c_void_p
         for f in ("gvt_hip_mesh_destroy", "gvt_hip_queue_destroy", "gvt_hip_top_destroy", "gvt_hip_fb_destroy", "gvt_hip_ctx_destroy", "gvt_hip_hub_abort",
                   "gvt_hip_hub_destroy", "gvt_hip_comm_destroy", "gvt_hip_tracer_destroy", "gvt_hip_volume_destroy"):

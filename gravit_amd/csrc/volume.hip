@@ -1,8 +1,10 @@
 // volume.hip -- volume domains: scalar bricks rendered with a transfer function.
 //   gvt_hip_volume_create / _set_transfer   Volume + TransferFunction (render/data/primitives/Volume.h, TransferFunction.cpp:40-72)
+//   gvt_hip_volume_create_typed             ... with 8- and 16-bit integer voxels kept at their own width (Volume::VoxelType, Volume.h:67-75):
+//                                           the kernels that read voxels are templates over the voxel's C type, a vertex's value is (float)v
 //   k_vol_ranges / k_vol_range_total        the macro cells' value ranges and the brick's, on the device (create and gvt_hip_volume_update_samples)
 //   k_volume_march / k_volume_march_surf    the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp): two
-//                                           entry points of one body, volume_march_body<SURF> (SURF: isovalues and slice planes)
+//                                           entry points of one body, volume_march_body<T, SURF> (SURF: isovalues and slice planes)
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
 //   gvt_hip_volume_frame                    Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks
@@ -28,7 +30,8 @@ struct gvt_hip_volume {
   bool has_tf = false;
   float tf_lo = 0.f, tf_hi = 1.f;
   float tf_a[256] = {};          // the table's corrected opacities (d_tf[i].w): what rebuild_tables reads after an update of the samples
-  float *d_vox = nullptr;
+  int vtype = GVT_HIP_VOXEL_F32;   // the voxel type, fixed at creation: d_vox holds the samples at that width and nothing wider exists
+  void *d_vox = nullptr;
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
   uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
   unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered
@@ -51,7 +54,7 @@ namespace {
 #define VOL_DEST_MAX 256
 
 struct VolDev {
-  const float *vox;
+  const void *vox; // samples of the brick's voxel type (vol_gather<T> reads them)
   const float4 *tf;
   const uint8_t *mc;
   int nx, ny, nz, ox, oy, oz, nbx, nby;
@@ -229,11 +232,15 @@ __device__ __forceinline__ int vol_jump_target(const VolDev &V, const float o[3]
 
 // the eight vertices of cell c and the trilinear value at the fractions f
 struct VolCorners { float v000, v100, v010, v110, v001, v101, v011, v111; };
+// (T: the voxel type.  A vertex's value is (float)v, exact for every 8- and 16-bit integer, so what follows the loads is the same whatever T)
+// (the compiler merges the two x-neighbours of a row into one load for every T -- 8, 2 or 4 bytes at T's alignment -- so the pair is not
+// written out here; no load is wider than the pair, which lies inside its row: profiles/volume_types.txt)
+template <typename T>
 __device__ __forceinline__ float vol_gather(const VolDev &V, const int c[3], const float f[3], VolCorners &G) {
   const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny;
-  const float *p = V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
-  G.v000 = p[0]; G.v100 = p[1]; G.v010 = p[sy]; G.v110 = p[sy + 1];
-  G.v001 = p[sz]; G.v101 = p[sz + 1]; G.v011 = p[sz + sy]; G.v111 = p[sz + sy + 1];
+  const T *p = (const T *)V.vox + (size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2];
+  G.v000 = (float)p[0]; G.v100 = (float)p[1]; G.v010 = (float)p[sy]; G.v110 = (float)p[sy + 1];
+  G.v001 = (float)p[sz]; G.v101 = (float)p[sz + 1]; G.v011 = (float)p[sz + sy]; G.v111 = (float)p[sz + sy + 1];
   const float c00 = lerp_(G.v000, G.v100, f[0]), c10 = lerp_(G.v010, G.v110, f[0]);
   const float c01 = lerp_(G.v001, G.v101, f[0]), c11 = lerp_(G.v011, G.v111, f[0]);
   const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
@@ -269,7 +276,7 @@ __device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, uns
 // One lane per ray, persistent waves with lane refill: a lane that finishes its ray takes the next one of the queue (one atomic per wave
 // and refill).  Rays are updated in place.  SURF (volumes that have surfaces): per sample the side mask, at a crossing the shaded
 // surfaces before the sample's own contribution.  prev < 0: no previous sample.
-template <bool SURF>
+template <typename T, bool SURF>
 __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::conditional_t<SURF, SurfDev, NoSurf> &S, RayPlanes q, unsigned n, const Mat4 &minv,
                                                   unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
   bool active = false, exhausted = false;
@@ -348,7 +355,7 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
         }
         n_gathered++;
         VolCorners G;
-        const float v = vol_gather(V, c, f, G);
+        const float v = vol_gather<T>(V, c, f, G);
         if constexpr (SURF) {
           unsigned sides = pl;
           for (int i = 0; i < S.n_iso; i++)
@@ -399,15 +406,17 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
   }
 }
 
-// The two entry points.  The plain one does not receive SurfDev: the table is about 600 bytes of kernel arguments, and its scalar
-// registers are full as it is.
+// The two entry points, per voxel type.  The plain one does not receive SurfDev: the table is about 600 bytes of kernel arguments, and its
+// scalar registers are full as it is.
+template <typename T>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                             unsigned long long *__restrict__ stats) {
-  volume_march_body<false>(V, NoSurf{}, q, n, minv, work, stats);
+  volume_march_body<T, false>(V, NoSurf{}, q, n, minv, work, stats);
 }
+template <typename T>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                  unsigned long long *__restrict__ stats) {
-  volume_march_body<true>(V, S, q, n, minv, work, stats);
+  volume_march_body<T, true>(V, S, q, n, minv, work, stats);
 }
 
 // ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
@@ -534,8 +543,11 @@ __device__ inline VRange vr_wave_all(VRange r) { // every lane: the wave's range
   return r;
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(VOL_BLOCK) void k_vol_ranges(const float *__restrict__ vox, unsigned nx, unsigned ny, unsigned nz, unsigned nbx, unsigned nby,
+// four consecutive vertices of a row as ONE load of 4 * sizeof(T) bytes (4, 8 or 16)
+template <typename T> struct alignas(4 * sizeof(T)) Vox4 { T v[4]; };
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(VOL_BLOCK) void k_vol_ranges(const T *__restrict__ vox, unsigned nx, unsigned ny, unsigned nz, unsigned nbx, unsigned nby,
                                                           unsigned runs, size_t n_work, float *__restrict__ bmin, float *__restrict__ bmax,
                                                           uint8_t *__restrict__ bnan) {
   constexpr int WAVES = VOL_BLOCK / 64;
@@ -550,19 +562,19 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_ranges(const float *__restric
     VRange first = vr_none(), all = vr_none(); // the lane's first vertex | all four
     if (x < nx)
       for (unsigned r = wave; r < rows; r += WAVES) {
-        const float *row = vox + ((size_t)(z0 + r / ry) * ny + (y0 + r % ry)) * nx;
-        if (VEC) { // nx % 4 == 0 and x % 4 == 0: x + 3 < nx
-          const float4 v = *reinterpret_cast<const float4 *>(row + x);
-          vr_add(first, v.x); vr_add(all, v.y); vr_add(all, v.z); vr_add(all, v.w);
+        const T *row = vox + ((size_t)(z0 + r / ry) * ny + (y0 + r % ry)) * nx;
+        if (VEC) { // nx % 4 == 0 and x % 4 == 0: x + 3 < nx, and row + x is a multiple of 4 vertices from the allocation's start
+          const Vox4<T> v = *reinterpret_cast<const Vox4<T> *>(row + x);
+          vr_add(first, (float)v.v[0]); vr_add(all, (float)v.v[1]); vr_add(all, (float)v.v[2]); vr_add(all, (float)v.v[3]);
         } else {
-          vr_add(first, row[x]);
-          for (unsigned i = 1; i < 4u && x + i < nx; i++) vr_add(all, row[x + i]);
+          vr_add(first, (float)row[x]);
+          for (unsigned i = 1; i < 4u && x + i < nx; i++) vr_add(all, (float)row[x + i]);
         }
       }
     vr_merge(all, first);
     VRange edge = vr_none(); // the boundary vertex behind the run's last cell: one row per thread (rows <= 81)
     const unsigned xe = x0 + 8u * VR_CELLS;
-    if (threadIdx.x < rows && xe < nx) vr_add(edge, vox[((size_t)(z0 + threadIdx.x / ry) * ny + (y0 + threadIdx.x % ry)) * nx + xe]);
+    if (threadIdx.x < rows && xe < nx) vr_add(edge, (float)vox[((size_t)(z0 + threadIdx.x / ry) * ny + (y0 + threadIdx.x % ry)) * nx + xe]);
     edge = vr_wave_all(edge);
     VRange cell = all; // even lanes: macro cell lane / 2 of the run, this wave's rows
     const VRange right = vr_shfl_down(all, 1), corner = vr_shfl_down(first, 2);
@@ -607,6 +619,21 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 }
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
+
+// The voxel types: bytes per sample (0: unknown type), and THE place a run-time type picks a kernel instantiation: f receives a value of
+// the voxel's C type.  volume_march and volume_ranges launch through it; nothing else reads d_vox.
+inline size_t voxel_bytes(int type) {
+  return type == GVT_HIP_VOXEL_F32 ? 4 : type == GVT_HIP_VOXEL_U8 ? 1 : (type == GVT_HIP_VOXEL_I16 || type == GVT_HIP_VOXEL_U16) ? 2 : 0;
+}
+template <typename Fn>
+inline void with_voxel_type(int type, Fn f) {
+  switch (type) {
+    case GVT_HIP_VOXEL_U8: f(uint8_t{}); break;
+    case GVT_HIP_VOXEL_I16: f(int16_t{}); break;
+    case GVT_HIP_VOXEL_U16: f(uint16_t{}); break;
+    default: f(float{}); break; // (create admits the four types only)
+  }
+}
 
 VolDev vol_dev(const gvt_hip_volume *Vh) {
   VolDev V;
@@ -684,10 +711,14 @@ int volume_ranges(gvt_hip_volume *V) {
   const unsigned blocks = (unsigned)std::min(n_work, (size_t)1 << 22);
   {
     ProfScope ps(KC_BUILD);
-    if (V->n[0] % 4 == 0)
-      k_vol_ranges<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(V->d_vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
-    else
-      k_vol_ranges<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(V->d_vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
+    with_voxel_type(V->vtype, [&](auto t) {
+      using T = decltype(t);
+      const T *vox = (const T *)V->d_vox;
+      if (V->n[0] % 4 == 0) // (every row then starts a multiple of 4 * sizeof(T) bytes from hipMalloc's pointer)
+        k_vol_ranges<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
+      else
+        k_vol_ranges<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
+    });
     k_vol_range_total<<<1, VR_TOTAL_BLOCK, 0, C.stream>>>(d_min, d_max, nbk, d_tot);
   }
   HIPCHK(hipGetLastError());
@@ -731,7 +762,8 @@ int rebuild_tables(gvt_hip_volume *V) {
   return upload_cells(V);
 }
 
-// the march of q's rays through brick Vh, in place, on the context's stream (no host wait)
+// the march of q's rays through brick Vh, in place, on the context's stream (no host wait): the one launch site of the march kernels
+// (gvt_hip_volume_trace and the frame loop come through here)
 int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
   if (!q->size) return 0;
   Ctx &C = gctx();
@@ -741,10 +773,13 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = minv[k];
   const unsigned blocks = std::min(blocks_of(q->size), (unsigned)(std::max(C.n_cu, 1) * 8));
-  if (Vh->n_iso + Vh->n_pl > 0)
-    k_volume_march_surf<<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
-  else
-    k_volume_march<<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+  with_voxel_type(Vh->vtype, [&](auto t) {
+    using T = decltype(t);
+    if (Vh->n_iso + Vh->n_pl > 0)
+      k_volume_march_surf<T><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+    else
+      k_volume_march<T><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+  });
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -837,9 +872,11 @@ bool resample(const float *map, int nrow, float out[256][W - 1]) {
 
 } // namespace
 
-extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int counts[3], const float origin[3], const float spacing[3], const int offset[3],
-                                                 const int global_counts[3], float sampling_rate, int flags) {
+extern "C" gvt_hip_volume *gvt_hip_volume_create_typed(const void *samples, int voxel_type, const int counts[3], const float origin[3], const float spacing[3],
+                                                       const int offset[3], const int global_counts[3], float sampling_rate, int flags) {
   if (ensure_init()) return nullptr;
+  const size_t vbytes = voxel_bytes(voxel_type);
+  if (!vbytes) { set_error("volume_create: unknown voxel type %d", voxel_type); return nullptr; }
   if (!samples || !counts || !origin || !spacing || !offset || !global_counts) { set_error("volume_create: null argument"); return nullptr; }
   if (flags & ~(GVT_HIP_VOLUME_DEVICE | GVT_HIP_VOLUME_NO_SKIP)) { set_error("volume_create: unknown flag bits %d", flags); return nullptr; }
   if (!(sampling_rate > 0.f) || !std::isfinite(sampling_rate)) { set_error("volume_create: sampling_rate %g is not positive", (double)sampling_rate); return nullptr; }
@@ -862,21 +899,36 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int
     V->hi[a] = origin[a] + (float)(offset[a] + counts[a] - 1) * spacing[a];
     V->nb[a] = (counts[a] - 1 + 7) / 8;
   }
+  V->vtype = voxel_type;
   V->rate = sampling_rate;
   V->dt = std::min(std::min(spacing[0], spacing[1]), spacing[2]) / sampling_rate;
   V->skip = (flags & GVT_HIP_VOLUME_NO_SKIP) ? 0 : 1;
   const size_t n_blocks = (size_t)V->nb[0] * V->nb[1] * V->nb[2];
-  bool ok = hipMalloc((void **)&V->d_vox, sizeof(float) * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
+  // d_vox is exactly the brick: total samples of the voxel type, no padding (no load of the march or the range kernels is wider than the
+  // vertices it asks for)
+  bool ok = hipMalloc(&V->d_vox, vbytes * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
             hipMalloc((void **)&V->d_stats, 3 * sizeof(unsigned long long)) == hipSuccess &&
             hipMemset(V->d_stats, 0, 3 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
             hipMalloc((void **)&V->d_cells, sizeof(uint32_t) * n_blocks) == hipSuccess;
   // the samples go to the device on the context's stream and the macro cells' ranges are computed there, behind the copy (volume_ranges
   // ends with a host wait): samples in device memory never touch the host
-  ok = ok && hipMemcpyAsync(V->d_vox, samples, sizeof(float) * total, (flags & GVT_HIP_VOLUME_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+  ok = ok && hipMemcpyAsync(V->d_vox, samples, vbytes * total, (flags & GVT_HIP_VOLUME_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                             gctx().stream) == hipSuccess;
   if (!ok) { set_error("volume_create: device allocation or copy failed"); gvt_hip_volume_destroy(V); return nullptr; }
   if (volume_ranges(V)) { gvt_hip_volume_destroy(V); return nullptr; }
   return V;
+}
+
+extern "C" gvt_hip_volume *gvt_hip_volume_create(const float *samples, const int counts[3], const float origin[3], const float spacing[3], const int offset[3],
+                                                 const int global_counts[3], float sampling_rate, int flags) {
+  return gvt_hip_volume_create_typed(samples, GVT_HIP_VOXEL_F32, counts, origin, spacing, offset, global_counts, sampling_rate, flags);
+}
+
+extern "C" int gvt_hip_volume_get_voxel_type(gvt_hip_volume *V, int *type_out, size_t *sample_bytes_out) {
+  if (!V) { set_error("volume_get_voxel_type: null"); return GVT_HIP_ERR_INVALID; }
+  if (type_out) *type_out = V->vtype;
+  if (sample_bytes_out) *sample_bytes_out = voxel_bytes(V->vtype);
+  return 0;
 }
 
 extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
@@ -916,9 +968,13 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   return rebuild_tables(V);
 }
 
-extern "C" int gvt_hip_volume_update_samples(gvt_hip_volume *V, const float *samples, size_t n_samples, uint32_t flags, float *ms_out) {
+extern "C" int gvt_hip_volume_update_samples_typed(gvt_hip_volume *V, const void *samples, int voxel_type, size_t n_samples, uint32_t flags, float *ms_out) {
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!V || !samples) { set_error("volume_update_samples: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (voxel_type != V->vtype) {
+    set_error("volume_update_samples: samples of voxel type %d, the volume holds type %d (fixed at creation)", voxel_type, V->vtype);
+    return GVT_HIP_ERR_INVALID;
+  }
   if (flags & ~GVT_HIP_UPDATE_DEVICE) { set_error("volume_update_samples: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
   const size_t total = (size_t)V->n[0] * V->n[1] * V->n[2];
   if (n_samples != total) {
@@ -927,7 +983,7 @@ extern "C" int gvt_hip_volume_update_samples(gvt_hip_volume *V, const float *sam
   }
   hipStream_t st = gctx().stream;
   HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the samples)
-  HIPCHK(hipMemcpyAsync(V->d_vox, samples, sizeof(float) * total, (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(V->d_vox, samples, voxel_bytes(V->vtype) * total, (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
   if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); set_error("volume_update_samples: hipEventCreate failed"); return GVT_HIP_ERR_DEVICE; }
@@ -943,6 +999,10 @@ extern "C" int gvt_hip_volume_update_samples(gvt_hip_volume *V, const float *sam
   hipEventDestroy(e0); hipEventDestroy(e1);
   if (!rc && ms_out) *ms_out = ms;
   return rc;
+}
+
+extern "C" int gvt_hip_volume_update_samples(gvt_hip_volume *V, const float *samples, size_t n_samples, uint32_t flags, float *ms_out) {
+  return gvt_hip_volume_update_samples_typed(V, samples, GVT_HIP_VOXEL_F32, n_samples, flags, ms_out);
 }
 
 extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isovalues, int n_iso, const float *slices, int n_slices, float opacity) {

@@ -527,7 +527,7 @@ def load_conf(path, geom_dirs=None, width=None, height=None):
 class VolumeData:
     """A scalar grid: data[z, y, x] (x fastest, the BOV order), the position of vertex 0 and the vertex spacing."""
 
-    data: np.ndarray  # (nz, ny, nx) f32
+    data: np.ndarray  # (nz, ny, nx); f32, or whatever the source held (uint8 / int16 / uint16 for HipVolumeAdapter(native=True))
     origin: np.ndarray = field(default_factory=lambda: np.zeros(3, F))
     spacing: np.ndarray = field(default_factory=lambda: np.ones(3, F))
 
@@ -542,7 +542,7 @@ class Brick:
     """One brick of a VolumeData (gvt_hip_volume_create's arguments): the vertices [offset, offset + counts) of the global grid, and the
     box they span in the volume's own space."""
 
-    data: np.ndarray  # (counts[2], counts[1], counts[0]) f32
+    data: np.ndarray  # (counts[2], counts[1], counts[0]), the volume's dtype
     offset: np.ndarray  # (3,) i32, x y z
     global_counts: np.ndarray
     origin: np.ndarray  # the GLOBAL grid's vertex 0
@@ -559,9 +559,10 @@ class Brick:
 _BOV_TYPES = {"FLOAT": "f4", "DOUBLE": "f8", "INT": "i4", "UCHAR": "u1", "BYTE": "u1", "SHORT": "i2", "CHAR": "i1"}
 
 
-def read_bov(path):
+def read_bov(path, native=False):
     """A Brick-Of-Values file (data/vol/*.bov): the header's keys and the data as f32 (z, y, x); FLOAT, INT and UCHAR (and their kin) are read,
-    non-float types converted on the host.  DATA_FILE is relative to the header."""
+    non-float types converted on the host.  DATA_FILE is relative to the header.  native=True keeps UCHAR / BYTE as uint8 and SHORT as int16
+    (in this machine's byte order, whatever the file's), for HipVolumeAdapter(native=True); every other format is f32 as before."""
     hdr = {}
     for line in open(path):
         if ":" in line:
@@ -580,7 +581,9 @@ def read_bov(path):
     origin = np.array([float(v) for v in hdr.get("BRICK_ORIGIN", "0 0 0").split()[:3]], F)
     size = np.array([float(v) for v in hdr.get("BRICK_SIZE", "%d %d %d" % (nx - 1, ny - 1, nz - 1)).split()[:3]], F)
     spacing = (size / np.array([nx - 1, ny - 1, nz - 1], F)).astype(F)
-    return hdr, VolumeData(np.ascontiguousarray(a.astype(F).reshape(nz, ny, nx)), origin, spacing)
+    keep = native and _BOV_TYPES[fmt] in ("u1", "i2")
+    a = a.astype(np.dtype(_BOV_TYPES[fmt]) if keep else F)  # (astype also brings a big-endian file into native order)
+    return hdr, VolumeData(np.ascontiguousarray(a.reshape(nz, ny, nx)), origin, spacing)
 
 
 def sphere_volume(n):

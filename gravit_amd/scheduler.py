@@ -559,9 +559,10 @@ class DomainTracer:
 
 class VolumeTracer:
     """Tracer<ImageScheduler> over the bricks of one volume instance (gvt_hip_volume_frame): bricks = scenes.split_volume(...) (or one
-    VolumeData), m = the instance's matrix (None: identity).  The world box of a brick is its box under m (scenes.instance_bbox)."""
+    VolumeData), m = the instance's matrix (None: identity).  The world box of a brick is its box under m (scenes.instance_bbox).
+    native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width)."""
 
-    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True):
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -571,7 +572,7 @@ class VolumeTracer:
         self.camera = camera
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
         self.minv = instance_matrices(self.m)[0]
-        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip) for b in bricks]
+        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native) for b in bricks]
         for a in self.adapters:
             a.set_transfer(tf)
         boxes = []
@@ -605,7 +606,8 @@ class VolumeTracer:
     @staticmethod
     def _same_bricking(adapters, bricks):
         """Helper of update(), not part of the tracer's surface (static so that the check runs without a device): the bricks of another time
-        step as a list, if they are the adapters' bricking (counts and offset per brick; a whole VolumeData has offset 0); ValueError otherwise."""
+        step as a list, if they are the adapters' bricking (counts and offset per brick; a whole VolumeData has offset 0) and, for adapters
+        that name one (dtype_name), of their dtype; ValueError otherwise."""
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         if len(bricks) != len(adapters):
             raise ValueError("VolumeTracer.update: %d bricks given, the tracer has %d" % (len(bricks), len(adapters)))
@@ -615,6 +617,9 @@ class VolumeTracer:
             if (counts != a.counts).any() or (offset != a.offset).any():
                 raise ValueError("VolumeTracer.update: brick %d has counts %s at offset %s, the tracer's has %s at %s (another bricking needs a new tracer)"
                                  % (i, counts.tolist(), offset.tolist(), a.counts.tolist(), a.offset.tolist()))
+            want, got = getattr(a, "dtype_name", None), str(b.data.dtype).replace("torch.", "")
+            if want is not None and got != want:
+                raise ValueError("VolumeTracer.update: brick %d has %s data, the tracer's holds %s (another voxel type needs a new tracer)" % (i, got, want))
         return bricks
 
     def update(self, bricks):

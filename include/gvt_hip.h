@@ -380,6 +380,31 @@ int gvt_hip_volume_get_info(gvt_hip_volume *, gvt_hip_volume_info *); /* synchro
  * ms_out (may be NULL): time on the context's stream from the end of the upload to the end of the update (ranges, their download, the
  * tables' rebuild on the host and their upload), as for gvt_hip_mesh_update_vertices. */
 int gvt_hip_volume_update_samples(gvt_hip_volume *, const float *samples, size_t n_samples, uint32_t flags, float *ms_out /* may be NULL */);
+/* Typed voxels (Volume::VoxelType, Volume.h:67-75; the BOV formats of VolApp.cpp:110-160).  A volume has a voxel type, fixed at creation,
+ * and its samples stay on the device at that width: a uint8 brick costs a quarter of the memory and of the upload of its float copy, a
+ * 16-bit one half.  No float copy of the grid exists on the device or on the host at any time, creation and update included.
+ * A vertex's value is (float)v, with no scale and no offset: the transfer function's value_lo / value_hi and the isovalues are given in
+ * those units (0..255 for uint8 data).  The conversion is exact for every 8- and 16-bit integer, and everything else of the volume
+ * contract (lattice, ownership, macro cells, skipping, surfaces, lights, flags) is unchanged, so a volume of type T made from samples s
+ * answers like the F32 volume made from (float)s with the same other arguments and the same set_transfer / set_surfaces / set_lights
+ * calls: every ray bit of gvt_hip_volume_trace, gvt_hip_shuffle_volume and gvt_hip_volume_frame, value_min / value_max, n_blocks /
+ * n_blocks_empty, the march counters and the crossings.  Integer voxels are never NaN or Inf: the not-finite flag of their macro cells
+ * is always clear.  DOUBLE and INT data are not exact in float32 and have no type here: the caller converts them, as before. */
+#define GVT_HIP_VOXEL_F32 0
+#define GVT_HIP_VOXEL_U8 1
+#define GVT_HIP_VOXEL_I16 2
+#define GVT_HIP_VOXEL_U16 3
+/* gvt_hip_volume_create with samples of voxel_type (counts[0] * counts[1] * counts[2] of them, host memory or, with GVT_HIP_VOLUME_DEVICE,
+ * device memory).  An unknown type: NULL and an error text.  gvt_hip_volume_create is this call with GVT_HIP_VOXEL_F32. */
+gvt_hip_volume *gvt_hip_volume_create_typed(const void *samples, int voxel_type, const int counts[3], const float origin[3], const float spacing[3],
+                                            const int offset[3], const int global_counts[3], float sampling_rate, int flags);
+/* gvt_hip_volume_update_samples for a volume of voxel_type, with everything that call promises.  voxel_type must be the volume's own:
+ * otherwise GVT_HIP_ERR_INVALID and nothing changes.  gvt_hip_volume_update_samples is this call with GVT_HIP_VOXEL_F32 (so on a volume of
+ * another type it is refused in the same way). */
+int gvt_hip_volume_update_samples_typed(gvt_hip_volume *, const void *samples, int voxel_type, size_t n_samples, uint32_t flags, float *ms_out /* may be NULL */);
+/* the volume's voxel type and the bytes one sample takes on the device (4, 1, 2, 2); either pointer may be NULL (gvt_hip_volume_info
+ * keeps its layout) */
+int gvt_hip_volume_get_voxel_type(gvt_hip_volume *, int *type_out, size_t *sample_bytes_out);
 /* TransferFunction: cmap rows (x r g b), omap rows (x a), each resampled to 256 entries as TransferFunction::DeviceCommit does
  * (TransferFunction.cpp:40-72); the opacity corrected on the host, a' = 1 - (1 - a)^(1 / sampling_rate) in double; the macro-cell table
  * rebuilt.  [value_lo, value_hi] maps onto the table.  At least 2 rows each, x not decreasing, value_lo < value_hi.

@@ -4,6 +4,9 @@ voxel bytes per sample by the algorithmic count (8 reads of 4 bytes per interpol
 Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (k_volume_march); counters in a run of their own.
 
   python tools/volume_bench.py [--sizes 256 512] [--steps 10] [--warmup 2] [--json OUT]
+  python tools/volume_bench.py --dtype u8    (or i16, u16; every mode) the noise grid quantised with np.rint to the type's range and stored at
+                                             that width (HipVolumeAdapter(native=True)), the transfer function's value range and the
+                                             isovalues scaled to match; f32 (the default): the float grid, as before
   python tools/volume_bench.py --update      time-varying volumes: per grid size, with the samples in host memory and in device memory, the
                                              wall time of destroy + create + set_transfer (what a new time step cost before
                                              gvt_hip_volume_update_samples) and of the in-place update, its ms_out and where that goes: the
@@ -32,14 +35,30 @@ F = np.float32
 CMAPS = os.path.join(ROOT, "tests", "golden", "colormaps")
 
 
-def transfer(kind):
+# --dtype: numpy dtype and the values the unit interval of noise_volume maps onto
+DTYPES = {"f32": (np.float32, 0.0, 1.0), "u8": (np.uint8, 0.0, 255.0), "i16": (np.int16, -30000.0, 30000.0), "u16": (np.uint16, 0.0, 65535.0)}
+
+
+def quantise(data, dtype):
+    """The [0, 1] grid in the voxel type's units: rounded to the nearest integer for the integer types, untouched for f32."""
+    np_t, lo, hi = DTYPES[dtype]
+    if dtype == "f32":
+        return data
+    out = np.empty(data.shape, np_t)
+    for z in range(data.shape[0]):  # slab by slab: no second float copy of a 512^3 grid
+        out[z] = np.rint(data[z] * F(hi - lo) + F(lo)).astype(np_t)
+    return out
+
+
+def transfer(kind, dtype="f32"):
     """"thin": opacity rising linearly to 0.03 -- rays cross the whole grid, every sample is interpolated; "spikes": GraviT's
-    fivespikes.omap -- opaque only around 0.9, most macro cells skipped."""
+    fivespikes.omap -- opaque only around 0.9, most macro cells skipped.  The value range is the dtype's image of [0, 1]."""
     rd = TransferFunction.read_map
     cmap = rd(os.path.join(CMAPS, "CoolWarm.cmap"), 4)
+    vr = DTYPES[dtype][1:]
     if kind == "thin":
-        return TransferFunction(cmap, np.array([[0.0, 0.0], [1.0, 0.03]], F), (0.0, 1.0))
-    return TransferFunction(cmap, rd(os.path.join(CMAPS, "fivespikes.omap"), 2), (0.0, 1.0))
+        return TransferFunction(cmap, np.array([[0.0, 0.0], [1.0, 0.03]], F), vr)
+    return TransferFunction(cmap, rd(os.path.join(CMAPS, "fivespikes.omap"), 2), vr)
 
 
 def camera():
@@ -49,14 +68,23 @@ def camera():
 SURFACE_MODES = {"plain": None, "never": (2.0, 3.0), "reached": (0.4, 0.6)}  # noise_volume lies in [0, 1]
 
 
-def run(n, split, steps, warmup, rate, kind, vol=None, surfaces=None):
+def noise(n, dtype):
+    vol = scenes.noise_volume(n, seed=1)
+    vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
+    vol.data = quantise(vol.data, dtype)
+    return vol
+
+
+def run(n, split, steps, warmup, rate, kind, vol=None, surfaces=None, dtype="f32"):
     if vol is None:
-        vol = scenes.noise_volume(n, seed=1)
-        vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
+        vol = noise(n, dtype)
+    _, lo, hi = DTYPES[dtype]
+    vbytes = np.dtype(DTYPES[dtype][0]).itemsize
     bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
     t0 = time.time()
-    tr = VolumeTracer(bricks, camera(), transfer(kind), sampling_rate=rate)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32")
     if surfaces:
+        surfaces = tuple(lo + v * (hi - lo) for v in surfaces)
         tr.set_surfaces(surfaces, (), 0.3).set_lights([((3.0, 4.0, 5.0), (1.0, 1.0, 1.0))])
     setup = time.time() - t0
     for _ in range(warmup):
@@ -75,13 +103,13 @@ def run(n, split, steps, warmup, rate, kind, vol=None, surfaces=None):
     ms = float(np.median(times))
     fb = tr.framebuffer(False)
     if surfaces:
-        return {"n": n, "tf": kind, "bricks": int(np.prod(split)), "isovalues": list(surfaces), "ms_median": round(ms, 3), "ms_min": round(min(times), 3),
+        return {"n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "isovalues": list(surfaces), "ms_median": round(ms, 3), "ms_min": round(min(times), 3),
                 "ms_max": round(max(times), 3), "samples_per_frame": int(marched), "samples_interpolated": int(gathered),
                 "crossings_per_frame": int((s1["crossings_rendered"] - s0["crossings_rendered"]) / steps), "lit_pixels": int((fb[..., 3] > 0).sum())}
-    return {"n": n, "tf": kind, "bricks": int(np.prod(split)), "split": list(split), "sampling_rate": rate, "ms_median": round(ms, 3),
+    return {"n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "split": list(split), "sampling_rate": rate, "ms_median": round(ms, 3),
             "ms_min": round(min(times), 3), "ms_max": round(max(times), 3), "adapter_calls": tr.calls,
             "samples_per_frame": int(marched), "samples_interpolated": int(gathered), "gsamples_per_s": round(marched / ms / 1e6, 3),
-            "voxel_bytes_per_sample": round(32.0 * gathered / max(marched, 1), 2), "voxel_bytes_per_frame_mb": round(32.0 * gathered / 1e6, 1),
+            "voxel_bytes_per_sample": round(8.0 * vbytes * gathered / max(marched, 1), 2), "voxel_bytes_per_frame_mb": round(8.0 * vbytes * gathered / 1e6, 1),
             "lit_pixels": int((fb[..., 3] > 0).sum()), "setup_s": round(setup, 1)}
 
 
@@ -89,25 +117,26 @@ def med(xs):
     return round(float(np.median(xs)), 3)
 
 
-def run_update(n, device, steps, warmup, recreate_only):
+def run_update(n, device, steps, warmup, recreate_only, dtype="f32"):
     """Two time steps of the n^3 noise grid, pushed alternately into one brick under the sparse table."""
     from gravit_amd.adapter import HipVolumeAdapter
 
-    data = [scenes.noise_volume(n, seed=s).data for s in (1, 2)]
+    data = [quantise(scenes.noise_volume(n, seed=s).data, dtype) for s in (1, 2)]
+    native, vbytes = dtype != "f32", np.dtype(DTYPES[dtype][0]).itemsize
     geo = (np.zeros(3, F), np.full(3, F(1.0 / (n - 1)), F))
     if device:
         import torch
 
         data = [torch.from_numpy(d).cuda() for d in data]
         torch.cuda.synchronize()
-    t = transfer("spikes")
-    out = {"n": n, "samples": "device" if device else "host", "grid_mb": round(4.0 * n ** 3 / 1e6, 1)}
+    t = transfer("spikes", dtype)
+    out = {"n": n, "dtype": dtype, "samples": "device" if device else "host", "grid_mb": round(vbytes * n ** 3 / 1e6, 1)}
     ad, wall = None, []
     for i in range(warmup + steps):  # what a new time step cost without the update: a new brick (a tracer around it not counted)
         t0 = time.perf_counter()
         if ad is not None:
             ad.close()
-        ad = HipVolumeAdapter(scenes.VolumeData(data[i % 2], *geo), 1.0)
+        ad = HipVolumeAdapter(scenes.VolumeData(data[i % 2], *geo), 1.0, native=native)
         ad.set_transfer(t)
         capi.synchronize()
         wall.append((time.perf_counter() - t0) * 1e3)
@@ -115,7 +144,7 @@ def run_update(n, device, steps, warmup, recreate_only):
     out["n_blocks"], out["n_blocks_empty"] = ad.info()["n_blocks"], ad.info()["n_blocks_empty"]
     if recreate_only:
         return out
-    bare = HipVolumeAdapter(scenes.VolumeData(data[0], *geo), 1.0)  # no transfer function: its update is ranges + download alone
+    bare = HipVolumeAdapter(scenes.VolumeData(data[0], *geo), 1.0, native=native)  # no transfer function: its update is ranges + download alone
     wall, ms, ms_bare, ms_kernel = [], [], [], []
     for i in range(warmup + steps):  # profiling off: the wall time and both ms_out
         t0 = time.perf_counter()
@@ -132,7 +161,7 @@ def run_update(n, device, steps, warmup, recreate_only):
     out.update({"update_wall_ms": med(wall[w:]), "update_wall_min_ms": round(min(wall[w:]), 3), "update_ms_out": med(ms[w:]),
                 "range_kernels_ms": med(ms_kernel[w:]), "ranges_and_download_ms": med(ms_bare[w:]),
                 "table_rebuild_ms": med(np.array(ms[w:]) - np.array(ms_bare[w:])),
-                "range_kernel_gbs_of_grid": round(4.0 * n ** 3 / 1e6 / max(float(np.median(ms_kernel[w:])), 1e-9), 1),
+                "range_kernel_gbs_of_grid": round(vbytes * n ** 3 / 1e6 / max(float(np.median(ms_kernel[w:])), 1e-9), 1),
                 "recreate_over_update": round(out["recreate_wall_ms"] / max(float(np.median(wall[w:])), 1e-9), 1)})
     return out
 
@@ -148,6 +177,7 @@ def main():
     ap.add_argument("--surfaces", action="store_true")
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
+    ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     a = ap.parse_args()
     if a.update:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
@@ -156,26 +186,26 @@ def main():
     if a.update:
         for n in a.sizes:
             for device in (False, True):
-                r = run_update(n, device, a.steps, a.warmup, a.recreate_only)
+                r = run_update(n, device, a.steps, a.warmup, a.recreate_only, a.dtype)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
         a.sizes = []
     for n in a.sizes if a.surfaces else ():
-        vol = scenes.noise_volume(n, seed=1)
-        vol.spacing = np.full(3, F(1.0 / (n - 1)), F)
+        vol = noise(n, a.dtype)
         for split in ((1, 1, 1), (2, 2, 2)):
             base = None
             for mode, iso in SURFACE_MODES.items():
-                r = run(n, split, a.steps, a.warmup, a.rate, "thin", vol, iso)
+                r = run(n, split, a.steps, a.warmup, a.rate, "thin", vol, iso, a.dtype)
                 r["mode"] = mode
                 base = r["ms_median"] if mode == "plain" else base
                 r["vs_plain"] = round(r["ms_median"] / base, 3)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
     for n in () if a.surfaces else a.sizes:
+        vol = noise(n, a.dtype)  # (once per size: the 512^3 grid takes longer to make than to render)
         for kind in a.tf:
             for split in ((1, 1, 1), (2, 2, 2)):
-                r = run(n, split, a.steps, a.warmup, a.rate, kind)
+                r = run(n, split, a.steps, a.warmup, a.rate, kind, vol, dtype=a.dtype)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
     if a.json:
