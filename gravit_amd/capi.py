@@ -58,7 +58,7 @@ class FrameStats(C.Structure):
     _fields_ = [("rounds", C.c_uint64), ("chains", C.c_uint64), ("host_syncs", C.c_uint64), ("rays_sent", C.c_uint64),
                 ("rays_closest", C.c_uint64), ("rays_any", C.c_uint64), ("packets_bailed", C.c_uint64), ("bytes_sent", C.c_uint64),
                 ("ms_chain", C.c_double), ("ms_announce", C.c_double), ("ms_payload", C.c_double), ("ms_composite", C.c_double), ("ms_host_wait", C.c_double),
-                ("exchanges", C.c_uint64), ("rays_inline", C.c_uint64)]
+                ("exchanges", C.c_uint64), ("rays_inline", C.c_uint64), ("early_deposit_launches", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

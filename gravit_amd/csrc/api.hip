@@ -238,7 +238,7 @@ extern "C" int gvt_hip_stats_reset(void) {
 namespace {
 struct KnobDef { const char *name; int Knobs::*field; int lo, hi; bool shipped; };
 const KnobDef g_knobs[] = {
-  // shipped (28)
+  // shipped (29)
   { "skip_known", &Knobs::skip_known, 0, 1, true },           { "frame_timing", &Knobs::frame_timing, 0, 1, true },
   { "term_sink", &Knobs::term_sink, 0, 1, true },
   { "sort_rays", &Knobs::sort_rays, 0, 1, true },             { "leaf_max", &Knobs::leaf_max, 1, 4, true },
@@ -252,7 +252,7 @@ const KnobDef g_knobs[] = {
   { "packet", &Knobs::packet, 0, 2, true },                   { "packet_sah_max", &Knobs::packet_sah_max, 0, 1 << 30, true },
   { "packet_min_rays", &Knobs::packet_min_rays, 0, 1 << 30, true },
   { "shadow_order", &Knobs::shadow_order, 0, 1, true },       { "shadow_order_min_rays", &Knobs::shadow_order_min_rays, 0, 1 << 30, true },
-  { "xcd_stripes", &Knobs::xcd_stripes, 0, 1, true },
+  { "xcd_stripes", &Knobs::xcd_stripes, 0, 1, true },           { "early_deposit", &Knobs::early_deposit, 0, 1, true },
 
   { "inline_kb", &Knobs::inline_kb, 0, 1024, true },          { "comm_cus", &Knobs::comm_cus, 0, 128, true },
   { "comm_stream", &Knobs::comm_stream, 0, 1, true },         { "spec_ticks", &Knobs::spec_ticks, 0, 1, true },

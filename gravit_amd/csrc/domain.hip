@@ -876,6 +876,7 @@ struct gvt_hip_tracer {
   int fin_choice = -1;         // -1: probing (frames take the routes in turn), else the route
   int fin_limit = 0;           // the frame in progress: rounds of at most this many rays go through k_finish
   int hop_now = 0;             // the frame in progress: hops (TraceParams::hop)
+  bool fb_fresh = false;       // the frame in progress: the framebuffer is as the frame's own clear left it -- no chain has run since (TraceParams::one_writer)
   unsigned cam_row_rays = 0;   // the frame in progress: list positions per row of tiles of the camera list its filter enumerated (0: unknown / not in tiles)
   bool fin_eligible = false;   // the frame in progress had a round small enough for k_finish
   unsigned fin_probe = 0;
@@ -1153,6 +1154,10 @@ int local_chain(gvt_hip_tracer *R, const std::vector<size_t> *extra_in, uint64_t
   // gvt_hip_tracer_frame; knob hop_local; not with the known-miss shortcut, whose list is kept by the shuffle kernels)
   P.hop = R->hop_now == 1 ? 1 : R->hop_now == 2 ? 2 : 0;
   P.hop_owner = R->world > 1 ? R->d_owner : nullptr; P.hop_rank = R->rank;
+  // the frame's first chain, over the camera's own rays at one sample per pixel: no pixel has been written since the frame's clear and none gets two deposits from this chain's
+  // first pass (what the single-mesh chain's early deposits rest on, trace.hip single_pass)
+  P.one_writer = (fresh_from_camera && R->fb_fresh && R->cam.samples == 1) ? 1 : 0;
+  R->fb_fresh = false;
   WaveSet W{ R->d_segs, R->d_insts, n_seg, (int)nI };
   if (C.finish_rays > 0 && N <= (size_t)C.finish_rays && P.sink.fb && !count_on_device && !exact) R->fin_eligible = true;
   if (R->fin_limit > 0 && N <= (size_t)R->fin_limit && P.sink.fb && !count_on_device && !exact) {
@@ -1478,6 +1483,8 @@ extern "C" int gvt_hip_tracer_frame(gvt_hip_tracer *R, int flags, gvt_hip_frame_
   R->sizes_exact = true; R->spec_enqueued_last = false;
   R->cam_row_rays = 0u;
   bool first_on_device = false; // the queues hold the camera's rays, their sizes are on the device only (R->present: bounds)
+  R->fb_fresh = true; // (cleared below, or by the lean camera filter in front of the first chain)
+  const uint64_t early0 = C.early_deposit_launches;
   if (!lean) {
     if ((rc = gvt_hip_fb_clear(R->fb))) return rc;
     k_zero_totals<<<(unsigned)std::max<size_t>(1, (nI + 255) / 256), 256, 0, st>>>(C.d_counters, R->d_overflow, R->fb->w, R->fb->h, R->d_count_ptr, (int)nI); // + every queue.clear()
@@ -1839,6 +1846,7 @@ extern "C" int gvt_hip_tracer_frame(gvt_hip_tracer *R, int flags, gvt_hip_frame_
     }
   }
   R->frame_no++;
+  S.early_deposit_launches = C.early_deposit_launches - early0;
   if (out) *out = S;
   return 0;
 }

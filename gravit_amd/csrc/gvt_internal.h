@@ -72,6 +72,8 @@ struct Knobs {
   int xcd_stripes = 1;   // the single-mesh k_trace launch over the camera's tile-ordered list (lists without film geometry stay front to back): every XCD's waves draw from a stripe of the ray list of their own -- an eighth of every list row, all stripes going down
                          // the film together (xcd_stripes.h) --, so that an XCD's L2 holds its columns of the band in flight instead of the whole band; they take from the other
                          // stripes once their own is used up.  0: the list front to back from one counter.  The order of work only: results never depend on it
+  int early_deposit = 1; // the one-instance frame with one light and one sample per pixel (trace.hip single_pass): k_shade stores a shadow ray's deposit to its pixel itself and the
+                         // any-hit launch only takes it back for an occluded ray -- no survivor list, no float atomics.  0: deposits by the any-hit launch.  Results never depend on it
   int shadow_order_min_rays = 262144; // ... in launches of at least this many rays (a small launch has no drain worth ordering)
   int packet_min_rays = 524288; // ... and only in launches of at least this many rays (bound): a small launch is a few thousand packets, each a long serial walk
   int packet_sah_max = 128; // meshes created afterwards: packet-friendly when sum(area(inner node)) / area(root) is at most this (lbvh.hip k_sah_sum)
@@ -134,6 +136,7 @@ struct Ctx : Knobs {
   gvt_hip_stats stats{};
   // traversal launch geometry + per-thread stack spill area
   int n_cu = 256;        // compute units the context's launches are sized for (all of the device's, minus cu_reserved)
+  uint64_t early_deposit_launches = 0; // any-hit launches of this context that took the early-deposit path (gvt_hip_frame_stats::early_deposit_launches)
   bool shadow_order_denied = false; // the class-ordered shadow list (8 x the plain one) could not be allocated once: this context lists shadow rays in arrival order
   int cu_reserved = 0;   // compute units masked away from the context's stream for a communicator's own stream (knob comm_cus)
   int trav_blocks = 0;
@@ -273,6 +276,9 @@ struct TraceParams {
   int hop;              // 0 no, 2 yes, 1 = the closest-hit launch only, and only while it still has rays to hand out (MultiSrc::hop_early)
   const int *hop_owner; // instance -> rank on the device (null: all local)
   int hop_rank;
+  // the frame loop's own knowledge (domain.hip): these rays are the camera's, ONE per pixel, and the loop cleared the framebuffer at the start of this frame -- a pixel
+  // then receives at most one deposit, into a zero.  0 wherever that is not known (the adapter call, later chains of a frame)
+  int one_writer;
 };
 
 // what k_shade needs of a mesh (shading attributes in their reference shapes)

@@ -186,7 +186,25 @@ struct ShadeArgs {
   unsigned *cls_cnt;       // SHADOW_CLASSES counters (null: off); shadow_count still receives the total
   unsigned cls_stride;
   int cls_lo, cls_shift;   // class = (steps - cls_lo) >> cls_shift, clamped
+  int early_deposit;       // k_shade<false, LEAN> only (the host's conditions, trace.hip single_pass): one light, one camera ray per pixel, the framebuffer cleared by this
+                           // frame -- store_shadow_early below instead of store_ray
 };
+
+// The early deposit of a frame in which every pixel has ONE writer: the any-hit launch would only decide WHETHER shadow ray s deposits c * w in its pixel (and for nearly every
+// ray it does), so the value is stored now -- deposit_shadow's predicate, and `0.0f + x`, which is what its atomic makes of a cleared pixel, bit for bit (x = -0 included) --
+// and k_trace<true, true, 2> stores zeros again where the ray turns out occluded.  The ray itself is THIN: origin and direction, which the traversal reads, and one word in
+// the third plane's place -- the pixel, or ~0 where the predicate failed: such a ray is traced and counted like the others and touches no pixel.  (A 4-byte word and not the
+// fourth plane as it was: a quarter of the bytes to write here, and the kernel behind reads one word per OCCLUDED ray and needs no n_pix, type or colour test of its own.)
+__device__ __forceinline__ void store_shadow_early(const ShadeArgs &A, unsigned slot, const RayRec &s) {
+  A.shadow.p0[slot] = make_float4(s.o.x, s.o.y, s.o.z, s.t_min);
+  A.shadow.p1[slot] = make_float4(s.d.x, s.d.y, s.d.z, s.t_max);
+  const bool dep = len3(s.c) > 0.f && (unsigned)s.id < A.sink.n_pix; // (s.type is 1)
+  if (dep) {
+    const V3 cw = scl3(s.c, s.w);
+    ((float4 *)A.sink.fb)[(unsigned)s.id] = make_float4(0.0f + cw.x, 0.0f + cw.y, 0.0f + cw.z, 1.0f);
+  }
+  ((uint32_t *)A.shadow.p2)[slot] = dep ? (uint32_t)s.id : 0xffffffffu;
+}
 
 // class of a tile whose longest primary took `steps` node steps (4-wide nodes; the benchmark soup: mean 26, parked at 96)
 __device__ __forceinline__ unsigned shadow_class(int steps, int lo, int shift) {
@@ -337,10 +355,18 @@ __global__ __launch_bounds__(SHADE_BLOCK, 4) void k_shade(ShadeArgs A, MeshView 
       // (the list's length is the sum of the class counts: the any-hit launch adds them up and leaves the total in *shadow_count for what reads it later)
       if (threadIdx.x < SHADOW_CLASSES && sh_cls[threadIdx.x]) sh_cls[SHADOW_CLASSES + threadIdx.x] = atomicAdd(&A.cls_cnt[threadIdx.x], sh_cls[threadIdx.x]);
       __syncthreads();
-      if (emit) store_ray(A.shadow, cls * A.cls_stride + sh_cls[SHADOW_CLASSES + cls] + woff + lanes_below(mask), s);
+      if (emit) {
+        const unsigned slot = cls * A.cls_stride + sh_cls[SHADOW_CLASSES + cls] + woff + lanes_below(mask);
+        if (LEAN && A.early_deposit) store_shadow_early(A, slot, s);
+        else store_ray(A.shadow, slot, s);
+      }
     } else {
       const unsigned slot = block_alloc(A.shadow_count, emit, &sh_alloc[2 * (2 + li)]);
-      if (emit) { store_ray(A.shadow, slot, s); if (MULTI) A.shadow_inst[slot] = inst; }
+      if (emit) {
+        if (LEAN && !MULTI && A.early_deposit) store_shadow_early(A, slot, s);
+        else store_ray(A.shadow, slot, s);
+        if (MULTI) A.shadow_inst[slot] = inst;
+      }
     }
   }
   if (!LEAN && shaded) { // :584-602

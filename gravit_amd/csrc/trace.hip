@@ -287,11 +287,21 @@ static void closest_step(StepMode mode, const TraceSrc &S, const unsigned *idx, 
 
 // The any-hit step over the shadow list S.q: un-occluded rays are appended to `out` or end in S.sink.  BY_LANES: idx / n / n_dev as k_trace takes them (n = 0: the
 // count is *n_dev), the grid sized for grid_rays;  BY_WAVES: the list's first CW_SHADOW rays.  (Any-hit packets are the single-mesh chain's own: any_packets.)
+// early (single-mesh chains, BY_LANES; the conditions: single_pass): k_shade has stored every ray's deposit already and S.q holds thin rays (shade.inc store_shadow_early) --
+// k_trace's MODE 2, which only takes an occluded ray's deposit back; `out` is not written.
 template <bool MULTI>
-static void any_step(StepMode mode, const TraceSrc &S, const unsigned *idx, size_t grid_rays, unsigned n, const unsigned *n_dev, RayPlanes out, unsigned *out_count) {
+static void any_step(StepMode mode, const TraceSrc &S, const unsigned *idx, size_t grid_rays, unsigned n, const unsigned *n_dev, RayPlanes out, unsigned *out_count, bool early = false) {
   Ctx &C = gctx();
   unsigned *c = C.d_counters;
   ProfScope ps(KC_ANY);
+  if constexpr (!MULTI) {
+    if (early && mode == BY_LANES) {
+      launch_trace<true, true, 2, false>(trav_grid2(grid_rays), C.stream, S.q, idx, n, S.minv, S.T, GVT_RAY_EPSILON, nullptr, nullptr, out, out_count, c + CW_WORK, C.d_spill,
+                                         C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{}, S.MS, stripe_arg(S.row));
+      C.early_deposit_launches++;
+      return;
+    }
+  }
   if (mode == BY_WAVES) k_wave_any<MULTI><<<wave_grid(grid_rays), 256, 0, C.stream>>>(S.q, c + CW_SHADOW, S.minv, S.T, GVT_RAY_EPSILON, out, out_count, c + CW_WORK, S.sink, S.MS);
   else launch_trace<true, true, 1, MULTI>(trav_grid2(grid_rays), C.stream, S.q, idx, n, S.minv, S.T, GVT_RAY_EPSILON, nullptr, nullptr, out, out_count, c + CW_WORK, C.d_spill,
                                           C.refill_min, C.inner_min, n_dev, C.share, (unsigned)C.share_min_rays, S.sink, LongQ{}, S.MS, MULTI ? XCD_STRIPES_OFF : stripe_arg(S.row));
@@ -568,13 +578,18 @@ static int single_pass(const Chain &K, Pass p, const WaveSingle &W1, size_t cls_
   A.steps = K.B.steps; A.cls_cnt = by_class ? c + CW_SHADOW_CLS : nullptr; A.cls_stride = (unsigned)cls_stride; A.cls_lo = C.shadow_cls_lo; A.cls_shift = C.shadow_cls_shift;
   // the simple frame (k_shade's LEAN instantiation): camera rays of the scene's only instance, depth 1, no area light, a LAMBERT mesh material
   const bool lean_shade = W1.coherent && p.pass == 0 && K.passes == 1 && K.P.sink.fb && K.P.sink.top.n_inst == 1 && nL >= 1 && plain_lambert(M) && no_area_light(K.lights_host, nL);
+  // ... and of it the frame in which every pixel has one writer -- one light, and the frame loop's word that these are the camera's rays, one per pixel, over a
+  // framebuffer it has just cleared (TraceParams::one_writer) --, its shadow rays a lane per ray: the deposit is stored by k_shade and taken back by the any-hit launch
+  // where the ray is occluded (knob early_deposit; shade.inc store_shadow_early, k_trace's MODE 2)
+  const bool early_deposit = lean_shade && nL == 1 && K.P.one_writer && !small1 && !pkt_any && C.early_deposit;
+  A.early_deposit = early_deposit ? 1 : 0;
   shade_step<false>(A, mesh_view(M), lean_shade);
   if (!nL) return 0;
   TraceSrc SA = S;
   SA.q = K.B.shadow; SA.sink = A.sink; SA.row = 0u;
   if (pkt_any) return any_packets(K, SA);
   if (by_class) { SA.MS.cls_cnt = c + CW_SHADOW_CLS; SA.MS.cls_stride = (unsigned)cls_stride; SA.MS.cls_total = c + CW_SHADOW; }
-  any_step<false>(small1 ? BY_WAVES : BY_LANES, SA, nullptr, K.B.shadow_cap, 0u, by_class ? nullptr : c + CW_SHADOW, K.outp, K.out->d_count);
+  any_step<false>(small1 ? BY_WAVES : BY_LANES, SA, nullptr, K.B.shadow_cap, 0u, by_class ? nullptr : c + CW_SHADOW, K.outp, K.out->d_count, early_deposit);
   return 0;
 }
 

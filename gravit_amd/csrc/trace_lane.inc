@@ -448,7 +448,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
               O = xfm_point(minv, O);
               D = mk3((m[0] * D.x + m[4] * D.y) + (m[8] * D.z + z12), (m[1] * D.x + m[5] * D.y) + (m[9] * D.z + z13), (m[2] * D.x + m[6] * D.y) + (m[10] * D.z + z14));
             }
-            if (ANY && MODE == 1) j = i; // a survivor is copied out of q by its slot there (an index list or the class regions: not its number in the launch)
+            if (ANY && MODE >= 1) j = i; // a survivor is copied out of q by its slot there (an index list or the class regions: not its number in the launch); MODE 2 reads an occluded ray's pixel there
           }
           if (start) {
             const float dx = fabsf(D.x) < 1e-30f ? copysignf(1e-30f, D.x) : D.x;
@@ -510,6 +510,9 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
         idle_m &= idle_m - 1;
         don_m &= don_m - 1; // one entry per donor and round: spread the helpers over the busy lanes
         sharing = true;
+#if GVT_STAMP
+        if (lane_id() == 0) atomicAdd(&g_stamp[23], 1ull); // hand-offs: subtrees given to a helper lane
+#endif
       }
     }
 #if GVT_STAMP == 1
@@ -714,6 +717,16 @@ __global__ __launch_bounds__(TRAV_BLOCK, (ANY ? KT_BLOCKS_ANY : KT_BLOCKS_CLOSES
           }
           LQ.recs[slot] = R;
         }
+      }
+    }
+    if (ANY && MODE == 2) {
+      // early deposits (k_shade, shade.inc): every ray's colour already lies in its pixel, stored there before this launch began -- one writer per pixel, the host's
+      // condition.  A survivor has nothing left to do: no list, no flush, no atomics.  An occluded ray takes its deposit back: the pixel is what the frame's clear left.
+      // Its word of the thin ray's third plane is the pixel, or ~0 where the shading kernel's predicate (deposit_shadow's own) failed and nothing was stored.
+      // (lanes that shared a ray: the survivors of the merge above carry the group's occlusion; a second store of the same zeros would change nothing)
+      if (fin && bp >= 0) {
+        const unsigned px = ((const unsigned *)q.p2)[j];
+        if (px != 0xffffffffu) ((float4 *)sink.fb)[px] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
     if (fin) {

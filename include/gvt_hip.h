@@ -319,6 +319,8 @@ typedef struct gvt_hip_frame_stats {
   uint64_t exchanges;    /* transport groups (ncclGroupStart .. End) this rank issued in the frame, composite included: one per tick when every pair's
                             payload rode inside the announce ("inline_kb"), two where a payload exchange followed */
   uint64_t rays_inline;  /* of rays_sent: rays that travelled inside an announce */
+  uint64_t early_deposit_launches; /* any-hit launches of the frame whose deposits were stored at shading time ("early_deposit"); added at the end of revision 6's record:
+                                    * gvt_hip_tracer_frame writes the whole record, so a caller compiled against the shorter one must be rebuilt against this header */
 } gvt_hip_frame_stats;
 /* One frame: clearBuffer, generateRays + FilterRaysLocally / shuffleDropRays, rounds until every queue of every rank is empty, then
  * (Domain) the composite: the sum of the ranks' float framebuffers on rank 0 (IceTComposite.cpp:84-101).  Collective under a comm. */
@@ -541,6 +543,10 @@ int gvt_hip_math_probe(int kind, const float *in, size_t n, float *out);
  *                "shadow_order" 1 (default): a single-mesh round with one light lists its shadow rays by how many node steps the primaries of their 64-ray tile
  *                               took, the longest first (a shadow ray's step count follows its primary's), so that the any-hit launch's drain is left to
  *                               short rays -- in launches of at least "shadow_order_min_rays" rays; 0: in arrival order.  Results do not depend on it
+ *                "early_deposit" 1 (default): the one-instance frame of gvt_hip_tracer_frame with one light, one sample per pixel, depth 1 and a plain LAMBERT mesh stores a shadow
+ *                               ray's deposit to its pixel at shading time (one writer per pixel, into the frame's own clear) and the any-hit launch only takes it back where
+ *                               the ray is occluded -- no survivor list, no float atomics; 0: deposits by the any-hit launch.  Results do not depend on it;
+ *                               gvt_hip_frame_stats::early_deposit_launches counts the launches that took the path
  *   build time   "leaf_max"     triangles per leaf of meshes created afterwards (1..4, default 2)
  *                "packet_sah_max"  meshes created afterwards are packet-friendly when gvt_hip_mesh_info::sah_inner is at most this (default 128)
  *   budgets      "long_steps" / "long_min_rays" / "long_auto"  closest hit: node steps after which a ray is parked for a whole wave (0: never), launches it
