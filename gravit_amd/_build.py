@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libgvt_hip.so")
 LIB_EXP = os.path.join(HERE, "libgvt_hip_exp.so")
-SOURCES = ["api.hip", "lbvh.hip", "trace.hip", "sched.hip", "domain.hip", "volume.hip"]
+SOURCES = ["api.hip", "lbvh.hip", "trace.hip", "sched.hip", "domain.hip", "volume.hip", "depth.hip"]
 
 
 def _headers():

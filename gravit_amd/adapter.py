@@ -315,10 +315,84 @@ class FrameBuffer:
         capi.check(self.lib.gvt_hip_fb_download(self.h, capi.ptr(out), C.c_int(int(clamp))), "gvt_hip_fb_download")
         return out
 
+    def composite_over(self, back, depth=None):
+        """gvt_hip_fb_composite_over: this (a volume frame) over `back` (a mesh frame), in place; coverage from the DepthPlane `depth`, or
+        from back's alpha without one."""
+        capi.check(self.lib.gvt_hip_fb_composite_over(self.h, back.h, depth.h if depth is not None else None), "gvt_hip_fb_composite_over")
+        return self
+
     def ppm_bytes(self):
         out = np.zeros((self.hgt, self.w, 3), np.uint8)
         capi.check(self.lib.gvt_hip_fb_write_ppm_bytes(self.h, capi.ptr(out)), "gvt_hip_fb_write_ppm_bytes")
         return out
+
+
+def camera_pod(cam):
+    """The gvt_hip_camera record of a scenes.Camera."""
+    return capi.CameraPod((C.c_float * 3)(*cam.eye), (C.c_float * 3)(*cam.focus), (C.c_float * 3)(*cam.up), cam.fov, cam.width, cam.height,
+                          cam.samples, cam.depth, cam.jitter)
+
+
+class DepthPlane:
+    """gvt_hip_depth: W*H floats on the device, t along every pixel's camera ray (+Inf: nothing there) -- what the mesh side hands to a
+    clipped volume frame (VolumeTracer.frame(depth=...)) and to FrameBuffer.composite_over."""
+
+    def __init__(self, width, height):
+        self.lib = capi.load()
+        self.w, self.hgt = int(width), int(height)
+        self._backend = None
+        self.h = C.c_void_p(self.lib.gvt_hip_depth_create(self.w, self.hgt))
+        if not self.h:
+            raise capi.GvtHipError("gvt_hip_depth_create: " + capi.last_error())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gvt_hip_depth_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def clear(self):
+        capi.check(self.lib.gvt_hip_depth_clear(self.h), "gvt_hip_depth_clear")
+        return self
+
+    def upload(self, t):
+        """t: (H, W) float32 -- a numpy array, or a contiguous torch tensor on the GPU (no host round trip)."""
+        if hasattr(t, "data_ptr") and t.is_cuda:
+            import torch
+
+            if not t.is_contiguous() or t.dtype != torch.float32 or t.numel() != self.w * self.hgt:
+                raise ValueError("DepthPlane.upload: a device tensor must be contiguous float32 of %d x %d" % (self.hgt, self.w))
+            torch.cuda.current_stream(t.device).synchronize()  # (the tensor is written on torch's stream, the copy runs on the library's)
+            capi.check(self.lib.gvt_hip_depth_upload(self.h, C.c_void_p(t.data_ptr()), 1), "gvt_hip_depth_upload")
+            return self
+        t = capi.f32(t.numpy() if hasattr(t, "data_ptr") else t)
+        if t.size != self.w * self.hgt:
+            raise ValueError("DepthPlane.upload: %d values for a %d x %d plane" % (t.size, self.hgt, self.w))
+        capi.check(self.lib.gvt_hip_depth_upload(self.h, capi.ptr(t), 0), "gvt_hip_depth_upload")
+        return self
+
+    def download(self):
+        out = np.zeros((self.hgt, self.w), np.float32)
+        capi.check(self.lib.gvt_hip_depth_download(self.h, capi.ptr(out)), "gvt_hip_depth_download")
+        return out
+
+    def render(self, scene_or_backend, cam=None):
+        """gvt_hip_depth_render: the nearest hit of every camera ray over all instances.  A scheduler.HipBackend brings its scene and its
+        mesh adapters; for a scenes.Scene the adapters are made here and kept for the next call with the same scene.  cam: the scene's."""
+        B = scene_or_backend
+        if not hasattr(B, "adapter_cache"):
+            if self._backend is None or self._backend[0] is not B:
+                self._backend = (B, {mi: HipMeshAdapter(B.meshes[mi]) for mi in sorted(set(B.inst_mesh))})
+            scene, adapters = B, [self._backend[1][mi] for mi in B.inst_mesh]
+        else:
+            scene, adapters = B.scene, [B.adapter(i) for i in range(B.scene.n_inst)]
+        cam = cam or scene.camera
+        pod = camera_pod(cam)
+        meshes = (C.c_void_p * max(1, scene.n_inst))(*[a.h for a in adapters])
+        m, minv = capi.f32(scene.m), capi.f32(scene.minv)
+        capi.check(self.lib.gvt_hip_depth_render(self.h, meshes, capi.ptr(m), capi.ptr(minv), scene.n_inst, C.byref(pod)), "gvt_hip_depth_render")
+        return self
 
 
 def camera_generate(q, cam, tile=0):

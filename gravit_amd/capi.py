@@ -36,6 +36,8 @@ SYMBOLS = [
     "gvt_hip_volume_set_surfaces", "gvt_hip_volume_set_lights", "gvt_hip_volume_get_crossings",
     "gvt_hip_volume_update_samples",
     "gvt_hip_volume_create_typed", "gvt_hip_volume_update_samples_typed", "gvt_hip_volume_get_voxel_type",
+    "gvt_hip_depth_create", "gvt_hip_depth_destroy", "gvt_hip_depth_clear", "gvt_hip_depth_upload", "gvt_hip_depth_download", "gvt_hip_depth_render",
+    "gvt_hip_volume_frame_clipped", "gvt_hip_fb_composite_over",
 ]
 
 
@@ -76,6 +78,7 @@ class VolumeInfo(C.Structure):
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10
 RAY_SIDES = 0x20  # the ray's t field holds the surface sides of the sample in t_min
+RAY_CLIP = 0x40  # the march takes only the samples with k * dt < the ray's t_max
 VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
@@ -118,13 +121,21 @@ def load():
         lib.gvt_hip_volume_create_typed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
         lib.gvt_hip_volume_update_samples_typed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.gvt_hip_volume_get_voxel_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_depth_create.argtypes = [C.c_int, C.c_int]
+        lib.gvt_hip_depth_clear.argtypes = [C.c_void_p]
+        lib.gvt_hip_depth_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.gvt_hip_depth_download.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_depth_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gvt_hip_volume_frame_clipped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
         for f in ("gvt_hip_mesh_create", "gvt_hip_queue_create", "gvt_hip_top_create", "gvt_hip_fb_create", "gvt_hip_fb_device_ptr", "gvt_hip_ctx_create",
-                  "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_comm_create_local", "gvt_hip_tracer_create", "gvt_hip_volume_create", "gvt_hip_volume_create_typed"):
+                  "gvt_hip_comm_create", "gvt_hip_hub_create", "gvt_hip_comm_create_local", "gvt_hip_tracer_create", "gvt_hip_volume_create", "gvt_hip_volume_create_typed",
+                  "gvt_hip_depth_create"):
             getattr(lib, f).restype = C.c_void_p
         for f in ("gvt_hip_mesh_destroy", "gvt_hip_queue_destroy", "gvt_hip_top_destroy", "gvt_hip_fb_destroy", "gvt_hip_ctx_destroy", "gvt_hip_hub_abort",
-                  "gvt_hip_hub_destroy", "gvt_hip_comm_destroy", "gvt_hip_tracer_destroy", "gvt_hip_volume_destroy"):
+                  "gvt_hip_hub_destroy", "gvt_hip_comm_destroy", "gvt_hip_tracer_destroy", "gvt_hip_volume_destroy", "gvt_hip_depth_destroy"):
             getattr(lib, f).restype = None
             getattr(lib, f).argtypes = [C.c_void_p]
         _lib = lib

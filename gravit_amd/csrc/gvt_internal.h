@@ -248,6 +248,11 @@ struct gvt_hip_fb {
   float *d_rgba = nullptr;
 };
 
+struct gvt_hip_depth { // a depth plane (depth.hip): t along every pixel's camera ray, +Inf = nothing there
+  int w = 0, h = 0;
+  float *d_t = nullptr;
+};
+
 struct QueueDesc { // device-visible view of one destination queue
   float4 *planes;
   unsigned long long cap;

@@ -4,10 +4,12 @@
 //                                           the kernels that read voxels are templates over the voxel's C type, a vertex's value is (float)v
 //   k_vol_ranges / k_vol_range_total        the macro cells' value ranges and the brick's, on the device (create and gvt_hip_volume_update_samples)
 //   k_volume_march / k_volume_march_surf    the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp): two
-//                                           entry points of one body, volume_march_body<T, SURF> (SURF: isovalues and slice planes)
+//                                           entry points of one body, volume_march_body<T, SURF, CLIP> (SURF: isovalues and slice planes;
+//                                           CLIP: the launch may hold rays clipped at their t_max, GVT_HIP_RAY_CLIP)
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
-//   gvt_hip_volume_frame                    Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks
+//   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
+//                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
 // The contract (lattice, ownership, evaluation order, flags) is stated in include/gvt_hip.h; tests/volume_checker.py restates it in numpy.
 #include <algorithm>
 #include <cmath>
@@ -88,6 +90,17 @@ __device__ inline int vol_first_after(float t, float dt) {
   int k = (int)q;
   while ((float)k * dt <= t) k++;
   while (k > 0 && (float)(k - 1) * dt > t) k--;
+  return k;
+}
+
+// a clipped ray (GVT_HIP_RAY_CLIP): the last lattice index k >= 0 with k * dt < t_max; -1: none (t_max <= 0, NaN); VOL_K_MAX: no cut
+__device__ inline int vol_last_before(float t_max, float dt) {
+  if (!(t_max > 0.f)) return -1;
+  const float q = floorf(t_max / dt);
+  if (!(q < VOL_K_MAX)) return (int)VOL_K_MAX;
+  int k = (int)q;
+  while ((float)(k + 1) * dt < t_max) k++;
+  while (k >= 0 && !((float)k * dt < t_max)) k--;
   return k;
 }
 
@@ -187,8 +200,10 @@ __device__ inline void surf_composite(const SurfDev &S, float4 c, const float g[
 // ---- the steps of the march.  Each is parity critical (the checkers compare bit for bit) and exists once.
 
 // ray (a = origin | t_min, b = direction) into the brick's object space, and the lattice range k .. k_hi its visit walks (k_hi < k:
-// none).  Returns the first lattice index after t_min.
-__device__ __forceinline__ int vol_ray_range(const VolDev &V, const Mat4 &minv, float4 a, float4 b, float o[3], float d[3], int &k, int &k_hi) {
+// none).  CLIP (the launches that may hold clipped rays): flags = the ray's depth word, and with GVT_HIP_RAY_CLIP in it the range ends
+// at the last sample in front of t_max (b.w).  Returns the first lattice index after t_min.
+template <bool CLIP>
+__device__ __forceinline__ int vol_ray_range(const VolDev &V, const Mat4 &minv, float4 a, float4 b, int flags, float o[3], float d[3], int &k, int &k_hi) {
   const V3 oo = xfm_point(minv, mk3(a.x, a.y, a.z)), dd = xfm_vector(minv, mk3(b.x, b.y, b.z));
   o[0] = oo.x; o[1] = oo.y; o[2] = oo.z; d[0] = dd.x; d[1] = dd.y; d[2] = dd.z;
   float tn, tf;
@@ -202,6 +217,8 @@ __device__ __forceinline__ int vol_ray_range(const VolDev &V, const Mat4 &minv, 
       k = max(k_prog, qlo > 1.f ? (int)qlo - 1 : 0);
       k_hi = qhi < VOL_K_MAX ? (int)qhi + 1 : (int)VOL_K_MAX;
       k_hi = min(k_hi, k + VOL_MAX_SAMPLES);
+      if constexpr (CLIP)
+        if (flags & GVT_HIP_RAY_CLIP) k_hi = min(k_hi, vol_last_before(b.w, V.dt));
     }
   }
   return k_prog;
@@ -275,8 +292,9 @@ __device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, uns
 
 // One lane per ray, persistent waves with lane refill: a lane that finishes its ray takes the next one of the queue (one atomic per wave
 // and refill).  Rays are updated in place.  SURF (volumes that have surfaces): per sample the side mask, at a crossing the shaded
-// surfaces before the sample's own contribution.  prev < 0: no previous sample.
-template <typename T, bool SURF>
+// surfaces before the sample's own contribution.  prev < 0: no previous sample.  CLIP: the launch may hold rays that carry
+// GVT_HIP_RAY_CLIP (vol_ray_range); without it the body is the unclipped march, instruction for instruction, and no ray is flagged.
+template <typename T, bool SURF, bool CLIP>
 __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::conditional_t<SURF, SurfDev, NoSurf> &S, RayPlanes q, unsigned n, const Mat4 &minv,
                                                   unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
   bool active = false, exhausted = false;
@@ -295,7 +313,7 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
         idx = slot;
         active = true;
         const float4 a = q.p0[idx], b = q.p1[idx], c = q.p2[idx], e = q.p3[idx];
-        const int k_prog = vol_ray_range(V, minv, a, b, o, d, k, k_hi);
+        const int k_prog = vol_ray_range<CLIP>(V, minv, a, b, __float_as_int(e.y), o, d, k, k_hi);
         C[0] = c.x; C[1] = c.y; C[2] = c.z;
         A = e.z;
         k_last = -1;
@@ -408,20 +426,21 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
 
 // The two entry points, per voxel type.  The plain one does not receive SurfDev: the table is about 600 bytes of kernel arguments, and its
 // scalar registers are full as it is.
-template <typename T>
+template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                             unsigned long long *__restrict__ stats) {
-  volume_march_body<T, false>(V, NoSurf{}, q, n, minv, work, stats);
+  volume_march_body<T, false, CLIP>(V, NoSurf{}, q, n, minv, work, stats);
 }
-template <typename T>
+template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                  unsigned long long *__restrict__ stats) {
-  volume_march_body<T, true>(V, S, q, n, minv, work, stats);
+  volume_march_body<T, true, CLIP>(V, S, q, n, minv, work, stats);
 }
 
 // ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
 // its first slot, so the queues keep the order of the list they were filled from.
-__device__ inline int vol_next(const TopDev &T, int from, const float o[3], const float d[3], float t_min) {
+// clip: the ray is clipped at t_clip (GVT_HIP_RAY_CLIP and its t_max): a box it enters at or behind t_clip holds no sample of its
+__device__ inline int vol_next(const TopDev &T, int from, const float o[3], const float d[3], float t_min, bool clip, float t_clip) {
   float p = t_min;
   if (from >= 0) { // progress = the exit of the source box (world space, the test below): it grows strictly from hop to hop
     for (int j = 0; j < T.n_inst; j++) {
@@ -441,13 +460,14 @@ __device__ inline int vol_next(const TopDev &T, int from, const float o[3], cons
     const float l[3] = { lo.x, lo.y, lo.z }, h[3] = { hi.x, hi.y, hi.z };
     float tn, tf;
     vol_slab(l, h, o, d, tn, tf);
-    if (tn <= tf && tf > p && (next < 0 || tn < best)) { next = inst; best = tn; }
+    if (tn <= tf && tf > p && (!clip || tn < t_clip) && (next < 0 || tn < best)) { next = inst; best = tn; } // (tn < NaN: false)
   }
   return next;
 }
 
 __global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigned n, TopDev T, int n_dest, int from, int *__restrict__ next_out,
-                                                            unsigned *__restrict__ blk_cnt, float *__restrict__ fb, unsigned n_pix) {
+                                                            unsigned *__restrict__ blk_cnt, float *__restrict__ fb, unsigned n_pix,
+                                                            const float *__restrict__ clip_plane, unsigned n_clip) {
   __shared__ unsigned sh[VOL_DEST_MAX];
   for (int j = threadIdx.x; j < n_dest; j += VOL_BLOCK) sh[j] = 0u;
   __syncthreads();
@@ -458,10 +478,17 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigne
     const float o[3] = { a.x, a.y, a.z }, d[3] = { b.x, b.y, b.z };
     const int depth = __float_as_int(e.y);
     bool deposit = false;
-    if (from < 0) next = vol_next(T, -1, o, d, a.w); // camera rays: no deposit where they meet no brick
+    bool clip = (depth & GVT_HIP_RAY_CLIP) != 0;
+    float t_clip = b.w;
+    if (clip_plane) { // the clipped frame's camera rays (from < 0): what k_vol_scatter is about to give them
+      const unsigned id = (unsigned)__float_as_int(e.x);
+      t_clip = id < n_clip ? clip_plane[id] : INFINITY;
+      clip = t_clip < INFINITY;
+    }
+    if (from < 0) next = vol_next(T, -1, o, d, a.w, clip, t_clip); // camera rays: no deposit where they meet no brick
     else if (depth & GVT_HIP_RAY_OPAQUE) deposit = true;
     else if (depth & GVT_HIP_RAY_BOUNDARY) {
-      next = vol_next(T, from, o, d, a.w);
+      next = vol_next(T, from, o, d, a.w, clip, t_clip);
       deposit = next < 0; // EXTERNAL: the ray leaves the volume
     }
     if (deposit && fb) {
@@ -483,9 +510,11 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigne
 
 #include "ordered_scan.inc" // k_dest_scan: every block's first slot per destination; totals[j] = the rays it receives
 
-// fresh (camera rays): they start with no colour, no opacity and no flags
+// fresh (camera rays): they start with no colour, no opacity and no flags; fresh == 2 (the clipped frame): ... and with t_max = their
+// pixel's depth and GVT_HIP_RAY_CLIP where that is below +Inf
 __global__ __launch_bounds__(VOL_BLOCK) void k_vol_scatter(RayPlanes q, unsigned n, const int *__restrict__ next_in, const unsigned *__restrict__ blk_base,
-                                                           const QueueDesc *__restrict__ queues, int n_dest, int fresh, unsigned *__restrict__ overflow) {
+                                                           const QueueDesc *__restrict__ queues, int n_dest, int fresh, unsigned *__restrict__ overflow,
+                                                           const float *__restrict__ clip_plane, unsigned n_clip) {
   __shared__ unsigned sh[(VOL_BLOCK / 64) * VOL_DEST_MAX]; // rays of wave w for destination j
   for (int x = threadIdx.x; x < (VOL_BLOCK / 64) * n_dest; x += VOL_BLOCK) sh[x] = 0u;
   __syncthreads();
@@ -503,6 +532,10 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_scatter(RayPlanes q, unsigned
   RayRec r = load_ray(q, i);
   r.depth &= ~GVT_HIP_RAY_BOUNDARY;
   if (fresh) { r.c = mk3(0.f, 0.f, 0.f); r.w = 0.f; r.depth = 0; }
+  if (fresh == 2 && (unsigned)r.id < n_clip) {
+    r.t_max = clip_plane[(unsigned)r.id];
+    r.depth = r.t_max < INFINITY ? GVT_HIP_RAY_CLIP : 0;
+  }
   const QueueDesc Q = queues[next];
   if (local < Q.cap) store_ray(make_planes(Q.planes, Q.cap), local, r);
   else atomicOr(overflow, 1u);
@@ -763,8 +796,9 @@ int rebuild_tables(gvt_hip_volume *V) {
 }
 
 // the march of q's rays through brick Vh, in place, on the context's stream (no host wait): the one launch site of the march kernels
-// (gvt_hip_volume_trace and the frame loop come through here)
-int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
+// (gvt_hip_volume_trace and the frame loop come through here).  clip: a ray of q may carry GVT_HIP_RAY_CLIP -- the clipped frame's
+// queues, host rays that were found flagged; the unclipped launches keep the march without the clip (profiles/volume_clip.txt)
+int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16], bool clip) {
   if (!q->size) return 0;
   Ctx &C = gctx();
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
@@ -775,17 +809,21 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16]) {
   const unsigned blocks = std::min(blocks_of(q->size), (unsigned)(std::max(C.n_cu, 1) * 8));
   with_voxel_type(Vh->vtype, [&](auto t) {
     using T = decltype(t);
-    if (Vh->n_iso + Vh->n_pl > 0)
-      k_volume_march_surf<T><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
-    else
-      k_volume_march<T><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), make_planes(q->d_planes, q->cap), (unsigned)q->size, M, work, Vh->d_stats);
+    const RayPlanes P = make_planes(q->d_planes, q->cap);
+    const unsigned n = (unsigned)q->size;
+    const bool surf = Vh->n_iso + Vh->n_pl > 0;
+    if (surf && clip) k_volume_march_surf<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (surf) k_volume_march_surf<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (clip) k_volume_march<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), P, n, M, work, Vh->d_stats);
+    else k_volume_march<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), P, n, M, work, Vh->d_stats);
   });
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 // consumes q_in; one host wait (two where a destination queue has to grow to its exact need first)
-int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb) {
+// clip (from < 0 only): the depth plane the camera's rays are clipped at
+int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *clip = nullptr) {
   Ctx &C = gctx();
   hipStream_t st = C.stream;
   const size_t n = q_in->size, nI = T->n;
@@ -817,10 +855,12 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
   if ((rc = upload_desc())) return rc;
   HIPCHK(hipMemsetAsync(d_ovf, 0, sizeof(unsigned), st));
   const RayPlanes P = make_planes(q_in->d_planes, q_in->cap);
+  const float *clip_plane = (clip && from < 0) ? clip->d_t : nullptr;
+  const unsigned n_clip = clip_plane ? (unsigned)(clip->w * clip->h) : 0u;
   {
     ProfScope ps(KC_SHUFFLE);
     k_vol_classify<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, T->dev(), (int)nI, from, d_next, d_blk, fb ? fb->d_rgba : nullptr,
-                                                fb ? (unsigned)(fb->w * fb->h) : 0u);
+                                                fb ? (unsigned)(fb->w * fb->h) : 0u, clip_plane, n_clip);
     if (nI) k_dest_scan<VOL_BLOCK><<<(unsigned)nI, VOL_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, T->d_hist);
   }
   HIPCHK(hipGetLastError());
@@ -833,7 +873,8 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
   }
   {
     ProfScope ps(KC_SHUFFLE);
-    k_vol_scatter<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, d_next, d_blk, (const QueueDesc *)T->d_qdesc, (int)nI, from < 0 ? 1 : 0, d_ovf);
+    k_vol_scatter<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, d_next, d_blk, (const QueueDesc *)T->d_qdesc, (int)nI, from < 0 ? (clip_plane ? 2 : 1) : 0, d_ovf,
+                                               clip_plane, n_clip);
   }
   HIPCHK(hipGetLastError());
   if (nI) HIPCHK(hipMemcpyAsync(T->h_hist, T->d_hist, sizeof(unsigned) * nI, hipMemcpyDeviceToHost, st));
@@ -1083,7 +1124,9 @@ extern "C" int gvt_hip_volume_trace(gvt_hip_volume *V, const gvt_hip_ray *rays, 
   int rc;
   if ((rc = gvt_hip_queue_clear(q))) return rc;
   if ((rc = gvt_hip_queue_append_flags(q, rays + begin, cnt, GVT_HIP_APPEND_KEEP_STATE))) return rc; // (bytes 64..79 pass through untouched)
-  if ((rc = volume_march(V, q, minv))) return rc;
+  bool clip = false; // (does a ray carry the flag?  One pass over the host rays, before they are staged)
+  for (size_t i = begin; i < end && !clip; i++) clip = (rays[i].depth & GVT_HIP_RAY_CLIP) != 0;
+  if ((rc = volume_march(V, q, minv, clip))) return rc;
   size_t got = 0;
   if ((rc = gvt_hip_queue_export(q, rays_out, cap, &got, 0))) return rc;
   *n_out = got;
@@ -1100,8 +1143,9 @@ extern "C" int gvt_hip_shuffle_volume(gvt_hip_top *T, gvt_hip_queue *q_in, int f
   return shuffle_volume_impl(T, q_in, from, queues, fb);
 }
 
-extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
-                                    gvt_hip_queue *const *queues, gvt_hip_fb *fb, uint64_t *adapter_calls) {
+// gvt_hip_volume_frame and gvt_hip_volume_frame_clipped (depth: the plane the camera's rays are clipped at, or null)
+static int volume_frame_impl(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                             gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!T || !cam || !fb || (n_inst && (!volumes || !m || !minv || !queues)) || T->n != n_inst) {
     set_error("volume_frame: null or inconsistent argument");
@@ -1110,6 +1154,11 @@ extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volum
   if (n_inst > VOL_DEST_MAX) { set_error("volume_frame: %zu bricks, at most %d", n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
   for (size_t i = 0; i < n_inst; i++)
     if (!volumes[i] || !queues[i] || !volumes[i]->has_tf) { set_error("volume_frame: brick %zu has no volume, queue or transfer function", i); return GVT_HIP_ERR_INVALID; }
+  if (depth && (cam->samples != 1 || depth->w != cam->width || depth->h != cam->height)) {
+    set_error("volume_frame_clipped: a %d x %d depth plane for a %d x %d film of %d x %d samples per pixel (one is needed)", depth->w, depth->h, cam->width, cam->height,
+              cam->samples, cam->samples);
+    return GVT_HIP_ERR_INVALID;
+  }
   Ctx &C = gctx();
   if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
   gvt_hip_queue *q_cam = C.abi_qout; // (a staging list of the context: the camera's rays before they are distributed)
@@ -1120,7 +1169,7 @@ extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volum
   // them into the first box): a ray keeps one sample lattice from start to end
   if ((rc = gvt_hip_camera_generate_tiled(q_cam, cam->eye, cam->focus, cam->up, cam->fov, cam->width, cam->height, cam->samples, 0,
                                           cam->jitter_window_size, 8))) return rc;
-  if ((rc = shuffle_volume_impl(T, q_cam, -1, queues, fb))) return rc;
+  if ((rc = shuffle_volume_impl(T, q_cam, -1, queues, fb, depth))) return rc;
   uint64_t calls = 0;
   for (;;) {                                                                                   // :159-259
     int target = -1;
@@ -1128,10 +1177,20 @@ extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volum
     for (size_t i = 0; i < n_inst; i++)
       if (queues[i]->size > cnt) { cnt = queues[i]->size; target = (int)i; }
     if (target < 0) break;
-    if ((rc = volume_march(volumes[target], queues[target], minv + 16 * (size_t)target))) return rc;
+    if ((rc = volume_march(volumes[target], queues[target], minv + 16 * (size_t)target, depth != nullptr))) return rc;
     calls++;
     if ((rc = shuffle_volume_impl(T, queues[target], target, queues, fb))) return rc;       // shuffleRays(moved_rays, instTarget) :252
   }
   if (adapter_calls) *adapter_calls = calls;
   return 0;
+}
+
+extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                                    gvt_hip_queue *const *queues, gvt_hip_fb *fb, uint64_t *adapter_calls) {
+  return volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, nullptr, adapter_calls);
+}
+
+extern "C" int gvt_hip_volume_frame_clipped(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                                            gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
+  return volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, adapter_calls);
 }

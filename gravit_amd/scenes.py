@@ -635,3 +635,15 @@ def split_volume(vol, bx, by, bz):
                 hi = (org + end.astype(F) * sp).astype(F)
                 out.append(Brick(d, off, cnt.copy(), org, sp, lo, hi))
     return out
+
+
+def mesh_in_volume(scene, vol, fill=0.6):
+    """Geometry inside a volume (scheduler.MixedTracer): `vol` placed so that its box is centred on the scene's instances and they take
+    `fill` of its smallest side (the grid keeps its shape: the spacing is scaled uniformly).  Returns the VolumeData; the scene is unchanged."""
+    lo, hi = np.asarray(scene.inst_lo, F).min(axis=0), np.asarray(scene.inst_hi, F).max(axis=0)
+    cells = (vol.counts - 1).astype(np.float64)
+    shape = cells * np.asarray(vol.spacing, np.float64)
+    scale = float((hi - lo).max()) / (fill * float(shape.min()))
+    spacing = (np.asarray(vol.spacing, np.float64) * scale).astype(F)
+    origin = (0.5 * (lo.astype(np.float64) + hi) - 0.5 * cells * spacing).astype(F)
+    return VolumeData(vol.data, origin, spacing)

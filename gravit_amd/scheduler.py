@@ -589,7 +589,9 @@ class VolumeTracer:
         self.calls = 0
         self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
 
-    def frame(self):
+    def frame(self, depth=None):
+        """One frame; depth (an adapter.DepthPlane of the film's size): every camera ray is clipped at its pixel's depth
+        (gvt_hip_volume_frame_clipped: geometry inside the volume)."""
         import ctypes as C
 
         cam = self.camera
@@ -598,8 +600,13 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        capi.check(capi.load().gvt_hip_volume_frame(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
-                                                    C.byref(pod), self._arr(self.queues), self.fb.h, C.byref(calls)), "gvt_hip_volume_frame")
+        if depth is None:
+            capi.check(capi.load().gvt_hip_volume_frame(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                        C.byref(pod), self._arr(self.queues), self.fb.h, C.byref(calls)), "gvt_hip_volume_frame")
+        else:
+            capi.check(capi.load().gvt_hip_volume_frame_clipped(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), self.n_inst,
+                                                                C.byref(pod), self._arr(self.queues), self.fb.h, depth.h, C.byref(calls)),
+                       "gvt_hip_volume_frame_clipped")
         self.calls = calls.value
         return self
 
@@ -648,3 +655,71 @@ class VolumeTracer:
         infos = [a.info() for a in self.adapters]
         return {"adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
                 "samples_gathered": sum(i["samples_gathered"] for i in infos)}
+
+
+class MixedTracer:
+    """A scene that holds geometry AND a volume: the meshes of `scene` inside the bricks of one volume instance.  It owns a NativeTracer
+    (the mesh frame, as it is on its own), a DepthPlane and a VolumeTracer; frame() renders the mesh frame, the depth plane of the
+    scene (a second closest-hit pass over the primaries), the volume frame clipped at it, and composites the volume over the meshes
+    (gvt_hip_fb_composite_over; the result is in the volume tracer's framebuffer).  The reference has no such path: shuffleRays
+    takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel)."""
+
+    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT):
+        from dataclasses import replace
+
+        from .adapter import DepthPlane
+
+        if camera.samples != 1:
+            raise ValueError("MixedTracer: the depth plane holds one ray per pixel (camera.samples must be 1)")
+        self.scene = replace(scene, camera=camera)
+        self.camera = camera
+        self.mesh = NativeTracer(self.scene, normal_mode)
+        self.depth = DepthPlane(camera.width, camera.height)
+        self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native)
+
+    def frame(self):
+        self.mesh()
+        self.depth.render(self.mesh.backend, self.camera)
+        self.volume.frame(self.depth)
+        self.volume.fb.composite_over(self.mesh.backend.fb, self.depth)
+        return self
+
+    def framebuffer(self, clamp=False):
+        """The composite: (H, W, 4), colour premultiplied, alpha = the volume's opacity plus what it leaves of the geometry's coverage."""
+        return self.volume.framebuffer(clamp)
+
+    def mesh_framebuffer(self, clamp=True):
+        return self.mesh.backend.framebuffer(clamp)
+
+    # the volume's controls
+    def update(self, bricks):
+        self.volume.update(bricks)
+        return self
+
+    def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
+        self.volume.set_surfaces(isovalues, slices, opacity)
+        return self
+
+    def set_lights(self, lights, ka=0.4, kd=0.6):
+        self.volume.set_lights(lights, ka, kd)
+        return self
+
+    # the scene's
+    def set_camera(self, cam):
+        if cam.samples != 1:
+            raise ValueError("MixedTracer: the depth plane holds one ray per pixel (camera.samples must be 1)")
+        self.mesh.set_camera(cam)
+        self.camera = self.volume.camera = self.scene.camera = self.mesh.backend.scene.camera = cam
+        return self
+
+    def update_scene(self, scene):
+        if scene.camera.samples != 1:
+            raise ValueError("MixedTracer: the depth plane holds one ray per pixel (camera.samples must be 1)")
+        self.mesh.update_scene(scene)
+        self.scene = scene
+        self.camera = self.volume.camera = scene.camera
+        return self
+
+    def close(self):
+        self.mesh.close()
+        self.depth.close()

@@ -477,6 +477,54 @@ int gvt_hip_volume_set_lights(gvt_hip_volume *, const float *positions /* n*3 */
 /* surfaces composited by the marches of this volume so far (gvt_hip_volume_info keeps its layout); synchronises */
 int gvt_hip_volume_get_crossings(gvt_hip_volume *, uint64_t *crossings_rendered);
 
+/* ---- geometry inside a volume: a march clipped at a depth plane, and the composite of the two images ----
+ * The reference has no counterpart (shuffleRays takes either the mesh or the volume branch, by adapter type): this contract is the
+ * project's own; tests/volume_clip_checker.py restates it in numpy.
+ * CLIPPED MARCH.  A ray that carries GVT_HIP_RAY_CLIP in depth marches lattice sample k only if (float)k * dt < t_max, t_max being the
+ * ray's own field (the comparison is false for NaN: a NaN t_max marches nothing, as does t_max <= 0).  k_clip = the largest k >= 0 that
+ * passes (-1: none), found from floorf(t_max / dt) and corrected with that very comparison in both directions; t_max = +Inf, or a
+ * k_clip that would reach 2^30, cuts nothing.  It bounds the visit last: k_hi = min(k_hi, k_clip).  Nothing changes per sample: the
+ * clipped ray leaves with GVT_HIP_RAY_BOUNDARY (or _OPAQUE) and t_min at its last marched sample (unchanged where it marched none);
+ * surfaces beyond the clip are not detected, their samples not being marched.  A ray without the flag gives the bits it gave before,
+ * whatever its t_max holds.  gvt_hip_volume_trace honours the flag on host rays.  Marching the rest afterwards (flag and
+ * GVT_HIP_RAY_BOUNDARY cleared, same brick) completes the ray to the bits of one unclipped march.
+ * SHUFFLE.  For a ray that carries the flag a box is a candidate of gvt_hip_shuffle_volume only if its entry distance tn < t_max as
+ * well (from < 0 and from >= 0 alike; false for NaN): a clipped ray deposits as EXTERNAL instead of hopping through bricks it cannot
+ * sample, and a clipped camera ray with the wall in front of every brick is dropped.  The entry distance is the float slab test's and
+ * the samples' owner the cell test's: the two can disagree by an ulp, so for a wall within an ulp of a brick's face a bricking may
+ * differ from another (a measure-zero case, like a ray along a shared edge). */
+#define GVT_HIP_RAY_CLIP 0x40             /* depth: march only the samples with k * dt < t_max */
+/* DEPTH PLANE: W*H floats on the device, pixel-major like the framebuffer; each is t along the pixel's camera ray in the ray's own
+ * parameter (the rays of gvt_hip_camera_generate_tiled: origin at the eye, unit direction), +Inf = nothing there. */
+typedef struct gvt_hip_depth gvt_hip_depth;
+gvt_hip_depth *gvt_hip_depth_create(int width, int height);
+void gvt_hip_depth_destroy(gvt_hip_depth *);
+int gvt_hip_depth_clear(gvt_hip_depth *);                                   /* every pixel +Inf */
+int gvt_hip_depth_upload(gvt_hip_depth *, const float *t /* W*H */, uint32_t flags); /* 0: host memory, GVT_HIP_UPDATE_DEVICE: device memory */
+int gvt_hip_depth_download(gvt_hip_depth *, float *t /* W*H, host */);
+/* depth[id] = the minimum over ALL instances i of the closest hit's t (a miss: +Inf) of the camera's ray of pixel id, origin at the eye
+ * and not advanced.  The ray of instance i is xfm_point(minv_i, o), xfm_vector(minv_i, d) = per row r (m[r]*x + m[4+r]*y) + (m[8+r]*z +
+ * m[12+r]*w), w = 1 | 0, the direction not normalised, so t means the same in every instance; tnear = 1e-6 (GVT_RAY_EPSILON).  One
+ * closest-hit launch per instance over the camera's list, in the order given, each followed by a one-writer-per-pixel minimum; one host
+ * wait, at the end.  m is not read (minv is what a trace needs) and may be NULL.  cam->samples != 1, a film that is not the plane's size
+ * or a null plane, camera, mesh or minv: GVT_HIP_ERR_INVALID, the plane unchanged. */
+int gvt_hip_depth_render(gvt_hip_depth *, gvt_hip_mesh *const *meshes, const float *m /* n_inst*16 */, const float *minv, size_t n_inst,
+                         const gvt_hip_camera *cam);
+/* gvt_hip_volume_frame with every camera ray clipped at its pixel of `depth`: the camera's rays enter the queues with colour, opacity
+ * and flags zeroed as before and, for pixel id, t_max = depth[id] and depth = GVT_HIP_RAY_CLIP where depth[id] < +Inf, 0 where it is not
+ * (the shuffle from -1 applies the tn < t_max rule with these values).  depth == NULL: gvt_hip_volume_frame itself (one body).  Otherwise
+ * cam->samples must be 1 and the film the plane's size: else GVT_HIP_ERR_INVALID, nothing changed. */
+int gvt_hip_volume_frame_clipped(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m /* n_inst*16 */, const float *minv, size_t n_inst,
+                                 const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                                 uint64_t *adapter_calls);
+/* front := front OVER back, per pixel p and in this order, every step one float32 operation (no contraction):
+ *   k = 1 - front.a;   front.c = front.c + k * fminf(back.c, 1) per colour channel;   front.a = front.a + k * cov
+ *   cov = depth ? (depth[p] < +Inf ? 1 : 0) : fminf(back.a, 1)
+ * front is a volume frame (premultiplied colour, opacity), back a mesh frame (clamped as gvt_hip_fb_download clamps).  Coverage comes from
+ * the depth plane, not from the mesh framebuffer's alpha: a shadowed surface pixel (colour 0, depth finite) is opaque black.  A pixel
+ * without volume (front all zero) becomes min(back, 1) exactly.  Sizes must agree, front and back must not be NULL (GVT_HIP_ERR_INVALID). */
+int gvt_hip_fb_composite_over(gvt_hip_fb *front, const gvt_hip_fb *back, const gvt_hip_depth *depth);
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

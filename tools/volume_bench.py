@@ -15,6 +15,10 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              first of these alone (it needs nothing the update added, so it also runs on an older tree)
   python tools/volume_bench.py --surfaces    the "thin" frames plain, with two isovalues the field never reaches (the per-sample cost of
                                              the side test alone) and with two it does (opacity 0.3, one light), each against the plain frame
+  python tools/volume_bench.py --clip        geometry inside the volume: per grid size and bricking the "thin" frame plain and clipped at a depth
+                                             plane that is +Inf everywhere (the same rays and samples: what the clip itself costs), frames
+                                             alternating in one process; then the mixed frame -- bun_zipper inside the grid
+                                             (scheduler.MixedTracer) -- and its parts: mesh frame, depth pass, clipped volume frame, composite
 """
 import argparse
 import json
@@ -117,6 +121,58 @@ def med(xs):
     return round(float(np.median(xs)), 3)
 
 
+def timed(fn):
+    t = time.perf_counter()
+    fn()
+    capi.synchronize()
+    return (time.perf_counter() - t) * 1e3
+
+
+def run_clip(n, split, steps, warmup, rate, vol, dtype="f32"):
+    """The plain frame against the frame clipped at an all-+Inf plane, alternating."""
+    from gravit_amd.adapter import DepthPlane
+
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
+    cam = camera()
+    tr = VolumeTracer(bricks, cam, transfer("thin", dtype), sampling_rate=rate, native=dtype != "f32")
+    inf = DepthPlane(cam.width, cam.height)
+    plain, clipped = [], []
+    for i in range(warmup + steps):
+        plain.append(timed(tr.frame))
+        clipped.append(timed(lambda: tr.frame(inf)))
+    plain, clipped = plain[warmup:], clipped[warmup:]
+    return {"mode": "clip_inf", "n": n, "dtype": dtype, "bricks": int(np.prod(split)), "plain_ms_median": med(plain), "plain_ms_min": round(min(plain), 3),
+            "plain_ms_max": round(max(plain), 3), "clipped_ms_median": med(clipped), "clipped_ms_min": round(min(clipped), 3), "clipped_ms_max": round(max(clipped), 3),
+            "clipped_over_plain": round(float(np.median(clipped)) / float(np.median(plain)), 4)}
+
+
+def run_mixed(n, split, steps, warmup, rate, vol, dtype="f32"):
+    """bun_zipper inside the grid at 1080p: the mixed frame and its four parts, each ended by a synchronisation."""
+    from gravit_amd.scheduler import MixedTracer
+
+    scene = scenes.bunny70k_scene(1920, 1080)
+    placed = scenes.mesh_in_volume(scene, vol, fill=0.6)
+    bricks = placed if split == (1, 1, 1) else scenes.split_volume(placed, *split)
+    mt = MixedTracer(scene, bricks, scene.camera, transfer("thin", dtype), sampling_rate=rate, native=dtype != "f32")
+    parts = {"frame": [], "mesh": [], "depth": [], "volume": [], "volume_unclipped": [], "composite": []}
+    B = mt.mesh.backend
+    for i in range(warmup + steps):
+        parts["frame"].append(timed(mt.frame))
+        parts["mesh"].append(timed(mt.mesh))
+        parts["depth"].append(timed(lambda: mt.depth.render(B, mt.camera)))
+        parts["volume"].append(timed(lambda: mt.volume.frame(mt.depth)))
+        parts["composite"].append(timed(lambda: mt.volume.fb.composite_over(B.fb, mt.depth)))
+        parts["volume_unclipped"].append(timed(mt.volume.frame))
+    fb = mt.frame().framebuffer(False)
+    depth = mt.depth.download()
+    out = {"mode": "mixed", "n": n, "dtype": dtype, "bricks": int(np.prod(split)), "mesh": "bun_zipper", "wall_pixels": int(np.isfinite(depth).sum()),
+           "lit_pixels": int((fb[..., 3] > 0).sum())}
+    for k, v in parts.items():
+        out[k + "_ms_median"] = med(v[warmup:])
+        out[k + "_ms_min"] = round(min(v[warmup:]), 3)
+    return out
+
+
 def run_update(n, device, steps, warmup, recreate_only, dtype="f32"):
     """Two time steps of the n^3 noise grid, pushed alternately into one brick under the sparse table."""
     from gravit_amd.adapter import HipVolumeAdapter
@@ -176,6 +232,7 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--surfaces", action="store_true")
     ap.add_argument("--update", action="store_true")
+    ap.add_argument("--clip", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     a = ap.parse_args()
@@ -189,6 +246,15 @@ def main():
                 r = run_update(n, device, a.steps, a.warmup, a.recreate_only, a.dtype)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
+        a.sizes = []
+    for n in a.sizes if a.clip else ():
+        vol = noise(n, a.dtype)
+        for fn in (run_clip, run_mixed):
+            for split in ((1, 1, 1), (2, 2, 2)):
+                r = fn(n, split, a.steps, a.warmup, a.rate, vol, a.dtype)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    if a.clip:
         a.sizes = []
     for n in a.sizes if a.surfaces else ():
         vol = noise(n, a.dtype)
