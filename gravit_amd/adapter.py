@@ -539,6 +539,17 @@ class HipVolumeAdapter:
         capi.check(self.lib.gvt_hip_volume_set_lights(self.h, capi.ptr(pos), capi.ptr(col), len(pos), float(ka), float(kd)),
                    "gvt_hip_volume_set_lights")
 
+    def set_shading(self, on=True):
+        """Lit volume: every sample the table gives opacity is shaded by the gradient of the interpolant in its cell, with the lights and
+        ka / kd of set_lights (without lights the march stays unlit).  on=False: the plain march again."""
+        mode = capi.VOLUME_SHADE_GRADIENT if on else capi.VOLUME_SHADE_NONE
+        capi.check(self.lib.gvt_hip_volume_set_shading(self.h, mode), "gvt_hip_volume_set_shading")
+
+    def shading(self):
+        mode = C.c_int(-1)
+        capi.check(self.lib.gvt_hip_volume_get_shading(self.h, C.byref(mode)), "gvt_hip_volume_get_shading")
+        return mode.value
+
     def info(self):
         i = capi.VolumeInfo()
         capi.check(self.lib.gvt_hip_volume_get_info(self.h, C.byref(i)), "gvt_hip_volume_get_info")
@@ -548,6 +559,12 @@ class HipVolumeAdapter:
         """Surfaces composited by this brick's marches so far."""
         n = C.c_uint64(0)
         capi.check(self.lib.gvt_hip_volume_get_crossings(self.h, C.byref(n)), "gvt_hip_volume_get_crossings")
+        return n.value
+
+    def shaded(self):
+        """Samples shaded by this brick's marches so far."""
+        n = C.c_uint64(0)
+        capi.check(self.lib.gvt_hip_volume_get_shaded(self.h, C.byref(n)), "gvt_hip_volume_get_shaded")
         return n.value
 
     def trace(self, rays, m, minv, begin=0, end=0):

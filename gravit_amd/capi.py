@@ -34,6 +34,7 @@ SYMBOLS = [
     "gvt_hip_volume_create", "gvt_hip_volume_destroy", "gvt_hip_volume_get_info", "gvt_hip_volume_set_transfer", "gvt_hip_volume_trace",
     "gvt_hip_shuffle_volume", "gvt_hip_volume_frame",
     "gvt_hip_volume_set_surfaces", "gvt_hip_volume_set_lights", "gvt_hip_volume_get_crossings",
+    "gvt_hip_volume_set_shading", "gvt_hip_volume_get_shading", "gvt_hip_volume_get_shaded",
     "gvt_hip_volume_update_samples",
     "gvt_hip_volume_create_typed", "gvt_hip_volume_update_samples_typed", "gvt_hip_volume_get_voxel_type",
     "gvt_hip_depth_create", "gvt_hip_depth_destroy", "gvt_hip_depth_clear", "gvt_hip_depth_upload", "gvt_hip_depth_download", "gvt_hip_depth_render",
@@ -82,6 +83,7 @@ RAY_CLIP = 0x40  # the march takes only the samples with k * dt < the ray's t_ma
 VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
+VOLUME_SHADE_NONE, VOLUME_SHADE_GRADIENT = 0, 1  # gvt_hip_volume_set_shading: the fog's samples lit by the interpolant's gradient
 VOXEL_F32, VOXEL_U8, VOXEL_I16, VOXEL_U16 = 0, 1, 2, 3  # a volume's voxel type: the samples stay on the device at that width
 VOXEL_TYPES = {"float32": VOXEL_F32, "uint8": VOXEL_U8, "int16": VOXEL_I16, "uint16": VOXEL_U16}  # by numpy / torch dtype name
 
@@ -117,6 +119,9 @@ def load():
         lib.gvt_hip_volume_set_transfer.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float]
         lib.gvt_hip_volume_set_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]
         lib.gvt_hip_volume_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float]
+        lib.gvt_hip_volume_set_shading.argtypes = [C.c_void_p, C.c_int]
+        lib.gvt_hip_volume_get_shading.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_get_shaded.argtypes = [C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_update_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.gvt_hip_volume_create_typed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
         lib.gvt_hip_volume_update_samples_typed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_void_p]

@@ -3,9 +3,10 @@
 //   gvt_hip_volume_create_typed             ... with 8- and 16-bit integer voxels kept at their own width (Volume::VoxelType, Volume.h:67-75):
 //                                           the kernels that read voxels are templates over the voxel's C type, a vertex's value is (float)v
 //   k_vol_ranges / k_vol_range_total        the macro cells' value ranges and the brick's, on the device (create and gvt_hip_volume_update_samples)
-//   k_volume_march / k_volume_march_surf    the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp): two
-//                                           entry points of one body, volume_march_body<T, SURF, CLIP> (SURF: isovalues and slice planes;
-//                                           CLIP: the launch may hold rays clipped at their t_max, GVT_HIP_RAY_CLIP)
+//   k_volume_march / k_volume_march_surf    the volume adapters' trace (adapter/ospray/OSPRayAdapter.cpp, adapter/pvol/PVolAdapter.cpp): entry
+//   k_volume_march_lit / _surf_lit          points of one body, volume_march_body<T, SURF, CLIP, LIT> (SURF: isovalues and slice planes;
+//                                           CLIP: the launch may hold rays clipped at their t_max, GVT_HIP_RAY_CLIP; LIT: every contributing
+//                                           sample is shaded by the interpolant's gradient, gvt_hip_volume_set_shading)
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
 //   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
@@ -36,11 +37,12 @@ struct gvt_hip_volume {
   void *d_vox = nullptr;
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
   uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
-  unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered
+  unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered, samples shaded
   // surfaces (gvt_hip_volume_set_surfaces / _set_lights): with n_iso + n_pl > 0 the march is k_volume_march_surf (volume_march_body<true>)
   int n_iso = 0, n_pl = 0, n_lights = 0;
   float iso[GVT_HIP_VOLUME_MAX_SURFACES] = {}, plane[GVT_HIP_VOLUME_MAX_SURFACES][4] = {};
   float surf_alpha = 1.f, ka = 0.4f, kd = 0.6f;
+  int shade = GVT_HIP_VOLUME_SHADE_NONE; // gvt_hip_volume_set_shading: with GRADIENT and n_lights > 0 the march is a LIT one (the lights above)
   float lpos[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {}, lcol[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {};
   std::vector<uint8_t> h_mc;     // host copy of d_mc
   uint32_t *d_cells = nullptr;   // per macro cell, for the surface march: skip bit and isovalue sides (rebuilt by set_transfer and set_surfaces)
@@ -133,6 +135,14 @@ struct SurfDev {
   float alpha, ka, kd;
 };
 struct NoSurf {}; // what the plain march has in SurfDev's place: nothing (its scalar registers are full without the table)
+// ... and what the lit plain march has there: the lights alone, about 200 bytes by value (the per-light loop reads them with scalar loads)
+struct LightDev {
+  float ldir[GVT_HIP_VOLUME_MAX_LIGHTS][3], lcol[GVT_HIP_VOLUME_MAX_LIGHTS][3]; // as SurfDev's
+  int n_lights;
+  float ka, kd;
+};
+template <bool SURF, bool LIT>
+using MarchTable = std::conditional_t<SURF, SurfDev, std::conditional_t<LIT, LightDev, NoSurf>>;
 #define VOL_CELL_SKIP 0x10000u
 
 __device__ inline void vol_point(const VolDev &V, const float o[3], const float d[3], int k, float p[3]) {
@@ -272,6 +282,42 @@ __device__ __forceinline__ void vol_accumulate(const VolDev &V, float v, float C
   A = A + fr;
 }
 
+// the gradient of the trilinear interpolant of cell G at the fractions f: the contract's three expressions, for the lit sample.  (The
+// crossing in volume_march_body keeps its own statement of them: routed through here, the unlit surface kernels schedule a handful of
+// instructions differently, and they are to stay what they were -- profiles/volume_shade.txt)
+__device__ __forceinline__ void vol_gradient(const VolDev &V, const VolCorners &G, const float f[3], float g[3]) {
+  g[0] = lerp_(lerp_(G.v100 - G.v000, G.v110 - G.v010, f[1]), lerp_(G.v101 - G.v001, G.v111 - G.v011, f[1]), f[2]) / V.sx;
+  g[1] = lerp_(lerp_(G.v010 - G.v000, G.v110 - G.v100, f[0]), lerp_(G.v011 - G.v001, G.v111 - G.v101, f[0]), f[2]) / V.sy;
+  g[2] = lerp_(lerp_(G.v001 - G.v000, G.v101 - G.v100, f[0]), lerp_(G.v011 - G.v010, G.v111 - G.v110, f[0]), f[1]) / V.sz;
+}
+
+// vol_accumulate for a lit volume (L: SurfDev or LightDev, n_lights > 0): a sample the table gives opacity is shaded by the gradient in its
+// own cell; one of zero opacity adds +0 whatever its colour, so it is neither shaded nor counted.  Unlike surf_composite, a gradient of
+// infinite length shades with S = 0 (g / Inf would be 0 or NaN): C stays finite on grids whose differences overflow.  Returns 1 if shaded
+template <typename LT>
+__device__ __forceinline__ unsigned vol_accumulate_lit(const VolDev &V, const LT &L, float v, const VolCorners &G, const float f[3], float C[3], float &A) {
+  const float4 tc = vol_lookup(V, v);
+  float rgb[3] = { tc.x, tc.y, tc.z };
+  const bool shaded = tc.w > 0.f; // (false for NaN)
+  if (shaded) {
+    float g[3], sum[3] = { 0.f, 0.f, 0.f };
+    vol_gradient(V, G, f, g);
+    const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+    if (len > 0.f && len < INFINITY) { // (false for NaN)
+      const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
+      for (int j = 0; j < L.n_lights; j++) {
+        const float ndl = fabsf((n[0] * L.ldir[j][0] + n[1] * L.ldir[j][1]) + n[2] * L.ldir[j][2]);
+        for (int a = 0; a < 3; a++) sum[a] = sum[a] + L.lcol[j][a] * ndl;
+      }
+    }
+    for (int a = 0; a < 3; a++) rgb[a] = rgb[a] * (L.ka + L.kd * sum[a]);
+  }
+  const float fr = (1.f - A) * tc.w;
+  C[0] = C[0] + fr * rgb[0]; C[1] = C[1] + fr * rgb[1]; C[2] = C[2] + fr * rgb[2];
+  A = A + fr;
+  return shaded ? 1u : 0u;
+}
+
 // the ray leaves the brick: t_min = its last sample here (k_last < 0: it had none), colour, opacity and flags; with surfaces the sides
 // of that sample too
 template <bool SURF>
@@ -294,8 +340,10 @@ __device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, uns
 // and refill).  Rays are updated in place.  SURF (volumes that have surfaces): per sample the side mask, at a crossing the shaded
 // surfaces before the sample's own contribution.  prev < 0: no previous sample.  CLIP: the launch may hold rays that carry
 // GVT_HIP_RAY_CLIP (vol_ray_range); without it the body is the unclipped march, instruction for instruction, and no ray is flagged.
-template <typename T, bool SURF, bool CLIP>
-__device__ __forceinline__ void volume_march_body(const VolDev &V, const std::conditional_t<SURF, SurfDev, NoSurf> &S, RayPlanes q, unsigned n, const Mat4 &minv,
+// LIT (shading on and at least one light): the sample's own contribution is vol_accumulate_lit's, from the corners the gather has just
+// loaded -- they stay live across the look-up; with SURF a crossing is rendered first, as ever.  Without LIT: the march as it was.
+template <typename T, bool SURF, bool CLIP, bool LIT>
+__device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTable<SURF, LIT> &S, RayPlanes q, unsigned n, const Mat4 &minv,
                                                   unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
   bool active = false, exhausted = false;
   unsigned idx = 0;
@@ -304,6 +352,7 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
   bool seen = false;
   unsigned long long n_marched = 0, n_gathered = 0;
   unsigned n_crossed = 0;
+  unsigned long long n_shaded = 0; // (LIT only)
   for (;;) {
     const unsigned long long idle = ballot64(!active);
     if (idle && !exhausted && (__popcll(idle) >= VOL_REFILL_MIN || idle == ballot64(true))) {
@@ -400,7 +449,8 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
             if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
           }
         }
-        vol_accumulate(V, v, C, A);
+        if constexpr (LIT) n_shaded += vol_accumulate_lit(V, S, v, G, f, C, A);
+        else vol_accumulate(V, v, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }
@@ -415,26 +465,39 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const std::co
     n_marched += __shfl_xor(n_marched, s);
     n_gathered += __shfl_xor(n_gathered, s);
     if constexpr (SURF) n_cr += __shfl_xor(n_cr, s);
+    if constexpr (LIT) n_shaded += __shfl_xor(n_shaded, s);
   }
   if (lane_id() == 0 && n_marched) {
     atomicAdd(&stats[0], n_marched);
     atomicAdd(&stats[1], n_gathered);
     if constexpr (SURF)
       if (n_cr) atomicAdd(&stats[2], n_cr);
+    if constexpr (LIT)
+      if (n_shaded) atomicAdd(&stats[3], n_shaded);
   }
 }
 
-// The two entry points, per voxel type.  The plain one does not receive SurfDev: the table is about 600 bytes of kernel arguments, and its
-// scalar registers are full as it is.
+// The entry points, per voxel type.  The plain one does not receive SurfDev: the table is about 600 bytes of kernel arguments, and its
+// scalar registers are full as it is.  The lit plain one receives the lights alone (LightDev); the lit surface one finds them in SurfDev.
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                             unsigned long long *__restrict__ stats) {
-  volume_march_body<T, false, CLIP>(V, NoSurf{}, q, n, minv, work, stats);
+  volume_march_body<T, false, CLIP, false>(V, NoSurf{}, q, n, minv, work, stats);
 }
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                  unsigned long long *__restrict__ stats) {
-  volume_march_body<T, true, CLIP>(V, S, q, n, minv, work, stats);
+  volume_march_body<T, true, CLIP, false>(V, S, q, n, minv, work, stats);
+}
+template <typename T, bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_lit(VolDev V, LightDev L, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                unsigned long long *__restrict__ stats) {
+  volume_march_body<T, false, CLIP, true>(V, L, q, n, minv, work, stats);
+}
+template <typename T, bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf_lit(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                     unsigned long long *__restrict__ stats) {
+  volume_march_body<T, true, CLIP, true>(V, S, q, n, minv, work, stats);
 }
 
 // ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
@@ -682,13 +745,9 @@ VolDev vol_dev(const gvt_hip_volume *Vh) {
 
 // the surface march's by-value block.  The lights' directions are computed here, on the host, in float32: -position as a vector through
 // minv (xfm_vector's order), divided by its length sqrt((x*x + y*y) + z*z); a light whose length is 0 or not finite shines from nowhere (0)
-SurfDev surf_dev(const gvt_hip_volume *Vh, const Mat4 &minv) {
-  SurfDev S{};
-  S.n_iso = Vh->n_iso; S.n_pl = Vh->n_pl; S.n_lights = Vh->n_lights;
-  S.alpha = Vh->surf_alpha; S.ka = Vh->ka; S.kd = Vh->kd;
-  S.cells = Vh->d_cells;
-  for (int i = 0; i < Vh->n_iso; i++) S.iso[i] = Vh->iso[i];
-  for (int i = 0; i < Vh->n_pl; i++) S.plane[i] = make_float4(Vh->plane[i][0], Vh->plane[i][1], Vh->plane[i][2], Vh->plane[i][3]);
+template <typename LT> // (SurfDev or LightDev)
+void lights_dev(const gvt_hip_volume *Vh, const Mat4 &minv, LT &S) {
+  S.n_lights = Vh->n_lights; S.ka = Vh->ka; S.kd = Vh->kd;
   for (int j = 0; j < Vh->n_lights; j++) {
     const V3 l = xfm_vector(minv, mk3(-Vh->lpos[j][0], -Vh->lpos[j][1], -Vh->lpos[j][2]));
     const float len = sqrtf((l.x * l.x + l.y * l.y) + l.z * l.z);
@@ -696,7 +755,22 @@ SurfDev surf_dev(const gvt_hip_volume *Vh, const Mat4 &minv) {
     S.ldir[j][0] = ok ? l.x / len : 0.f; S.ldir[j][1] = ok ? l.y / len : 0.f; S.ldir[j][2] = ok ? l.z / len : 0.f;
     for (int a = 0; a < 3; a++) S.lcol[j][a] = Vh->lcol[j][a];
   }
+}
+SurfDev surf_dev(const gvt_hip_volume *Vh, const Mat4 &minv) {
+  SurfDev S{};
+  S.n_iso = Vh->n_iso; S.n_pl = Vh->n_pl;
+  S.alpha = Vh->surf_alpha;
+  S.cells = Vh->d_cells;
+  for (int i = 0; i < Vh->n_iso; i++) S.iso[i] = Vh->iso[i];
+  for (int i = 0; i < Vh->n_pl; i++) S.plane[i] = make_float4(Vh->plane[i][0], Vh->plane[i][1], Vh->plane[i][2], Vh->plane[i][3]);
+  lights_dev(Vh, minv, S);
   return S;
+}
+// the lit plain march's by-value block: the same lights, prepared the same way
+LightDev light_dev(const gvt_hip_volume *Vh, const Mat4 &minv) {
+  LightDev L{};
+  lights_dev(Vh, minv, L);
+  return L;
 }
 
 // Can a sample of macro cell b evaluate to NaN or to +-Inf?  With a vertex that is not finite, or with finite vertices so far apart that
@@ -812,7 +886,12 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16], boo
     const RayPlanes P = make_planes(q->d_planes, q->cap);
     const unsigned n = (unsigned)q->size;
     const bool surf = Vh->n_iso + Vh->n_pl > 0;
-    if (surf && clip) k_volume_march_surf<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    const bool lit = Vh->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && Vh->n_lights > 0; // (no lights: nothing to shade with, the march as it was)
+    if (lit && surf && clip) k_volume_march_surf_lit<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (lit && surf) k_volume_march_surf_lit<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (lit && clip) k_volume_march_lit<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), light_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (lit) k_volume_march_lit<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), light_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (surf && clip) k_volume_march_surf<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
     else if (surf) k_volume_march_surf<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
     else if (clip) k_volume_march<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), P, n, M, work, Vh->d_stats);
     else k_volume_march<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), P, n, M, work, Vh->d_stats);
@@ -948,8 +1027,8 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create_typed(const void *samples, int 
   // d_vox is exactly the brick: total samples of the voxel type, no padding (no load of the march or the range kernels is wider than the
   // vertices it asks for)
   bool ok = hipMalloc(&V->d_vox, vbytes * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
-            hipMalloc((void **)&V->d_stats, 3 * sizeof(unsigned long long)) == hipSuccess &&
-            hipMemset(V->d_stats, 0, 3 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
+            hipMalloc((void **)&V->d_stats, 4 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMemset(V->d_stats, 0, 4 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
             hipMalloc((void **)&V->d_cells, sizeof(uint32_t) * n_blocks) == hipSuccess;
   // the samples go to the device on the context's stream and the macro cells' ranges are computed there, behind the copy (volume_ranges
   // ends with a host wait): samples in device memory never touch the host
@@ -1088,6 +1167,30 @@ extern "C" int gvt_hip_volume_get_crossings(gvt_hip_volume *V, uint64_t *crossin
   HIPCHK(hipStreamSynchronize(gctx().stream));
   HIPCHK(hipMemcpy(&s, V->d_stats + 2, sizeof(s), hipMemcpyDeviceToHost));
   *crossings_rendered = s;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_set_shading(gvt_hip_volume *V, int mode) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V) { set_error("volume_set_shading: null"); return GVT_HIP_ERR_INVALID; }
+  if (mode != GVT_HIP_VOLUME_SHADE_NONE && mode != GVT_HIP_VOLUME_SHADE_GRADIENT) { set_error("volume_set_shading: unknown mode %d", mode); return GVT_HIP_ERR_INVALID; }
+  V->shade = mode;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_get_shading(gvt_hip_volume *V, int *mode_out) {
+  if (!V || !mode_out) { set_error("volume_get_shading: null"); return GVT_HIP_ERR_INVALID; }
+  *mode_out = V->shade;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_get_shaded(gvt_hip_volume *V, uint64_t *samples_shaded) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !samples_shaded) { set_error("volume_get_shaded: null"); return GVT_HIP_ERR_INVALID; }
+  unsigned long long s = 0;
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(&s, V->d_stats + 3, sizeof(s), hipMemcpyDeviceToHost));
+  *samples_shaded = s;
   return 0;
 }
 

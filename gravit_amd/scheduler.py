@@ -648,13 +648,19 @@ class VolumeTracer:
             a.set_lights(lights, ka, kd)
         return self
 
+    def set_shading(self, on=True):
+        """Lit fog on every brick (HipVolumeAdapter.set_shading): the lights are set_lights'."""
+        for a in self.adapters:
+            a.set_shading(on)
+        return self
+
     def framebuffer(self, clamp=False):
         return self.fb.download(clamp)
 
     def stats(self):
         infos = [a.info() for a in self.adapters]
         return {"adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
-                "samples_gathered": sum(i["samples_gathered"] for i in infos)}
+                "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in self.adapters)}
 
 
 class MixedTracer:
@@ -702,6 +708,10 @@ class MixedTracer:
 
     def set_lights(self, lights, ka=0.4, kd=0.6):
         self.volume.set_lights(lights, ka, kd)
+        return self
+
+    def set_shading(self, on=True):
+        self.volume.set_shading(on)
         return self
 
     # the scene's

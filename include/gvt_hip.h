@@ -477,6 +477,45 @@ int gvt_hip_volume_set_lights(gvt_hip_volume *, const float *positions /* n*3 */
 /* surfaces composited by the marches of this volume so far (gvt_hip_volume_info keeps its layout); synchronises */
 int gvt_hip_volume_get_crossings(gvt_hip_volume *, uint64_t *crossings_rendered);
 
+/* ---- lit volumes: the fog's own samples shaded by the scalar gradient, as the volume engines behind the reference's adapters shade
+ *      theirs with the lights and the ka = 0.4, kd = 0.6 material the adapters hand them (adapter/galaxy/PVolAdapter.cpp:366-397,
+ *      adapter/ospray/OSPRayAdapter.cpp:249-295) ----
+ * The lights, ka and kd are those of gvt_hip_volume_set_lights, prepared by the host at every march exactly as for the surfaces (unit
+ * directions in object space, direction 0 for a degenerate light).  Shading applies when the mode is GVT_HIP_VOLUME_SHADE_GRADIENT AND the
+ * volume has at least one light; otherwise the march is the one stated above, through the same kernels: a volume whose shading was never
+ * switched on is untouched, and _set_lights without _set_shading keeps its meaning (the lights are for the surfaces only).
+ * A shaded march replaces the sample's own contribution.  Sample k has value v, fractions f, cell vertices v000..v111, tc = the table's
+ * look-up at v (rgb and corrected opacity tc.w):
+ *   if tc.w > 0:  g = the three expressions stated above for an isovalue's gradient (same lerp nesting, divided by the spacing);
+ *                 len = sqrt((g.x*g.x + g.y*g.y) + g.z*g.z);  S = (0, 0, 0);
+ *                 if len > 0 and len < +Inf (false for NaN): n = g / len and per light j in order
+ *                     ndl = |(n.x*l.x + n.y*l.y) + n.z*l.z|,  S = S + colour_j * ndl;
+ *                 rgb = tc.rgb * (ka + kd * S) per channel
+ *   otherwise:    rgb = tc.rgb (no gradient is computed, nothing is counted)
+ *   then as ever: f = (1 - A) * tc.w;  C = C + f * rgb;  A = A + f.
+ * Every operation is one float32 operation in this order: no contraction, no fast math.  samples_shaded counts the samples that took the
+ * tc.w > 0 branch.
+ * Why tc.w > 0: a sample of zero opacity adds exactly +0 whether it is shaded or not, so macro-cell skipping stays bit-exact against
+ * GVT_HIP_VOLUME_NO_SKIP (a skipped sample is one of those), samples_shaded is the same with and without skipping, and on a sparse table
+ * the gradient is computed only where it shows.
+ * Why len < +Inf: on a grid with Inf vertices, or finite ones whose differences overflow, g has an infinite component and g / len would
+ * be NaN (Inf / Inf); the guard shades such a sample with S = 0, i.e. rgb = tc.rgb * ka, and C stays finite as the non-finite part of the
+ * volume contract promises.  THE SURFACE RULE DIFFERS: a crossed isosurface tests len > 0 only (its rule above is unchanged).
+ * Consequences: ka = 1, kd = 0 gives the plain march's bits (x * (1 + 0 * S) = x, S being finite); so do no lights and mode NONE.
+ * With surfaces, a crossing detected at sample k is rendered first, as above, and then -- unless it ended the ray -- the sample's own
+ * contribution is shaded with the same g.  The clipped march and typed voxels shade alike.
+ * Bricking: the interpolant's gradient in the sample's own cell needs that cell's eight vertices only, which the sample's owner holds:
+ * no ghost layers, and the image is the same bits for every bricking.
+ * DEVIATION from the reference's engines: they shade with central differences of the vertices, a gradient that is continuous across
+ * cells.  This one is the gradient of the trilinear interpolant: continuous inside a cell, discontinuous across cell faces (faint facets
+ * at low resolution).  Central differences would need the neighbouring bricks' vertices and give up "the same bits for every bricking". */
+#define GVT_HIP_VOLUME_SHADE_NONE 0
+#define GVT_HIP_VOLUME_SHADE_GRADIENT 1
+int gvt_hip_volume_set_shading(gvt_hip_volume *, int mode);        /* any other mode: GVT_HIP_ERR_INVALID, the volume unchanged */
+int gvt_hip_volume_get_shading(gvt_hip_volume *, int *mode_out);
+/* samples shaded by the marches of this volume so far (gvt_hip_volume_info keeps its layout); synchronises, as _get_crossings does */
+int gvt_hip_volume_get_shaded(gvt_hip_volume *, uint64_t *samples_shaded);
+
 /* ---- geometry inside a volume: a march clipped at a depth plane, and the composite of the two images ----
  * The reference has no counterpart (shuffleRays takes either the mesh or the volume branch, by adapter type): this contract is the
  * project's own; tests/volume_clip_checker.py restates it in numpy.

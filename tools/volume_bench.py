@@ -19,6 +19,9 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              plane that is +Inf everywhere (the same rays and samples: what the clip itself costs), frames
                                              alternating in one process; then the mixed frame -- bun_zipper inside the grid
                                              (scheduler.MixedTracer) -- and its parts: mesh frame, depth pass, clipped volume frame, composite
+  python tools/volume_bench.py --shade       lit volumes: per grid size, table and bricking the frame unlit, lit by one light and lit by three
+                                             (VolumeTracer.set_shading), frames alternating in one process on one tracer; with each the
+                                             samples shaded per frame
 """
 import argparse
 import json
@@ -146,6 +149,34 @@ def run_clip(n, split, steps, warmup, rate, vol, dtype="f32"):
             "clipped_over_plain": round(float(np.median(clipped)) / float(np.median(plain)), 4)}
 
 
+SHADE_LIGHTS = [((3.0, 4.0, 5.0), (1.0, 0.9, 0.8)), ((-2.0, 1.0, 0.5), (0.2, 0.3, 0.4)), ((0.0, -6.0, 1.0), (0.5, 0.1, 0.3))]
+
+
+def run_shade(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
+    """The frame unlit, with one light and with three, alternating on one tracer (the same rays and samples: what the lighting costs)."""
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32")
+    modes = {"unlit": 0, "lit1": 1, "lit3": 3}
+    ms = {k: [] for k in modes}
+    shaded = {}
+    for i in range(warmup + steps):
+        for k, n_lights in modes.items():
+            tr.set_lights(SHADE_LIGHTS[:n_lights]).set_shading(n_lights > 0)
+            s0 = tr.stats()["samples_shaded"] if i == warmup else 0
+            ms[k].append(timed(tr.frame))
+            if i == warmup:
+                shaded[k] = tr.stats()["samples_shaded"] - s0
+    st = tr.stats()
+    out = {"mode": "shade", "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)),
+           "samples_per_frame": int(st["samples_marched"] / (3 * (warmup + steps))), "samples_interpolated": int(st["samples_gathered"] / (3 * (warmup + steps)))}
+    for k in modes:
+        v = ms[k][warmup:]
+        out.update({k + "_ms_median": med(v), k + "_ms_min": round(min(v), 3), k + "_ms_max": round(max(v), 3), k + "_samples_shaded": int(shaded[k])})
+    for k in ("lit1", "lit3"):
+        out[k + "_over_unlit"] = round(out[k + "_ms_median"] / out["unlit_ms_median"], 4)
+    return out
+
+
 def run_mixed(n, split, steps, warmup, rate, vol, dtype="f32"):
     """bun_zipper inside the grid at 1080p: the mixed frame and its four parts, each ended by a synchronisation."""
     from gravit_amd.scheduler import MixedTracer
@@ -233,6 +264,7 @@ def main():
     ap.add_argument("--surfaces", action="store_true")
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--clip", action="store_true")
+    ap.add_argument("--shade", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     a = ap.parse_args()
@@ -255,6 +287,15 @@ def main():
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
     if a.clip:
+        a.sizes = []
+    for n in a.sizes if a.shade else ():
+        vol = noise(n, a.dtype)
+        for kind in a.tf:
+            for split in ((1, 1, 1), (2, 2, 2)):
+                r = run_shade(n, split, a.steps, a.warmup, a.rate, kind, vol, a.dtype)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    if a.shade:
         a.sizes = []
     for n in a.sizes if a.surfaces else ():
         vol = noise(n, a.dtype)
