@@ -431,6 +431,7 @@ class TransferFunction:
 class HipVolumeAdapter:
     """A volume brick on the device (gvt_hip_volume): the counterpart of the reference's volume adapters (OSPRayAdapter, PVolAdapter).
     `brick` is a scenes.Brick (or a scenes.VolumeData: the whole grid as one brick); its data may also be a torch tensor on the GPU.
+    A brick that carries `subgrids` (scenes.refine, scenes.split_amr_volume) is an AMR volume: they are set at construction (set_subgrids).
     native=False: the data is converted to float32, whatever it was.  native=True: a uint8, int16 or uint16 brick (numpy array or contiguous
     GPU tensor) is stored at its own width (gvt_hip_volume_create_typed: a vertex's value is (float)v, so transfer functions and isovalues
     are in the data's units) and answers bit for bit like the float32 brick of the converted data; any other dtype raises ValueError.
@@ -478,6 +479,43 @@ class HipVolumeAdapter:
         vt, nb = C.c_int(-1), C.c_size_t(0)
         capi.check(self.lib.gvt_hip_volume_get_voxel_type(self.h, C.byref(vt), C.byref(nb)), "gvt_hip_volume_get_voxel_type")
         self.voxel_type, self.sample_bytes = vt.value, nb.value
+        if getattr(brick, "subgrids", None):  # an AMR brick: its subgrids come with it
+            self.set_subgrids(brick.subgrids)
+
+    def set_subgrids(self, subgrids):
+        """gvt_hip_volume_set_subgrids: the brick's whole set of refined subgrids (scenes.Subgrid; an empty list removes it).  Their data:
+        numpy arrays, or contiguous float32 torch tensors on the GPU (all of them: no host round trip).  The library keeps its own copies."""
+        subgrids = list(subgrids)
+        n = len(subgrids)
+        pods = (capi.SubgridPod * max(n, 1))()
+        ptrs = (C.c_void_p * max(n, 1))()
+        keep, device = [], [hasattr(s.data, "data_ptr") and s.data.is_cuda for s in subgrids]
+        if any(device) and not all(device):
+            raise ValueError("set_subgrids: the subgrids' data must be all host arrays or all GPU tensors")
+        for i, s in enumerate(subgrids):
+            pods[i] = capi.SubgridPod(int(s.parent), int(s.ratio), (C.c_int32 * 3)(*[int(v) for v in s.lo]), (C.c_int32 * 3)(*[int(v) for v in s.cells]))
+            shape = tuple(int(c) * int(s.ratio) + 1 for c in list(s.cells)[::-1])
+            if tuple(s.data.shape) != shape:
+                raise ValueError("set_subgrids: subgrid %d has data of shape %s, its cells and ratio need %s" % (i, tuple(s.data.shape), shape))
+            if device[i]:
+                import torch
+
+                if not s.data.is_contiguous() or self.dtype_of(s.data) != "float32":
+                    raise ValueError("set_subgrids: a device tensor must be contiguous float32")
+                torch.cuda.current_stream(s.data.device).synchronize()  # (written on torch's stream, copied on the library's)
+                keep.append(s.data)
+                ptrs[i] = s.data.data_ptr()
+            else:
+                keep.append(np.ascontiguousarray(s.data.numpy() if hasattr(s.data, "data_ptr") else s.data, np.float32))
+                ptrs[i] = keep[-1].ctypes.data
+        flags = capi.VOLUME_DEVICE if n and all(device) else 0
+        capi.check(self.lib.gvt_hip_volume_set_subgrids(self.h, C.cast(pods, C.c_void_p), C.cast(ptrs, C.c_void_p), n, flags), "gvt_hip_volume_set_subgrids")
+
+    def amr_info(self):
+        """n_subgrids, n_levels, subgrid_bytes, samples_refined, amr_marches (gvt_hip_volume_get_amr_info)."""
+        i = capi.VolumeAmrInfo()
+        capi.check(self.lib.gvt_hip_volume_get_amr_info(self.h, C.byref(i)), "gvt_hip_volume_get_amr_info")
+        return i.as_dict()
 
     def close(self):
         if getattr(self, "h", None):

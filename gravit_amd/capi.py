@@ -39,6 +39,7 @@ SYMBOLS = [
     "gvt_hip_volume_create_typed", "gvt_hip_volume_update_samples_typed", "gvt_hip_volume_get_voxel_type",
     "gvt_hip_depth_create", "gvt_hip_depth_destroy", "gvt_hip_depth_clear", "gvt_hip_depth_upload", "gvt_hip_depth_download", "gvt_hip_depth_render",
     "gvt_hip_volume_frame_clipped", "gvt_hip_fb_composite_over",
+    "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
 ]
 
 
@@ -76,6 +77,19 @@ class VolumeInfo(C.Structure):
         return {k: (list(getattr(self, k)) if k in ("box_lo", "box_hi", "blocks") else getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+class SubgridPod(C.Structure):
+    """gvt_hip_subgrid: one refined subgrid of an AMR volume."""
+    _fields_ = [("parent", C.c_int32), ("ratio", C.c_int32), ("lo", C.c_int32 * 3), ("cells", C.c_int32 * 3)]
+
+
+class VolumeAmrInfo(C.Structure):
+    _fields_ = [("n_subgrids", C.c_int32), ("n_levels", C.c_int32), ("subgrid_bytes", C.c_uint64), ("samples_refined", C.c_uint64),
+                ("amr_marches", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10
 RAY_SIDES = 0x20  # the ray's t field holds the surface sides of the sample in t_min
@@ -83,6 +97,7 @@ RAY_CLIP = 0x40  # the march takes only the samples with k * dt < the ray's t_ma
 VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
+VOLUME_MAX_SUBGRIDS, VOLUME_MAX_LEVELS = 4096, 4  # AMR volumes (gvt_hip_volume_set_subgrids)
 VOLUME_SHADE_NONE, VOLUME_SHADE_GRADIENT = 0, 1  # gvt_hip_volume_set_shading: the fog's samples lit by the interpolant's gradient
 VOXEL_F32, VOXEL_U8, VOXEL_I16, VOXEL_U16 = 0, 1, 2, 3  # a volume's voxel type: the samples stay on the device at that width
 VOXEL_TYPES = {"float32": VOXEL_F32, "uint8": VOXEL_U8, "int16": VOXEL_I16, "uint16": VOXEL_U16}  # by numpy / torch dtype name
@@ -126,6 +141,8 @@ def load():
         lib.gvt_hip_volume_create_typed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int]
         lib.gvt_hip_volume_update_samples_typed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, C.c_void_p]
         lib.gvt_hip_volume_get_voxel_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_set_subgrids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        lib.gvt_hip_volume_get_amr_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.gvt_hip_depth_create.argtypes = [C.c_int, C.c_int]
         lib.gvt_hip_depth_clear.argtypes = [C.c_void_p]
         lib.gvt_hip_depth_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
@@ -213,5 +230,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

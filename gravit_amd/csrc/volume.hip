@@ -9,6 +9,7 @@
 //                                           sample is shaded by the interpolant's gradient, gvt_hip_volume_set_shading)
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
+//   k_volume_march_amr / k_amr_ranges       AMR volumes (Volume::AddAMRGrid): nested refined subgrids inside a brick, volume_amr.inc
 //   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
 //                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
 // The contract (lattice, ownership, evaluation order, flags) is stated in include/gvt_hip.h; tests/volume_checker.py restates it in numpy.
@@ -37,7 +38,7 @@ struct gvt_hip_volume {
   void *d_vox = nullptr;
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
   uint8_t *d_mc = nullptr;       // per macro cell: 1 = some table entry its values can reach has a > 0
-  unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered, samples shaded
+  unsigned long long *d_stats = nullptr; // samples marched, samples gathered, surface crossings rendered, samples shaded, samples refined (VOL_N_STATS words)
   // surfaces (gvt_hip_volume_set_surfaces / _set_lights): with n_iso + n_pl > 0 the march is k_volume_march_surf (volume_march_body<true>)
   int n_iso = 0, n_pl = 0, n_lights = 0;
   float iso[GVT_HIP_VOLUME_MAX_SURFACES] = {}, plane[GVT_HIP_VOLUME_MAX_SURFACES][4] = {};
@@ -46,6 +47,17 @@ struct gvt_hip_volume {
   float lpos[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {}, lcol[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {};
   std::vector<uint8_t> h_mc;     // host copy of d_mc
   uint32_t *d_cells = nullptr;   // per macro cell, for the surface march: skip bit and isovalue sides (rebuilt by set_transfer and set_surfaces)
+  // AMR (gvt_hip_volume_set_subgrids): with subgrids the march is k_volume_march_amr (volume_amr.inc: the device tables)
+  std::vector<gvt_hip_subgrid> sub;
+  int amr_levels = 1;            // level 0 and the deepest subgrid's
+  uint64_t amr_bytes = 0, amr_marches = 0;
+  float *d_amr_vox = nullptr;
+  uint2 *d_amr_mc = nullptr;
+  int *d_amr_list = nullptr;
+  int4 *d_amr_desc = nullptr;
+  std::vector<uint32_t> amr_first, amr_count; // per macro cell: its level-1 subgrids in d_amr_list (d_amr_mc without the skip bit)
+  std::vector<float> amr_min, amr_max;        // per macro cell: the subgrids' part of its value range (bmin / bmax / bnan hold the union)
+  std::vector<uint8_t> amr_nan;
 };
 
 namespace {
@@ -56,6 +68,7 @@ namespace {
 #define VOL_K_MAX 1073741824.f
 #define VOL_MAX_SAMPLES (1 << 22) // lattice positions one visit of a brick walks at most (only reached by rays whose |d| is far below the spacing)
 #define VOL_DEST_MAX 256
+#define VOL_N_STATS 8        // words of gvt_hip_volume::d_stats (five in use)
 
 struct VolDev {
   const void *vox; // samples of the brick's voxel type (vol_gather<T> reads them)
@@ -714,6 +727,8 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
   }
 }
 
+#include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges
+
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
 // The voxel types: bytes per sample (0: unknown type), and THE place a run-time type picks a kernel instantiation: f receives a value of
@@ -840,6 +855,16 @@ int volume_ranges(gvt_hip_volume *V) {
   return 0;
 }
 
+// d_amr_mc: per macro cell the place of its level-1 subgrids in d_amr_list and, in bit 31 of y, h_mc (all zero before a transfer function)
+int amr_upload_words(gvt_hip_volume *V) {
+  const size_t nbk = V->amr_first.size();
+  std::vector<uint2> words(nbk);
+  for (size_t b = 0; b < nbk; b++) words[b] = make_uint2(V->amr_first[b], V->amr_count[b] | ((b < V->h_mc.size() && V->h_mc[b]) ? 0x80000000u : 0u));
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the table)
+  HIPCHK(hipMemcpy(V->d_amr_mc, words.data(), sizeof(uint2) * nbk, hipMemcpyHostToDevice));
+  return 0;
+}
+
 // the tables that depend on the samples AND the transfer function (gvt_hip_volume_set_transfer, gvt_hip_volume_update_samples): d_mc,
 // n_empty and, through upload_cells, d_cells.  The one statement of the rule: a block may be skipped when every table entry its values
 // can reach -- one entry of margin either side for the rounding of the interpolation -- has a == 0: its samples then add exactly +0
@@ -866,6 +891,10 @@ int rebuild_tables(gvt_hip_volume *V) {
   HIPCHK(hipMemcpy(V->d_mc, mc.data(), nbk, hipMemcpyHostToDevice));
   V->n_empty = empty;
   V->h_mc.swap(mc);
+  if (!V->sub.empty()) { // the AMR march reads the skip bit from its own per-cell word
+    int rc = amr_upload_words(V);
+    if (rc) return rc;
+  }
   return upload_cells(V);
 }
 
@@ -881,6 +910,15 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16], boo
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = minv[k];
   const unsigned blocks = std::min(blocks_of(q->size), (unsigned)(std::max(C.n_cu, 1) * 8));
+  if (!Vh->sub.empty()) { // an AMR volume: F32, no surfaces, unlit (gvt_hip_volume_set_subgrids and the setters see to it)
+    const RayPlanes P = make_planes(q->d_planes, q->cap);
+    const AmrDev Am{ Vh->d_amr_mc, Vh->d_amr_list, Vh->d_amr_desc, Vh->d_amr_vox };
+    if (clip) k_volume_march_amr<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, P, (unsigned)q->size, M, work, Vh->d_stats);
+    else k_volume_march_amr<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, P, (unsigned)q->size, M, work, Vh->d_stats);
+    HIPCHK(hipGetLastError());
+    Vh->amr_marches++;
+    return 0;
+  }
   with_voxel_type(Vh->vtype, [&](auto t) {
     using T = decltype(t);
     const RayPlanes P = make_planes(q->d_planes, q->cap);
@@ -1027,8 +1065,8 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create_typed(const void *samples, int 
   // d_vox is exactly the brick: total samples of the voxel type, no padding (no load of the march or the range kernels is wider than the
   // vertices it asks for)
   bool ok = hipMalloc(&V->d_vox, vbytes * total) == hipSuccess && hipMalloc((void **)&V->d_tf, sizeof(float4) * 256) == hipSuccess &&
-            hipMalloc((void **)&V->d_stats, 4 * sizeof(unsigned long long)) == hipSuccess &&
-            hipMemset(V->d_stats, 0, 4 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
+            hipMalloc((void **)&V->d_stats, VOL_N_STATS * sizeof(unsigned long long)) == hipSuccess &&
+            hipMemset(V->d_stats, 0, VOL_N_STATS * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&V->d_mc, n_blocks) == hipSuccess &&
             hipMalloc((void **)&V->d_cells, sizeof(uint32_t) * n_blocks) == hipSuccess;
   // the samples go to the device on the context's stream and the macro cells' ranges are computed there, behind the copy (volume_ranges
   // ends with a host wait): samples in device memory never touch the host
@@ -1055,6 +1093,7 @@ extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
   hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats);
+  hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
   delete V;
 }
 
@@ -1096,6 +1135,10 @@ extern "C" int gvt_hip_volume_update_samples_typed(gvt_hip_volume *V, const void
     return GVT_HIP_ERR_INVALID;
   }
   if (flags & ~GVT_HIP_UPDATE_DEVICE) { set_error("volume_update_samples: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
+  if (!V->sub.empty()) {
+    set_error("volume_update_samples: the volume has %zu AMR subgrids (remove them with gvt_hip_volume_set_subgrids(n = 0) first, then set the new step's)", V->sub.size());
+    return GVT_HIP_ERR_INVALID;
+  }
   const size_t total = (size_t)V->n[0] * V->n[1] * V->n[2];
   if (n_samples != total) {
     set_error("volume_update_samples: %zu samples given, the brick has %zu (%d x %d x %d; another grid needs a new volume)", n_samples, total, V->n[0], V->n[1], V->n[2]);
@@ -1132,6 +1175,7 @@ extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isova
     set_error("volume_set_surfaces: %d isovalues and %d slices, at most %d surfaces", n_iso, n_slices, GVT_HIP_VOLUME_MAX_SURFACES);
     return GVT_HIP_ERR_INVALID;
   }
+  if (n_iso + n_slices > 0 && !V->sub.empty()) { set_error("volume_set_surfaces: the volume has AMR subgrids, which take no surfaces"); return GVT_HIP_ERR_INVALID; }
   if (!(opacity > 0.f && opacity <= 1.f)) { set_error("volume_set_surfaces: opacity %g is not in (0, 1]", (double)opacity); return GVT_HIP_ERR_INVALID; }
   for (int i = 0; i < n_iso; i++)
     if (isovalues[i] != isovalues[i]) { set_error("volume_set_surfaces: isovalue %d is NaN", i); return GVT_HIP_ERR_INVALID; }
@@ -1174,6 +1218,7 @@ extern "C" int gvt_hip_volume_set_shading(gvt_hip_volume *V, int mode) {
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!V) { set_error("volume_set_shading: null"); return GVT_HIP_ERR_INVALID; }
   if (mode != GVT_HIP_VOLUME_SHADE_NONE && mode != GVT_HIP_VOLUME_SHADE_GRADIENT) { set_error("volume_set_shading: unknown mode %d", mode); return GVT_HIP_ERR_INVALID; }
+  if (mode == GVT_HIP_VOLUME_SHADE_GRADIENT && !V->sub.empty()) { set_error("volume_set_shading: the volume has AMR subgrids, which are not shaded"); return GVT_HIP_ERR_INVALID; }
   V->shade = mode;
   return 0;
 }
@@ -1296,4 +1341,212 @@ extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volum
 extern "C" int gvt_hip_volume_frame_clipped(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
                                             gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
   return volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, adapter_calls);
+}
+
+// ---- AMR volumes: the host side of volume_amr.inc (the contract: include/gvt_hip.h, "AMR volumes")
+namespace {
+
+// everything gvt_hip_volume_set_subgrids derives from the subgrids before the volume changes
+struct AmrPlan {
+  std::vector<int> level;                 // 1 .. GVT_HIP_VOLUME_MAX_LEVELS - 1
+  std::vector<size_t> offset, count;      // first sample in d_amr_vox, samples
+  std::vector<uint32_t> first, cnt;       // per macro cell: its level-1 subgrids in list
+  std::vector<int> list;
+  std::vector<int4> desc;
+  std::vector<AmrRangeItem> items;
+  std::vector<size_t> item_cell;          // the macro cell of every range item
+  size_t total = 0;
+  int levels = 1;
+};
+
+// the refusals of gvt_hip_volume_set_subgrids that concern the subgrids themselves; fills P
+bool amr_plan(const gvt_hip_volume *V, const gvt_hip_subgrid *g, int n, AmrPlan &P) {
+  const size_t nbk = (size_t)V->nb[0] * V->nb[1] * V->nb[2];
+  P.level.assign(n, 0); P.offset.assign(n, 0); P.count.assign(n, 0);
+  std::vector<long long> rt(n), p0((size_t)3 * n), nv((size_t)3 * n); // total ratio | vertex 0 and vertices per axis, in 1 / rt of a level-0 cell from the brick's vertex 0
+  std::vector<std::vector<int>> kids(n), in_cell(nbk);
+  for (int i = 0; i < n; i++) {
+    const gvt_hip_subgrid &S = g[i];
+    if (S.ratio != 2 && S.ratio != 4 && S.ratio != 8) { set_error("volume_set_subgrids: subgrid %d has ratio %d (2, 4 or 8)", i, S.ratio); return false; }
+    if (S.parent < -1 || S.parent >= i) { set_error("volume_set_subgrids: subgrid %d names parent %d (-1 or an earlier entry)", i, S.parent); return false; }
+    P.level[i] = S.parent < 0 ? 1 : P.level[S.parent] + 1;
+    if (P.level[i] >= GVT_HIP_VOLUME_MAX_LEVELS) { set_error("volume_set_subgrids: subgrid %d is at level %d, at most %d levels", i, P.level[i], GVT_HIP_VOLUME_MAX_LEVELS); return false; }
+    P.levels = std::max(P.levels, P.level[i] + 1);
+    rt[i] = (S.parent < 0 ? 1 : rt[S.parent]) * S.ratio;
+    size_t total = 1;
+    for (int a = 0; a < 3; a++) {
+      if (S.cells[a] < 1) { set_error("volume_set_subgrids: subgrid %d covers %d cells on axis %d", i, S.cells[a], a); return false; }
+      const long long plo = S.parent < 0 ? V->off[a] : 0;
+      const long long phi = S.parent < 0 ? (long long)V->off[a] + V->n[a] - 1 : (long long)g[S.parent].cells[a] * g[S.parent].ratio;
+      if (S.lo[a] < plo || (long long)S.lo[a] + S.cells[a] > phi) {
+        set_error("volume_set_subgrids: subgrid %d covers cells [%d, %lld) of axis %d, its parent has [%lld, %lld)", i, S.lo[a], (long long)S.lo[a] + S.cells[a], a, plo, phi);
+        return false;
+      }
+      nv[3 * i + a] = (long long)S.cells[a] * S.ratio + 1;
+      if (nv[3 * i + a] >= (1 << 24)) { set_error("volume_set_subgrids: subgrid %d is too large on axis %d", i, a); return false; }
+      p0[3 * i + a] = (S.parent < 0 ? (long long)S.lo[a] - V->off[a] : p0[3 * S.parent + a] + S.lo[a]) * S.ratio;
+      total *= (size_t)nv[3 * i + a];
+    }
+    if (total >= 0xffffffffull) { set_error("volume_set_subgrids: subgrid %d of %zu vertices is too large", i, total); return false; }
+    for (int j = 0; j < i; j++) { // siblings must not share a cell
+      if (g[j].parent != S.parent) continue;
+      bool overlap = true;
+      for (int a = 0; a < 3; a++) overlap = overlap && (long long)S.lo[a] < (long long)g[j].lo[a] + g[j].cells[a] && (long long)g[j].lo[a] < (long long)S.lo[a] + S.cells[a];
+      if (overlap) { set_error("volume_set_subgrids: subgrids %d and %d of parent %d overlap", j, i, S.parent); return false; }
+    }
+    P.offset[i] = P.total; P.count[i] = total; P.total += total;
+    if (S.parent >= 0) kids[S.parent].push_back(i);
+    else
+      for (int z = (S.lo[2] - V->off[2]) >> 3; z <= (S.lo[2] - V->off[2] + S.cells[2] - 1) >> 3; z++)
+        for (int y = (S.lo[1] - V->off[1]) >> 3; y <= (S.lo[1] - V->off[1] + S.cells[1] - 1) >> 3; y++)
+          for (int x = (S.lo[0] - V->off[0]) >> 3; x <= (S.lo[0] - V->off[0] + S.cells[0] - 1) >> 3; x++)
+            in_cell[((size_t)z * V->nb[1] + y) * V->nb[0] + x].push_back(i);
+    // the macro cells whose closed box holds vertices of this subgrid, and the index rectangle in each
+    long long m0[3], m1[3];
+    for (int a = 0; a < 3; a++) {
+      const long long w = 8 * rt[i], last = p0[3 * i + a] + nv[3 * i + a] - 1;
+      m0[a] = std::max(0ll, (p0[3 * i + a] - w + w - 1) / w); // the first macro cell with (8 m + 8) rt >= p0 (p0 >= 0)
+      m1[a] = std::min((long long)V->nb[a] - 1, last / w);
+    }
+    for (long long z = m0[2]; z <= m1[2]; z++)
+      for (long long y = m0[1]; y <= m1[1]; y++)
+        for (long long x = m0[0]; x <= m1[0]; x++) {
+          const long long m[3] = { x, y, z };
+          AmrRangeItem I;
+          I.base = P.offset[i]; I.nx = (unsigned)nv[3 * i]; I.nxy = (unsigned)(nv[3 * i] * nv[3 * i + 1]);
+          for (int a = 0; a < 3; a++) {
+            const long long i0 = std::max(0ll, 8 * m[a] * rt[i] - p0[3 * i + a]), i1 = std::min(nv[3 * i + a] - 1, (8 * m[a] + 8) * rt[i] - p0[3 * i + a]);
+            I.i0[a] = (unsigned)i0; I.ext[a] = (unsigned)(i1 - i0 + 1);
+          }
+          P.items.push_back(I);
+          P.item_cell.push_back(((size_t)z * V->nb[1] + y) * V->nb[0] + x);
+        }
+  }
+  P.first.assign(nbk, 0u); P.cnt.assign(nbk, 0u);
+  for (size_t b = 0; b < nbk; b++) {
+    P.first[b] = (uint32_t)P.list.size(); P.cnt[b] = (uint32_t)in_cell[b].size();
+    P.list.insert(P.list.end(), in_cell[b].begin(), in_cell[b].end());
+  }
+  P.desc.resize((size_t)4 * n);
+  for (int i = 0; i < n; i++) {
+    const gvt_hip_subgrid &S = g[i];
+    const int shift = S.ratio == 2 ? 1 : S.ratio == 4 ? 2 : 3;
+    const int rel[3] = { S.parent < 0 ? V->off[0] : 0, S.parent < 0 ? V->off[1] : 0, S.parent < 0 ? V->off[2] : 0 };
+    P.desc[4 * (size_t)i] = make_int4(S.lo[0] - rel[0], S.lo[1] - rel[1], S.lo[2] - rel[2], shift);
+    P.desc[4 * (size_t)i + 1] = make_int4(S.cells[0], S.cells[1], S.cells[2], (int)nv[3 * i]);
+    P.desc[4 * (size_t)i + 2] = make_int4((int)(unsigned)(nv[3 * i] * nv[3 * i + 1]), (int)P.list.size(), (int)kids[i].size(), 0);
+    P.desc[4 * (size_t)i + 3] = make_int4((int)(unsigned)(P.offset[i] & 0xffffffffull), (int)(unsigned)(P.offset[i] >> 32), 0, 0);
+    P.list.insert(P.list.end(), kids[i].begin(), kids[i].end());
+  }
+  if (P.list.empty()) P.list.push_back(0); // (never read: no allocation of zero bytes)
+  return true;
+}
+
+void amr_release(gvt_hip_volume *V) {
+  hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
+  V->d_amr_vox = nullptr; V->d_amr_mc = nullptr; V->d_amr_list = nullptr; V->d_amr_desc = nullptr;
+  V->sub.clear(); V->amr_first.clear(); V->amr_count.clear(); V->amr_min.clear(); V->amr_max.clear(); V->amr_nan.clear();
+  V->amr_levels = 1; V->amr_bytes = 0;
+}
+
+// bmin / bmax / bnan, vmin / vmax: the level-0 ranges afresh from d_vox, then the subgrids' part merged in; the tables from the union
+int amr_refresh_ranges(gvt_hip_volume *V) {
+  int rc = volume_ranges(V);
+  if (rc) return rc;
+  for (size_t b = 0; b < V->amr_min.size(); b++) {
+    if (V->amr_min[b] < V->bmin[b]) V->bmin[b] = V->amr_min[b];
+    if (V->amr_max[b] > V->bmax[b]) V->bmax[b] = V->amr_max[b];
+    V->bnan[b] |= V->amr_nan[b];
+    if (V->amr_min[b] < V->vmin) V->vmin = V->amr_min[b];
+    if (V->amr_max[b] > V->vmax) V->vmax = V->amr_max[b];
+  }
+  return V->has_tf ? rebuild_tables(V) : 0;
+}
+
+} // namespace
+
+extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subgrid *grids, const float *const *samples, int n, int flags) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || (n > 0 && (!grids || !samples))) { set_error("volume_set_subgrids: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (n < 0 || n > GVT_HIP_VOLUME_MAX_SUBGRIDS) { set_error("volume_set_subgrids: %d subgrids, at most %d", n, GVT_HIP_VOLUME_MAX_SUBGRIDS); return GVT_HIP_ERR_INVALID; }
+  if (flags & ~GVT_HIP_VOLUME_DEVICE) { set_error("volume_set_subgrids: unknown flag bits %d", flags); return GVT_HIP_ERR_INVALID; }
+  if (V->vtype != GVT_HIP_VOXEL_F32) { set_error("volume_set_subgrids: the volume holds voxel type %d, subgrids are float32", V->vtype); return GVT_HIP_ERR_INVALID; }
+  if (V->n_iso + V->n_pl > 0 || V->shade == GVT_HIP_VOLUME_SHADE_GRADIENT) {
+    set_error("volume_set_subgrids: the volume has surfaces or gradient shading, which AMR volumes do not take");
+    return GVT_HIP_ERR_INVALID;
+  }
+  for (int i = 0; i < n; i++)
+    if (!samples[i]) { set_error("volume_set_subgrids: subgrid %d has no samples", i); return GVT_HIP_ERR_INVALID; }
+  hipStream_t st = gctx().stream;
+  if (n == 0) {
+    if (V->sub.empty()) return 0;
+    HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the tables)
+    amr_release(V);
+    return amr_refresh_ranges(V);
+  }
+  AmrPlan P;
+  if (!amr_plan(V, grids, n, P)) return GVT_HIP_ERR_INVALID;
+  // the new device tables and the subgrids' ranges, all before the volume changes
+  const size_t nbk = P.first.size(), n_items = P.items.size();
+  float *d_vox = nullptr;
+  uint2 *d_mc = nullptr;
+  int *d_list = nullptr;
+  int4 *d_desc = nullptr;
+  AmrRangeItem *d_items = nullptr;
+  AmrRangeOut *d_out = nullptr;
+  std::vector<AmrRangeOut> out(n_items);
+  auto fail = [&](const char *what) {
+    set_error("volume_set_subgrids: %s failed: %s", what, hipGetErrorString(hipGetLastError()));
+    hipFree(d_vox); hipFree(d_mc); hipFree(d_list); hipFree(d_desc); hipFree(d_items); hipFree(d_out);
+    return GVT_HIP_ERR_DEVICE;
+  };
+  HIPCHK(hipStreamSynchronize(st));
+  bool ok = hipMalloc((void **)&d_vox, sizeof(float) * P.total) == hipSuccess && hipMalloc((void **)&d_mc, sizeof(uint2) * nbk) == hipSuccess &&
+            hipMalloc((void **)&d_list, sizeof(int) * P.list.size()) == hipSuccess && hipMalloc((void **)&d_desc, sizeof(int4) * P.desc.size()) == hipSuccess &&
+            hipMalloc((void **)&d_items, sizeof(AmrRangeItem) * n_items) == hipSuccess && hipMalloc((void **)&d_out, sizeof(AmrRangeOut) * n_items) == hipSuccess;
+  if (!ok) return fail("device allocation");
+  const hipMemcpyKind kind = (flags & GVT_HIP_VOLUME_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  for (int i = 0; i < n && ok; i++) ok = hipMemcpyAsync(d_vox + P.offset[i], samples[i], sizeof(float) * P.count[i], kind, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(d_list, P.list.data(), sizeof(int) * P.list.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+       hipMemcpyAsync(d_desc, P.desc.data(), sizeof(int4) * P.desc.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+       hipMemcpyAsync(d_items, P.items.data(), sizeof(AmrRangeItem) * n_items, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (!ok) return fail("upload");
+  {
+    ProfScope ps(KC_BUILD);
+    k_amr_ranges<<<(unsigned)std::min(n_items, (size_t)1 << 20), VOL_BLOCK, 0, st>>>(d_vox, d_items, (unsigned)n_items, d_out);
+  }
+  ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(out.data(), d_out, sizeof(AmrRangeOut) * n_items, hipMemcpyDeviceToHost, st) == hipSuccess &&
+       hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) return fail("the range kernel");
+  hipFree(d_items); hipFree(d_out);
+  // commit
+  amr_release(V);
+  V->d_amr_vox = d_vox; V->d_amr_mc = d_mc; V->d_amr_list = d_list; V->d_amr_desc = d_desc;
+  V->sub.assign(grids, grids + n);
+  V->amr_levels = P.levels;
+  V->amr_bytes = sizeof(float) * P.total + sizeof(uint2) * nbk + sizeof(int) * P.list.size() + sizeof(int4) * P.desc.size();
+  V->amr_first.swap(P.first); V->amr_count.swap(P.cnt);
+  V->amr_min.assign(nbk, INFINITY); V->amr_max.assign(nbk, -INFINITY); V->amr_nan.assign(nbk, 0);
+  for (size_t i = 0; i < n_items; i++) {
+    const size_t b = P.item_cell[i];
+    if (out[i].mn < V->amr_min[b]) V->amr_min[b] = out[i].mn;
+    if (out[i].mx > V->amr_max[b]) V->amr_max[b] = out[i].mx;
+    V->amr_nan[b] |= (uint8_t)out[i].wild;
+  }
+  int rc = amr_upload_words(V); // (before a transfer function: no skip bit yet; rebuild_tables uploads them again)
+  if (rc) return rc;
+  return amr_refresh_ranges(V);
+}
+
+extern "C" int gvt_hip_volume_get_amr_info(gvt_hip_volume *V, gvt_hip_volume_amr_info *out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !out) { set_error("volume_get_amr_info: null"); return GVT_HIP_ERR_INVALID; }
+  unsigned long long s = 0;
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(&s, V->d_stats + 4, sizeof(s), hipMemcpyDeviceToHost));
+  gvt_hip_volume_amr_info I{};
+  I.n_subgrids = (int32_t)V->sub.size(); I.n_levels = V->amr_levels;
+  I.subgrid_bytes = V->amr_bytes; I.samples_refined = s; I.amr_marches = V->amr_marches;
+  *out = I;
+  return 0;
 }

@@ -524,12 +524,27 @@ def load_conf(path, geom_dirs=None, width=None, height=None):
 
 # ------------------------------------------------------------------ volumes (render/data/primitives/Volume.h; data/vol/*.bov)
 @dataclass
+class Subgrid:
+    """One refined subgrid of an AMR volume (gvt_hip_subgrid; Volume::AddAMRGrid): it refines the cells [lo, lo + cells) of its parent --
+    the level-0 grid (parent -1: lo is a GLOBAL cell index) or an EARLIER entry of the same list -- `ratio` (2, 4 or 8) times per axis.
+    data[z, y, x]: cells * ratio + 1 vertices per axis, float32; vertex 0 sits on the parent's vertex lo."""
+
+    parent: int
+    ratio: int
+    lo: np.ndarray  # (3,) i32, x y z
+    cells: np.ndarray  # (3,) i32
+    data: np.ndarray
+
+
+@dataclass
 class VolumeData:
-    """A scalar grid: data[z, y, x] (x fastest, the BOV order), the position of vertex 0 and the vertex spacing."""
+    """A scalar grid: data[z, y, x] (x fastest, the BOV order), the position of vertex 0 and the vertex spacing.  subgrids: the refined
+    subgrids of an AMR volume (a list of Subgrid; empty: a uniform grid)."""
 
     data: np.ndarray  # (nz, ny, nx); f32, or whatever the source held (uint8 / int16 / uint16 for HipVolumeAdapter(native=True))
     origin: np.ndarray = field(default_factory=lambda: np.zeros(3, F))
     spacing: np.ndarray = field(default_factory=lambda: np.ones(3, F))
+    subgrids: list = field(default_factory=list)
 
     @property
     def counts(self):
@@ -549,6 +564,7 @@ class Brick:
     spacing: np.ndarray
     lo: np.ndarray
     hi: np.ndarray
+    subgrids: list = field(default_factory=list)  # the AMR subgrids this brick holds (split_amr_volume); level-1 lo stays GLOBAL
 
     @property
     def counts(self):
@@ -647,3 +663,130 @@ def mesh_in_volume(scene, vol, fill=0.6):
     spacing = (np.asarray(vol.spacing, np.float64) * scale).astype(F)
     origin = (0.5 * (lo.astype(np.float64) + hi) - 0.5 * cells * spacing).astype(F)
     return VolumeData(vol.data, origin, spacing)
+
+
+# ------------------------------------------------------------------ AMR volumes (Volume::AddAMRGrid; api::addAmrSubgrid; apps/render/AmrApp.cpp)
+def subgrid_geometry(vol, index):
+    """Origin (the position of vertex 0) and vertex spacing of subgrid `index` of vol (-1: the level-0 grid), in float64."""
+    if index < 0:
+        return np.asarray(vol.origin, np.float64), np.asarray(vol.spacing, np.float64)
+    s = vol.subgrids[index]
+    org, sp = subgrid_geometry(vol, s.parent)
+    return org + np.asarray(s.lo, np.float64) * sp, sp / s.ratio
+
+
+def _parent_cells(vol, parent):
+    """The cells [lo, hi) a subgrid of `parent` may cover: the grid's own (for a brick: the global indices of the cells it owns)."""
+    if parent < 0:
+        off = np.asarray(getattr(vol, "offset", np.zeros(3)), np.int64)
+        return off, off + np.asarray(vol.counts, np.int64) - 1
+    p = vol.subgrids[parent]
+    return np.zeros(3, np.int64), np.asarray(p.cells, np.int64) * p.ratio
+
+
+def _prolong(data, lo, cells, ratio):
+    """Trilinear prolongation: the grid `data` (z, y, x) sampled at the vertices of a subgrid that refines its cells [lo, lo + cells)."""
+    out = np.asarray(data, np.float64)
+    for axis, a in ((2, 0), (1, 1), (0, 2)):  # x, y, z
+        pos = lo[a] + np.arange(cells[a] * ratio + 1, dtype=np.float64) / ratio
+        i0 = np.minimum(pos.astype(np.int64), out.shape[axis] - 2)
+        w = pos - i0
+        shape = [1, 1, 1]
+        shape[axis] = len(w)
+        w = w.reshape(shape)
+        out = np.take(out, i0, axis=axis) * (1 - w) + np.take(out, i0 + 1, axis=axis) * w
+    return out
+
+
+def refine(vol, lo, cells, ratio, parent=-1, fn=None, seed=0, detail=0.05):
+    """Appends a Subgrid to vol.subgrids (vol: a VolumeData or a Brick) and returns its index (the `parent` of a child).  It refines
+    the cells [lo, lo + cells) of `parent` (-1: the level-0 grid, lo a global cell index) `ratio` times.  fn(x, y, z): the field as a
+    function of position in the volume's own space (arrays that broadcast to (nz, ny, nx)).  Without fn: the trilinear prolongation of
+    the parent plus uniform detail noise of amplitude `detail` from `seed`.  ValueError for what gvt_hip_volume_set_subgrids refuses."""
+    lo, cells = np.asarray(lo, np.int64).reshape(3), np.asarray(cells, np.int64).reshape(3)
+    if ratio not in (2, 4, 8):
+        raise ValueError("refine: ratio %r (2, 4 or 8)" % (ratio,))
+    if not -1 <= parent < len(vol.subgrids):
+        raise ValueError("refine: parent %d of %d subgrids" % (parent, len(vol.subgrids)))
+    plo, phi = _parent_cells(vol, parent)
+    if (cells < 1).any() or (lo < plo).any() or (lo + cells > phi).any():
+        raise ValueError("refine: cells [%s, %s) leave the parent's [%s, %s)" % (lo.tolist(), (lo + cells).tolist(), plo.tolist(), phi.tolist()))
+    for s in vol.subgrids:
+        if s.parent == parent and ((lo < np.asarray(s.lo) + np.asarray(s.cells)) & (np.asarray(s.lo) < lo + cells)).all():
+            raise ValueError("refine: the box overlaps another subgrid of parent %d" % parent)
+    nv = cells * ratio + 1
+    if fn is not None:
+        org, sp = subgrid_geometry(vol, parent)
+        p = [org[a] + (lo[a] + np.arange(nv[a], dtype=np.float64) / ratio) * sp[a] for a in range(3)]
+        data = np.broadcast_to(np.asarray(fn(p[0][None, None, :], p[1][None, :, None], p[2][:, None, None]), np.float64), (nv[2], nv[1], nv[0]))
+    else:
+        src = vol.data if parent < 0 else vol.subgrids[parent].data
+        rel = lo - (plo if parent < 0 else 0)  # the level-0 array starts at the brick's first vertex
+        data = _prolong(src, rel, cells, ratio) + detail * (np.random.default_rng(seed).random((nv[2], nv[1], nv[0])) - 0.5)
+    vol.subgrids.append(Subgrid(int(parent), int(ratio), lo.astype(np.int32), cells.astype(np.int32), np.ascontiguousarray(data, F)))
+    return len(vol.subgrids) - 1
+
+
+def subgrid_from_geometry(parent_origin, parent_spacing, origin, spacing, counts, tol=1e-4):
+    """The reference's addAmrSubgrid(origin, spacing, counts) triple (counts: vertices per axis) against its parent grid's origin and
+    spacing, as (ratio, lo, cells).  ValueError if the ratio is not 2, 4 or 8 on every axis, or the grid is not cell-aligned: vertex 0 on
+    a parent vertex at or after the parent's first, and whole parent cells covered (tol: in units of a parent cell)."""
+    po, ps = np.asarray(parent_origin, np.float64).reshape(3), np.asarray(parent_spacing, np.float64).reshape(3)
+    o, sp, cnt = np.asarray(origin, np.float64).reshape(3), np.asarray(spacing, np.float64).reshape(3), np.asarray(counts, np.int64).reshape(3)
+    r = ps / sp
+    ratio = int(round(float(r[0])))
+    if ratio not in (2, 4, 8) or (np.abs(r - ratio) > tol * ratio).any():
+        raise ValueError("subgrid_from_geometry: spacing ratio %s is not 2, 4 or 8 on every axis" % r.tolist())
+    g = (o - po) / ps
+    lo = np.rint(g).astype(np.int64)
+    if (np.abs(g - lo) > tol).any() or (lo < 0).any():
+        raise ValueError("subgrid_from_geometry: vertex 0 at %s parent cells is not on a parent vertex" % g.tolist())
+    if (cnt < ratio + 1).any() or ((cnt - 1) % ratio != 0).any():
+        raise ValueError("subgrid_from_geometry: %s vertices at ratio %d do not cover whole parent cells" % (cnt.tolist(), ratio))
+    return ratio, lo.astype(np.int32), ((cnt - 1) // ratio).astype(np.int32)
+
+
+def split_amr_volume(vol, bx, by, bz, cuts=None):
+    """split_volume, and every level-1 subgrid of vol -- with its descendants, re-indexed in the brick's own list -- handed to the brick
+    that owns its cells.  ValueError if a level-1 subgrid straddles a cut (the caller cuts it, or chooses another bricking).
+    cuts (optional): per axis the vertices the bricks begin and end at, ([0, ..., nx - 1], [0, ..., ny - 1], [0, ..., nz - 1]) with
+    bx + 1, by + 1 and bz + 1 increasing entries, instead of split_volume's even cuts -- to keep the cuts clear of the subgrids."""
+    if cuts is None:
+        bricks = split_volume(vol, bx, by, bz)
+    else:
+        cnt = vol.counts
+        for a, (c, parts) in enumerate(zip(cuts, (bx, by, bz))):
+            c = [int(v) for v in c]
+            if len(c) != parts + 1 or c[0] != 0 or c[-1] != int(cnt[a]) - 1 or any(q <= p for p, q in zip(c, c[1:])):
+                raise ValueError("split_amr_volume: cuts %s of axis %d do not divide its %d cells into %d bricks" % (c, a, int(cnt[a]) - 1, parts))
+        org, sp = np.asarray(vol.origin, F), np.asarray(vol.spacing, F)
+        bricks = []
+        for k in range(bz):
+            for j in range(by):
+                for i in range(bx):
+                    off = np.array([cuts[0][i], cuts[1][j], cuts[2][k]], np.int32)
+                    end = np.array([cuts[0][i + 1], cuts[1][j + 1], cuts[2][k + 1]], np.int32)  # last vertex
+                    d = np.ascontiguousarray(vol.data[off[2]:end[2] + 1, off[1]:end[1] + 1, off[0]:end[0] + 1])
+                    bricks.append(Brick(d, off, cnt.copy(), org, sp, (org + off.astype(F) * sp).astype(F), (org + end.astype(F) * sp).astype(F)))
+    root = []  # per subgrid: its level-1 ancestor
+    for i, s in enumerate(vol.subgrids):
+        root.append(i if s.parent < 0 else root[s.parent])
+    home = {}
+    for i, s in enumerate(vol.subgrids):
+        if s.parent >= 0:
+            continue
+        lo, hi = np.asarray(s.lo, np.int64), np.asarray(s.lo, np.int64) + np.asarray(s.cells, np.int64)
+        for j, b in enumerate(bricks):
+            if (lo >= b.offset).all() and (hi <= b.offset.astype(np.int64) + b.counts - 1).all():
+                home[i] = j
+                break
+        else:
+            raise ValueError("split_amr_volume: level-1 subgrid %d (cells %s to %s) straddles a cut of %d x %d x %d bricks" % (i, lo.tolist(), hi.tolist(), bx, by, bz))
+    for j, b in enumerate(bricks):
+        new = {}
+        for i, s in enumerate(vol.subgrids):
+            if home[root[i]] != j:
+                continue
+            new[i] = len(b.subgrids)
+            b.subgrids.append(Subgrid(-1 if s.parent < 0 else new[s.parent], s.ratio, s.lo, s.cells, s.data))
+    return bricks

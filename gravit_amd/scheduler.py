@@ -559,7 +559,7 @@ class DomainTracer:
 
 class VolumeTracer:
     """Tracer<ImageScheduler> over the bricks of one volume instance (gvt_hip_volume_frame): bricks = scenes.split_volume(...) (or one
-    VolumeData), m = the instance's matrix (None: identity).  The world box of a brick is its box under m (scenes.instance_bbox).
+    VolumeData), m = the instance's matrix (None: identity).  Bricks may carry AMR subgrids (scenes.split_amr_volume, scenes.refine).  The world box of a brick is its box under m (scenes.instance_bbox).
     native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width)."""
 
     def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False):
@@ -659,7 +659,9 @@ class VolumeTracer:
 
     def stats(self):
         infos = [a.info() for a in self.adapters]
-        return {"adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
+        amr = [a.amr_info() for a in self.adapters]
+        return {"samples_refined": sum(i["samples_refined"] for i in amr), "amr_marches": sum(i["amr_marches"] for i in amr),
+                "adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
                 "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in self.adapters)}
 
 

@@ -564,6 +564,59 @@ int gvt_hip_volume_frame_clipped(gvt_hip_top *, gvt_hip_volume *const *volumes, 
  * without volume (front all zero) becomes min(back, 1) exactly.  Sizes must agree, front and back must not be NULL (GVT_HIP_ERR_INVALID). */
 int gvt_hip_fb_composite_over(gvt_hip_fb *front, const gvt_hip_fb *back, const gvt_hip_depth *depth);
 
+/* ---- AMR volumes: nested refined subgrids inside a brick (Volume::griddata / AddAMRGrid / is_AMR, render/data/primitives/Volume.h:40-58,
+ *      101-135; api::createVolume(name, amr) and api::addAmrSubgrid, api.cpp:543-612; one domain = one level-0 grid with its descendants,
+ *      all handed to one trace call, adapter/galaxy/PVolAdapter.cpp:74-107) ----
+ * A volume (a level-0 brick) holds a set of subgrids, a tree: entry i refines a box of cells of its parent -- the brick's own grid
+ * (parent -1) or an EARLIER entry -- `ratio` times per axis.  tests/volume_amr_checker.py restates what follows in numpy.
+ * Everything of the volume contract stays: ONE lattice per ray for all levels, t_k = k * dt with dt = min(level-0 spacing) /
+ * sampling_rate; a sample is owned by the brick whose level-0 cell floor((p - origin) / spacing) it lies in.  What is new is WHICH CELL
+ * IS INTERPOLATED.  With g = (p - origin) / spacing, fl = floor(g) and f = g - fl as ever, start at the level-0 grid with the cell
+ * ci = (int)fl (a global index) and the fractions f.  While a subgrid S of the current grid covers ci (S.lo[a] <= ci[a] < S.lo[a] +
+ * S.cells[a] on every axis; there is at most one), per axis:
+ *   h = f * (float)ratio;   j = (int)floorf(h);   ci = (ci - S.lo) * ratio + j;   f = h - (float)j;   the current grid = S
+ * The final grid's cell ci, its 8 vertices and f go through the same trilinear expression, table look-up and compositing as before.
+ * Every step of the descent is exact in float32 (f < 1, the ratio a power of two), so the choice between parent and child at a shared
+ * face is made on integer cell indices and cannot differ between bricks, runs or skip modes.  Level-0 vertices strictly inside a
+ * subgrid's footprint (and a subgrid's strictly inside a child's) are never read by the march.
+ * MACRO CELLS.  The grid of level-0 macro cells (8^3 level-0 cells) stays.  The value range of a macro cell, and its not-finite flag, is
+ * the union over every vertex whose position lies in the macro cell's closed box: the level-0 vertices, covered ones included, and the
+ * vertices of every subgrid of every level (subgrids are cell-aligned, so per subgrid these form an index rectangle).  The empty rule of
+ * _set_transfer is applied to that union, so skipping stays exact (GVT_HIP_VOLUME_NO_SKIP gives the same bits), and
+ * gvt_hip_volume_info's n_blocks_empty, value_min and value_max follow the union.
+ * DEVIATIONS.  One lattice for all levels: a refined region is not sampled more densely by itself (raise sampling_rate; the opacity
+ * correction keeps the look).  The field is discontinuous across coarse-fine faces (no ghost or blend cells), as a cell-wise AMR
+ * sampler's is.  A level-1 subgrid must lie inside one brick: the caller cuts it otherwise.
+ * OUT OF SCOPE, refused.  A volume that has subgrids takes no surfaces, no gradient shading and no in-place update: on it
+ * _set_surfaces with any surface, _set_shading with GVT_HIP_VOLUME_SHADE_GRADIENT and _update_samples / _update_samples_typed return
+ * GVT_HIP_ERR_INVALID and change nothing.  A new time step of an AMR volume is _set_subgrids with n = 0, _update_samples and
+ * _set_subgrids again, or a new volume.  The clipped march (GVT_HIP_RAY_CLIP, gvt_hip_volume_frame_clipped) works on AMR volumes. */
+#define GVT_HIP_VOLUME_MAX_SUBGRIDS 4096
+#define GVT_HIP_VOLUME_MAX_LEVELS 4          /* level 0 and up to three levels of subgrids */
+typedef struct gvt_hip_subgrid {
+  int32_t parent;    /* -1: the brick's own grid; else the index of an EARLIER entry of the same array */
+  int32_t ratio;     /* 2, 4 or 8: cells per parent cell and axis (a power of two keeps every coordinate of the descent exact) */
+  int32_t lo[3];     /* first parent cell covered; for parent -1 a GLOBAL cell index (as `offset` is), else a cell of the parent subgrid */
+  int32_t cells[3];  /* parent cells covered per axis, >= 1 */
+} gvt_hip_subgrid;    /* vertices: cells[a] * ratio + 1 per axis, float32, x fastest; vertex 0 sits on the parent's vertex lo; spacing = parent's / ratio */
+/* Replaces the volume's whole set of subgrids (n == 0 removes it: the plain volume again, through the kernels it launched before).
+ * samples[i]: the vertices of grids[i], in host memory or, with flags = GVT_HIP_VOLUME_DEVICE, in device memory (they never visit the
+ * host); the volume keeps copies of its own.  Legal before and after _set_transfer; waits for the calling context's stream first, as
+ * _set_transfer does; the macro cells' ranges are rebuilt on the device (the min / max / not-finite rule of the level-0 ranges).
+ * GVT_HIP_ERR_INVALID, the volume exactly as it was: a null argument; a volume that is not GVT_HIP_VOXEL_F32; a ratio other than 2, 4
+ * or 8; a parent outside [-1, own index); cells < 1 on an axis; a box that leaves its parent's cells (for parent -1: the cells the brick
+ * owns, [offset, offset + counts - 1)); two subgrids of one parent that share a cell; more than GVT_HIP_VOLUME_MAX_LEVELS levels;
+ * n < 0 or n > GVT_HIP_VOLUME_MAX_SUBGRIDS; an unknown flag bit; a subgrid of 2^24 or more vertices on an axis or 2^32 - 1 or more in
+ * all; a volume that has surfaces or GVT_HIP_VOLUME_SHADE_GRADIENT. */
+int gvt_hip_volume_set_subgrids(gvt_hip_volume *, const gvt_hip_subgrid *grids, const float *const *samples, int n, int flags);
+typedef struct gvt_hip_volume_amr_info {
+  int32_t n_subgrids, n_levels; /* n_levels: level 0 and the deepest subgrid's (1 without subgrids) */
+  uint64_t subgrid_bytes;       /* device memory of the subgrids' samples and tables */
+  uint64_t samples_refined;     /* gathered samples whose final grid was a subgrid, so far */
+  uint64_t amr_marches;         /* marches that ran an AMR entry point, so far (0 on a volume that never had subgrids) */
+} gvt_hip_volume_amr_info;
+int gvt_hip_volume_get_amr_info(gvt_hip_volume *, gvt_hip_volume_amr_info *); /* synchronises */
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

@@ -22,6 +22,11 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
   python tools/volume_bench.py --shade       lit volumes: per grid size, table and bricking the frame unlit, lit by one light and lit by three
                                              (VolumeTracer.set_shading), frames alternating in one process on one tracer; with each the
                                              samples shaded per frame
+  python tools/volume_bench.py --amr         AMR volumes: 1080p frames of the 256^3 noise grid at rate 2 under the "thin" table, frames
+                                             alternating in one process: (a) the plain volume, (b) the same with an empty set of subgrids
+                                             (the plain path), (c) one ratio-2 subgrid over the central eighth, (d) as (c) plus a ratio-4
+                                             child over the subgrid's central eighth; then (e) the uniform 512^3 grid (c) would need, for
+                                             memory and time beside it.  --sizes N: another level-0 size ((e) is 2 N)
 """
 import argparse
 import json
@@ -204,6 +209,53 @@ def run_mixed(n, split, steps, warmup, rate, vol, dtype="f32"):
     return out
 
 
+def run_amr(n, steps, warmup, rate):
+    """Configurations (a)-(d) alternating on four tracers, then (e) on its own; one line per configuration."""
+    base = noise(n, "f32")
+    cells = n - 1
+    lo, ext = cells // 4, cells // 2  # the central eighth, in cells
+    vols = {"a_plain": base, "b_empty_set": scenes.VolumeData(base.data, base.origin, base.spacing)}
+    c = scenes.VolumeData(base.data, base.origin, base.spacing)
+    s0 = scenes.refine(c, (lo,) * 3, (ext,) * 3, 2, seed=1)
+    d = scenes.VolumeData(base.data, base.origin, base.spacing, list(c.subgrids))
+    scenes.refine(d, (ext // 2,) * 3, (ext,) * 3, 4, parent=s0, seed=2)  # (the subgrid has 2 * ext cells per axis)
+    vols["c_ratio2"], vols["d_ratio2_ratio4"] = c, d
+    cam, t = camera(), transfer("thin")
+    trs = {k: VolumeTracer(v, cam, t, sampling_rate=rate) for k, v in vols.items()}
+    trs["b_empty_set"].adapters[0].set_subgrids([])
+    ms = {k: [] for k in trs}
+    first = {}
+    for i in range(warmup + steps):
+        for k, tr in trs.items():
+            if i == warmup:
+                first[k] = tr.stats()
+            ms[k].append(timed(tr.frame))
+    out = []
+    for k, tr in trs.items():
+        st, amr, v = tr.stats(), tr.adapters[0].amr_info(), ms[k][warmup:]
+        out.append({"mode": "amr", "config": k, "n": n, "sampling_rate": rate, "ms_median": med(v), "ms_min": round(min(v), 3), "ms_max": round(max(v), 3),
+                    "samples_per_frame": int((st["samples_marched"] - first[k]["samples_marched"]) / steps),
+                    "samples_refined_per_frame": int((st["samples_refined"] - first[k]["samples_refined"]) / steps),
+                    "amr_marches_per_frame": (st["amr_marches"] - first[k]["amr_marches"]) / steps, "n_subgrids": amr["n_subgrids"], "n_levels": amr["n_levels"],
+                    "device_mb": round((4.0 * n ** 3 + amr["subgrid_bytes"]) / 1e6, 1), "lit_pixels": int((tr.framebuffer(False)[..., 3] > 0).sum())})
+    for r in out:
+        r["vs_plain"] = round(r["ms_median"] / out[0]["ms_median"], 4)
+    for tr in trs.values():
+        for a in tr.adapters:
+            a.close()
+    del trs, vols, c, d
+    big = noise(2 * n, "f32")  # (e): the whole domain at the subgrid's resolution
+    big.spacing = np.full(3, F(1.0 / (2 * n - 1)), F)
+    tr = VolumeTracer(big, cam, t, sampling_rate=rate)
+    v = [timed(tr.frame) for _ in range(warmup + steps)][warmup:]
+    st = tr.stats()
+    out.append({"mode": "amr", "config": "e_uniform_2n", "n": 2 * n, "sampling_rate": rate, "ms_median": med(v), "ms_min": round(min(v), 3), "ms_max": round(max(v), 3),
+                "samples_per_frame": int(st["samples_marched"] / (warmup + steps)), "samples_refined_per_frame": 0, "amr_marches_per_frame": 0.0, "n_subgrids": 0,
+                "n_levels": 1, "device_mb": round(4.0 * (2 * n) ** 3 / 1e6, 1), "lit_pixels": int((tr.framebuffer(False)[..., 3] > 0).sum()),
+                "vs_plain": round(med(v) / out[0]["ms_median"], 4)})
+    return out
+
+
 def run_update(n, device, steps, warmup, recreate_only, dtype="f32"):
     """Two time steps of the n^3 noise grid, pushed alternately into one brick under the sparse table."""
     from gravit_amd.adapter import HipVolumeAdapter
@@ -265,6 +317,7 @@ def main():
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--shade", action="store_true")
+    ap.add_argument("--amr", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     a = ap.parse_args()
@@ -276,6 +329,12 @@ def main():
         for n in a.sizes:
             for device in (False, True):
                 r = run_update(n, device, a.steps, a.warmup, a.recreate_only, a.dtype)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+        a.sizes = []
+    if a.amr:
+        for n in ([256] if a.sizes == [256, 512] else a.sizes):
+            for r in run_amr(n, a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate):
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
         a.sizes = []
