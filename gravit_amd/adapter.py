@@ -65,6 +65,26 @@ class RayQueue:
         return out
 
 
+def queues_export_wire(queues, dptr, cap):
+    """gvt_hip_queues_export_wire: the rays of `queues` (RayQueue), in that order, as 80-byte wire rays at device address dptr (room
+    for cap rays), in one launch; the queues are cleared.  Returns the rays per queue.  Too small a capacity raises and changes nothing."""
+    n = len(queues)
+    arr = (C.c_void_p * max(1, n))(*[q.h for q in queues])
+    counts = (C.c_uint64 * max(1, n))()
+    total = C.c_uint64(0)
+    capi.check(capi.load().gvt_hip_queues_export_wire(arr, n, C.c_void_p(dptr), cap, counts, C.byref(total)), "gvt_hip_queues_export_wire")
+    return [int(c) for c in counts[:n]]
+
+
+def queues_append_wire(queues, dptr, counts):
+    """gvt_hip_queues_append_wire: consecutive runs of counts[i] wire rays at device address dptr appended to queues[i], their state
+    kept, in one launch."""
+    n = len(queues)
+    arr = (C.c_void_p * max(1, n))(*[q.h for q in queues])
+    cnt = (C.c_uint64 * max(1, n))(*[int(c) for c in counts])
+    capi.check(capi.load().gvt_hip_queues_append_wire(arr, n, C.c_void_p(dptr), cnt), "gvt_hip_queues_append_wire")
+
+
 class HipMeshAdapter:
     """gvt::render::adapter::hip::data::HipMeshAdapter -- drop-in for EmbreeMeshAdapter.
 
@@ -604,6 +624,12 @@ class HipVolumeAdapter:
         n = C.c_uint64(0)
         capi.check(self.lib.gvt_hip_volume_get_shaded(self.h, C.byref(n)), "gvt_hip_volume_get_shaded")
         return n.value
+
+    def march_queue(self, queue, minv, may_clip=False):
+        """gvt_hip_volume_march_queue: Adapter::trace on a device-resident RayQueue, in place and without a host wait; the rays keep
+        their flags for the volume shuffle.  may_clip: the queue may hold rays that carry RAY_CLIP."""
+        capi.check(self.lib.gvt_hip_volume_march_queue(self.h, queue.h, capi.ptr(capi.f32(minv, 16)), capi.MARCH_MAY_CLIP if may_clip else 0),
+                   "gvt_hip_volume_march_queue")
 
     def trace(self, rays, m, minv, begin=0, end=0):
         """OSPRayAdapter::trace: every ray of rays[begin, end) comes back marched through the brick, with its flags."""

@@ -40,6 +40,7 @@ SYMBOLS = [
     "gvt_hip_depth_create", "gvt_hip_depth_destroy", "gvt_hip_depth_clear", "gvt_hip_depth_upload", "gvt_hip_depth_download", "gvt_hip_depth_render",
     "gvt_hip_volume_frame_clipped", "gvt_hip_fb_composite_over",
     "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
+    "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
 ]
 
 
@@ -94,6 +95,8 @@ class VolumeAmrInfo(C.Structure):
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10
 RAY_SIDES = 0x20  # the ray's t field holds the surface sides of the sample in t_min
 RAY_CLIP = 0x40  # the march takes only the samples with k * dt < the ray's t_max
+MARCH_MAY_CLIP = 1  # gvt_hip_volume_march_queue: the queue may hold rays that carry RAY_CLIP
+WIRE_MAX_QUEUES = 256  # queues of one gvt_hip_queues_export_wire / _append_wire call
 VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
@@ -143,6 +146,10 @@ def load():
         lib.gvt_hip_volume_get_voxel_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_set_subgrids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         lib.gvt_hip_volume_get_amr_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_march_queue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.gvt_hip_volume_camera_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_queues_export_wire.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_queues_append_wire.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         lib.gvt_hip_depth_create.argtypes = [C.c_int, C.c_int]
         lib.gvt_hip_depth_clear.argtypes = [C.c_void_p]
         lib.gvt_hip_depth_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]

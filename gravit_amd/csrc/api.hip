@@ -132,6 +132,8 @@ extern "C" void gvt_hip_ctx_destroy(gvt_hip_ctx *c) {
     hipSetDevice(C->device);
     for (int k = 0; k < SCRATCH_COUNT; k++) if (C->scratch[k]) hipFree(C->scratch[k]);
     hipFree(C->d_spill); hipFree(C->d_counters); hipHostFree(C->h_pinned);
+    if (C->h_wire) hipHostFree(C->h_wire);
+    if (C->wire_ev) hipEventDestroy(C->wire_ev);
     hipStreamDestroy(C->own_stream);
   }
   delete C;

@@ -23,6 +23,74 @@ __global__ __launch_bounds__(256) void k_planes_to_aos(RayPlanes src, unsigned l
   d[4] = make_float4(__uint_as_float(src.p4 ? src.p4[off + i] : 0u), __uint_as_float(src.p5 ? src.p5[3 * (off + i)] : 0u), __uint_as_float(src.p5 ? src.p5[3 * (off + i) + 1] : 0u),
                      __uint_as_float(src.p5 ? src.p5[3 * (off + i) + 2] : 0u));
 }
+// ---- the same two conversions for ALL the queues of one exchange message in one launch (gvt_hip_queues_export_wire / _append_wire).
+// Ray i of the concatenation belongs to queue s = the last one with begin[s] <= i (begin: n + 1 prefix sums, begin[n] = the total; empty
+// queues repeat a value and are never chosen), where it is slot off[s] + (i - begin[s]).  Absent p4 / p5 planes read as 0 and are not
+// written, as above.  The launch also writes the queues' count words (fill[s]; one thread per queue), so a message is one launch.
+struct WireTable {
+  const QueueDesc *q;
+  const unsigned *begin; // n + 1
+  const unsigned *off;   // n: export 0, append the queue's fill before the call
+  const unsigned *fill;  // n: the count word after the call (export 0, append off + the run)
+  int n;
+};
+#define WIRE_BLOCK 256
+__device__ __forceinline__ int wire_queue_of(const WireTable &W, unsigned i) {
+  int lo = 0, hi = W.n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (W.begin[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ void wire_set_counts(const WireTable &W) {
+  for (unsigned s = blockIdx.x * WIRE_BLOCK + threadIdx.x; s < (unsigned)W.n; s += gridDim.x * WIRE_BLOCK)
+    if (W.begin[s + 1] != W.begin[s]) *W.q[s].count = W.fill[s]; // (a queue without rays in the message keeps its word)
+}
+// Export: k_planes_to_aos' pattern -- coalesced plane reads, five 16-byte stores per lane at an 80-byte stride.  Staging a wave's 5120
+// contiguous wire bytes through LDS so that every store covers 1 KiB was measured and is 15 % slower here (EXPERIMENTS.md, "wire pair").
+__global__ __launch_bounds__(WIRE_BLOCK) void k_queues_to_wire(WireTable W, unsigned total, float4 *__restrict__ dst) {
+  wire_set_counts(W);
+  const unsigned i = blockIdx.x * WIRE_BLOCK + threadIdx.x;
+  if (i >= total) return;
+  const int s = wire_queue_of(W, i);
+  const QueueDesc Q = W.q[s];
+  const RayPlanes P = make_planes(Q.planes, Q.cap);
+  const size_t j = (size_t)W.off[s] + (i - W.begin[s]);
+  float4 *d = dst + (size_t)5 * i;
+  d[0] = P.p0[j]; d[1] = P.p1[j]; d[2] = P.p2[j]; d[3] = P.p3[j];
+  d[4] = make_float4(__uint_as_float(P.p4 ? P.p4[j] : 0u), __uint_as_float(P.p5 ? P.p5[3 * j] : 0u), __uint_as_float(P.p5 ? P.p5[3 * j + 1] : 0u),
+                     __uint_as_float(P.p5 ? P.p5[3 * j + 2] : 0u));
+}
+// Append: the other way round the staging pays (25 % less kernel time than five 16-byte loads per lane at an 80-byte stride): a wave's
+// 64 rays are 5120 contiguous wire bytes, read as five loads of 1 KiB into the wave's part of LDS, then every lane takes its ray's five
+// pieces from there and writes the planes coalesced.
+__global__ __launch_bounds__(WIRE_BLOCK) void k_wire_to_queues(const float4 *__restrict__ src, unsigned total, WireTable W) {
+  __shared__ float4 sh[WIRE_BLOCK * 5];
+  wire_set_counts(W);
+  const unsigned i = blockIdx.x * WIRE_BLOCK + threadIdx.x;
+  const unsigned lane = threadIdx.x & 63u;
+  float4 *w = sh + (size_t)(threadIdx.x - lane) * 5; // the wave's 320 pieces
+  const unsigned base = i - lane;                    // the wave's first ray
+  if (base < total) {
+    const unsigned m = min(64u, total - base) * 5u;
+    for (unsigned k = 0; k < 5; k++) {
+      const unsigned x = k * 64u + lane;
+      if (x < m) w[x] = src[(size_t)5 * base + x];
+    }
+  }
+  __syncthreads();
+  if (i >= total) return;
+  float4 r[5];
+  for (int k = 0; k < 5; k++) r[k] = w[lane * 5 + k];
+  const int s = wire_queue_of(W, i);
+  const QueueDesc Q = W.q[s];
+  const RayPlanes P = make_planes(Q.planes, Q.cap);
+  const size_t j = (size_t)W.off[s] + (i - W.begin[s]);
+  P.p0[j] = r[0]; P.p1[j] = r[1]; P.p2[j] = r[2]; P.p3[j] = r[3];
+  if (P.p4) P.p4[j] = __float_as_uint(r[4].x); // the rays are this library's own: their state is kept (k_aos_to_planes' keep_state)
+  if (P.p5) { P.p5[3 * j] = __float_as_uint(r[4].y); P.p5[3 * j + 1] = __float_as_uint(r[4].z); P.p5[3 * j + 2] = __float_as_uint(r[4].w); }
+}
 __global__ __launch_bounds__(256) void k_od_to_planes(const float *__restrict__ org, const float *__restrict__ dir, unsigned n, RayPlanes dst) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

@@ -46,6 +46,8 @@ enum ScratchSlot {
   SCR_VOL_RANGES,  // the macro cells' value ranges of the brick being created or updated, on their way to the host (volume.hip volume_ranges)
   SCR_BUILD,       // the builder's and the refit's temporaries (lbvh.hip); released again beyond 1 GiB
   SCR_HOP,         // merged chains with hops: the instance every ray is in now
+  SCR_WIRE_TABLE,  // the queue table of a batched wire conversion (trace.hip wire_table)
+  SCR_VOL_KEEP,    // the keep mask of gvt_hip_volume_camera_filter on the device (volume.hip)
   SCRATCH_COUNT
 };
 struct Knobs {
@@ -144,6 +146,10 @@ struct Ctx : Knobs {
   unsigned *d_counters = nullptr; // CW_COUNT device counter words (enum CounterWord, gvt_device.h)
   // pinned host scratch for small read-backs
   unsigned *h_pinned = nullptr;
+  // pinned staging of the batched wire conversions' queue table (trace.hip wire_table) and the event behind its last upload
+  void *h_wire = nullptr;
+  hipEvent_t wire_ev = nullptr;
+  bool wire_busy = false;
   // grow-only device scratch arenas (never freed inside hot calls)
   void *scratch[SCRATCH_COUNT] = { nullptr };
   size_t scratch_bytes[SCRATCH_COUNT] = { 0 };

@@ -722,3 +722,101 @@ int set_device_u32(unsigned *p, unsigned v) {
   HIPCHK(hipGetLastError());
   return 0;
 }
+
+// ---- the batched wire pair: all the queues of one exchange message through ONE launch (convert.inc k_queues_to_wire / k_wire_to_queues)
+#define WIRE_MAX_QUEUES 256
+namespace {
+// The launch's queue table: built in the context's pinned staging block (one block: the event says when its last upload has been read),
+// copied to the context's device copy on the stream.  runs[i]: rays of queue i in the message; append: they go behind the queue's fill
+int wire_table(gvt_hip_queue *const *queues, size_t n, const uint64_t *runs, bool append, WireTable &W) {
+  Ctx &C = gctx();
+  const size_t o_begin = sizeof(QueueDesc) * n, o_off = o_begin + sizeof(unsigned) * (n + 1), o_fill = o_off + sizeof(unsigned) * n,
+               bytes = o_fill + sizeof(unsigned) * n;
+  if (!C.h_wire) {
+    HIPCHK(hipHostMalloc(&C.h_wire, sizeof(QueueDesc) * WIRE_MAX_QUEUES + sizeof(unsigned) * (3 * WIRE_MAX_QUEUES + 1), hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&C.wire_ev, hipEventDisableTiming));
+  }
+  char *d = (char *)scratch_get(SCR_WIRE_TABLE, bytes);
+  if (!d) return GVT_HIP_ERR_DEVICE;
+  if (C.wire_busy) HIPCHK(hipEventSynchronize(C.wire_ev));
+  char *h = (char *)C.h_wire;
+  QueueDesc *q = (QueueDesc *)h;
+  unsigned *begin = (unsigned *)(h + o_begin), *off = (unsigned *)(h + o_off), *fill = (unsigned *)(h + o_fill);
+  unsigned at = 0;
+  for (size_t i = 0; i < n; i++) {
+    q[i].planes = queues[i]->d_planes; q[i].cap = queues[i]->cap; q[i].count = queues[i]->d_count; q[i].keep = 0u;
+    begin[i] = at;
+    off[i] = append ? (unsigned)queues[i]->size : 0u;
+    fill[i] = append ? (unsigned)(queues[i]->size + runs[i]) : 0u;
+    at += (unsigned)runs[i];
+  }
+  begin[n] = at;
+  HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, C.stream));
+  HIPCHK(hipEventRecord(C.wire_ev, C.stream));
+  C.wire_busy = true;
+  W.q = (const QueueDesc *)d; W.begin = (const unsigned *)(d + o_begin); W.off = (const unsigned *)(d + o_off); W.fill = (const unsigned *)(d + o_fill);
+  W.n = (int)n;
+  return 0;
+}
+} // namespace
+
+extern "C" int gvt_hip_queues_export_wire(gvt_hip_queue *const *queues, size_t n, gvt_hip_ray *dst_device, size_t cap_rays, uint64_t *counts_out,
+                                          uint64_t *total_out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!queues || !total_out || n < 1 || n > WIRE_MAX_QUEUES) { set_error("queues_export_wire: null argument or %zu queues (1..%d)", n, WIRE_MAX_QUEUES); return GVT_HIP_ERR_INVALID; }
+  uint64_t runs[WIRE_MAX_QUEUES];
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!queues[i]) { set_error("queues_export_wire: queue %zu is null", i); return GVT_HIP_ERR_INVALID; }
+    runs[i] = queues[i]->size;
+    total += runs[i];
+  }
+  *total_out = total;
+  if (counts_out) std::copy(runs, runs + n, counts_out);
+  if (total > cap_rays) { set_error("queues_export_wire: %llu rays, capacity %zu", (unsigned long long)total, cap_rays); return GVT_HIP_ERR_CAPACITY; }
+  if (!total) return 0;
+  if (!dst_device) { set_error("queues_export_wire: null destination"); return GVT_HIP_ERR_INVALID; }
+  if (total >= 0xffffffffull) { set_error("queues_export_wire: %llu rays exceed the 32-bit ray index", (unsigned long long)total); return GVT_HIP_ERR_INVALID; }
+  Ctx &C = gctx();
+  WireTable W;
+  int rc = wire_table(queues, n, runs, false, W);
+  if (rc) return rc;
+  {
+    ProfScope ps(KC_CONVERT);
+    const unsigned blocks = (unsigned)((total + WIRE_BLOCK - 1) / WIRE_BLOCK);
+    k_queues_to_wire<<<blocks, WIRE_BLOCK, 0, C.stream>>>(W, (unsigned)total, (float4 *)dst_device);
+  }
+  HIPCHK(hipGetLastError());
+  for (size_t i = 0; i < n; i++) queues[i]->size = 0; // (the launch cleared the count words)
+  HIPCHK(hipStreamSynchronize(C.stream));
+  return 0;
+}
+
+extern "C" int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt_hip_ray *src_device, const uint64_t *counts) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!queues || !counts || n < 1 || n > WIRE_MAX_QUEUES) { set_error("queues_append_wire: null argument or %zu queues (1..%d)", n, WIRE_MAX_QUEUES); return GVT_HIP_ERR_INVALID; }
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!queues[i]) { set_error("queues_append_wire: queue %zu is null", i); return GVT_HIP_ERR_INVALID; }
+    for (size_t k = 0; k < i && counts[i]; k++)
+      if (queues[k] == queues[i] && counts[k]) { set_error("queues_append_wire: queue %zu appears twice", i); return GVT_HIP_ERR_INVALID; }
+    total += counts[i];
+  }
+  if (!total) return 0;
+  if (!src_device) { set_error("queues_append_wire: null source"); return GVT_HIP_ERR_INVALID; }
+  if (total >= 0xffffffffull) { set_error("queues_append_wire: %llu rays exceed the 32-bit ray index", (unsigned long long)total); return GVT_HIP_ERR_INVALID; }
+  int rc;
+  for (size_t i = 0; i < n; i++)
+    if (counts[i] && (rc = queue_reserve(queues[i], queues[i]->size + counts[i]))) return rc;
+  Ctx &C = gctx();
+  WireTable W;
+  if ((rc = wire_table(queues, n, counts, true, W))) return rc;
+  {
+    ProfScope ps(KC_CONVERT);
+    const unsigned blocks = (unsigned)((total + WIRE_BLOCK - 1) / WIRE_BLOCK);
+    k_wire_to_queues<<<blocks, WIRE_BLOCK, 0, C.stream>>>((const float4 *)src_device, (unsigned)total, W);
+  }
+  HIPCHK(hipGetLastError());
+  for (size_t i = 0; i < n; i++) queues[i]->size += counts[i];
+  return 0;
+}

@@ -12,6 +12,9 @@
 //   k_volume_march_amr / k_amr_ranges       AMR volumes (Volume::AddAMRGrid): nested refined subgrids inside a brick, volume_amr.inc
 //   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
 //                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
+//   gvt_hip_volume_march_queue / _camera_filter   the Domain scheduler's steps over bricks spread over ranks (algorithm/DomainTracer.h:148-326): the march
+//                                           on a device queue, and the camera step with shuffleDropRays' keep mask (k_vol_classify<MASK>); the
+//                                           exchange's batched wire conversions are beside k_planes_to_aos (convert.inc, trace.hip)
 // The contract (lattice, ownership, evaluation order, flags) is stated in include/gvt_hip.h; tests/volume_checker.py restates it in numpy.
 #include <algorithm>
 #include <cmath>
@@ -541,9 +544,12 @@ __device__ inline int vol_next(const TopDev &T, int from, const float o[3], cons
   return next;
 }
 
+// MASK (gvt_hip_volume_camera_filter, from < 0): a camera ray whose first brick b has keep[b] == 0 is dropped (shuffleDropRays: b's owner
+// generates the same ray); the unmasked instantiation is the kernel as it was and never reads keep
+template <bool MASK>
 __global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigned n, TopDev T, int n_dest, int from, int *__restrict__ next_out,
                                                             unsigned *__restrict__ blk_cnt, float *__restrict__ fb, unsigned n_pix,
-                                                            const float *__restrict__ clip_plane, unsigned n_clip) {
+                                                            const float *__restrict__ clip_plane, unsigned n_clip, const unsigned char *__restrict__ keep) {
   __shared__ unsigned sh[VOL_DEST_MAX];
   for (int j = threadIdx.x; j < n_dest; j += VOL_BLOCK) sh[j] = 0u;
   __syncthreads();
@@ -561,7 +567,10 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_vol_classify(RayPlanes q, unsigne
       t_clip = id < n_clip ? clip_plane[id] : INFINITY;
       clip = t_clip < INFINITY;
     }
-    if (from < 0) next = vol_next(T, -1, o, d, a.w, clip, t_clip); // camera rays: no deposit where they meet no brick
+    if (from < 0) { // camera rays: no deposit where they meet no brick
+      next = vol_next(T, -1, o, d, a.w, clip, t_clip);
+      if (MASK && next >= 0 && !keep[next]) next = -1;
+    }
     else if (depth & GVT_HIP_RAY_OPAQUE) deposit = true;
     else if (depth & GVT_HIP_RAY_BOUNDARY) {
       next = vol_next(T, from, o, d, a.w, clip, t_clip);
@@ -940,7 +949,9 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16], boo
 
 // consumes q_in; one host wait (two where a destination queue has to grow to its exact need first)
 // clip (from < 0 only): the depth plane the camera's rays are clipped at
-int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *clip = nullptr) {
+// keep (from < 0 only): the host's keep mask of gvt_hip_volume_camera_filter, one byte per brick, or null
+int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *clip = nullptr,
+                        const uint8_t *keep = nullptr) {
   Ctx &C = gctx();
   hipStream_t st = C.stream;
   const size_t n = q_in->size, nI = T->n;
@@ -950,9 +961,14 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
   unsigned *d_blk = (unsigned *)scratch_get(SCR_BLOCK_COUNTS, sizeof(unsigned) * (nI ? nI : 1) * n_blk);
   unsigned *d_ovf = (unsigned *)scratch_get(SCR_VOL_OVF, sizeof(unsigned));
   if (!d_next || !d_blk || !d_ovf) return GVT_HIP_ERR_DEVICE;
+  unsigned char *d_keep = nullptr;
+  if (keep && from < 0 && nI) {
+    if (!(d_keep = (unsigned char *)scratch_get(SCR_VOL_KEEP, nI))) return GVT_HIP_ERR_DEVICE;
+    HIPCHK(hipMemcpyAsync(d_keep, keep, nI, hipMemcpyHostToDevice, st)); // (the caller's mask outlives the call: the shuffle ends with a host wait)
+  }
   bool roomy = true;
   for (size_t i = 0; i < nI; i++) {
-    if ((int)i == from) continue;
+    if ((int)i == from || (d_keep && !keep[i])) continue; // (a masked brick receives nothing)
     if (nI <= 16 && queues[i]->cap < queues[i]->size + n) { // few bricks: worst-case room, so that the round has one host wait
       int rc = queue_reserve(queues[i], queues[i]->size + n);
       if (rc) return rc;
@@ -976,8 +992,9 @@ int shuffle_volume_impl(gvt_hip_top *T, gvt_hip_queue *q_in, int from, gvt_hip_q
   const unsigned n_clip = clip_plane ? (unsigned)(clip->w * clip->h) : 0u;
   {
     ProfScope ps(KC_SHUFFLE);
-    k_vol_classify<<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, T->dev(), (int)nI, from, d_next, d_blk, fb ? fb->d_rgba : nullptr,
-                                                fb ? (unsigned)(fb->w * fb->h) : 0u, clip_plane, n_clip);
+    if (d_keep) k_vol_classify<true><<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, T->dev(), (int)nI, from, d_next, d_blk, nullptr, 0u, clip_plane, n_clip, d_keep);
+    else k_vol_classify<false><<<n_blk, VOL_BLOCK, 0, st>>>(P, (unsigned)n, T->dev(), (int)nI, from, d_next, d_blk, fb ? fb->d_rgba : nullptr,
+                                                       fb ? (unsigned)(fb->w * fb->h) : 0u, clip_plane, n_clip, nullptr);
     if (nI) k_dest_scan<VOL_BLOCK><<<(unsigned)nI, VOL_BLOCK, 0, st>>>(d_blk, n_blk, (const QueueDesc *)T->d_qdesc, T->d_hist);
   }
   HIPCHK(hipGetLastError());
@@ -1291,6 +1308,37 @@ extern "C" int gvt_hip_shuffle_volume(gvt_hip_top *T, gvt_hip_queue *q_in, int f
   return shuffle_volume_impl(T, q_in, from, queues, fb);
 }
 
+// generateRays (ImageTracer.h:137), then every camera ray into the brick it enters first: the camera step of gvt_hip_volume_frame and the
+// whole of gvt_hip_volume_camera_filter (keep: its mask).  The origins stay at the eye (gvt_hip_camera_filter would advance them into the
+// first box): a ray keeps one sample lattice from start to end
+static int volume_camera_step(gvt_hip_top *T, const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                              const uint8_t *keep) {
+  Ctx &C = gctx();
+  if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
+  gvt_hip_queue *q_cam = C.abi_qout; // (a staging list of the context: the camera's rays before they are distributed)
+  int rc;
+  if ((rc = gvt_hip_camera_generate_tiled(q_cam, cam->eye, cam->focus, cam->up, cam->fov, cam->width, cam->height, cam->samples, 0,
+                                          cam->jitter_window_size, 8))) return rc;
+  return shuffle_volume_impl(T, q_cam, -1, queues, fb, depth, keep);
+}
+
+extern "C" int gvt_hip_volume_camera_filter(gvt_hip_top *T, const gvt_hip_camera *cam, gvt_hip_queue *const *queues, const uint8_t *keep_mask) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!T || !cam || (T->n && !queues)) { set_error("volume_camera_filter: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (T->n > VOL_DEST_MAX) { set_error("volume_camera_filter: %zu bricks, at most %d", T->n, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
+  for (size_t i = 0; i < T->n; i++)
+    if (!queues[i]) { set_error("volume_camera_filter: queue %zu is null", i); return GVT_HIP_ERR_INVALID; }
+  return volume_camera_step(T, cam, queues, nullptr, nullptr, keep_mask);
+}
+
+extern "C" int gvt_hip_volume_march_queue(gvt_hip_volume *V, gvt_hip_queue *queue, const float minv[16], uint32_t flags) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !queue || !minv) { set_error("volume_march_queue: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (flags & ~(uint32_t)GVT_HIP_MARCH_MAY_CLIP) { set_error("volume_march_queue: unknown flag bits %u", flags); return GVT_HIP_ERR_INVALID; }
+  if (!V->has_tf) { set_error("volume_march_queue: the volume has no transfer function (gvt_hip_volume_set_transfer)"); return GVT_HIP_ERR_INVALID; }
+  return volume_march(V, queue, minv, (flags & GVT_HIP_MARCH_MAY_CLIP) != 0);
+}
+
 // gvt_hip_volume_frame and gvt_hip_volume_frame_clipped (depth: the plane the camera's rays are clipped at, or null)
 static int volume_frame_impl(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
                              gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
@@ -1307,17 +1355,10 @@ static int volume_frame_impl(gvt_hip_top *T, gvt_hip_volume *const *volumes, con
               cam->samples, cam->samples);
     return GVT_HIP_ERR_INVALID;
   }
-  Ctx &C = gctx();
-  if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
-  gvt_hip_queue *q_cam = C.abi_qout; // (a staging list of the context: the camera's rays before they are distributed)
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;                                                  // clearBuffer :142
   for (size_t i = 0; i < n_inst; i++) if ((rc = gvt_hip_queue_clear(queues[i]))) return rc;
-  // generateRays :137, then every camera ray into the brick it enters first.  The origins stay at the eye (gvt_hip_camera_filter would advance
-  // them into the first box): a ray keeps one sample lattice from start to end
-  if ((rc = gvt_hip_camera_generate_tiled(q_cam, cam->eye, cam->focus, cam->up, cam->fov, cam->width, cam->height, cam->samples, 0,
-                                          cam->jitter_window_size, 8))) return rc;
-  if ((rc = shuffle_volume_impl(T, q_cam, -1, queues, fb, depth))) return rc;
+  if ((rc = volume_camera_step(T, cam, queues, fb, depth, nullptr))) return rc;               // generateRays :137 + shuffleRays(rays, -1)
   uint64_t calls = 0;
   for (;;) {                                                                                   // :159-259
     int target = -1;

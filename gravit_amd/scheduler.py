@@ -401,18 +401,21 @@ class DomainTracer:
 
     def _complete_exchange(self, posted, counts):
         reqs, recv_bufs, _send_bufs = posted
-        B = self.backend
-        n_inst = len(self.owner)
         for req in reqs:
             req.wait()
         if self.on_cuda:
             self.torch.cuda.current_stream().synchronize()
-        for p, buf in recv_bufs.items():  # unpack into queue[q] (:466-481)
-            off = 0
-            for i in range(n_inst):
-                if self.owned[i] and counts[p][i]:
-                    B.append_wire(i, buf, off, int(counts[p][i]))
-                    off += int(counts[p][i])
+        for p, buf in recv_bufs.items():
+            self._unpack(buf, counts[p])
+
+    def _unpack(self, buf, counts_p):
+        """A received payload into queue[q] (:466-481): peer p's rays for this rank's instances lie in instance order."""
+        B = self.backend
+        off = 0
+        for i in range(len(self.owner)):
+            if self.owned[i] and counts_p[i]:
+                B.append_wire(i, buf, off, int(counts_p[i]))
+                off += int(counts_p[i])
 
     def _frame_overlapped(self):
         """The same frame with the ray exchange overlapped with traversal: every iteration all ranks exchange the outgoing counts (and
@@ -497,12 +500,8 @@ class DomainTracer:
                     req.wait()
             if self.on_cuda:
                 torch.cuda.current_stream().synchronize()
-            for p, buf in recv_bufs.items():  # unpack into queue[q] (:466-481)
-                off = 0
-                for i in range(n_inst):
-                    if self.owned[i] and counts[p][i]:
-                        B.append_wire(i, buf, off, int(counts[p][i]))
-                        off += int(counts[p][i])
+            for p, buf in recv_bufs.items():
+                self._unpack(buf, counts[p])
         return B
 
     render = __call__
@@ -566,7 +565,7 @@ class VolumeTracer:
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
-        from .scenes import instance_bbox, instance_matrices, mat_translate_scale
+        from .scenes import instance_matrices, mat_translate_scale
 
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         self.camera = camera
@@ -575,13 +574,7 @@ class VolumeTracer:
         self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native) for b in bricks]
         for a in self.adapters:
             a.set_transfer(tf)
-        boxes = []
-        for b in bricks:
-            lo = b.lo if hasattr(b, "lo") else np.asarray(b.origin, np.float32)
-            hi = b.hi if hasattr(b, "hi") else (np.asarray(b.origin, np.float32) + (b.counts - 1).astype(np.float32) * np.asarray(b.spacing, np.float32)).astype(np.float32)
-            boxes.append(instance_bbox(self.m, lo, hi))
-        self.inst_lo = np.array([b[0] for b in boxes], np.float32)
-        self.inst_hi = np.array([b[1] for b in boxes], np.float32)
+        self.inst_lo, self.inst_hi = _brick_boxes(bricks, self.m)
         self.n_inst = len(bricks)
         self.top = TopLevel(self.inst_lo, self.inst_hi)
         self.queues = [RayQueue() for _ in range(self.n_inst)]
@@ -663,6 +656,210 @@ class VolumeTracer:
         return {"samples_refined": sum(i["samples_refined"] for i in amr), "amr_marches": sum(i["amr_marches"] for i in amr),
                 "adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
                 "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in self.adapters)}
+
+
+def _brick_boxes(bricks, m):
+    """The world boxes of bricks under the instance matrix m, as VolumeTracer places them."""
+    from .scenes import instance_bbox
+
+    boxes = []
+    for b in bricks:
+        lo = b.lo if hasattr(b, "lo") else np.asarray(b.origin, np.float32)
+        hi = b.hi if hasattr(b, "hi") else (np.asarray(b.origin, np.float32) + (b.counts - 1).astype(np.float32) * np.asarray(b.spacing, np.float32)).astype(np.float32)
+        boxes.append(instance_bbox(m, lo, hi))
+    return np.array([b[0] for b in boxes], np.float32), np.array([b[1] for b in boxes], np.float32)
+
+
+class HipVolumeBackend:
+    """One rank's device state under the Domain scheduler over the bricks of one volume instance, with HipBackend's method names (the
+    loops of DomainTracer drive it).  Every brick has a top-level box and a queue here; only the owned ones (owned[i], None: all) have
+    an adapter.  The queue of a brick this rank does not own is its outgoing list to that brick's owner.  A ray that ends on this rank,
+    OPAQUE or EXTERNAL, deposits into this rank's framebuffer.  bricks, m, sampling_rate, skip, native: VolumeTracer's."""
+
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, owned=None):
+        from .adapter import HipVolumeAdapter
+        from .scenes import instance_matrices, mat_translate_scale
+
+        bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
+        self.camera = camera
+        self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
+        self.minv = instance_matrices(self.m)[0]
+        self.n_inst = len(bricks)
+        self.owned = [True] * self.n_inst if owned is None else [bool(o) for o in owned]
+        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native) if self.owned[i] else None for i, b in enumerate(bricks)]
+        for a in self.local_adapters():
+            a.set_transfer(tf)
+        self.inst_lo, self.inst_hi = _brick_boxes(bricks, self.m)
+        self.top = TopLevel(self.inst_lo, self.inst_hi)
+        self.queues = [RayQueue() for _ in range(self.n_inst)]
+        self.fb = FrameBuffer(camera.width, camera.height)
+        self.calls = 0
+
+    def local_adapters(self):
+        return [a for a in self.adapters if a is not None]
+
+    def _arr(self, xs):
+        import ctypes as C
+
+        return (C.c_void_p * max(1, len(xs)))(*[x.h for x in xs])
+
+    # ---- frame steps
+    def begin_frame(self):
+        self.fb.clear()
+        for q in self.queues:
+            q.clear()
+        self.calls = 0
+
+    def generate_and_filter(self, keep_mask=None):
+        """shuffleDropRays (DomainTracer.h:148-183): the camera's rays into the kept bricks they enter first (gvt_hip_volume_camera_filter)."""
+        import ctypes as C
+
+        from .adapter import camera_pod
+
+        pod = camera_pod(self.camera)
+        km = None if keep_mask is None else np.ascontiguousarray(keep_mask, dtype=np.uint8)
+        capi.check(capi.load().gvt_hip_volume_camera_filter(self.top.h, C.byref(pod), self._arr(self.queues), capi.ptr(km)), "gvt_hip_volume_camera_filter")
+
+    def queue_sizes(self):
+        return [len(q) for q in self.queues]
+
+    def trace_and_shuffle(self, inst):
+        """Adapter::trace on brick inst's queue, then shuffleRays(moved_rays, inst): onward rays into the next bricks' queues, local or
+        not; rays that end deposit here."""
+        self.adapters[inst].march_queue(self.queues[inst], self.minv)
+        self.calls += 1
+        capi.check(capi.load().gvt_hip_shuffle_volume(self.top.h, self.queues[inst].h, inst, self._arr(self.queues), self.fb.h), "gvt_hip_shuffle_volume")
+
+    # ---- exchange (the 80-byte wire image, all the queues of a message in one launch)
+    def export_wire(self, insts, torch, device):
+        """Concatenate the queues `insts` into one wire tensor [n, 20] f32 and clear them (gvt_hip_queues_export_wire)."""
+        from .adapter import queues_export_wire
+
+        total = sum(len(self.queues[i]) for i in insts)
+        buf = torch.empty((total, 20), dtype=torch.float32, device=device)
+        if insts:  # (one call: a top level holds at most capi.WIRE_MAX_QUEUES bricks)
+            queues_export_wire([self.queues[i] for i in insts], buf.data_ptr(), total)
+        return buf
+
+    def append_wire(self, insts, buf, off, counts):
+        """Consecutive runs of counts[k] rays of the wire tensor, from ray `off` on, appended to the queues insts[k], their state kept
+        (gvt_hip_queues_append_wire)."""
+        from .adapter import queues_append_wire
+
+        if insts:
+            queues_append_wire([self.queues[i] for i in insts], buf.data_ptr() + off * 80, counts)
+
+    def fb_tensor(self, torch, device):
+        """torch view of the framebuffer's device memory (un-clamped sums) for the composite."""
+        cam = self.camera
+
+        class _View:
+            __cuda_array_interface__ = {"shape": (cam.height * cam.width * 4,), "typestr": "<f4", "data": (self.fb.device_ptr(), False), "version": 2}
+
+        return torch.as_tensor(_View(), device=device)
+
+    def framebuffer(self, clamp=False):
+        return self.fb.download(clamp)
+
+    def sync(self):
+        capi.synchronize()
+
+    # ---- the volume's controls, on the owned bricks (VolumeTracer's)
+    def update(self, bricks):
+        """The next time step: the same bricking of the new data (all bricks given; the owned ones are updated in place)."""
+        bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
+        if len(bricks) != self.n_inst:
+            raise ValueError("HipVolumeBackend.update: %d bricks given, the volume has %d" % (len(bricks), self.n_inst))
+        mine = VolumeTracer._same_bricking(self.local_adapters(), [b for i, b in enumerate(bricks) if self.owned[i]])
+        for a, b in zip(self.local_adapters(), mine):
+            a.update_samples(b.data)
+        return self
+
+    def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
+        for a in self.local_adapters():
+            a.set_surfaces(isovalues, slices, opacity)
+        return self
+
+    def set_lights(self, lights, ka=0.4, kd=0.6):
+        for a in self.local_adapters():
+            a.set_lights(lights, ka, kd)
+        return self
+
+    def set_shading(self, on=True):
+        for a in self.local_adapters():
+            a.set_shading(on)
+        return self
+
+    def stats(self):
+        """VolumeTracer.stats() summed over the owned bricks (the counters run from the adapters' creation)."""
+        ads = self.local_adapters()
+        infos = [a.info() for a in ads]
+        amr = [a.amr_info() for a in ads]
+        return {"samples_refined": sum(i["samples_refined"] for i in amr), "amr_marches": sum(i["amr_marches"] for i in amr),
+                "adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in ads), "samples_marched": sum(i["samples_marched"] for i in infos),
+                "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in ads)}
+
+
+class VolumeDomainTracer(DomainTracer):
+    """Tracer<DomainScheduler> over the bricks of one volume spread over the ranks of a job: DomainTracer's BSP and overlapped loops
+    and its composite, over a HipVolumeBackend (or a backend with its method names: tests/volume_domain_backend.py).  owner[i] = the
+    rank that holds brick i.
+
+    With one sample per pixel rank 0's composited framebuffer equals VolumeTracer(...).frame()'s in every bit, for every owner map, world
+    size and both loops (include/gvt_hip.h, "volume domains across ranks"): a pixel has one ray, so one deposit, on the rank where the
+    ray ends; the sum-reduce and the rows_only rectangles add it to zeros."""
+
+    def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False):
+        from types import SimpleNamespace
+
+        self.overlap = overlap
+        self.scene = SimpleNamespace(camera=camera)  # (what the shared loops and the composite read of a scene)
+        self.camera = camera
+        self.owner = list(owner)
+        self.dist, self.torch, self.dev = dist, torch, comm_device
+        self.on_cuda = torch.device(comm_device).type == "cuda"
+        self.rank = dist.get_rank() if dist.is_initialized() else 0
+        self.world = dist.get_world_size() if dist.is_initialized() else 1
+        self.owned = [o == self.rank for o in self.owner]
+        self.backend = backend or HipVolumeBackend(bricks, camera, tf, m, sampling_rate, skip, native, self.owned)
+        self.rounds = 0
+        self.rays_sent = 0
+        self.adapter_calls = 0
+
+    def _unpack(self, buf, counts_p):
+        """A peer's payload into the owned bricks' queues: one batched append instead of one per brick."""
+        insts = [i for i in range(len(self.owner)) if self.owned[i] and counts_p[i]]
+        self.backend.append_wire(insts, buf, 0, [int(counts_p[i]) for i in insts])
+
+    def composite(self, download=True, rows_only=True, clamp=False):
+        """DomainTracer.composite; the image comes back un-clamped (premultiplied colour, opacity) unless clamp."""
+        super().composite(download=False, rows_only=rows_only)
+        if self.rank != 0 or not download:
+            return None
+        cam = self.camera
+        return self.backend.framebuffer(clamp).reshape(cam.height, cam.width, 4)
+
+    def update(self, bricks):
+        self.backend.update(bricks)
+        return self
+
+    def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
+        self.backend.set_surfaces(isovalues, slices, opacity)
+        return self
+
+    def set_lights(self, lights, ka=0.4, kd=0.6):
+        self.backend.set_lights(lights, ka, kd)
+        return self
+
+    def set_shading(self, on=True):
+        self.backend.set_shading(on)
+        return self
+
+    def stats(self):
+        """This rank's share: VolumeTracer.stats() over the bricks it owns, and the loop's own counts."""
+        st = dict(self.backend.stats())
+        st.update(adapter_calls=self.adapter_calls, rounds=self.rounds, rays_sent=self.rays_sent)
+        return st
 
 
 class MixedTracer:

@@ -617,6 +617,50 @@ typedef struct gvt_hip_volume_amr_info {
 } gvt_hip_volume_amr_info;
 int gvt_hip_volume_get_amr_info(gvt_hip_volume *, gvt_hip_volume_amr_info *); /* synchronises */
 
+/* ---- volume domains across ranks: Tracer<DomainScheduler> taking the volume branch of shuffleRays (TracerBase.h:325-414,
+ *      DomainTracer.h:148-496).  The bricks of one volume are spread over the ranks of a job (owner[brick] = rank); every rank holds a
+ *      queue and a top-level box for EVERY brick and a gvt_hip_volume for the bricks it owns.  The queue of a brick a rank does not own
+ *      is its outgoing list to that brick's owner.  The frame loop itself lives in the caller (gravit_amd/scheduler.py
+ *      VolumeDomainTracer); the library supplies its four steps. ----
+ * CONTRACT.  With ONE sample per pixel, for every assignment of bricks to ranks, every number of ranks and any interleaving of marches
+ * and exchanges, the sum of the ranks' framebuffers equals the framebuffer of gvt_hip_volume_frame over the same bricks IN EVERY BIT,
+ * and the bricks' counters (samples_marched, samples_gathered, crossings, shaded samples) sum to the one-rank frame's.  Why:
+ *   - a ray keeps one sample lattice from brick to brick, and its whole state (colour, opacity, flags, side mask, t_min, t_max) lies in
+ *     the 80-byte wire image, which the exchange moves unchanged (gvt_hip_queues_export_wire / _append_wire, state kept);
+ *   - the march and the shuffle of a ray read that ray alone: neither its position in a queue, nor the rank, nor what else the launch
+ *     holds enters its result;
+ *   - a pixel has exactly one ray, so exactly one deposit, on the rank where the ray ends (OPAQUE or EXTERNAL): the composite adds that
+ *     value to zeros, x + 0 = x.
+ * With several samples per pixel the deposits of a pixel meet in float atomics in an unspecified order, as they do in the one-rank frame:
+ * not bit-exact, and not promised.
+ * OUT OF SCOPE.  A native frame loop over gvt_hip_comm for volumes; the clipped (mixed) frame across ranks; a ray marching through
+ * several locally owned bricks inside one launch. */
+/* Adapter::trace on a device-resident queue: the march of the queue's rays through the brick, in place, on the calling context's stream,
+ * without a host wait -- what gvt_hip_volume_frame does per target, and the same kernels.  flags: GVT_HIP_MARCH_MAY_CLIP -- the queue may
+ * hold rays that carry GVT_HIP_RAY_CLIP (without it the launch ignores that flag, as gvt_hip_volume_frame's does).  The rays stay in the
+ * queue with their flags (OPAQUE / BOUNDARY) for gvt_hip_shuffle_volume.  An empty queue: nothing is launched.  A null argument, a volume
+ * without a transfer function or an unknown flag bit: GVT_HIP_ERR_INVALID, nothing changed. */
+#define GVT_HIP_MARCH_MAY_CLIP 1
+int gvt_hip_volume_march_queue(gvt_hip_volume *, gvt_hip_queue *queue, const float minv[16], uint32_t flags);
+/* shuffleDropRays for volumes (DomainTracer.h:148-183): the camera's rays, generated exactly as gvt_hip_volume_frame generates them (8x8
+ * tiles, origins left at the eye: one lattice per ray), shuffled from -1 into queues[] (one per brick of the top, appended to).  A ray
+ * whose first brick b has keep_mask[b] == 0 is dropped: that brick's owner generates the same ray.  A ray that meets no brick is dropped
+ * everywhere.  keep_mask == NULL keeps everything.  A kept brick's queue receives the same rays in the same order as in the camera step
+ * of gvt_hip_volume_frame; the other queues are not touched.  The framebuffer is not involved (a camera ray deposits nothing). */
+int gvt_hip_volume_camera_filter(gvt_hip_top *, const gvt_hip_camera *cam, gvt_hip_queue *const *queues, const uint8_t *keep_mask /* n bricks, or NULL */);
+/* The ray exchange's two ends, batched: ONE kernel launch for all the queues of a message, whatever n is (1..256).
+ * _export_wire: the rays of queues[0], queues[1], ... laid end to end in dst_device (device memory, cap_rays rays of 80 bytes), byte
+ * for byte what gvt_hip_queue_export(queues[i], ..., dst_on_device = 1) writes per queue; counts_out[i] (optional) = rays of queue i,
+ * *total_out = their sum; the queues are cleared; waits for the stream, so the buffer is complete on return.  total > cap_rays:
+ * GVT_HIP_ERR_CAPACITY, *total_out = the count needed, nothing changed.  A queue may appear once.
+ * _append_wire: consecutive runs of counts[i] rays of src_device are appended to queues[i], state bytes 64..79 kept, the queues grown as
+ * gvt_hip_queue_append grows them: the result of gvt_hip_queue_append(queues[i], run i, counts[i], 1) per queue.  No host wait; the
+ * source must stay valid until the stream has passed the launch.
+ * Null arguments (queues, an entry of it, total_out / counts, a buffer where rays exist) or n outside 1..256: GVT_HIP_ERR_INVALID. */
+int gvt_hip_queues_export_wire(gvt_hip_queue *const *queues, size_t n, gvt_hip_ray *dst_device, size_t cap_rays, uint64_t *counts_out /* n, may be NULL */,
+                               uint64_t *total_out);
+int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt_hip_ray *src_device, const uint64_t *counts /* n */);
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

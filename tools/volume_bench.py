@@ -27,6 +27,14 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              (the plain path), (c) one ratio-2 subgrid over the central eighth, (d) as (c) plus a ratio-4
                                              child over the subgrid's central eighth; then (e) the uniform 512^3 grid (c) would need, for
                                              memory and time beside it.  --sizes N: another level-0 size ((e) is 2 N)
+  python tools/volume_bench.py --domains 1 2 4 8   volume domains across ranks: the "thin" 1080p frame of the 256^3 grid in 8 and in 64 bricks
+                                             (round-robin owners) through scheduler.VolumeDomainTracer, W ranks as W threads of this process on
+                                             ONE GPU over the stand-in transport of tests/fake_dist.py, one lock around library calls.  Per W and
+                                             bricking: frame time (all ranks, composite included), rounds, rays sent, adapter calls, and the share
+                                             of the frame the slowest rank spent in export + transfer + append; beside it the one-rank
+                                             VolumeTracer.frame() (W = 1 against it prices the Python loop) and, with --per-queue, the same
+                                             frames exchanging through one gvt_hip_queue_export / _append call per brick.  W > 1 on one GPU
+                                             SHARES the device: this measures the protocol's overhead, not scaling
 """
 import argparse
 import json
@@ -256,6 +264,121 @@ def run_amr(n, steps, warmup, rate):
     return out
 
 
+def run_domains(n, split, world, steps, warmup, rate, kind, vol, per_queue, overlap):
+    """One bricking at one world size: `world` threads, each a rank with its own HipVolumeBackend, frames started together."""
+    import threading
+
+    import torch
+
+    from gravit_amd.scheduler import HipVolumeBackend, VolumeDomainTracer
+    from tests.fake_dist import FakeWorld
+
+    class PerQueueBackend(HipVolumeBackend):  # the exchange as HipBackend does it: one export / append call per brick
+        def export_wire(self, insts, torch, device):
+            sizes = [len(self.queues[i]) for i in insts]
+            buf = torch.empty((sum(sizes), 20), dtype=torch.float32, device=device)
+            off = 0
+            for i, cnt in zip(insts, sizes):
+                if cnt:
+                    self.queues[i].export_device(buf.data_ptr() + off * 80, cnt)
+                    self.queues[i].clear()
+                off += cnt
+            return buf
+
+        def append_wire(self, insts, buf, off, counts):
+            for i, cnt in zip(insts, counts):
+                self.queues[i].append_device(buf.data_ptr() + off * 80, cnt)
+                off += cnt
+
+    lock = threading.Lock()
+
+    class Timed:  # one thread inside the library at a time; the exchange's own calls are timed inside the lock
+        def __init__(self, inner, acc):
+            self._b, self._acc = inner, acc
+
+        def __getattr__(self, name):
+            attr = getattr(self._b, name)
+            if not callable(attr):
+                return attr
+
+            def call(*a, **k):
+                with lock:
+                    if name not in ("export_wire", "append_wire"):
+                        return attr(*a, **k)
+                    t = time.perf_counter()
+                    r = attr(*a, **k)
+                    capi.synchronize()
+                    self._acc[name] += time.perf_counter() - t
+                    return r
+            return call
+
+    class TimedDist:  # the payload's way through the transport: posting and waiting
+        def __init__(self, inner, acc):
+            self._d, self._acc = inner, acc
+
+        def __getattr__(self, name):
+            return getattr(self._d, name)
+
+        def batch_isend_irecv(self, ops):
+            if any(op.tensor.dim() != 2 for op in ops):  # (the composite's rectangles: not the ray exchange)
+                return self._d.batch_isend_irecv(ops)
+            t = time.perf_counter()
+            for r in self._d.batch_isend_irecv(ops):
+                r.wait()  # (a receive also waits for its peer to reach the exchange)
+            torch.cuda.current_stream().synchronize()
+            self._acc["transfer"] += time.perf_counter() - t
+            return []
+
+    bricks = scenes.split_volume(vol, *split)
+    owner = [i % world for i in range(len(bricks))]
+    cam, tf = camera(), transfer(kind)
+    fw = FakeWorld(world)
+    start = threading.Barrier(world)
+    res, errs = {}, []
+
+    def rank_main(rank):
+        try:
+            acc = {"export_wire": 0.0, "append_wire": 0.0, "transfer": 0.0}
+            with lock:
+                B = (PerQueueBackend if per_queue else HipVolumeBackend)(bricks, cam, tf, None, rate, True, False, [o == rank for o in owner])
+            tr = VolumeDomainTracer(bricks, owner, cam, tf, TimedDist(fw.rank_view(rank), acc), torch, torch.device("cuda", 0), sampling_rate=rate,
+                                    backend=Timed(B, acc), overlap=overlap)
+            frames, shares = [], []
+            for i in range(warmup + steps):
+                for k in acc:
+                    acc[k] = 0.0
+                start.wait()
+                t = time.perf_counter()
+                tr()
+                tr.composite(download=False)
+                with lock:
+                    capi.synchronize()
+                start.wait()  # (the frame is over when every rank has composited)
+                frames.append((time.perf_counter() - t) * 1e3)
+                shares.append(dict(acc))
+            res[rank] = (frames[warmup:], shares[warmup:], tr.rounds, tr.rays_sent, tr.adapter_calls)
+        except Exception:  # noqa: BLE001
+            import traceback
+
+            errs.append(traceback.format_exc())
+            for b in (fw.barrier, start):
+                b.abort()
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(world)]
+    [t.start() for t in th]
+    [t.join(timeout=900) for t in th]
+    if errs:
+        raise RuntimeError(errs[0])
+    frames = res[0][0]
+    ex = [max(1e3 * sum(res[r][1][i].values()) for r in range(world)) for i in range(steps)]
+    parts = {k: med([max(1e3 * res[r][1][i][k] for r in range(world)) for i in range(steps)]) for k in ("export_wire", "transfer", "append_wire")}
+    return {"mode": "domains", "n": n, "tf": kind, "bricks": len(bricks), "world": world, "exchange": "per_queue" if per_queue else "batched",
+            "loop": "overlapped" if overlap else "bsp", "ms_median": med(frames), "ms_min": round(min(frames), 3), "ms_max": round(max(frames), 3),
+            "rounds": res[0][2], "rays_sent": sum(res[r][3] for r in range(world)), "adapter_calls": sum(res[r][4] for r in range(world)),
+            "exchange_ms_median": med(ex), "exchange_share": round(float(np.median(ex)) / float(np.median(frames)), 4), "export_ms": parts["export_wire"],
+            "transfer_ms": parts["transfer"], "append_ms": parts["append_wire"]}
+
+
 def run_update(n, device, steps, warmup, recreate_only, dtype="f32"):
     """Two time steps of the n^3 noise grid, pushed alternately into one brick under the sparse table."""
     from gravit_amd.adapter import HipVolumeAdapter
@@ -319,9 +442,12 @@ def main():
     ap.add_argument("--shade", action="store_true")
     ap.add_argument("--amr", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
+    ap.add_argument("--domains", type=int, nargs="+", metavar="W")
+    ap.add_argument("--per-queue", action="store_true")
+    ap.add_argument("--overlap", action="store_true")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     a = ap.parse_args()
-    if a.update:
+    if a.update or a.domains:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
     capi.init(0)
     out = {"source_hash": _build.source_hash(), "width": 1920, "height": 1080, "runs": []}
@@ -331,6 +457,20 @@ def main():
                 r = run_update(n, device, a.steps, a.warmup, a.recreate_only, a.dtype)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
+        a.sizes = []
+    if a.domains:
+        for n in ([256] if a.sizes == [256, 512] else a.sizes):
+            vol = noise(n, "f32")
+            for split in ((2, 2, 2), (4, 4, 4)):
+                r = run(n, split, a.steps, a.warmup, a.rate, "thin", vol)  # the one-rank native frame of the same bricks
+                r["mode"] = "one_rank_native"
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+                for w in a.domains:
+                    for per_queue in ((False, True) if a.per_queue else (False,)):
+                        r = run_domains(n, split, w, a.steps, a.warmup, a.rate, "thin", vol, per_queue, a.overlap)
+                        out["runs"].append(r)
+                        print(json.dumps(r), flush=True)
         a.sizes = []
     if a.amr:
         for n in ([256] if a.sizes == [256, 512] else a.sizes):
