@@ -501,6 +501,8 @@ class HipVolumeAdapter:
         self.voxel_type, self.sample_bytes = vt.value, nb.value
         if getattr(brick, "subgrids", None):  # an AMR brick: its subgrids come with it
             self.set_subgrids(brick.subgrids)
+        if getattr(brick, "ghosts", None) is not None:  # a brick that knows its neighbours' face layers (scenes.split_volume(ghosts=True))
+            self.set_ghosts(brick.ghosts)
 
     def set_subgrids(self, subgrids):
         """gvt_hip_volume_set_subgrids: the brick's whole set of refined subgrids (scenes.Subgrid; an empty list removes it).  Their data:
@@ -530,6 +532,65 @@ class HipVolumeAdapter:
                 ptrs[i] = keep[-1].ctypes.data
         flags = capi.VOLUME_DEVICE if n and all(device) else 0
         capi.check(self.lib.gvt_hip_volume_set_subgrids(self.h, C.cast(pods, C.c_void_p), C.cast(ptrs, C.c_void_p), n, flags), "gvt_hip_volume_set_subgrids")
+
+    GRADIENT_KINDS = {"cell": capi.VOLUME_GRADIENT_CELL, "central": capi.VOLUME_GRADIENT_CENTRAL}
+
+    def set_ghosts(self, faces):
+        """gvt_hip_volume_set_ghosts: the six layers of global vertices just outside the brick, in the order -x +x -y +y -z +z; None = no
+        layer (a face on the global grid's boundary has none).  +-x: (nz, ny), +-y: (nz, nx), +-z: (ny, nx), of the adapter's dtype: numpy
+        arrays, or contiguous torch tensors on the GPU (all of them: no host round trip).  The library keeps its own copies."""
+        faces = list(faces)
+        if len(faces) != 6:
+            raise ValueError("set_ghosts: six faces (-x +x -y +y -z +z, None for a missing one), not %d" % len(faces))
+        nx, ny, nz = (int(v) for v in self.counts)
+        shapes = [(nz, ny), (nz, ny), (nz, nx), (nz, nx), (ny, nx), (ny, nx)]
+        want = getattr(self, "dtype_name", "float32")
+        present = [f for f in faces if f is not None]
+        device = [hasattr(f, "data_ptr") and f.is_cuda for f in present]
+        if any(device) and not all(device):
+            raise ValueError("set_ghosts: the faces must be all host arrays or all GPU tensors")
+        ptrs = (C.c_void_p * 6)()
+        keep = []
+        for i, f in enumerate(faces):
+            if f is None:
+                continue
+            if tuple(f.shape) != shapes[i]:
+                raise ValueError("set_ghosts: face %d has shape %s, the brick needs %s" % (i, tuple(f.shape), shapes[i]))
+            if hasattr(f, "data_ptr") and f.is_cuda:
+                import torch
+
+                if not f.is_contiguous() or self.dtype_of(f) != want:
+                    raise ValueError("set_ghosts: a device tensor must be contiguous %s" % want)
+                torch.cuda.current_stream(f.device).synchronize()  # (written on torch's stream, copied on the library's)
+                keep.append(f)
+                ptrs[i] = f.data_ptr()
+            else:
+                a = np.asarray(f.numpy() if hasattr(f, "data_ptr") else f)
+                keep.append(np.ascontiguousarray(a, dtype=np.dtype(want)) if self.dtype_name == "float32" else np.ascontiguousarray(a))
+                if keep[-1].dtype.name != want:
+                    raise ValueError("set_ghosts: face %d of dtype %s, the brick holds %s" % (i, keep[-1].dtype, want))
+                ptrs[i] = keep[-1].ctypes.data
+        flags = capi.VOLUME_DEVICE if device and all(device) else 0
+        capi.check(self.lib.gvt_hip_volume_set_ghosts(self.h, C.cast(ptrs, C.c_void_p), self.voxel_type, flags), "gvt_hip_volume_set_ghosts")
+
+    def set_gradient(self, kind):
+        """gvt_hip_volume_set_gradient: "cell" (the interpolant's gradient in the sample's cell, the default) or "central" (central
+        differences at the vertices, interpolated; every face that is not on the global boundary needs its layer: set_ghosts)."""
+        if kind not in self.GRADIENT_KINDS:
+            raise ValueError("set_gradient: kind %r is neither 'cell' nor 'central'" % (kind,))
+        capi.check(self.lib.gvt_hip_volume_set_gradient(self.h, self.GRADIENT_KINDS[kind]), "gvt_hip_volume_set_gradient")
+
+    def gradient(self):
+        """The gradient kind, "cell" or "central"."""
+        k = C.c_int(-1)
+        capi.check(self.lib.gvt_hip_volume_get_gradient(self.h, C.byref(k), None), "gvt_hip_volume_get_gradient")
+        return {v: n for n, v in self.GRADIENT_KINDS.items()}[k.value]
+
+    def central_marches(self):
+        """The launches of this brick that shaded with central differences so far."""
+        n = C.c_uint64(0)
+        capi.check(self.lib.gvt_hip_volume_get_gradient(self.h, None, C.byref(n)), "gvt_hip_volume_get_gradient")
+        return n.value
 
     def amr_info(self):
         """n_subgrids, n_levels, subgrid_bytes, samples_refined, amr_marches (gvt_hip_volume_get_amr_info)."""

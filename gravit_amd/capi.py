@@ -41,6 +41,7 @@ SYMBOLS = [
     "gvt_hip_volume_frame_clipped", "gvt_hip_fb_composite_over",
     "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
     "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
+    "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
 ]
 
 
@@ -102,6 +103,7 @@ VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
 VOLUME_MAX_SUBGRIDS, VOLUME_MAX_LEVELS = 4096, 4  # AMR volumes (gvt_hip_volume_set_subgrids)
 VOLUME_SHADE_NONE, VOLUME_SHADE_GRADIENT = 0, 1  # gvt_hip_volume_set_shading: the fog's samples lit by the interpolant's gradient
+VOLUME_GRADIENT_CELL, VOLUME_GRADIENT_CENTRAL = 0, 1  # gvt_hip_volume_set_gradient: which gradient shades (CENTRAL needs set_ghosts)
 VOXEL_F32, VOXEL_U8, VOXEL_I16, VOXEL_U16 = 0, 1, 2, 3  # a volume's voxel type: the samples stay on the device at that width
 VOXEL_TYPES = {"float32": VOXEL_F32, "uint8": VOXEL_U8, "int16": VOXEL_I16, "uint16": VOXEL_U16}  # by numpy / torch dtype name
 
@@ -146,6 +148,9 @@ def load():
         lib.gvt_hip_volume_get_voxel_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_set_subgrids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         lib.gvt_hip_volume_get_amr_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_set_ghosts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]
+        lib.gvt_hip_volume_set_gradient.argtypes = [C.c_void_p, C.c_int]
+        lib.gvt_hip_volume_get_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_march_queue.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         lib.gvt_hip_volume_camera_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_queues_export_wire.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]

@@ -7,6 +7,9 @@
 //   k_volume_march_lit / _surf_lit          points of one body, volume_march_body<T, SURF, CLIP, LIT> (SURF: isovalues and slice planes;
 //                                           CLIP: the launch may hold rays clipped at their t_max, GVT_HIP_RAY_CLIP; LIT: every contributing
 //                                           sample is shaded by the interpolant's gradient, gvt_hip_volume_set_shading)
+//   k_volume_march_surf_central / _lit_central / _surf_lit_central   the three shaded marches with GVT_HIP_VOLUME_GRADIENT_CENTRAL: the
+//                                           same body with CENTRAL, the gradient from central differences at the vertices, which read
+//                                           one ghost layer beyond the brick's interior faces (gvt_hip_volume_set_ghosts / _set_gradient)
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
 //   k_volume_march_amr / k_amr_ranges       AMR volumes (Volume::AddAMRGrid): nested refined subgrids inside a brick, volume_amr.inc
@@ -61,6 +64,14 @@ struct gvt_hip_volume {
   std::vector<uint32_t> amr_first, amr_count; // per macro cell: its level-1 subgrids in d_amr_list (d_amr_mc without the skip bit)
   std::vector<float> amr_min, amr_max;        // per macro cell: the subgrids' part of its value range (bmin / bmax / bnan hold the union)
   std::vector<uint8_t> amr_nan;
+  // smooth gradients (gvt_hip_volume_set_ghosts / _set_gradient): with GVT_HIP_VOLUME_GRADIENT_CENTRAL the shaded marches are the _central
+  // entry points, which read the six face layers beyond the brick from d_ghost (one allocation: -x +x -y +y -z +z, a slab of a missing
+  // face is never read)
+  int gn[3] = { 0, 0, 0 };       // the global grid's vertices per axis
+  int grad = GVT_HIP_VOLUME_GRADIENT_CELL;
+  unsigned ghost_mask = 0;       // bit 2 * axis + side: that face has a layer
+  void *d_ghost = nullptr;
+  uint64_t central_marches = 0;
 };
 
 namespace {
@@ -157,6 +168,15 @@ struct LightDev {
   int n_lights;
   float ka, kd;
 };
+// ... and what the _central entry points receive beside their table: the six face layers beyond the brick, samples of the brick's voxel
+// type in one allocation (-x +x: ny*nz each at j + ny*k; -y +y: nx*nz at i + nx*k; -z +z: nx*ny at i + nx*j), and the global grid's size
+struct GhostDev {
+  const void *faces;
+  int gnx, gny, gnz;
+};
+struct NoGhost {};
+template <bool CENTRAL>
+using GhostTable = std::conditional_t<CENTRAL, GhostDev, NoGhost>;
 template <bool SURF, bool LIT>
 using MarchTable = std::conditional_t<SURF, SurfDev, std::conditional_t<LIT, LightDev, NoSurf>>;
 #define VOL_CELL_SKIP 0x10000u
@@ -307,17 +327,70 @@ __device__ __forceinline__ void vol_gradient(const VolDev &V, const VolCorners &
   g[2] = lerp_(lerp_(G.v001 - G.v000, G.v101 - G.v100, f[0]), lerp_(G.v011 - G.v010, G.v111 - G.v110, f[0]), f[1]) / V.sz;
 }
 
+// GVT_HIP_VOLUME_GRADIENT_CENTRAL: central differences at the cell's eight vertices, interpolated trilinearly (the contract: include/
+// gvt_hip.h, "smooth gradients"; tests/volume_smooth_checker.py).  Per axis the vertex before the cell and the one after it, at the four
+// positions of the other two axes: inside the brick they are its own samples, one layer beyond a face the ghost layer's, and on the
+// global boundary the difference is one-sided (the cell's own corner, half the span).  The guards differ from lane to lane; the loads
+// are eight per axis, beside the corners the gather has left in G.  A: the axis, with B and C the other two in x y z order.
+template <typename T, int A>
+__device__ __forceinline__ float vol_central_axis(const VolDev &V, const GhostDev &H, const int c[3], const float lo[4], const float hi[4], const float f[3]) {
+  constexpr int B = A == 0 ? 1 : 0, C = A == 2 ? 1 : 2;
+  const int n[3] = { V.nx, V.ny, V.nz }, off[3] = { V.ox, V.oy, V.oz }, gn[3] = { H.gnx, H.gny, H.gnz };
+  const float sp[3] = { V.sx, V.sy, V.sz };
+  const size_t str[3] = { 1, (size_t)V.nx, (size_t)V.nx * (size_t)V.ny };
+  const size_t slab[3] = { (size_t)V.ny * (size_t)V.nz, (size_t)V.nx * (size_t)V.nz, (size_t)V.nx * (size_t)V.ny };
+  // a face layer's strides along B and C: x faces (j + ny*k), y faces (i + nx*k), z faces (i + nx*j)
+  const size_t fb = 1, fc = (size_t)n[B];
+  const T *face = (const T *)H.faces + (A > 0 ? 2 * slab[0] : 0) + (A > 1 ? 2 * slab[1] : 0);
+  const size_t in_brick = (size_t)c[0] + str[1] * (size_t)c[1] + str[2] * (size_t)c[2], in_face = fb * (size_t)c[B] + fc * (size_t)c[C];
+  float m[4], p[4];        // the vertex before the cell's low corners, and the one after its high corners
+  float dm = 2.f, dp = 2.f; // (float)(ip - im) of the low and of the high vertices
+  if (off[A] + c[A] == 0) { // the low vertices lie on the global boundary: im = i
+    for (int q = 0; q < 4; q++) m[q] = lo[q];
+    dm = 1.f;
+  } else {
+    const bool own = c[A] > 0;
+    const T *b = own ? (const T *)V.vox + (in_brick - str[A]) : face + in_face;
+    const size_t s1 = own ? str[B] : fb, s2 = own ? str[C] : fc;
+    m[0] = (float)b[0]; m[1] = (float)b[s1]; m[2] = (float)b[s2]; m[3] = (float)b[s1 + s2];
+  }
+  if (off[A] + c[A] + 1 == gn[A] - 1) { // the high vertices lie on it: ip = i
+    for (int q = 0; q < 4; q++) p[q] = hi[q];
+    dp = 1.f;
+  } else {
+    const bool own = c[A] + 2 < n[A];
+    const T *b = own ? (const T *)V.vox + (in_brick + 2 * str[A]) : face + slab[A] + in_face;
+    const size_t s1 = own ? str[B] : fb, s2 = own ? str[C] : fc;
+    p[0] = (float)b[0]; p[1] = (float)b[s1]; p[2] = (float)b[s2]; p[3] = (float)b[s1 + s2];
+  }
+  const float hm = sp[A] * dm, hp = sp[A] * dp;
+  float gl[4], gh[4]; // the component at the low and at the high vertices
+  for (int q = 0; q < 4; q++) { gl[q] = (hi[q] - m[q]) / hm; gh[q] = (p[q] - lo[q]) / hp; }
+  // vol_gather's nesting: x, then y, then z.  q = (B bit) + 2 * (C bit)
+  if constexpr (A == 0) return lerp_(lerp_(lerp_(gl[0], gh[0], f[0]), lerp_(gl[1], gh[1], f[0]), f[1]), lerp_(lerp_(gl[2], gh[2], f[0]), lerp_(gl[3], gh[3], f[0]), f[1]), f[2]);
+  else if constexpr (A == 1) return lerp_(lerp_(lerp_(gl[0], gl[1], f[0]), lerp_(gh[0], gh[1], f[0]), f[1]), lerp_(lerp_(gl[2], gl[3], f[0]), lerp_(gh[2], gh[3], f[0]), f[1]), f[2]);
+  else return lerp_(lerp_(lerp_(gl[0], gl[1], f[0]), lerp_(gl[2], gl[3], f[0]), f[1]), lerp_(lerp_(gh[0], gh[1], f[0]), lerp_(gh[2], gh[3], f[0]), f[1]), f[2]);
+}
+template <typename T>
+__device__ __forceinline__ void vol_gradient_central(const VolDev &V, const GhostDev &H, const int c[3], const VolCorners &G, const float f[3], float g[3]) {
+  { const float lo[4] = { G.v000, G.v010, G.v001, G.v011 }, hi[4] = { G.v100, G.v110, G.v101, G.v111 }; g[0] = vol_central_axis<T, 0>(V, H, c, lo, hi, f); }
+  { const float lo[4] = { G.v000, G.v100, G.v001, G.v101 }, hi[4] = { G.v010, G.v110, G.v011, G.v111 }; g[1] = vol_central_axis<T, 1>(V, H, c, lo, hi, f); }
+  { const float lo[4] = { G.v000, G.v100, G.v010, G.v110 }, hi[4] = { G.v001, G.v101, G.v011, G.v111 }; g[2] = vol_central_axis<T, 2>(V, H, c, lo, hi, f); }
+}
+
 // vol_accumulate for a lit volume (L: SurfDev or LightDev, n_lights > 0): a sample the table gives opacity is shaded by the gradient in its
 // own cell; one of zero opacity adds +0 whatever its colour, so it is neither shaded nor counted.  Unlike surf_composite, a gradient of
 // infinite length shades with S = 0 (g / Inf would be 0 or NaN): C stays finite on grids whose differences overflow.  Returns 1 if shaded
-template <typename LT>
-__device__ __forceinline__ unsigned vol_accumulate_lit(const VolDev &V, const LT &L, float v, const VolCorners &G, const float f[3], float C[3], float &A) {
+template <typename T, bool CENTRAL, typename LT>
+__device__ __forceinline__ unsigned vol_accumulate_lit(const VolDev &V, const LT &L, const GhostTable<CENTRAL> &H, const int c[3], float v, const VolCorners &G,
+                                                       const float f[3], float C[3], float &A) {
   const float4 tc = vol_lookup(V, v);
   float rgb[3] = { tc.x, tc.y, tc.z };
   const bool shaded = tc.w > 0.f; // (false for NaN)
   if (shaded) {
     float g[3], sum[3] = { 0.f, 0.f, 0.f };
-    vol_gradient(V, G, f, g);
+    if constexpr (CENTRAL) vol_gradient_central<T>(V, H, c, G, f, g);
+    else vol_gradient(V, G, f, g);
     const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
     if (len > 0.f && len < INFINITY) { // (false for NaN)
       const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
@@ -358,8 +431,10 @@ __device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, uns
 // GVT_HIP_RAY_CLIP (vol_ray_range); without it the body is the unclipped march, instruction for instruction, and no ray is flagged.
 // LIT (shading on and at least one light): the sample's own contribution is vol_accumulate_lit's, from the corners the gather has just
 // loaded -- they stay live across the look-up; with SURF a crossing is rendered first, as ever.  Without LIT: the march as it was.
-template <typename T, bool SURF, bool CLIP, bool LIT>
-__device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTable<SURF, LIT> &S, RayPlanes q, unsigned n, const Mat4 &minv,
+// CENTRAL (the _central entry points): the gradient of a crossed isovalue and of a lit sample is vol_gradient_central's, from H; nothing
+// else of the march reads H or depends on the kind.
+template <typename T, bool SURF, bool CLIP, bool LIT, bool CENTRAL = false>
+__device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTable<SURF, LIT> &S, const GhostTable<CENTRAL> &H, RayPlanes q, unsigned n, const Mat4 &minv,
                                                   unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
   bool active = false, exhausted = false;
   unsigned idx = 0;
@@ -447,11 +522,18 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTa
           prev = (int)sides;
           if (crossed) {
             const float v000 = G.v000, v100 = G.v100, v010 = G.v010, v110 = G.v110, v001 = G.v001, v101 = G.v101, v011 = G.v011, v111 = G.v111;
+            float gc[3] = { 0.f, 0.f, 0.f }; // (CENTRAL only: the isovalues crossed here share one gradient, fetched once, ahead of the loop)
+            if constexpr (CENTRAL)
+              if (crossed & ((1u << S.n_iso) - 1u)) vol_gradient_central<T>(V, H, c, G, f, gc);
             while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
               const int i = __ffs((int)crossed) - 1;
               crossed &= crossed - 1u;
               n_crossed++;
               if (i < S.n_iso) {
+                if constexpr (CENTRAL) {
+                  surf_composite(S, vol_lookup(V, S.iso[i]), gc, C, A);
+                  continue;
+                }
                 const float g[3] = { lerp_(lerp_(v100 - v000, v110 - v010, f[1]), lerp_(v101 - v001, v111 - v011, f[1]), f[2]) / V.sx,
                                      lerp_(lerp_(v010 - v000, v110 - v100, f[0]), lerp_(v011 - v001, v111 - v101, f[0]), f[2]) / V.sy,
                                      lerp_(lerp_(v001 - v000, v101 - v100, f[0]), lerp_(v011 - v010, v111 - v110, f[0]), f[1]) / V.sz };
@@ -465,7 +547,7 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTa
             if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
           }
         }
-        if constexpr (LIT) n_shaded += vol_accumulate_lit(V, S, v, G, f, C, A);
+        if constexpr (LIT) n_shaded += vol_accumulate_lit<T, CENTRAL>(V, S, H, c, v, G, f, C, A);
         else vol_accumulate(V, v, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
@@ -498,22 +580,39 @@ __device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTa
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march(VolDev V, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                             unsigned long long *__restrict__ stats) {
-  volume_march_body<T, false, CLIP, false>(V, NoSurf{}, q, n, minv, work, stats);
+  volume_march_body<T, false, CLIP, false>(V, NoSurf{}, NoGhost{}, q, n, minv, work, stats);
 }
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                  unsigned long long *__restrict__ stats) {
-  volume_march_body<T, true, CLIP, false>(V, S, q, n, minv, work, stats);
+  volume_march_body<T, true, CLIP, false>(V, S, NoGhost{}, q, n, minv, work, stats);
 }
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_lit(VolDev V, LightDev L, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                 unsigned long long *__restrict__ stats) {
-  volume_march_body<T, false, CLIP, true>(V, L, q, n, minv, work, stats);
+  volume_march_body<T, false, CLIP, true>(V, L, NoGhost{}, q, n, minv, work, stats);
 }
 template <typename T, bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf_lit(VolDev V, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                      unsigned long long *__restrict__ stats) {
-  volume_march_body<T, true, CLIP, true>(V, S, q, n, minv, work, stats);
+  volume_march_body<T, true, CLIP, true>(V, S, NoGhost{}, q, n, minv, work, stats);
+}
+
+// ... and the three shaded marches with GVT_HIP_VOLUME_GRADIENT_CENTRAL: the same body, with the ghost table
+template <typename T, bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf_central(VolDev V, SurfDev S, GhostDev H, RayPlanes q, unsigned n, Mat4 minv,
+                                                                         unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
+  volume_march_body<T, true, CLIP, false, true>(V, S, H, q, n, minv, work, stats);
+}
+template <typename T, bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_lit_central(VolDev V, LightDev L, GhostDev H, RayPlanes q, unsigned n, Mat4 minv,
+                                                                        unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
+  volume_march_body<T, false, CLIP, true, true>(V, L, H, q, n, minv, work, stats);
+}
+template <typename T, bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_surf_lit_central(VolDev V, SurfDev S, GhostDev H, RayPlanes q, unsigned n, Mat4 minv,
+                                                                             unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
+  volume_march_body<T, true, CLIP, true, true>(V, S, H, q, n, minv, work, stats);
 }
 
 // ---- shuffleRays, volume branch.  Destinations are counted per (wave, destination) in LDS and a scan per destination gives every block
@@ -934,6 +1033,17 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16], boo
     const unsigned n = (unsigned)q->size;
     const bool surf = Vh->n_iso + Vh->n_pl > 0;
     const bool lit = Vh->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && Vh->n_lights > 0; // (no lights: nothing to shade with, the march as it was)
+    if (Vh->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && (lit || surf)) { // (the plain march computes no gradient: the kind is inert there)
+      const GhostDev H{ Vh->d_ghost, Vh->gn[0], Vh->gn[1], Vh->gn[2] };
+      if (lit && surf && clip) k_volume_march_surf_lit_central<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), H, P, n, M, work, Vh->d_stats);
+      else if (lit && surf) k_volume_march_surf_lit_central<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), H, P, n, M, work, Vh->d_stats);
+      else if (lit && clip) k_volume_march_lit_central<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), light_dev(Vh, M), H, P, n, M, work, Vh->d_stats);
+      else if (lit) k_volume_march_lit_central<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), light_dev(Vh, M), H, P, n, M, work, Vh->d_stats);
+      else if (clip) k_volume_march_surf_central<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), H, P, n, M, work, Vh->d_stats);
+      else k_volume_march_surf_central<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), H, P, n, M, work, Vh->d_stats);
+      Vh->central_marches++;
+      return;
+    }
     if (lit && surf && clip) k_volume_march_surf_lit<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
     else if (lit && surf) k_volume_march_surf_lit<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
     else if (lit && clip) k_volume_march_lit<T, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), light_dev(Vh, M), P, n, M, work, Vh->d_stats);
@@ -1069,7 +1179,7 @@ extern "C" gvt_hip_volume *gvt_hip_volume_create_typed(const void *samples, int 
   if (total >= 0xffffffffull) { set_error("volume_create: brick of %zu vertices is too large", total); return nullptr; }
   gvt_hip_volume *V = new gvt_hip_volume();
   for (int a = 0; a < 3; a++) {
-    V->n[a] = counts[a]; V->off[a] = offset[a]; V->go[a] = origin[a]; V->sp[a] = spacing[a];
+    V->n[a] = counts[a]; V->off[a] = offset[a]; V->gn[a] = global_counts[a]; V->go[a] = origin[a]; V->sp[a] = spacing[a];
     V->lo[a] = origin[a] + (float)offset[a] * spacing[a];
     V->hi[a] = origin[a] + (float)(offset[a] + counts[a] - 1) * spacing[a];
     V->nb[a] = (counts[a] - 1 + 7) / 8;
@@ -1109,7 +1219,7 @@ extern "C" int gvt_hip_volume_get_voxel_type(gvt_hip_volume *V, int *type_out, s
 extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
-  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats);
+  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost);
   hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
   delete V;
 }
@@ -1253,6 +1363,77 @@ extern "C" int gvt_hip_volume_get_shaded(gvt_hip_volume *V, uint64_t *samples_sh
   HIPCHK(hipStreamSynchronize(gctx().stream));
   HIPCHK(hipMemcpy(&s, V->d_stats + 3, sizeof(s), hipMemcpyDeviceToHost));
   *samples_shaded = s;
+  return 0;
+}
+
+// ---- smooth gradients: the six face layers beyond the brick and the gradient kind (the contract: include/gvt_hip.h)
+namespace {
+// is face 2 * a + side of the brick on the global grid's boundary (no vertex beyond it)?
+bool face_on_boundary(const gvt_hip_volume *V, int a, int side) { return side ? V->off[a] + V->n[a] == V->gn[a] : V->off[a] == 0; }
+size_t face_samples(const gvt_hip_volume *V, int a) { return (size_t)V->n[a == 0 ? 1 : 0] * (size_t)V->n[a == 2 ? 1 : 2]; }
+} // namespace
+
+extern "C" int gvt_hip_volume_set_ghosts(gvt_hip_volume *V, const void *const faces[6], int voxel_type, uint32_t flags) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !faces) { set_error("volume_set_ghosts: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (voxel_type != V->vtype) {
+    set_error("volume_set_ghosts: faces of voxel type %d, the volume holds type %d (fixed at creation)", voxel_type, V->vtype);
+    return GVT_HIP_ERR_INVALID;
+  }
+  if (flags & ~(uint32_t)GVT_HIP_VOLUME_DEVICE) { set_error("volume_set_ghosts: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
+  unsigned mask = 0;
+  for (int a = 0; a < 3; a++)
+    for (int side = 0; side < 2; side++) {
+      const int i = 2 * a + side;
+      if (faces[i] && face_on_boundary(V, a, side)) {
+        set_error("volume_set_ghosts: face %d lies on the global grid's boundary, there is no layer beyond it", i);
+        return GVT_HIP_ERR_INVALID;
+      }
+      if (!faces[i] && !face_on_boundary(V, a, side) && V->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL) {
+        set_error("volume_set_ghosts: the gradient kind is CENTRAL, which needs the layer of face %d", i);
+        return GVT_HIP_ERR_INVALID;
+      }
+      if (faces[i]) mask |= 1u << i;
+    }
+  const size_t vb = voxel_bytes(V->vtype);
+  hipStream_t st = gctx().stream;
+  HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the layers)
+  if (mask && !V->d_ghost) {
+    const size_t total = 2 * (face_samples(V, 0) + face_samples(V, 1) + face_samples(V, 2));
+    if (hipMalloc(&V->d_ghost, vb * total) != hipSuccess) { V->d_ghost = nullptr; set_error("volume_set_ghosts: device allocation failed"); return GVT_HIP_ERR_DEVICE; }
+  }
+  size_t at = 0;
+  for (int i = 0; i < 6; i++) {
+    const size_t cnt = face_samples(V, i / 2);
+    if (faces[i])
+      HIPCHK(hipMemcpyAsync((char *)V->d_ghost + vb * at, faces[i], vb * cnt, (flags & GVT_HIP_VOLUME_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    at += cnt;
+  }
+  HIPCHK(hipStreamSynchronize(st)); // (the samples are copied: the caller's memory is free on return)
+  V->ghost_mask = mask;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_set_gradient(gvt_hip_volume *V, int kind) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V) { set_error("volume_set_gradient: null"); return GVT_HIP_ERR_INVALID; }
+  if (kind != GVT_HIP_VOLUME_GRADIENT_CELL && kind != GVT_HIP_VOLUME_GRADIENT_CENTRAL) { set_error("volume_set_gradient: unknown kind %d", kind); return GVT_HIP_ERR_INVALID; }
+  if (kind == GVT_HIP_VOLUME_GRADIENT_CENTRAL) {
+    if (!V->sub.empty()) { set_error("volume_set_gradient: the volume has AMR subgrids, which are not shaded"); return GVT_HIP_ERR_INVALID; }
+    for (int i = 0; i < 6; i++)
+      if (!face_on_boundary(V, i / 2, i % 2) && !(V->ghost_mask & (1u << i))) {
+        set_error("volume_set_gradient: CENTRAL needs the layer beyond face %d (gvt_hip_volume_set_ghosts)", i);
+        return GVT_HIP_ERR_INVALID;
+      }
+  }
+  V->grad = kind;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_get_gradient(gvt_hip_volume *V, int *kind_out, uint64_t *central_marches_out) {
+  if (!V) { set_error("volume_get_gradient: null"); return GVT_HIP_ERR_INVALID; }
+  if (kind_out) *kind_out = V->grad;
+  if (central_marches_out) *central_marches_out = V->central_marches;
   return 0;
 }
 
@@ -1514,6 +1695,10 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   if (V->vtype != GVT_HIP_VOXEL_F32) { set_error("volume_set_subgrids: the volume holds voxel type %d, subgrids are float32", V->vtype); return GVT_HIP_ERR_INVALID; }
   if (V->n_iso + V->n_pl > 0 || V->shade == GVT_HIP_VOLUME_SHADE_GRADIENT) {
     set_error("volume_set_subgrids: the volume has surfaces or gradient shading, which AMR volumes do not take");
+    return GVT_HIP_ERR_INVALID;
+  }
+  if (n > 0 && V->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL) {
+    set_error("volume_set_subgrids: the volume's gradient kind is CENTRAL, which AMR volumes do not take");
     return GVT_HIP_ERR_INVALID;
   }
   for (int i = 0; i < n; i++)

@@ -565,6 +565,9 @@ class Brick:
     lo: np.ndarray
     hi: np.ndarray
     subgrids: list = field(default_factory=list)  # the AMR subgrids this brick holds (split_amr_volume); level-1 lo stays GLOBAL
+    # the layers of global vertices just outside the six faces, -x +x -y +y -z +z (gvt_hip_volume_set_ghosts): +-x (nz, ny), +-y (nz, nx),
+    # +-z (ny, nx); None for a face on the global boundary.  None: the brick does not know its neighbours
+    ghosts: Optional[list] = None
 
     @property
     def counts(self):
@@ -634,9 +637,23 @@ def _cuts(n_vertices, parts):
     return [k * cells // parts for k in range(parts + 1)]
 
 
-def split_volume(vol, bx, by, bz):
+def brick_ghosts(data, off, end):
+    """The six face layers beyond the vertices [off, end] (x y z, end inclusive) of the global grid data[z, y, x]: what a bricked
+    simulation output carries as ghost data.  None where the face is on the grid's boundary."""
+    nz, ny, nx = data.shape
+    zs, ys, xs = slice(off[2], end[2] + 1), slice(off[1], end[1] + 1), slice(off[0], end[0] + 1)
+    return [np.ascontiguousarray(data[zs, ys, off[0] - 1]) if off[0] > 0 else None,
+            np.ascontiguousarray(data[zs, ys, end[0] + 1]) if end[0] + 1 < nx else None,
+            np.ascontiguousarray(data[zs, off[1] - 1, xs]) if off[1] > 0 else None,
+            np.ascontiguousarray(data[zs, end[1] + 1, xs]) if end[1] + 1 < ny else None,
+            np.ascontiguousarray(data[off[2] - 1, ys, xs]) if off[2] > 0 else None,
+            np.ascontiguousarray(data[end[2] + 1, ys, xs]) if end[2] + 1 < nz else None]
+
+
+def split_volume(vol, bx, by, bz, ghosts=False):
     """Bricks of bx * by * bz: the cells cut evenly per axis, neighbours sharing one layer of vertices; every cell is owned by exactly one
-    brick.  Order: x fastest.  Boxes in the volume's own space, computed as gvt_hip_volume_create computes them (f32)."""
+    brick.  Order: x fastest.  Boxes in the volume's own space, computed as gvt_hip_volume_create computes them (f32).  ghosts=True:
+    every brick also carries the six face layers beyond it (Brick.ghosts), for central-difference gradients."""
     cnt = vol.counts
     cx, cy, cz = _cuts(int(cnt[0]), bx), _cuts(int(cnt[1]), by), _cuts(int(cnt[2]), bz)
     org, sp = np.asarray(vol.origin, F), np.asarray(vol.spacing, F)
@@ -650,6 +667,8 @@ def split_volume(vol, bx, by, bz):
                 lo = (org + off.astype(F) * sp).astype(F)
                 hi = (org + end.astype(F) * sp).astype(F)
                 out.append(Brick(d, off, cnt.copy(), org, sp, lo, hi))
+                if ghosts:
+                    out[-1].ghosts = brick_ghosts(vol.data, [int(v) for v in off], [int(v) for v in end])
     return out
 
 

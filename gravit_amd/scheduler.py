@@ -628,6 +628,8 @@ class VolumeTracer:
         bricks = self._same_bricking(self.adapters, bricks)  # (all of them checked before the first one changes)
         for a, b in zip(self.adapters, bricks):
             a.update_samples(b.data)
+            if getattr(b, "ghosts", None) is not None:  # the new step's face layers travel with its bricks
+                a.set_ghosts(b.ghosts)
         return self
 
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
@@ -647,6 +649,12 @@ class VolumeTracer:
             a.set_shading(on)
         return self
 
+    def set_gradient(self, kind):
+        """The gradient kind on every brick (HipVolumeAdapter.set_gradient): "central" needs bricks that carry their ghosts."""
+        for a in self.adapters:
+            a.set_gradient(kind)
+        return self
+
     def framebuffer(self, clamp=False):
         return self.fb.download(clamp)
 
@@ -655,7 +663,8 @@ class VolumeTracer:
         amr = [a.amr_info() for a in self.adapters]
         return {"samples_refined": sum(i["samples_refined"] for i in amr), "amr_marches": sum(i["amr_marches"] for i in amr),
                 "adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in self.adapters), "samples_marched": sum(i["samples_marched"] for i in infos),
-                "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in self.adapters)}
+                "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in self.adapters),
+                "central_marches": sum(a.central_marches() for a in self.adapters)}
 
 
 def _brick_boxes(bricks, m):
@@ -773,6 +782,8 @@ class HipVolumeBackend:
         mine = VolumeTracer._same_bricking(self.local_adapters(), [b for i, b in enumerate(bricks) if self.owned[i]])
         for a, b in zip(self.local_adapters(), mine):
             a.update_samples(b.data)
+            if getattr(b, "ghosts", None) is not None:
+                a.set_ghosts(b.ghosts)
         return self
 
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
@@ -790,6 +801,11 @@ class HipVolumeBackend:
             a.set_shading(on)
         return self
 
+    def set_gradient(self, kind):
+        for a in self.local_adapters():
+            a.set_gradient(kind)
+        return self
+
     def stats(self):
         """VolumeTracer.stats() summed over the owned bricks (the counters run from the adapters' creation)."""
         ads = self.local_adapters()
@@ -797,7 +813,8 @@ class HipVolumeBackend:
         amr = [a.amr_info() for a in ads]
         return {"samples_refined": sum(i["samples_refined"] for i in amr), "amr_marches": sum(i["amr_marches"] for i in amr),
                 "adapter_calls": self.calls, "crossings_rendered": sum(a.crossings() for a in ads), "samples_marched": sum(i["samples_marched"] for i in infos),
-                "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in ads)}
+                "samples_gathered": sum(i["samples_gathered"] for i in infos), "samples_shaded": sum(a.shaded() for a in ads),
+                "central_marches": sum(a.central_marches() for a in ads)}
 
 
 class VolumeDomainTracer(DomainTracer):
@@ -853,6 +870,10 @@ class VolumeDomainTracer(DomainTracer):
 
     def set_shading(self, on=True):
         self.backend.set_shading(on)
+        return self
+
+    def set_gradient(self, kind):
+        self.backend.set_gradient(kind)
         return self
 
     def stats(self):
@@ -911,6 +932,10 @@ class MixedTracer:
 
     def set_shading(self, on=True):
         self.volume.set_shading(on)
+        return self
+
+    def set_gradient(self, kind):
+        self.volume.set_gradient(kind)
         return self
 
     # the scene's

@@ -377,6 +377,8 @@ int gvt_hip_volume_get_info(gvt_hip_volume *, gvt_hip_volume_info *); /* synchro
  * tracers, tops and queues built around it keep working.  The call waits for the calling context's stream first, as _set_transfer does,
  * and returns when it is done; the caller serialises it against frames that use the brick.  Before any _set_transfer it is legal: the
  * tables are then built when the transfer function arrives.  Samples need not be finite (the rules above).
+ * The ghost layers of gvt_hip_volume_set_ghosts are left alone: they still hold the previous step's vertices, and the caller sends the
+ * new step's with another _set_ghosts (until then a CENTRAL gradient next to a face mixes the two steps).
  * GVT_HIP_ERR_DEVICE (a HIP call failed part way): the samples may already be replaced while ranges and tables are not; the volume is then
  * undefined until an update succeeds, and may only be updated again or destroyed.
  * ms_out (may be NULL): time on the context's stream from the end of the upload to the end of the update (ranges, their download, the
@@ -506,15 +508,55 @@ int gvt_hip_volume_get_crossings(gvt_hip_volume *, uint64_t *crossings_rendered)
  * contribution is shaded with the same g.  The clipped march and typed voxels shade alike.
  * Bricking: the interpolant's gradient in the sample's own cell needs that cell's eight vertices only, which the sample's owner holds:
  * no ghost layers, and the image is the same bits for every bricking.
- * DEVIATION from the reference's engines: they shade with central differences of the vertices, a gradient that is continuous across
- * cells.  This one is the gradient of the trilinear interpolant: continuous inside a cell, discontinuous across cell faces (faint facets
- * at low resolution).  Central differences would need the neighbouring bricks' vertices and give up "the same bits for every bricking". */
+ * DEVIATION from the reference's engines, in the DEFAULT gradient kind only: they shade with central differences of the vertices, a
+ * gradient that is continuous across cells.  The default (GVT_HIP_VOLUME_GRADIENT_CELL) is the gradient of the trilinear interpolant:
+ * continuous inside a cell, discontinuous across cell faces (facets at low resolution, plain to see on an isosurface).  A brick that
+ * is given its six ghost faces can shade with central differences instead and keeps "the same bits for every bricking": smooth
+ * gradients, below. */
 #define GVT_HIP_VOLUME_SHADE_NONE 0
 #define GVT_HIP_VOLUME_SHADE_GRADIENT 1
 int gvt_hip_volume_set_shading(gvt_hip_volume *, int mode);        /* any other mode: GVT_HIP_ERR_INVALID, the volume unchanged */
 int gvt_hip_volume_get_shading(gvt_hip_volume *, int *mode_out);
 /* samples shaded by the marches of this volume so far (gvt_hip_volume_info keeps its layout); synchronises, as _get_crossings does */
 int gvt_hip_volume_get_shaded(gvt_hip_volume *, uint64_t *samples_shaded);
+
+/* ---- smooth gradients: central differences at the vertices, interpolated trilinearly, with one ghost layer per interior face ----
+ * The gradient KIND says which gradient shades a crossed isovalue and a lit sample.  CELL (the default) is the one stated above.  CENTRAL:
+ * along an axis of N = global_counts vertices and spacing s, the vertex with GLOBAL index i has im = max(i - 1, 0), ip = min(i + 1, N - 1)
+ * and the component
+ *     (v[ip] - v[im]) / (s * (float)(ip - im))
+ * with the other two indices held and v a global vertex value (float)sample: one subtraction, one multiplication (by 2 or by 1), one
+ * division.  On the global boundary the difference is one-sided.  v[ip] and v[im] are the brick's own samples where it holds them and
+ * the ghost face's otherwise.  A sample's component is the trilinear interpolation of that component at the eight vertices of its cell,
+ * with the sample's fractions and the value's own lerp nesting (x first, then y, then z; lerp(a, b, f) = a + f * (b - a)).  Every
+ * operation is one float32 operation in this order: no contraction, no fast math.
+ * From g on everything is the rule stated above, unchanged: a crossed isovalue tests len > 0; a lit sample tests tc.w > 0, then len > 0 and
+ * len < +Inf; the lights, ka + kd * S and the compositing are the same.  Slice planes keep their own normal.  The kind is inert unless
+ * something is shaded: the plain march has no central variant.  Crossing detection, the sides carried in t, skipping, jumps, the clip,
+ * the flags and the counters do not depend on the kind, so skipping stays exact for the reasons given above (a sample is shaded only
+ * where tc.w > 0 or a crossing is detected, and neither depends on g).  On a volume whose kind is CELL every ray bit is what it was
+ * before the kind existed, a volume switched to CENTRAL and back included.
+ * GHOSTS.  A central difference along an axis reaches one vertex beyond the cell on that axis and none on the others: six face layers
+ * suffice, no edges and no corners.  faces[0..5] = the layer of global vertices just outside the brick at -x, +x, -y, +y, -z, +z;
+ * +-x holds ny*nz samples at index j + ny*k, +-y nx*nz at i + nx*k, +-z nx*ny at i + nx*j (nx, ny, nz: the brick's counts; i, j, k:
+ * the vertex's indices inside the brick).  The samples have the volume's voxel type and are copied; flags: 0 (host pointers) or
+ * GVT_HIP_VOLUME_DEVICE (device pointers: the samples never visit the host).  A call replaces all six: NULL = no layer.  A face lies on
+ * the global boundary when offset[a] == 0 (low side) or offset[a] + counts[a] == global_counts[a] (high side).
+ * GVT_HIP_ERR_INVALID with an error text, the volume exactly as it was: a non-NULL face on the global boundary; a NULL face that is not on
+ * it while the kind is CENTRAL; another voxel type than the volume's; unknown flag bits; a null volume or a null faces.
+ * gvt_hip_volume_update_samples[_typed] leaves the layers alone (see there).
+ * _set_gradient(CENTRAL) is accepted only when every face that is not on the global boundary has a layer, and refused on a volume with
+ * AMR subgrids (as _set_subgrids is on a CENTRAL volume: AMR takes no shading); an unknown kind is refused; each refusal changes nothing.
+ * Bricking: with its faces a brick sees every global vertex a sample it owns can reach, so g is a function of global vertex values
+ * and global indices only, and the image is the same bits for every bricking -- unconditionally, since CENTRAL cannot be set without the
+ * layers.  tests/volume_smooth_checker.py restates the contract in numpy.
+ * central_marches: the launches of this volume that shaded with CENTRAL so far (a march of a CENTRAL volume without surfaces and without
+ * lit shading is the plain one and is not counted). */
+#define GVT_HIP_VOLUME_GRADIENT_CELL 0    /* the interpolant's gradient in the sample's cell: the default */
+#define GVT_HIP_VOLUME_GRADIENT_CENTRAL 1 /* central differences at the vertices, interpolated trilinearly */
+int gvt_hip_volume_set_ghosts(gvt_hip_volume *, const void *const faces[6], int voxel_type, uint32_t flags);
+int gvt_hip_volume_set_gradient(gvt_hip_volume *, int kind);
+int gvt_hip_volume_get_gradient(gvt_hip_volume *, int *kind_out, uint64_t *central_marches_out); /* either may be NULL */
 
 /* ---- geometry inside a volume: a march clipped at a depth plane, and the composite of the two images ----
  * The reference has no counterpart (shuffleRays takes either the mesh or the volume branch, by adapter type): this contract is the

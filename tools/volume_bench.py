@@ -19,6 +19,8 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              plane that is +Inf everywhere (the same rays and samples: what the clip itself costs), frames
                                              alternating in one process; then the mixed frame -- bun_zipper inside the grid
                                              (scheduler.MixedTracer) -- and its parts: mesh frame, depth pass, clipped volume frame, composite
+  python tools/volume_bench.py --shade --gradient central   smooth gradients: per grid size, table and bricking the lit frame and the
+                                             isosurface frame with the CELL and with the CENTRAL gradient, alternating; the ratio
   python tools/volume_bench.py --shade       lit volumes: per grid size, table and bricking the frame unlit, lit by one light and lit by three
                                              (VolumeTracer.set_shading), frames alternating in one process on one tracer; with each the
                                              samples shaded per frame
@@ -187,6 +189,38 @@ def run_shade(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
         out.update({k + "_ms_median": med(v), k + "_ms_min": round(min(v), 3), k + "_ms_max": round(max(v), 3), k + "_samples_shaded": int(shaded[k])})
     for k in ("lit1", "lit3"):
         out[k + "_over_unlit"] = round(out[k + "_ms_median"] / out["unlit_ms_median"], 4)
+    return out
+
+
+SMOOTH_ISO = [0.45, 0.55]
+
+
+def run_smooth(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
+    """The lit frame (three lights) and the isosurface frame (two isovalues, lights, shading off), each with the CELL and with the
+    CENTRAL gradient, alternating on one tracer whose bricks carry their ghost faces: what central differences cost."""
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split, ghosts=True)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32").set_lights(SHADE_LIGHTS)
+    _, lo, hi = DTYPES[dtype]
+    frames = {"lit": lambda: tr.set_surfaces().set_shading(True), "iso": lambda: tr.set_surfaces([lo + v * (hi - lo) for v in SMOOTH_ISO], (), 0.5).set_shading(False)}
+    ms = {(f, g): [] for f in frames for g in ("cell", "central")}
+    count = {}
+    for i in range(warmup + steps):
+        for f, setup in frames.items():
+            setup()
+            for g in ("cell", "central"):
+                tr.set_gradient(g)
+                s0 = tr.stats() if i == warmup else None
+                ms[f, g].append(timed(tr.frame))
+                if i == warmup:
+                    s1 = tr.stats()
+                    count[f, g] = (s1["samples_shaded"] - s0["samples_shaded"], s1["crossings_rendered"] - s0["crossings_rendered"])
+    out = {"mode": "smooth", "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "central_marches": tr.stats()["central_marches"]}
+    for (f, g), v in ms.items():
+        v = v[warmup:]
+        out.update({"%s_%s_ms_median" % (f, g): med(v), "%s_%s_ms_min" % (f, g): round(min(v), 3), "%s_%s_ms_max" % (f, g): round(max(v), 3),
+                    "%s_%s_samples_shaded" % (f, g): int(count[f, g][0]), "%s_%s_crossings" % (f, g): int(count[f, g][1])})
+    for f in frames:
+        out[f + "_central_over_cell"] = round(out[f + "_central_ms_median"] / out[f + "_cell_ms_median"], 4)
     return out
 
 
@@ -440,6 +474,7 @@ def main():
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--shade", action="store_true")
+    ap.add_argument("--gradient", choices=["cell", "central"], default="cell", help="with --shade: central = the lit and the isosurface frame with both gradient kinds")
     ap.add_argument("--amr", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
     ap.add_argument("--domains", type=int, nargs="+", metavar="W")
@@ -491,7 +526,7 @@ def main():
         vol = noise(n, a.dtype)
         for kind in a.tf:
             for split in ((1, 1, 1), (2, 2, 2)):
-                r = run_shade(n, split, a.steps, a.warmup, a.rate, kind, vol, a.dtype)
+                r = (run_smooth if a.gradient == "central" else run_shade)(n, split, a.steps, a.warmup, a.rate, kind, vol, a.dtype)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
     if a.shade:
