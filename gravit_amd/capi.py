@@ -42,6 +42,7 @@ SYMBOLS = [
     "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
     "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
     "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
+    "gvt_hip_volume_frame_fused",
 ]
 
 
@@ -90,6 +91,15 @@ class VolumeAmrInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class VolumeFusedStats(C.Structure):
+    """gvt_hip_volume_fused_stats: what gvt_hip_volume_frame_fused reports of one frame."""
+    _fields_ = [("fused", C.c_uint32), ("pad", C.c_uint32), ("samples_marched", C.c_uint64), ("samples_gathered", C.c_uint64),
+                ("brick_visits", C.c_uint64), ("rays_deposited", C.c_uint64), ("adapter_calls", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
@@ -161,6 +171,7 @@ def load():
         lib.gvt_hip_depth_download.argtypes = [C.c_void_p, C.c_void_p]
         lib.gvt_hip_depth_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gvt_hip_volume_frame_clipped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_frame_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
@@ -242,5 +253,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

@@ -48,6 +48,7 @@ enum ScratchSlot {
   SCR_HOP,         // merged chains with hops: the instance every ray is in now
   SCR_WIRE_TABLE,  // the queue table of a batched wire conversion (trace.hip wire_table)
   SCR_VOL_KEEP,    // the keep mask of gvt_hip_volume_camera_filter on the device (volume.hip)
+  SCR_VOL_BRICKS, SCR_VOL_FUSED, // the fused frame's per-brick records and its four counter words (volume.hip volume_frame_fused)
   SCRATCH_COUNT
 };
 struct Knobs {
@@ -146,7 +147,8 @@ struct Ctx : Knobs {
   unsigned *d_counters = nullptr; // CW_COUNT device counter words (enum CounterWord, gvt_device.h)
   // pinned host scratch for small read-backs
   unsigned *h_pinned = nullptr;
-  // pinned staging of the batched wire conversions' queue table (trace.hip wire_table) and the event behind its last upload
+  // pinned staging of small per-call device tables -- the batched wire conversions' queue table (trace.hip wire_table), the fused volume
+  // frame's brick records (volume.hip) -- and the event behind its last upload: pinned_stage_begin / _end (trace.hip)
   void *h_wire = nullptr;
   hipEvent_t wire_ev = nullptr;
   bool wire_busy = false;
@@ -357,6 +359,12 @@ int launch_wide_visit_stats(gvt_hip_mesh *M, RayPlanes q, size_t n, float tnear,
 int wide_root_marks(gvt_hip_mesh *M, int width, unsigned char *d_marks, size_t *n_wide); // lbvh.hip
 int launch_any_flags(gvt_hip_mesh *M, RayPlanes q, size_t n, bool xform, const Mat4 &minv, float tnear, int *d_flags);
 int set_device_u32(unsigned *p, unsigned v); // stream-ordered store of a host-known value
+// The context's pinned staging block (Ctx::h_wire, PINNED_STAGE_BYTES, made on first use).  _begin: *h = the block, free to be written (it
+// waits for the stream to have read the last upload from it: an event, no stream synchronisation).  The caller fills it, enqueues ONE
+// hipMemcpyAsync from it on the context's stream and calls _end, which records the event behind that copy.
+#define PINNED_STAGE_BYTES (24 * 1024)
+int pinned_stage_begin(void **h);
+int pinned_stage_end();
 // one round's merged launch chain (no host round trip inside); `out` must have room for n_total * (1 + n_lights * passes) rays and
 // is filled from slot 0 (its device count is reset); d_out_from receives the source instance of every ray appended
 struct WaveSingle { // the launch has ONE segment: its queue planes and instance, for the single-mesh kernels

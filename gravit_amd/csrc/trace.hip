@@ -725,6 +725,25 @@ int set_device_u32(unsigned *p, unsigned v) {
 
 // ---- the batched wire pair: all the queues of one exchange message through ONE launch (convert.inc k_queues_to_wire / k_wire_to_queues)
 #define WIRE_MAX_QUEUES 256
+static_assert(sizeof(QueueDesc) * WIRE_MAX_QUEUES + sizeof(unsigned) * (3 * WIRE_MAX_QUEUES + 1) <= PINNED_STAGE_BYTES, "the queue table fits the staging block");
+
+int pinned_stage_begin(void **h) {
+  Ctx &C = gctx();
+  if (!C.h_wire) {
+    HIPCHK(hipHostMalloc(&C.h_wire, PINNED_STAGE_BYTES, hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(&C.wire_ev, hipEventDisableTiming));
+  }
+  if (C.wire_busy) HIPCHK(hipEventSynchronize(C.wire_ev));
+  *h = C.h_wire;
+  return 0;
+}
+int pinned_stage_end() {
+  Ctx &C = gctx();
+  HIPCHK(hipEventRecord(C.wire_ev, C.stream));
+  C.wire_busy = true;
+  return 0;
+}
+
 namespace {
 // The launch's queue table: built in the context's pinned staging block (one block: the event says when its last upload has been read),
 // copied to the context's device copy on the stream.  runs[i]: rays of queue i in the message; append: they go behind the queue's fill
@@ -732,14 +751,12 @@ int wire_table(gvt_hip_queue *const *queues, size_t n, const uint64_t *runs, boo
   Ctx &C = gctx();
   const size_t o_begin = sizeof(QueueDesc) * n, o_off = o_begin + sizeof(unsigned) * (n + 1), o_fill = o_off + sizeof(unsigned) * n,
                bytes = o_fill + sizeof(unsigned) * n;
-  if (!C.h_wire) {
-    HIPCHK(hipHostMalloc(&C.h_wire, sizeof(QueueDesc) * WIRE_MAX_QUEUES + sizeof(unsigned) * (3 * WIRE_MAX_QUEUES + 1), hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&C.wire_ev, hipEventDisableTiming));
-  }
   char *d = (char *)scratch_get(SCR_WIRE_TABLE, bytes);
   if (!d) return GVT_HIP_ERR_DEVICE;
-  if (C.wire_busy) HIPCHK(hipEventSynchronize(C.wire_ev));
-  char *h = (char *)C.h_wire;
+  void *stage = nullptr;
+  int rc;
+  if ((rc = pinned_stage_begin(&stage))) return rc;
+  char *h = (char *)stage;
   QueueDesc *q = (QueueDesc *)h;
   unsigned *begin = (unsigned *)(h + o_begin), *off = (unsigned *)(h + o_off), *fill = (unsigned *)(h + o_fill);
   unsigned at = 0;
@@ -752,8 +769,7 @@ int wire_table(gvt_hip_queue *const *queues, size_t n, const uint64_t *runs, boo
   }
   begin[n] = at;
   HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, C.stream));
-  HIPCHK(hipEventRecord(C.wire_ev, C.stream));
-  C.wire_busy = true;
+  if ((rc = pinned_stage_end())) return rc;
   W.q = (const QueueDesc *)d; W.begin = (const unsigned *)(d + o_begin); W.off = (const unsigned *)(d + o_off); W.fill = (const unsigned *)(d + o_fill);
   W.n = (int)n;
   return 0;

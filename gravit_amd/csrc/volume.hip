@@ -15,6 +15,8 @@
 //   k_volume_march_amr / k_amr_ranges       AMR volumes (Volume::AddAMRGrid): nested refined subgrids inside a brick, volume_amr.inc
 //   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
 //                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
+//   gvt_hip_volume_frame_fused / k_volume_march_fused   the same frame over bricks of ONE grid in one launch: a lane carries its ray from brick to
+//                                           brick (volume_fused.inc); every other frame takes the loop
 //   gvt_hip_volume_march_queue / _camera_filter   the Domain scheduler's steps over bricks spread over ranks (algorithm/DomainTracer.h:148-326): the march
 //                                           on a device queue, and the camera step with shuffleDropRays' keep mask (k_vol_classify<MASK>); the
 //                                           exchange's batched wire conversions are beside k_planes_to_aos (convert.inc, trace.hip)
@@ -40,6 +42,7 @@ struct gvt_hip_volume {
   bool has_tf = false;
   float tf_lo = 0.f, tf_hi = 1.f;
   float tf_a[256] = {};          // the table's corrected opacities (d_tf[i].w): what rebuild_tables reads after an update of the samples
+  float tf_rgb[256][3] = {};     // ... and its colours (d_tf[i].xyz): with tf_a the host's copy of the table (the fused frame compares the bricks' tables)
   int vtype = GVT_HIP_VOXEL_F32;   // the voxel type, fixed at creation: d_vox holds the samples at that width and nothing wider exists
   void *d_vox = nullptr;
   float4 *d_tf = nullptr;        // 256 x (r, g, b, corrected a)
@@ -836,6 +839,7 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 }
 
 #include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges
+#include "volume_fused.inc" // k_volume_march_fused
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
@@ -1249,7 +1253,7 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   }
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
   HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
-  for (int i = 0; i < 256; i++) V->tf_a[i] = tf[i].w;
+  for (int i = 0; i < 256; i++) { V->tf_a[i] = tf[i].w; V->tf_rgb[i][0] = tf[i].x; V->tf_rgb[i][1] = tf[i].y; V->tf_rgb[i][2] = tf[i].z; }
   V->tf_lo = value_lo; V->tf_hi = value_hi; V->has_tf = true;
   return rebuild_tables(V);
 }
@@ -1520,9 +1524,9 @@ extern "C" int gvt_hip_volume_march_queue(gvt_hip_volume *V, gvt_hip_queue *queu
   return volume_march(V, queue, minv, (flags & GVT_HIP_MARCH_MAY_CLIP) != 0);
 }
 
-// gvt_hip_volume_frame and gvt_hip_volume_frame_clipped (depth: the plane the camera's rays are clipped at, or null)
-static int volume_frame_impl(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
-                             gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
+// the frame entry points' argument errors (nothing has changed when one is returned): the loop's and the fused frame's
+static int volume_frame_args(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                             gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth) {
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!T || !cam || !fb || (n_inst && (!volumes || !m || !minv || !queues)) || T->n != n_inst) {
     set_error("volume_frame: null or inconsistent argument");
@@ -1536,7 +1540,14 @@ static int volume_frame_impl(gvt_hip_top *T, gvt_hip_volume *const *volumes, con
               cam->samples, cam->samples);
     return GVT_HIP_ERR_INVALID;
   }
+  return 0;
+}
+
+// gvt_hip_volume_frame and gvt_hip_volume_frame_clipped (depth: the plane the camera's rays are clipped at, or null)
+static int volume_frame_impl(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                             gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
   int rc;
+  if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;                                                  // clearBuffer :142
   for (size_t i = 0; i < n_inst; i++) if ((rc = gvt_hip_queue_clear(queues[i]))) return rc;
   if ((rc = volume_camera_step(T, cam, queues, fb, depth, nullptr))) return rc;               // generateRays :137 + shuffleRays(rays, -1)
@@ -1563,6 +1574,97 @@ extern "C" int gvt_hip_volume_frame(gvt_hip_top *T, gvt_hip_volume *const *volum
 extern "C" int gvt_hip_volume_frame_clipped(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
                                             gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint64_t *adapter_calls) {
   return volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, adapter_calls);
+}
+
+// ---- the fused frame (the contract: include/gvt_hip.h, "fused frame"; the kernel: volume_fused.inc)
+namespace {
+
+bool same_bits(const void *a, const void *b, size_t bytes) { return std::memcmp(a, b, bytes) == 0; }
+
+// Eligibility, decided per call from the volumes as they are now: bricks of ONE grid (global origin, spacing, dt, table, value range, skip
+// flag and minv equal as bits), one voxel type, and nothing the plain march does not do -- no surfaces, no subgrids, no lit shading (the
+// gradient kind is inert then)
+bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst) {
+  if (n_inst < 1 || n_inst > VOL_DEST_MAX) return false;
+  const gvt_hip_volume *A = volumes[0];
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    if (!B->has_tf || B->n_iso + B->n_pl > 0 || !B->sub.empty() || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0)) return false;
+    if (B->vtype != A->vtype || B->skip != A->skip) return false;
+    if (!same_bits(B->go, A->go, sizeof(A->go)) || !same_bits(B->sp, A->sp, sizeof(A->sp)) || !same_bits(&B->dt, &A->dt, sizeof(float))) return false;
+    if (!same_bits(&B->tf_lo, &A->tf_lo, sizeof(float)) || !same_bits(&B->tf_hi, &A->tf_hi, sizeof(float))) return false;
+    if (!same_bits(B->tf_a, A->tf_a, sizeof(A->tf_a)) || !same_bits(B->tf_rgb, A->tf_rgb, sizeof(A->tf_rgb))) return false;
+    if (!same_bits(minv + 16 * i, minv, 16 * sizeof(float))) return false;
+  }
+  return true;
+}
+
+// the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back)
+int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
+                       gvt_hip_fb *fb, const gvt_hip_depth *depth, gvt_hip_volume_fused_stats &S) {
+  Ctx &C = gctx();
+  int rc;
+  if ((rc = gvt_hip_fb_clear(fb))) return rc;
+  for (size_t i = 0; i < n_inst; i++) if ((rc = gvt_hip_queue_clear(queues[i]))) return rc;
+  if (!staging_queues(C)) return GVT_HIP_ERR_DEVICE;
+  gvt_hip_queue *q_cam = C.abi_qout; // (volume_camera_step's staging list)
+  if ((rc = gvt_hip_camera_generate_tiled(q_cam, cam->eye, cam->focus, cam->up, cam->fov, cam->width, cam->height, cam->samples, 0,
+                                          cam->jitter_window_size, 8))) return rc;
+  const size_t n = q_cam->size;
+  FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
+  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_STATS * sizeof(unsigned long long));
+  unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
+  if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
+  static_assert(sizeof(FusedBrick) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table fits the staging block");
+  void *stage = nullptr;
+  if ((rc = pinned_stage_begin(&stage))) return rc;
+  FusedBrick *h = (FusedBrick *)stage;
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    FusedBrick R{};
+    R.vox = B->d_vox; R.mc = B->d_mc;
+    R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
+    for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
+    h[i] = R;
+  }
+  HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if ((rc = pinned_stage_end())) return rc;
+  HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
+  HIPCHK(hipMemsetAsync(d_stats, 0, VOL_FUSED_STATS * sizeof(unsigned long long), C.stream));
+  Mat4 M;
+  for (int k = 0; k < 16; k++) M.m[k] = minv[k];
+  const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
+  const RayPlanes P = make_planes(q_cam->d_planes, q_cam->cap);
+  const unsigned n_pix = (unsigned)(fb->w * fb->h);
+  if (n)
+    with_voxel_type(volumes[0]->vtype, [&](auto t) {
+      using VT = decltype(t);
+      if (depth) k_volume_march_fused<VT, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
+                                                                                   (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
+      else k_volume_march_fused<VT, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, nullptr, 0u, fb->d_rgba,
+                                                                               n_pix, work, d_stats);
+    });
+  HIPCHK(hipGetLastError());
+  unsigned long long *h_stats = (unsigned long long *)(C.h_pinned + 16); // (pinned words 16..23 of the context)
+  HIPCHK(hipMemcpyAsync(h_stats, d_stats, VOL_FUSED_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.stream));
+  if ((rc = gvt_hip_queue_clear(q_cam))) return rc;
+  HIPCHK(hipStreamSynchronize(C.stream));
+  S.fused = 1; S.adapter_calls = 1;
+  S.samples_marched = h_stats[0]; S.samples_gathered = h_stats[1]; S.brick_visits = h_stats[2]; S.rays_deposited = h_stats[3];
+  return 0;
+}
+
+} // namespace
+
+extern "C" int gvt_hip_volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                                          gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, gvt_hip_volume_fused_stats *stats) {
+  int rc;
+  if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
+  gvt_hip_volume_fused_stats S{};
+  if (fused_eligible(volumes, minv, n_inst)) rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, S);
+  else rc = volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, &S.adapter_calls); // (not an error: the loop, fused = 0)
+  if (!rc && stats) *stats = S;
+  return rc;
 }
 
 // ---- AMR volumes: the host side of volume_amr.inc (the contract: include/gvt_hip.h, "AMR volumes")

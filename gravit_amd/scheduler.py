@@ -559,9 +559,11 @@ class DomainTracer:
 class VolumeTracer:
     """Tracer<ImageScheduler> over the bricks of one volume instance (gvt_hip_volume_frame): bricks = scenes.split_volume(...) (or one
     VolumeData), m = the instance's matrix (None: identity).  Bricks may carry AMR subgrids (scenes.split_amr_volume, scenes.refine).  The world box of a brick is its box under m (scenes.instance_bbox).
-    native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width)."""
+    native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width).
+    fused: frame() goes through gvt_hip_volume_frame_fused -- every brick in ONE march launch where the frame is eligible (plain bricks of
+    one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop."""
 
-    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False):
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -580,6 +582,8 @@ class VolumeTracer:
         self.queues = [RayQueue() for _ in range(self.n_inst)]
         self.fb = FrameBuffer(camera.width, camera.height)
         self.calls = 0
+        self.fused = bool(fused)
+        self.fused_stats = None  # fused=True: gvt_hip_volume_fused_stats of the last frame, as a dict
         self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
 
     def frame(self, depth=None):
@@ -593,7 +597,14 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        if depth is None:
+        if self.fused:
+            st = capi.VolumeFusedStats()
+            capi.check(capi.load().gvt_hip_volume_frame_fused(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                              C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
+                                                              C.byref(st)), "gvt_hip_volume_frame_fused")
+            self.fused_stats = st.as_dict()
+            calls = C.c_uint64(st.adapter_calls)
+        elif depth is None:
             capi.check(capi.load().gvt_hip_volume_frame(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
                                                         C.byref(pod), self._arr(self.queues), self.fb.h, C.byref(calls)), "gvt_hip_volume_frame")
         else:
@@ -659,6 +670,17 @@ class VolumeTracer:
         return self.fb.download(clamp)
 
     def stats(self):
+        """The bricks' counters summed (they accumulate over frames).  fused=True adds fused, brick_visits and rays_deposited of the last
+        frame, and where that frame was fused samples_marched / samples_gathered are ITS counts: the bricks' own did not move."""
+        out = self._brick_stats()
+        if self.fused and self.fused_stats is not None:
+            f = self.fused_stats
+            out.update(fused=f["fused"], brick_visits=f["brick_visits"], rays_deposited=f["rays_deposited"])
+            if f["fused"]:
+                out.update(samples_marched=f["samples_marched"], samples_gathered=f["samples_gathered"])
+        return out
+
+    def _brick_stats(self):
         infos = [a.info() for a in self.adapters]
         amr = [a.amr_info() for a in self.adapters]
         return {"samples_refined": sum(i["samples_refined"] for i in amr), "amr_marches": sum(i["amr_marches"] for i in amr),
@@ -890,7 +912,7 @@ class MixedTracer:
     (gvt_hip_fb_composite_over; the result is in the volume tracer's framebuffer).  The reference has no such path: shuffleRays
     takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel)."""
 
-    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT):
+    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -901,7 +923,7 @@ class MixedTracer:
         self.camera = camera
         self.mesh = NativeTracer(self.scene, normal_mode)
         self.depth = DepthPlane(camera.width, camera.height)
-        self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native)
+        self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused)  # (fused: its clipped frame in one launch)
 
     def frame(self):
         self.mesh()

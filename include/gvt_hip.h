@@ -703,6 +703,51 @@ int gvt_hip_queues_export_wire(gvt_hip_queue *const *queues, size_t n, gvt_hip_r
                                uint64_t *total_out);
 int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt_hip_ray *src_device, const uint64_t *counts /* n */);
 
+/* ---- fused frame: every brick of a bricked volume marched in ONE launch (opt-in; gvt_hip_volume_frame stays the default) ----
+ * gvt_hip_volume_frame renders a bricked volume brick by brick: one march launch, one three-kernel shuffle and one host wait per round.
+ * The fused frame generates the camera's list once (gvt_hip_camera_generate_tiled into the context's staging list, as the loop does),
+ * launches ONE kernel in which every lane carries its ray from brick to brick until it deposits, and waits for the host once.
+ * CONTRACT.  The fused frame is DEFINED BY THE LOOP.  For every eligible input (below) with ONE sample per pixel, the framebuffer after
+ * gvt_hip_volume_frame_fused equals the framebuffer after gvt_hip_volume_frame (depth == NULL) / gvt_hip_volume_frame_clipped on the
+ * same arguments IN EVERY BIT; no tolerance applies.  Why: a ray's march and its next-brick decision read that ray alone, so the fused
+ * ray passes through exactly the states the loop's ray passes through between its visits:
+ *   - first brick: a camera ray starts with colour 0, opacity 0 and flags 0; under a depth plane with t_max = depth[id] and
+ *     GVT_HIP_RAY_CLIP where that is below +Inf (the loop's scatter of fresh rays).  Its first brick is the shuffle's rule from -1 (the
+ *     nearest box the ray enters, tn < t_max under the clip).  With no first brick the ray is dropped and deposits nothing;
+ *   - visit of brick b: the lattice range of the ray in b's vertex box from the ray's current t_min (and its clip), then the plain
+ *     march's per-sample steps -- the same device functions as gvt_hip_volume_trace's kernels, once in the source: cell ownership, the
+ *     macro-cell test and its verified jump, the trilinear gather, the front-to-back accumulation; the arrives-opaque rule, the
+ *     contiguity rule and the limit of 2^22 lattice positions per visit apply;
+ *   - leaving b: t_min = (float)k_last * dt if the visit owned a sample, unchanged otherwise.  opacity >= GVT_HIP_VOLUME_OPAQUE_A ends
+ *     the ray: it deposits.  Otherwise the shuffle's rule from b names the next brick; none (EXTERNAL): it deposits;
+ *   - progress: the next visit's first lattice index comes from t_min on the float (the first k with k * dt > t_min), not from
+ *     k_last + 1: one statement of the lattice;
+ *   - deposit: four atomic adds (r, g, b, opacity) into the cleared framebuffer at the ray's pixel (id < width * height), as the shuffle
+ *     deposits.  With samples > 1 a pixel's deposits meet in arrival order, as in the loop: not bit-exact, not promised.
+ * ELIGIBILITY is decided at every call from the volumes' current state (no object is kept between frames): 1 <= n_inst <= 256; every
+ * volume has a transfer function; all bricks have one voxel type; no brick has surfaces, subgrids or effective lit shading
+ * (GVT_HIP_VOLUME_SHADE_GRADIENT with at least one light; the gradient kind is inert otherwise); and the bricks are bricks of ONE grid:
+ * global origin, spacing, dt, the 256-entry table, the table's value range, the skip flag and the minv of every instance are equal as
+ * bits across the bricks.  An ineligible call is NOT an error: the loop runs with the queues given and stats->fused = 0.
+ * Argument errors are gvt_hip_volume_frame's / _clipped's (GVT_HIP_ERR_INVALID, nothing changed).
+ * queues are used by the fallback only; a fused frame leaves them cleared.  The per-brick counters of the volumes (gvt_hip_volume_info's
+ * samples_marched / samples_gathered) are NOT touched by a fused frame: its counters are the call's own, below.
+ * OUT OF SCOPE.  Surfaces, lit shading, central gradients and AMR inside the fused kernel (such frames take the loop); bricks of
+ * different grids, tables or matrices; the Domain scheduler (a rank fusing the bricks it owns needs rays that leave for foreign bricks
+ * appended to outgoing queues inside the kernel); fused as the default. */
+typedef struct {
+  uint32_t fused;            /* 1: the fused kernel ran; 0: the loop did (the frame was not eligible) */
+  uint32_t pad;
+  uint64_t samples_marched;  /* fused: the sums over the bricks of what the loop adds to each brick's gvt_hip_volume_info for the same */
+  uint64_t samples_gathered; /*        frame; 0 after the loop (the bricks' own counters moved instead) */
+  uint64_t brick_visits;     /* fused: (ray, brick) visits = the sum of the loop's queue sizes over its rounds; 0 after the loop */
+  uint64_t rays_deposited;   /* fused: deposits; 0 after the loop */
+  uint64_t adapter_calls;    /* march launches: 1 for a fused frame, the loop's count otherwise */
+} gvt_hip_volume_fused_stats;
+int gvt_hip_volume_frame_fused(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m /* n_inst*16 */, const float *minv, size_t n_inst,
+                               const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth /* may be NULL */,
+                               gvt_hip_volume_fused_stats *stats /* may be NULL */);
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

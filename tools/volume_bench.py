@@ -37,6 +37,10 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              VolumeTracer.frame() (W = 1 against it prices the Python loop) and, with --per-queue, the same
                                              frames exchanging through one gvt_hip_queue_export / _append call per brick.  W > 1 on one GPU
                                              SHARES the device: this measures the protocol's overhead, not scaling
+  python tools/volume_bench.py --fused       the fused frame (gvt_hip_volume_frame_fused): per grid size, table and bricking (1, 8 and 64
+                                             bricks; --bricks to choose) the loop frame and the fused frame alternating frame by frame on ONE
+                                             tracer in one process: median [min .. max] of each, brick visits, samples per second; "fused_wins" only
+                                             where the fused maximum lies below the loop's minimum
 """
 import argparse
 import json
@@ -162,6 +166,40 @@ def run_clip(n, split, steps, warmup, rate, vol, dtype="f32"):
     return {"mode": "clip_inf", "n": n, "dtype": dtype, "bricks": int(np.prod(split)), "plain_ms_median": med(plain), "plain_ms_min": round(min(plain), 3),
             "plain_ms_max": round(max(plain), 3), "clipped_ms_median": med(clipped), "clipped_ms_min": round(min(clipped), 3), "clipped_ms_max": round(max(clipped), 3),
             "clipped_over_plain": round(float(np.median(clipped)) / float(np.median(plain)), 4)}
+
+
+FUSED_SPLITS = {1: (1, 1, 1), 8: (2, 2, 2), 64: (4, 4, 4)}
+
+
+def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
+    """The loop frame against the fused frame, alternating frame by frame on one tracer (VolumeTracer.fused switches the entry point)."""
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True)
+    loop, fused = [], []
+
+    def frame(flag):
+        tr.fused = flag
+        tr.frame()
+
+    for i in range(warmup + steps):
+        loop.append(timed(lambda: frame(False)))
+        loop_calls = tr.calls
+        fused.append(timed(lambda: frame(True)))
+    loop, fused = loop[warmup:], fused[warmup:]
+    st = tr.stats()
+    same = None
+    if steps:  # (one more pair, compared: the two paths promise the same bits)
+        frame(False)
+        a = tr.framebuffer(False).copy()
+        frame(True)
+        same = bool((a.view(np.uint32) == tr.framebuffer(False).view(np.uint32)).all())
+    return {"mode": "fused", "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "loop_ms_median": med(loop),
+            "loop_ms_min": round(min(loop), 3), "loop_ms_max": round(max(loop), 3), "loop_adapter_calls": int(loop_calls), "fused_ms_median": med(fused),
+            "fused_ms_min": round(min(fused), 3), "fused_ms_max": round(max(fused), 3), "fused": int(st["fused"]), "brick_visits": int(st["brick_visits"]),
+            "rays_deposited": int(st["rays_deposited"]), "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]),
+            "loop_gsamples_per_s": round(st["samples_marched"] / float(np.median(loop)) / 1e6, 3),
+            "fused_gsamples_per_s": round(st["samples_marched"] / float(np.median(fused)) / 1e6, 3),
+            "fused_over_loop": round(float(np.median(fused)) / float(np.median(loop)), 4), "fused_wins": bool(max(fused) < min(loop)), "same_bits": same}
 
 
 SHADE_LIGHTS = [((3.0, 4.0, 5.0), (1.0, 0.9, 0.8)), ((-2.0, 1.0, 0.5), (0.2, 0.3, 0.4)), ((0.0, -6.0, 1.0), (0.5, 0.1, 0.3))]
@@ -481,6 +519,8 @@ def main():
     ap.add_argument("--per-queue", action="store_true")
     ap.add_argument("--overlap", action="store_true")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
+    ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--bricks", type=int, nargs="+", choices=sorted(FUSED_SPLITS), default=sorted(FUSED_SPLITS), help="with --fused: the brickings")
     a = ap.parse_args()
     if a.update or a.domains:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
@@ -512,6 +552,15 @@ def main():
             for r in run_amr(n, a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate):
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
+        a.sizes = []
+    for n in a.sizes if a.fused else ():
+        vol = noise(n, a.dtype)
+        for kind in a.tf:
+            for nb in a.bricks:
+                r = run_fused(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, a.dtype)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    if a.fused:
         a.sizes = []
     for n in a.sizes if a.clip else ():
         vol = noise(n, a.dtype)
