@@ -1535,6 +1535,19 @@ static int volume_frame_args(gvt_hip_top *T, gvt_hip_volume *const *volumes, con
   if (n_inst > VOL_DEST_MAX) { set_error("volume_frame: %zu bricks, at most %d", n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
   for (size_t i = 0; i < n_inst; i++)
     if (!volumes[i] || !queues[i] || !volumes[i]->has_tf) { set_error("volume_frame: brick %zu has no volume, queue or transfer function", i); return GVT_HIP_ERR_INVALID; }
+  // several bricks under a matrix that turns or shears them (gvt_hip.h, "bricks under a matrix"): their world boxes overlap and vol_next would skip bricks.
+  // Allowed: one non-zero entry per row and column of the 3x3 block (a signed, scaled axis permutation)
+  for (size_t i = 0; n_inst > 1 && i < n_inst; i++) {
+    const float *mi = m + 16 * i;
+    for (int a = 0; a < 3; a++) {
+      int in_col = 0, in_row = 0;
+      for (int b = 0; b < 3; b++) { in_col += mi[4 * a + b] != 0.0f; in_row += mi[4 * b + a] != 0.0f; }
+      if (in_col != 1 || in_row != 1) {
+        set_error("volume_frame: %zu bricks, and the matrix of brick %zu rotates or shears it: the world boxes of neighbouring bricks overlap and bricks would be skipped", n_inst, i);
+        return GVT_HIP_ERR_INVALID;
+      }
+    }
+  }
   if (depth && (cam->samples != 1 || depth->w != cam->width || depth->h != cam->height)) {
     set_error("volume_frame_clipped: a %d x %d depth plane for a %d x %d film of %d x %d samples per pixel (one is needed)", depth->w, depth->h, cam->width, cam->height,
               cam->samples, cam->samples);

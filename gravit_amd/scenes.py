@@ -84,11 +84,18 @@ def instance_matrices(m16):
 
 
 def instance_bbox(m16, lo, hi):
-    """Box3D(M*min, M*max): only the two corners are transformed (api.cpp:309-312)."""
+    """The world box of all eight corners of [lo, hi] taken through M.  A departure from the reference, which transforms only the two
+    corners, Box3D(M*min, M*max) (api.cpp:309-312): it never builds a rotated instance, and under a rotation that is no multiple of 90
+    degrees the box of two corners does not contain the instance -- the top level would cull rays that hit it.  Where M's 3x3 block is
+    diagonal (every scene the reference builds) each world coordinate depends on one object coordinate alone, and the result is the
+    two-corner box bit for bit: the corners go through the same float32 product as before."""
     M = m16.reshape(4, 4).T
-    a = (M @ np.array([lo[0], lo[1], lo[2], 1], F)).astype(F)[:3]
-    b = (M @ np.array([hi[0], hi[1], hi[2], 1], F)).astype(F)[:3]
-    return np.minimum(a, b), np.maximum(a, b)
+    c = [(M @ np.array([x, y, z, 1], F)).astype(F)[:3] for z in (lo[2], hi[2]) for y in (lo[1], hi[1]) for x in (lo[0], hi[0])]
+    a, b = c[0], c[7]  # M*min and M*max first, as before
+    lo_w, hi_w = np.minimum(a, b), np.maximum(a, b)
+    for p in c[1:7]:
+        lo_w, hi_w = np.minimum(lo_w, p), np.maximum(hi_w, p)
+    return lo_w, hi_w
 
 
 def add_faces_1based(verts, faces1):

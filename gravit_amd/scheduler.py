@@ -572,6 +572,7 @@ class VolumeTracer:
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         self.camera = camera
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
+        _refuse_turned_bricks(self.m, len(bricks), "VolumeTracer")
         self.minv = instance_matrices(self.m)[0]
         self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native) for b in bricks]
         for a in self.adapters:
@@ -689,6 +690,24 @@ class VolumeTracer:
                 "central_marches": sum(a.central_marches() for a in self.adapters)}
 
 
+def axis_aligned_matrix(m):
+    """True if the 3x3 block of the column-major m[16] is a signed, scaled axis permutation (one non-zero entry per row and column, a
+    diagonal block among them): the instance's axes stay parallel to the world's, so the world box of a brick IS the brick."""
+    nz = np.asarray(m, np.float32).reshape(4, 4)[:3, :3] != 0
+    return bool((nz.sum(axis=0) == 1).all() and (nz.sum(axis=1) == 1).all())
+
+
+def _refuse_turned_bricks(m, n_bricks, who):
+    """Several bricks under a matrix that turns or shears them are refused: the world boxes of neighbouring bricks then overlap, and the
+    next-brick rule (vol_next: a brick is entered only if its exit lies strictly beyond the last brick's) skips a brick whose box ends
+    inside its neighbour's -- samples would be lost without a word (include/gvt_hip.h, "bricks under a matrix").  One brick is marched
+    under any affine matrix."""
+    if n_bricks > 1 and not axis_aligned_matrix(m):
+        raise ValueError("%s: %d bricks under a matrix that rotates or shears them: the world boxes of neighbouring bricks overlap and the "
+                         "next-brick rule would skip bricks (samples lost); use one brick, or a matrix whose 3x3 block is a signed, scaled "
+                         "axis permutation" % (who, n_bricks))
+
+
 def _brick_boxes(bricks, m):
     """The world boxes of bricks under the instance matrix m, as VolumeTracer places them."""
     from .scenes import instance_bbox
@@ -714,6 +733,7 @@ class HipVolumeBackend:
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         self.camera = camera
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
+        _refuse_turned_bricks(self.m, len(bricks), "HipVolumeBackend")
         self.minv = instance_matrices(self.m)[0]
         self.n_inst = len(bricks)
         self.owned = [True] * self.n_inst if owned is None else [bool(o) for o in owned]
@@ -851,6 +871,9 @@ class VolumeDomainTracer(DomainTracer):
     def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False):
         from types import SimpleNamespace
 
+        bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
+        if m is not None:  # (whatever backend marches the bricks: the next-brick rule is the same)
+            _refuse_turned_bricks(m, len(bricks), "VolumeDomainTracer")
         self.overlap = overlap
         self.scene = SimpleNamespace(camera=camera)  # (what the shared loops and the composite read of a scene)
         self.camera = camera
@@ -919,6 +942,8 @@ class MixedTracer:
 
         if camera.samples != 1:
             raise ValueError("MixedTracer: the depth plane holds one ray per pixel (camera.samples must be 1)")
+        if m is not None:  # before the mesh tracer and the depth plane are made
+            _refuse_turned_bricks(m, len(bricks) if isinstance(bricks, (list, tuple)) else 1, "MixedTracer")
         self.scene = replace(scene, camera=camera)
         self.camera = camera
         self.mesh = NativeTracer(self.scene, normal_mode)

@@ -150,7 +150,9 @@ int gvt_hip_mesh_update_vertices(gvt_hip_mesh *, const float *verts /* nV*3 */, 
  * rays[begin,end) are traced (end==0 -> n_rays, EmbreeMeshAdapter.cpp:642) and updated in place like the
  * reference's rayList (t, and origin/direction/w/depth/type on a bounce).  rays_out receives every
  * PRIMARY/SECONDARY ray that missed and every un-occluded SHADOW ray (moved_rays); order unspecified.
- * If cap is too small: returns GVT_HIP_ERR_CAPACITY, *n_out = needed count, rays_out untouched. */
+ * If cap is too small: returns GVT_HIP_ERR_CAPACITY, *n_out = needed count, rays_out untouched.
+ * m / minv / normi: any affine instance matrix (rotation, non-uniform scale, shear, mirroring) and what api.cpp:307-308 makes of it.
+ * Projective matrices are not supported: the bottom row (m[3], m[7], m[11], m[15]) is taken to be 0 0 0 1 and overwritten. */
 int gvt_hip_trace(gvt_hip_mesh *, gvt_hip_ray *rays, size_t n_rays, size_t begin, size_t end, gvt_hip_ray *rays_out,
                   size_t cap, size_t *n_out, const float m[16], const float minv[16], const float normi[9],
                   const gvt_hip_light *lights, size_t n_lights, int normal_mode, uint32_t seed);
@@ -290,7 +292,8 @@ gvt_hip_tracer *gvt_hip_tracer_create(gvt_hip_top *, gvt_hip_mesh *const *meshes
                                       int normal_mode, const gvt_hip_camera *cam, gvt_hip_fb *fb);
 void gvt_hip_tracer_destroy(gvt_hip_tracer *);
 int gvt_hip_tracer_set_camera(gvt_hip_tracer *, const gvt_hip_camera *cam);
-/* Rigid motion: the next frame's instance matrices (n_inst as at create), replacing the tracer's copies (stream-ordered). */
+/* Rigid motion: the next frame's instance matrices (n_inst as at create), replacing the tracer's copies (stream-ordered).  Any affine
+ * matrix is taken (gvt_hip_trace); the caller updates the top level's boxes to match (gvt_hip_top_update). */
 int gvt_hip_tracer_set_transforms(gvt_hip_tracer *, const float *m /* n_inst*16 */, const float *minv, const float *normi /* n_inst*9 */, size_t n_inst);
 /* mpiInstanceMap (DomainTracer.h:115-144): owner[i] = rank holding instance i.  comm == NULL (or never called): one rank, Image scheduler. */
 int gvt_hip_tracer_set_domains(gvt_hip_tracer *, const int32_t *owner /* n_inst */, gvt_hip_comm *comm);
@@ -730,6 +733,16 @@ int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt
  * global origin, spacing, dt, the 256-entry table, the table's value range, the skip flag and the minv of every instance are equal as
  * bits across the bricks.  An ineligible call is NOT an error: the loop runs with the queues given and stats->fused = 0.
  * Argument errors are gvt_hip_volume_frame's / _clipped's (GVT_HIP_ERR_INVALID, nothing changed).
+ * BRICKS UNDER A MATRIX (the loop, the clipped and the fused frame alike).  One brick is marched under any affine matrix.  SEVERAL bricks
+ * need a matrix whose 3x3 block is a signed, scaled axis permutation (one non-zero entry per row and column; a diagonal block among
+ * them): then the world box of a brick is the brick, and neighbours share a face.  Under a rotation by anything but a multiple of 90
+ * degrees, or a shear, the world boxes of neighbouring bricks overlap, and the next-brick rule -- a brick is entered only if the ray
+ * leaves it strictly later than it left the last one -- skips a brick whose box ends inside its neighbour's: samples are lost (measured
+ * on the numpy restatement: up to 94 of 932 lit pixels of a 64 x 48 film differ from the one-brick frame, by up to 0.99).  The three
+ * frame entry points refuse such a call (n_inst > 1) with GVT_HIP_ERR_INVALID.  The refusal looks at the matrices alone and is
+ * conservative: it also refuses instances that are not bricks of one grid and whose world boxes happen to be disjoint, which would be
+ * marched correctly.  gvt_hip_shuffle_volume, which sees boxes only, cannot refuse: a caller that drives the bricks itself (the Domain
+ * scheduler's backend) must make the same check.
  * queues are used by the fallback only; a fused frame leaves them cleared.  The per-brick counters of the volumes (gvt_hip_volume_info's
  * samples_marched / samples_gathered) are NOT touched by a fused frame: its counters are the call's own, below.
  * OUT OF SCOPE.  Surfaces, lit shading, central gradients and AMR inside the fused kernel (such frames take the loop); bricks of

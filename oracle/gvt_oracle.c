@@ -630,6 +630,14 @@ void orc_math_probe(int kind, const float *in, size_t n, float *out) {
   }
 }
 
+void orc_matrix_probe(int kind, const float *m, const float *v, size_t n, float *out) {
+  for (size_t i = 0; i < n; i++) {
+    const v3 x = ld3(v + 3 * i);
+    const v3 r = kind == 0 ? xfm_point(m, x) : kind == 1 ? xfm_vector(m, x) : mat3_mul(m, x);
+    out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+  }
+}
+
 typedef struct {
   const orc_mesh *M;
   orc_ray *rays;

@@ -118,6 +118,8 @@ void orc_cos_weighted_dir(const float n[3], uint32_t *seed, float out[3]);
 /* include/gvt_math.h evaluated on the host, element-wise: kind 0 gvt_sinf(x), 1 gvt_cosf(x), 2 (float)gvt_acos(sqrt(1.0 - x)),
  * and the libm calls the reference makes in their place: 16 sinf, 17 cosf, 18 (float)acos(sqrt(1.0 - x)) */
 void orc_math_probe(int kind, const float *in, size_t n, float *out);
+/* the matrix products Adapter::trace makes, on n vectors v[3n]: kind 0 xfm_point(m[16], v), 1 xfm_vector(m[16], v), 2 mat3_mul(m[9], v) */
+void orc_matrix_probe(int kind, const float *m, const float *v, size_t n, float *out);
 
 /* ---- camera (gvtCamera.cpp:89-171, 233-312) ---- */
 void orc_camera_generate(const float eye[3], const float focus[3], const float up[3], float fov, int width,

@@ -206,6 +206,14 @@ def math_probe(kind, x):
     return out
 
 
+def matrix_probe(kind, m, v):
+    """The oracle's own matrix products on the vectors v (n, 3): kind 0 xfm_point(m[16], v), 1 xfm_vector(m[16], v), 2 mat3_mul(m[9], v)."""
+    m, v = _f32(m, 9 if kind == 2 else 16), _f32(v, (-1, 3))
+    out = np.zeros_like(v)
+    lib().orc_matrix_probe(C.c_int(kind), _p(m), _p(v), C.c_size_t(len(v)), _p(out))
+    return out
+
+
 def camera_rays(eye, focus, up, fov, width, height, samples=1, depth=1, jitter=0.0):
     rays = np.zeros(width * height * samples * samples, RAY_DTYPE)
     lib().orc_camera_generate(_p(_f32(eye, 3)), _p(_f32(focus, 3)), _p(_f32(up, 3)), C.c_float(fov), C.c_int(width),

@@ -125,4 +125,32 @@ int ref_box_wide_dir(const float *lo, const float *hi) {
   data::primitives::Box3D b(glm::vec3(lo[0], lo[1], lo[2]), glm::vec3(hi[0], hi[1], hi[2]));
   return b.wideRangingBoxDir();
 }
+
+// The vendored glm's matrix arithmetic as Adapter::trace and api.cpp:307-308 use it (m16 / m9: column-major, glm's own storage).
+// kind 0: vec3(mat4 * vec4(v, 1)); 1: vec3(mat4 * vec4(v, 0)); 2: mat3 * vec3 (m holds 9 floats)
+void ref_matrix_product(int kind, const float *m, const float *v, float *out) {
+  glm::vec3 r;
+  if (kind == 2) {
+    glm::mat3 M;
+    std::memcpy(&M, m, sizeof M);
+    r = M * glm::vec3(v[0], v[1], v[2]);
+  } else {
+    glm::mat4 M;
+    std::memcpy(&M, m, sizeof M);
+    r = glm::vec3(M * glm::vec4(v[0], v[1], v[2], kind == 0 ? 1.f : 0.f));
+  }
+  out[0] = r.x; out[1] = r.y; out[2] = r.z;
+}
+void ref_mat4_inverse(const float *m16, float *out16) {
+  glm::mat4 M;
+  std::memcpy(&M, m16, sizeof M);
+  glm::mat4 I = glm::inverse(M);
+  std::memcpy(out16, &I, sizeof I);
+}
+void ref_normal_matrix(const float *m16, float *out9) {
+  glm::mat4 M;
+  std::memcpy(&M, m16, sizeof M);
+  glm::mat3 N = glm::transpose(glm::inverse(glm::mat3(M)));
+  std::memcpy(out9, &N, sizeof N);
+}
 }

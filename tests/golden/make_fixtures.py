@@ -13,6 +13,8 @@ Fixtures are DATA (inputs and expected outputs), never reference source text:
                                  RayPacketIntersection, RandEngine, Mesh::addFace, struct sizes) through oracle/ref_shim.cpp
   oracle_vectors.npz             outputs of the pinned CPU oracle on seeded inputs (per-ray hits on bunny.obj, framebuffer
                                  hashes of the golden scenes in flat and smooth mode) for the GPU parity tests
+  ref_matrix_vectors.json        (python tests/golden/make_fixtures.py --matrix) the vendored glm's mat4 * vec4, mat3 * vec3, inverse(mat4) and
+                                 transpose(inverse(mat3)) on the matrix families of tests/affine_cases.py; writes nothing else
   round2_vectors.json            (python tests/golden/make_fixtures.py --round2; needs no reference tree) regression pins of what
                                  the oracle DEFINES where the reference is schedule dependent: gvt_math known answers, camera stream
                                  words, bounce directions, and the hash / ray counts of a depth-2, 4-rays-per-pixel config-5 frame
@@ -74,9 +76,48 @@ def round2():
     print("wrote round2_vectors.json")
 
 
+def matrix_vectors():
+    """ref_matrix_vectors.json: the vendored glm's own matrix arithmetic (oracle/ref_shim.cpp ref_matrix_product / ref_mat4_inverse /
+    ref_normal_matrix) on the matrix families of tests/affine_cases.py -- per family 4 matrices x 10 vectors, the last five of each with
+    zero, -0, inf and NaN components (the `translation x 0` term of mat4 * vec4(d, 0) decides the sign of a zero and makes inf x 0).
+    Every float is stored as its uint32 bit pattern."""
+    from tests import affine_cases as ac
+
+    ref = orc.ref()
+    assert ref is not None, "build oracle/_ref first (make -C oracle)"
+    u = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1).view(np.uint32).tolist()  # noqa: E731
+    out = {}
+    for fam in ac.FAMILIES:
+        rows = []
+        for k in range(4):
+            m = ac.matrix(fam, 100 + k)
+            inv, nrm = np.zeros(16, np.float32), np.zeros(9, np.float32)
+            ref.ref_mat4_inverse(p(m), p(inv))
+            ref.ref_normal_matrix(p(m), p(nrm))
+            rng = np.random.default_rng([ac.FAMILIES.index(fam), 7000 + k])
+            v = (rng.normal(size=(10, 3)) * 10.0 ** rng.integers(-2, 3, (10, 1))).astype(np.float32)
+            v[5] = (-0.0, -0.0, -0.0)
+            v[6, k % 3] = 0.0
+            v[7, (k + 1) % 3] = -0.0
+            v[8, (k + 2) % 3] = np.inf if k % 2 else -np.inf
+            v[9, k % 3] = np.nan
+            row = {"m": u(m), "inverse": u(inv), "normal_matrix": u(nrm), "v": [u(x) for x in v]}
+            for kind, name, mat in ((0, "point", m), (1, "vector", m), (0, "inv_point", inv), (1, "inv_vector", inv), (2, "mat3", nrm)):
+                res = np.zeros((len(v), 3), np.float32)
+                for i in range(len(v)):
+                    ref.ref_matrix_product(C.c_int(kind), p(mat), p(v[i]), p(res[i]))
+                row[name] = [u(x) for x in res]
+            rows.append(row)
+        out[fam] = rows
+    json.dump(out, open(os.path.join(HERE, "ref_matrix_vectors.json"), "w"), indent=None, separators=(",", ":"), sort_keys=True)
+    print("wrote ref_matrix_vectors.json")
+
+
 def main():
     if "--round2" in sys.argv:
         return round2()
+    if "--matrix" in sys.argv:
+        return matrix_vectors()
     assert os.path.isdir(REF), "needs /root/reference"
     ref = orc.ref()
     assert ref is not None, "build oracle/_ref first (make -C oracle)"

@@ -17,33 +17,7 @@ from tests.conftest import GOLDEN
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-CMAPS = os.path.join(GOLDEN, "colormaps")
-IDENT = scenes.mat_translate_scale((0, 0, 0), (1, 1, 1))
-MOVED = scenes.mat_translate_scale((0.3, -0.2, 0.5), (1.5, 1.5, 1.5))
-
-
-def read(name, width):
-    return TransferFunction.read_map(os.path.join(CMAPS, name), width)
-
-
-def tf(kind):
-    cool = read("CoolWarm.cmap", 4)
-    if kind == "cool":
-        return TransferFunction(cool, read("CoolWarm.omap", 2), (0.0, 1.0))
-    if kind == "spikes":  # sparse: opacity only around 0.9
-        return TransferFunction(read("Grayramp.cmap", 4), read("fivespikes.omap", 2), (0.0, 1.0))
-    if kind == "ramp":
-        return TransferFunction(cool, read("ramp.omap", 2), (0.1, 0.8))
-    if kind == "opaque":
-        return TransferFunction(cool, np.array([[0, 1], [1, 1]], F), (0.0, 1.0))
-    raise KeyError(kind)
-
-
-def grid(n=24):
-    vol = scenes.noise_volume(n, seed=3)
-    vol.origin = np.array([-0.25, 0.1, -0.4], F)
-    vol.spacing = np.array([1.0 / (n - 1), 1.1 / (n - 1), 0.9 / (n - 1)], F)
-    return vol
+from tests.volume_common import CMAPS, IDENT, MOVED, grid, read, tf  # noqa: E402,F401  (shared with the host tests; other test modules import them from here)
 
 
 def make_rays(vol, m, n=3000, seed=7):

@@ -23,32 +23,7 @@ F = np.float32
 PLAIN = ("color", "w", "t_min", "depth")
 INFO = ("value_min", "value_max", "n_blocks", "n_blocks_empty")
 COUNTERS = ("samples_marched", "samples_gathered")
-# per type: numpy dtype, the library's constant, the image of noise_volume's [0, 1] (the transfer functions' value range), the quantiser,
-# and a value just across the sign bit
-TYPES = {
-    "u8": (np.uint8, capi.VOXEL_U8, (0.0, 255.0), lambda d: np.rint(d * 255.0), 128),
-    "i16": (np.int16, capi.VOXEL_I16, (-30000.0, 30000.0), lambda d: np.rint((d - 0.5) * 60000.0), -1),
-    "u16": (np.uint16, capi.VOXEL_U16, (0.0, 65535.0), lambda d: np.rint(d * 65535.0), 32768),
-}
-ALL = sorted(TYPES)
-
-
-def quantised(vol, ty):
-    """The [0, 1] grid in the type's units, geometry kept."""
-    q = np.ascontiguousarray(TYPES[ty][3](vol.data.astype(np.float64)).astype(TYPES[ty][0]))
-    return scenes.VolumeData(q, vol.origin, vol.spacing)
-
-
-def as_float(vol):
-    return scenes.VolumeData(vol.data.astype(F), vol.origin, vol.spacing)
-
-
-def scaled(kind, ty, value_range=None):
-    """tests.test_gpu_volume.tf's tables with the value range in the type's units (or the one given)."""
-    t = tf(kind)
-    lo, hi = TYPES[ty][2]
-    vr = value_range or tuple(lo + r * (hi - lo) for r in t.value_range)
-    return TransferFunction(t.cmap, t.omap, vr)
+from tests.volume_common import ALL, TYPES, as_float, quantised, scaled  # noqa: E402,F401  (shared with the host tests)
 
 
 def volume(vol, t=None, rate=1.3, skip=True, native=True, S=None):

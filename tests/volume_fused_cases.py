@@ -9,7 +9,7 @@ import numpy as np
 from gravit_amd import scenes
 from tests import volume_checker as vc
 from tests import volume_clip_checker as cc
-from tests.test_gpu_volume import IDENT, MOVED, grid, tf
+from tests.volume_common import IDENT, MOVED, grid, tf
 
 F = np.float32
 RATE = 1.7
