@@ -42,7 +42,7 @@ SYMBOLS = [
     "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
     "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
     "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
-    "gvt_hip_volume_frame_fused",
+    "gvt_hip_volume_frame_fused", "gvt_hip_volume_frame_fused_shaded",
 ]
 
 
@@ -101,6 +101,18 @@ class VolumeFusedStats(C.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
+
+class VolumeFusedShadedStats(C.Structure):
+    """gvt_hip_volume_fused_shaded_stats: what gvt_hip_volume_frame_fused_shaded reports of one frame."""
+    _fields_ = [("fused", C.c_uint32), ("features", C.c_uint32), ("samples_marched", C.c_uint64), ("samples_gathered", C.c_uint64),
+                ("brick_visits", C.c_uint64), ("rays_deposited", C.c_uint64), ("adapter_calls", C.c_uint64), ("crossings_rendered", C.c_uint64),
+                ("samples_shaded", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10
@@ -172,6 +184,8 @@ def load():
         lib.gvt_hip_depth_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gvt_hip_volume_frame_clipped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_frame_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_frame_fused_shaded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                          C.c_void_p]
         lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))

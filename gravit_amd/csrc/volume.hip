@@ -17,6 +17,8 @@
 //                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
 //   gvt_hip_volume_frame_fused / k_volume_march_fused   the same frame over bricks of ONE grid in one launch: a lane carries its ray from brick to
 //                                           brick (volume_fused.inc); every other frame takes the loop
+//   gvt_hip_volume_frame_fused_shaded / k_volume_march_fused_shaded   ... and, where the caller allows it, frames whose bricks have isovalues,
+//                                           slice planes or lit fog: the same structure around the surface / lit visit (volume_fused_shaded.inc)
 //   gvt_hip_volume_march_queue / _camera_filter   the Domain scheduler's steps over bricks spread over ranks (algorithm/DomainTracer.h:148-326): the march
 //                                           on a device queue, and the camera step with shuffleDropRays' keep mask (k_vol_classify<MASK>); the
 //                                           exchange's batched wire conversions are beside k_planes_to_aos (convert.inc, trace.hip)
@@ -436,6 +438,8 @@ __device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, uns
 // loaded -- they stay live across the look-up; with SURF a crossing is rendered first, as ever.  Without LIT: the march as it was.
 // CENTRAL (the _central entry points): the gradient of a crossed isovalue and of a lit sample is vol_gradient_central's, from H; nothing
 // else of the march reads H or depends on the kind.
+// KEEP IN STEP: k_volume_march_fused_shaded (volume_fused_shaded.inc) restates the per-sample steps of the loop below for SURF / LIT
+// without CENTRAL; a change to the visit here is a change there.
 template <typename T, bool SURF, bool CLIP, bool LIT, bool CENTRAL = false>
 __device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTable<SURF, LIT> &S, const GhostTable<CENTRAL> &H, RayPlanes q, unsigned n, const Mat4 &minv,
                                                   unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
@@ -840,6 +844,7 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 
 #include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges
 #include "volume_fused.inc" // k_volume_march_fused
+#include "volume_fused_shaded.inc" // k_volume_march_fused_shaded
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
@@ -1595,26 +1600,52 @@ namespace {
 bool same_bits(const void *a, const void *b, size_t bytes) { return std::memcmp(a, b, bytes) == 0; }
 
 // Eligibility, decided per call from the volumes as they are now: bricks of ONE grid (global origin, spacing, dt, table, value range, skip
-// flag and minv equal as bits), one voxel type, and nothing the plain march does not do -- no surfaces, no subgrids, no lit shading (the
-// gradient kind is inert then)
-bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst) {
+// flag and minv equal as bits), one voxel type, no subgrids, and nothing the kernels allowed do not do.  allow = 0 (gvt_hip_volume_frame_fused):
+// no surfaces and no lit shading (the gradient kind is inert then).  GVT_HIP_FUSED_SURFACES / _LIT drop those two clauses; a frame that
+// has an isovalue or effective lit shading then needs the cell gradient on every brick, and what the bricks must share of surfaces and
+// lights is compared as bits too.  features: the bits of `allow` the frame needs (0: the plain fused kernel)
+bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, uint32_t allow, uint32_t &features) {
+  features = 0;
   if (n_inst < 1 || n_inst > VOL_DEST_MAX) return false;
   const gvt_hip_volume *A = volumes[0];
+  const bool surf = A->n_iso + A->n_pl > 0, lit = A->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && A->n_lights > 0;
+  if ((surf && !(allow & GVT_HIP_FUSED_SURFACES)) || (lit && !(allow & GVT_HIP_FUSED_LIT))) return false;
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
-    if (!B->has_tf || B->n_iso + B->n_pl > 0 || !B->sub.empty() || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0)) return false;
+    if (!B->has_tf || !B->sub.empty()) return false;
+    if ((B->n_iso + B->n_pl > 0) != surf || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0) != lit) return false;
+    if ((B->n_iso > 0 || lit) && B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL) return false; // (planes alone read no gradient: the kind is inert)
     if (B->vtype != A->vtype || B->skip != A->skip) return false;
     if (!same_bits(B->go, A->go, sizeof(A->go)) || !same_bits(B->sp, A->sp, sizeof(A->sp)) || !same_bits(&B->dt, &A->dt, sizeof(float))) return false;
     if (!same_bits(&B->tf_lo, &A->tf_lo, sizeof(float)) || !same_bits(&B->tf_hi, &A->tf_hi, sizeof(float))) return false;
     if (!same_bits(B->tf_a, A->tf_a, sizeof(A->tf_a)) || !same_bits(B->tf_rgb, A->tf_rgb, sizeof(A->tf_rgb))) return false;
     if (!same_bits(minv + 16 * i, minv, 16 * sizeof(float))) return false;
+    if (surf) { // (entries beyond n_iso / n_pl are never read)
+      if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float))) return false;
+      if (!same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) || !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) return false;
+    }
+    if (surf || lit) { // (a surface frame without effective lit shading still lights its crossings: surf_composite)
+      if (B->n_lights != A->n_lights || B->shade != A->shade || !same_bits(&B->ka, &A->ka, sizeof(float)) || !same_bits(&B->kd, &A->kd, sizeof(float))) return false;
+      if (!same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights) || !same_bits(B->lcol, A->lcol, sizeof(A->lcol[0]) * (size_t)A->n_lights)) return false;
+    }
   }
+  features = (surf ? GVT_HIP_FUSED_SURFACES : 0u) | (lit ? GVT_HIP_FUSED_LIT : 0u);
   return true;
 }
 
-// the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back)
+// the shaded fused kernel's instantiation for the frame's features (one of the three shaded combinations) and its by-value table
+template <typename VT, bool CLIP, typename... Args>
+void launch_fused_shaded(uint32_t features, unsigned blocks, hipStream_t st, const gvt_hip_volume *V0, const Mat4 &M, VolDev U, Args... args) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0, lit = (features & GVT_HIP_FUSED_LIT) != 0;
+  if (surf && lit) k_volume_march_fused_shaded<VT, CLIP, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
+  else if (surf) k_volume_march_fused_shaded<VT, CLIP, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
+  else k_volume_march_fused_shaded<VT, CLIP, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
+}
+
+// the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
+// features: fused_eligible's -- 0 launches k_volume_march_fused, anything else the shaded kernel with the table of volumes[0]
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
-                       gvt_hip_fb *fb, const gvt_hip_depth *depth, gvt_hip_volume_fused_stats &S) {
+                       gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S) {
   Ctx &C = gctx();
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;
@@ -1625,7 +1656,8 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
                                           cam->jitter_window_size, 8))) return rc;
   const size_t n = q_cam->size;
   FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
-  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_STATS * sizeof(unsigned long long));
+  static_assert(VOL_FUSED_SHADED_STATS >= VOL_FUSED_STATS, "one block of counter words serves both kernels");
+  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADED_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
   static_assert(sizeof(FusedBrick) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table fits the staging block");
@@ -1635,7 +1667,8 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     FusedBrick R{};
-    R.vox = B->d_vox; R.mc = B->d_mc;
+    R.vox = B->d_vox;
+    R.mc = (features & GVT_HIP_FUSED_SURFACES) ? (const uint8_t *)B->d_cells : B->d_mc; // (the surface visit reads the per-cell words, never the skip bytes)
     R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
     for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
     h[i] = R;
@@ -1643,7 +1676,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if ((rc = pinned_stage_end())) return rc;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
-  HIPCHK(hipMemsetAsync(d_stats, 0, VOL_FUSED_STATS * sizeof(unsigned long long), C.stream));
+  HIPCHK(hipMemsetAsync(d_stats, 0, VOL_FUSED_SHADED_STATS * sizeof(unsigned long long), C.stream));
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = minv[k];
   const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
@@ -1652,30 +1685,60 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if (n)
     with_voxel_type(volumes[0]->vtype, [&](auto t) {
       using VT = decltype(t);
+      if (features) {
+        if (depth) launch_fused_shaded<VT, true>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
+                                                 (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
+        else launch_fused_shaded<VT, false>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, (const float *)nullptr, 0u,
+                                            fb->d_rgba, n_pix, work, d_stats);
+        return;
+      }
       if (depth) k_volume_march_fused<VT, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
                                                                                    (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
       else k_volume_march_fused<VT, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, nullptr, 0u, fb->d_rgba,
                                                                                n_pix, work, d_stats);
     });
   HIPCHK(hipGetLastError());
-  unsigned long long *h_stats = (unsigned long long *)(C.h_pinned + 16); // (pinned words 16..23 of the context)
-  HIPCHK(hipMemcpyAsync(h_stats, d_stats, VOL_FUSED_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.stream));
+  unsigned long long *h_stats = (unsigned long long *)(C.h_pinned + 16); // (pinned words 16..27 of the context: six 64-bit counters; 28..31 are free, 32.. the builder's)
+  HIPCHK(hipMemcpyAsync(h_stats, d_stats, VOL_FUSED_SHADED_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.stream));
   if ((rc = gvt_hip_queue_clear(q_cam))) return rc;
   HIPCHK(hipStreamSynchronize(C.stream));
-  S.fused = 1; S.adapter_calls = 1;
+  S.fused = 1; S.adapter_calls = 1; S.features = features;
   S.samples_marched = h_stats[0]; S.samples_gathered = h_stats[1]; S.brick_visits = h_stats[2]; S.rays_deposited = h_stats[3];
+  S.crossings_rendered = h_stats[4]; S.samples_shaded = h_stats[5]; // (0 from the plain kernel: the words were cleared)
   return 0;
+}
+
+// both fused entry points: the arguments' errors, then the fused frame where the frame is eligible under `allow`, else the loop
+int volume_frame_fused_or_loop(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                               gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t allow, gvt_hip_volume_fused_shaded_stats &S) {
+  int rc;
+  if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
+  uint32_t features = 0;
+  if (fused_eligible(volumes, minv, n_inst, allow, features)) return volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S);
+  return volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, &S.adapter_calls); // (not an error: the loop, fused = 0)
 }
 
 } // namespace
 
 extern "C" int gvt_hip_volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
                                           gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, gvt_hip_volume_fused_stats *stats) {
-  int rc;
-  if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
-  gvt_hip_volume_fused_stats S{};
-  if (fused_eligible(volumes, minv, n_inst)) rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, S);
-  else rc = volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, &S.adapter_calls); // (not an error: the loop, fused = 0)
+  gvt_hip_volume_fused_shaded_stats S{};
+  const int rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, 0u, S);
+  if (!rc && stats) {
+    gvt_hip_volume_fused_stats O{};
+    O.fused = S.fused; O.samples_marched = S.samples_marched; O.samples_gathered = S.samples_gathered; O.brick_visits = S.brick_visits;
+    O.rays_deposited = S.rays_deposited; O.adapter_calls = S.adapter_calls;
+    *stats = O;
+  }
+  return rc;
+}
+
+extern "C" int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                                 const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t allow,
+                                                 gvt_hip_volume_fused_shaded_stats *stats) {
+  if (allow & ~(uint32_t)(GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT)) { set_error("volume_frame_fused_shaded: unknown allow bits %u", allow); return GVT_HIP_ERR_INVALID; }
+  gvt_hip_volume_fused_shaded_stats S{};
+  const int rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, allow, S);
   if (!rc && stats) *stats = S;
   return rc;
 }

@@ -561,9 +561,11 @@ class VolumeTracer:
     VolumeData), m = the instance's matrix (None: identity).  Bricks may carry AMR subgrids (scenes.split_amr_volume, scenes.refine).  The world box of a brick is its box under m (scenes.instance_bbox).
     native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width).
     fused: frame() goes through gvt_hip_volume_frame_fused -- every brick in ONE march launch where the frame is eligible (plain bricks of
-    one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop."""
+    one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop.
+    fused_shaded (with fused): frame() goes through gvt_hip_volume_frame_fused_shaded with both bits (fused_allow), so frames with
+    isovalues, slice planes or lit fog are fused too; without it such frames take the loop, as ever."""
 
-    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False):
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -584,7 +586,9 @@ class VolumeTracer:
         self.fb = FrameBuffer(camera.width, camera.height)
         self.calls = 0
         self.fused = bool(fused)
-        self.fused_stats = None  # fused=True: gvt_hip_volume_fused_stats of the last frame, as a dict
+        self.fused_shaded = bool(fused_shaded)
+        self.fused_allow = capi.FUSED_SURFACES | capi.FUSED_LIT  # fused_shaded=True: the allow word of gvt_hip_volume_frame_fused_shaded
+        self.fused_stats = None  # fused=True: gvt_hip_volume_fused_stats (fused_shaded: gvt_hip_volume_fused_shaded_stats) of the last frame, as a dict
         self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
 
     def frame(self, depth=None):
@@ -598,7 +602,14 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        if self.fused:
+        if self.fused and self.fused_shaded:
+            st = capi.VolumeFusedShadedStats()
+            capi.check(capi.load().gvt_hip_volume_frame_fused_shaded(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                                     C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
+                                                                     C.c_uint32(self.fused_allow), C.byref(st)), "gvt_hip_volume_frame_fused_shaded")
+            self.fused_stats = st.as_dict()
+            calls = C.c_uint64(st.adapter_calls)
+        elif self.fused:
             st = capi.VolumeFusedStats()
             capi.check(capi.load().gvt_hip_volume_frame_fused(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
                                                               C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
@@ -672,13 +683,18 @@ class VolumeTracer:
 
     def stats(self):
         """The bricks' counters summed (they accumulate over frames).  fused=True adds fused, brick_visits and rays_deposited of the last
-        frame, and where that frame was fused samples_marched / samples_gathered are ITS counts: the bricks' own did not move."""
+        frame, and where that frame was fused samples_marched / samples_gathered are ITS counts: the bricks' own did not move.
+        fused_shaded=True adds features and, where the frame was fused, its crossings_rendered / samples_shaded likewise."""
         out = self._brick_stats()
         if self.fused and self.fused_stats is not None:
             f = self.fused_stats
             out.update(fused=f["fused"], brick_visits=f["brick_visits"], rays_deposited=f["rays_deposited"])
             if f["fused"]:
                 out.update(samples_marched=f["samples_marched"], samples_gathered=f["samples_gathered"])
+            if "features" in f:
+                out.update(features=f["features"])
+                if f["fused"]:
+                    out.update(crossings_rendered=f["crossings_rendered"], samples_shaded=f["samples_shaded"])
         return out
 
     def _brick_stats(self):
@@ -935,7 +951,7 @@ class MixedTracer:
     (gvt_hip_fb_composite_over; the result is in the volume tracer's framebuffer).  The reference has no such path: shuffleRays
     takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel)."""
 
-    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False):
+    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -948,7 +964,8 @@ class MixedTracer:
         self.camera = camera
         self.mesh = NativeTracer(self.scene, normal_mode)
         self.depth = DepthPlane(camera.width, camera.height)
-        self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused)  # (fused: its clipped frame in one launch)
+        self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
+                                   fused_shaded=fused_shaded)  # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too)
 
     def frame(self):
         self.mesh()

@@ -745,7 +745,8 @@ int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt
  * scheduler's backend) must make the same check.
  * queues are used by the fallback only; a fused frame leaves them cleared.  The per-brick counters of the volumes (gvt_hip_volume_info's
  * samples_marched / samples_gathered) are NOT touched by a fused frame: its counters are the call's own, below.
- * OUT OF SCOPE.  Surfaces, lit shading, central gradients and AMR inside the fused kernel (such frames take the loop); bricks of
+ * Surfaces and lit shading are taken by gvt_hip_volume_frame_fused_shaded, below; this entry point keeps its rule.
+ * OUT OF SCOPE.  Central gradients and AMR inside a fused kernel (such frames take the loop); bricks of
  * different grids, tables or matrices; the Domain scheduler (a rank fusing the bricks it owns needs rays that leave for foreign bricks
  * appended to outgoing queues inside the kernel); fused as the default. */
 typedef struct {
@@ -760,6 +761,38 @@ typedef struct {
 int gvt_hip_volume_frame_fused(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m /* n_inst*16 */, const float *minv, size_t n_inst,
                                const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth /* may be NULL */,
                                gvt_hip_volume_fused_stats *stats /* may be NULL */);
+
+/* ---- fused frame: surfaces and lit fog (a further opt-in beside gvt_hip_volume_frame_fused, whose rule does not change) ----
+ * allow: which frames beyond the plain ones the fused kernel may take.  allow == 0 is gvt_hip_volume_frame_fused in every respect.
+ * Bits other than the two below: GVT_HIP_ERR_INVALID, nothing changed.  Argument errors are gvt_hip_volume_frame's / _clipped's.
+ * ELIGIBILITY is gvt_hip_volume_frame_fused's with two clauses relaxed: "no brick has surfaces" is dropped with
+ * GVT_HIP_FUSED_SURFACES, "no effective lit shading" with GVT_HIP_FUSED_LIT.  What the bricks must share is then compared as bits
+ * too: n_iso, n_pl, the isovalues, the planes and the surfaces' opacity; the number of lights, their positions and colours, ka, kd and
+ * the shading mode.  Still ineligible -- the loop runs, fused = 0, no error: subgrids on any brick; GVT_HIP_VOLUME_GRADIENT_CENTRAL on
+ * any brick of a frame that has an isovalue or effective lit shading (in a frame that has neither the kind stays inert, as ever); a
+ * frame that needs a bit `allow` lacks; everything ineligible above.
+ * CONTRACT.  As above: for every eligible input at one sample per pixel the framebuffer equals gvt_hip_volume_frame's / _clipped's on the
+ * same arguments in every bit.  The visit of a brick is the surface / lit march's (the crossings of a sample composited in front of it,
+ * the sample shaded by the cell gradient), and between two visits the ray carries what the loop's ray carries: beyond t_min, colour and
+ * opacity, the side mask of its last owned sample with GVT_HIP_RAY_SIDES once a visit has owned one (a camera ray carries none; a visit
+ * that owns no sample leaves mask, flag and t_min as they were).  On entering a brick the mask counts only for the sample right after
+ * the one in t_min (the first lattice index after t_min); at any other first sample the ray has no previous sides.
+ * A frame that has neither surfaces nor lit shading launches the plain fused kernel (features = 0).  The bricks' own counters
+ * (gvt_hip_volume_info, gvt_hip_volume_get_crossings, gvt_hip_volume_get_shaded) are not touched by a fused frame.  samples > 1:
+ * arrival order, as in the loop. */
+#define GVT_HIP_FUSED_SURFACES 1u   /* the fused kernel may take frames whose bricks have isovalues / slice planes */
+#define GVT_HIP_FUSED_LIT      2u   /* ... and frames with effective lit shading (SHADE_GRADIENT and >= 1 light)   */
+typedef struct {
+  uint32_t fused;      /* as gvt_hip_volume_fused_stats */
+  uint32_t features;   /* bits of the kernel that ran: 0 = the plain fused kernel, or the loop */
+  uint64_t samples_marched, samples_gathered, brick_visits, rays_deposited, adapter_calls;
+  uint64_t crossings_rendered;  /* fused: the sum of what the loop adds to the bricks' gvt_hip_volume_get_crossings; 0 after the loop */
+  uint64_t samples_shaded;      /* fused: likewise for gvt_hip_volume_get_shaded */
+} gvt_hip_volume_fused_shaded_stats;
+int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                      const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
+                                      const gvt_hip_depth *depth /* may be NULL */, uint32_t allow,
+                                      gvt_hip_volume_fused_shaded_stats *stats /* may be NULL */);
 
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);

@@ -41,6 +41,10 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              bricks; --bricks to choose) the loop frame and the fused frame alternating frame by frame on ONE
                                              tracer in one process: median [min .. max] of each, brick visits, samples per second; "fused_wins" only
                                              where the fused maximum lies below the loop's minimum
+  python tools/volume_bench.py --fused --surfaces   (and / or --shade) the shaded fused frame (gvt_hip_volume_frame_fused_shaded) against the loop,
+                                             the same protocol: --surfaces = the "thin" frame with the two isovalues the field reaches (opacity
+                                             0.3, one light), --shade = lit fog by one light under every --tf table; with each the crossings
+                                             and the samples shaded per frame, and the two framebuffers compared bitwise after every pair
 """
 import argparse
 import json
@@ -169,13 +173,22 @@ def run_clip(n, split, steps, warmup, rate, vol, dtype="f32"):
 
 
 FUSED_SPLITS = {1: (1, 1, 1), 8: (2, 2, 2), 64: (4, 4, 4)}
+SHADE_LIGHTS = [((3.0, 4.0, 5.0), (1.0, 0.9, 0.8)), ((-2.0, 1.0, 0.5), (0.2, 0.3, 0.4)), ((0.0, -6.0, 1.0), (0.5, 0.1, 0.3))]
 
 
-def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
-    """The loop frame against the fused frame, alternating frame by frame on one tracer (VolumeTracer.fused switches the entry point)."""
+def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32", shaded=None):
+    """The loop frame against the fused frame, alternating frame by frame on one tracer (VolumeTracer.fused switches the entry point).
+    shaded: None (plain fog, gvt_hip_volume_frame_fused), "surfaces" (--surfaces' reached isovalues, opacity 0.3, one light) or "lit" (lit
+    fog by --shade's first light): the shaded fused frame, its framebuffer compared with the loop's after every pair."""
     bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
-    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=shaded is not None)
+    if shaded == "surfaces":
+        _, lo, hi = DTYPES[dtype]
+        tr.set_surfaces(tuple(lo + v * (hi - lo) for v in SURFACE_MODES["reached"]), (), 0.3).set_lights([((3.0, 4.0, 5.0), (1.0, 1.0, 1.0))])
+    elif shaded == "lit":
+        tr.set_lights(SHADE_LIGHTS[:1]).set_shading(True)
     loop, fused = [], []
+    pairs_same = True
 
     def frame(flag):
         tr.fused = flag
@@ -184,7 +197,11 @@ def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
     for i in range(warmup + steps):
         loop.append(timed(lambda: frame(False)))
         loop_calls = tr.calls
+        if shaded:
+            a = tr.framebuffer(False).copy()
         fused.append(timed(lambda: frame(True)))
+        if shaded:  # (outside the timed region)
+            pairs_same = pairs_same and bool((a.view(np.uint32) == tr.framebuffer(False).view(np.uint32)).all())
     loop, fused = loop[warmup:], fused[warmup:]
     st = tr.stats()
     same = None
@@ -192,8 +209,11 @@ def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
         frame(False)
         a = tr.framebuffer(False).copy()
         frame(True)
-        same = bool((a.view(np.uint32) == tr.framebuffer(False).view(np.uint32)).all())
-    return {"mode": "fused", "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "loop_ms_median": med(loop),
+        same = pairs_same and bool((a.view(np.uint32) == tr.framebuffer(False).view(np.uint32)).all())
+    extra = {}
+    if shaded:
+        extra = {"features": int(st["features"]), "crossings_per_frame": int(st["crossings_rendered"]), "samples_shaded": int(st["samples_shaded"])}
+    return {"mode": "fused" if not shaded else "fused_" + shaded, **extra, "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "loop_ms_median": med(loop),
             "loop_ms_min": round(min(loop), 3), "loop_ms_max": round(max(loop), 3), "loop_adapter_calls": int(loop_calls), "fused_ms_median": med(fused),
             "fused_ms_min": round(min(fused), 3), "fused_ms_max": round(max(fused), 3), "fused": int(st["fused"]), "brick_visits": int(st["brick_visits"]),
             "rays_deposited": int(st["rays_deposited"]), "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]),
@@ -201,8 +221,6 @@ def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
             "fused_gsamples_per_s": round(st["samples_marched"] / float(np.median(fused)) / 1e6, 3),
             "fused_over_loop": round(float(np.median(fused)) / float(np.median(loop)), 4), "fused_wins": bool(max(fused) < min(loop)), "same_bits": same}
 
-
-SHADE_LIGHTS = [((3.0, 4.0, 5.0), (1.0, 0.9, 0.8)), ((-2.0, 1.0, 0.5), (0.2, 0.3, 0.4)), ((0.0, -6.0, 1.0), (0.5, 0.1, 0.3))]
 
 
 def run_shade(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
@@ -555,9 +573,12 @@ def main():
         a.sizes = []
     for n in a.sizes if a.fused else ():
         vol = noise(n, a.dtype)
-        for kind in a.tf:
+        cases = [(None, kind) for kind in a.tf]
+        if a.surfaces or a.shade:  # the shaded fused frame
+            cases = ([("surfaces", "thin")] if a.surfaces else []) + ([("lit", kind) for kind in a.tf] if a.shade else [])
+        for shaded, kind in cases:
             for nb in a.bricks:
-                r = run_fused(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, a.dtype)
+                r = run_fused(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, a.dtype, shaded)
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
     if a.fused:
