@@ -43,6 +43,7 @@ SYMBOLS = [
     "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
     "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
     "gvt_hip_volume_frame_fused", "gvt_hip_volume_frame_fused_shaded",
+    "gvt_hip_volume_frame_shadowed",
 ]
 
 
@@ -110,6 +111,20 @@ class VolumeFusedShadedStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class VolumeShadowParams(C.Structure):
+    """gvt_hip_volume_shadow_params: flags must be 0; bias = the first shadow sample's lattice index, 1 .. 64."""
+    _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
+
+
+class VolumeShadowStats(C.Structure):
+    """gvt_hip_volume_shadow_stats: gvt_hip_volume_fused_shaded_stats' fields (the camera rays), then the shadow rays' counters."""
+    _fields_ = VolumeFusedShadedStats._fields_ + [("shadowed", C.c_uint32), ("pad", C.c_uint32), ("shadow_rays", C.c_uint64), ("shadow_brick_visits", C.c_uint64),
+                                                  ("shadow_crossings", C.c_uint64), ("shadow_samples_marched", C.c_uint64), ("shadow_samples_gathered", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
@@ -186,6 +201,8 @@ def load():
         lib.gvt_hip_volume_frame_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_frame_fused_shaded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                           C.c_void_p]
+        lib.gvt_hip_volume_frame_shadowed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]
         lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
@@ -267,5 +284,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeShadowParams", "VolumeShadowStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

@@ -19,6 +19,8 @@
 //                                           brick (volume_fused.inc); every other frame takes the loop
 //   gvt_hip_volume_frame_fused_shaded / k_volume_march_fused_shaded   ... and, where the caller allows it, frames whose bricks have isovalues,
 //                                           slice planes or lit fog: the same structure around the surface / lit visit (volume_fused_shaded.inc)
+//   gvt_hip_volume_frame_shadowed / k_volume_march_fused_shadow   ... with the crossings lit only by the lights that reach them: a lane marches the
+//                                           shadow rays of its camera ray itself, from brick to brick (volume_fused_shadow.inc)
 //   gvt_hip_volume_march_queue / _camera_filter   the Domain scheduler's steps over bricks spread over ranks (algorithm/DomainTracer.h:148-326): the march
 //                                           on a device queue, and the camera step with shuffleDropRays' keep mask (k_vol_classify<MASK>); the
 //                                           exchange's batched wire conversions are beside k_planes_to_aos (convert.inc, trace.hip)
@@ -845,6 +847,7 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 #include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges
 #include "volume_fused.inc" // k_volume_march_fused
 #include "volume_fused_shaded.inc" // k_volume_march_fused_shaded
+#include "volume_fused_shadow.inc" // k_volume_march_fused_shadow
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
@@ -1604,29 +1607,34 @@ bool same_bits(const void *a, const void *b, size_t bytes) { return std::memcmp(
 // no surfaces and no lit shading (the gradient kind is inert then).  GVT_HIP_FUSED_SURFACES / _LIT drop those two clauses; a frame that
 // has an isovalue or effective lit shading then needs the cell gradient on every brick, and what the bricks must share of surfaces and
 // lights is compared as bits too.  features: the bits of `allow` the frame needs (0: the plain fused kernel)
-bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, uint32_t allow, uint32_t &features) {
+bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, uint32_t allow, uint32_t &features, const char **why = nullptr) {
   features = 0;
-  if (n_inst < 1 || n_inst > VOL_DEST_MAX) return false;
+  const auto no = [&](const char *clause) { // (why: the clause that fails, for the entry point that refuses such a frame instead of taking the loop)
+    if (why) *why = clause;
+    return false;
+  };
+  if (n_inst < 1 || n_inst > VOL_DEST_MAX) return no("between 1 and 256 bricks");
   const gvt_hip_volume *A = volumes[0];
   const bool surf = A->n_iso + A->n_pl > 0, lit = A->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && A->n_lights > 0;
-  if ((surf && !(allow & GVT_HIP_FUSED_SURFACES)) || (lit && !(allow & GVT_HIP_FUSED_LIT))) return false;
+  if ((surf && !(allow & GVT_HIP_FUSED_SURFACES)) || (lit && !(allow & GVT_HIP_FUSED_LIT))) return no("a feature the allow word lacks");
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
-    if (!B->has_tf || !B->sub.empty()) return false;
-    if ((B->n_iso + B->n_pl > 0) != surf || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0) != lit) return false;
-    if ((B->n_iso > 0 || lit) && B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL) return false; // (planes alone read no gradient: the kind is inert)
-    if (B->vtype != A->vtype || B->skip != A->skip) return false;
-    if (!same_bits(B->go, A->go, sizeof(A->go)) || !same_bits(B->sp, A->sp, sizeof(A->sp)) || !same_bits(&B->dt, &A->dt, sizeof(float))) return false;
-    if (!same_bits(&B->tf_lo, &A->tf_lo, sizeof(float)) || !same_bits(&B->tf_hi, &A->tf_hi, sizeof(float))) return false;
-    if (!same_bits(B->tf_a, A->tf_a, sizeof(A->tf_a)) || !same_bits(B->tf_rgb, A->tf_rgb, sizeof(A->tf_rgb))) return false;
-    if (!same_bits(minv + 16 * i, minv, 16 * sizeof(float))) return false;
+    if (!B->has_tf) return no("a brick without a transfer function");
+    if (!B->sub.empty()) return no("a brick with AMR subgrids");
+    if ((B->n_iso + B->n_pl > 0) != surf || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0) != lit) return no("bricks that differ in having surfaces or lit shading");
+    if ((B->n_iso > 0 || lit) && B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL) return no("central gradients on a brick of a frame with an isovalue or lit shading"); // (planes alone read no gradient: the kind is inert)
+    if (B->vtype != A->vtype || B->skip != A->skip) return no("bricks of different voxel types or skip flags");
+    if (!same_bits(B->go, A->go, sizeof(A->go)) || !same_bits(B->sp, A->sp, sizeof(A->sp)) || !same_bits(&B->dt, &A->dt, sizeof(float))) return no("bricks of different grids");
+    if (!same_bits(&B->tf_lo, &A->tf_lo, sizeof(float)) || !same_bits(&B->tf_hi, &A->tf_hi, sizeof(float))) return no("bricks with different transfer functions");
+    if (!same_bits(B->tf_a, A->tf_a, sizeof(A->tf_a)) || !same_bits(B->tf_rgb, A->tf_rgb, sizeof(A->tf_rgb))) return no("bricks with different transfer functions");
+    if (!same_bits(minv + 16 * i, minv, 16 * sizeof(float))) return no("bricks under different matrices");
     if (surf) { // (entries beyond n_iso / n_pl are never read)
-      if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float))) return false;
-      if (!same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) || !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) return false;
+      if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float))) return no("bricks with different surfaces");
+      if (!same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) || !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) return no("bricks with different surfaces");
     }
     if (surf || lit) { // (a surface frame without effective lit shading still lights its crossings: surf_composite)
-      if (B->n_lights != A->n_lights || B->shade != A->shade || !same_bits(&B->ka, &A->ka, sizeof(float)) || !same_bits(&B->kd, &A->kd, sizeof(float))) return false;
-      if (!same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights) || !same_bits(B->lcol, A->lcol, sizeof(A->lcol[0]) * (size_t)A->n_lights)) return false;
+      if (B->n_lights != A->n_lights || B->shade != A->shade || !same_bits(&B->ka, &A->ka, sizeof(float)) || !same_bits(&B->kd, &A->kd, sizeof(float))) return no("bricks with different lights or shading");
+      if (!same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights) || !same_bits(B->lcol, A->lcol, sizeof(A->lcol[0]) * (size_t)A->n_lights)) return no("bricks with different lights or shading");
     }
   }
   features = (surf ? GVT_HIP_FUSED_SURFACES : 0u) | (lit ? GVT_HIP_FUSED_LIT : 0u);
@@ -1642,10 +1650,26 @@ void launch_fused_shaded(uint32_t features, unsigned blocks, hipStream_t st, con
   else k_volume_march_fused_shaded<VT, CLIP, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
 }
 
+// the shadowed kernel's instantiation: clipped or not, lit fog or not (surfaces are implied)
+template <typename VT, typename... Args>
+void launch_fused_shadow(uint32_t features, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H, const FusedBrick *d_bricks,
+                         TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
+  const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
+  const float *d_t = depth ? depth->d_t : nullptr;
+  const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
+  if (depth && lit) k_volume_march_fused_shadow<VT, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  else if (depth) k_volume_march_fused_shadow<VT, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  else if (lit) k_volume_march_fused_shadow<VT, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  else k_volume_march_fused_shadow<VT, false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+}
+
 // the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
 // features: fused_eligible's -- 0 launches k_volume_march_fused, anything else the shaded kernel with the table of volumes[0]
+// shadow (gvt_hip_volume_frame_shadowed; features has SURFACES then): the launch is k_volume_march_fused_shadow's, and shadow_out gets
+// its five further counter words, read back in the same wait
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
-                       gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S) {
+                       gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S, const ShadowDev *shadow = nullptr,
+                       uint64_t *shadow_out = nullptr) {
   Ctx &C = gctx();
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;
@@ -1657,7 +1681,9 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   const size_t n = q_cam->size;
   FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
   static_assert(VOL_FUSED_SHADED_STATS >= VOL_FUSED_STATS, "one block of counter words serves both kernels");
-  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADED_STATS * sizeof(unsigned long long));
+  static_assert(VOL_FUSED_SHADOW_STATS >= VOL_FUSED_SHADED_STATS, "... and the shadowed kernel");
+  const size_t n_words = shadow ? VOL_FUSED_SHADOW_STATS : VOL_FUSED_SHADED_STATS;
+  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
   static_assert(sizeof(FusedBrick) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table fits the staging block");
@@ -1676,7 +1702,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if ((rc = pinned_stage_end())) return rc;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
-  HIPCHK(hipMemsetAsync(d_stats, 0, VOL_FUSED_SHADED_STATS * sizeof(unsigned long long), C.stream));
+  HIPCHK(hipMemsetAsync(d_stats, 0, n_words * sizeof(unsigned long long), C.stream));
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = minv[k];
   const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
@@ -1685,6 +1711,11 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if (n)
     with_voxel_type(volumes[0]->vtype, [&](auto t) {
       using VT = decltype(t);
+      if (shadow) {
+        launch_fused_shadow<VT>(features, depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba,
+                                n_pix, work, d_stats);
+        return;
+      }
       if (features) {
         if (depth) launch_fused_shaded<VT, true>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
                                                  (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
@@ -1698,13 +1729,17 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
                                                                                n_pix, work, d_stats);
     });
   HIPCHK(hipGetLastError());
-  unsigned long long *h_stats = (unsigned long long *)(C.h_pinned + 16); // (pinned words 16..27 of the context: six 64-bit counters; 28..31 are free, 32.. the builder's)
-  HIPCHK(hipMemcpyAsync(h_stats, d_stats, VOL_FUSED_SHADED_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.stream));
+  // (pinned words 16..27 of the context: six 64-bit counters; 28..31 are free, 32..41 the builder's; the shadowed frame's eleven are words 42..63)
+  static_assert(42 + 2 * VOL_FUSED_SHADOW_STATS <= 64, "the context has 64 pinned words");
+  unsigned long long *h_stats = (unsigned long long *)(C.h_pinned + (shadow ? 42 : 16));
+  HIPCHK(hipMemcpyAsync(h_stats, d_stats, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.stream));
   if ((rc = gvt_hip_queue_clear(q_cam))) return rc;
   HIPCHK(hipStreamSynchronize(C.stream));
   S.fused = 1; S.adapter_calls = 1; S.features = features;
   S.samples_marched = h_stats[0]; S.samples_gathered = h_stats[1]; S.brick_visits = h_stats[2]; S.rays_deposited = h_stats[3];
   S.crossings_rendered = h_stats[4]; S.samples_shaded = h_stats[5]; // (0 from the plain kernel: the words were cleared)
+  if (shadow && shadow_out)
+    for (int i = 0; i < VOL_FUSED_SHADOW_STATS - VOL_FUSED_SHADED_STATS; i++) shadow_out[i] = h_stats[VOL_FUSED_SHADED_STATS + i];
   return 0;
 }
 
@@ -1740,6 +1775,55 @@ extern "C" int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *T, gvt_hip_volume 
   gvt_hip_volume_fused_shaded_stats S{};
   const int rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, allow, S);
   if (!rc && stats) *stats = S;
+  return rc;
+}
+
+// ---- shadowed surfaces (the contract: include/gvt_hip.h, "shadowed surfaces"; the kernel: volume_fused_shadow.inc)
+extern "C" int gvt_hip_volume_frame_shadowed(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                             const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                                             const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats *stats) {
+  int rc;
+  if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
+  if (!params) { set_error("volume_frame_shadowed: null params"); return GVT_HIP_ERR_INVALID; }
+  if (params->flags) { set_error("volume_frame_shadowed: unknown flag bits %u", params->flags); return GVT_HIP_ERR_INVALID; }
+  if (params->bias < 1 || params->bias > 64) { set_error("volume_frame_shadowed: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
+  bool any_surface = false, any_light = false;
+  for (size_t i = 0; i < n_inst; i++) {
+    any_surface = any_surface || volumes[i]->n_iso + volumes[i]->n_pl > 0;
+    any_light = any_light || volumes[i]->n_lights > 0;
+  }
+  gvt_hip_volume_fused_shaded_stats S{};
+  uint64_t sh[VOL_FUSED_SHADOW_STATS - VOL_FUSED_SHADED_STATS] = {};
+  const bool inert = !any_surface || !any_light; // nothing a shadow could fall on, or nothing that casts one
+  if (inert) {
+    rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, S);
+  } else {
+    uint32_t features = 0;
+    const char *why = "";
+    if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, features, &why)) { // (no loop renders shadows: refused, nothing changed)
+      set_error("volume_frame_shadowed: the frame has surfaces and lights but is not eligible for the fused kernel: %s", why);
+      return GVT_HIP_ERR_INVALID;
+    }
+    const gvt_hip_volume *A = volumes[0];
+    ShadowDev H{};
+    for (int j = 0; j < A->n_lights; j++) { // towards the light: the direction lights_dev's ldir is the negative of, in world space
+      const float x = A->lpos[j][0], y = A->lpos[j][1], z = A->lpos[j][2];
+      const float len = sqrtf((x * x + y * y) + z * z);
+      if (!(len > 0.f && std::isfinite(len))) continue; // (no ray: T_j = 1)
+      H.ws[j][0] = x / len; H.ws[j][1] = y / len; H.ws[j][2] = z / len;
+      H.usable |= 1u << j;
+    }
+    H.t0 = (float)(params->bias - 1) * A->dt;
+    rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh);
+  }
+  if (!rc && stats) {
+    gvt_hip_volume_shadow_stats O{};
+    O.fused = S.fused; O.features = S.features; O.samples_marched = S.samples_marched; O.samples_gathered = S.samples_gathered; O.brick_visits = S.brick_visits;
+    O.rays_deposited = S.rays_deposited; O.adapter_calls = S.adapter_calls; O.crossings_rendered = S.crossings_rendered; O.samples_shaded = S.samples_shaded;
+    O.shadowed = inert ? 0u : 1u;
+    O.shadow_rays = sh[0]; O.shadow_brick_visits = sh[1]; O.shadow_crossings = sh[2]; O.shadow_samples_marched = sh[3]; O.shadow_samples_gathered = sh[4];
+    *stats = O;
+  }
   return rc;
 }
 

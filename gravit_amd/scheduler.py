@@ -563,9 +563,13 @@ class VolumeTracer:
     fused: frame() goes through gvt_hip_volume_frame_fused -- every brick in ONE march launch where the frame is eligible (plain bricks of
     one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop.
     fused_shaded (with fused): frame() goes through gvt_hip_volume_frame_fused_shaded with both bits (fused_allow), so frames with
-    isovalues, slice planes or lit fog are fused too; without it such frames take the loop, as ever."""
+    isovalues, slice planes or lit fog are fused too; without it such frames take the loop, as ever.
+    shadows: frame() goes through gvt_hip_volume_frame_shadowed whatever fused says -- a crossing is lit only by the lights that reach it,
+    a shadow ray per light marched inside the one launch; shadow_bias = the lattice index of a shadow ray's first sample (1 .. 64; 2 is
+    a choice, not a measurement).  A frame that has surfaces and lights but cannot be fused is refused (GvtHipError): no loop renders
+    shadows.  Without surfaces or without lights the frame is fused_shaded's."""
 
-    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False):
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -589,6 +593,9 @@ class VolumeTracer:
         self.fused_shaded = bool(fused_shaded)
         self.fused_allow = capi.FUSED_SURFACES | capi.FUSED_LIT  # fused_shaded=True: the allow word of gvt_hip_volume_frame_fused_shaded
         self.fused_stats = None  # fused=True: gvt_hip_volume_fused_stats (fused_shaded: gvt_hip_volume_fused_shaded_stats) of the last frame, as a dict
+        self.shadows = bool(shadows)
+        self.shadow_bias = int(shadow_bias)
+        self.shadow_stats = None  # shadows=True: gvt_hip_volume_shadow_stats of the last frame, as a dict
         self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
 
     def frame(self, depth=None):
@@ -602,7 +609,15 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        if self.fused and self.fused_shaded:
+        if self.shadows:
+            st = capi.VolumeShadowStats()
+            params = capi.VolumeShadowParams(0, self.shadow_bias)
+            capi.check(capi.load().gvt_hip_volume_frame_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                                 C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
+                                                                 C.byref(params), C.byref(st)), "gvt_hip_volume_frame_shadowed")
+            self.shadow_stats = st.as_dict()
+            calls = C.c_uint64(st.adapter_calls)
+        elif self.fused and self.fused_shaded:
             st = capi.VolumeFusedShadedStats()
             capi.check(capi.load().gvt_hip_volume_frame_fused_shaded(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
                                                                      C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
@@ -684,9 +699,18 @@ class VolumeTracer:
     def stats(self):
         """The bricks' counters summed (they accumulate over frames).  fused=True adds fused, brick_visits and rays_deposited of the last
         frame, and where that frame was fused samples_marched / samples_gathered are ITS counts: the bricks' own did not move.
-        fused_shaded=True adds features and, where the frame was fused, its crossings_rendered / samples_shaded likewise."""
+        fused_shaded=True adds features and, where the frame was fused, its crossings_rendered / samples_shaded likewise.
+        shadows=True: the last frame's gvt_hip_volume_shadow_stats in fused_shaded's form (the camera rays' counters), and beside them
+        shadowed, shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched and shadow_samples_gathered."""
         out = self._brick_stats()
-        if self.fused and self.fused_stats is not None:
+        if self.shadows and self.shadow_stats is not None:
+            f = self.shadow_stats
+            out.update({k: v for k, v in f.items() if k.startswith("shadow")})
+            out.update(fused=f["fused"], brick_visits=f["brick_visits"], rays_deposited=f["rays_deposited"], features=f["features"])
+            if f["fused"]:
+                out.update(samples_marched=f["samples_marched"], samples_gathered=f["samples_gathered"], crossings_rendered=f["crossings_rendered"],
+                           samples_shaded=f["samples_shaded"])
+        elif self.fused and self.fused_stats is not None:
             f = self.fused_stats
             out.update(fused=f["fused"], brick_visits=f["brick_visits"], rays_deposited=f["rays_deposited"])
             if f["fused"]:
@@ -884,8 +908,12 @@ class VolumeDomainTracer(DomainTracer):
     size and both loops (include/gvt_hip.h, "volume domains across ranks"): a pixel has one ray, so one deposit, on the rank where the
     ray ends; the sum-reduce and the rows_only rectangles add it to zeros."""
 
-    def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False):
+    def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False,
+                 shadows=False):
         from types import SimpleNamespace
+
+        if shadows:  # (a shadow ray is marched to its end by the lane that needs it: a rank does not hold the foreign bricks it crosses)
+            raise ValueError("VolumeDomainTracer: shadows need every brick of the volume on one device (VolumeTracer(shadows=True))")
 
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         if m is not None:  # (whatever backend marches the bricks: the next-brick rule is the same)
@@ -951,7 +979,8 @@ class MixedTracer:
     (gvt_hip_fb_composite_over; the result is in the volume tracer's framebuffer).  The reference has no such path: shuffleRays
     takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel)."""
 
-    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False):
+    def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
+                 shadows=False, shadow_bias=2):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -965,7 +994,9 @@ class MixedTracer:
         self.mesh = NativeTracer(self.scene, normal_mode)
         self.depth = DepthPlane(camera.width, camera.height)
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
-                                   fused_shaded=fused_shaded)  # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too)
+                                   fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias)
+        # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; shadows: the volume's surfaces shadowed by the
+        # volume -- the meshes cast no shadow into it)
 
     def frame(self):
         self.mesh()

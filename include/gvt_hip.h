@@ -794,6 +794,60 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
                                       const gvt_hip_depth *depth /* may be NULL */, uint32_t allow,
                                       gvt_hip_volume_fused_shaded_stats *stats /* may be NULL */);
 
+/* ---- shadowed surfaces: shadow rays marched inside the fused frame (additive: the ABI revision stays 6, no entry point above changes) ----
+ * gvt_hip_volume_frame_shadowed is the shaded fused frame in which a crossing is lit only by the light that reaches it.  A shadow ray
+ * crosses bricks; it is marched to its end by the lane whose camera ray needs it, inside the one launch, so a pixel keeps ONE writer
+ * and the image stays the same bits however the volume is bricked.
+ * INERT.  A frame in which no brick has a surface, or no brick has a light, cannot show a shadow: the call is then
+ * gvt_hip_volume_frame_fused_shaded with allow = GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT in every respect, its fallback to the loop
+ * included; shadowed = 0 and the shadow counters are 0.
+ * REFUSED.  A frame that has a surface and a light but is not eligible for the shaded fused kernel under that allow word (subgrids;
+ * GVT_HIP_VOLUME_GRADIENT_CENTRAL on a brick of a frame with an isovalue; bricks of different grids, tables, matrices, surfaces or
+ * lights; more than 256 bricks): no loop renders shadows, so the call returns GVT_HIP_ERR_INVALID with a message that names the clause.
+ * A null params pointer, flags != 0 and a bias outside 1 .. 64 are refused likewise.  A refusal changes nothing: the framebuffer is not
+ * cleared, the queues are untouched.  Argument errors are gvt_hip_volume_frame's / _clipped's.
+ * CONTRACT.  The shadowed frame is the shaded fused frame with one change.  At a lattice sample k of a camera ray at which at least one
+ * crossing is rendered, a transmittance T_j is found once per light j before the first crossing is composited; all crossings of that
+ * sample share it, and the light loop of the crossing's shading becomes
+ *     ndl_s = ndl * T_j;   sum[a] = sum[a] + lcol[j][a] * ndl_s;
+ * Everything else is as it was: the len > 0 rule, ka + kd * sum, f, C and A.  Lit fog samples are lit as before and are NOT shadowed.
+ * T_j is defined by the contract that exists.  The shadow ray has the world origin wp[a] = wo[a] + wd[a] * t with t = (float)k * dt (the
+ * world ray as it stands in the camera's list), the world direction ws_j = lpos_j / sqrt((x*x + y*y) + z*z) computed on the host in
+ * float32 (the lights are directional; this is the direction towards the light), t_min = (float)(bias - 1) * dt, and no colour, no
+ * opacity, no flags and no clip.  Let A_s be the opacity this ray would deposit as a camera ray of the shaded fused frame over the same
+ * bricks with the same surfaces and shading mode NONE -- its first brick by the next-brick rule from none, the surface visits, the
+ * carried side mask, the arrives-opaque rule, the contiguity rule, the 2^22 limit, GVT_HIP_VOLUME_OPAQUE_A ending it, exits growing
+ * from hop to hop.  Then T_j = 1 - A_s.  A ray that meets no brick has A_s = 0.  A light whose ws_j is zero or not finite casts no ray:
+ * its T_j = 1.  (Opacity never depends on colour in the march, so the kernel runs its own visit with the colour dead.)
+ * CONSEQUENCES.  The image is the same bits for every bricking and with or without macro-cell skipping: wp, ws_j and every shadow sample
+ * are functions of global vertex values.  With T_j = 1 everywhere the bits are gvt_hip_volume_frame_fused_shaded's.  Where every T_j = 0
+ * a pixel has the bits of the same frame rendered with kd = 0.
+ * DEVIATIONS.  (1) A surface is rendered at the far sample of its step, so a shadow ray towards a light on the camera's side would
+ * cross its own sheet again; bias is the remedy: the first shadow sample is lattice index `bias`, and a first sample has no previous
+ * sides, so nothing within `bias` steps casts a shadow.  (2) The geometry of a mixed frame casts no shadow into the volume: the depth
+ * plane clips camera rays only.  (3) The fog is not shadowed.  (4) At samples > 1 deposits meet in arrival order, as ever.
+ * COUNTERS.  shadow_rays = (samples with at least one rendered crossing) x (lights with a usable ws_j); shadow_brick_visits,
+ * shadow_crossings and shadow_samples_marched / _gathered are the fused frame's counters applied to the shadow rays.  They are kept
+ * apart from the camera rays' counters, which equal those of the unshadowed frame whenever the two images agree.
+ * OUT OF SCOPE.  Ambient occlusion; shadowed fog; geometry shadowing the volume or the volume attenuating mesh shadow rays; the Domain
+ * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR and CENTRAL frames; shadows in the per-brick loop. */
+typedef struct {
+  uint32_t flags; /* must be 0 */
+  int32_t bias;   /* 1 .. 64, lattice steps */
+} gvt_hip_volume_shadow_params;
+typedef struct {
+  uint32_t fused, features;  /* the fields of gvt_hip_volume_fused_shaded_stats, same order and meaning (the camera rays' counters) */
+  uint64_t samples_marched, samples_gathered, brick_visits, rays_deposited, adapter_calls;
+  uint64_t crossings_rendered, samples_shaded;
+  uint32_t shadowed;         /* 1: the shadow kernel ran; 0: shadows were inert (above) */
+  uint32_t pad;
+  uint64_t shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched, shadow_samples_gathered;
+} gvt_hip_volume_shadow_stats;
+int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                  const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
+                                  const gvt_hip_depth *depth /* may be NULL */, const gvt_hip_volume_shadow_params *params,
+                                  gvt_hip_volume_shadow_stats *stats /* may be NULL */);
+
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
 void gvt_hip_fb_destroy(gvt_hip_fb *);

@@ -45,6 +45,11 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              the same protocol: --surfaces = the "thin" frame with the two isovalues the field reaches (opacity
                                              0.3, one light), --shade = lit fog by one light under every --tf table; with each the crossings
                                              and the samples shaded per frame, and the two framebuffers compared bitwise after every pair
+  python tools/volume_bench.py --fused --surfaces --shadows   shadowed surfaces (gvt_hip_volume_frame_shadowed): --surfaces' frame shadowed
+                                             against the same frame through the shaded fused kernel, alternating frame by frame on ONE
+                                             tracer; with each the shadow rays and the shadow samples per frame, so that the cost per shadow
+                                             sample stands beside the camera march's; the shadowed framebuffers of the brickings of one
+                                             grid compared bitwise with each other ("same_bits_as_first": they must agree)
 """
 import argparse
 import json
@@ -221,6 +226,40 @@ def run_fused(n, split, steps, warmup, rate, kind, vol, dtype="f32", shaded=None
             "fused_gsamples_per_s": round(st["samples_marched"] / float(np.median(fused)) / 1e6, 3),
             "fused_over_loop": round(float(np.median(fused)) / float(np.median(loop)), 4), "fused_wins": bool(max(fused) < min(loop)), "same_bits": same}
 
+def run_shadows(n, split, steps, warmup, rate, vol, dtype="f32", first=None, bias=2):
+    """--surfaces' reached frame through the shaded fused kernel against the same frame shadowed, alternating frame by frame on one tracer
+    (VolumeTracer.shadows switches the entry point).  first: the shadowed framebuffer of another bricking of the same grid, compared
+    bitwise.  Returns (row, the shadowed framebuffer)."""
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split)
+    tr = VolumeTracer(bricks, camera(), transfer("thin", dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=True, shadow_bias=bias)
+    _, lo, hi = DTYPES[dtype]
+    tr.set_surfaces(tuple(lo + v * (hi - lo) for v in SURFACE_MODES["reached"]), (), 0.3).set_lights([((3.0, 4.0, 5.0), (1.0, 1.0, 1.0))])
+    plain, shadowed = [], []
+
+    def frame(flag):
+        tr.shadows = flag
+        tr.frame()
+
+    for i in range(warmup + steps):
+        plain.append(timed(lambda: frame(False)))
+        ps = tr.stats()
+        shadowed.append(timed(lambda: frame(True)))
+    plain, shadowed = plain[warmup:], shadowed[warmup:]
+    st = tr.stats()
+    fb = tr.framebuffer(False).copy()
+    extra_ms = float(np.median(shadowed)) - float(np.median(plain))
+    row = {"mode": "fused_shadows", "n": n, "dtype": dtype, "tf": "thin", "bricks": int(np.prod(split)), "sampling_rate": rate, "bias": bias,
+           "plain_ms_median": med(plain), "plain_ms_min": round(min(plain), 3), "plain_ms_max": round(max(plain), 3),
+           "shadowed_ms_median": med(shadowed), "shadowed_ms_min": round(min(shadowed), 3), "shadowed_ms_max": round(max(shadowed), 3),
+           "shadowed_over_plain": round(float(np.median(shadowed)) / float(np.median(plain)), 4), "shadowed": int(st["shadowed"]),
+           "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "crossings_per_frame": int(st["crossings_rendered"]),
+           "camera_counters_same": bool(all(st[k] == ps[k] for k in ("samples_marched", "samples_gathered", "crossings_rendered", "brick_visits", "rays_deposited"))),
+           "shadow_rays": int(st["shadow_rays"]), "shadow_brick_visits": int(st["shadow_brick_visits"]), "shadow_crossings": int(st["shadow_crossings"]),
+           "shadow_samples": int(st["shadow_samples_marched"]), "shadow_samples_interpolated": int(st["shadow_samples_gathered"]),
+           "plain_ns_per_sample": round(float(np.median(plain)) * 1e6 / max(st["samples_marched"], 1), 4),
+           "extra_ns_per_shadow_sample": round(extra_ms * 1e6 / max(st["shadow_samples_marched"], 1), 4),
+           "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())}
+    return row, fb
 
 
 def run_shade(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
@@ -539,6 +578,8 @@ def main():
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="f32")
     ap.add_argument("--fused", action="store_true")
     ap.add_argument("--bricks", type=int, nargs="+", choices=sorted(FUSED_SPLITS), default=sorted(FUSED_SPLITS), help="with --fused: the brickings")
+    ap.add_argument("--shadows", action="store_true", help="with --fused --surfaces: the shadowed frame against the shaded fused frame")
+    ap.add_argument("--bias", type=int, default=2, help="with --shadows: the first shadow sample's lattice index")
     a = ap.parse_args()
     if a.update or a.domains:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
@@ -570,6 +611,18 @@ def main():
             for r in run_amr(n, a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate):
                 out["runs"].append(r)
                 print(json.dumps(r), flush=True)
+        a.sizes = []
+    if a.shadows and not (a.fused and a.surfaces):
+        ap.error("--shadows goes with --fused --surfaces")
+    for n in a.sizes if a.shadows else ():
+        vol = noise(n, a.dtype)
+        first = None
+        for nb in a.bricks:
+            r, fb = run_shadows(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, vol, a.dtype, first, a.bias)
+            first = fb if first is None else first
+            out["runs"].append(r)
+            print(json.dumps(r), flush=True)
+    if a.shadows:
         a.sizes = []
     for n in a.sizes if a.fused else ():
         vol = noise(n, a.dtype)
