@@ -686,6 +686,22 @@ class HipVolumeAdapter:
         capi.check(self.lib.gvt_hip_volume_get_shaded(self.h, C.byref(n)), "gvt_hip_volume_get_shaded")
         return n.value
 
+    def light_grid_info(self):
+        """present, current, n_planes, bias, bytes of the brick's light transmittance grid (gvt_hip_volume_light_grid_info)."""
+        i = capi.VolumeLightGridState()
+        capi.check(self.lib.gvt_hip_volume_light_grid_info(self.h, C.byref(i)), "gvt_hip_volume_light_grid_info")
+        return i.as_dict()
+
+    def light_grid(self, j):
+        """The baked transmittance towards light j at the brick's vertices, (nz, ny, nx) float32 (gvt_hip_volume_light_grid_download); a
+        light that was unusable at the bake, or no grid: GvtHipError."""
+        out = np.zeros(tuple(int(c) for c in self.counts[::-1]), np.float32)
+        capi.check(self.lib.gvt_hip_volume_light_grid_download(self.h, int(j), capi.ptr(out)), "gvt_hip_volume_light_grid_download")
+        return out
+
+    def light_grid_release(self):
+        capi.check(self.lib.gvt_hip_volume_light_grid_release(self.h), "gvt_hip_volume_light_grid_release")
+
     def march_queue(self, queue, minv, may_clip=False):
         """gvt_hip_volume_march_queue: Adapter::trace on a device-resident RayQueue, in place and without a host wait; the rays keep
         their flags for the volume shuffle.  may_clip: the queue may hold rays that carry RAY_CLIP."""

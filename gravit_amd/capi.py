@@ -44,6 +44,8 @@ SYMBOLS = [
     "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
     "gvt_hip_volume_frame_fused", "gvt_hip_volume_frame_fused_shaded",
     "gvt_hip_volume_frame_shadowed",
+    "gvt_hip_volume_light_grid_bake", "gvt_hip_volume_light_grid_download", "gvt_hip_volume_light_grid_info", "gvt_hip_volume_light_grid_release",
+    "gvt_hip_volume_frame_fog_shadowed",
 ]
 
 
@@ -127,6 +129,36 @@ class VolumeShadowStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class VolumeLightGridParams(C.Structure):
+    """gvt_hip_volume_light_grid_params: flags must be 0; bias = the first sample of a vertex's shadow ray, 1 .. 64."""
+    _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
+
+
+class VolumeLightGridStats(C.Structure):
+    """gvt_hip_volume_light_grid_stats: what gvt_hip_volume_light_grid_bake reports of one bake."""
+    _fields_ = [("rays", C.c_uint64), ("samples_marched", C.c_uint64), ("samples_gathered", C.c_uint64), ("crossings", C.c_uint64), ("bytes", C.c_uint64),
+                ("ms", C.c_float), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class VolumeLightGridState(C.Structure):
+    """gvt_hip_volume_light_grid_state: what gvt_hip_volume_light_grid_info reports of one volume."""
+    _fields_ = [("present", C.c_uint32), ("current", C.c_uint32), ("n_planes", C.c_int32), ("bias", C.c_int32), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class VolumeFogShadowStats(C.Structure):
+    """gvt_hip_volume_fog_shadow_stats: the shadowed frame's counters, then the lit fog samples that read the light grids."""
+    _fields_ = VolumeShadowStats._fields_ + [("fog_samples_shadowed", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
@@ -203,6 +235,11 @@ def load():
                                                           C.c_void_p]
         lib.gvt_hip_volume_frame_shadowed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p]
+        lib.gvt_hip_volume_frame_fog_shadowed.argtypes = lib.gvt_hip_volume_frame_shadowed.argtypes
+        lib.gvt_hip_volume_light_grid_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_light_grid_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.gvt_hip_volume_light_grid_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_light_grid_release.argtypes = [C.c_void_p]
         lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
@@ -284,5 +321,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeShadowParams", "VolumeShadowStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeShadowParams", "VolumeShadowStats", "VolumeLightGridParams", "VolumeLightGridStats", "VolumeLightGridState", "VolumeFogShadowStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

@@ -49,6 +49,7 @@ enum ScratchSlot {
   SCR_WIRE_TABLE,  // the queue table of a batched wire conversion (trace.hip wire_table)
   SCR_VOL_KEEP,    // the keep mask of gvt_hip_volume_camera_filter on the device (volume.hip)
   SCR_VOL_BRICKS, SCR_VOL_FUSED, // the fused frame's per-brick records and its counter words, six or with shadows eleven (volume.hip volume_frame_fused)
+  SCR_VOL_GRIDS,   // the light grids' per-brick table beside SCR_VOL_BRICKS: the bake's work list and planes, the fog-shadowed frame's planes (volume.hip)
   SCRATCH_COUNT
 };
 struct Knobs {

@@ -21,6 +21,9 @@
 //                                           slice planes or lit fog: the same structure around the surface / lit visit (volume_fused_shaded.inc)
 //   gvt_hip_volume_frame_shadowed / k_volume_march_fused_shadow   ... with the crossings lit only by the lights that reach them: a lane marches the
 //                                           shadow rays of its camera ray itself, from brick to brick (volume_fused_shadow.inc)
+//   gvt_hip_volume_light_grid_bake / k_volume_bake_light   the transmittance towards every light at every grid vertex, kept beside the samples
+//                                           (volume_light_grid.inc), and gvt_hip_volume_frame_fog_shadowed / k_volume_march_fused_fog, the
+//                                           shadowed frame whose lit fog samples interpolate it (volume_fused_fog.inc)
 //   gvt_hip_volume_march_queue / _camera_filter   the Domain scheduler's steps over bricks spread over ranks (algorithm/DomainTracer.h:148-326): the march
 //                                           on a device queue, and the camera step with shuffleDropRays' keep mask (k_vol_classify<MASK>); the
 //                                           exchange's batched wire conversions are beside k_planes_to_aos (convert.inc, trace.hip)
@@ -79,6 +82,16 @@ struct gvt_hip_volume {
   unsigned ghost_mask = 0;       // bit 2 * axis + side: that face has a layer
   void *d_ghost = nullptr;
   uint64_t central_marches = 0;
+  // the light transmittance grids of the fog-shadowed frame (gvt_hip_volume_light_grid_bake; volume_light_grid.inc): lg_planes planes of
+  // the brick's vertices, one per usable light in the order of their bits.  lg_current: no call that changes what a shadow ray meets has
+  // touched the volume since the bake; lg_bake / lg_index / lg_count / lg_m / lg_minv: which bake, and what it covered
+  float *d_lgrid = nullptr;
+  int lg_planes = 0, lg_bias = 0;
+  unsigned lg_usable = 0;
+  bool lg_current = false;
+  uint64_t lg_bake = 0;
+  size_t lg_index = 0, lg_count = 0;
+  float lg_m[16] = {}, lg_minv[16] = {};
 };
 
 namespace {
@@ -848,6 +861,8 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 #include "volume_fused.inc" // k_volume_march_fused
 #include "volume_fused_shaded.inc" // k_volume_march_fused_shaded
 #include "volume_fused_shadow.inc" // k_volume_march_fused_shadow
+#include "volume_light_grid.inc" // k_volume_bake_light
+#include "volume_fused_fog.inc" // k_volume_march_fused_fog
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
@@ -1231,7 +1246,7 @@ extern "C" int gvt_hip_volume_get_voxel_type(gvt_hip_volume *V, int *type_out, s
 extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
-  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost);
+  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost); hipFree(V->d_lgrid);
   hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
   delete V;
 }
@@ -1261,6 +1276,7 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   }
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
   HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
+  V->lg_current = false; // (a light grid baked under the old table is stale)
   for (int i = 0; i < 256; i++) { V->tf_a[i] = tf[i].w; V->tf_rgb[i][0] = tf[i].x; V->tf_rgb[i][1] = tf[i].y; V->tf_rgb[i][2] = tf[i].z; }
   V->tf_lo = value_lo; V->tf_hi = value_hi; V->has_tf = true;
   return rebuild_tables(V);
@@ -1285,6 +1301,7 @@ extern "C" int gvt_hip_volume_update_samples_typed(gvt_hip_volume *V, const void
   }
   hipStream_t st = gctx().stream;
   HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the samples)
+  V->lg_current = false; // (a light grid baked from the old samples is stale)
   HIPCHK(hipMemcpyAsync(V->d_vox, samples, voxel_bytes(V->vtype) * total, (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
@@ -1324,6 +1341,7 @@ extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isova
     if (!finite || (p[0] == 0.f && p[1] == 0.f && p[2] == 0.f)) { set_error("volume_set_surfaces: slice %d has a zero or non-finite plane", i); return GVT_HIP_ERR_INVALID; }
   }
   V->n_iso = n_iso; V->n_pl = n_slices; V->surf_alpha = opacity;
+  V->lg_current = false; // (the surfaces cast shadows: a light grid baked under the old ones is stale)
   for (int i = 0; i < n_iso; i++) V->iso[i] = isovalues[i];
   for (int i = 0; i < n_slices; i++)
     for (int a = 0; a < 4; a++) V->plane[i][a] = slices[4 * i + a];
@@ -1338,6 +1356,7 @@ extern "C" int gvt_hip_volume_set_lights(gvt_hip_volume *V, const float *positio
   for (int i = 0; i < 3 * n; i++)
     if (!std::isfinite(positions[i]) || !std::isfinite(colours[i])) { set_error("volume_set_lights: light %d is not finite", i / 3); return GVT_HIP_ERR_INVALID; }
   V->n_lights = n; V->ka = ka; V->kd = kd;
+  V->lg_current = false; // (a light grid holds one plane per light of the old list)
   for (int j = 0; j < n; j++)
     for (int a = 0; a < 3; a++) { V->lpos[j][a] = positions[3 * j + a]; V->lcol[j][a] = colours[3 * j + a]; }
   return 0;
@@ -1663,13 +1682,28 @@ void launch_fused_shadow(uint32_t features, const gvt_hip_depth *depth, unsigned
   else k_volume_march_fused_shadow<VT, false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
 }
 
+// the fog-shadowed kernels' instantiation: clipped or not (lit fog is implied), with surfaces or -- the lean kernel -- without
+template <typename VT, typename... Args>
+void launch_fused_fog(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
+                      const FusedBrick *d_bricks, const FogBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
+  if (!(features & GVT_HIP_FUSED_SURFACES)) {
+    const LightDev L = light_dev(V0, M);
+    if (depth) k_volume_march_fused_fog_lean<VT, true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
+    else k_volume_march_fused_fog_lean<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
+    return;
+  }
+  if (depth) k_volume_march_fused_fog<VT, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
+  else k_volume_march_fused_fog<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
+}
+
 // the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
 // features: fused_eligible's -- 0 launches k_volume_march_fused, anything else the shaded kernel with the table of volumes[0]
 // shadow (gvt_hip_volume_frame_shadowed; features has SURFACES then): the launch is k_volume_march_fused_shadow's, and shadow_out gets
-// its five further counter words, read back in the same wait
+// its five further counter words, read back in the same wait.  fog (gvt_hip_volume_frame_fog_shadowed; shadow is given and features has
+// LIT): the launch is k_volume_march_fused_fog's, and the bricks' light grid planes travel in a second table beside the records
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
                        gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S, const ShadowDev *shadow = nullptr,
-                       uint64_t *shadow_out = nullptr) {
+                       uint64_t *shadow_out = nullptr, bool fog = false) {
   Ctx &C = gctx();
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;
@@ -1686,20 +1720,25 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
-  static_assert(sizeof(FusedBrick) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table fits the staging block");
+  FogBrick *d_grids = fog ? (FogBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(FogBrick) * n_inst) : nullptr;
+  if (fog && !d_grids) return GVT_HIP_ERR_DEVICE;
+  static_assert((sizeof(FusedBrick) + sizeof(FogBrick)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table and the grids' fit the staging block");
   void *stage = nullptr;
   if ((rc = pinned_stage_begin(&stage))) return rc;
   FusedBrick *h = (FusedBrick *)stage;
+  FogBrick *hg = (FogBrick *)(h + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     FusedBrick R{};
     R.vox = B->d_vox;
     R.mc = (features & GVT_HIP_FUSED_SURFACES) ? (const uint8_t *)B->d_cells : B->d_mc; // (the surface visit reads the per-cell words, never the skip bytes)
+    if (fog) hg[i].grid = B->d_lgrid;
     R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
     for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
     h[i] = R;
   }
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if ((rc = pinned_stage_end())) return rc;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
   HIPCHK(hipMemsetAsync(d_stats, 0, n_words * sizeof(unsigned long long), C.stream));
@@ -1711,6 +1750,11 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if (n)
     with_voxel_type(volumes[0]->vtype, [&](auto t) {
       using VT = decltype(t);
+      if (shadow && fog) {
+        launch_fused_fog<VT>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_grids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work,
+                             d_stats);
+        return;
+      }
       if (shadow) {
         launch_fused_shadow<VT>(features, depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba,
                                 n_pix, work, d_stats);
@@ -1778,53 +1822,290 @@ extern "C" int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *T, gvt_hip_volume 
   return rc;
 }
 
-// ---- shadowed surfaces (the contract: include/gvt_hip.h, "shadowed surfaces"; the kernel: volume_fused_shadow.inc)
-extern "C" int gvt_hip_volume_frame_shadowed(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
-                                             const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
-                                             const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats *stats) {
+// ---- shadowed surfaces (the contract: include/gvt_hip.h, "shadowed surfaces"; the kernel: volume_fused_shadow.inc) and shadowed fog
+// ("shadowed fog"; volume_light_grid.inc, volume_fused_fog.inc)
+namespace {
+
+// the shadow rays' directions: towards each light, in world space (the direction lights_dev's ldir is the negative of); t0 from the bias
+ShadowDev shadow_dev(const gvt_hip_volume *A, int bias) {
+  ShadowDev H{};
+  for (int j = 0; j < A->n_lights; j++) {
+    const float x = A->lpos[j][0], y = A->lpos[j][1], z = A->lpos[j][2];
+    const float len = sqrtf((x * x + y * y) + z * z);
+    if (!(len > 0.f && std::isfinite(len))) continue; // (no ray: T_j = 1)
+    H.ws[j][0] = x / len; H.ws[j][1] = y / len; H.ws[j][2] = z / len;
+    H.usable |= 1u << j;
+  }
+  H.t0 = (float)(bias - 1) * A->dt;
+  return H;
+}
+
+// Do these bricks, in this order and under these matrices, all hold a light grid of ONE bake that nothing has made stale since?
+bool light_grids_current(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, unsigned usable, const char **why) {
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    if (!B->d_lgrid) { *why = "a brick holds no light grid (gvt_hip_volume_light_grid_bake)"; return false; }
+    if (!B->lg_current) { *why = "a brick's light grid is stale: its samples, table, surfaces, lights or subgrids were set after the bake"; return false; }
+    if (B->lg_bake != volumes[0]->lg_bake || B->lg_index != i || B->lg_count != n_inst) { *why = "the light grids were not baked over exactly these bricks in this order"; return false; }
+    if (!same_bits(B->lg_m, m + 16 * i, sizeof(B->lg_m)) || !same_bits(B->lg_minv, minv + 16 * i, sizeof(B->lg_minv))) { *why = "the light grids were baked under another matrix"; return false; }
+    if (B->lg_usable != usable || B->lg_planes != __builtin_popcount(usable)) { *why = "the light grids were baked for other lights"; return false; }
+  }
+  return true;
+}
+
+// both shadowed frames.  fog: gvt_hip_volume_frame_fog_shadowed (fn: the entry point's name in the error texts)
+int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                               const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                               const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats &O, uint64_t &fog_samples) {
   int rc;
   if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
-  if (!params) { set_error("volume_frame_shadowed: null params"); return GVT_HIP_ERR_INVALID; }
-  if (params->flags) { set_error("volume_frame_shadowed: unknown flag bits %u", params->flags); return GVT_HIP_ERR_INVALID; }
-  if (params->bias < 1 || params->bias > 64) { set_error("volume_frame_shadowed: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
-  bool any_surface = false, any_light = false;
+  if (!params) { set_error("%s: null params", fn); return GVT_HIP_ERR_INVALID; }
+  if (params->flags) { set_error("%s: unknown flag bits %u", fn, params->flags); return GVT_HIP_ERR_INVALID; }
+  if (params->bias < 1 || params->bias > 64) { set_error("%s: bias %d, 1 to 64 lattice steps are allowed", fn, params->bias); return GVT_HIP_ERR_INVALID; }
+  bool any_surface = false, any_light = false, any_lit = false;
   for (size_t i = 0; i < n_inst; i++) {
     any_surface = any_surface || volumes[i]->n_iso + volumes[i]->n_pl > 0;
     any_light = any_light || volumes[i]->n_lights > 0;
+    any_lit = any_lit || (volumes[i]->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && volumes[i]->n_lights > 0);
   }
   gvt_hip_volume_fused_shaded_stats S{};
   uint64_t sh[VOL_FUSED_SHADOW_STATS - VOL_FUSED_SHADED_STATS] = {};
-  const bool inert = !any_surface || !any_light; // nothing a shadow could fall on, or nothing that casts one
+  // nothing a shadow could fall on, or nothing that casts one (the fog frame: lit fog is something a shadow falls on)
+  const bool inert = !any_light || (!any_surface && !(fog && any_lit));
+  bool fog_ran = false;
   if (inert) {
     rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, S);
   } else {
     uint32_t features = 0;
     const char *why = "";
     if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, features, &why)) { // (no loop renders shadows: refused, nothing changed)
-      set_error("volume_frame_shadowed: the frame has surfaces and lights but is not eligible for the fused kernel: %s", why);
+      set_error("%s: the frame has %s and lights but is not eligible for the fused kernel: %s", fn, fog ? "surfaces or lit fog" : "surfaces", why);
       return GVT_HIP_ERR_INVALID;
     }
-    const gvt_hip_volume *A = volumes[0];
-    ShadowDev H{};
-    for (int j = 0; j < A->n_lights; j++) { // towards the light: the direction lights_dev's ldir is the negative of, in world space
-      const float x = A->lpos[j][0], y = A->lpos[j][1], z = A->lpos[j][2];
-      const float len = sqrtf((x * x + y * y) + z * z);
-      if (!(len > 0.f && std::isfinite(len))) continue; // (no ray: T_j = 1)
-      H.ws[j][0] = x / len; H.ws[j][1] = y / len; H.ws[j][2] = z / len;
-      H.usable |= 1u << j;
+    const ShadowDev H = shadow_dev(volumes[0], params->bias);
+    fog_ran = fog && (features & GVT_HIP_FUSED_LIT) && H.usable; // (no lit fog: gvt_hip_volume_frame_shadowed in every bit; no usable light: every Tg = 1, nothing is read)
+    if (fog_ran && !light_grids_current(volumes, m, minv, n_inst, H.usable, &why)) {
+      set_error("%s: the frame has lit fog but its bricks do not all hold a current light grid: %s", fn, why);
+      return GVT_HIP_ERR_INVALID;
     }
-    H.t0 = (float)(params->bias - 1) * A->dt;
-    rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh);
+    if (fog && (features & GVT_HIP_FUSED_LIT) && !(features & GVT_HIP_FUSED_SURFACES) && !H.usable) // (lit fog alone and no light casts a ray: the shaded fused frame)
+      rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S);
+    else
+      rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh, fog_ran);
   }
+  if (rc) return rc;
+  O = gvt_hip_volume_shadow_stats{};
+  O.fused = S.fused; O.features = S.features; O.samples_marched = S.samples_marched; O.samples_gathered = S.samples_gathered; O.brick_visits = S.brick_visits;
+  O.rays_deposited = S.rays_deposited; O.adapter_calls = S.adapter_calls; O.crossings_rendered = S.crossings_rendered; O.samples_shaded = S.samples_shaded;
+  O.shadowed = inert ? 0u : 1u;
+  O.shadow_rays = sh[0]; O.shadow_brick_visits = sh[1]; O.shadow_crossings = sh[2]; O.shadow_samples_marched = sh[3]; O.shadow_samples_gathered = sh[4];
+  fog_samples = fog_ran ? S.samples_shaded : 0;
+  return 0;
+}
+
+} // namespace
+
+extern "C" int gvt_hip_volume_frame_shadowed(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                             const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                                             const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats *stats) {
+  gvt_hip_volume_shadow_stats O{};
+  uint64_t fog_samples = 0;
+  const int rc = volume_frame_shadowed_impl("volume_frame_shadowed", false, T, volumes, m, minv, n_inst, cam, queues, fb, depth, params, O, fog_samples);
+  if (!rc && stats) *stats = O;
+  return rc;
+}
+
+extern "C" int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                                 const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                                                 const gvt_hip_volume_shadow_params *params, gvt_hip_volume_fog_shadow_stats *stats) {
+  gvt_hip_volume_shadow_stats O{};
+  uint64_t fog_samples = 0;
+  const int rc = volume_frame_shadowed_impl("volume_frame_fog_shadowed", true, T, volumes, m, minv, n_inst, cam, queues, fb, depth, params, O, fog_samples);
   if (!rc && stats) {
-    gvt_hip_volume_shadow_stats O{};
-    O.fused = S.fused; O.features = S.features; O.samples_marched = S.samples_marched; O.samples_gathered = S.samples_gathered; O.brick_visits = S.brick_visits;
-    O.rays_deposited = S.rays_deposited; O.adapter_calls = S.adapter_calls; O.crossings_rendered = S.crossings_rendered; O.samples_shaded = S.samples_shaded;
-    O.shadowed = inert ? 0u : 1u;
-    O.shadow_rays = sh[0]; O.shadow_brick_visits = sh[1]; O.shadow_crossings = sh[2]; O.shadow_samples_marched = sh[3]; O.shadow_samples_gathered = sh[4];
-    *stats = O;
+    gvt_hip_volume_fog_shadow_stats F{};
+    F.frame = O;
+    F.fog_samples_shadowed = fog_samples;
+    *stats = F;
   }
   return rc;
+}
+
+extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                              const gvt_hip_volume_light_grid_params *params, gvt_hip_volume_light_grid_stats *stats) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!volumes || !m || !minv || !params) { set_error("volume_light_grid_bake: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (n_inst < 1 || n_inst > VOL_DEST_MAX) { set_error("volume_light_grid_bake: %zu bricks, 1 to %d are allowed", n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
+  for (size_t i = 0; i < n_inst; i++)
+    if (!volumes[i] || !volumes[i]->has_tf) { set_error("volume_light_grid_bake: brick %zu is null or has no transfer function", i); return GVT_HIP_ERR_INVALID; }
+  if (params->flags) { set_error("volume_light_grid_bake: unknown flag bits %u", params->flags); return GVT_HIP_ERR_INVALID; }
+  if (params->bias < 1 || params->bias > 64) { set_error("volume_light_grid_bake: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
+  uint32_t features = 0;
+  const char *why = "";
+  if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, features, &why)) {
+    set_error("volume_light_grid_bake: the bricks are not eligible for the fused kernels: %s", why);
+    return GVT_HIP_ERR_INVALID;
+  }
+  const gvt_hip_volume *A = volumes[0];
+  uint64_t cells = 0, verts = 0;
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    if (!same_bits(m + 16 * i, m, 16 * sizeof(float))) { set_error("volume_light_grid_bake: bricks under different matrices"); return GVT_HIP_ERR_INVALID; }
+    if (!same_bits(B->gn, A->gn, sizeof(A->gn))) { set_error("volume_light_grid_bake: bricks of different grids (global counts)"); return GVT_HIP_ERR_INVALID; }
+    if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && B->n_iso > 0) { set_error("volume_light_grid_bake: central gradients on a brick of a frame with an isovalue"); return GVT_HIP_ERR_INVALID; }
+    // (fused_eligible compares surfaces and lights only where the frame renders them: the bake needs them equal whatever the shading)
+    if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float)) || !same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) ||
+        !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) { set_error("volume_light_grid_bake: bricks with different surfaces"); return GVT_HIP_ERR_INVALID; }
+    if (B->n_lights != A->n_lights || !same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights)) { set_error("volume_light_grid_bake: bricks with different lights"); return GVT_HIP_ERR_INVALID; }
+    cells += (uint64_t)(B->n[0] - 1) * (uint64_t)(B->n[1] - 1) * (uint64_t)(B->n[2] - 1);
+    verts += (uint64_t)B->n[0] * (uint64_t)B->n[1] * (uint64_t)B->n[2];
+    for (size_t k = 0; k < i; k++) { // owned cells [off, off + n - 1) per axis: disjoint
+      const gvt_hip_volume *K = volumes[k];
+      bool apart = false;
+      for (int a = 0; a < 3; a++) apart = apart || B->off[a] + B->n[a] - 1 <= K->off[a] || K->off[a] + K->n[a] - 1 <= B->off[a];
+      if (!apart) { set_error("volume_light_grid_bake: the bricks do not tile the grid: bricks %zu and %zu share a cell", k, i); return GVT_HIP_ERR_INVALID; }
+    }
+  }
+  if (cells != (uint64_t)(A->gn[0] - 1) * (uint64_t)(A->gn[1] - 1) * (uint64_t)(A->gn[2] - 1)) {
+    set_error("volume_light_grid_bake: the bricks do not tile the grid: they own %llu of its %llu cells", (unsigned long long)cells,
+              (unsigned long long)((uint64_t)(A->gn[0] - 1) * (uint64_t)(A->gn[1] - 1) * (uint64_t)(A->gn[2] - 1)));
+    return GVT_HIP_ERR_INVALID;
+  }
+  const ShadowDev H = shadow_dev(A, params->bias);
+  const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
+  if (!n_usable) { set_error("volume_light_grid_bake: no usable light (none set, or every position is zero)"); return GVT_HIP_ERR_INVALID; }
+  if (verts * n_usable > 0xffffffffull) { set_error("volume_light_grid_bake: %llu (vertex, light) pairs, at most 2^32 - 1", (unsigned long long)(verts * n_usable)); return GVT_HIP_ERR_INVALID; }
+  Ctx &C = gctx();
+  // the new planes, all before any brick changes
+  std::vector<float *> fresh(n_inst, nullptr);
+  const auto drop = [&]() { for (float *p : fresh) hipFree(p); };
+  uint64_t bytes = 0;
+  for (size_t i = 0; i < n_inst; i++) {
+    const size_t nb = sizeof(float) * (size_t)volumes[i]->n[0] * volumes[i]->n[1] * volumes[i]->n[2] * n_usable;
+    if (hipMalloc((void **)&fresh[i], nb) != hipSuccess) {
+      (void)hipGetLastError();
+      drop();
+      set_error("volume_light_grid_bake: no device memory for the planes of brick %zu (%zu bytes); the old grids are kept", i, nb);
+      return GVT_HIP_ERR_CAPACITY;
+    }
+    bytes += nb;
+  }
+  FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
+  LightGridBrick *d_parts = (LightGridBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(LightGridBrick) * n_inst);
+  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
+  unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const auto fail = [&](const char *what) {
+    set_error("volume_light_grid_bake: %s failed: %s; the old grids are kept", what, hipGetErrorString(hipGetLastError()));
+    hipStreamSynchronize(C.stream);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    drop();
+    return GVT_HIP_ERR_DEVICE;
+  };
+  if (!d_bricks || !d_parts || !d_stats || !work) return fail("a scratch allocation");
+  static_assert(VOL_BAKE_STATS <= VOL_FUSED_SHADOW_STATS, "the fused frames' counter words serve the bake");
+  static_assert((sizeof(FusedBrick) + sizeof(LightGridBrick)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "both tables fit the staging block");
+  void *stage = nullptr;
+  if (pinned_stage_begin(&stage)) return fail("the staging block");
+  FusedBrick *h = (FusedBrick *)stage;
+  LightGridBrick *hp = (LightGridBrick *)(h + VOL_DEST_MAX);
+  unsigned first = 0;
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    FusedBrick R{};
+    R.vox = B->d_vox;
+    R.mc = (const uint8_t *)B->d_cells; // (the surface visit's per-cell words: without surfaces they hold the skip bit alone)
+    R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2];
+    for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
+    h[i] = R;
+    hp[i] = LightGridBrick{ fresh[i], first, 0u };
+    first += (unsigned)((size_t)B->n[0] * B->n[1] * B->n[2]) * n_usable;
+  }
+  const unsigned n = first;
+  bool ok = hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess &&
+            hipMemcpyAsync(d_parts, hp, sizeof(LightGridBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess;
+  if (pinned_stage_end() || !ok) return fail("the table upload");
+  ok = hipMemsetAsync(work, 0, sizeof(unsigned), C.stream) == hipSuccess && hipMemsetAsync(d_stats, 0, VOL_BAKE_STATS * sizeof(unsigned long long), C.stream) == hipSuccess &&
+       hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+  if (!ok) return fail("the launch's preparation");
+  Mat4 M, Mi;
+  for (int k = 0; k < 16; k++) { M.m[k] = m[k]; Mi.m[k] = minv[k]; }
+  // the whole grid as one brick: offset 0, counts = the global counts, the global vertex box (gvt_hip_volume_create's expressions)
+  VolDev U = vol_dev(A);
+  U.vox = nullptr; U.mc = nullptr;
+  U.nx = A->gn[0]; U.ny = A->gn[1]; U.nz = A->gn[2]; U.ox = 0; U.oy = 0; U.oz = 0;
+  U.nbx = (A->gn[0] - 1 + 7) / 8; U.nby = (A->gn[1] - 1 + 7) / 8;
+  for (int a = 0; a < 3; a++) { U.lo[a] = A->go[a] + (float)0 * A->sp[a]; U.hi[a] = A->go[a] + (float)(A->gn[a] - 1) * A->sp[a]; }
+  const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
+  ok = hipEventRecord(e0, C.stream) == hipSuccess;
+  if (ok)
+    with_voxel_type(A->vtype, [&](auto t) {
+      using VT = decltype(t);
+      k_volume_bake_light<VT><<<blocks, VOL_BLOCK, 0, C.stream>>>(U, surf_dev(A, Mi), H, d_bricks, d_parts, (unsigned)n_inst, n, M, Mi, work, d_stats);
+    });
+  unsigned long long h_stats[VOL_BAKE_STATS] = {};
+  float ms = 0.f;
+  ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(e1, C.stream) == hipSuccess &&
+       hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, C.stream) == hipSuccess && hipStreamSynchronize(C.stream) == hipSuccess &&
+       hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+  if (!ok) return fail("the bake kernel");
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  // commit: every brick at once
+  static uint64_t bake_serial = 0;
+  bake_serial++;
+  for (size_t i = 0; i < n_inst; i++) {
+    gvt_hip_volume *B = volumes[i];
+    hipFree(B->d_lgrid);
+    B->d_lgrid = fresh[i];
+    B->lg_planes = (int)n_usable; B->lg_bias = params->bias; B->lg_usable = H.usable; B->lg_current = true;
+    B->lg_bake = bake_serial; B->lg_index = i; B->lg_count = n_inst;
+    std::memcpy(B->lg_m, m + 16 * i, sizeof(B->lg_m));
+    std::memcpy(B->lg_minv, minv + 16 * i, sizeof(B->lg_minv));
+  }
+  if (stats) {
+    gvt_hip_volume_light_grid_stats O{};
+    O.rays = n; O.samples_marched = h_stats[0]; O.samples_gathered = h_stats[1]; O.crossings = h_stats[2]; O.bytes = bytes; O.ms = ms;
+    *stats = O;
+  }
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_light_grid_download(gvt_hip_volume *V, int light, float *out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !out) { set_error("volume_light_grid_download: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (!V->d_lgrid) { set_error("volume_light_grid_download: the volume holds no light grid"); return GVT_HIP_ERR_INVALID; }
+  if (light < 0 || light >= GVT_HIP_VOLUME_MAX_LIGHTS || !((V->lg_usable >> light) & 1u)) {
+    set_error("volume_light_grid_download: light %d was not usable at the bake and has no grid (its transmittance is 1)", light);
+    return GVT_HIP_ERR_INVALID;
+  }
+  const size_t n_vert = (size_t)V->n[0] * V->n[1] * V->n[2];
+  const int plane = __builtin_popcount(V->lg_usable & ((1u << light) - 1u));
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(out, V->d_lgrid + n_vert * (size_t)plane, sizeof(float) * n_vert, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_light_grid_info(gvt_hip_volume *V, gvt_hip_volume_light_grid_state *out) {
+  if (!V || !out) { set_error("volume_light_grid_info: null argument"); return GVT_HIP_ERR_INVALID; }
+  gvt_hip_volume_light_grid_state I{};
+  I.present = V->d_lgrid ? 1u : 0u;
+  I.current = (V->d_lgrid && V->lg_current) ? 1u : 0u;
+  I.n_planes = V->d_lgrid ? V->lg_planes : 0;
+  I.bias = V->d_lgrid ? V->lg_bias : 0;
+  I.bytes = V->d_lgrid ? sizeof(float) * (uint64_t)V->n[0] * V->n[1] * V->n[2] * (uint64_t)V->lg_planes : 0;
+  *out = I;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_light_grid_release(gvt_hip_volume *V) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V) { set_error("volume_light_grid_release: null"); return GVT_HIP_ERR_INVALID; }
+  if (!V->d_lgrid) return 0;
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a frame in flight reads the planes)
+  hipFree(V->d_lgrid);
+  V->d_lgrid = nullptr;
+  V->lg_planes = 0; V->lg_bias = 0; V->lg_usable = 0; V->lg_current = false; V->lg_bake = 0;
+  return 0;
 }
 
 // ---- AMR volumes: the host side of volume_amr.inc (the contract: include/gvt_hip.h, "AMR volumes")
@@ -1969,6 +2250,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   if (n == 0) {
     if (V->sub.empty()) return 0;
     HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the tables)
+    V->lg_current = false; // (a light grid never covers subgrids, and the ranges change)
     amr_release(V);
     return amr_refresh_ranges(V);
   }
@@ -2008,6 +2290,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   if (!ok) return fail("the range kernel");
   hipFree(d_items); hipFree(d_out);
   // commit
+  V->lg_current = false;
   amr_release(V);
   V->d_amr_vox = d_vox; V->d_amr_mc = d_mc; V->d_amr_list = d_list; V->d_amr_desc = d_desc;
   V->sub.assign(grids, grids + n);

@@ -567,14 +567,22 @@ class VolumeTracer:
     shadows: frame() goes through gvt_hip_volume_frame_shadowed whatever fused says -- a crossing is lit only by the lights that reach it,
     a shadow ray per light marched inside the one launch; shadow_bias = the lattice index of a shadow ray's first sample (1 .. 64; 2 is
     a choice, not a measurement).  A frame that has surfaces and lights but cannot be fused is refused (GvtHipError): no loop renders
-    shadows.  Without surfaces or without lights the frame is fused_shaded's."""
+    shadows.  Without surfaces or without lights the frame is fused_shaded's.
+    fog_shadows (with shadows; alone it raises ValueError): frame() goes through gvt_hip_volume_frame_fog_shadowed -- lit fog samples are
+    shadowed too, by the transmittance towards each light interpolated from grids baked at the vertices (gvt_hip_volume_light_grid_bake;
+    fog_bias = the bake's bias).  frame() bakes on the first frame that has lit fog and a usable light, and again after update(),
+    set_surfaces() or set_lights() -- the cost is per change of data, table, surfaces or lights, not per frame; rebake() is explicit
+    (needed after a call on a single adapter, which the tracer does not see: the library then refuses the frame)."""
 
-    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2):
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2,
+                 fog_shadows=False, fog_bias=1):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
         from .scenes import instance_matrices, mat_translate_scale
 
+        if fog_shadows and not shadows:
+            raise ValueError("VolumeTracer: fog_shadows needs shadows=True (the fog-shadowed frame is the shadowed frame with one more change)")
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         self.camera = camera
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
@@ -596,6 +604,13 @@ class VolumeTracer:
         self.shadows = bool(shadows)
         self.shadow_bias = int(shadow_bias)
         self.shadow_stats = None  # shadows=True: gvt_hip_volume_shadow_stats of the last frame, as a dict
+        self.fog_shadows = bool(fog_shadows)
+        self.fog_bias = int(fog_bias)
+        self.light_bakes = 0
+        self.light_grid_stats = None  # fog_shadows=True: gvt_hip_volume_light_grid_stats of the last bake, as a dict
+        self._grid_stale = True  # nothing baked yet, or a setter / update of this tracer since the last bake
+        self._lit = False  # set_shading(True)?
+        self._usable_lights = 0  # lights of set_lights that cast shadow rays
         self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
 
     def frame(self, depth=None):
@@ -609,7 +624,17 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        if self.shadows:
+        if self.shadows and self.fog_shadows:
+            if self._grid_stale and self._lit and self._usable_lights:
+                self.rebake()
+            st = capi.VolumeFogShadowStats()
+            params = capi.VolumeShadowParams(0, self.shadow_bias)
+            capi.check(capi.load().gvt_hip_volume_frame_fog_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                                     C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
+                                                                     C.byref(params), C.byref(st)), "gvt_hip_volume_frame_fog_shadowed")
+            self.shadow_stats = st.as_dict()
+            calls = C.c_uint64(st.adapter_calls)
+        elif self.shadows:
             st = capi.VolumeShadowStats()
             params = capi.VolumeShadowParams(0, self.shadow_bias)
             capi.check(capi.load().gvt_hip_volume_frame_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
@@ -641,6 +666,21 @@ class VolumeTracer:
         self.calls = calls.value
         return self
 
+    def rebake(self):
+        """gvt_hip_volume_light_grid_bake over the tracer's bricks under its matrix: the light grids of the fog-shadowed frame."""
+        import ctypes as C
+
+        m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
+        minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
+        st = capi.VolumeLightGridStats()
+        params = capi.VolumeLightGridParams(0, self.fog_bias)
+        capi.check(capi.load().gvt_hip_volume_light_grid_bake(self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst), C.byref(params),
+                                                              C.byref(st)), "gvt_hip_volume_light_grid_bake")
+        self.light_grid_stats = st.as_dict()
+        self.light_bakes += 1
+        self._grid_stale = False
+        return self
+
     @staticmethod
     def _same_bricking(adapters, bricks):
         """Helper of update(), not part of the tracer's surface (static so that the check runs without a device): the bricks of another time
@@ -664,6 +704,7 @@ class VolumeTracer:
         """The next time step: the same bricking of the new data (scenes.split_volume with the same split, or one VolumeData), pushed into
         the bricks in place (gvt_hip_volume_update_samples).  Transfer function, surfaces, lights, top level, queues and framebuffer stay."""
         bricks = self._same_bricking(self.adapters, bricks)  # (all of them checked before the first one changes)
+        self._grid_stale = True
         for a, b in zip(self.adapters, bricks):
             a.update_samples(b.data)
             if getattr(b, "ghosts", None) is not None:  # the new step's face layers travel with its bricks
@@ -672,19 +713,29 @@ class VolumeTracer:
 
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
         """The volume's isosurfaces and slice planes (object space), on every brick."""
+        self._grid_stale = True
         for a in self.adapters:
             a.set_surfaces(isovalues, slices, opacity)
         return self
 
     def set_lights(self, lights, ka=0.4, kd=0.6):
+        self._grid_stale = True
         for a in self.adapters:
             a.set_lights(lights, ka, kd)
+        if isinstance(lights, np.ndarray) and lights.dtype.names:
+            pos = np.asarray(lights["position"], np.float32).reshape(-1, 3)
+        else:
+            pos = np.asarray([l[0] for l in lights], np.float32).reshape(-1, 3)
+        with np.errstate(all="ignore"):
+            ln = np.sqrt((pos[:, 0] * pos[:, 0] + pos[:, 1] * pos[:, 1]) + pos[:, 2] * pos[:, 2])
+        self._usable_lights = int(((ln > 0) & np.isfinite(ln)).sum())
         return self
 
     def set_shading(self, on=True):
         """Lit fog on every brick (HipVolumeAdapter.set_shading): the lights are set_lights'."""
         for a in self.adapters:
             a.set_shading(on)
+        self._lit = bool(on)
         return self
 
     def set_gradient(self, kind):
@@ -701,8 +752,14 @@ class VolumeTracer:
         frame, and where that frame was fused samples_marched / samples_gathered are ITS counts: the bricks' own did not move.
         fused_shaded=True adds features and, where the frame was fused, its crossings_rendered / samples_shaded likewise.
         shadows=True: the last frame's gvt_hip_volume_shadow_stats in fused_shaded's form (the camera rays' counters), and beside them
-        shadowed, shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched and shadow_samples_gathered."""
+        shadowed, shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched and shadow_samples_gathered.
+        fog_shadows=True adds fog_samples_shadowed of the last frame, light_bakes (bakes so far) and light_grid_rays / _bytes / _ms of the
+        last bake (0 before the first)."""
         out = self._brick_stats()
+        if self.fog_shadows:
+            g = self.light_grid_stats or {"rays": 0, "bytes": 0, "ms": 0.0}
+            out.update(light_bakes=self.light_bakes, light_grid_rays=g["rays"], light_grid_bytes=g["bytes"], light_grid_ms=g["ms"],
+                       fog_samples_shadowed=0 if self.shadow_stats is None else self.shadow_stats["fog_samples_shadowed"])
         if self.shadows and self.shadow_stats is not None:
             f = self.shadow_stats
             out.update({k: v for k, v in f.items() if k.startswith("shadow")})
@@ -909,11 +966,13 @@ class VolumeDomainTracer(DomainTracer):
     ray ends; the sum-reduce and the rows_only rectangles add it to zeros."""
 
     def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False,
-                 shadows=False):
+                 shadows=False, fog_shadows=False):
         from types import SimpleNamespace
 
         if shadows:  # (a shadow ray is marched to its end by the lane that needs it: a rank does not hold the foreign bricks it crosses)
             raise ValueError("VolumeDomainTracer: shadows need every brick of the volume on one device (VolumeTracer(shadows=True))")
+        if fog_shadows:  # (nor the bricks a vertex's ray crosses)
+            raise ValueError("VolumeDomainTracer: fog_shadows need every brick of the volume on one device (VolumeTracer(shadows=True, fog_shadows=True))")
 
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         if m is not None:  # (whatever backend marches the bricks: the next-brick rule is the same)
@@ -980,7 +1039,7 @@ class MixedTracer:
     takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel)."""
 
     def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
-                 shadows=False, shadow_bias=2):
+                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -994,9 +1053,9 @@ class MixedTracer:
         self.mesh = NativeTracer(self.scene, normal_mode)
         self.depth = DepthPlane(camera.width, camera.height)
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
-                                   fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias)
+                                   fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias)
         # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; shadows: the volume's surfaces shadowed by the
-        # volume -- the meshes cast no shadow into it)
+        # volume -- the meshes cast no shadow into it; fog_shadows: its lit fog too, from the baked light grids)
 
     def frame(self):
         self.mesh()

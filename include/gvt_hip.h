@@ -825,11 +825,17 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
  * DEVIATIONS.  (1) A surface is rendered at the far sample of its step, so a shadow ray towards a light on the camera's side would
  * cross its own sheet again; bias is the remedy: the first shadow sample is lattice index `bias`, and a first sample has no previous
  * sides, so nothing within `bias` steps casts a shadow.  (2) The geometry of a mixed frame casts no shadow into the volume: the depth
- * plane clips camera rays only.  (3) The fog is not shadowed.  (4) At samples > 1 deposits meet in arrival order, as ever.
+ * plane clips camera rays only.  (3) The fog is not shadowed (gvt_hip_volume_frame_fog_shadowed below shadows it).  (4) At samples > 1
+ * deposits meet in arrival order, as ever.  (5) A shadow ray that runs IN a face two bricks share -- its origin on the face, ws_j with a
+ * zero component along the face's axis -- has its samples owned by one of the two bricks (cell floor), while the next-brick rule enters
+ * a brick only if the ray leaves it strictly later than it left the last one; the two neighbours share their exit, so the owner is
+ * skipped after the non-owner and those samples are lost: A_s then depends on the bricking.  For crossing points this is a measure-zero
+ * case and the rule is kept; for rays from grid vertices under an axis-aligned light it is systematic, and the light grids below are
+ * defined and walked otherwise.
  * COUNTERS.  shadow_rays = (samples with at least one rendered crossing) x (lights with a usable ws_j); shadow_brick_visits,
  * shadow_crossings and shadow_samples_marched / _gathered are the fused frame's counters applied to the shadow rays.  They are kept
  * apart from the camera rays' counters, which equal those of the unshadowed frame whenever the two images agree.
- * OUT OF SCOPE.  Ambient occlusion; shadowed fog; geometry shadowing the volume or the volume attenuating mesh shadow rays; the Domain
+ * OUT OF SCOPE.  Ambient occlusion; shadowed fog (below); geometry shadowing the volume or the volume attenuating mesh shadow rays; the Domain
  * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR and CENTRAL frames; shadows in the per-brick loop. */
 typedef struct {
   uint32_t flags; /* must be 0 */
@@ -847,6 +853,87 @@ int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes,
                                   const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
                                   const gvt_hip_depth *depth /* may be NULL */, const gvt_hip_volume_shadow_params *params,
                                   gvt_hip_volume_shadow_stats *stats /* may be NULL */);
+
+/* ---- shadowed fog: light transmittance grids baked on the device (additive: the ABI revision stays 6, no entry point above changes) ----
+ * Marching a shadow ray per light at every lit fog sample would multiply the frame by hundreds.  Instead the transmittance towards each
+ * light is computed ONCE at every grid vertex (gvt_hip_volume_light_grid_bake), kept on the device beside the samples and interpolated
+ * at each lit sample (gvt_hip_volume_frame_fog_shadowed).  It is rebuilt when the data, the table, the surfaces or the lights change,
+ * not when the camera moves.
+ * THE GRID.  For a frame of bricks of ONE grid, every usable light j (ws_j finite and not zero, as above) has a float32 value G_j at
+ * every global vertex I = (I0, I1, I2):
+ *   p[a] = origin[a] + (float)I[a] * spacing[a]                      object space: one multiply, one add
+ *   wp   = (m[r]*p.x + m[4+r]*p.y) + (m[8+r]*p.z + m[12+r]*1)         m applied as a point
+ *   the ray: origin wp, direction ws_j, t_min = (float)(bias - 1) * dt, no colour, no opacity, no flags, no clip
+ *   A_s  = the opacity this ray deposits when it is marched over the WHOLE grid as ONE brick (offset 0, counts = global_counts) with
+ *          the frame's surfaces and shading NONE
+ *   G_j(I) = 1 - A_s
+ * For every ray on which the walk of "shadowed surfaces" is bricking-invariant this is that section's T_j; for a ray in a brick face
+ * (DEVIATIONS (5) there) it pins the value down.  The bake gives these bits for every bricking: its walk is driven by sample ownership.
+ * The lattice range is taken once from the global vertex box; the next visit goes to the brick that owns the global cell of the first
+ * lattice index after t_min; a visit ends by the contiguity rule; the ray ends when that cell lies outside the grid (the one brick's
+ * rules: before its first sample the next index is tried, after it the ray is over) or when A >= GVT_HIP_VOLUME_OPAQUE_A.  The side
+ * mask is carried from visit to visit.  A brick stores G_j at its own vertices, the shared layers twice with the same bits.  An
+ * unusable light has no grid; its transmittance is 1.
+ * THE BAKE.  Eligibility is the shaded fused frame's "bricks of one grid" comparison (allow = both bits) and, on top of it: m equal as
+ * bits on every brick; surfaces and lights equal on every brick whatever the shading; at least one usable light; no subgrids; no
+ * CENTRAL kind on a brick of a frame with an isovalue; the bricks' owned cells tile the global grid exactly (disjoint, and their sum is
+ * the global cell count); at most 2^32 - 1 (vertex, light) pairs; flags == 0; bias 1 .. 64; no null pointer.  Anything else:
+ * GVT_HIP_ERR_INVALID with a message that names the clause, the old grids kept.  Planes that cannot be allocated: GVT_HIP_ERR_CAPACITY;
+ * a HIP call that fails: GVT_HIP_ERR_DEVICE; in both cases every brick keeps the grid it had (all planes are allocated and filled
+ * before the first brick changes).  The call waits for the launch.
+ * CURRENT.  A frame's grids are current if ONE bake covered exactly these volumes in this order with the same m and minv bits, and since
+ * then no brick has had _update_samples[_typed], _set_transfer, _set_surfaces, _set_lights or _set_subgrids.  _set_shading and
+ * _set_gradient do not make a grid stale: shadow rays march with shading NONE.
+ * THE FRAME.  gvt_hip_volume_frame_fog_shadowed is gvt_hip_volume_frame_shadowed -- same arguments, same refusals, crossings lit
+ * through exact in-kernel shadow rays with the bias of its params -- with one more change.  In a lit fog sample that is shaded
+ * (tc.w > 0, 0 < len < +Inf) the light loop becomes
+ *     Tg = trilinear interpolation of G_j at the cell's eight vertices (the sample's fractions; the value's nesting: x, then y, then z)
+ *     ndl_s = ndl * Tg;   sum[a] = sum[a] + lcol[j][a] * ndl_s;
+ * with Tg = 1 and nothing read for an unusable light.  G is read only inside that branch, so skipping stays exact against
+ * GVT_HIP_VOLUME_NO_SKIP and samples_shaded does not change; A never depends on G.  The frame takes the depth plane as its siblings do.
+ * INERT.  No light, or neither surfaces nor effective lit shading: gvt_hip_volume_frame_fused_shaded with both allow bits.  Surfaces and
+ * lights but no effective lit shading: gvt_hip_volume_frame_shadowed with the same bias in every bit; no grid is needed.
+ * REFUSED (GVT_HIP_ERR_INVALID, the message names the clause, nothing changed, the framebuffer not cleared): everything
+ * gvt_hip_volume_frame_shadowed refuses -- with lit fog alone a frame that is not eligible for the fused kernel is refused too, no loop
+ * shadows fog -- and a frame with effective lit shading and a usable light whose bricks do not all hold a CURRENT grid ("light grid").
+ * DEVIATIONS.  (1) Transmittance is interpolated from vertices: a shadow's edge is one cell soft, and an occluder thinner than a cell
+ * leaks.  (2) Crossings keep exact rays, so the two kinds of shadow meet at slightly different softness.  (3) Meshes cast no shadow
+ * into the volume.  (4) The grid's bias is the bake's, the crossings' bias the frame's.
+ * COUNTERS.  Bake: rays = (vertices summed over the bricks) x (usable lights); samples_marched / _gathered and crossings as the fused
+ * frames count them; bytes = the planes' size; ms = the launch's event time.  Frame: gvt_hip_volume_shadow_stats, and
+ * fog_samples_shadowed = samples_shaded when the fog kernel ran (else 0).
+ * A volume that holds a grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees the grid.
+ * OUT OF SCOPE.  A coarser or compressed grid; pruning vertices no sample reads; ambient occlusion; meshes shadowing the volume; the
+ * Domain scheduler; AMR and CENTRAL frames; moving the crossings' shadow rays onto the grid. */
+typedef struct {
+  uint32_t flags; /* must be 0 */
+  int32_t bias;   /* 1 .. 64, lattice steps */
+} gvt_hip_volume_light_grid_params;
+typedef struct {
+  uint64_t rays, samples_marched, samples_gathered, crossings, bytes;
+  float ms;
+  uint32_t pad;
+} gvt_hip_volume_light_grid_stats;
+typedef struct {
+  uint32_t present, current; /* a grid is held | ... and no call has made it stale since its bake */
+  int32_t n_planes, bias;    /* usable lights at the bake | the bake's bias */
+  uint64_t bytes;
+} gvt_hip_volume_light_grid_state;
+typedef struct {
+  gvt_hip_volume_shadow_stats frame; /* the shadowed frame's counters, same meaning */
+  uint64_t fog_samples_shadowed;
+} gvt_hip_volume_fog_shadow_stats;
+int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                   const gvt_hip_volume_light_grid_params *params, gvt_hip_volume_light_grid_stats *stats /* may be NULL */);
+/* out: host memory, counts[0] * counts[1] * counts[2] floats at i + nx * (j + ny * k).  No grid, or a light that was unusable at the
+ * bake: GVT_HIP_ERR_INVALID.  A stale grid can still be downloaded. */
+int gvt_hip_volume_light_grid_download(gvt_hip_volume *, int light, float *out);
+int gvt_hip_volume_light_grid_info(gvt_hip_volume *, gvt_hip_volume_light_grid_state *out);
+int gvt_hip_volume_light_grid_release(gvt_hip_volume *); /* frees the planes; a volume without a grid: 0 */
+int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                      const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
+                                      const gvt_hip_depth *depth /* may be NULL */, const gvt_hip_volume_shadow_params *params,
+                                      gvt_hip_volume_fog_shadow_stats *stats /* may be NULL */);
 
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);

@@ -45,6 +45,8 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              the same protocol: --surfaces = the "thin" frame with the two isovalues the field reaches (opacity
                                              0.3, one light), --shade = lit fog by one light under every --tf table; with each the crossings
                                              and the samples shaded per frame, and the two framebuffers compared bitwise after every pair
+  python tools/volume_bench.py --fused --shade --fog-shadows  shadowed fog (gvt_hip_volume_frame_fog_shadowed): the lit fused frame, the same
+                                                        frame with the fog shadowed from the light grids, and the bake
   python tools/volume_bench.py --fused --surfaces --shadows   shadowed surfaces (gvt_hip_volume_frame_shadowed): --surfaces' frame shadowed
                                              against the same frame through the shaded fused kernel, alternating frame by frame on ONE
                                              tracer; with each the shadow rays and the shadow samples per frame, so that the cost per shadow
@@ -258,6 +260,57 @@ def run_shadows(n, split, steps, warmup, rate, vol, dtype="f32", first=None, bia
            "shadow_samples": int(st["shadow_samples_marched"]), "shadow_samples_interpolated": int(st["shadow_samples_gathered"]),
            "plain_ns_per_sample": round(float(np.median(plain)) * 1e6 / max(st["samples_marched"], 1), 4),
            "extra_ns_per_shadow_sample": round(extra_ms * 1e6 / max(st["shadow_samples_marched"], 1), 4),
+           "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())}
+    return row, fb
+
+
+def run_fog_shadows(n, split, steps, warmup, rate, kind, vol, dtype="f32", first=None, bias=1):
+    """--fused --shade's lit frame (one light, gvt_hip_volume_frame_fused_shaded) against the same frame with the fog shadowed from the
+    baked light grids (gvt_hip_volume_frame_fog_shadowed), alternating frame by frame on one tracer; the bake timed on its own (the
+    launch's event time: a cost per change of data, table, surfaces or lights, not per frame); and, as a yardstick, the loop's lit frame
+    with the CELL and with the CENTRAL gradient on a second tracer of the same bricks.  Returns (row, the fog-shadowed framebuffer)."""
+    bricks = vol if split == (1, 1, 1) else scenes.split_volume(vol, *split, ghosts=True)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=True, shadows=True, fog_shadows=True,
+                      fog_bias=bias)
+    tr.set_lights(SHADE_LIGHTS[:1]).set_shading(True)
+    bake = []
+    for i in range(warmup + steps):
+        tr.rebake()
+        bake.append(tr.light_grid_stats["ms"])
+    bake = bake[warmup:]
+    g = tr.light_grid_stats
+    plain, fog = [], []
+
+    def frame(flag):
+        tr.shadows = tr.fog_shadows = flag
+        tr.frame()
+
+    for i in range(warmup + steps):
+        plain.append(timed(lambda: frame(False)))
+        ps = tr.stats()
+        fog.append(timed(lambda: frame(True)))
+    plain, fog = plain[warmup:], fog[warmup:]
+    st = tr.stats()
+    fb = tr.framebuffer(False).copy()
+    ref = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32").set_lights(SHADE_LIGHTS[:1]).set_shading(True)
+    grad = {"cell": [], "central": []}
+    for i in range(warmup + steps):
+        for k in grad:
+            ref.set_gradient(k)
+            grad[k].append(timed(ref.frame))
+    grad = {k: v[warmup:] for k, v in grad.items()}
+    row = {"mode": "fused_fog_shadows", "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "bias": bias,
+           "bake_ms_median": med(bake), "bake_ms_min": round(min(bake), 3), "bake_ms_max": round(max(bake), 3), "bake_rays": int(g["rays"]),
+           "bake_mrays_per_s": round(g["rays"] / float(np.median(bake)) / 1e3, 1), "bake_samples": int(g["samples_marched"]),
+           "bake_samples_interpolated": int(g["samples_gathered"]), "grid_bytes": int(g["bytes"]), "light_bakes": int(st["light_bakes"]),
+           "plain_ms_median": med(plain), "plain_ms_min": round(min(plain), 3), "plain_ms_max": round(max(plain), 3),
+           "fog_ms_median": med(fog), "fog_ms_min": round(min(fog), 3), "fog_ms_max": round(max(fog), 3),
+           "fog_over_plain": round(float(np.median(fog)) / float(np.median(plain)), 4),
+           "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "samples_shaded": int(st["samples_shaded"]),
+           "fog_samples_shadowed": int(st["fog_samples_shadowed"]),
+           "camera_counters_same": bool(all(st[k] == ps[k] for k in ("samples_marched", "samples_gathered", "samples_shaded", "brick_visits", "rays_deposited"))),
+           "loop_cell_ms_median": med(grad["cell"]), "loop_central_ms_median": med(grad["central"]),
+           "central_over_cell": round(float(np.median(grad["central"])) / float(np.median(grad["cell"])), 4),
            "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())}
     return row, fb
 
@@ -580,6 +633,7 @@ def main():
     ap.add_argument("--bricks", type=int, nargs="+", choices=sorted(FUSED_SPLITS), default=sorted(FUSED_SPLITS), help="with --fused: the brickings")
     ap.add_argument("--shadows", action="store_true", help="with --fused --surfaces: the shadowed frame against the shaded fused frame")
     ap.add_argument("--bias", type=int, default=2, help="with --shadows: the first shadow sample's lattice index")
+    ap.add_argument("--fog-shadows", action="store_true", help="with --fused --shade: the lit fused frame against the fog-shadowed frame, and the bake of its light grids")
     a = ap.parse_args()
     if a.update or a.domains:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
@@ -623,6 +677,19 @@ def main():
             out["runs"].append(r)
             print(json.dumps(r), flush=True)
     if a.shadows:
+        a.sizes = []
+    if a.fog_shadows and not (a.fused and a.shade):
+        ap.error("--fog-shadows goes with --fused --shade")
+    for n in a.sizes if a.fog_shadows else ():
+        vol = noise(n, a.dtype)
+        for kind in a.tf:
+            first = None
+            for nb in a.bricks:
+                r, fb = run_fog_shadows(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, a.dtype, first)
+                first = fb if first is None else first
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    if a.fog_shadows:
         a.sizes = []
     for n in a.sizes if a.fused else ():
         vol = noise(n, a.dtype)
