@@ -400,19 +400,24 @@ class DepthPlane:
     def render(self, scene_or_backend, cam=None):
         """gvt_hip_depth_render: the nearest hit of every camera ray over all instances.  A scheduler.HipBackend brings its scene and its
         mesh adapters; for a scenes.Scene the adapters are made here and kept for the next call with the same scene.  cam: the scene's."""
-        B = scene_or_backend
-        if not hasattr(B, "adapter_cache"):
-            if self._backend is None or self._backend[0] is not B:
-                self._backend = (B, {mi: HipMeshAdapter(B.meshes[mi]) for mi in sorted(set(B.inst_mesh))})
-            scene, adapters = B, [self._backend[1][mi] for mi in B.inst_mesh]
-        else:
-            scene, adapters = B.scene, [B.adapter(i) for i in range(B.scene.n_inst)]
+        scene, adapters, self._backend = scene_instances(scene_or_backend, self._backend)
         cam = cam or scene.camera
         pod = camera_pod(cam)
         meshes = (C.c_void_p * max(1, scene.n_inst))(*[a.h for a in adapters])
         m, minv = capi.f32(scene.m), capi.f32(scene.minv)
         capi.check(self.lib.gvt_hip_depth_render(self.h, meshes, capi.ptr(m), capi.ptr(minv), scene.n_inst, C.byref(pod)), "gvt_hip_depth_render")
         return self
+
+
+def scene_instances(scene_or_backend, kept=None):
+    """(scene, the mesh adapter of every instance, what to keep) of a scheduler.HipBackend, which brings its scene and its adapters, or
+    of a scenes.Scene, whose adapters are made here; kept: the third result of the last call, so that the same scene's are used again."""
+    B = scene_or_backend
+    if hasattr(B, "adapter_cache"):
+        return B.scene, [B.adapter(i) for i in range(B.scene.n_inst)], kept
+    if kept is None or kept[0] is not B:
+        kept = (B, {mi: HipMeshAdapter(B.meshes[mi]) for mi in sorted(set(B.inst_mesh))})
+    return B, [kept[1][mi] for mi in B.inst_mesh], kept
 
 
 def camera_generate(q, cam, tile=0):
@@ -701,6 +706,22 @@ class HipVolumeAdapter:
 
     def light_grid_release(self):
         capi.check(self.lib.gvt_hip_volume_light_grid_release(self.h), "gvt_hip_volume_light_grid_release")
+
+    def occluder_grid_info(self):
+        """present, current, n_planes, bytes of the brick's occluder grid (gvt_hip_volume_occluder_grid_info)."""
+        i = capi.VolumeOccluderState()
+        capi.check(self.lib.gvt_hip_volume_occluder_grid_info(self.h, C.byref(i)), "gvt_hip_volume_occluder_grid_info")
+        return i.as_dict()
+
+    def occluder_grid(self, j):
+        """The baked occlusion towards light j at the brick's vertices, (nz, ny, nx) uint8, 0 = a mesh stands between the vertex and the
+        light (gvt_hip_volume_occluder_grid_download); a light that was unusable at the bake, or no grid: GvtHipError."""
+        out = np.zeros(tuple(int(c) for c in self.counts[::-1]), np.uint8)
+        capi.check(self.lib.gvt_hip_volume_occluder_grid_download(self.h, int(j), capi.ptr(out)), "gvt_hip_volume_occluder_grid_download")
+        return out
+
+    def occluder_grid_release(self):
+        capi.check(self.lib.gvt_hip_volume_occluder_grid_release(self.h), "gvt_hip_volume_occluder_grid_release")
 
     def march_queue(self, queue, minv, may_clip=False):
         """gvt_hip_volume_march_queue: Adapter::trace on a device-resident RayQueue, in place and without a host wait; the rays keep

@@ -46,6 +46,8 @@ SYMBOLS = [
     "gvt_hip_volume_frame_shadowed",
     "gvt_hip_volume_light_grid_bake", "gvt_hip_volume_light_grid_download", "gvt_hip_volume_light_grid_info", "gvt_hip_volume_light_grid_release",
     "gvt_hip_volume_frame_fog_shadowed",
+    "gvt_hip_volume_occluder_grid_bake", "gvt_hip_volume_occluder_grid_download", "gvt_hip_volume_occluder_grid_info", "gvt_hip_volume_occluder_grid_release",
+    "gvt_hip_volume_frame_mesh_shadowed",
 ]
 
 
@@ -159,6 +161,37 @@ class VolumeFogShadowStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class VolumeOccluderParams(C.Structure):
+    """gvt_hip_volume_occluder_params: flags must be 0."""
+    _fields_ = [("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class VolumeOccluderStats(C.Structure):
+    """gvt_hip_volume_occluder_stats: what gvt_hip_volume_occluder_grid_bake reports of one bake."""
+    _fields_ = [("rays", C.c_uint64), ("rays_blocked", C.c_uint64), ("any_hit_launches", C.c_uint64), ("bytes", C.c_uint64), ("ms", C.c_float), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class VolumeOccluderState(C.Structure):
+    """gvt_hip_volume_occluder_state: what gvt_hip_volume_occluder_grid_info reports of one volume."""
+    _fields_ = [("present", C.c_uint32), ("current", C.c_uint32), ("n_planes", C.c_int32), ("pad", C.c_int32), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class VolumeMeshShadowStats(C.Structure):
+    """gvt_hip_volume_mesh_shadow_stats: the fog-shadowed frame's counters, then whether the mesh-shadowed kernel ran."""
+    _fields_ = [("fog", VolumeFogShadowStats), ("mesh_shadowed", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        out = self.fog.as_dict()
+        out["mesh_shadowed"] = self.mesh_shadowed
+        return out
+
+
 FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
@@ -240,6 +273,11 @@ def load():
         lib.gvt_hip_volume_light_grid_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.gvt_hip_volume_light_grid_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_light_grid_release.argtypes = [C.c_void_p]
+        lib.gvt_hip_volume_frame_mesh_shadowed.argtypes = lib.gvt_hip_volume_frame_shadowed.argtypes
+        lib.gvt_hip_volume_occluder_grid_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_occluder_grid_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.gvt_hip_volume_occluder_grid_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_occluder_grid_release.argtypes = [C.c_void_p]
         lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))

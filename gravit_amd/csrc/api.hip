@@ -240,7 +240,7 @@ extern "C" int gvt_hip_stats_reset(void) {
 namespace {
 struct KnobDef { const char *name; int Knobs::*field; int lo, hi; bool shipped; };
 const KnobDef g_knobs[] = {
-  // shipped (29)
+  // shipped (30)
   { "skip_known", &Knobs::skip_known, 0, 1, true },           { "frame_timing", &Knobs::frame_timing, 0, 1, true },
   { "term_sink", &Knobs::term_sink, 0, 1, true },
   { "sort_rays", &Knobs::sort_rays, 0, 1, true },             { "leaf_max", &Knobs::leaf_max, 1, 4, true },
@@ -259,6 +259,7 @@ const KnobDef g_knobs[] = {
   { "inline_kb", &Knobs::inline_kb, 0, 1024, true },          { "comm_cus", &Knobs::comm_cus, 0, 128, true },
   { "comm_stream", &Knobs::comm_stream, 0, 1, true },         { "spec_ticks", &Knobs::spec_ticks, 0, 1, true },
   { "finish_clusters", &Knobs::finish_clusters, 0, 1, true }, { "hop_local", &Knobs::hop_local, 0, 3, true },
+  { "occluder_chunk", &Knobs::occluder_chunk, 0, 1 << 24, true },
   // experiments build only: a tuned constant, or an alternative arm that was measured and lost
   { "blocks_per_cu", &Knobs::blocks_per_cu, 1, 8, false },    { "blocks_per_cu_closest", &Knobs::blocks_per_cu_closest, 0, 8, false },
   { "refill_min", &Knobs::refill_min, 1, 64, false },         { "inner_min", &Knobs::inner_min, 1, 64, false },

@@ -50,6 +50,8 @@ enum ScratchSlot {
   SCR_VOL_KEEP,    // the keep mask of gvt_hip_volume_camera_filter on the device (volume.hip)
   SCR_VOL_BRICKS, SCR_VOL_FUSED, // the fused frame's per-brick records and its counter words, six or with shadows eleven (volume.hip volume_frame_fused)
   SCR_VOL_GRIDS,   // the light grids' per-brick table beside SCR_VOL_BRICKS: the bake's work list and planes, the fog-shadowed frame's planes (volume.hip)
+  SCR_VOL_OCC_RAYS, SCR_VOL_OCC, // the occluder bake: a chunk's p0 / p1 ray planes | its uint8 O words (volume.hip; the chunk's any-hit flags are SCR_GENERAL's, its
+                   // per-brick table SCR_VOL_GRIDS', its counter word SCR_VOL_FUSED's)
   SCRATCH_COUNT
 };
 struct Knobs {
@@ -126,6 +128,7 @@ struct Knobs {
   int top_ordered = 1;   // shuffle: order-preserving, deterministic slots (<= 64 destinations) instead of arrival-order atomics
   int top_lds = 1;       // shuffle kernels: aggregate destination counters in LDS per 1024-thread block
   int leaf_max = 2;      // triangles per leaf at mesh build (1..4): closest hit on the 10 M soup 0.51 ms (2) vs 0.57 ms (4)
+  int occluder_chunk = 0; // tests: (vertex, light) pairs per chunk of gvt_hip_volume_occluder_grid_bake, so that small grids span several chunks (0: VOL_OCC_CHUNK)
 };
 
 struct Ctx : Knobs {

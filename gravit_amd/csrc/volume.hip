@@ -24,6 +24,10 @@
 //   gvt_hip_volume_light_grid_bake / k_volume_bake_light   the transmittance towards every light at every grid vertex, kept beside the samples
 //                                           (volume_light_grid.inc), and gvt_hip_volume_frame_fog_shadowed / k_volume_march_fused_fog, the
 //                                           shadowed frame whose lit fog samples interpolate it (volume_fused_fog.inc)
+//   gvt_hip_volume_occluder_grid_bake / k_occluder_rays, _fold, _pack   whether a mesh stands between every grid vertex and every light, from the
+//                                           any-hit traversal of trace.hip, as uint8 planes beside the samples (volume_occluder_grid.inc), and
+//                                           gvt_hip_volume_frame_mesh_shadowed / k_volume_march_fused_mesh, the fog-shadowed frame in which
+//                                           every transmittance is multiplied by their interpolant (volume_fused_mesh.inc)
 //   gvt_hip_volume_march_queue / _camera_filter   the Domain scheduler's steps over bricks spread over ranks (algorithm/DomainTracer.h:148-326): the march
 //                                           on a device queue, and the camera step with shuffleDropRays' keep mask (k_vol_classify<MASK>); the
 //                                           exchange's batched wire conversions are beside k_planes_to_aos (convert.inc, trace.hip)
@@ -92,6 +96,16 @@ struct gvt_hip_volume {
   uint64_t lg_bake = 0;
   size_t lg_index = 0, lg_count = 0;
   float lg_m[16] = {}, lg_minv[16] = {};
+  // the occluder grids of the mesh-shadowed frame (gvt_hip_volume_occluder_grid_bake; volume_occluder_grid.inc): og_planes uint8 planes of
+  // the brick's vertices, one per usable light in the order of their bits (1: no mesh between the vertex and the light, 0: one).
+  // og_current: neither the lights nor the subgrids were set since the bake; og_bake / og_index / og_count / og_m / og_minv: as lg_*
+  uint8_t *d_occ = nullptr;
+  int og_planes = 0;
+  unsigned og_usable = 0;
+  bool og_current = false;
+  uint64_t og_bake = 0;
+  size_t og_index = 0, og_count = 0;
+  float og_m[16] = {}, og_minv[16] = {};
 };
 
 namespace {
@@ -863,6 +877,8 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 #include "volume_fused_shadow.inc" // k_volume_march_fused_shadow
 #include "volume_light_grid.inc" // k_volume_bake_light
 #include "volume_fused_fog.inc" // k_volume_march_fused_fog
+#include "volume_occluder_grid.inc" // k_occluder_rays, k_occluder_fold, k_occluder_pack
+#include "volume_fused_mesh.inc" // k_volume_march_fused_mesh
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
@@ -1246,7 +1262,7 @@ extern "C" int gvt_hip_volume_get_voxel_type(gvt_hip_volume *V, int *type_out, s
 extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
-  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost); hipFree(V->d_lgrid);
+  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost); hipFree(V->d_lgrid); hipFree(V->d_occ);
   hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
   delete V;
 }
@@ -1357,6 +1373,7 @@ extern "C" int gvt_hip_volume_set_lights(gvt_hip_volume *V, const float *positio
     if (!std::isfinite(positions[i]) || !std::isfinite(colours[i])) { set_error("volume_set_lights: light %d is not finite", i / 3); return GVT_HIP_ERR_INVALID; }
   V->n_lights = n; V->ka = ka; V->kd = kd;
   V->lg_current = false; // (a light grid holds one plane per light of the old list)
+  V->og_current = false; // (... and so does an occluder grid)
   for (int j = 0; j < n; j++)
     for (int a = 0; a < 3; a++) { V->lpos[j][a] = positions[3 * j + a]; V->lcol[j][a] = colours[3 * j + a]; }
   return 0;
@@ -1696,14 +1713,35 @@ void launch_fused_fog(uint32_t features, const gvt_hip_volume *V0, const gvt_hip
   else k_volume_march_fused_fog<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
 }
 
+// the mesh-shadowed kernels' instantiation: clipped or not, lit fog or not, with surfaces or -- the lean kernel, lit fog implied -- without
+template <typename VT, typename... Args>
+void launch_fused_mesh(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
+                       const FusedBrick *d_bricks, const MeshBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
+  const float *d_t = depth ? depth->d_t : nullptr;
+  const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
+  if (!(features & GVT_HIP_FUSED_SURFACES)) {
+    const LightDev L = light_dev(V0, M);
+    if (depth) k_volume_march_fused_mesh_lean<VT, true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else k_volume_march_fused_mesh_lean<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+    return;
+  }
+  const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
+  if (depth && lit) k_volume_march_fused_mesh<VT, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  else if (depth) k_volume_march_fused_mesh<VT, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  else if (lit) k_volume_march_fused_mesh<VT, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  else k_volume_march_fused_mesh<VT, false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+}
+
 // the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
 // features: fused_eligible's -- 0 launches k_volume_march_fused, anything else the shaded kernel with the table of volumes[0]
 // shadow (gvt_hip_volume_frame_shadowed; features has SURFACES then): the launch is k_volume_march_fused_shadow's, and shadow_out gets
 // its five further counter words, read back in the same wait.  fog (gvt_hip_volume_frame_fog_shadowed; shadow is given and features has
-// LIT): the launch is k_volume_march_fused_fog's, and the bricks' light grid planes travel in a second table beside the records
+// LIT): the launch is k_volume_march_fused_fog's, and the bricks' light grid planes travel in a second table beside the records.  mesh
+// (gvt_hip_volume_frame_mesh_shadowed; shadow is given): the launch is k_volume_march_fused_mesh's, and that table holds the occluder
+// grid's planes too (the light grid's only where fog is set as well)
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
                        gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S, const ShadowDev *shadow = nullptr,
-                       uint64_t *shadow_out = nullptr, bool fog = false) {
+                       uint64_t *shadow_out = nullptr, bool fog = false, bool mesh = false) {
   Ctx &C = gctx();
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;
@@ -1720,25 +1758,31 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
-  FogBrick *d_grids = fog ? (FogBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(FogBrick) * n_inst) : nullptr;
-  if (fog && !d_grids) return GVT_HIP_ERR_DEVICE;
-  static_assert((sizeof(FusedBrick) + sizeof(FogBrick)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table and the grids' fit the staging block");
+  static_assert(sizeof(MeshBrick) >= sizeof(FogBrick), "one allocation serves either table");
+  void *d_planes = (fog || mesh) ? scratch_get(SCR_VOL_GRIDS, sizeof(MeshBrick) * n_inst) : nullptr;
+  if ((fog || mesh) && !d_planes) return GVT_HIP_ERR_DEVICE;
+  FogBrick *d_grids = (FogBrick *)d_planes;
+  MeshBrick *d_mgrids = (MeshBrick *)d_planes;
+  static_assert((sizeof(FusedBrick) + sizeof(MeshBrick)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table and the grids' fit the staging block");
   void *stage = nullptr;
   if ((rc = pinned_stage_begin(&stage))) return rc;
   FusedBrick *h = (FusedBrick *)stage;
   FogBrick *hg = (FogBrick *)(h + VOL_DEST_MAX);
+  MeshBrick *hm = (MeshBrick *)(h + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     FusedBrick R{};
     R.vox = B->d_vox;
     R.mc = (features & GVT_HIP_FUSED_SURFACES) ? (const uint8_t *)B->d_cells : B->d_mc; // (the surface visit reads the per-cell words, never the skip bytes)
-    if (fog) hg[i].grid = B->d_lgrid;
+    if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
+    else if (fog) hg[i].grid = B->d_lgrid;
     R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
     for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
     h[i] = R;
   }
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
-  if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if (mesh) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  else if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if ((rc = pinned_stage_end())) return rc;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
   HIPCHK(hipMemsetAsync(d_stats, 0, n_words * sizeof(unsigned long long), C.stream));
@@ -1750,6 +1794,11 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if (n)
     with_voxel_type(volumes[0]->vtype, [&](auto t) {
       using VT = decltype(t);
+      if (shadow && mesh) {
+        launch_fused_mesh<VT>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
+                              work, d_stats);
+        return;
+      }
       if (shadow && fog) {
         launch_fused_fog<VT>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_grids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work,
                              d_stats);
@@ -1853,10 +1902,25 @@ bool light_grids_current(gvt_hip_volume *const *volumes, const float *m, const f
   return true;
 }
 
-// both shadowed frames.  fog: gvt_hip_volume_frame_fog_shadowed (fn: the entry point's name in the error texts)
+// Do these bricks, in this order and under these matrices, all hold an occluder grid of ONE bake that nothing has made stale since?
+bool occluder_grids_current(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, unsigned usable, const char **why) {
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    if (!B->d_occ) { *why = "a brick holds no occluder grid (gvt_hip_volume_occluder_grid_bake)"; return false; }
+    if (!B->og_current) { *why = "a brick's occluder grid is stale: its lights or subgrids were set after the bake"; return false; }
+    if (B->og_bake != volumes[0]->og_bake || B->og_index != i || B->og_count != n_inst) { *why = "the occluder grids were not baked over exactly these bricks in this order"; return false; }
+    if (!same_bits(B->og_m, m + 16 * i, sizeof(B->og_m)) || !same_bits(B->og_minv, minv + 16 * i, sizeof(B->og_minv))) { *why = "the occluder grids were baked under another matrix"; return false; }
+    if (B->og_usable != usable || B->og_planes != __builtin_popcount(usable)) { *why = "the occluder grids were baked for other lights"; return false; }
+  }
+  return true;
+}
+
+// the shadowed frames.  fog: gvt_hip_volume_frame_fog_shadowed; mesh (with fog): gvt_hip_volume_frame_mesh_shadowed, *mesh_ran = did its
+// kernel run? (fn: the entry point's name in the error texts)
 int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
                                const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
-                               const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats &O, uint64_t &fog_samples) {
+                               const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats &O, uint64_t &fog_samples, bool mesh = false,
+                               bool *mesh_ran = nullptr) {
   int rc;
   if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
   if (!params) { set_error("%s: null params", fn); return GVT_HIP_ERR_INVALID; }
@@ -1888,10 +1952,17 @@ int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip
       set_error("%s: the frame has lit fog but its bricks do not all hold a current light grid: %s", fn, why);
       return GVT_HIP_ERR_INVALID;
     }
+    // (the mesh frame without a usable light is the fog-shadowed frame in every respect: no occluder grid is needed)
+    const bool with_mesh = mesh && H.usable;
+    if (with_mesh && !occluder_grids_current(volumes, m, minv, n_inst, H.usable, &why)) {
+      set_error("%s: the frame has surfaces or lit fog but its bricks do not all hold a current occluder grid: %s", fn, why);
+      return GVT_HIP_ERR_INVALID;
+    }
     if (fog && (features & GVT_HIP_FUSED_LIT) && !(features & GVT_HIP_FUSED_SURFACES) && !H.usable) // (lit fog alone and no light casts a ray: the shaded fused frame)
       rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S);
     else
-      rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh, fog_ran);
+      rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh, fog_ran, with_mesh);
+    if (!rc && mesh_ran) *mesh_ran = with_mesh;
   }
   if (rc) return rc;
   O = gvt_hip_volume_shadow_stats{};
@@ -1930,50 +2001,75 @@ extern "C" int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *T, gvt_hip_volume 
   return rc;
 }
 
-extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
-                                              const gvt_hip_volume_light_grid_params *params, gvt_hip_volume_light_grid_stats *stats) {
-  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
-  if (!volumes || !m || !minv || !params) { set_error("volume_light_grid_bake: null argument"); return GVT_HIP_ERR_INVALID; }
-  if (n_inst < 1 || n_inst > VOL_DEST_MAX) { set_error("volume_light_grid_bake: %zu bricks, 1 to %d are allowed", n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
+namespace {
+
+// What both bakes (the light grids' and the occluder grids') ask of their arguments and of their bricks.  fn: the entry point's name in the
+// error texts.  bake_args: no null pointer, 1 to VOL_DEST_MAX bricks that have a table, flags == 0
+int bake_args(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const uint32_t *flags) {
+  if (!volumes || !m || !minv || !flags) { set_error("%s: null argument", fn); return GVT_HIP_ERR_INVALID; }
+  if (n_inst < 1 || n_inst > VOL_DEST_MAX) { set_error("%s: %zu bricks, 1 to %d are allowed", fn, n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
   for (size_t i = 0; i < n_inst; i++)
-    if (!volumes[i] || !volumes[i]->has_tf) { set_error("volume_light_grid_bake: brick %zu is null or has no transfer function", i); return GVT_HIP_ERR_INVALID; }
-  if (params->flags) { set_error("volume_light_grid_bake: unknown flag bits %u", params->flags); return GVT_HIP_ERR_INVALID; }
-  if (params->bias < 1 || params->bias > 64) { set_error("volume_light_grid_bake: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
+    if (!volumes[i] || !volumes[i]->has_tf) { set_error("%s: brick %zu is null or has no transfer function", fn, i); return GVT_HIP_ERR_INVALID; }
+  if (*flags) { set_error("%s: unknown flag bits %u", fn, *flags); return GVT_HIP_ERR_INVALID; }
+  return 0;
+}
+
+// ... bake_bricks: bricks of one grid that tile it, under one matrix, with equal surfaces and lights, at least one usable light, no
+// subgrids, the CENTRAL clause, at most 2^32 - 1 (vertex, light) pairs.  verts: the vertices summed over the bricks; usable: the lights' bits
+int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, uint64_t &verts, unsigned &usable) {
   uint32_t features = 0;
   const char *why = "";
   if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, features, &why)) {
-    set_error("volume_light_grid_bake: the bricks are not eligible for the fused kernels: %s", why);
+    set_error("%s: the bricks are not eligible for the fused kernels: %s", fn, why);
     return GVT_HIP_ERR_INVALID;
   }
   const gvt_hip_volume *A = volumes[0];
-  uint64_t cells = 0, verts = 0;
+  uint64_t cells = 0;
+  verts = 0;
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
-    if (!same_bits(m + 16 * i, m, 16 * sizeof(float))) { set_error("volume_light_grid_bake: bricks under different matrices"); return GVT_HIP_ERR_INVALID; }
-    if (!same_bits(B->gn, A->gn, sizeof(A->gn))) { set_error("volume_light_grid_bake: bricks of different grids (global counts)"); return GVT_HIP_ERR_INVALID; }
-    if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && B->n_iso > 0) { set_error("volume_light_grid_bake: central gradients on a brick of a frame with an isovalue"); return GVT_HIP_ERR_INVALID; }
+    if (!same_bits(m + 16 * i, m, 16 * sizeof(float))) { set_error("%s: bricks under different matrices", fn); return GVT_HIP_ERR_INVALID; }
+    if (!same_bits(B->gn, A->gn, sizeof(A->gn))) { set_error("%s: bricks of different grids (global counts)", fn); return GVT_HIP_ERR_INVALID; }
+    if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && B->n_iso > 0) { set_error("%s: central gradients on a brick of a frame with an isovalue", fn); return GVT_HIP_ERR_INVALID; }
     // (fused_eligible compares surfaces and lights only where the frame renders them: the bake needs them equal whatever the shading)
     if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float)) || !same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) ||
-        !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) { set_error("volume_light_grid_bake: bricks with different surfaces"); return GVT_HIP_ERR_INVALID; }
-    if (B->n_lights != A->n_lights || !same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights)) { set_error("volume_light_grid_bake: bricks with different lights"); return GVT_HIP_ERR_INVALID; }
+        !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) { set_error("%s: bricks with different surfaces", fn); return GVT_HIP_ERR_INVALID; }
+    if (B->n_lights != A->n_lights || !same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights)) { set_error("%s: bricks with different lights", fn); return GVT_HIP_ERR_INVALID; }
     cells += (uint64_t)(B->n[0] - 1) * (uint64_t)(B->n[1] - 1) * (uint64_t)(B->n[2] - 1);
     verts += (uint64_t)B->n[0] * (uint64_t)B->n[1] * (uint64_t)B->n[2];
     for (size_t k = 0; k < i; k++) { // owned cells [off, off + n - 1) per axis: disjoint
       const gvt_hip_volume *K = volumes[k];
       bool apart = false;
       for (int a = 0; a < 3; a++) apart = apart || B->off[a] + B->n[a] - 1 <= K->off[a] || K->off[a] + K->n[a] - 1 <= B->off[a];
-      if (!apart) { set_error("volume_light_grid_bake: the bricks do not tile the grid: bricks %zu and %zu share a cell", k, i); return GVT_HIP_ERR_INVALID; }
+      if (!apart) { set_error("%s: the bricks do not tile the grid: bricks %zu and %zu share a cell", fn, k, i); return GVT_HIP_ERR_INVALID; }
     }
   }
   if (cells != (uint64_t)(A->gn[0] - 1) * (uint64_t)(A->gn[1] - 1) * (uint64_t)(A->gn[2] - 1)) {
-    set_error("volume_light_grid_bake: the bricks do not tile the grid: they own %llu of its %llu cells", (unsigned long long)cells,
+    set_error("%s: the bricks do not tile the grid: they own %llu of its %llu cells", fn, (unsigned long long)cells,
               (unsigned long long)((uint64_t)(A->gn[0] - 1) * (uint64_t)(A->gn[1] - 1) * (uint64_t)(A->gn[2] - 1)));
     return GVT_HIP_ERR_INVALID;
   }
+  usable = shadow_dev(A, 1).usable;
+  const unsigned n_usable = (unsigned)__builtin_popcount(usable);
+  if (!n_usable) { set_error("%s: no usable light (none set, or every position is zero)", fn); return GVT_HIP_ERR_INVALID; }
+  if (verts * n_usable > 0xffffffffull) { set_error("%s: %llu (vertex, light) pairs, at most 2^32 - 1", fn, (unsigned long long)(verts * n_usable)); return GVT_HIP_ERR_INVALID; }
+  return 0;
+}
+
+} // namespace
+
+extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                              const gvt_hip_volume_light_grid_params *params, gvt_hip_volume_light_grid_stats *stats) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  int rc;
+  if ((rc = bake_args("volume_light_grid_bake", volumes, m, minv, n_inst, params ? &params->flags : nullptr))) return rc;
+  if (params->bias < 1 || params->bias > 64) { set_error("volume_light_grid_bake: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
+  uint64_t verts = 0;
+  unsigned usable = 0;
+  if ((rc = bake_bricks("volume_light_grid_bake", volumes, m, minv, n_inst, verts, usable))) return rc;
+  const gvt_hip_volume *A = volumes[0];
   const ShadowDev H = shadow_dev(A, params->bias);
   const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
-  if (!n_usable) { set_error("volume_light_grid_bake: no usable light (none set, or every position is zero)"); return GVT_HIP_ERR_INVALID; }
-  if (verts * n_usable > 0xffffffffull) { set_error("volume_light_grid_bake: %llu (vertex, light) pairs, at most 2^32 - 1", (unsigned long long)(verts * n_usable)); return GVT_HIP_ERR_INVALID; }
   Ctx &C = gctx();
   // the new planes, all before any brick changes
   std::vector<float *> fresh(n_inst, nullptr);
@@ -2105,6 +2201,181 @@ extern "C" int gvt_hip_volume_light_grid_release(gvt_hip_volume *V) {
   hipFree(V->d_lgrid);
   V->d_lgrid = nullptr;
   V->lg_planes = 0; V->lg_bias = 0; V->lg_usable = 0; V->lg_current = false; V->lg_bake = 0;
+  return 0;
+}
+
+// ---- meshes shadowing the volume (the contract: include/gvt_hip.h, "meshes shadowing the volume"; volume_occluder_grid.inc,
+// volume_fused_mesh.inc)
+extern "C" int gvt_hip_volume_frame_mesh_shadowed(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                                  const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
+                                                  const gvt_hip_volume_shadow_params *params, gvt_hip_volume_mesh_shadow_stats *stats) {
+  gvt_hip_volume_shadow_stats O{};
+  uint64_t fog_samples = 0;
+  bool mesh_ran = false;
+  const int rc = volume_frame_shadowed_impl("volume_frame_mesh_shadowed", true, T, volumes, m, minv, n_inst, cam, queues, fb, depth, params, O, fog_samples, true, &mesh_ran);
+  if (!rc && stats) {
+    gvt_hip_volume_mesh_shadow_stats F{};
+    F.fog.frame = O;
+    F.fog.fog_samples_shadowed = fog_samples;
+    F.mesh_shadowed = mesh_ran ? 1u : 0u;
+    *stats = F;
+  }
+  return rc;
+}
+
+// Scratch of one bake, each slot in one use along the chain: SCR_VOL_GRIDS the per-brick table, SCR_VOL_OCC_RAYS a chunk's p0 / p1 planes,
+// SCR_VOL_OCC its O words, SCR_GENERAL its any-hit flags (as gvt_hip_occluded), SCR_VOL_FUSED the counter word
+extern "C" int gvt_hip_volume_occluder_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, gvt_hip_mesh *const *meshes,
+                                                 const float *mesh_minv, size_t n_mesh_inst, const gvt_hip_volume_occluder_params *params,
+                                                 gvt_hip_volume_occluder_stats *stats) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  int rc;
+  if ((rc = bake_args("volume_occluder_grid_bake", volumes, m, minv, n_inst, params ? &params->flags : nullptr))) return rc;
+  if (n_mesh_inst && (!meshes || !mesh_minv)) { set_error("volume_occluder_grid_bake: null argument (the mesh instances)"); return GVT_HIP_ERR_INVALID; }
+  for (size_t i = 0; i < n_mesh_inst; i++)
+    if (!meshes[i]) { set_error("volume_occluder_grid_bake: mesh instance %zu has no mesh", i); return GVT_HIP_ERR_INVALID; }
+  uint64_t verts = 0;
+  unsigned usable = 0;
+  if ((rc = bake_bricks("volume_occluder_grid_bake", volumes, m, minv, n_inst, verts, usable))) return rc;
+  const gvt_hip_volume *A = volumes[0];
+  const ShadowDev H = shadow_dev(A, 1); // (the directions and their bits; the bias is the light grid's business)
+  const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
+  Ctx &C = gctx();
+  // the new planes, all before any brick changes
+  std::vector<uint8_t *> fresh(n_inst, nullptr);
+  const auto drop = [&]() { for (uint8_t *p : fresh) hipFree(p); };
+  uint64_t bytes = 0;
+  for (size_t i = 0; i < n_inst; i++) {
+    const size_t nb = (size_t)volumes[i]->n[0] * volumes[i]->n[1] * volumes[i]->n[2] * n_usable;
+    if (hipMalloc((void **)&fresh[i], nb) != hipSuccess) {
+      (void)hipGetLastError();
+      drop();
+      set_error("volume_occluder_grid_bake: no device memory for the planes of brick %zu (%zu bytes); the old grids are kept", i, nb);
+      return GVT_HIP_ERR_CAPACITY;
+    }
+    bytes += nb;
+  }
+  const unsigned n = (unsigned)(verts * n_usable);
+  const unsigned chunk = std::min(n, C.occluder_chunk > 0 ? (unsigned)C.occluder_chunk : VOL_OCC_CHUNK);
+  OccluderBrick *d_parts = (OccluderBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(OccluderBrick) * n_inst);
+  float4 *d_rays = (float4 *)scratch_get(SCR_VOL_OCC_RAYS, sizeof(float4) * 2 * (size_t)chunk);
+  uint8_t *d_O = (uint8_t *)scratch_get(SCR_VOL_OCC, chunk);
+  int *d_flags = n_mesh_inst ? (int *)scratch_get(SCR_GENERAL, sizeof(int) * (size_t)chunk) : nullptr;
+  unsigned long long *d_blocked = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const auto fail = [&](const char *what) {
+    set_error("volume_occluder_grid_bake: %s failed: %s; the old grids are kept", what, hipGetErrorString(hipGetLastError()));
+    hipStreamSynchronize(C.stream);
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    drop();
+    return GVT_HIP_ERR_DEVICE;
+  };
+  if (!d_parts || !d_rays || !d_O || (n_mesh_inst && !d_flags) || !d_blocked) return fail("a scratch allocation");
+  static_assert(sizeof(OccluderBrick) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the table fits the staging block");
+  void *stage = nullptr;
+  if (pinned_stage_begin(&stage)) return fail("the staging block");
+  OccluderBrick *hp = (OccluderBrick *)stage;
+  unsigned first = 0;
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    hp[i] = OccluderBrick{ fresh[i], first, B->n[0], B->n[1], B->n[2], B->off[0], B->off[1], B->off[2] };
+    first += (unsigned)((size_t)B->n[0] * B->n[1] * B->n[2]) * n_usable;
+  }
+  bool ok = hipMemcpyAsync(d_parts, hp, sizeof(OccluderBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess;
+  if (pinned_stage_end() || !ok) return fail("the table upload");
+  ok = hipMemsetAsync(d_blocked, 0, sizeof(unsigned long long), C.stream) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
+       hipEventRecord(e0, C.stream) == hipSuccess;
+  if (!ok) return fail("the launches' preparation");
+  Mat4 M;
+  for (int k = 0; k < 16; k++) M.m[k] = m[k];
+  RayPlanes P{};
+  P.p0 = d_rays; P.p1 = d_rays + chunk;
+  uint64_t launches = 0;
+  for (unsigned base = 0; base < n; base += chunk) {
+    const unsigned nc = std::min(chunk, n - base);
+    if (hipMemsetAsync(d_O, 1, nc, C.stream) != hipSuccess) return fail("the chunk's clear");
+    if (n_mesh_inst) {
+      k_occluder_rays<<<blocks_of(nc), VOL_BLOCK, 0, C.stream>>>(A->go[0], A->go[1], A->go[2], A->sp[0], A->sp[1], A->sp[2], H, d_parts, (unsigned)n_inst, base, nc, M, P.p0, P.p1);
+      if (hipGetLastError() != hipSuccess) return fail("the ray kernel");
+    }
+    for (size_t i = 0; i < n_mesh_inst; i++) {
+      Mat4 Mi;
+      for (int k = 0; k < 16; k++) Mi.m[k] = mesh_minv[16 * i + k];
+      if ((rc = launch_any_flags(meshes[i], P, nc, true, Mi, GVT_RAY_EPSILON, d_flags))) { // (its own message stands)
+        hipStreamSynchronize(C.stream);
+        hipEventDestroy(e0); hipEventDestroy(e1);
+        drop();
+        return rc;
+      }
+      launches++;
+      k_occluder_fold<<<blocks_of(nc), VOL_BLOCK, 0, C.stream>>>(d_flags, nc, d_O);
+      if (hipGetLastError() != hipSuccess) return fail("the fold kernel");
+    }
+    k_occluder_pack<<<blocks_of(nc), VOL_BLOCK, 0, C.stream>>>(d_O, d_parts, (unsigned)n_inst, base, nc, d_blocked);
+    if (hipGetLastError() != hipSuccess) return fail("the pack kernel");
+  }
+  unsigned long long h_blocked = 0;
+  float ms = 0.f;
+  ok = hipEventRecord(e1, C.stream) == hipSuccess && hipMemcpyAsync(&h_blocked, d_blocked, sizeof(h_blocked), hipMemcpyDeviceToHost, C.stream) == hipSuccess &&
+       (!n_mesh_inst || trav_overflow_fetch_async() == 0) && hipStreamSynchronize(C.stream) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+  if (!ok) return fail("the bake's last wait");
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (n_mesh_inst && (rc = trav_overflow_result())) { drop(); return rc; } // (GVT_HIP_ERR_DEVICE: the flags are incomplete; the old grids are kept)
+  // commit: every brick at once
+  static uint64_t bake_serial = 0;
+  bake_serial++;
+  for (size_t i = 0; i < n_inst; i++) {
+    gvt_hip_volume *B = volumes[i];
+    hipFree(B->d_occ);
+    B->d_occ = fresh[i];
+    B->og_planes = (int)n_usable; B->og_usable = H.usable; B->og_current = true;
+    B->og_bake = bake_serial; B->og_index = i; B->og_count = n_inst;
+    std::memcpy(B->og_m, m + 16 * i, sizeof(B->og_m));
+    std::memcpy(B->og_minv, minv + 16 * i, sizeof(B->og_minv));
+  }
+  if (stats) {
+    gvt_hip_volume_occluder_stats O{};
+    O.rays = n; O.rays_blocked = h_blocked; O.any_hit_launches = launches; O.bytes = bytes; O.ms = ms;
+    *stats = O;
+  }
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_occluder_grid_download(gvt_hip_volume *V, int light, uint8_t *out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !out) { set_error("volume_occluder_grid_download: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (!V->d_occ) { set_error("volume_occluder_grid_download: the volume holds no occluder grid"); return GVT_HIP_ERR_INVALID; }
+  if (light < 0 || light >= GVT_HIP_VOLUME_MAX_LIGHTS || !((V->og_usable >> light) & 1u)) {
+    set_error("volume_occluder_grid_download: light %d was not usable at the bake and has no grid (its factor is 1)", light);
+    return GVT_HIP_ERR_INVALID;
+  }
+  const size_t n_vert = (size_t)V->n[0] * V->n[1] * V->n[2];
+  const int plane = __builtin_popcount(V->og_usable & ((1u << light) - 1u));
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(out, V->d_occ + n_vert * (size_t)plane, n_vert, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_occluder_grid_info(gvt_hip_volume *V, gvt_hip_volume_occluder_state *out) {
+  if (!V || !out) { set_error("volume_occluder_grid_info: null argument"); return GVT_HIP_ERR_INVALID; }
+  gvt_hip_volume_occluder_state I{};
+  I.present = V->d_occ ? 1u : 0u;
+  I.current = (V->d_occ && V->og_current) ? 1u : 0u;
+  I.n_planes = V->d_occ ? V->og_planes : 0;
+  I.bytes = V->d_occ ? (uint64_t)V->n[0] * V->n[1] * V->n[2] * (uint64_t)V->og_planes : 0;
+  *out = I;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_occluder_grid_release(gvt_hip_volume *V) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V) { set_error("volume_occluder_grid_release: null"); return GVT_HIP_ERR_INVALID; }
+  if (!V->d_occ) return 0;
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a frame in flight reads the planes)
+  hipFree(V->d_occ);
+  V->d_occ = nullptr;
+  V->og_planes = 0; V->og_usable = 0; V->og_current = false; V->og_bake = 0;
   return 0;
 }
 
@@ -2251,6 +2522,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
     if (V->sub.empty()) return 0;
     HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the tables)
     V->lg_current = false; // (a light grid never covers subgrids, and the ranges change)
+    V->og_current = false;
     amr_release(V);
     return amr_refresh_ranges(V);
   }
@@ -2291,6 +2563,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   hipFree(d_items); hipFree(d_out);
   // commit
   V->lg_current = false;
+  V->og_current = false;
   amr_release(V);
   V->d_amr_vox = d_vox; V->d_amr_mc = d_mc; V->d_amr_list = d_list; V->d_amr_desc = d_desc;
   V->sub.assign(grids, grids + n);

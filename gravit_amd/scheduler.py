@@ -572,10 +572,14 @@ class VolumeTracer:
     shadowed too, by the transmittance towards each light interpolated from grids baked at the vertices (gvt_hip_volume_light_grid_bake;
     fog_bias = the bake's bias).  frame() bakes on the first frame that has lit fog and a usable light, and again after update(),
     set_surfaces() or set_lights() -- the cost is per change of data, table, surfaces or lights, not per frame; rebake() is explicit
-    (needed after a call on a single adapter, which the tracer does not see: the library then refuses the frame)."""
+    (needed after a call on a single adapter, which the tracer does not see: the library then refuses the frame).
+    mesh_shadows (with shadows and fog_shadows; otherwise ValueError): frame() goes through gvt_hip_volume_frame_mesh_shadowed -- meshes
+    cast shadows into the volume, from occluder grids baked at the vertices (gvt_hip_volume_occluder_grid_bake).  bake_occluders(scene)
+    bakes them; frame() bakes again from the same scene after set_lights().  The library cannot see a mesh move: call bake_occluders
+    again after the scene changed.  A frame that needs a grid and has none is refused (GvtHipError)."""
 
     def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2,
-                 fog_shadows=False, fog_bias=1):
+                 fog_shadows=False, fog_bias=1, mesh_shadows=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -583,6 +587,8 @@ class VolumeTracer:
 
         if fog_shadows and not shadows:
             raise ValueError("VolumeTracer: fog_shadows needs shadows=True (the fog-shadowed frame is the shadowed frame with one more change)")
+        if mesh_shadows and not (shadows and fog_shadows):
+            raise ValueError("VolumeTracer: mesh_shadows needs shadows=True and fog_shadows=True (the mesh-shadowed frame is the fog-shadowed frame with one more change)")
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         self.camera = camera
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
@@ -609,6 +615,13 @@ class VolumeTracer:
         self.light_bakes = 0
         self.light_grid_stats = None  # fog_shadows=True: gvt_hip_volume_light_grid_stats of the last bake, as a dict
         self._grid_stale = True  # nothing baked yet, or a setter / update of this tracer since the last bake
+        self.mesh_shadows = bool(mesh_shadows)
+        self.occluder_bakes = 0
+        self.occluder_stats = None  # mesh_shadows=True: gvt_hip_volume_occluder_stats of the last bake, as a dict
+        self._occluder_source = None  # the scene or backend of the last bake_occluders: what frame() bakes from again
+        self._occluder_stale = True  # nothing baked yet, or set_lights since the last bake
+        self._occluder_kept = None  # adapter.scene_instances' third result: the mesh adapters made here for a scenes.Scene
+        self._surfaces = False  # set_surfaces with at least one isovalue or slice plane?
         self._lit = False  # set_shading(True)?
         self._usable_lights = 0  # lights of set_lights that cast shadow rays
         self._arr = lambda xs: (C.c_void_p * max(1, self.n_inst))(*[x.h for x in xs])
@@ -624,7 +637,19 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        if self.shadows and self.fog_shadows:
+        if self.mesh_shadows:
+            if self._grid_stale and self._lit and self._usable_lights:
+                self.rebake()
+            if self._occluder_stale and self._occluder_source is not None and self._usable_lights and (self._lit or self._surfaces):
+                self.bake_occluders(self._occluder_source)
+            st = capi.VolumeMeshShadowStats()
+            params = capi.VolumeShadowParams(0, self.shadow_bias)
+            capi.check(capi.load().gvt_hip_volume_frame_mesh_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                                      C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
+                                                                      C.byref(params), C.byref(st)), "gvt_hip_volume_frame_mesh_shadowed")
+            self.shadow_stats = st.as_dict()
+            calls = C.c_uint64(st.fog.adapter_calls)
+        elif self.shadows and self.fog_shadows:
             if self._grid_stale and self._lit and self._usable_lights:
                 self.rebake()
             st = capi.VolumeFogShadowStats()
@@ -681,6 +706,29 @@ class VolumeTracer:
         self._grid_stale = False
         return self
 
+    def bake_occluders(self, scene_or_backend):
+        """gvt_hip_volume_occluder_grid_bake over the tracer's bricks under its matrix: which vertices the meshes of scene_or_backend (a
+        scenes.Scene or a scheduler.HipBackend, taken as adapter.DepthPlane.render takes them) shadow from each usable light."""
+        import ctypes as C
+
+        from .adapter import scene_instances
+
+        scene, adapters, self._occluder_kept = scene_instances(scene_or_backend, self._occluder_kept)
+        m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
+        minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
+        meshes = (C.c_void_p * max(1, scene.n_inst))(*[a.h for a in adapters])
+        mesh_minv = capi.f32(scene.minv)
+        st = capi.VolumeOccluderStats()
+        params = capi.VolumeOccluderParams(0, 0)
+        capi.check(capi.load().gvt_hip_volume_occluder_grid_bake(self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst), meshes,
+                                                                 capi.ptr(mesh_minv), C.c_size_t(scene.n_inst), C.byref(params), C.byref(st)),
+                   "gvt_hip_volume_occluder_grid_bake")
+        self.occluder_stats = st.as_dict()
+        self.occluder_bakes += 1
+        self._occluder_source = scene_or_backend
+        self._occluder_stale = False
+        return self
+
     @staticmethod
     def _same_bricking(adapters, bricks):
         """Helper of update(), not part of the tracer's surface (static so that the check runs without a device): the bricks of another time
@@ -714,12 +762,14 @@ class VolumeTracer:
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
         """The volume's isosurfaces and slice planes (object space), on every brick."""
         self._grid_stale = True
+        self._surfaces = bool(len(isovalues) or len(slices))
         for a in self.adapters:
             a.set_surfaces(isovalues, slices, opacity)
         return self
 
     def set_lights(self, lights, ka=0.4, kd=0.6):
         self._grid_stale = True
+        self._occluder_stale = True
         for a in self.adapters:
             a.set_lights(lights, ka, kd)
         if isinstance(lights, np.ndarray) and lights.dtype.names:
@@ -754,8 +804,14 @@ class VolumeTracer:
         shadows=True: the last frame's gvt_hip_volume_shadow_stats in fused_shaded's form (the camera rays' counters), and beside them
         shadowed, shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched and shadow_samples_gathered.
         fog_shadows=True adds fog_samples_shadowed of the last frame, light_bakes (bakes so far) and light_grid_rays / _bytes / _ms of the
-        last bake (0 before the first)."""
+        last bake (0 before the first).
+        mesh_shadows=True adds mesh_shadowed of the last frame, occluder_bakes (bakes so far) and occluder_rays / _rays_blocked / _bytes /
+        _ms of the last bake (0 before the first)."""
         out = self._brick_stats()
+        if self.mesh_shadows:
+            g = self.occluder_stats or {"rays": 0, "rays_blocked": 0, "bytes": 0, "ms": 0.0}
+            out.update(occluder_bakes=self.occluder_bakes, occluder_rays=g["rays"], occluder_rays_blocked=g["rays_blocked"], occluder_bytes=g["bytes"],
+                       occluder_ms=g["ms"], mesh_shadowed=0 if self.shadow_stats is None else self.shadow_stats["mesh_shadowed"])
         if self.fog_shadows:
             g = self.light_grid_stats or {"rays": 0, "bytes": 0, "ms": 0.0}
             out.update(light_bakes=self.light_bakes, light_grid_rays=g["rays"], light_grid_bytes=g["bytes"], light_grid_ms=g["ms"],
@@ -966,13 +1022,15 @@ class VolumeDomainTracer(DomainTracer):
     ray ends; the sum-reduce and the rows_only rectangles add it to zeros."""
 
     def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False,
-                 shadows=False, fog_shadows=False):
+                 shadows=False, fog_shadows=False, mesh_shadows=False):
         from types import SimpleNamespace
 
         if shadows:  # (a shadow ray is marched to its end by the lane that needs it: a rank does not hold the foreign bricks it crosses)
             raise ValueError("VolumeDomainTracer: shadows need every brick of the volume on one device (VolumeTracer(shadows=True))")
         if fog_shadows:  # (nor the bricks a vertex's ray crosses)
             raise ValueError("VolumeDomainTracer: fog_shadows need every brick of the volume on one device (VolumeTracer(shadows=True, fog_shadows=True))")
+        if mesh_shadows:  # (the mesh-shadowed frame is the fog-shadowed frame with one more change)
+            raise ValueError("VolumeDomainTracer: mesh_shadows need every brick of the volume on one device (VolumeTracer(shadows=True, fog_shadows=True, mesh_shadows=True))")
 
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         if m is not None:  # (whatever backend marches the bricks: the next-brick rule is the same)
@@ -1036,10 +1094,13 @@ class MixedTracer:
     (the mesh frame, as it is on its own), a DepthPlane and a VolumeTracer; frame() renders the mesh frame, the depth plane of the
     scene (a second closest-hit pass over the primaries), the volume frame clipped at it, and composites the volume over the meshes
     (gvt_hip_fb_composite_over; the result is in the volume tracer's framebuffer).  The reference has no such path: shuffleRays
-    takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel)."""
+    takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel).
+    mesh_shadows (with shadows and fog_shadows): the meshes cast shadows into the volume (VolumeTracer's mesh_shadows).  frame() bakes the
+    occluder grids before the first volume frame that needs them and again after update_scene() and set_lights(); rebake_occluders() is
+    explicit.  set_camera(), update() and set_surfaces() do not bake."""
 
     def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
-                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1):
+                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -1053,9 +1114,19 @@ class MixedTracer:
         self.mesh = NativeTracer(self.scene, normal_mode)
         self.depth = DepthPlane(camera.width, camera.height)
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
-                                   fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias)
+                                   fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias,
+                                   mesh_shadows=mesh_shadows)
         # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; shadows: the volume's surfaces shadowed by the
-        # volume -- the meshes cast no shadow into it; fog_shadows: its lit fog too, from the baked light grids)
+        # volume; fog_shadows: its lit fog too, from the baked light grids; mesh_shadows: both shadowed by the meshes as well, from the baked
+        # occluder grids -- without it the meshes cast no shadow into the volume)
+        self.mesh_shadows = bool(mesh_shadows)
+        if self.mesh_shadows:
+            self.volume._occluder_source = self.mesh.backend  # (frame() bakes from it once the frame needs a grid)
+
+    def rebake_occluders(self):
+        """The occluder grids of the scene as it is now (VolumeTracer.bake_occluders over the mesh tracer's backend)."""
+        self.volume.bake_occluders(self.mesh.backend)
+        return self
 
     def frame(self):
         self.mesh()
@@ -1105,6 +1176,7 @@ class MixedTracer:
             raise ValueError("MixedTracer: the depth plane holds one ray per pixel (camera.samples must be 1)")
         self.mesh.update_scene(scene)
         self.scene = scene
+        self.volume._occluder_stale = True  # (the library cannot see a mesh move)
         self.camera = self.volume.camera = scene.camera
         return self
 

@@ -824,8 +824,8 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
  * a pixel has the bits of the same frame rendered with kd = 0.
  * DEVIATIONS.  (1) A surface is rendered at the far sample of its step, so a shadow ray towards a light on the camera's side would
  * cross its own sheet again; bias is the remedy: the first shadow sample is lattice index `bias`, and a first sample has no previous
- * sides, so nothing within `bias` steps casts a shadow.  (2) The geometry of a mixed frame casts no shadow into the volume: the depth
- * plane clips camera rays only.  (3) The fog is not shadowed (gvt_hip_volume_frame_fog_shadowed below shadows it).  (4) At samples > 1
+ * sides, so nothing within `bias` steps casts a shadow.  (2) The geometry of a mixed frame casts no shadow into the volume in THIS frame: the depth
+ * plane clips camera rays only (gvt_hip_volume_frame_mesh_shadowed below lets it).  (3) The fog is not shadowed (gvt_hip_volume_frame_fog_shadowed below shadows it).  (4) At samples > 1
  * deposits meet in arrival order, as ever.  (5) A shadow ray that runs IN a face two bricks share -- its origin on the face, ws_j with a
  * zero component along the face's axis -- has its samples owned by one of the two bricks (cell floor), while the next-brick rule enters
  * a brick only if the ray leaves it strictly later than it left the last one; the two neighbours share their exit, so the owner is
@@ -835,7 +835,7 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
  * COUNTERS.  shadow_rays = (samples with at least one rendered crossing) x (lights with a usable ws_j); shadow_brick_visits,
  * shadow_crossings and shadow_samples_marched / _gathered are the fused frame's counters applied to the shadow rays.  They are kept
  * apart from the camera rays' counters, which equal those of the unshadowed frame whenever the two images agree.
- * OUT OF SCOPE.  Ambient occlusion; shadowed fog (below); geometry shadowing the volume or the volume attenuating mesh shadow rays; the Domain
+ * OUT OF SCOPE.  Ambient occlusion; shadowed fog and geometry shadowing the volume (both below); the volume attenuating mesh shadow rays; the Domain
  * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR and CENTRAL frames; shadows in the per-brick loop. */
 typedef struct {
   uint32_t flags; /* must be 0 */
@@ -898,12 +898,12 @@ int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes,
  * shadows fog -- and a frame with effective lit shading and a usable light whose bricks do not all hold a CURRENT grid ("light grid").
  * DEVIATIONS.  (1) Transmittance is interpolated from vertices: a shadow's edge is one cell soft, and an occluder thinner than a cell
  * leaks.  (2) Crossings keep exact rays, so the two kinds of shadow meet at slightly different softness.  (3) Meshes cast no shadow
- * into the volume.  (4) The grid's bias is the bake's, the crossings' bias the frame's.
+ * into the volume in this frame (gvt_hip_volume_frame_mesh_shadowed below).  (4) The grid's bias is the bake's, the crossings' bias the frame's.
  * COUNTERS.  Bake: rays = (vertices summed over the bricks) x (usable lights); samples_marched / _gathered and crossings as the fused
  * frames count them; bytes = the planes' size; ms = the launch's event time.  Frame: gvt_hip_volume_shadow_stats, and
  * fog_samples_shadowed = samples_shaded when the fog kernel ran (else 0).
  * A volume that holds a grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees the grid.
- * OUT OF SCOPE.  A coarser or compressed grid; pruning vertices no sample reads; ambient occlusion; meshes shadowing the volume; the
+ * OUT OF SCOPE.  A coarser or compressed grid; pruning vertices no sample reads; ambient occlusion; the
  * Domain scheduler; AMR and CENTRAL frames; moving the crossings' shadow rays onto the grid. */
 typedef struct {
   uint32_t flags; /* must be 0 */
@@ -934,6 +934,87 @@ int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *, gvt_hip_volume *const *volu
                                       const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
                                       const gvt_hip_depth *depth /* may be NULL */, const gvt_hip_volume_shadow_params *params,
                                       gvt_hip_volume_fog_shadow_stats *stats /* may be NULL */);
+
+/* ---- meshes shadowing the volume: occluder grids baked on the device (additive: the ABI revision stays 6, no entry point above changes) ----
+ * The two halves of a mixed frame now agree about light: whether a mesh stands between a point of the volume and a light is computed
+ * ONCE at every grid vertex (gvt_hip_volume_occluder_grid_bake), kept beside the samples as uint8 planes and interpolated wherever the
+ * fog-shadowed frame uses a transmittance (gvt_hip_volume_frame_mesh_shadowed).
+ * THE GRID.  For a frame of bricks of ONE grid, every usable light j (ws_j finite and not zero, as in "shadowed surfaces") has a uint8
+ * value O_j at every global vertex I:
+ *   wp     = the vertex in world space, exactly as "shadowed fog" computes it (p[a] = origin[a] + (float)I[a] * spacing[a]; m as a point)
+ *   the ray: origin wp, direction ws_j, t_min = GVT_RAY_EPSILON, no far limit (the words of an object-space query, gvt_hip_occluded)
+ *   taken into every mesh instance i by that instance's minv, exactly as gvt_hip_depth_render's rays are
+ *   O_j(I) = 0 if the any-hit traversal reports a hit in at least one instance, else 1
+ * A brick stores O_j at its own vertices, at the samples' own index: one plane per usable light in the order of their bits, the shared
+ * layers twice with the same bits.  An unusable light has no plane; its factor is 1.  O does not depend on the volume's data, table or
+ * surfaces; (float)O is exact, and the planes take a quarter of a light grid's memory.
+ * THE BAKE.  Eligibility is gvt_hip_volume_light_grid_bake's, clause for clause (the library checks both through one function), without
+ * the bias.  n_mesh_inst == 0 is allowed: every O is 1 and no traversal is launched.  A null mesh among the instances is refused.
+ * Refusals: GVT_HIP_ERR_INVALID, the message names the clause.  Planes that cannot be allocated: GVT_HIP_ERR_CAPACITY.  A HIP call that
+ * fails, or the traversal's overflow word: GVT_HIP_ERR_DEVICE.  In every failing case each brick keeps the occluder grid it had (all
+ * planes are allocated and filled before the first brick changes).  The call waits for its last launch.  The work is done in chunks of
+ * (vertex, light) pairs: one kernel writes the chunk's rays, one any-hit launch per mesh instance runs over them, each followed by a
+ * fold (O &= !flag), and one kernel packs the chunk into the bricks' planes.
+ * CURRENT.  A frame's occluder grids are current if ONE bake covered exactly these volumes in this order with the same m and minv bits
+ * and since then no brick has had _set_lights or _set_subgrids.  _update_samples[_typed], _set_transfer, _set_surfaces, _set_shading and
+ * _set_gradient do NOT make them stale.  THE LIBRARY CANNOT SEE A MESH MOVE: the caller bakes again after gvt_hip_mesh_update_vertices,
+ * gvt_hip_top_update or any change of the instance matrices.
+ * THE FRAME.  gvt_hip_volume_frame_mesh_shadowed is gvt_hip_volume_frame_fog_shadowed -- same arguments, same refusals, crossings lit
+ * through exact in-kernel shadow rays -- with one more change.  At a sample whose cell is c and whose fractions are f, for every usable
+ * light
+ *     Og = trilinear interpolation of (float)O_j at the cell's eight vertices (the sample's c and f; nesting x, then y, then z)
+ *     lit fog sample:        ndl_s = ndl * (Tg * Og)
+ *     crossing at sample k:  ndl_s = ndl * (T_j * Og)     Og from sample k's own cell, the sample at which the crossing is rendered
+ * with Og = 1 and nothing read for an unusable light.  O is read only where G or T_j is used; A never depends on O, and no shadow ray
+ * is cast or skipped because of O, so every counter of gvt_hip_volume_fog_shadow_stats equals the fog-shadowed frame's and skipping stays
+ * exact against GVT_HIP_VOLUME_NO_SKIP.  A frame with surfaces but no effective lit shading needs no light grid, as today.
+ * INERT.  No usable light, or neither surfaces nor effective lit shading: the call is gvt_hip_volume_frame_fog_shadowed in every respect;
+ * no occluder grid is needed.
+ * REFUSED (GVT_HIP_ERR_INVALID, the message names the clause, nothing changed, the framebuffer not cleared): everything the fog-shadowed
+ * frame refuses, and a frame that is not inert and whose bricks do not all hold a CURRENT occluder grid ("occluder grid").
+ * CONSEQUENCES.  With every O = 1 (no mesh, or meshes outside every vertex ray) the bits are the fog-shadowed frame's.  Where every O of
+ * a sample's cell is 0 for every light -- and that holds for every shaded sample of the pixel -- the pixel has the bits of the same
+ * frame rendered with kd = 0.  The image is the same bits for every bricking and with or without skipping.
+ * DEVIATIONS.  (1) Mesh shadows are interpolated from vertices: one cell soft, and an occluder thinner than a cell leaks -- on crossings
+ * too, where the volume's own shadows are exact.  (2) The volume's lights are directional and the scene's own lights are not; the mesh
+ * frame is untouched, so the fog neither attenuates mesh shadow rays nor shades the meshes.  (3) The mesh frame's framebuffer keeps its
+ * bits.
+ * COUNTERS.  Bake: rays = (vertices summed over the bricks) x (usable lights); rays_blocked = those with O = 0; any_hit_launches;
+ * bytes = the planes' size; ms = the event time from the first to the last launch.  Frame: the fog-shadowed frame's, and mesh_shadowed
+ * = 1 when the mesh kernel ran (0: inert).
+ * A volume that holds an occluder grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees it.
+ * OUT OF SCOPE.  The fog attenuating mesh shadow rays; exact per-crossing mesh shadow rays; skipping volume shadow rays where O = 0;
+ * the Domain scheduler; AMR and CENTRAL frames. */
+typedef struct {
+  uint32_t flags; /* must be 0 */
+  uint32_t pad;
+} gvt_hip_volume_occluder_params;
+typedef struct {
+  uint64_t rays, rays_blocked, any_hit_launches, bytes;
+  float ms;
+  uint32_t pad;
+} gvt_hip_volume_occluder_stats;
+typedef struct {
+  uint32_t present, current; /* a grid is held | ... and no call has made it stale since its bake */
+  int32_t n_planes, pad;     /* usable lights at the bake */
+  uint64_t bytes;
+} gvt_hip_volume_occluder_state;
+typedef struct {
+  gvt_hip_volume_fog_shadow_stats fog; /* the fog-shadowed frame's counters, same meaning */
+  uint32_t mesh_shadowed, pad;
+} gvt_hip_volume_mesh_shadow_stats;
+int gvt_hip_volume_occluder_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                      gvt_hip_mesh *const *meshes, const float *mesh_minv /* 16 floats per mesh instance */, size_t n_mesh_inst,
+                                      const gvt_hip_volume_occluder_params *params, gvt_hip_volume_occluder_stats *stats /* may be NULL */);
+/* out: host memory, counts[0] * counts[1] * counts[2] bytes at i + nx * (j + ny * k).  No grid, or a light that was unusable at the
+ * bake: GVT_HIP_ERR_INVALID.  A stale grid can still be downloaded. */
+int gvt_hip_volume_occluder_grid_download(gvt_hip_volume *, int light, uint8_t *out);
+int gvt_hip_volume_occluder_grid_info(gvt_hip_volume *, gvt_hip_volume_occluder_state *out);
+int gvt_hip_volume_occluder_grid_release(gvt_hip_volume *); /* frees the planes; a volume without a grid: 0 */
+int gvt_hip_volume_frame_mesh_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                       const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
+                                       const gvt_hip_depth *depth /* may be NULL */, const gvt_hip_volume_shadow_params *params,
+                                       gvt_hip_volume_mesh_shadow_stats *stats /* may be NULL */);
 
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);
@@ -1030,7 +1111,8 @@ int gvt_hip_math_probe(int kind, const float *in, size_t n, float *out);
  *                "comm_stream"                   Domain scheduler: 1 = every exchange of a frame on the communicator's own stream, ordered against the compute stream
  *                                                by events (also GVT_HIP_COMM_STREAM in the environment); default 0: on the compute stream, large payloads beside it
  *                "abi_lanes" / "abi_chunk"     gvt_hip_trace on a host RayVector: pipeline lanes (0: one shot), rays per chunk
- *   test hook    "inject_fail_tick"
+ *   test hooks   "inject_fail_tick"; "occluder_chunk": (vertex, light) pairs per chunk of gvt_hip_volume_occluder_grid_bake (0, the default: the
+ *                               library's own constant), so that a test's small grid spans several chunks.  Results never depend on it
  * Everything else -- the tuned constants of the kernels (refill / phase thresholds, grid sizes, drain sharing ...) and the alternative arms that
  * were measured and lost but stay in the code (merged kernels for one queue, compacted shadow slots, non-lean frames, camera rays in
  * generateRays' pixel-major order ("camera_tile" = 0) ...: EXPERIMENTS.md) -- can be moved only in the experiments build of the library

@@ -47,6 +47,11 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              and the samples shaded per frame, and the two framebuffers compared bitwise after every pair
   python tools/volume_bench.py --fused --shade --fog-shadows  shadowed fog (gvt_hip_volume_frame_fog_shadowed): the lit fused frame, the same
                                                         frame with the fog shadowed from the light grids, and the bake
+  python tools/volume_bench.py --fused --shade --fog-shadows --mesh-shadows  meshes shadowing the volume (gvt_hip_volume_frame_mesh_shadowed):
+                                                        the bunny of scenes.bunny_scene inside the grid (scenes.mesh_in_volume); the bake of the
+                                                        occluder grids and its share spent in any-hit launches; the fog-shadowed frame and the
+                                                        mesh-shadowed frame alternating frame by frame on ONE tracer; the brickings' framebuffers
+                                                        compared bitwise.  With --surfaces also the frame with two isovalues, lit fog on and off
   python tools/volume_bench.py --fused --surfaces --shadows   shadowed surfaces (gvt_hip_volume_frame_shadowed): --surfaces' frame shadowed
                                              against the same frame through the shaded fused kernel, alternating frame by frame on ONE
                                              tracer; with each the shadow rays and the shadow samples per frame, so that the cost per shadow
@@ -311,6 +316,60 @@ def run_fog_shadows(n, split, steps, warmup, rate, kind, vol, dtype="f32", first
            "camera_counters_same": bool(all(st[k] == ps[k] for k in ("samples_marched", "samples_gathered", "samples_shaded", "brick_visits", "rays_deposited"))),
            "loop_cell_ms_median": med(grad["cell"]), "loop_central_ms_median": med(grad["central"]),
            "central_over_cell": round(float(np.median(grad["central"])) / float(np.median(grad["cell"])), 4),
+           "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())}
+    return row, fb
+
+
+def run_mesh_shadows(n, split, steps, warmup, rate, kind, vol, shape, dtype="f32", first=None):
+    """The bunny inside the grid: the fog-shadowed frame (shape "surf": surfaces with unlit fog, which is the shadowed frame) against the
+    same frame with the meshes' shadows (gvt_hip_volume_frame_mesh_shadowed), alternating frame by frame on one tracer
+    (VolumeTracer.mesh_shadows switches the entry point); the occluder bake timed on its own (its launches' event time: a cost per change
+    of the scene or the lights, not per frame) and once more under the any-hit profile, for the share of it spent in traversal.  The
+    volume is rendered alone and unclipped, so that the two frames march the same samples.  Returns (row, the mesh-shadowed framebuffer)."""
+    scene = scenes.bunny_scene(1920, 1080)
+    placed = scenes.mesh_in_volume(scene, vol, fill=0.6)
+    bricks = placed if split == (1, 1, 1) else scenes.split_volume(placed, *split)
+    tr = VolumeTracer(bricks, scene.camera, transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=True, shadows=True, fog_shadows=True,
+                      mesh_shadows=True)
+    _, lo, hi = DTYPES[dtype]
+    if shape != "lit":
+        tr.set_surfaces(tuple(lo + v * (hi - lo) for v in SURFACE_MODES["reached"]), (), 0.3)
+    tr.set_lights(SHADE_LIGHTS[:1]).set_shading(shape != "surf")
+    bake = []
+    for i in range(warmup + steps):
+        tr.bake_occluders(scene)
+        bake.append(tr.occluder_stats["ms"])
+    bake = bake[warmup:]
+    g = tr.occluder_stats
+    capi.profile(4)  # (the any-hit launches alone)
+    capi.stats(reset=True)
+    tr.bake_occluders(scene)
+    any_ms = float(capi.stats()["ms_any"])
+    capi.profile(0)
+    fog, mesh = [], []
+
+    def frame(flag):
+        tr.mesh_shadows = flag
+        tr.frame()
+
+    for i in range(warmup + steps):
+        fog.append(timed(lambda: frame(False)))
+        ps = tr.stats()
+        mesh.append(timed(lambda: frame(True)))
+    fog, mesh = fog[warmup:], mesh[warmup:]
+    st = tr.stats()
+    fb = tr.framebuffer(False).copy()
+    row = {"mode": "fused_mesh_shadows", "shape": shape, "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "mesh": "bunny",
+           "bake_ms_median": med(bake), "bake_ms_min": round(min(bake), 3), "bake_ms_max": round(max(bake), 3), "bake_rays": int(g["rays"]),
+           "bake_rays_blocked": int(g["rays_blocked"]), "bake_any_hit_launches": int(g["any_hit_launches"]), "bake_any_hit_ms": round(any_ms, 3),
+           "bake_any_hit_share": round(any_ms / max(float(tr.occluder_stats["ms"]), 1e-9), 3), "grid_bytes": int(g["bytes"]),
+           "fog_ms_median": med(fog), "fog_ms_min": round(min(fog), 3), "fog_ms_max": round(max(fog), 3),
+           "mesh_ms_median": med(mesh), "mesh_ms_min": round(min(mesh), 3), "mesh_ms_max": round(max(mesh), 3),
+           "mesh_over_fog": round(float(np.median(mesh)) / float(np.median(fog)), 4), "mesh_shadowed": int(st["mesh_shadowed"]),
+           "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "samples_shaded": int(st["samples_shaded"]),
+           "crossings_per_frame": int(st["crossings_rendered"]), "shadow_rays": int(st["shadow_rays"]),
+           "counters_same": bool(all(st[k] == ps[k] for k in ("samples_marched", "samples_gathered", "samples_shaded", "brick_visits", "rays_deposited", "shadow_rays",
+                                                              "shadow_samples_marched"))),
            "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())}
     return row, fb
 
@@ -634,6 +693,7 @@ def main():
     ap.add_argument("--shadows", action="store_true", help="with --fused --surfaces: the shadowed frame against the shaded fused frame")
     ap.add_argument("--bias", type=int, default=2, help="with --shadows: the first shadow sample's lattice index")
     ap.add_argument("--fog-shadows", action="store_true", help="with --fused --shade: the lit fused frame against the fog-shadowed frame, and the bake of its light grids")
+    ap.add_argument("--mesh-shadows", action="store_true", help="with --fused --shade --fog-shadows: the fog-shadowed frame against the mesh-shadowed frame, and the bake of its occluder grids")
     a = ap.parse_args()
     if a.update or a.domains:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
@@ -680,6 +740,19 @@ def main():
         a.sizes = []
     if a.fog_shadows and not (a.fused and a.shade):
         ap.error("--fog-shadows goes with --fused --shade")
+    if a.mesh_shadows and not a.fog_shadows:
+        ap.error("--mesh-shadows goes with --fused --shade --fog-shadows")
+    for n in a.sizes if a.mesh_shadows else ():
+        vol = noise(n, a.dtype)
+        for shape, kind in [("lit", k) for k in a.tf] + ([("surf_lit", "thin"), ("surf", "thin")] if a.surfaces else []):
+            first = None
+            for nb in a.bricks:
+                r, fb = run_mesh_shadows(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, shape, a.dtype, first)
+                first = fb if first is None else first
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+    if a.mesh_shadows:
+        a.sizes = []
     for n in a.sizes if a.fog_shadows else ():
         vol = noise(n, a.dtype)
         for kind in a.tf:
