@@ -118,7 +118,7 @@ class VolumeFusedShadedStats(C.Structure):
 
 
 class VolumeShadowParams(C.Structure):
-    """gvt_hip_volume_shadow_params: flags must be 0; bias = the first shadow sample's lattice index, 1 .. 64."""
+    """gvt_hip_volume_shadow_params: flags is 0 or VOLUME_ALLOW_CENTRAL; bias = the first shadow sample's lattice index, 1 .. 64."""
     _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
 
 
@@ -132,7 +132,7 @@ class VolumeShadowStats(C.Structure):
 
 
 class VolumeLightGridParams(C.Structure):
-    """gvt_hip_volume_light_grid_params: flags must be 0; bias = the first sample of a vertex's shadow ray, 1 .. 64."""
+    """gvt_hip_volume_light_grid_params: flags is 0 or VOLUME_ALLOW_CENTRAL; bias = the first sample of a vertex's shadow ray, 1 .. 64."""
     _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
 
 
@@ -162,7 +162,7 @@ class VolumeFogShadowStats(C.Structure):
 
 
 class VolumeOccluderParams(C.Structure):
-    """gvt_hip_volume_occluder_params: flags must be 0."""
+    """gvt_hip_volume_occluder_params: flags is 0 or VOLUME_ALLOW_CENTRAL."""
     _fields_ = [("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
@@ -193,6 +193,8 @@ class VolumeMeshShadowStats(C.Structure):
 
 
 FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
+FUSED_CENTRAL = 8  # ... and such frames whose bricks all shade with VOLUME_GRADIENT_CENTRAL (the kernel's CENTRAL instantiation; its bit in features)
+VOLUME_ALLOW_CENTRAL = 2  # flags of VolumeShadowParams, VolumeLightGridParams and VolumeOccluderParams: accept frames whose bricks are all CENTRAL
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10

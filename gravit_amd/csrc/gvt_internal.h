@@ -52,6 +52,7 @@ enum ScratchSlot {
   SCR_VOL_GRIDS,   // the light grids' per-brick table beside SCR_VOL_BRICKS: the bake's work list and planes, the fog-shadowed frame's planes (volume.hip)
   SCR_VOL_OCC_RAYS, SCR_VOL_OCC, // the occluder bake: a chunk's p0 / p1 ray planes | its uint8 O words (volume.hip; the chunk's any-hit flags are SCR_GENERAL's, its
                    // per-brick table SCR_VOL_GRIDS', its counter word SCR_VOL_FUSED's)
+  SCR_VOL_GHOSTS,  // the fused frames' per-brick ghost face pointers beside SCR_VOL_BRICKS, for the kernels' CENTRAL instantiations (volume.hip volume_frame_fused)
   SCRATCH_COUNT
 };
 struct Knobs {

@@ -18,7 +18,10 @@
 //   gvt_hip_volume_frame_fused / k_volume_march_fused   the same frame over bricks of ONE grid in one launch: a lane carries its ray from brick to
 //                                           brick (volume_fused.inc); every other frame takes the loop
 //   gvt_hip_volume_frame_fused_shaded / k_volume_march_fused_shaded   ... and, where the caller allows it, frames whose bricks have isovalues,
-//                                           slice planes or lit fog: the same structure around the surface / lit visit (volume_fused_shaded.inc)
+//                                           slice planes or lit fog: the same structure around the surface / lit visit (volume_fused_shaded.inc).
+//                                           GVT_HIP_FUSED_CENTRAL / GVT_HIP_VOLUME_ALLOW_CENTRAL: the CENTRAL instantiations of this kernel
+//                                           and of the three shadowed ones below, for frames whose bricks all shade with central
+//                                           differences; a lane carries its brick's ghost pointer from brick to brick (FusedGhost)
 //   gvt_hip_volume_frame_shadowed / k_volume_march_fused_shadow   ... with the crossings lit only by the lights that reach them: a lane marches the
 //                                           shadow rays of its camera ray itself, from brick to brick (volume_fused_shadow.inc)
 //   gvt_hip_volume_light_grid_bake / k_volume_bake_light   the transmittance towards every light at every grid vertex, kept beside the samples
@@ -467,8 +470,8 @@ __device__ __forceinline__ void vol_write_back(const VolDev &V, RayPlanes q, uns
 // loaded -- they stay live across the look-up; with SURF a crossing is rendered first, as ever.  Without LIT: the march as it was.
 // CENTRAL (the _central entry points): the gradient of a crossed isovalue and of a lit sample is vol_gradient_central's, from H; nothing
 // else of the march reads H or depends on the kind.
-// KEEP IN STEP: k_volume_march_fused_shaded (volume_fused_shaded.inc) restates the per-sample steps of the loop below for SURF / LIT
-// without CENTRAL; a change to the visit here is a change there.
+// KEEP IN STEP: k_volume_march_fused_shaded (volume_fused_shaded.inc) restates the per-sample steps of the loop below for SURF / LIT,
+// with and without CENTRAL; a change to the visit here is a change there.
 template <typename T, bool SURF, bool CLIP, bool LIT, bool CENTRAL = false>
 __device__ __forceinline__ void volume_march_body(const VolDev &V, const MarchTable<SURF, LIT> &S, const GhostTable<CENTRAL> &H, RayPlanes q, unsigned n, const Mat4 &minv,
                                                   unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
@@ -1641,8 +1644,9 @@ bool same_bits(const void *a, const void *b, size_t bytes) { return std::memcmp(
 // Eligibility, decided per call from the volumes as they are now: bricks of ONE grid (global origin, spacing, dt, table, value range, skip
 // flag and minv equal as bits), one voxel type, no subgrids, and nothing the kernels allowed do not do.  allow = 0 (gvt_hip_volume_frame_fused):
 // no surfaces and no lit shading (the gradient kind is inert then).  GVT_HIP_FUSED_SURFACES / _LIT drop those two clauses; a frame that
-// has an isovalue or effective lit shading then needs the cell gradient on every brick, and what the bricks must share of surfaces and
-// lights is compared as bits too.  features: the bits of `allow` the frame needs (0: the plain fused kernel)
+// has an isovalue or effective lit shading then needs the cell gradient on every brick -- or, with GVT_HIP_FUSED_CENTRAL, ONE kind on
+// every brick -- and what the bricks must share of surfaces and lights is compared as bits too.  features: the bits of `allow` the frame
+// needs (0: the plain fused kernel; GVT_HIP_FUSED_CENTRAL: the bricks shade with CENTRAL, the kernels' CENTRAL instantiations run)
 bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, uint32_t allow, uint32_t &features, const char **why = nullptr) {
   features = 0;
   const auto no = [&](const char *clause) { // (why: the clause that fails, for the entry point that refuses such a frame instead of taking the loop)
@@ -1652,13 +1656,20 @@ bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_
   if (n_inst < 1 || n_inst > VOL_DEST_MAX) return no("between 1 and 256 bricks");
   const gvt_hip_volume *A = volumes[0];
   const bool surf = A->n_iso + A->n_pl > 0, lit = A->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && A->n_lights > 0;
+  int kind = -1; // the gradient kind of the first brick that reads a gradient (none yet)
   if ((surf && !(allow & GVT_HIP_FUSED_SURFACES)) || (lit && !(allow & GVT_HIP_FUSED_LIT))) return no("a feature the allow word lacks");
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     if (!B->has_tf) return no("a brick without a transfer function");
     if (!B->sub.empty()) return no("a brick with AMR subgrids");
     if ((B->n_iso + B->n_pl > 0) != surf || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0) != lit) return no("bricks that differ in having surfaces or lit shading");
-    if ((B->n_iso > 0 || lit) && B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL) return no("central gradients on a brick of a frame with an isovalue or lit shading"); // (planes alone read no gradient: the kind is inert)
+    if (B->n_iso > 0 || lit) { // (planes alone read no gradient: the kind is inert)
+      if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && !(allow & GVT_HIP_FUSED_CENTRAL)) return no("central gradients on a brick of a frame with an isovalue or lit shading");
+      if (kind >= 0 && B->grad != kind) return no("bricks that mix cell and central gradients in a frame with an isovalue or lit shading");
+      kind = B->grad;
+      // (the CENTRAL kernels take the global grid's size from volumes[0] alone: a brick that counts the grid otherwise would find its boundary elsewhere)
+      if (kind == GVT_HIP_VOLUME_GRADIENT_CENTRAL && !same_bits(B->gn, A->gn, sizeof(A->gn))) return no("central gradients on bricks of different grids (global counts)");
+    }
     if (B->vtype != A->vtype || B->skip != A->skip) return no("bricks of different voxel types or skip flags");
     if (!same_bits(B->go, A->go, sizeof(A->go)) || !same_bits(B->sp, A->sp, sizeof(A->sp)) || !same_bits(&B->dt, &A->dt, sizeof(float))) return no("bricks of different grids");
     if (!same_bits(&B->tf_lo, &A->tf_lo, sizeof(float)) || !same_bits(&B->tf_hi, &A->tf_hi, sizeof(float))) return no("bricks with different transfer functions");
@@ -1673,63 +1684,65 @@ bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_
       if (!same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights) || !same_bits(B->lcol, A->lcol, sizeof(A->lcol[0]) * (size_t)A->n_lights)) return no("bricks with different lights or shading");
     }
   }
-  features = (surf ? GVT_HIP_FUSED_SURFACES : 0u) | (lit ? GVT_HIP_FUSED_LIT : 0u);
+  features = (surf ? GVT_HIP_FUSED_SURFACES : 0u) | (lit ? GVT_HIP_FUSED_LIT : 0u) | (kind == GVT_HIP_VOLUME_GRADIENT_CENTRAL ? GVT_HIP_FUSED_CENTRAL : 0u);
   return true;
 }
 
-// the shaded fused kernel's instantiation for the frame's features (one of the three shaded combinations) and its by-value table
-template <typename VT, bool CLIP, typename... Args>
+// the shaded fused kernel's instantiation for the frame's features (one of the three shaded combinations) and its by-value table.
+// CENTRAL (here and in the launchers below): the instantiation, decided by the caller from GVT_HIP_FUSED_CENTRAL in the features; the
+// argument list then ends in the ghost table (FusedGhost), else in NoGhost
+template <typename VT, bool CLIP, bool CENTRAL, typename... Args>
 void launch_fused_shaded(uint32_t features, unsigned blocks, hipStream_t st, const gvt_hip_volume *V0, const Mat4 &M, VolDev U, Args... args) {
   const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0, lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  if (surf && lit) k_volume_march_fused_shaded<VT, CLIP, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
-  else if (surf) k_volume_march_fused_shaded<VT, CLIP, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
-  else k_volume_march_fused_shaded<VT, CLIP, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
+  if (surf && lit) k_volume_march_fused_shaded<VT, CLIP, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
+  else if (surf) k_volume_march_fused_shaded<VT, CLIP, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
+  else k_volume_march_fused_shaded<VT, CLIP, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
 }
 
 // the shadowed kernel's instantiation: clipped or not, lit fog or not (surfaces are implied)
-template <typename VT, typename... Args>
+template <typename VT, bool CENTRAL, typename... Args>
 void launch_fused_shadow(uint32_t features, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H, const FusedBrick *d_bricks,
                          TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
   const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
   const float *d_t = depth ? depth->d_t : nullptr;
   const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
-  if (depth && lit) k_volume_march_fused_shadow<VT, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
-  else if (depth) k_volume_march_fused_shadow<VT, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
-  else if (lit) k_volume_march_fused_shadow<VT, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
-  else k_volume_march_fused_shadow<VT, false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  if (depth && lit) k_volume_march_fused_shadow<VT, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  else if (depth) k_volume_march_fused_shadow<VT, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  else if (lit) k_volume_march_fused_shadow<VT, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+  else k_volume_march_fused_shadow<VT, false, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
 }
 
 // the fog-shadowed kernels' instantiation: clipped or not (lit fog is implied), with surfaces or -- the lean kernel -- without
-template <typename VT, typename... Args>
+template <typename VT, bool CENTRAL, typename... Args>
 void launch_fused_fog(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
                       const FusedBrick *d_bricks, const FogBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
   if (!(features & GVT_HIP_FUSED_SURFACES)) {
     const LightDev L = light_dev(V0, M);
-    if (depth) k_volume_march_fused_fog_lean<VT, true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
-    else k_volume_march_fused_fog_lean<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
+    if (depth) k_volume_march_fused_fog_lean<VT, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
+    else k_volume_march_fused_fog_lean<VT, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
     return;
   }
-  if (depth) k_volume_march_fused_fog<VT, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
-  else k_volume_march_fused_fog<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
+  if (depth) k_volume_march_fused_fog<VT, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
+  else k_volume_march_fused_fog<VT, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
 }
 
 // the mesh-shadowed kernels' instantiation: clipped or not, lit fog or not, with surfaces or -- the lean kernel, lit fog implied -- without
-template <typename VT, typename... Args>
+template <typename VT, bool CENTRAL, typename... Args>
 void launch_fused_mesh(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
                        const FusedBrick *d_bricks, const MeshBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
   const float *d_t = depth ? depth->d_t : nullptr;
   const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
   if (!(features & GVT_HIP_FUSED_SURFACES)) {
     const LightDev L = light_dev(V0, M);
-    if (depth) k_volume_march_fused_mesh_lean<VT, true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else k_volume_march_fused_mesh_lean<VT, false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+    if (depth) k_volume_march_fused_mesh_lean<VT, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else k_volume_march_fused_mesh_lean<VT, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
     return;
   }
   const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  if (depth && lit) k_volume_march_fused_mesh<VT, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-  else if (depth) k_volume_march_fused_mesh<VT, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-  else if (lit) k_volume_march_fused_mesh<VT, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-  else k_volume_march_fused_mesh<VT, false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  if (depth && lit) k_volume_march_fused_mesh<VT, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  else if (depth) k_volume_march_fused_mesh<VT, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  else if (lit) k_volume_march_fused_mesh<VT, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+  else k_volume_march_fused_mesh<VT, false, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
 }
 
 // the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
@@ -1763,12 +1776,17 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if ((fog || mesh) && !d_planes) return GVT_HIP_ERR_DEVICE;
   FogBrick *d_grids = (FogBrick *)d_planes;
   MeshBrick *d_mgrids = (MeshBrick *)d_planes;
-  static_assert((sizeof(FusedBrick) + sizeof(MeshBrick)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table and the grids' fit the staging block");
+  // the CENTRAL instantiations' ghost table: the bricks' face pointers, beside the records (FusedGhost, volume_fused.inc)
+  const bool central = (features & GVT_HIP_FUSED_CENTRAL) != 0;
+  const void **d_faces = central ? (const void **)scratch_get(SCR_VOL_GHOSTS, sizeof(void *) * n_inst) : nullptr;
+  if (central && !d_faces) return GVT_HIP_ERR_DEVICE;
+  static_assert((sizeof(FusedBrick) + sizeof(MeshBrick) + sizeof(void *)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table, the grids' and the ghosts' fit the staging block");
   void *stage = nullptr;
   if ((rc = pinned_stage_begin(&stage))) return rc;
   FusedBrick *h = (FusedBrick *)stage;
   FogBrick *hg = (FogBrick *)(h + VOL_DEST_MAX);
   MeshBrick *hm = (MeshBrick *)(h + VOL_DEST_MAX);
+  const void **hf = (const void **)(hm + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     FusedBrick R{};
@@ -1776,6 +1794,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
     R.mc = (features & GVT_HIP_FUSED_SURFACES) ? (const uint8_t *)B->d_cells : B->d_mc; // (the surface visit reads the per-cell words, never the skip bytes)
     if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
     else if (fog) hg[i].grid = B->d_lgrid;
+    if (central) hf[i] = B->d_ghost; // (null on a brick without an interior face: none of its layers is ever read)
     R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
     for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
     h[i] = R;
@@ -1783,6 +1802,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (mesh) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   else if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if (central) HIPCHK(hipMemcpyAsync(d_faces, hf, sizeof(void *) * n_inst, hipMemcpyHostToDevice, C.stream));
   if ((rc = pinned_stage_end())) return rc;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
   HIPCHK(hipMemsetAsync(d_stats, 0, n_words * sizeof(unsigned long long), C.stream));
@@ -1791,29 +1811,32 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
   const RayPlanes P = make_planes(q_cam->d_planes, q_cam->cap);
   const unsigned n_pix = (unsigned)(fb->w * fb->h);
+  const FusedGhost HG{ d_faces, volumes[0]->gn[0], volumes[0]->gn[1], volumes[0]->gn[2] };
   if (n)
     with_voxel_type(volumes[0]->vtype, [&](auto t) {
       using VT = decltype(t);
-      if (shadow && mesh) {
-        launch_fused_mesh<VT>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
-                              work, d_stats);
-        return;
-      }
-      if (shadow && fog) {
-        launch_fused_fog<VT>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_grids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work,
-                             d_stats);
-        return;
-      }
-      if (shadow) {
-        launch_fused_shadow<VT>(features, depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba,
-                                n_pix, work, d_stats);
-        return;
-      }
-      if (features) {
-        if (depth) launch_fused_shaded<VT, true>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
-                                                 (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
-        else launch_fused_shaded<VT, false>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, (const float *)nullptr, 0u,
-                                            fb->d_rgba, n_pix, work, d_stats);
+      // the shaded launches, for the kernels' CENTRAL instantiation (gh: FusedGhost) or the other (NoGhost)
+      const auto shaded = [&](auto central_c, auto gh) {
+        constexpr bool CENTRAL = decltype(central_c)::value;
+        if (shadow && mesh)
+          launch_fused_mesh<VT, CENTRAL>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba,
+                                         n_pix, work, d_stats, gh);
+        else if (shadow && fog)
+          launch_fused_fog<VT, CENTRAL>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_grids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
+                                        work, d_stats, gh);
+        else if (shadow)
+          launch_fused_shadow<VT, CENTRAL>(features, depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba,
+                                           n_pix, work, d_stats, gh);
+        else if (depth)
+          launch_fused_shaded<VT, true, CENTRAL>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
+                                                 (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats, gh);
+        else
+          launch_fused_shaded<VT, false, CENTRAL>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, (const float *)nullptr, 0u,
+                                                  fb->d_rgba, n_pix, work, d_stats, gh);
+      };
+      if (shadow || features) {
+        if (central) shaded(std::true_type{}, HG);
+        else shaded(std::false_type{}, NoGhost{});
         return;
       }
       if (depth) k_volume_march_fused<VT, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
@@ -1864,7 +1887,7 @@ extern "C" int gvt_hip_volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const 
 extern "C" int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
                                                  const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t allow,
                                                  gvt_hip_volume_fused_shaded_stats *stats) {
-  if (allow & ~(uint32_t)(GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT)) { set_error("volume_frame_fused_shaded: unknown allow bits %u", allow); return GVT_HIP_ERR_INVALID; }
+  if (allow & ~(uint32_t)(GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | GVT_HIP_FUSED_CENTRAL)) { set_error("volume_frame_fused_shaded: unknown allow bits %u", allow); return GVT_HIP_ERR_INVALID; }
   gvt_hip_volume_fused_shaded_stats S{};
   const int rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, allow, S);
   if (!rc && stats) *stats = S;
@@ -1924,7 +1947,8 @@ int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip
   int rc;
   if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
   if (!params) { set_error("%s: null params", fn); return GVT_HIP_ERR_INVALID; }
-  if (params->flags) { set_error("%s: unknown flag bits %u", fn, params->flags); return GVT_HIP_ERR_INVALID; }
+  if (params->flags & ~(uint32_t)GVT_HIP_VOLUME_ALLOW_CENTRAL) { set_error("%s: unknown flag bits %u", fn, params->flags); return GVT_HIP_ERR_INVALID; }
+  const uint32_t allow = GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | ((params->flags & GVT_HIP_VOLUME_ALLOW_CENTRAL) ? GVT_HIP_FUSED_CENTRAL : 0u);
   if (params->bias < 1 || params->bias > 64) { set_error("%s: bias %d, 1 to 64 lattice steps are allowed", fn, params->bias); return GVT_HIP_ERR_INVALID; }
   bool any_surface = false, any_light = false, any_lit = false;
   for (size_t i = 0; i < n_inst; i++) {
@@ -1938,11 +1962,11 @@ int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip
   const bool inert = !any_light || (!any_surface && !(fog && any_lit));
   bool fog_ran = false;
   if (inert) {
-    rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, S);
+    rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, allow, S);
   } else {
     uint32_t features = 0;
     const char *why = "";
-    if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, features, &why)) { // (no loop renders shadows: refused, nothing changed)
+    if (!fused_eligible(volumes, minv, n_inst, allow, features, &why)) { // (no loop renders shadows: refused, nothing changed)
       set_error("%s: the frame has %s and lights but is not eligible for the fused kernel: %s", fn, fog ? "surfaces or lit fog" : "surfaces", why);
       return GVT_HIP_ERR_INVALID;
     }
@@ -2004,22 +2028,25 @@ extern "C" int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *T, gvt_hip_volume 
 namespace {
 
 // What both bakes (the light grids' and the occluder grids') ask of their arguments and of their bricks.  fn: the entry point's name in the
-// error texts.  bake_args: no null pointer, 1 to VOL_DEST_MAX bricks that have a table, flags == 0
+// error texts.  bake_args: no null pointer, 1 to VOL_DEST_MAX bricks that have a table, flags 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL
 int bake_args(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const uint32_t *flags) {
   if (!volumes || !m || !minv || !flags) { set_error("%s: null argument", fn); return GVT_HIP_ERR_INVALID; }
   if (n_inst < 1 || n_inst > VOL_DEST_MAX) { set_error("%s: %zu bricks, 1 to %d are allowed", fn, n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
   for (size_t i = 0; i < n_inst; i++)
     if (!volumes[i] || !volumes[i]->has_tf) { set_error("%s: brick %zu is null or has no transfer function", fn, i); return GVT_HIP_ERR_INVALID; }
-  if (*flags) { set_error("%s: unknown flag bits %u", fn, *flags); return GVT_HIP_ERR_INVALID; }
+  if (*flags & ~(uint32_t)GVT_HIP_VOLUME_ALLOW_CENTRAL) { set_error("%s: unknown flag bits %u", fn, *flags); return GVT_HIP_ERR_INVALID; }
   return 0;
 }
 
 // ... bake_bricks: bricks of one grid that tile it, under one matrix, with equal surfaces and lights, at least one usable light, no
-// subgrids, the CENTRAL clause, at most 2^32 - 1 (vertex, light) pairs.  verts: the vertices summed over the bricks; usable: the lights' bits
-int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, uint64_t &verts, unsigned &usable) {
+// subgrids, the CENTRAL clause (flags: the params' word -- with GVT_HIP_VOLUME_ALLOW_CENTRAL bricks that are all CENTRAL pass; the bake's
+// rays march with shading NONE and read no gradient, so the planes do not depend on the kind), at most 2^32 - 1 (vertex, light) pairs.
+// verts: the vertices summed over the bricks; usable: the lights' bits
+int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, uint32_t flags, uint64_t &verts, unsigned &usable) {
   uint32_t features = 0;
   const char *why = "";
-  if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT, features, &why)) {
+  const bool allow_central = (flags & GVT_HIP_VOLUME_ALLOW_CENTRAL) != 0;
+  if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | (allow_central ? GVT_HIP_FUSED_CENTRAL : 0u), features, &why)) {
     set_error("%s: the bricks are not eligible for the fused kernels: %s", fn, why);
     return GVT_HIP_ERR_INVALID;
   }
@@ -2030,7 +2057,7 @@ int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, 
     const gvt_hip_volume *B = volumes[i];
     if (!same_bits(m + 16 * i, m, 16 * sizeof(float))) { set_error("%s: bricks under different matrices", fn); return GVT_HIP_ERR_INVALID; }
     if (!same_bits(B->gn, A->gn, sizeof(A->gn))) { set_error("%s: bricks of different grids (global counts)", fn); return GVT_HIP_ERR_INVALID; }
-    if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && B->n_iso > 0) { set_error("%s: central gradients on a brick of a frame with an isovalue", fn); return GVT_HIP_ERR_INVALID; }
+    if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && B->n_iso > 0 && !allow_central) { set_error("%s: central gradients on a brick of a frame with an isovalue", fn); return GVT_HIP_ERR_INVALID; }
     // (fused_eligible compares surfaces and lights only where the frame renders them: the bake needs them equal whatever the shading)
     if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float)) || !same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) ||
         !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) { set_error("%s: bricks with different surfaces", fn); return GVT_HIP_ERR_INVALID; }
@@ -2066,7 +2093,7 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
   if (params->bias < 1 || params->bias > 64) { set_error("volume_light_grid_bake: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
   uint64_t verts = 0;
   unsigned usable = 0;
-  if ((rc = bake_bricks("volume_light_grid_bake", volumes, m, minv, n_inst, verts, usable))) return rc;
+  if ((rc = bake_bricks("volume_light_grid_bake", volumes, m, minv, n_inst, params->flags, verts, usable))) return rc;
   const gvt_hip_volume *A = volumes[0];
   const ShadowDev H = shadow_dev(A, params->bias);
   const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
@@ -2236,7 +2263,7 @@ extern "C" int gvt_hip_volume_occluder_grid_bake(gvt_hip_volume *const *volumes,
     if (!meshes[i]) { set_error("volume_occluder_grid_bake: mesh instance %zu has no mesh", i); return GVT_HIP_ERR_INVALID; }
   uint64_t verts = 0;
   unsigned usable = 0;
-  if ((rc = bake_bricks("volume_occluder_grid_bake", volumes, m, minv, n_inst, verts, usable))) return rc;
+  if ((rc = bake_bricks("volume_occluder_grid_bake", volumes, m, minv, n_inst, params->flags, verts, usable))) return rc;
   const gvt_hip_volume *A = volumes[0];
   const ShadowDev H = shadow_dev(A, 1); // (the directions and their bits; the bias is the light grid's business)
   const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);

@@ -17,6 +17,22 @@ struct FusedBrick {
   float lo[3], hi[3];  // the vertex box, object space: read by vol_ray_range on entry, dead afterwards
 };
 static_assert(sizeof(FusedBrick) == 64, "four 16-byte loads per record");
+// ... and what the CENTRAL instantiations of the shaded, shadowed, fog and mesh kernels receive beside it (GVT_HIP_FUSED_CENTRAL,
+// GVT_HIP_VOLUME_ALLOW_CENTRAL): the bricks' ghost layers as a further device table of face pointers (gvt_hip_volume::d_ghost; null for a
+// brick without an interior face, whose layers are never read), indexed like the records and loaded where they are loaded -- the pointer
+// is part of the lane's brick state -- and the global grid's size, uniform, by value.  Every other instantiation receives NoGhost
+struct FusedGhost {
+  const void *const *faces;
+  int gnx, gny, gnz;
+};
+template <bool CENTRAL>
+using FusedGhostArg = std::conditional_t<CENTRAL, FusedGhost, NoGhost>;
+// the lane's ghost table: the uniform sizes from the argument, the pointer of no brick yet
+template <bool CENTRAL>
+__device__ __forceinline__ GhostTable<CENTRAL> fused_ghost_init(const FusedGhostArg<CENTRAL> &HG) {
+  if constexpr (CENTRAL) return GhostDev{ nullptr, HG.gnx, HG.gny, HG.gnz };
+  else return NoGhost{};
+}
 #define VOL_FUSED_STATS 4 // words of the launch's counters: samples marched, samples gathered, brick visits, rays deposited
 
 // the depth plane's word for ray idx: what k_vol_scatter (fresh == 2) gives the ray as t_max and GVT_HIP_RAY_CLIP, read again at every

@@ -1,6 +1,6 @@
 // volume_fused_fog.inc -- the fog-shadowed fused frame (gvt_hip_volume_frame_fog_shadowed; the contract: include/gvt_hip.h, "shadowed fog").
 // Included by volume.hip behind volume_light_grid.inc, which bakes the grids this kernel reads.
-//   k_volume_march_fused_fog<T, CLIP>   k_volume_march_fused_shadow<T, CLIP, true> with ONE change: a lit fog sample multiplies each light's
+//   k_volume_march_fused_fog<T, CLIP, CENTRAL>   k_volume_march_fused_shadow<T, CLIP, true, CENTRAL> with ONE change: a lit fog sample multiplies each light's
 //                                   n . l by the transmittance towards that light, interpolated from the baked grid G_j at the eight
 //                                   vertices of the sample's cell (the sample's fractions, vol_gather's nesting).  Crossings keep their
 //                                   exact in-kernel shadow rays.
@@ -8,12 +8,13 @@
 // is that kernel restated, for the reason that one restates its parents -- the kernels that exist are to stay what they are, instruction
 // for instruction.  The differences: LIT is always on; the brick's grid pointer travels beside its record, in a parallel device table
 // loaded where the record is loaded (FusedBrick is unchanged); the camera ray's lit sample is vol_accumulate_lit_fog's.
-//   k_volume_march_fused_fog_lean<T, CLIP>   the same change on k_volume_march_fused_shaded<T, CLIP, false, true>, for a frame WITHOUT
+//   k_volume_march_fused_fog_lean<T, CLIP, CENTRAL>   the same change on k_volume_march_fused_shaded<T, CLIP, false, true, CENTRAL>, for a frame WITHOUT
 //                                   surfaces: no crossing exists, so no shadow ray is ever cast and the park, the modes and the side masks
 //                                   fall away with their registers and their LDS.  Measured before it existed (profiles/
 //                                   volume_fog_shadows.txt, 3): the surface-capable kernel on a frame without surfaces took 1.40 to 1.46
 //                                   times the lit fused frame under a table that shades 0.1 % of the samples -- the kernel's shape, not
 //                                   the grid's reads.
+// CENTRAL: as in k_volume_march_fused_shadow -- the lane's ghost pointer is loaded beside the grid pointer, with every record.
 // G is read only inside the branch that shades (tc.w > 0, 0 < len < Inf), so skipping stays exact and samples_shaded does not move; A
 // never depends on G.
 
@@ -23,15 +24,16 @@ struct FogBrick {
 };
 
 // vol_accumulate_lit<T, false> with the transmittance per light: ndl_s = ndl * Tg (an unusable light: Tg = 1, nothing read)
-template <typename LT> // (SurfDev or LightDev)
-__device__ __forceinline__ unsigned vol_accumulate_lit_fog(const VolDev &V, const LT &L, unsigned usable, const float *__restrict__ grid, const int c[3], float v,
+template <typename T, bool CENTRAL, typename LT> // (LT: SurfDev or LightDev; CENTRAL: the gradient is vol_gradient_central's, from Hg)
+__device__ __forceinline__ unsigned vol_accumulate_lit_fog(const VolDev &V, const LT &L, const GhostTable<CENTRAL> &Hg, unsigned usable, const float *__restrict__ grid, const int c[3], float v,
                                                            const VolCorners &G, const float f[3], float C[3], float &A) {
   const float4 tc = vol_lookup(V, v);
   float rgb[3] = { tc.x, tc.y, tc.z };
   const bool shaded = tc.w > 0.f; // (false for NaN)
   if (shaded) {
     float g[3], sum[3] = { 0.f, 0.f, 0.f };
-    vol_gradient(V, G, f, g);
+    if constexpr (CENTRAL) vol_gradient_central<T>(V, Hg, c, G, f, g);
+    else vol_gradient(V, G, f, g);
     const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
     if (len > 0.f && len < INFINITY) { // (false for NaN)
       const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
@@ -58,11 +60,11 @@ __device__ __forceinline__ unsigned vol_accumulate_lit_fog(const VolDev &V, cons
   return shaded ? 1u : 0u;
 }
 
-template <typename T, bool CLIP>
+template <typename T, bool CLIP, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, SurfDev S, ShadowDev H, const FusedBrick *__restrict__ bricks, const FogBrick *__restrict__ grids, TopDev top, RayPlanes q,
                                                                       unsigned n, Mat4 minv, const float *__restrict__ clip_plane, unsigned n_clip,
                                                                       float *__restrict__ fb, unsigned n_pix, unsigned *__restrict__ work,
-                                                                      unsigned long long *__restrict__ stats) {
+                                                                      unsigned long long *__restrict__ stats, FusedGhostArg<CENTRAL> HG) {
   __shared__ float park[VOL_SHADOW_WORDS][VOL_BLOCK];
   float *const P = &park[0][threadIdx.x]; // the lane's column: word w at P[w * VOL_BLOCK]
   enum { P_K = 0, P_BRICK = 1, P_PREV = 2, P_C = 3, P_A = 6, P_TMIN = 7, P_T = 8 };
@@ -71,6 +73,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
   unsigned idx = 0;
   VolDev V = U;
   const float *grid = nullptr; // the lane's brick's planes
+  GhostTable<CENTRAL> Hl = fused_ghost_init<CENTRAL>(HG); // (CENTRAL only) the lane's brick's ghost layers: the pointer changes wherever the brick does
   int brick = -1;
   int mode = 0;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
@@ -157,6 +160,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
       if (next >= 0) {
         const FusedBrick R = bricks[next];
         grid = grids[next].grid;
+        if constexpr (CENTRAL) Hl.faces = HG.faces[next];
         V.vox = R.vox; V.mc = R.mc;
         V.nx = R.nx; V.ny = R.ny; V.nz = R.nz; V.ox = R.ox; V.oy = R.oy; V.oz = R.oz;
         for (int x = 0; x < 3; x++) { V.lo[x] = R.lo[x]; V.hi[x] = R.hi[x]; }
@@ -189,6 +193,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
         V.vox = nullptr; V.mc = nullptr;
         grid = nullptr;
+        if constexpr (CENTRAL) Hl.faces = nullptr;
         V.nx = V.ny = V.nz = V.ox = V.oy = V.oz = 0;
         for (int x = 0; x < 3; x++) { o[x] = 0.f; d[x] = 0.f; }
         k = 0; k_hi = -1; k_last = -1; k_carry = -1; prev = -1;
@@ -262,6 +267,35 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
         prev = (int)sides;
         const bool have_T = mode < 0; // (the re-run of the parked sample, and that sample alone)
         if (have_T) mode = 0;
+        if constexpr (CENTRAL) { // the same loop with the gradient of the ghost table (stated apart: the loop below is to compile to what it was)
+          if (crossed) {
+            float gc[3] = { 0.f, 0.f, 0.f }; // the isovalues a camera ray crosses here share one gradient, fetched once, ahead of the loop
+            if (mode <= 0 && (crossed & ((1u << S.n_iso) - 1u))) vol_gradient_central<T>(V, Hl, c, G, f, gc);
+            while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+              const int i = __ffs((int)crossed) - 1;
+              crossed &= crossed - 1u;
+              if (mode > 0) { // the shadow ray: opacity alone
+                s_crossed++;
+                A = A + (1.f - A) * S.alpha;
+                continue;
+              }
+              n_crossed++;
+              float4 col;
+              float g[3];
+              if (i < S.n_iso) {
+                g[0] = gc[0]; g[1] = gc[1]; g[2] = gc[2];
+                col = vol_lookup(V, S.iso[i]);
+              } else {
+                const float4 Q = S.plane[i - S.n_iso];
+                g[0] = Q.x; g[1] = Q.y; g[2] = Q.z;
+                col = vol_lookup(V, v);
+              }
+              if (have_T) surf_composite_shadowed(S, col, g, P + P_T * VOL_BLOCK, C, A);
+              else surf_composite(S, col, g, C, A); // (no usable light: every T_j = 1)
+            }
+            if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
+          }
+        } else
         if (crossed) {
           while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) { // (at most 16 bits are set: sides and prev stay below 2^16)
             const int i = __ffs((int)crossed) - 1;
@@ -288,7 +322,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
           if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
         }
         if (mode > 0) vol_accumulate(V, v, C, A); // (shading NONE; the colour is dead)
-        else n_shaded += vol_accumulate_lit_fog(V, S, H.usable, grid, c, v, G, f, C, A);
+        else n_shaded += vol_accumulate_lit_fog<T, CENTRAL>(V, S, Hl, H.usable, grid, c, v, G, f, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }
@@ -333,16 +367,17 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
 
 // KEEP IN STEP with k_volume_march_fused_shaded<T, CLIP, false, true>: that kernel restated, with the brick's planes loaded beside its
 // record and vol_accumulate_lit_fog in vol_accumulate_lit's place
-template <typename T, bool CLIP>
+template <typename T, bool CLIP, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDev U, LightDev S, unsigned usable, const FusedBrick *__restrict__ bricks,
                                                                            const FogBrick *__restrict__ grids, TopDev top, RayPlanes q, unsigned n, Mat4 minv,
                                                                            const float *__restrict__ clip_plane, unsigned n_clip, float *__restrict__ fb, unsigned n_pix,
-                                                                           unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
+                                                                           unsigned *__restrict__ work, unsigned long long *__restrict__ stats, FusedGhostArg<CENTRAL> HG) {
   bool active = false, exhausted = false;
   bool hop = false;  // the lane's ray is between two bricks: fresh from the list (brick < 0) or at the end of a visit
   unsigned idx = 0;
   VolDev V = U;      // the lane's brick: U with the record's fields
   const float *grid = nullptr; // ... and its planes
+  GhostTable<CENTRAL> Hl = fused_ghost_init<CENTRAL>(HG); // (CENTRAL only) the lane's brick's ghost layers: the pointer changes wherever the brick does
   int brick = -1;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
   int k = 0, k_hi = -1, k_last = -1;
@@ -386,6 +421,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDe
       if (next >= 0) {
         const FusedBrick R = bricks[next];
         grid = grids[next].grid;
+        if constexpr (CENTRAL) Hl.faces = HG.faces[next];
         V.vox = R.vox; V.mc = R.mc;
         V.nx = R.nx; V.ny = R.ny; V.nz = R.nz; V.ox = R.ox; V.oy = R.oy; V.oz = R.oz;
         for (int x = 0; x < 3; x++) { V.lo[x] = R.lo[x]; V.hi[x] = R.hi[x]; }
@@ -404,6 +440,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDe
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
         V.vox = nullptr; V.mc = nullptr;
         grid = nullptr;
+        if constexpr (CENTRAL) Hl.faces = nullptr;
         V.nx = V.ny = V.nz = V.ox = V.oy = V.oz = 0;
         for (int x = 0; x < 3; x++) { o[x] = 0.f; d[x] = 0.f; }
         k = 0; k_hi = -1; k_last = -1;
@@ -441,7 +478,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDe
         n_gathered++;
         VolCorners G;
         const float v = vol_gather<T>(V, c, f, G);
-        n_shaded += vol_accumulate_lit_fog(V, S, usable, grid, c, v, G, f, C, A);
+        n_shaded += vol_accumulate_lit_fog<T, CENTRAL>(V, S, Hl, usable, grid, c, v, G, f, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }

@@ -1,15 +1,16 @@
 // volume_fused_mesh.inc -- the mesh-shadowed fused frame (gvt_hip_volume_frame_mesh_shadowed; the contract: include/gvt_hip.h, "meshes
 // shadowing the volume").  Included by volume.hip behind volume_occluder_grid.inc, which bakes the uint8 planes these kernels read.
-//   k_volume_march_fused_mesh<T, CLIP, LIT>   k_volume_march_fused_shadow<T, CLIP, LIT> with the fog kernel's change (LIT: a lit fog sample
+//   k_volume_march_fused_mesh<T, CLIP, LIT, CENTRAL>   k_volume_march_fused_shadow<T, CLIP, LIT, CENTRAL> with the fog kernel's change (LIT: a lit fog sample
 //                                   multiplies n . l by Tg, interpolated from the light grid) and ONE more: wherever a transmittance is
 //                                   used it is multiplied by Og, the occluder grid interpolated at the sample's cell.  For the fog that is
 //                                   Tg * Og inside the shading branch; for a crossing the parked camera ray multiplies its T words in LDS
 //                                   by Og when it re-runs its sample, before the first crossing of that sample is composited.
-//   k_volume_march_fused_mesh_lean<T, CLIP>   the same change on k_volume_march_fused_fog_lean, for a frame WITHOUT surfaces.
+//   k_volume_march_fused_mesh_lean<T, CLIP, CENTRAL>   the same change on k_volume_march_fused_fog_lean, for a frame WITHOUT surfaces.
 // KEEP IN STEP with k_volume_march_fused_shadow, k_volume_march_fused_fog and k_volume_march_fused_fog_lean: the kernels below are those
 // kernels restated, for the reason they restate their parents -- the kernels that exist are to stay what they are, instruction for
 // instruction.  The differences: both plane pointers of the brick travel beside its record in a parallel device table (MeshBrick; the
 // light grid's is null and never read without LIT); the T words; vol_accumulate_lit_mesh.
+// CENTRAL: as in k_volume_march_fused_shadow -- the lane's ghost pointer is loaded beside the plane pointers, with every record.
 // O is read only where G or T_j is used, so skipping stays exact and no counter moves; A never depends on O; no shadow ray is cast or
 // skipped because of O.
 
@@ -30,15 +31,16 @@ __device__ __forceinline__ float occluder_lerp(const VolDev &V, const uint8_t *_
 }
 
 // vol_accumulate_lit_fog with the occluder grid: ndl_s = ndl * (Tg * Og) (an unusable light: both 1, nothing read)
-template <typename LT> // (SurfDev or LightDev)
-__device__ __forceinline__ unsigned vol_accumulate_lit_mesh(const VolDev &V, const LT &L, unsigned usable, const float *__restrict__ grid, const uint8_t *__restrict__ occ,
+template <typename T, bool CENTRAL, typename LT> // (LT: SurfDev or LightDev; CENTRAL: the gradient is vol_gradient_central's, from Hg)
+__device__ __forceinline__ unsigned vol_accumulate_lit_mesh(const VolDev &V, const LT &L, const GhostTable<CENTRAL> &Hg, unsigned usable, const float *__restrict__ grid, const uint8_t *__restrict__ occ,
                                                             const int c[3], float v, const VolCorners &G, const float f[3], float C[3], float &A) {
   const float4 tc = vol_lookup(V, v);
   float rgb[3] = { tc.x, tc.y, tc.z };
   const bool shaded = tc.w > 0.f; // (false for NaN)
   if (shaded) {
     float g[3], sum[3] = { 0.f, 0.f, 0.f };
-    vol_gradient(V, G, f, g);
+    if constexpr (CENTRAL) vol_gradient_central<T>(V, Hg, c, G, f, g);
+    else vol_gradient(V, G, f, g);
     const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
     if (len > 0.f && len < INFINITY) { // (false for NaN)
       const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
@@ -68,11 +70,11 @@ __device__ __forceinline__ unsigned vol_accumulate_lit_mesh(const VolDev &V, con
   return shaded ? 1u : 0u;
 }
 
-template <typename T, bool CLIP, bool LIT>
+template <typename T, bool CLIP, bool LIT, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U, SurfDev S, ShadowDev H, const FusedBrick *__restrict__ bricks, const MeshBrick *__restrict__ grids, TopDev top, RayPlanes q,
                                                                        unsigned n, Mat4 minv, const float *__restrict__ clip_plane, unsigned n_clip,
                                                                        float *__restrict__ fb, unsigned n_pix, unsigned *__restrict__ work,
-                                                                       unsigned long long *__restrict__ stats) {
+                                                                       unsigned long long *__restrict__ stats, FusedGhostArg<CENTRAL> HG) {
   __shared__ float park[VOL_SHADOW_WORDS][VOL_BLOCK];
   float *const P = &park[0][threadIdx.x]; // the lane's column: word w at P[w * VOL_BLOCK]
   enum { P_K = 0, P_BRICK = 1, P_PREV = 2, P_C = 3, P_A = 6, P_TMIN = 7, P_T = 8 };
@@ -81,6 +83,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U,
   unsigned idx = 0;
   VolDev V = U;
   MeshBrick grid{ nullptr, nullptr }; // the lane's brick's planes: the light grid's (LIT only) and the occluder grid's
+  GhostTable<CENTRAL> Hl = fused_ghost_init<CENTRAL>(HG); // (CENTRAL only) the lane's brick's ghost layers: the pointer changes wherever the brick does
   int brick = -1;
   int mode = 0;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
@@ -167,6 +170,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U,
       if (next >= 0) {
         const FusedBrick R = bricks[next];
         grid = grids[next];
+        if constexpr (CENTRAL) Hl.faces = HG.faces[next];
         V.vox = R.vox; V.mc = R.mc;
         V.nx = R.nx; V.ny = R.ny; V.nz = R.nz; V.ox = R.ox; V.oy = R.oy; V.oz = R.oz;
         for (int x = 0; x < 3; x++) { V.lo[x] = R.lo[x]; V.hi[x] = R.hi[x]; }
@@ -199,6 +203,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U,
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
         V.vox = nullptr; V.mc = nullptr;
         grid = MeshBrick{ nullptr, nullptr };
+        if constexpr (CENTRAL) Hl.faces = nullptr;
         V.nx = V.ny = V.nz = V.ox = V.oy = V.oz = 0;
         for (int x = 0; x < 3; x++) { o[x] = 0.f; d[x] = 0.f; }
         k = 0; k_hi = -1; k_last = -1; k_carry = -1; prev = -1;
@@ -278,6 +283,35 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U,
               P[(P_T + j) * VOL_BLOCK] = P[(P_T + j) * VOL_BLOCK] * occluder_lerp(V, grid.occ, l, c, f);
               l++;
             }
+        if constexpr (CENTRAL) { // the same loop with the gradient of the ghost table (stated apart: the loop below is to compile to what it was)
+          if (crossed) {
+            float gc[3] = { 0.f, 0.f, 0.f }; // the isovalues a camera ray crosses here share one gradient, fetched once, ahead of the loop
+            if (mode <= 0 && (crossed & ((1u << S.n_iso) - 1u))) vol_gradient_central<T>(V, Hl, c, G, f, gc);
+            while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+              const int i = __ffs((int)crossed) - 1;
+              crossed &= crossed - 1u;
+              if (mode > 0) { // the shadow ray: opacity alone
+                s_crossed++;
+                A = A + (1.f - A) * S.alpha;
+                continue;
+              }
+              n_crossed++;
+              float4 col;
+              float g[3];
+              if (i < S.n_iso) {
+                g[0] = gc[0]; g[1] = gc[1]; g[2] = gc[2];
+                col = vol_lookup(V, S.iso[i]);
+              } else {
+                const float4 Q = S.plane[i - S.n_iso];
+                g[0] = Q.x; g[1] = Q.y; g[2] = Q.z;
+                col = vol_lookup(V, v);
+              }
+              if (have_T) surf_composite_shadowed(S, col, g, P + P_T * VOL_BLOCK, C, A);
+              else surf_composite(S, col, g, C, A); // (no usable light: every T_j = 1)
+            }
+            if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
+          }
+        } else
         if (crossed) {
           while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) { // (at most 16 bits are set: sides and prev stay below 2^16)
             const int i = __ffs((int)crossed) - 1;
@@ -305,7 +339,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U,
         }
         if constexpr (LIT) {
           if (mode > 0) vol_accumulate(V, v, C, A); // (shading NONE; the colour is dead)
-          else n_shaded += vol_accumulate_lit_mesh(V, S, H.usable, grid.grid, grid.occ, c, v, G, f, C, A);
+          else n_shaded += vol_accumulate_lit_mesh<T, CENTRAL>(V, S, Hl, H.usable, grid.grid, grid.occ, c, v, G, f, C, A);
         } else {
           vol_accumulate(V, v, C, A);
         }
@@ -354,16 +388,17 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh(VolDev U,
 
 // KEEP IN STEP with k_volume_march_fused_fog_lean (and through it with k_volume_march_fused_shaded<T, CLIP, false, true>): that kernel
 // restated, with both of the brick's plane pointers loaded beside its record and vol_accumulate_lit_mesh in vol_accumulate_lit_fog's place
-template <typename T, bool CLIP>
+template <typename T, bool CLIP, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh_lean(VolDev U, LightDev S, unsigned usable, const FusedBrick *__restrict__ bricks,
                                                                             const MeshBrick *__restrict__ grids, TopDev top, RayPlanes q, unsigned n, Mat4 minv,
                                                                             const float *__restrict__ clip_plane, unsigned n_clip, float *__restrict__ fb, unsigned n_pix,
-                                                                           unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
+                                                                           unsigned *__restrict__ work, unsigned long long *__restrict__ stats, FusedGhostArg<CENTRAL> HG) {
   bool active = false, exhausted = false;
   bool hop = false;  // the lane's ray is between two bricks: fresh from the list (brick < 0) or at the end of a visit
   unsigned idx = 0;
   VolDev V = U;      // the lane's brick: U with the record's fields
   MeshBrick grid{ nullptr, nullptr }; // ... and its planes
+  GhostTable<CENTRAL> Hl = fused_ghost_init<CENTRAL>(HG); // (CENTRAL only) the lane's brick's ghost layers: the pointer changes wherever the brick does
   int brick = -1;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
   int k = 0, k_hi = -1, k_last = -1;
@@ -407,6 +442,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh_lean(VolD
       if (next >= 0) {
         const FusedBrick R = bricks[next];
         grid = grids[next];
+        if constexpr (CENTRAL) Hl.faces = HG.faces[next];
         V.vox = R.vox; V.mc = R.mc;
         V.nx = R.nx; V.ny = R.ny; V.nz = R.nz; V.ox = R.ox; V.oy = R.oy; V.oz = R.oz;
         for (int x = 0; x < 3; x++) { V.lo[x] = R.lo[x]; V.hi[x] = R.hi[x]; }
@@ -425,6 +461,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh_lean(VolD
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
         V.vox = nullptr; V.mc = nullptr;
         grid = MeshBrick{ nullptr, nullptr };
+        if constexpr (CENTRAL) Hl.faces = nullptr;
         V.nx = V.ny = V.nz = V.ox = V.oy = V.oz = 0;
         for (int x = 0; x < 3; x++) { o[x] = 0.f; d[x] = 0.f; }
         k = 0; k_hi = -1; k_last = -1;
@@ -462,7 +499,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh_lean(VolD
         n_gathered++;
         VolCorners G;
         const float v = vol_gather<T>(V, c, f, G);
-        n_shaded += vol_accumulate_lit_mesh(V, S, usable, grid.grid, grid.occ, c, v, G, f, C, A);
+        n_shaded += vol_accumulate_lit_mesh<T, CENTRAL>(V, S, Hl, usable, grid.grid, grid.occ, c, v, G, f, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }

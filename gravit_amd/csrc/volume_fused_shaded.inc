@@ -1,7 +1,10 @@
 // volume_fused_shaded.inc -- the fused frame for bricks that have isovalues / slice planes or lit fog (gvt_hip_volume_frame_fused_shaded).
 // Included by volume.hip behind volume_fused.inc, whose FusedBrick record, counters and fused_clip it uses.
-//   k_volume_march_fused_shaded<T, CLIP, SURF, LIT>   k_volume_march_fused's structure (persistent waves, lane refill, the "between two
-//                                   bricks" block, a VOL_STEP inner loop) around the visit of volume_march_body<T, SURF, CLIP, LIT, false>
+//   k_volume_march_fused_shaded<T, CLIP, SURF, LIT, CENTRAL>   k_volume_march_fused's structure (persistent waves, lane refill, the "between
+//                                   two bricks" block, a VOL_STEP inner loop) around the visit of volume_march_body<T, SURF, CLIP, LIT, CENTRAL>
+// CENTRAL (GVT_HIP_FUSED_CENTRAL: every brick's gradient kind is CENTRAL): the gradient of a crossed isovalue and of a lit sample is
+// vol_gradient_central's, from the lane's ghost table (FusedGhost, volume_fused.inc); nothing else reads it.  Without CENTRAL the kernel
+// is what it was before the parameter existed, instruction for instruction (profiles/volume_fused_central.txt, 1).
 // KEEP IN STEP with volume_march_body (volume.hip): the visit below restates its per-sample steps -- the sides, the skip decision on the
 // per-cell word, surf_planes_clear, the crossing loop, the lit accumulation -- through the same device functions, in the same order.
 // They are restated, not hoisted: the march kernels of volume.hip are to stay what they were, instruction for instruction
@@ -19,16 +22,17 @@
 // them as bits) and travel by value, as in k_volume_march_surf; S.cells is not read here.
 #define VOL_FUSED_SHADED_STATS 6 // VOL_FUSED_STATS' four words, then surface crossings rendered and samples shaded
 
-template <typename T, bool CLIP, bool SURF, bool LIT>
+template <typename T, bool CLIP, bool SURF, bool LIT, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded(VolDev U, MarchTable<SURF, LIT> S, const FusedBrick *__restrict__ bricks, TopDev top, RayPlanes q,
                                                                          unsigned n, Mat4 minv, const float *__restrict__ clip_plane, unsigned n_clip,
                                                                          float *__restrict__ fb, unsigned n_pix, unsigned *__restrict__ work,
-                                                                         unsigned long long *__restrict__ stats) {
+                                                                         unsigned long long *__restrict__ stats, FusedGhostArg<CENTRAL> HG) {
   static_assert(SURF || LIT, "the plain frame is k_volume_march_fused's");
   bool active = false, exhausted = false;
   bool hop = false;  // the lane's ray is between two bricks: fresh from the list (brick < 0) or at the end of a visit
   unsigned idx = 0;
   VolDev V = U;      // the lane's brick: U with the record's fields (SURF: V.mc points at the brick's per-cell words)
+  GhostTable<CENTRAL> Hl = fused_ghost_init<CENTRAL>(HG); // ... and, CENTRAL only, its ghost layers: the pointer changes with the brick
   int brick = -1;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
   int k = 0, k_hi = -1, k_last = -1, k_carry = -1, prev = -1; // (k_carry, prev, n_crossed: SURF only)
@@ -76,6 +80,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded(VolDev 
       if (A < GVT_HIP_VOLUME_OPAQUE_A) next = vol_next(top, brick, wo, wd, t_min, clip, t_clip);
       if (next >= 0) {
         const FusedBrick R = bricks[next];
+        if constexpr (CENTRAL) Hl.faces = HG.faces[next];
         V.vox = R.vox; V.mc = R.mc;
         V.nx = R.nx; V.ny = R.ny; V.nz = R.nz; V.ox = R.ox; V.oy = R.oy; V.oz = R.oz;
         for (int x = 0; x < 3; x++) { V.lo[x] = R.lo[x]; V.hi[x] = R.hi[x]; }
@@ -94,6 +99,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded(VolDev 
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
         V.vox = nullptr; V.mc = nullptr;
+        if constexpr (CENTRAL) Hl.faces = nullptr;
         V.nx = V.ny = V.nz = V.ox = V.oy = V.oz = 0;
         for (int x = 0; x < 3; x++) { o[x] = 0.f; d[x] = 0.f; }
         k = 0; k_hi = -1; k_last = -1; k_carry = -1; prev = -1;
@@ -102,7 +108,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded(VolDev 
     }
     n_visits += (unsigned)__popcll(ballot64(entered));
     n_deposits += (unsigned)__popcll(ballot64(deposited));
-    // ---- the visit: volume_march_body<T, SURF, CLIP, LIT, false>'s, step for step (KEEP IN STEP; `seen` there is k_last >= 0 here)
+    // ---- the visit: volume_march_body<T, SURF, CLIP, LIT, CENTRAL>'s, step for step (KEEP IN STEP; `seen` there is k_last >= 0 here)
     if (active) {
       bool done = false;
       for (int s = 0; s < VOL_STEP; s++) {
@@ -153,6 +159,25 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded(VolDev 
             if (v >= S.iso[i]) sides |= 1u << i;
           unsigned crossed = prev < 0 ? 0u : (sides ^ (unsigned)prev);
           prev = (int)sides;
+          if constexpr (CENTRAL) { // the same loop with the gradient of the ghost table (stated apart: the loop below is to compile to what it was)
+            if (crossed) {
+              float gc[3] = { 0.f, 0.f, 0.f }; // the isovalues crossed here share one gradient, fetched once, ahead of the loop, as in the body
+              if (crossed & ((1u << S.n_iso) - 1u)) vol_gradient_central<T>(V, Hl, c, G, f, gc);
+              while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+                const int i = __ffs((int)crossed) - 1;
+                crossed &= crossed - 1u;
+                n_crossed++;
+                if (i < S.n_iso) {
+                  surf_composite(S, vol_lookup(V, S.iso[i]), gc, C, A);
+                } else {
+                  const float4 P = S.plane[i - S.n_iso];
+                  const float g[3] = { P.x, P.y, P.z };
+                  surf_composite(S, vol_lookup(V, v), g, C, A);
+                }
+              }
+              if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
+            }
+          } else
           if (crossed) {
             while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) { // (at most 16 bits are set: sides and prev stay below 2^16)
               const int i = __ffs((int)crossed) - 1;
@@ -171,7 +196,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded(VolDev 
             if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
           }
         }
-        if constexpr (LIT) n_shaded += vol_accumulate_lit<T, false>(V, S, NoGhost{}, c, v, G, f, C, A);
+        if constexpr (LIT) n_shaded += vol_accumulate_lit<T, CENTRAL>(V, S, Hl, c, v, G, f, C, A);
         else vol_accumulate(V, v, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }

@@ -1,6 +1,6 @@
 // volume_fused_shadow.inc -- the shadowed fused frame (gvt_hip_volume_frame_shadowed; the contract: include/gvt_hip.h, "shadowed surfaces").
 // Included by volume.hip behind volume_fused_shaded.inc, whose structure it has and whose counters it extends.
-//   k_volume_march_fused_shadow<T, CLIP, LIT>   k_volume_march_fused_shaded<T, CLIP, true, LIT> in which "shadow ray" is a MODE OF THE LANE:
+//   k_volume_march_fused_shadow<T, CLIP, LIT, CENTRAL>   k_volume_march_fused_shaded<T, CLIP, true, LIT, CENTRAL> in which "shadow ray" is a MODE OF THE LANE:
 //                                   a camera ray that meets a sample with a crossing parks itself, walks one shadow ray per usable light
 //                                   through the same "between two bricks" block and the same VOL_STEP loop as its neighbours, and then
 //                                   re-runs the sample with the transmittances in hand.  One writer per pixel, as ever.
@@ -18,6 +18,10 @@
 // not parked is recomputed on the way back: the brick's record is loaded again and vol_ray_range gives o, d and k_hi again from the
 // list's words, which no shadow ray has touched.  The re-run of sample k then takes every decision it took (the skip word and prev are
 // the same), so it arrives at the crossing; what it had counted on the first pass is taken back when it parks.
+//
+// CENTRAL (GVT_HIP_VOLUME_ALLOW_CENTRAL and CENTRAL bricks): the g of a camera ray's crossed isovalue and lit sample is
+// vol_gradient_central's.  A shadow ray reads no gradient, but it changes the lane's brick, so the lane's ghost pointer (FusedGhost,
+// volume_fused.inc) is loaded with EVERY record, the one the camera ray returns to included.  T_j, the counters and A do not depend on it.
 //
 // Termination: a shadow ray's visits are bounded like a camera ray's (vol_next's progress grows from hop to hop, a visit walks at most
 // 2^22 positions); a camera ray casts at most (its samples with a crossing) x 8 of them, and each such sample is re-run once; no lane
@@ -51,11 +55,11 @@ __device__ inline void surf_composite_shadowed(const SurfDev &S, float4 c, const
   A = A + f;
 }
 
-template <typename T, bool CLIP, bool LIT>
+template <typename T, bool CLIP, bool LIT, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev U, SurfDev S, ShadowDev H, const FusedBrick *__restrict__ bricks, TopDev top, RayPlanes q,
                                                                          unsigned n, Mat4 minv, const float *__restrict__ clip_plane, unsigned n_clip,
                                                                          float *__restrict__ fb, unsigned n_pix, unsigned *__restrict__ work,
-                                                                         unsigned long long *__restrict__ stats) {
+                                                                         unsigned long long *__restrict__ stats, FusedGhostArg<CENTRAL> HG) {
   __shared__ float park[VOL_SHADOW_WORDS][VOL_BLOCK];
   float *const P = &park[0][threadIdx.x]; // the lane's column: word w at P[w * VOL_BLOCK]
   enum { P_K = 0, P_BRICK = 1, P_PREV = 2, P_C = 3, P_A = 6, P_TMIN = 7, P_T = 8 };
@@ -63,6 +67,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
   bool hop = false;
   unsigned idx = 0;
   VolDev V = U;
+  GhostTable<CENTRAL> Hl = fused_ghost_init<CENTRAL>(HG); // (CENTRAL only) the lane's brick's ghost layers: the pointer changes wherever the brick does
   int brick = -1;
   int mode = 0;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
@@ -148,6 +153,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
       }
       if (next >= 0) {
         const FusedBrick R = bricks[next];
+        if constexpr (CENTRAL) Hl.faces = HG.faces[next]; // (a shadow ray's brick, or -- resume -- the parked camera ray's again)
         V.vox = R.vox; V.mc = R.mc;
         V.nx = R.nx; V.ny = R.ny; V.nz = R.nz; V.ox = R.ox; V.oy = R.oy; V.oz = R.oz;
         for (int x = 0; x < 3; x++) { V.lo[x] = R.lo[x]; V.hi[x] = R.hi[x]; }
@@ -179,6 +185,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
         V.vox = nullptr; V.mc = nullptr;
+        if constexpr (CENTRAL) Hl.faces = nullptr;
         V.nx = V.ny = V.nz = V.ox = V.oy = V.oz = 0;
         for (int x = 0; x < 3; x++) { o[x] = 0.f; d[x] = 0.f; }
         k = 0; k_hi = -1; k_last = -1; k_carry = -1; prev = -1;
@@ -252,6 +259,35 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
         prev = (int)sides;
         const bool have_T = mode < 0; // (the re-run of the parked sample, and that sample alone)
         if (have_T) mode = 0;
+        if constexpr (CENTRAL) { // the same loop with the gradient of the ghost table (stated apart: the loop below is to compile to what it was)
+          if (crossed) {
+            float gc[3] = { 0.f, 0.f, 0.f }; // the isovalues a camera ray crosses here share one gradient, fetched once, ahead of the loop
+            if (mode <= 0 && (crossed & ((1u << S.n_iso) - 1u))) vol_gradient_central<T>(V, Hl, c, G, f, gc);
+            while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+              const int i = __ffs((int)crossed) - 1;
+              crossed &= crossed - 1u;
+              if (mode > 0) { // the shadow ray: opacity alone
+                s_crossed++;
+                A = A + (1.f - A) * S.alpha;
+                continue;
+              }
+              n_crossed++;
+              float4 col;
+              float g[3];
+              if (i < S.n_iso) {
+                g[0] = gc[0]; g[1] = gc[1]; g[2] = gc[2];
+                col = vol_lookup(V, S.iso[i]);
+              } else {
+                const float4 Q = S.plane[i - S.n_iso];
+                g[0] = Q.x; g[1] = Q.y; g[2] = Q.z;
+                col = vol_lookup(V, v);
+              }
+              if (have_T) surf_composite_shadowed(S, col, g, P + P_T * VOL_BLOCK, C, A);
+              else surf_composite(S, col, g, C, A); // (no usable light: every T_j = 1)
+            }
+            if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
+          }
+        } else
         if (crossed) {
           while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) { // (at most 16 bits are set: sides and prev stay below 2^16)
             const int i = __ffs((int)crossed) - 1;
@@ -279,7 +315,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
         }
         if constexpr (LIT) {
           if (mode > 0) vol_accumulate(V, v, C, A); // (shading NONE; the colour is dead)
-          else n_shaded += vol_accumulate_lit<T, false>(V, S, NoGhost{}, c, v, G, f, C, A);
+          else n_shaded += vol_accumulate_lit<T, CENTRAL>(V, S, Hl, c, v, G, f, C, A);
         } else {
           vol_accumulate(V, v, C, A);
         }

@@ -564,6 +564,10 @@ class VolumeTracer:
     one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop.
     fused_shaded (with fused): frame() goes through gvt_hip_volume_frame_fused_shaded with both bits (fused_allow), so frames with
     isovalues, slice planes or lit fog are fused too; without it such frames take the loop, as ever.
+    fused_central: fused_allow gains capi.FUSED_CENTRAL, and every VolumeShadowParams, VolumeLightGridParams and VolumeOccluderParams the
+    tracer builds carries capi.VOLUME_ALLOW_CENTRAL -- frames whose bricks all have set_gradient("central") are fused, shadowed and baked
+    too (the kernels' CENTRAL instantiations; the image is the loop's in every bit where a loop exists).  Without it (the default) such a
+    frame takes the loop under fused_shaded and is refused by the shadowed frames and the bakes, as ever.
     shadows: frame() goes through gvt_hip_volume_frame_shadowed whatever fused says -- a crossing is lit only by the lights that reach it,
     a shadow ray per light marched inside the one launch; shadow_bias = the lattice index of a shadow ray's first sample (1 .. 64; 2 is
     a choice, not a measurement).  A frame that has surfaces and lights but cannot be fused is refused (GvtHipError): no loop renders
@@ -579,7 +583,7 @@ class VolumeTracer:
     again after the scene changed.  A frame that needs a grid and has none is refused (GvtHipError)."""
 
     def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2,
-                 fog_shadows=False, fog_bias=1, mesh_shadows=False):
+                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -605,7 +609,9 @@ class VolumeTracer:
         self.calls = 0
         self.fused = bool(fused)
         self.fused_shaded = bool(fused_shaded)
-        self.fused_allow = capi.FUSED_SURFACES | capi.FUSED_LIT  # fused_shaded=True: the allow word of gvt_hip_volume_frame_fused_shaded
+        self.fused_central = bool(fused_central)
+        self.fused_allow = capi.FUSED_SURFACES | capi.FUSED_LIT | (capi.FUSED_CENTRAL if self.fused_central else 0)  # fused_shaded=True: the allow word of gvt_hip_volume_frame_fused_shaded
+        self.param_flags = capi.VOLUME_ALLOW_CENTRAL if self.fused_central else 0  # the flags word of the shadowed frames' and the bakes' params
         self.fused_stats = None  # fused=True: gvt_hip_volume_fused_stats (fused_shaded: gvt_hip_volume_fused_shaded_stats) of the last frame, as a dict
         self.shadows = bool(shadows)
         self.shadow_bias = int(shadow_bias)
@@ -643,7 +649,7 @@ class VolumeTracer:
             if self._occluder_stale and self._occluder_source is not None and self._usable_lights and (self._lit or self._surfaces):
                 self.bake_occluders(self._occluder_source)
             st = capi.VolumeMeshShadowStats()
-            params = capi.VolumeShadowParams(0, self.shadow_bias)
+            params = capi.VolumeShadowParams(self.param_flags, self.shadow_bias)
             capi.check(capi.load().gvt_hip_volume_frame_mesh_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
                                                                       C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
                                                                       C.byref(params), C.byref(st)), "gvt_hip_volume_frame_mesh_shadowed")
@@ -653,7 +659,7 @@ class VolumeTracer:
             if self._grid_stale and self._lit and self._usable_lights:
                 self.rebake()
             st = capi.VolumeFogShadowStats()
-            params = capi.VolumeShadowParams(0, self.shadow_bias)
+            params = capi.VolumeShadowParams(self.param_flags, self.shadow_bias)
             capi.check(capi.load().gvt_hip_volume_frame_fog_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
                                                                      C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
                                                                      C.byref(params), C.byref(st)), "gvt_hip_volume_frame_fog_shadowed")
@@ -661,7 +667,7 @@ class VolumeTracer:
             calls = C.c_uint64(st.adapter_calls)
         elif self.shadows:
             st = capi.VolumeShadowStats()
-            params = capi.VolumeShadowParams(0, self.shadow_bias)
+            params = capi.VolumeShadowParams(self.param_flags, self.shadow_bias)
             capi.check(capi.load().gvt_hip_volume_frame_shadowed(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
                                                                  C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
                                                                  C.byref(params), C.byref(st)), "gvt_hip_volume_frame_shadowed")
@@ -698,7 +704,7 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         st = capi.VolumeLightGridStats()
-        params = capi.VolumeLightGridParams(0, self.fog_bias)
+        params = capi.VolumeLightGridParams(self.param_flags, self.fog_bias)
         capi.check(capi.load().gvt_hip_volume_light_grid_bake(self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst), C.byref(params),
                                                               C.byref(st)), "gvt_hip_volume_light_grid_bake")
         self.light_grid_stats = st.as_dict()
@@ -719,7 +725,7 @@ class VolumeTracer:
         meshes = (C.c_void_p * max(1, scene.n_inst))(*[a.h for a in adapters])
         mesh_minv = capi.f32(scene.minv)
         st = capi.VolumeOccluderStats()
-        params = capi.VolumeOccluderParams(0, 0)
+        params = capi.VolumeOccluderParams(self.param_flags, 0)
         capi.check(capi.load().gvt_hip_volume_occluder_grid_bake(self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst), meshes,
                                                                  capi.ptr(mesh_minv), C.c_size_t(scene.n_inst), C.byref(params), C.byref(st)),
                    "gvt_hip_volume_occluder_grid_bake")
@@ -801,6 +807,8 @@ class VolumeTracer:
         """The bricks' counters summed (they accumulate over frames).  fused=True adds fused, brick_visits and rays_deposited of the last
         frame, and where that frame was fused samples_marched / samples_gathered are ITS counts: the bricks' own did not move.
         fused_shaded=True adds features and, where the frame was fused, its crossings_rendered / samples_shaded likewise.
+        fused_central=True adds nothing: features carries capi.FUSED_CENTRAL where a CENTRAL instantiation ran, and central_marches goes on
+        counting the LOOP's per-brick launches only (it does not move in a fused frame).
         shadows=True: the last frame's gvt_hip_volume_shadow_stats in fused_shaded's form (the camera rays' counters), and beside them
         shadowed, shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched and shadow_samples_gathered.
         fog_shadows=True adds fog_samples_shadowed of the last frame, light_bakes (bakes so far) and light_grid_rays / _bytes / _ms of the
@@ -1100,7 +1108,7 @@ class MixedTracer:
     explicit.  set_camera(), update() and set_surfaces() do not bake."""
 
     def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
-                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False):
+                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -1115,8 +1123,8 @@ class MixedTracer:
         self.depth = DepthPlane(camera.width, camera.height)
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
                                    fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias,
-                                   mesh_shadows=mesh_shadows)
-        # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; shadows: the volume's surfaces shadowed by the
+                                   mesh_shadows=mesh_shadows, fused_central=fused_central)
+        # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; fused_central: with CENTRAL bricks too; shadows: the volume's surfaces shadowed by the
         # volume; fog_shadows: its lit fog too, from the baked light grids; mesh_shadows: both shadowed by the meshes as well, from the baked
         # occluder grids -- without it the meshes cast no shadow into the volume)
         self.mesh_shadows = bool(mesh_shadows)

@@ -746,7 +746,7 @@ int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt
  * queues are used by the fallback only; a fused frame leaves them cleared.  The per-brick counters of the volumes (gvt_hip_volume_info's
  * samples_marched / samples_gathered) are NOT touched by a fused frame: its counters are the call's own, below.
  * Surfaces and lit shading are taken by gvt_hip_volume_frame_fused_shaded, below; this entry point keeps its rule.
- * OUT OF SCOPE.  Central gradients and AMR inside a fused kernel (such frames take the loop); bricks of
+ * OUT OF SCOPE.  AMR inside a fused kernel, and central gradients without GVT_HIP_FUSED_CENTRAL below (such frames take the loop); bricks of
  * different grids, tables or matrices; the Domain scheduler (a rank fusing the bricks it owns needs rays that leave for foreign bricks
  * appended to outgoing queues inside the kernel); fused as the default. */
 typedef struct {
@@ -764,13 +764,21 @@ int gvt_hip_volume_frame_fused(gvt_hip_top *, gvt_hip_volume *const *volumes, co
 
 /* ---- fused frame: surfaces and lit fog (a further opt-in beside gvt_hip_volume_frame_fused, whose rule does not change) ----
  * allow: which frames beyond the plain ones the fused kernel may take.  allow == 0 is gvt_hip_volume_frame_fused in every respect.
- * Bits other than the two below: GVT_HIP_ERR_INVALID, nothing changed.  Argument errors are gvt_hip_volume_frame's / _clipped's.
+ * Bits other than the three below (4 among them): GVT_HIP_ERR_INVALID, nothing changed.  Argument errors are gvt_hip_volume_frame's / _clipped's.
  * ELIGIBILITY is gvt_hip_volume_frame_fused's with two clauses relaxed: "no brick has surfaces" is dropped with
  * GVT_HIP_FUSED_SURFACES, "no effective lit shading" with GVT_HIP_FUSED_LIT.  What the bricks must share is then compared as bits
  * too: n_iso, n_pl, the isovalues, the planes and the surfaces' opacity; the number of lights, their positions and colours, ka, kd and
- * the shading mode.  Still ineligible -- the loop runs, fused = 0, no error: subgrids on any brick; GVT_HIP_VOLUME_GRADIENT_CENTRAL on
- * any brick of a frame that has an isovalue or effective lit shading (in a frame that has neither the kind stays inert, as ever); a
- * frame that needs a bit `allow` lacks; everything ineligible above.
+ * the shading mode.  Still ineligible -- the loop runs, fused = 0, no error: subgrids on any brick; without GVT_HIP_FUSED_CENTRAL,
+ * GVT_HIP_VOLUME_GRADIENT_CENTRAL on any brick of a frame that has an isovalue or effective lit shading (in a frame that has neither
+ * -- no isovalue and no lit shading, or planes only -- the kind stays inert, as ever, whatever the bit); a frame that needs a bit
+ * `allow` lacks; everything ineligible above.
+ * GVT_HIP_FUSED_CENTRAL drops the gradient clause for frames in which EVERY brick has the same kind: a frame that has an isovalue or
+ * effective lit shading and whose bricks are all CENTRAL is then eligible and is marched by the CENTRAL instantiation of the kernel,
+ * which shades with the gradient of "smooth gradients" above from the bricks' ghost layers; features carries the bit exactly when that
+ * instantiation ran.  Such a frame's bricks must also agree, as bits, on the global grid's vertex counts (global_counts at creation: where
+ * the one-sided differences lie); bricks that do not take the loop, or are refused by the shadowed frames ("central" in the message).  A frame that mixes CELL and CENTRAL bricks takes the loop, with or without the bit, and with the bit a frame of
+ * CELL bricks launches what it launches without it.  central_marches of the bricks (gvt_hip_volume_get_gradient) keeps its meaning:
+ * it counts per-volume launches of the LOOP's march and does not move in a fused frame.
  * CONTRACT.  As above: for every eligible input at one sample per pixel the framebuffer equals gvt_hip_volume_frame's / _clipped's on the
  * same arguments in every bit.  The visit of a brick is the surface / lit march's (the crossings of a sample composited in front of it,
  * the sample shaded by the cell gradient), and between two visits the ray carries what the loop's ray carries: beyond t_min, colour and
@@ -782,6 +790,7 @@ int gvt_hip_volume_frame_fused(gvt_hip_top *, gvt_hip_volume *const *volumes, co
  * arrival order, as in the loop. */
 #define GVT_HIP_FUSED_SURFACES 1u   /* the fused kernel may take frames whose bricks have isovalues / slice planes */
 #define GVT_HIP_FUSED_LIT      2u   /* ... and frames with effective lit shading (SHADE_GRADIENT and >= 1 light)   */
+#define GVT_HIP_FUSED_CENTRAL  8u   /* ... and such frames whose bricks all have GVT_HIP_VOLUME_GRADIENT_CENTRAL (bit 2, value 4, stays undefined and refused, as it was) */
 typedef struct {
   uint32_t fused;      /* as gvt_hip_volume_fused_stats */
   uint32_t features;   /* bits of the kernel that ran: 0 = the plain fused kernel, or the loop */
@@ -802,9 +811,20 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
  * gvt_hip_volume_frame_fused_shaded with allow = GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT in every respect, its fallback to the loop
  * included; shadowed = 0 and the shadow counters are 0.
  * REFUSED.  A frame that has a surface and a light but is not eligible for the shaded fused kernel under that allow word (subgrids;
- * GVT_HIP_VOLUME_GRADIENT_CENTRAL on a brick of a frame with an isovalue; bricks of different grids, tables, matrices, surfaces or
- * lights; more than 256 bricks): no loop renders shadows, so the call returns GVT_HIP_ERR_INVALID with a message that names the clause.
- * A null params pointer, flags != 0 and a bias outside 1 .. 64 are refused likewise.  A refusal changes nothing: the framebuffer is not
+ * GVT_HIP_VOLUME_GRADIENT_CENTRAL on a brick of a frame with an isovalue, unless flags allows it, below; bricks of different grids,
+ * tables, matrices, surfaces or lights; more than 256 bricks): no loop renders shadows, so the call returns GVT_HIP_ERR_INVALID with a
+ * message that names the clause.  A null params pointer, flag bits other than GVT_HIP_VOLUME_ALLOW_CENTRAL and a bias outside 1 .. 64
+ * are refused likewise.
+ * CENTRAL.  flags = GVT_HIP_VOLUME_ALLOW_CENTRAL (the first defined bit of the flags word of gvt_hip_volume_shadow_params,
+ * gvt_hip_volume_light_grid_params and gvt_hip_volume_occluder_params; bit 0 stays undefined and refused) adds GVT_HIP_FUSED_CENTRAL
+ * to the allow word of the three shadowed frames, the inert forward included: a frame whose bricks are ALL CENTRAL is accepted, a frame
+ * that mixes the kinds is refused (the message says "central"), and a frame of CELL bricks launches what it launches with flags = 0.
+ * The contract changes in one place: the g that shades a crossed isovalue and a lit fog sample is vol_gradient_central's ("smooth
+ * gradients").  T_j, Tg, Og, every counter and the opacity do not depend on g.  So the alpha plane and every counter -- the camera
+ * rays' and the shadow rays' -- of a CENTRAL shadowed frame equal those of the same frame with the bricks switched to CELL; only the
+ * colour planes differ.  The two bakes accept CENTRAL bricks under the flag and write the bits they write for the same bricks under
+ * CELL: their rays march with shading NONE and read no gradient.  Neither gvt_hip_volume_set_gradient nor gvt_hip_volume_set_ghosts
+ * makes a light grid or an occluder grid stale.  A refusal changes nothing: the framebuffer is not
  * cleared, the queues are untouched.  Argument errors are gvt_hip_volume_frame's / _clipped's.
  * CONTRACT.  The shadowed frame is the shaded fused frame with one change.  At a lattice sample k of a camera ray at which at least one
  * crossing is rendered, a transmittance T_j is found once per light j before the first crossing is composited; all crossings of that
@@ -836,9 +856,11 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
  * shadow_crossings and shadow_samples_marched / _gathered are the fused frame's counters applied to the shadow rays.  They are kept
  * apart from the camera rays' counters, which equal those of the unshadowed frame whenever the two images agree.
  * OUT OF SCOPE.  Ambient occlusion; shadowed fog and geometry shadowing the volume (both below); the volume attenuating mesh shadow rays; the Domain
- * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR and CENTRAL frames; shadows in the per-brick loop. */
+ * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR frames, and CENTRAL frames without
+ * GVT_HIP_VOLUME_ALLOW_CENTRAL; shadows in the per-brick loop. */
+#define GVT_HIP_VOLUME_ALLOW_CENTRAL 2u /* flags of the shadowed frames and the two bakes: accept frames whose bricks are all CENTRAL */
 typedef struct {
-  uint32_t flags; /* must be 0 */
+  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
   int32_t bias;   /* 1 .. 64, lattice steps */
 } gvt_hip_volume_shadow_params;
 typedef struct {
@@ -876,8 +898,9 @@ int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes,
  * unusable light has no grid; its transmittance is 1.
  * THE BAKE.  Eligibility is the shaded fused frame's "bricks of one grid" comparison (allow = both bits) and, on top of it: m equal as
  * bits on every brick; surfaces and lights equal on every brick whatever the shading; at least one usable light; no subgrids; no
- * CENTRAL kind on a brick of a frame with an isovalue; the bricks' owned cells tile the global grid exactly (disjoint, and their sum is
- * the global cell count); at most 2^32 - 1 (vertex, light) pairs; flags == 0; bias 1 .. 64; no null pointer.  Anything else:
+ * CENTRAL kind on a brick of a frame with an isovalue or lit shading unless flags is GVT_HIP_VOLUME_ALLOW_CENTRAL and every brick has
+ * it; the bricks' owned cells tile the global grid exactly (disjoint, and their sum is
+ * the global cell count); at most 2^32 - 1 (vertex, light) pairs; flags 0 or that bit; bias 1 .. 64; no null pointer.  Anything else:
  * GVT_HIP_ERR_INVALID with a message that names the clause, the old grids kept.  Planes that cannot be allocated: GVT_HIP_ERR_CAPACITY;
  * a HIP call that fails: GVT_HIP_ERR_DEVICE; in both cases every brick keeps the grid it had (all planes are allocated and filled
  * before the first brick changes).  The call waits for the launch.
@@ -904,9 +927,10 @@ int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes,
  * fog_samples_shadowed = samples_shaded when the fog kernel ran (else 0).
  * A volume that holds a grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees the grid.
  * OUT OF SCOPE.  A coarser or compressed grid; pruning vertices no sample reads; ambient occlusion; the
- * Domain scheduler; AMR and CENTRAL frames; moving the crossings' shadow rays onto the grid. */
+ * Domain scheduler; AMR frames, and CENTRAL frames without GVT_HIP_VOLUME_ALLOW_CENTRAL ("shadowed surfaces", CENTRAL); moving the
+ * crossings' shadow rays onto the grid. */
 typedef struct {
-  uint32_t flags; /* must be 0 */
+  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
   int32_t bias;   /* 1 .. 64, lattice steps */
 } gvt_hip_volume_light_grid_params;
 typedef struct {
@@ -984,9 +1008,9 @@ int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *, gvt_hip_volume *const *volu
  * = 1 when the mesh kernel ran (0: inert).
  * A volume that holds an occluder grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees it.
  * OUT OF SCOPE.  The fog attenuating mesh shadow rays; exact per-crossing mesh shadow rays; skipping volume shadow rays where O = 0;
- * the Domain scheduler; AMR and CENTRAL frames. */
+ * the Domain scheduler; AMR frames, and CENTRAL frames without GVT_HIP_VOLUME_ALLOW_CENTRAL ("shadowed surfaces", CENTRAL). */
 typedef struct {
-  uint32_t flags; /* must be 0 */
+  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
   uint32_t pad;
 } gvt_hip_volume_occluder_params;
 typedef struct {

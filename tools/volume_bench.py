@@ -52,6 +52,12 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                                         occluder grids and its share spent in any-hit launches; the fog-shadowed frame and the
                                                         mesh-shadowed frame alternating frame by frame on ONE tracer; the brickings' framebuffers
                                                         compared bitwise.  With --surfaces also the frame with two isovalues, lit fog on and off
+  python tools/volume_bench.py --fused ... --gradient central   ADDS, ahead of the rows the other flags print, the fused frames with CENTRAL
+                                             bricks (GVT_HIP_FUSED_CENTRAL / GVT_HIP_VOLUME_ALLOW_CENTRAL): the lit and the isosurface frame,
+                                             fused against the loop, per bricking; and for each of --shadows, --fog-shadows and --mesh-shadows
+                                             (with the flags they go with, as ever) that shadowed frame with the CELL and with the CENTRAL
+                                             gradient, alternating, from one bake.  All of them: --fused --surfaces --shade --shadows
+                                             --fog-shadows --mesh-shadows --gradient central
   python tools/volume_bench.py --fused --surfaces --shadows   shadowed surfaces (gvt_hip_volume_frame_shadowed): --surfaces' frame shadowed
                                              against the same frame through the shaded fused kernel, alternating frame by frame on ONE
                                              tracer; with each the shadow rays and the shadow samples per frame, so that the cost per shadow
@@ -400,6 +406,86 @@ def run_shade(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
 
 
 SMOOTH_ISO = [0.45, 0.55]
+CENTRAL_FRAMES = ("shadows", "fog_shadows", "mesh_shadows")
+
+
+def run_fused_central(n, split, steps, warmup, rate, kind, vol, what, dtype="f32"):
+    """--shade --gradient central's lit frame (what = "lit": three lights) or isosurface frame ("iso": two isovalues, shading off) with the
+    CENTRAL gradient on every brick: the loop against the fused frame (GVT_HIP_FUSED_CENTRAL), alternating frame by frame on one tracer
+    whose bricks carry their ghost faces; the framebuffers compared after every pair."""
+    bricks = scenes.split_volume(vol, *split, ghosts=True)
+    tr = VolumeTracer(bricks, camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=True, fused_central=True)
+    _, lo, hi = DTYPES[dtype]
+    tr.set_lights(SHADE_LIGHTS)
+    if what == "iso":
+        tr.set_surfaces([lo + v * (hi - lo) for v in SMOOTH_ISO], (), 0.5).set_shading(False)
+    else:
+        tr.set_shading(True)
+    tr.set_gradient("central")
+    loop, fused = [], []
+    same = True
+
+    def frame(flag):
+        tr.fused = flag
+        tr.frame()
+
+    for i in range(warmup + steps):
+        loop.append(timed(lambda: frame(False)))
+        loop_calls = tr.calls
+        a = tr.framebuffer(False).copy()
+        fused.append(timed(lambda: frame(True)))
+        same = same and bool((a.view(np.uint32) == tr.framebuffer(False).view(np.uint32)).all())  # (outside the timed region)
+    loop, fused = loop[warmup:], fused[warmup:]
+    st = tr.stats()
+    return {"mode": "fused_central_" + what, "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "features": int(st["features"]),
+            "fused": int(st["fused"]), "loop_ms_median": med(loop), "loop_ms_min": round(min(loop), 3), "loop_ms_max": round(max(loop), 3), "loop_adapter_calls": int(loop_calls),
+            "fused_ms_median": med(fused), "fused_ms_min": round(min(fused), 3), "fused_ms_max": round(max(fused), 3),
+            "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "samples_shaded": int(st["samples_shaded"]),
+            "crossings_per_frame": int(st["crossings_rendered"]), "brick_visits": int(st["brick_visits"]),
+            "fused_over_loop": round(float(np.median(fused)) / float(np.median(loop)), 4), "fused_wins": bool(max(fused) < min(loop)), "same_bits": same}
+
+
+def run_central_shadows(n, split, steps, warmup, rate, kind, vol, which, dtype="f32", first=None):
+    """A shadowed frame (which: one of CENTRAL_FRAMES) of two isovalues in lit fog under one light, with the CELL and with the CENTRAL
+    gradient (GVT_HIP_VOLUME_ALLOW_CENTRAL), alternating frame by frame on one tracer whose bricks carry their ghost faces: what the
+    smooth gradient costs inside the shadowed kernels.  The grids are baked once -- the kind makes none stale.  mesh_shadows: the bunny
+    inside the grid, as --mesh-shadows has it.  first: the CENTRAL framebuffer of another bricking, compared bitwise."""
+    cam = camera()
+    scene = None
+    if which == "mesh_shadows":
+        scene = scenes.bunny_scene(1920, 1080)
+        vol, cam = scenes.mesh_in_volume(scene, vol, fill=0.6), scene.camera
+    bricks = scenes.split_volume(vol, *split, ghosts=True)
+    tr = VolumeTracer(bricks, cam, transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=True, shadows=True,
+                      fog_shadows=which != "shadows", mesh_shadows=which == "mesh_shadows", fused_central=True)
+    _, lo, hi = DTYPES[dtype]
+    tr.set_surfaces([lo + v * (hi - lo) for v in SMOOTH_ISO], (), 0.5).set_lights(SHADE_LIGHTS[:1]).set_shading(True)
+    if scene is not None:
+        tr.bake_occluders(scene)
+    ms = {"cell": [], "central": []}
+    stats, fbs = {}, {}
+    for i in range(warmup + steps):
+        for g in ms:
+            tr.set_gradient(g)
+            ms[g].append(timed(tr.frame))
+            if i == warmup + steps - 1:
+                stats[g], fbs[g] = tr.stats(), tr.framebuffer(False).copy()
+    ms = {g: v[warmup:] for g, v in ms.items()}
+    st, sc_ = stats["central"], stats["cell"]
+    keys = ("samples_marched", "samples_gathered", "samples_shaded", "crossings_rendered", "brick_visits", "rays_deposited", "shadow_rays", "shadow_brick_visits",
+            "shadow_crossings", "shadow_samples_marched", "shadow_samples_gathered")
+    row = {"mode": "central_" + which, "n": n, "dtype": dtype, "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "features": int(st["features"]),
+           "cell_features": int(sc_["features"]), "shadowed": int(st["shadowed"]), "light_bakes": int(st.get("light_bakes", 0)), "occluder_bakes": int(st.get("occluder_bakes", 0))}
+    for g, v in ms.items():
+        row.update({g + "_ms_median": med(v), g + "_ms_min": round(min(v), 3), g + "_ms_max": round(max(v), 3)})
+    row.update({"central_over_cell": round(float(np.median(ms["central"])) / float(np.median(ms["cell"])), 4),
+                "samples_per_frame": int(st["samples_marched"]), "samples_shaded": int(st["samples_shaded"]), "crossings_per_frame": int(st["crossings_rendered"]),
+                "shadow_rays": int(st["shadow_rays"]), "shadow_samples": int(st["shadow_samples_marched"]),
+                "counters_same": bool(all(st[k] == sc_[k] for k in keys)),
+                "alpha_same": bool((fbs["cell"][..., 3].view(np.uint32) == fbs["central"][..., 3].view(np.uint32)).all()),
+                "colour_differs": bool((fbs["cell"][..., :3].view(np.uint32) != fbs["central"][..., :3].view(np.uint32)).any()),
+                "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fbs["central"].view(np.uint32)).all())})
+    return row, fbs["central"]
 
 
 def run_smooth(n, split, steps, warmup, rate, kind, vol, dtype="f32"):
@@ -681,7 +767,9 @@ def main():
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--shade", action="store_true")
-    ap.add_argument("--gradient", choices=["cell", "central"], default="cell", help="with --shade: central = the lit and the isosurface frame with both gradient kinds")
+    ap.add_argument("--gradient", choices=["cell", "central"], default="cell",
+                    help="with --shade: central = the lit and the isosurface frame with both gradient kinds; with --fused: central = those two frames with CENTRAL "
+                         "bricks, fused against the loop, and with --shadows / --fog-shadows / --mesh-shadows the shadowed frames, CENTRAL against CELL")
     ap.add_argument("--amr", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
     ap.add_argument("--domains", type=int, nargs="+", metavar="W")
@@ -728,6 +816,25 @@ def main():
         a.sizes = []
     if a.shadows and not (a.fused and a.surfaces):
         ap.error("--shadows goes with --fused --surfaces")
+    if a.fog_shadows and not (a.fused and a.shade):
+        ap.error("--fog-shadows goes with --fused --shade")
+    if a.mesh_shadows and not a.fog_shadows:
+        ap.error("--mesh-shadows goes with --fused --shade --fog-shadows")
+    if a.fused and a.gradient == "central":  # the CENTRAL rows, ahead of the rows the other flags print: fused against the loop, and the shadowed frames asked for against their CELL frames
+        for n in a.sizes:
+            vol = noise(n, a.dtype)
+            for what, kind in [("lit", k) for k in a.tf] + [("iso", "thin")]:
+                for nb in a.bricks:
+                    r = run_fused_central(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, what, a.dtype)
+                    out["runs"].append(r)
+                    print(json.dumps(r), flush=True)
+            for which, on in zip(CENTRAL_FRAMES, (a.shadows, a.fog_shadows, a.mesh_shadows)):
+                first = None
+                for nb in a.bricks if on else ():
+                    r, fb = run_central_shadows(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, "thin", vol, which, a.dtype, first)
+                    first = fb if first is None else first
+                    out["runs"].append(r)
+                    print(json.dumps(r), flush=True)
     for n in a.sizes if a.shadows else ():
         vol = noise(n, a.dtype)
         first = None
@@ -738,10 +845,6 @@ def main():
             print(json.dumps(r), flush=True)
     if a.shadows:
         a.sizes = []
-    if a.fog_shadows and not (a.fused and a.shade):
-        ap.error("--fog-shadows goes with --fused --shade")
-    if a.mesh_shadows and not a.fog_shadows:
-        ap.error("--mesh-shadows goes with --fused --shade --fog-shadows")
     for n in a.sizes if a.mesh_shadows else ():
         vol = noise(n, a.dtype)
         for shape, kind in [("lit", k) for k in a.tf] + ([("surf_lit", "thin"), ("surf", "thin")] if a.surfaces else []):
