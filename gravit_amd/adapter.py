@@ -457,6 +457,8 @@ class HipVolumeAdapter:
     """A volume brick on the device (gvt_hip_volume): the counterpart of the reference's volume adapters (OSPRayAdapter, PVolAdapter).
     `brick` is a scenes.Brick (or a scenes.VolumeData: the whole grid as one brick); its data may also be a torch tensor on the GPU.
     A brick that carries `subgrids` (scenes.refine, scenes.split_amr_volume) is an AMR volume: they are set at construction (set_subgrids).
+    amr_shaded: the subgrids are set with capi.VOLUME_AMR_SHADED, so the AMR brick takes set_surfaces and set_shading (isovalues, slice
+    planes and lit fog in the refined cells); without it (the default) both are refused on a brick that has subgrids.
     native=False: the data is converted to float32, whatever it was.  native=True: a uint8, int16 or uint16 brick (numpy array or contiguous
     GPU tensor) is stored at its own width (gvt_hip_volume_create_typed: a vertex's value is (float)v, so transfer functions and isovalues
     are in the data's units) and answers bit for bit like the float32 brick of the converted data; any other dtype raises ValueError.
@@ -467,8 +469,9 @@ class HipVolumeAdapter:
         """The dtype's name, for numpy arrays and torch tensors alike."""
         return str(data.dtype).replace("torch.", "")
 
-    def __init__(self, brick, sampling_rate=1.0, skip=True, native=False):
+    def __init__(self, brick, sampling_rate=1.0, skip=True, native=False, amr_shaded=False):
         self.lib = capi.load()
+        self.amr_shaded = bool(amr_shaded)
         if hasattr(brick, "global_counts"):
             counts, offset, gcounts = brick.counts, brick.offset, brick.global_counts
         else:
@@ -509,9 +512,11 @@ class HipVolumeAdapter:
         if getattr(brick, "ghosts", None) is not None:  # a brick that knows its neighbours' face layers (scenes.split_volume(ghosts=True))
             self.set_ghosts(brick.ghosts)
 
-    def set_subgrids(self, subgrids):
+    def set_subgrids(self, subgrids, shaded=None):
         """gvt_hip_volume_set_subgrids: the brick's whole set of refined subgrids (scenes.Subgrid; an empty list removes it).  Their data:
-        numpy arrays, or contiguous float32 torch tensors on the GPU (all of them: no host round trip).  The library keeps its own copies."""
+        numpy arrays, or contiguous float32 torch tensors on the GPU (all of them: no host round trip).  The library keeps its own copies.
+        shaded: pass capi.VOLUME_AMR_SHADED (None: the adapter's amr_shaded) -- the call is then accepted on a brick that has surfaces or
+        gradient shading, and the set takes both."""
         subgrids = list(subgrids)
         n = len(subgrids)
         pods = (capi.SubgridPod * max(n, 1))()
@@ -536,6 +541,8 @@ class HipVolumeAdapter:
                 keep.append(np.ascontiguousarray(s.data.numpy() if hasattr(s.data, "data_ptr") else s.data, np.float32))
                 ptrs[i] = keep[-1].ctypes.data
         flags = capi.VOLUME_DEVICE if n and all(device) else 0
+        if self.amr_shaded if shaded is None else shaded:
+            flags |= capi.VOLUME_AMR_SHADED
         capi.check(self.lib.gvt_hip_volume_set_subgrids(self.h, C.cast(pods, C.c_void_p), C.cast(ptrs, C.c_void_p), n, flags), "gvt_hip_volume_set_subgrids")
 
     GRADIENT_KINDS = {"cell": capi.VOLUME_GRADIENT_CELL, "central": capi.VOLUME_GRADIENT_CENTRAL}

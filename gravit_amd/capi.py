@@ -206,6 +206,7 @@ VOLUME_MAX_SURFACES, VOLUME_MAX_LIGHTS = 16, 8
 VOLUME_OPAQUE_A = 0.99
 VOLUME_DEVICE, VOLUME_NO_SKIP = 1, 2
 VOLUME_MAX_SUBGRIDS, VOLUME_MAX_LEVELS = 4096, 4  # AMR volumes (gvt_hip_volume_set_subgrids)
+VOLUME_AMR_SHADED = 8  # gvt_hip_volume_set_subgrids flag: this set of subgrids takes surfaces and gradient shading
 VOLUME_SHADE_NONE, VOLUME_SHADE_GRADIENT = 0, 1  # gvt_hip_volume_set_shading: the fog's samples lit by the interpolant's gradient
 VOLUME_GRADIENT_CELL, VOLUME_GRADIENT_CENTRAL = 0, 1  # gvt_hip_volume_set_gradient: which gradient shades (CENTRAL needs set_ghosts)
 VOXEL_F32, VOXEL_U8, VOXEL_I16, VOXEL_U16 = 0, 1, 2, 3  # a volume's voxel type: the samples stay on the device at that width

@@ -13,6 +13,7 @@
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
 //   k_volume_march_amr / k_amr_ranges       AMR volumes (Volume::AddAMRGrid): nested refined subgrids inside a brick, volume_amr.inc
+//   k_volume_march_amr_surf / _lit / _surf_lit   ... with isovalues, slice planes and lit fog in the refined cells (GVT_HIP_VOLUME_AMR_SHADED)
 //   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
 //                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
 //   gvt_hip_volume_frame_fused / k_volume_march_fused   the same frame over bricks of ONE grid in one launch: a lane carries its ray from brick to
@@ -70,10 +71,12 @@ struct gvt_hip_volume {
   float lpos[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {}, lcol[GVT_HIP_VOLUME_MAX_LIGHTS][3] = {};
   std::vector<uint8_t> h_mc;     // host copy of d_mc
   uint32_t *d_cells = nullptr;   // per macro cell, for the surface march: skip bit and isovalue sides (rebuilt by set_transfer and set_surfaces)
-  // AMR (gvt_hip_volume_set_subgrids): with subgrids the march is k_volume_march_amr (volume_amr.inc: the device tables)
+  // AMR (gvt_hip_volume_set_subgrids): with subgrids the march is k_volume_march_amr or, with surfaces or lit shading on a set flagged
+  // GVT_HIP_VOLUME_AMR_SHADED, one of its three shaded entry points (volume_amr.inc: the device tables)
   std::vector<gvt_hip_subgrid> sub;
   int amr_levels = 1;            // level 0 and the deepest subgrid's
   uint64_t amr_bytes = 0, amr_marches = 0;
+  int amr_flags = 0;             // the flags of the current set of subgrids (GVT_HIP_VOLUME_AMR_SHADED: it takes surfaces and lit shading); 0 without one
   float *d_amr_vox = nullptr;
   uint2 *d_amr_mc = nullptr;
   int *d_amr_list = nullptr;
@@ -1064,11 +1067,20 @@ int volume_march(gvt_hip_volume *Vh, gvt_hip_queue *q, const float minv[16], boo
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = minv[k];
   const unsigned blocks = std::min(blocks_of(q->size), (unsigned)(std::max(C.n_cu, 1) * 8));
-  if (!Vh->sub.empty()) { // an AMR volume: F32, no surfaces, unlit (gvt_hip_volume_set_subgrids and the setters see to it)
+  if (!Vh->sub.empty()) { // an AMR volume: F32, CELL gradients; surfaces and lit shading only under GVT_HIP_VOLUME_AMR_SHADED (the setters see to it)
     const RayPlanes P = make_planes(q->d_planes, q->cap);
+    const unsigned n = (unsigned)q->size;
     const AmrDev Am{ Vh->d_amr_mc, Vh->d_amr_list, Vh->d_amr_desc, Vh->d_amr_vox };
-    if (clip) k_volume_march_amr<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, P, (unsigned)q->size, M, work, Vh->d_stats);
-    else k_volume_march_amr<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, P, (unsigned)q->size, M, work, Vh->d_stats);
+    const bool surf = Vh->n_iso + Vh->n_pl > 0;
+    const bool lit = Vh->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && Vh->n_lights > 0; // (no lights: nothing to shade with, the plain AMR march)
+    if (lit && surf && clip) k_volume_march_amr_surf_lit<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (lit && surf) k_volume_march_amr_surf_lit<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (lit && clip) k_volume_march_amr_lit<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, light_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (lit) k_volume_march_amr_lit<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, light_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (surf && clip) k_volume_march_amr_surf<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (surf) k_volume_march_amr_surf<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, surf_dev(Vh, M), P, n, M, work, Vh->d_stats);
+    else if (clip) k_volume_march_amr<true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, P, n, M, work, Vh->d_stats);
+    else k_volume_march_amr<false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(Vh), Am, P, n, M, work, Vh->d_stats);
     HIPCHK(hipGetLastError());
     Vh->amr_marches++;
     return 0;
@@ -1350,7 +1362,7 @@ extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isova
     set_error("volume_set_surfaces: %d isovalues and %d slices, at most %d surfaces", n_iso, n_slices, GVT_HIP_VOLUME_MAX_SURFACES);
     return GVT_HIP_ERR_INVALID;
   }
-  if (n_iso + n_slices > 0 && !V->sub.empty()) { set_error("volume_set_surfaces: the volume has AMR subgrids, which take no surfaces"); return GVT_HIP_ERR_INVALID; }
+  if (n_iso + n_slices > 0 && !V->sub.empty() && !(V->amr_flags & GVT_HIP_VOLUME_AMR_SHADED)) { set_error("volume_set_surfaces: the volume has AMR subgrids, which take no surfaces"); return GVT_HIP_ERR_INVALID; }
   if (!(opacity > 0.f && opacity <= 1.f)) { set_error("volume_set_surfaces: opacity %g is not in (0, 1]", (double)opacity); return GVT_HIP_ERR_INVALID; }
   for (int i = 0; i < n_iso; i++)
     if (isovalues[i] != isovalues[i]) { set_error("volume_set_surfaces: isovalue %d is NaN", i); return GVT_HIP_ERR_INVALID; }
@@ -1396,7 +1408,7 @@ extern "C" int gvt_hip_volume_set_shading(gvt_hip_volume *V, int mode) {
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!V) { set_error("volume_set_shading: null"); return GVT_HIP_ERR_INVALID; }
   if (mode != GVT_HIP_VOLUME_SHADE_NONE && mode != GVT_HIP_VOLUME_SHADE_GRADIENT) { set_error("volume_set_shading: unknown mode %d", mode); return GVT_HIP_ERR_INVALID; }
-  if (mode == GVT_HIP_VOLUME_SHADE_GRADIENT && !V->sub.empty()) { set_error("volume_set_shading: the volume has AMR subgrids, which are not shaded"); return GVT_HIP_ERR_INVALID; }
+  if (mode == GVT_HIP_VOLUME_SHADE_GRADIENT && !V->sub.empty() && !(V->amr_flags & GVT_HIP_VOLUME_AMR_SHADED)) { set_error("volume_set_shading: the volume has AMR subgrids, which are not shaded"); return GVT_HIP_ERR_INVALID; }
   V->shade = mode;
   return 0;
 }
@@ -2509,7 +2521,7 @@ void amr_release(gvt_hip_volume *V) {
   hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
   V->d_amr_vox = nullptr; V->d_amr_mc = nullptr; V->d_amr_list = nullptr; V->d_amr_desc = nullptr;
   V->sub.clear(); V->amr_first.clear(); V->amr_count.clear(); V->amr_min.clear(); V->amr_max.clear(); V->amr_nan.clear();
-  V->amr_levels = 1; V->amr_bytes = 0;
+  V->amr_levels = 1; V->amr_bytes = 0; V->amr_flags = 0;
 }
 
 // bmin / bmax / bnan, vmin / vmax: the level-0 ranges afresh from d_vox, then the subgrids' part merged in; the tables from the union
@@ -2532,9 +2544,9 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!V || (n > 0 && (!grids || !samples))) { set_error("volume_set_subgrids: null argument"); return GVT_HIP_ERR_INVALID; }
   if (n < 0 || n > GVT_HIP_VOLUME_MAX_SUBGRIDS) { set_error("volume_set_subgrids: %d subgrids, at most %d", n, GVT_HIP_VOLUME_MAX_SUBGRIDS); return GVT_HIP_ERR_INVALID; }
-  if (flags & ~GVT_HIP_VOLUME_DEVICE) { set_error("volume_set_subgrids: unknown flag bits %d", flags); return GVT_HIP_ERR_INVALID; }
+  if (flags & ~(GVT_HIP_VOLUME_DEVICE | GVT_HIP_VOLUME_AMR_SHADED)) { set_error("volume_set_subgrids: unknown flag bits %d", flags); return GVT_HIP_ERR_INVALID; }
   if (V->vtype != GVT_HIP_VOXEL_F32) { set_error("volume_set_subgrids: the volume holds voxel type %d, subgrids are float32", V->vtype); return GVT_HIP_ERR_INVALID; }
-  if (V->n_iso + V->n_pl > 0 || V->shade == GVT_HIP_VOLUME_SHADE_GRADIENT) {
+  if (!(flags & GVT_HIP_VOLUME_AMR_SHADED) && (V->n_iso + V->n_pl > 0 || V->shade == GVT_HIP_VOLUME_SHADE_GRADIENT)) {
     set_error("volume_set_subgrids: the volume has surfaces or gradient shading, which AMR volumes do not take");
     return GVT_HIP_ERR_INVALID;
   }
@@ -2595,6 +2607,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   V->d_amr_vox = d_vox; V->d_amr_mc = d_mc; V->d_amr_list = d_list; V->d_amr_desc = d_desc;
   V->sub.assign(grids, grids + n);
   V->amr_levels = P.levels;
+  V->amr_flags = flags & GVT_HIP_VOLUME_AMR_SHADED;
   V->amr_bytes = sizeof(float) * P.total + sizeof(uint2) * nbk + sizeof(int) * P.list.size() + sizeof(int4) * P.desc.size();
   V->amr_first.swap(P.first); V->amr_count.swap(P.cnt);
   V->amr_min.assign(nbk, INFINITY); V->amr_max.assign(nbk, -INFINITY); V->amr_nan.assign(nbk, 0);

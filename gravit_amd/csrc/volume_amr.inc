@@ -1,6 +1,8 @@
 // volume_amr.inc -- AMR volumes: nested refined subgrids inside a brick (Volume::griddata / AddAMRGrid, render/data/primitives/Volume.h:40-58,
 // 101-135; api::addAmrSubgrid, api.cpp:543-612).  Included by volume.hip, inside its anonymous namespace, behind the steps of the march.
 //   k_volume_march_amr<CLIP>   the plain F32 march with the descent: per gathered sample, from the level-0 cell down the subgrids that cover it
+//   k_volume_march_amr_surf / _lit / _surf_lit <CLIP>   the same body with the surface and lit steps of volume_march_body, for volumes whose
+//                              subgrids were set with GVT_HIP_VOLUME_AMR_SHADED: crossings and shading read the FINAL grid's cell
 //   k_amr_ranges               every subgrid's vertices reduced into the level-0 macro cells whose closed box they lie in
 // The contract is stated in include/gvt_hip.h ("AMR volumes"); tests/volume_amr_checker.py restates it in numpy.
 //
@@ -28,16 +30,26 @@ __device__ __forceinline__ float amr_gather(const float *p, size_t sy, size_t sz
   const float c0 = lerp_(c00, c10, f[1]), c1 = lerp_(c01, c11, f[1]);
   return lerp_(c0, c1, f[2]);
 }
+// ... and the eight corners it has just read, for the gradient of the shaded marches: the same addresses, so the loads are the gather's.
+// (Handed back by amr_gather itself, through a reference or a pointer, the plain AMR kernels schedule two moves the other way round, and
+// they are to stay what they were; a function of its own leaves them alone)
+__device__ __forceinline__ void amr_corners(const float *p, size_t sy, size_t sz, VolCorners &G) {
+  G.v000 = p[0]; G.v100 = p[1]; G.v010 = p[sy]; G.v110 = p[sy + 1];
+  G.v001 = p[sz]; G.v101 = p[sz + 1]; G.v011 = p[sz + sy]; G.v111 = p[sz + sy + 1];
+}
 
 // The descent: cell c (relative to the brick) and fractions f of the level-0 grid become the cell and fractions of the finest grid that
 // covers the sample; p / sy / sz = that grid's first vertex of the cell and its strides.  Every step is exact in float32 (f < 1, the
-// ratio a power of two), so which grid a sample falls into is decided on integer cell indices.  Returns true if the final grid is a subgrid
-__device__ __forceinline__ bool amr_descend(const VolDev &V, const AmrDev &A, uint2 word, const int c[3], float f[3], const float *&p, size_t &sy, size_t &sz) {
+// ratio a power of two), so which grid a sample falls into is decided on integer cell indices.  log2_r: log2 of R, the product of the
+// ratios down to the final grid (0 at level 0, at most 9).  Returns true if the final grid is a subgrid
+__device__ __forceinline__ bool amr_descend(const VolDev &V, const AmrDev &A, uint2 word, const int c[3], float f[3], const float *&p, size_t &sy, size_t &sz,
+                                            int &log2_r) {
   int ci[3] = { c[0], c[1], c[2] };
   int first = (int)word.x, cnt = (int)(word.y & 0x7fffffffu);
   sy = (size_t)V.nx; sz = (size_t)V.nx * (size_t)V.ny;
   const float *base = (const float *)V.vox;
   bool refined = false;
+  log2_r = 0;
   for (int level = 1; level < GVT_HIP_VOLUME_MAX_LEVELS && cnt > 0; level++) {
     int found = -1;
     int4 d0 = make_int4(0, 0, 0, 0);
@@ -59,23 +71,39 @@ __device__ __forceinline__ bool amr_descend(const VolDev &V, const AmrDev &A, ui
     sy = (size_t)(unsigned)d1.w; sz = (size_t)(unsigned)d2.x;
     base = A.vox + (((size_t)(unsigned)d3.y << 32) | (size_t)(unsigned)d3.x);
     first = d2.y; cnt = d2.z;
+    log2_r += shift;
     refined = true;
   }
   p = base + (size_t)ci[0] + sy * (size_t)ci[1] + sz * (size_t)ci[2];
   return refined;
 }
 
-// volume_march_body<float, false, CLIP, false> with the descent between the skip decision and the gather: lattice, ownership, skipping,
-// jumps, look-up, compositing and write-back are the plain march's, through the same functions.  stats[4] counts the refined samples
-template <bool CLIP>
-__device__ __forceinline__ void volume_march_amr_body(const VolDev &V, const AmrDev &Am, RayPlanes q, unsigned n, const Mat4 &minv, unsigned *__restrict__ work,
-                                                      unsigned long long *__restrict__ stats) {
+// The final grid's spacing per axis, s_a = spacing.a / (float)R, in a copy of V: what vol_gradient and vol_accumulate_lit divide by.  R is a
+// power of two, so the product with 2^-log2_r is that quotient, bit for bit (both are the one correctly rounded value)
+__device__ __forceinline__ VolDev amr_fine_spacing(const VolDev &V, int log2_r) {
+  const float inv_r = __int_as_float((127 - log2_r) << 23);
+  VolDev F = V;
+  F.sx = V.sx * inv_r; F.sy = V.sy * inv_r; F.sz = V.sz * inv_r;
+  return F;
+}
+
+// volume_march_body<float, SURF, CLIP, LIT> with the descent between the skip decision and the gather: lattice, ownership, skipping,
+// jumps, sides, crossings, look-up, shading, compositing and write-back are the plain marches', through the same functions.  The corners,
+// the fractions and the spacing a gradient reads are the FINAL grid's (amr_corners, the descended f, amr_fine_spacing); the plane sides
+// and a plane's normal read the lattice point as ever.  stats[4] counts the refined samples.  Without SURF and LIT: the plain AMR march as
+// it was, instruction for instruction (S is NoSurf, nothing of the shaded steps is instantiated).
+// KEEP IN STEP: the per-sample steps for SURF / LIT are volume_march_body's (volume.hip); a change to the visit there is a change here.
+template <bool SURF, bool LIT, bool CLIP>
+__device__ __forceinline__ void volume_march_amr_body(const VolDev &V, const AmrDev &Am, const MarchTable<SURF, LIT> &S, RayPlanes q, unsigned n, const Mat4 &minv,
+                                                      unsigned *__restrict__ work, unsigned long long *__restrict__ stats) {
   bool active = false, exhausted = false;
   unsigned idx = 0;
   float o[3] = { 0.f, 0.f, 0.f }, d[3] = { 0.f, 0.f, 0.f }, C[3] = { 0.f, 0.f, 0.f }, A = 0.f;
-  int k = 0, k_hi = -1, k_last = -1;
+  int k = 0, k_hi = -1, k_last = -1, k_carry = -1, prev = -1; // (k_carry, prev, n_crossed: SURF only)
   bool seen = false;
   unsigned long long n_marched = 0, n_gathered = 0, n_refined = 0;
+  unsigned n_crossed = 0;
+  unsigned long long n_shaded = 0; // (LIT only)
   for (;;) {
     const unsigned long long idle = ballot64(!active);
     if (idle && !exhausted && (__popcll(idle) >= VOL_REFILL_MIN || idle == ballot64(true))) {
@@ -85,11 +113,16 @@ __device__ __forceinline__ void volume_march_amr_body(const VolDev &V, const Amr
         idx = slot;
         active = true;
         const float4 a = q.p0[idx], b = q.p1[idx], c = q.p2[idx], e = q.p3[idx];
-        vol_ray_range<CLIP>(V, minv, a, b, __float_as_int(e.y), o, d, k, k_hi);
+        const int k_prog = vol_ray_range<CLIP>(V, minv, a, b, __float_as_int(e.y), o, d, k, k_hi);
         C[0] = c.x; C[1] = c.y; C[2] = c.z;
         A = e.z;
         k_last = -1;
         seen = false;
+        if constexpr (SURF) { // the sides of the sample in t_min count only for the sample right after it
+          const bool carried = (__float_as_int(e.y) & GVT_HIP_RAY_SIDES) != 0;
+          prev = carried ? ((int)c.w & 0xffff) : -1;
+          k_carry = carried ? k_prog : -1;
+        }
       }
     }
     if (!ballot64(active)) break;
@@ -104,15 +137,33 @@ __device__ __forceinline__ void volume_march_amr_body(const VolDev &V, const Amr
           k++;
           continue;
         }
+        if constexpr (SURF)
+          if (!seen && k != k_carry) prev = -1;
         seen = true;
         k_last = k;
         n_marched++;
         const int bi = ((c[2] >> 3) * V.nby + (c[1] >> 3)) * V.nbx + (c[0] >> 3);
         const uint2 word = Am.mc[bi];
-        if (V.skip && !(word.y >> 31)) { // empty by the union of every level's vertices in the macro cell: +0 per sample, whatever grid it is in
+        // Plain: empty by the union of every level's vertices in the macro cell: +0 per sample, whatever grid it is in.  SURF: the cell word
+        // is built from that union too (upload_cells reads the merged ranges), so no sample of any level in it changes an isovalue side
+        unsigned pl = 0u;
+        bool skip;
+        if constexpr (SURF) {
+          float p[3];
+          vol_point(V, o, d, k, p);
+          pl = surf_plane_sides(S, p);
+          const unsigned cell = V.skip ? S.cells[bi] : 0u;
+          skip = (cell & VOL_CELL_SKIP) && (prev < 0 || prev == (int)((cell & 0xffffu) | pl));
+          if (skip) prev = (int)((cell & 0xffffu) | pl);
+        } else {
+          skip = V.skip && !(word.y >> 31);
+        }
+        if (skip) {
           if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; }
           const int kj = vol_jump_target(V, o, d, k, k_hi, c);
-          if (kj > k) {
+          bool jump = kj > k;
+          if constexpr (SURF) jump = jump && surf_planes_clear(V, S, o, d, k, kj);
+          if (jump) {
             n_marched += (unsigned long long)(kj - k);
             k_last = kj;
             k = kj;
@@ -123,34 +174,86 @@ __device__ __forceinline__ void volume_march_amr_body(const VolDev &V, const Amr
         n_gathered++;
         const float *p;
         size_t sy, sz;
-        if (amr_descend(V, Am, word, c, f, p, sy, sz)) n_refined++;
+        int log2_r;
+        if (amr_descend(V, Am, word, c, f, p, sy, sz, log2_r)) n_refined++;
         const float v = amr_gather(p, sy, sz, f);
-        vol_accumulate(V, v, C, A);
+        VolCorners G;
+        if constexpr (SURF || LIT) amr_corners(p, sy, sz, G);
+        if constexpr (SURF) {
+          unsigned sides = pl;
+          for (int i = 0; i < S.n_iso; i++)
+            if (v >= S.iso[i]) sides |= 1u << i;
+          unsigned crossed = prev < 0 ? 0u : (sides ^ (unsigned)prev);
+          prev = (int)sides;
+          if (crossed) {
+            float gc[3] = { 0.f, 0.f, 0.f }; // the isovalues crossed here share one gradient: the final cell's
+            if (crossed & ((1u << S.n_iso) - 1u)) vol_gradient(amr_fine_spacing(V, log2_r), G, f, gc);
+            while (crossed && A < GVT_HIP_VOLUME_OPAQUE_A) {
+              const int i = __ffs((int)crossed) - 1;
+              crossed &= crossed - 1u;
+              n_crossed++;
+              if (i < S.n_iso) {
+                surf_composite(S, vol_lookup(V, S.iso[i]), gc, C, A);
+              } else {
+                const float4 P = S.plane[i - S.n_iso];
+                const float g[3] = { P.x, P.y, P.z };
+                surf_composite(S, vol_lookup(V, v), g, C, A);
+              }
+            }
+            if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
+          }
+        }
+        if constexpr (LIT) n_shaded += vol_accumulate_lit<float, false>(amr_fine_spacing(V, log2_r), S, NoGhost{}, c, v, G, f, C, A);
+        else vol_accumulate(V, v, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }
       if (done) {
-        vol_write_back<false>(V, q, idx, k_last, C, A, -1);
+        vol_write_back<SURF>(V, q, idx, k_last, C, A, prev);
         active = false;
       }
     }
   }
+  unsigned long long n_cr = n_crossed;
   for (int s = 32; s >= 1; s >>= 1) {
     n_marched += __shfl_xor(n_marched, s);
     n_gathered += __shfl_xor(n_gathered, s);
     n_refined += __shfl_xor(n_refined, s);
+    if constexpr (SURF) n_cr += __shfl_xor(n_cr, s);
+    if constexpr (LIT) n_shaded += __shfl_xor(n_shaded, s);
   }
   if (lane_id() == 0 && n_marched) {
     atomicAdd(&stats[0], n_marched);
     atomicAdd(&stats[1], n_gathered);
     if (n_refined) atomicAdd(&stats[4], n_refined);
+    if constexpr (SURF)
+      if (n_cr) atomicAdd(&stats[2], n_cr);
+    if constexpr (LIT)
+      if (n_shaded) atomicAdd(&stats[3], n_shaded);
   }
 }
 
+// The entry points.  The plain one is the march AMR volumes always had; the three shaded ones (GVT_HIP_VOLUME_AMR_SHADED) receive the
+// tables the plain shaded marches receive: SurfDev with surfaces, the lights alone (LightDev) without
 template <bool CLIP>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_amr(VolDev V, AmrDev Am, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
                                                                 unsigned long long *__restrict__ stats) {
-  volume_march_amr_body<CLIP>(V, Am, q, n, minv, work, stats);
+  volume_march_amr_body<false, false, CLIP>(V, Am, NoSurf{}, q, n, minv, work, stats);
+}
+template <bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_amr_surf(VolDev V, AmrDev Am, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                     unsigned long long *__restrict__ stats) {
+  volume_march_amr_body<true, false, CLIP>(V, Am, S, q, n, minv, work, stats);
+}
+template <bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_amr_lit(VolDev V, AmrDev Am, LightDev L, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                    unsigned long long *__restrict__ stats) {
+  volume_march_amr_body<false, true, CLIP>(V, Am, L, q, n, minv, work, stats);
+}
+template <bool CLIP>
+__global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_amr_surf_lit(VolDev V, AmrDev Am, SurfDev S, RayPlanes q, unsigned n, Mat4 minv, unsigned *__restrict__ work,
+                                                                         unsigned long long *__restrict__ stats) {
+  volume_march_amr_body<true, true, CLIP>(V, Am, S, q, n, minv, work, stats);
 }
 
 // ---- the subgrids' part of the macro cells' value ranges.  A work item is (subgrid, level-0 macro cell whose closed box holds some of its

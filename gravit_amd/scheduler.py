@@ -560,6 +560,9 @@ class VolumeTracer:
     """Tracer<ImageScheduler> over the bricks of one volume instance (gvt_hip_volume_frame): bricks = scenes.split_volume(...) (or one
     VolumeData), m = the instance's matrix (None: identity).  Bricks may carry AMR subgrids (scenes.split_amr_volume, scenes.refine).  The world box of a brick is its box under m (scenes.instance_bbox).
     native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width).
+    amr_shaded: HipVolumeAdapter's -- the bricks' subgrids are set with capi.VOLUME_AMR_SHADED, so set_surfaces, set_lights and set_shading work
+    on AMR bricks too (isovalues, slice planes and lit fog in the refined cells); such frames take the loop (the fused and the shadowed
+    frames treat a brick with subgrids as ever).  Without it (the default) the setters are refused on a brick that has subgrids.
     fused: frame() goes through gvt_hip_volume_frame_fused -- every brick in ONE march launch where the frame is eligible (plain bricks of
     one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop.
     fused_shaded (with fused): frame() goes through gvt_hip_volume_frame_fused_shaded with both bits (fused_allow), so frames with
@@ -583,7 +586,7 @@ class VolumeTracer:
     again after the scene changed.  A frame that needs a grid and has none is refused (GvtHipError)."""
 
     def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2,
-                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False):
+                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -598,7 +601,7 @@ class VolumeTracer:
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
         _refuse_turned_bricks(self.m, len(bricks), "VolumeTracer")
         self.minv = instance_matrices(self.m)[0]
-        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native) for b in bricks]
+        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native, amr_shaded) for b in bricks]
         for a in self.adapters:
             a.set_transfer(tf)
         self.inst_lo, self.inst_hi = _brick_boxes(bricks, self.m)
@@ -885,9 +888,9 @@ class HipVolumeBackend:
     """One rank's device state under the Domain scheduler over the bricks of one volume instance, with HipBackend's method names (the
     loops of DomainTracer drive it).  Every brick has a top-level box and a queue here; only the owned ones (owned[i], None: all) have
     an adapter.  The queue of a brick this rank does not own is its outgoing list to that brick's owner.  A ray that ends on this rank,
-    OPAQUE or EXTERNAL, deposits into this rank's framebuffer.  bricks, m, sampling_rate, skip, native: VolumeTracer's."""
+    OPAQUE or EXTERNAL, deposits into this rank's framebuffer.  bricks, m, sampling_rate, skip, native, amr_shaded: VolumeTracer's."""
 
-    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, owned=None):
+    def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, owned=None, amr_shaded=False):
         from .adapter import HipVolumeAdapter
         from .scenes import instance_matrices, mat_translate_scale
 
@@ -898,7 +901,7 @@ class HipVolumeBackend:
         self.minv = instance_matrices(self.m)[0]
         self.n_inst = len(bricks)
         self.owned = [True] * self.n_inst if owned is None else [bool(o) for o in owned]
-        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native) if self.owned[i] else None for i, b in enumerate(bricks)]
+        self.adapters = [HipVolumeAdapter(b, sampling_rate, skip, native, amr_shaded) if self.owned[i] else None for i, b in enumerate(bricks)]
         for a in self.local_adapters():
             a.set_transfer(tf)
         self.inst_lo, self.inst_hi = _brick_boxes(bricks, self.m)
@@ -1108,7 +1111,7 @@ class MixedTracer:
     explicit.  set_camera(), update() and set_surfaces() do not bake."""
 
     def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
-                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False):
+                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -1123,8 +1126,8 @@ class MixedTracer:
         self.depth = DepthPlane(camera.width, camera.height)
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
                                    fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias,
-                                   mesh_shadows=mesh_shadows, fused_central=fused_central)
-        # (fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; fused_central: with CENTRAL bricks too; shadows: the volume's surfaces shadowed by the
+                                   mesh_shadows=mesh_shadows, fused_central=fused_central, amr_shaded=amr_shaded)
+        # (amr_shaded: AMR bricks take surfaces and lit fog, in the clipped frame too; fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; fused_central: with CENTRAL bricks too; shadows: the volume's surfaces shadowed by the
         # volume; fog_shadows: its lit fog too, from the baked light grids; mesh_shadows: both shadowed by the meshes as well, from the baked
         # occluder grids -- without it the meshes cast no shadow into the volume)
         self.mesh_shadows = bool(mesh_shadows)

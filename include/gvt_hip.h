@@ -549,7 +549,7 @@ int gvt_hip_volume_get_shaded(gvt_hip_volume *, uint64_t *samples_shaded);
  * it while the kind is CENTRAL; another voxel type than the volume's; unknown flag bits; a null volume or a null faces.
  * gvt_hip_volume_update_samples[_typed] leaves the layers alone (see there).
  * _set_gradient(CENTRAL) is accepted only when every face that is not on the global boundary has a layer, and refused on a volume with
- * AMR subgrids (as _set_subgrids is on a CENTRAL volume: AMR takes no shading); an unknown kind is refused; each refusal changes nothing.
+ * AMR subgrids (as _set_subgrids is on a CENTRAL volume: AMR shades with the cell gradient only); an unknown kind is refused; each refusal changes nothing.
  * Bricking: with its faces a brick sees every global vertex a sample it owns can reach, so g is a function of global vertex values
  * and global indices only, and the image is the same bits for every bricking -- unconditionally, since CENTRAL cannot be set without the
  * layers.  tests/volume_smooth_checker.py restates the contract in numpy.
@@ -632,10 +632,31 @@ int gvt_hip_fb_composite_over(gvt_hip_fb *front, const gvt_hip_fb *back, const g
  * DEVIATIONS.  One lattice for all levels: a refined region is not sampled more densely by itself (raise sampling_rate; the opacity
  * correction keeps the look).  The field is discontinuous across coarse-fine faces (no ghost or blend cells), as a cell-wise AMR
  * sampler's is.  A level-1 subgrid must lie inside one brick: the caller cuts it otherwise.
- * OUT OF SCOPE, refused.  A volume that has subgrids takes no surfaces, no gradient shading and no in-place update: on it
- * _set_surfaces with any surface, _set_shading with GVT_HIP_VOLUME_SHADE_GRADIENT and _update_samples / _update_samples_typed return
- * GVT_HIP_ERR_INVALID and change nothing.  A new time step of an AMR volume is _set_subgrids with n = 0, _update_samples and
- * _set_subgrids again, or a new volume.  The clipped march (GVT_HIP_RAY_CLIP, gvt_hip_volume_frame_clipped) works on AMR volumes. */
+ * SURFACES AND LIT FOG (the flag GVT_HIP_VOLUME_AMR_SHADED of _set_subgrids; Volume::SetIsovalues / SetSlices and the AMR grids live on
+ * one object in the reference).  A set of subgrids given with the flag takes isovalues, slice planes and GVT_HIP_VOLUME_SHADE_GRADIENT.
+ * Everything of "surfaces of a volume" and "lit volumes" holds with these substitutions: v_k, the eight corner values v000..v111 and the
+ * fractions f are those of the FINAL grid's cell after the descent; the gradient's divisor is the final grid's spacing per axis,
+ * s_a = spacing.a / (float)R with R the product of the ratios down to the final grid (1 at level 0; a power of two up to 512, so s_a is
+ * exact), i.e. g.a = (the lerp nest of corner differences stated there) / s_a.  Plane sides use the lattice point p_k as ever, a plane's
+ * colour is looked up at the descended v_k, the isosurface rule len > 0 and the fog rule 0 < len < +Inf stay, and so do the side-mask
+ * carry (GVT_HIP_RAY_SIDES, the t field), "a crossing is rendered at the sample after it", GVT_HIP_RAY_OPAQUE and GVT_HIP_RAY_CLIP.
+ * tests/volume_amr_surface_checker.py restates this in numpy.  Skipping stays exact: the surface skip word of a macro cell is built from
+ * the union range above, and a fine cell lies inside one macro cell, so with no isovalue within that range no sample of any level in
+ * the cell changes an isovalue side; GVT_HIP_VOLUME_NO_SKIP gives the same bits, the rays' t field included.  _get_crossings, _get_shaded
+ * and _get_amr_info count these marches too (samples_refined as before; amr_marches counts every AMR entry point).
+ * DEVIATION.  The field is discontinuous across coarse-fine faces, so a crossing can be detected between a coarse and a fine sample
+ * where a continuous field would have none.  It is deterministic and belongs to the owner of the later sample: the image is the same
+ * bits for every bricking that keeps each level-1 subgrid in one brick.
+ * Without the flag (the default) a volume that has subgrids takes no surfaces and no gradient shading: _set_surfaces with any surface
+ * and _set_shading with GVT_HIP_VOLUME_SHADE_GRADIENT return GVT_HIP_ERR_INVALID and change nothing, as _set_subgrids without the flag
+ * does on a volume that has either.
+ * OUT OF SCOPE, refused on every AMR volume, flagged or not, with GVT_HIP_ERR_INVALID and nothing changed: central gradients
+ * (_set_gradient(CENTRAL), and _set_subgrids on a CENTRAL volume) and in-place updates (_update_samples / _update_samples_typed).  A new
+ * time step of an AMR volume is _set_subgrids with n = 0, _update_samples and _set_subgrids again, or a new volume.  The fused,
+ * shadowed, fog-shadowed and mesh-shadowed frames and both bakes do not take bricks with subgrids (the frames fall back to the loop or
+ * refuse, as stated with each).  The clipped march (GVT_HIP_RAY_CLIP, gvt_hip_volume_frame_clipped) works on AMR volumes, shaded ones
+ * included. */
+#define GVT_HIP_VOLUME_AMR_SHADED 8          /* _set_subgrids: this set takes surfaces and gradient shading (2 and 4 stay unknown bits) */
 #define GVT_HIP_VOLUME_MAX_SUBGRIDS 4096
 #define GVT_HIP_VOLUME_MAX_LEVELS 4          /* level 0 and up to three levels of subgrids */
 typedef struct gvt_hip_subgrid {
@@ -652,7 +673,11 @@ typedef struct gvt_hip_subgrid {
  * or 8; a parent outside [-1, own index); cells < 1 on an axis; a box that leaves its parent's cells (for parent -1: the cells the brick
  * owns, [offset, offset + counts - 1)); two subgrids of one parent that share a cell; more than GVT_HIP_VOLUME_MAX_LEVELS levels;
  * n < 0 or n > GVT_HIP_VOLUME_MAX_SUBGRIDS; an unknown flag bit; a subgrid of 2^24 or more vertices on an axis or 2^32 - 1 or more in
- * all; a volume that has surfaces or GVT_HIP_VOLUME_SHADE_GRADIENT. */
+ * all; without GVT_HIP_VOLUME_AMR_SHADED a volume that has surfaces or GVT_HIP_VOLUME_SHADE_GRADIENT; a CENTRAL volume (n > 0).
+ * flags: GVT_HIP_VOLUME_DEVICE | GVT_HIP_VOLUME_AMR_SHADED.  The volume remembers the flags of its current set.  With _AMR_SHADED the call
+ * is accepted on a volume that already has surfaces and / or gradient shading, for n > 0 and for n == 0 (n == 0: the plain surface /
+ * lit volume again, through the kernels it launched before), and while the volume holds the flagged set _set_surfaces and
+ * _set_shading(GRADIENT) are accepted; they rebuild the per-cell skip table from the merged ranges, as on a plain volume. */
 int gvt_hip_volume_set_subgrids(gvt_hip_volume *, const gvt_hip_subgrid *grids, const float *const *samples, int n, int flags);
 typedef struct gvt_hip_volume_amr_info {
   int32_t n_subgrids, n_levels; /* n_levels: level 0 and the deepest subgrid's (1 without subgrids) */

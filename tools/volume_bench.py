@@ -29,6 +29,10 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              (the plain path), (c) one ratio-2 subgrid over the central eighth, (d) as (c) plus a ratio-4
                                              child over the subgrid's central eighth; then (e) the uniform 512^3 grid (c) would need, for
                                              memory and time beside it.  --sizes N: another level-0 size ((e) is 2 N)
+  python tools/volume_bench.py --amr --surfaces   (and / or --amr --shade) shaded AMR volumes (GVT_HIP_VOLUME_AMR_SHADED): grid, subgrids,
+                                             table and rate of (d) above; three frames alternating in one process: the AMR volume with two
+                                             isovalues and a light (--surfaces) or lit by one light (--shade), the same level-0 volume without
+                                             subgrids under the same surfaces / shading, and the plain AMR frame; the two ratios beside them
   python tools/volume_bench.py --domains 1 2 4 8   volume domains across ranks: the "thin" 1080p frame of the 256^3 grid in 8 and in 64 bricks
                                              (round-robin owners) through scheduler.VolumeDomainTracer, W ranks as W threads of this process on
                                              ONE GPU over the stand-in transport of tests/fake_dist.py, one lock around library calls.  Per W and
@@ -591,6 +595,47 @@ def run_amr(n, steps, warmup, rate):
     return out
 
 
+def run_amr_shaded(n, steps, warmup, rate, what):
+    """--amr --surfaces / --amr --shade: run_amr's grid, subgrids (ratio 2 with its ratio-4 child), table and rate.  Three tracers alternate
+    frame by frame: the flagged AMR volume under the surfaces (what == "surfaces": the "reached" isovalues, opacity 0.3, one light) or
+    the lit shading (what == "shade": one light); the same level-0 volume without subgrids under the same surfaces / shading; and the
+    plain AMR frame.  One line."""
+    base = noise(n, "f32")
+    cells = n - 1
+    lo, ext = cells // 4, cells // 2
+    d = scenes.VolumeData(base.data, base.origin, base.spacing)
+    s0 = scenes.refine(d, (lo,) * 3, (ext,) * 3, 2, seed=1)
+    scenes.refine(d, (ext // 2,) * 3, (ext,) * 3, 4, parent=s0, seed=2)
+    cam, t = camera(), transfer("thin")
+    trs = {"amr_shaded": VolumeTracer(d, cam, t, sampling_rate=rate, amr_shaded=True), "plain_shaded": VolumeTracer(base, cam, t, sampling_rate=rate),
+           "amr_fog": VolumeTracer(d, cam, t, sampling_rate=rate)}
+    for k in ("amr_shaded", "plain_shaded"):
+        if what == "surfaces":
+            trs[k].set_surfaces(SURFACE_MODES["reached"], (), 0.3).set_lights([((3.0, 4.0, 5.0), (1.0, 1.0, 1.0))])
+        else:
+            trs[k].set_lights(SHADE_LIGHTS[:1]).set_shading(True)
+    ms = {k: [] for k in trs}
+    first = {}
+    for i in range(warmup + steps):
+        for k, tr in trs.items():
+            if i == warmup:
+                first[k] = tr.stats()
+            ms[k].append(timed(tr.frame))
+    out = {"mode": "amr_" + what, "n": n, "sampling_rate": rate, "n_subgrids": 2, "n_levels": 3}
+    for k, tr in trs.items():
+        st, v = tr.stats(), ms[k][warmup:]
+        out.update({k + "_ms_median": med(v), k + "_ms_min": round(min(v), 3), k + "_ms_max": round(max(v), 3),
+                    k + "_samples_per_frame": int((st["samples_marched"] - first[k]["samples_marched"]) / steps),
+                    k + "_samples_refined_per_frame": int((st["samples_refined"] - first[k]["samples_refined"]) / steps),
+                    k + "_crossings_per_frame": int((st["crossings_rendered"] - first[k]["crossings_rendered"]) / steps),
+                    k + "_samples_shaded_per_frame": int((st["samples_shaded"] - first[k]["samples_shaded"]) / steps),
+                    k + "_amr_marches_per_frame": (st["amr_marches"] - first[k]["amr_marches"]) / steps,
+                    k + "_lit_pixels": int((tr.framebuffer(False)[..., 3] > 0).sum())})
+    out["amr_shaded_over_plain_shaded"] = round(out["amr_shaded_ms_median"] / out["plain_shaded_ms_median"], 4)
+    out["amr_shaded_over_amr_fog"] = round(out["amr_shaded_ms_median"] / out["amr_fog_ms_median"], 4)
+    return out
+
+
 def run_domains(n, split, world, steps, warmup, rate, kind, vol, per_queue, overlap):
     """One bricking at one world size: `world` threads, each a rank with its own HipVolumeBackend, frames started together."""
     import threading
@@ -808,7 +853,14 @@ def main():
                         out["runs"].append(r)
                         print(json.dumps(r), flush=True)
         a.sizes = []
-    if a.amr:
+    if a.amr and (a.surfaces or a.shade):  # the shaded AMR frame against the plain volume's shaded frame and against the plain AMR frame
+        for n in ([256] if a.sizes == [256, 512] else a.sizes):
+            for what in (["surfaces"] if a.surfaces else []) + (["shade"] if a.shade else []):
+                r = run_amr_shaded(n, a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate, what)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+        a.sizes = []
+    elif a.amr:
         for n in ([256] if a.sizes == [256, 512] else a.sizes):
             for r in run_amr(n, a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate):
                 out["runs"].append(r)
