@@ -42,7 +42,7 @@ SYMBOLS = [
     "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
     "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
     "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
-    "gvt_hip_volume_frame_fused", "gvt_hip_volume_frame_fused_shaded",
+    "gvt_hip_volume_frame_fused", "gvt_hip_volume_frame_fused_shaded", "gvt_hip_volume_frame_fused_amr",
     "gvt_hip_volume_frame_shadowed",
     "gvt_hip_volume_light_grid_bake", "gvt_hip_volume_light_grid_download", "gvt_hip_volume_light_grid_info", "gvt_hip_volume_light_grid_release",
     "gvt_hip_volume_frame_fog_shadowed",
@@ -115,6 +115,14 @@ class VolumeFusedShadedStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class VolumeFusedAmrStats(C.Structure):
+    """gvt_hip_volume_fused_amr_stats: gvt_hip_volume_fused_shaded_stats' fields, then the refined samples and the AMR bricks of the frame."""
+    _fields_ = VolumeFusedShadedStats._fields_ + [("samples_refined", C.c_uint64), ("amr_bricks", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 class VolumeShadowParams(C.Structure):
@@ -193,6 +201,7 @@ class VolumeMeshShadowStats(C.Structure):
 
 
 FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
+FUSED_AMR = 16  # gvt_hip_volume_frame_fused_amr's further allow bit: frames in which some or all bricks have AMR subgrids may be fused
 FUSED_CENTRAL = 8  # ... and such frames whose bricks all shade with VOLUME_GRADIENT_CENTRAL (the kernel's CENTRAL instantiation; its bit in features)
 VOLUME_ALLOW_CENTRAL = 2  # flags of VolumeShadowParams, VolumeLightGridParams and VolumeOccluderParams: accept frames whose bricks are all CENTRAL
 
@@ -269,6 +278,7 @@ def load():
         lib.gvt_hip_volume_frame_fused.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_frame_fused_shaded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                           C.c_void_p]
+        lib.gvt_hip_volume_frame_fused_amr.argtypes = lib.gvt_hip_volume_frame_fused_shaded.argtypes
         lib.gvt_hip_volume_frame_shadowed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.c_void_p]
         lib.gvt_hip_volume_frame_fog_shadowed.argtypes = lib.gvt_hip_volume_frame_shadowed.argtypes
@@ -362,5 +372,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeShadowParams", "VolumeShadowStats", "VolumeLightGridParams", "VolumeLightGridStats", "VolumeLightGridState", "VolumeFogShadowStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeFusedAmrStats", "VolumeShadowParams", "VolumeShadowStats", "VolumeLightGridParams", "VolumeLightGridStats", "VolumeLightGridState", "VolumeFogShadowStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

@@ -48,11 +48,12 @@ enum ScratchSlot {
   SCR_HOP,         // merged chains with hops: the instance every ray is in now
   SCR_WIRE_TABLE,  // the queue table of a batched wire conversion (trace.hip wire_table)
   SCR_VOL_KEEP,    // the keep mask of gvt_hip_volume_camera_filter on the device (volume.hip)
-  SCR_VOL_BRICKS, SCR_VOL_FUSED, // the fused frame's per-brick records and its counter words, six or with shadows eleven (volume.hip volume_frame_fused)
+  SCR_VOL_BRICKS, SCR_VOL_FUSED, // the fused frame's per-brick records and its counter words, six, with subgrids seven, with shadows eleven (volume.hip volume_frame_fused)
   SCR_VOL_GRIDS,   // the light grids' per-brick table beside SCR_VOL_BRICKS: the bake's work list and planes, the fog-shadowed frame's planes (volume.hip)
   SCR_VOL_OCC_RAYS, SCR_VOL_OCC, // the occluder bake: a chunk's p0 / p1 ray planes | its uint8 O words (volume.hip; the chunk's any-hit flags are SCR_GENERAL's, its
                    // per-brick table SCR_VOL_GRIDS', its counter word SCR_VOL_FUSED's)
   SCR_VOL_GHOSTS,  // the fused frames' per-brick ghost face pointers beside SCR_VOL_BRICKS, for the kernels' CENTRAL instantiations (volume.hip volume_frame_fused)
+  SCR_VOL_AMR,     // the fused frame's per-brick AMR tables beside SCR_VOL_BRICKS, for the AMR instantiations (GVT_HIP_FUSED_AMR; volume.hip volume_frame_fused)
   SCRATCH_COUNT
 };
 struct Knobs {

@@ -23,6 +23,9 @@
 //                                           GVT_HIP_FUSED_CENTRAL / GVT_HIP_VOLUME_ALLOW_CENTRAL: the CENTRAL instantiations of this kernel
 //                                           and of the three shadowed ones below, for frames whose bricks all shade with central
 //                                           differences; a lane carries its brick's ghost pointer from brick to brick (FusedGhost)
+//   gvt_hip_volume_frame_fused_amr / k_volume_march_fused_amr, k_volume_march_fused_shaded_amr   ... and, with GVT_HIP_FUSED_AMR, frames in
+//                                           which some or all bricks have subgrids: the same structure around the AMR visit; a lane carries
+//                                           its brick's AMR tables, all null on a brick without subgrids (volume_fused_amr.inc)
 //   gvt_hip_volume_frame_shadowed / k_volume_march_fused_shadow   ... with the crossings lit only by the lights that reach them: a lane marches the
 //                                           shadow rays of its camera ray itself, from brick to brick (volume_fused_shadow.inc)
 //   gvt_hip_volume_light_grid_bake / k_volume_bake_light   the transmittance towards every light at every grid vertex, kept beside the samples
@@ -880,6 +883,7 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 #include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges
 #include "volume_fused.inc" // k_volume_march_fused
 #include "volume_fused_shaded.inc" // k_volume_march_fused_shaded
+#include "volume_fused_amr.inc" // k_volume_march_fused_amr, k_volume_march_fused_shaded_amr
 #include "volume_fused_shadow.inc" // k_volume_march_fused_shadow
 #include "volume_light_grid.inc" // k_volume_bake_light
 #include "volume_fused_fog.inc" // k_volume_march_fused_fog
@@ -1654,11 +1658,13 @@ namespace {
 bool same_bits(const void *a, const void *b, size_t bytes) { return std::memcmp(a, b, bytes) == 0; }
 
 // Eligibility, decided per call from the volumes as they are now: bricks of ONE grid (global origin, spacing, dt, table, value range, skip
-// flag and minv equal as bits), one voxel type, no subgrids, and nothing the kernels allowed do not do.  allow = 0 (gvt_hip_volume_frame_fused):
+// flag and minv equal as bits), one voxel type, no subgrids without GVT_HIP_FUSED_AMR, and nothing the kernels allowed do not do.  allow = 0 (gvt_hip_volume_frame_fused):
 // no surfaces and no lit shading (the gradient kind is inert then).  GVT_HIP_FUSED_SURFACES / _LIT drop those two clauses; a frame that
 // has an isovalue or effective lit shading then needs the cell gradient on every brick -- or, with GVT_HIP_FUSED_CENTRAL, ONE kind on
 // every brick -- and what the bricks must share of surfaces and lights is compared as bits too.  features: the bits of `allow` the frame
-// needs (0: the plain fused kernel; GVT_HIP_FUSED_CENTRAL: the bricks shade with CENTRAL, the kernels' CENTRAL instantiations run)
+// needs (0: the plain fused kernel; GVT_HIP_FUSED_CENTRAL: the bricks shade with CENTRAL, the kernels' CENTRAL instantiations run;
+// GVT_HIP_FUSED_AMR: at least one brick has subgrids, the AMR instantiations run -- such a brick is F32 and CELL, the setters see to it, so
+// a frame that reads a gradient and mixes it with CENTRAL bricks falls out through the "mixed kinds" clause)
 bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, uint32_t allow, uint32_t &features, const char **why = nullptr) {
   features = 0;
   const auto no = [&](const char *clause) { // (why: the clause that fails, for the entry point that refuses such a frame instead of taking the loop)
@@ -1669,11 +1675,13 @@ bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_
   const gvt_hip_volume *A = volumes[0];
   const bool surf = A->n_iso + A->n_pl > 0, lit = A->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && A->n_lights > 0;
   int kind = -1; // the gradient kind of the first brick that reads a gradient (none yet)
+  bool amr = false; // a brick has subgrids
   if ((surf && !(allow & GVT_HIP_FUSED_SURFACES)) || (lit && !(allow & GVT_HIP_FUSED_LIT))) return no("a feature the allow word lacks");
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     if (!B->has_tf) return no("a brick without a transfer function");
-    if (!B->sub.empty()) return no("a brick with AMR subgrids");
+    if (!B->sub.empty() && !(allow & GVT_HIP_FUSED_AMR)) return no("a brick with AMR subgrids");
+    amr = amr || !B->sub.empty();
     if ((B->n_iso + B->n_pl > 0) != surf || (B->shade == GVT_HIP_VOLUME_SHADE_GRADIENT && B->n_lights > 0) != lit) return no("bricks that differ in having surfaces or lit shading");
     if (B->n_iso > 0 || lit) { // (planes alone read no gradient: the kind is inert)
       if (B->grad == GVT_HIP_VOLUME_GRADIENT_CENTRAL && !(allow & GVT_HIP_FUSED_CENTRAL)) return no("central gradients on a brick of a frame with an isovalue or lit shading");
@@ -1696,7 +1704,8 @@ bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_
       if (!same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights) || !same_bits(B->lcol, A->lcol, sizeof(A->lcol[0]) * (size_t)A->n_lights)) return no("bricks with different lights or shading");
     }
   }
-  features = (surf ? GVT_HIP_FUSED_SURFACES : 0u) | (lit ? GVT_HIP_FUSED_LIT : 0u) | (kind == GVT_HIP_VOLUME_GRADIENT_CENTRAL ? GVT_HIP_FUSED_CENTRAL : 0u);
+  features = (surf ? GVT_HIP_FUSED_SURFACES : 0u) | (lit ? GVT_HIP_FUSED_LIT : 0u) | (kind == GVT_HIP_VOLUME_GRADIENT_CENTRAL ? GVT_HIP_FUSED_CENTRAL : 0u) |
+             (amr ? GVT_HIP_FUSED_AMR : 0u);
   return true;
 }
 
@@ -1709,6 +1718,16 @@ void launch_fused_shaded(uint32_t features, unsigned blocks, hipStream_t st, con
   if (surf && lit) k_volume_march_fused_shaded<VT, CLIP, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
   else if (surf) k_volume_march_fused_shaded<VT, CLIP, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
   else k_volume_march_fused_shaded<VT, CLIP, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
+}
+
+// the AMR kernels' instantiation for the frame's features (GVT_HIP_FUSED_AMR is among them): plain, or one of the three shaded combinations
+template <bool CLIP, typename... Args>
+void launch_fused_amr(uint32_t features, unsigned blocks, hipStream_t st, const gvt_hip_volume *V0, const Mat4 &M, VolDev U, Args... args) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0, lit = (features & GVT_HIP_FUSED_LIT) != 0;
+  if (surf && lit) k_volume_march_fused_shaded_amr<CLIP, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
+  else if (surf) k_volume_march_fused_shaded_amr<CLIP, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
+  else if (lit) k_volume_march_fused_shaded_amr<CLIP, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
+  else k_volume_march_fused_amr<CLIP><<<blocks, VOL_BLOCK, 0, st>>>(U, args...);
 }
 
 // the shadowed kernel's instantiation: clipped or not, lit fog or not (surfaces are implied)
@@ -1763,10 +1782,12 @@ void launch_fused_mesh(uint32_t features, const gvt_hip_volume *V0, const gvt_hi
 // its five further counter words, read back in the same wait.  fog (gvt_hip_volume_frame_fog_shadowed; shadow is given and features has
 // LIT): the launch is k_volume_march_fused_fog's, and the bricks' light grid planes travel in a second table beside the records.  mesh
 // (gvt_hip_volume_frame_mesh_shadowed; shadow is given): the launch is k_volume_march_fused_mesh's, and that table holds the occluder
-// grid's planes too (the light grid's only where fog is set as well)
+// grid's planes too (the light grid's only where fog is set as well).  GVT_HIP_FUSED_AMR in features (never with shadow, fog, mesh or
+// GVT_HIP_FUSED_CENTRAL: those callers do not allow the bit, and a brick with subgrids is CELL): the launch is the AMR kernels', the
+// bricks' AMR tables travel in a second table beside the records, read from the volumes NOW, and *refined_out gets the seventh counter
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
                        gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S, const ShadowDev *shadow = nullptr,
-                       uint64_t *shadow_out = nullptr, bool fog = false, bool mesh = false) {
+                       uint64_t *shadow_out = nullptr, bool fog = false, bool mesh = false, uint64_t *refined_out = nullptr) {
   Ctx &C = gctx();
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;
@@ -1779,7 +1800,9 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
   static_assert(VOL_FUSED_SHADED_STATS >= VOL_FUSED_STATS, "one block of counter words serves both kernels");
   static_assert(VOL_FUSED_SHADOW_STATS >= VOL_FUSED_SHADED_STATS, "... and the shadowed kernel");
-  const size_t n_words = shadow ? VOL_FUSED_SHADOW_STATS : VOL_FUSED_SHADED_STATS;
+  static_assert(VOL_FUSED_SHADOW_STATS >= VOL_FUSED_AMR_STATS && VOL_FUSED_AMR_REFINED == VOL_FUSED_SHADED_STATS, "... and the AMR kernels, whose word follows the shaded kernel's six");
+  const bool amr = (features & GVT_HIP_FUSED_AMR) != 0;
+  const size_t n_words = shadow ? VOL_FUSED_SHADOW_STATS : amr ? VOL_FUSED_AMR_STATS : VOL_FUSED_SHADED_STATS;
   unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
@@ -1792,13 +1815,18 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   const bool central = (features & GVT_HIP_FUSED_CENTRAL) != 0;
   const void **d_faces = central ? (const void **)scratch_get(SCR_VOL_GHOSTS, sizeof(void *) * n_inst) : nullptr;
   if (central && !d_faces) return GVT_HIP_ERR_DEVICE;
+  // the AMR instantiations' table: the bricks' four AMR pointers, beside the records (AmrDev, volume_fused_amr.inc)
+  AmrDev *d_amr = amr ? (AmrDev *)scratch_get(SCR_VOL_AMR, sizeof(AmrDev) * n_inst) : nullptr;
+  if (amr && !d_amr) return GVT_HIP_ERR_DEVICE;
   static_assert((sizeof(FusedBrick) + sizeof(MeshBrick) + sizeof(void *)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table, the grids' and the ghosts' fit the staging block");
+  static_assert((sizeof(FusedBrick) + sizeof(AmrDev)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "... and so do the brick table and the AMR table, which takes the grids' and the ghosts' place (an AMR frame has neither)");
   void *stage = nullptr;
   if ((rc = pinned_stage_begin(&stage))) return rc;
   FusedBrick *h = (FusedBrick *)stage;
   FogBrick *hg = (FogBrick *)(h + VOL_DEST_MAX);
   MeshBrick *hm = (MeshBrick *)(h + VOL_DEST_MAX);
   const void **hf = (const void **)(hm + VOL_DEST_MAX);
+  AmrDev *ha = (AmrDev *)(h + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     FusedBrick R{};
@@ -1807,6 +1835,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
     if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
     else if (fog) hg[i].grid = B->d_lgrid;
     if (central) hf[i] = B->d_ghost; // (null on a brick without an interior face: none of its layers is ever read)
+    if (amr) ha[i] = B->sub.empty() ? AmrDev{ nullptr, nullptr, nullptr, nullptr } : AmrDev{ B->d_amr_mc, B->d_amr_list, B->d_amr_desc, B->d_amr_vox };
     R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
     for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
     h[i] = R;
@@ -1815,6 +1844,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if (mesh) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   else if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (central) HIPCHK(hipMemcpyAsync(d_faces, hf, sizeof(void *) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if (amr) HIPCHK(hipMemcpyAsync(d_amr, ha, sizeof(AmrDev) * n_inst, hipMemcpyHostToDevice, C.stream));
   if ((rc = pinned_stage_end())) return rc;
   HIPCHK(hipMemsetAsync(work, 0, sizeof(unsigned), C.stream));
   HIPCHK(hipMemsetAsync(d_stats, 0, n_words * sizeof(unsigned long long), C.stream));
@@ -1824,7 +1854,12 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   const RayPlanes P = make_planes(q_cam->d_planes, q_cam->cap);
   const unsigned n_pix = (unsigned)(fb->w * fb->h);
   const FusedGhost HG{ d_faces, volumes[0]->gn[0], volumes[0]->gn[1], volumes[0]->gn[2] };
-  if (n)
+  if (n && amr) { // (F32 and CELL: fused_eligible has compared the voxel types, and a brick with subgrids is F32)
+    if (depth) launch_fused_amr<true>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, (const AmrDev *)d_amr, T->dev(), P, (unsigned)n, M, depth->d_t,
+                                      (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
+    else launch_fused_amr<false>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, (const AmrDev *)d_amr, T->dev(), P, (unsigned)n, M,
+                                 (const float *)nullptr, 0u, fb->d_rgba, n_pix, work, d_stats);
+  } else if (n)
     with_voxel_type(volumes[0]->vtype, [&](auto t) {
       using VT = decltype(t);
       // the shaded launches, for the kernels' CENTRAL instantiation (gh: FusedGhost) or the other (NoGhost)
@@ -1857,7 +1892,8 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
                                                                                n_pix, work, d_stats);
     });
   HIPCHK(hipGetLastError());
-  // (pinned words 16..27 of the context: six 64-bit counters; 28..31 are free, 32..41 the builder's; the shadowed frame's eleven are words 42..63)
+  // (pinned words 16..27 of the context: six 64-bit counters, and 28..29 the AMR kernels' seventh; 30..31 are free, 32..41 the builder's; the shadowed frame's eleven are words 42..63)
+  static_assert(16 + 2 * VOL_FUSED_AMR_STATS <= 32, "the AMR frame's counters end before the builder's words");
   static_assert(42 + 2 * VOL_FUSED_SHADOW_STATS <= 64, "the context has 64 pinned words");
   unsigned long long *h_stats = (unsigned long long *)(C.h_pinned + (shadow ? 42 : 16));
   HIPCHK(hipMemcpyAsync(h_stats, d_stats, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, C.stream));
@@ -1866,6 +1902,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   S.fused = 1; S.adapter_calls = 1; S.features = features;
   S.samples_marched = h_stats[0]; S.samples_gathered = h_stats[1]; S.brick_visits = h_stats[2]; S.rays_deposited = h_stats[3];
   S.crossings_rendered = h_stats[4]; S.samples_shaded = h_stats[5]; // (0 from the plain kernel: the words were cleared)
+  if (refined_out) *refined_out = amr ? h_stats[VOL_FUSED_AMR_REFINED] : 0;
   if (shadow && shadow_out)
     for (int i = 0; i < VOL_FUSED_SHADOW_STATS - VOL_FUSED_SHADED_STATS; i++) shadow_out[i] = h_stats[VOL_FUSED_SHADED_STATS + i];
   return 0;
@@ -1873,11 +1910,13 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
 
 // both fused entry points: the arguments' errors, then the fused frame where the frame is eligible under `allow`, else the loop
 int volume_frame_fused_or_loop(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
-                               gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t allow, gvt_hip_volume_fused_shaded_stats &S) {
+                               gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t allow, gvt_hip_volume_fused_shaded_stats &S,
+                               uint64_t *refined_out = nullptr) {
   int rc;
   if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
   uint32_t features = 0;
-  if (fused_eligible(volumes, minv, n_inst, allow, features)) return volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S);
+  if (fused_eligible(volumes, minv, n_inst, allow, features))
+    return volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, nullptr, nullptr, false, false, refined_out);
   return volume_frame_impl(T, volumes, m, minv, n_inst, cam, queues, fb, depth, &S.adapter_calls); // (not an error: the loop, fused = 0)
 }
 
@@ -1903,6 +1942,29 @@ extern "C" int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *T, gvt_hip_volume 
   gvt_hip_volume_fused_shaded_stats S{};
   const int rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, allow, S);
   if (!rc && stats) *stats = S;
+  return rc;
+}
+
+// the fused frame that may take bricks with subgrids (the contract: include/gvt_hip.h, "fused frame: AMR bricks"; the kernels: volume_fused_amr.inc)
+extern "C" int gvt_hip_volume_frame_fused_amr(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                                              gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t allow,
+                                              gvt_hip_volume_fused_amr_stats *stats) {
+  if (allow & ~(uint32_t)(GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | GVT_HIP_FUSED_CENTRAL | GVT_HIP_FUSED_AMR)) {
+    set_error("volume_frame_fused_amr: unknown allow bits %u", allow);
+    return GVT_HIP_ERR_INVALID;
+  }
+  gvt_hip_volume_fused_shaded_stats S{};
+  uint64_t refined = 0;
+  const int rc = volume_frame_fused_or_loop(T, volumes, m, minv, n_inst, cam, queues, fb, depth, allow, S, &refined);
+  if (!rc && stats) {
+    gvt_hip_volume_fused_amr_stats O{};
+    O.fused = S.fused; O.features = S.features; O.samples_marched = S.samples_marched; O.samples_gathered = S.samples_gathered; O.brick_visits = S.brick_visits;
+    O.rays_deposited = S.rays_deposited; O.adapter_calls = S.adapter_calls; O.crossings_rendered = S.crossings_rendered; O.samples_shaded = S.samples_shaded;
+    O.samples_refined = refined;
+    if (S.fused && (S.features & GVT_HIP_FUSED_AMR)) // (the bricks of the frame that had subgrids; 0 after the loop and after a frame without any)
+      for (size_t i = 0; i < n_inst; i++) O.amr_bricks += volumes[i]->sub.empty() ? 0u : 1u;
+    *stats = O;
+  }
   return rc;
 }
 

@@ -652,9 +652,10 @@ int gvt_hip_fb_composite_over(gvt_hip_fb *front, const gvt_hip_fb *back, const g
  * does on a volume that has either.
  * OUT OF SCOPE, refused on every AMR volume, flagged or not, with GVT_HIP_ERR_INVALID and nothing changed: central gradients
  * (_set_gradient(CENTRAL), and _set_subgrids on a CENTRAL volume) and in-place updates (_update_samples / _update_samples_typed).  A new
- * time step of an AMR volume is _set_subgrids with n = 0, _update_samples and _set_subgrids again, or a new volume.  The fused,
- * shadowed, fog-shadowed and mesh-shadowed frames and both bakes do not take bricks with subgrids (the frames fall back to the loop or
- * refuse, as stated with each).  The clipped march (GVT_HIP_RAY_CLIP, gvt_hip_volume_frame_clipped) works on AMR volumes, shaded ones
+ * time step of an AMR volume is _set_subgrids with n = 0, _update_samples and _set_subgrids again, or a new volume.  The
+ * shadowed, fog-shadowed and mesh-shadowed frames and both bakes do not take bricks with subgrids (they refuse, as stated with each),
+ * and neither do gvt_hip_volume_frame_fused and _fused_shaded (they fall back to the loop); gvt_hip_volume_frame_fused_amr with
+ * GVT_HIP_FUSED_AMR marches such bricks in the fused frame ("fused frame: AMR bricks" below).  The clipped march (GVT_HIP_RAY_CLIP, gvt_hip_volume_frame_clipped) works on AMR volumes, shaded ones
  * included. */
 #define GVT_HIP_VOLUME_AMR_SHADED 8          /* _set_subgrids: this set takes surfaces and gradient shading (2 and 4 stay unknown bits) */
 #define GVT_HIP_VOLUME_MAX_SUBGRIDS 4096
@@ -771,7 +772,7 @@ int gvt_hip_queues_append_wire(gvt_hip_queue *const *queues, size_t n, const gvt
  * queues are used by the fallback only; a fused frame leaves them cleared.  The per-brick counters of the volumes (gvt_hip_volume_info's
  * samples_marched / samples_gathered) are NOT touched by a fused frame: its counters are the call's own, below.
  * Surfaces and lit shading are taken by gvt_hip_volume_frame_fused_shaded, below; this entry point keeps its rule.
- * OUT OF SCOPE.  AMR inside a fused kernel, and central gradients without GVT_HIP_FUSED_CENTRAL below (such frames take the loop); bricks of
+ * OUT OF SCOPE.  Subgrids without GVT_HIP_FUSED_AMR and central gradients without GVT_HIP_FUSED_CENTRAL, both below (such frames take the loop); bricks of
  * different grids, tables or matrices; the Domain scheduler (a rank fusing the bricks it owns needs rays that leave for foreign bricks
  * appended to outgoing queues inside the kernel); fused as the default. */
 typedef struct {
@@ -793,7 +794,8 @@ int gvt_hip_volume_frame_fused(gvt_hip_top *, gvt_hip_volume *const *volumes, co
  * ELIGIBILITY is gvt_hip_volume_frame_fused's with two clauses relaxed: "no brick has surfaces" is dropped with
  * GVT_HIP_FUSED_SURFACES, "no effective lit shading" with GVT_HIP_FUSED_LIT.  What the bricks must share is then compared as bits
  * too: n_iso, n_pl, the isovalues, the planes and the surfaces' opacity; the number of lights, their positions and colours, ka, kd and
- * the shading mode.  Still ineligible -- the loop runs, fused = 0, no error: subgrids on any brick; without GVT_HIP_FUSED_CENTRAL,
+ * the shading mode.  Still ineligible -- the loop runs, fused = 0, no error: subgrids on any brick (this entry point refuses the bit
+ * that would take them, GVT_HIP_FUSED_AMR of gvt_hip_volume_frame_fused_amr below); without GVT_HIP_FUSED_CENTRAL,
  * GVT_HIP_VOLUME_GRADIENT_CENTRAL on any brick of a frame that has an isovalue or effective lit shading (in a frame that has neither
  * -- no isovalue and no lit shading, or planes only -- the kind stays inert, as ever, whatever the bit); a frame that needs a bit
  * `allow` lacks; everything ineligible above.
@@ -827,6 +829,46 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
                                       const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
                                       const gvt_hip_depth *depth /* may be NULL */, uint32_t allow,
                                       gvt_hip_volume_fused_shaded_stats *stats /* may be NULL */);
+
+/* ---- fused frame: AMR bricks (one more opt-in; additive: the ABI revision stays 6, no entry point above changes its rule) ----
+ * gvt_hip_volume_frame_fused_amr is gvt_hip_volume_frame_fused_shaded with one more allow bit.  It is an entry point of its own because
+ * the caller allocates the stats struct, which has to grow.  allow: GVT_HIP_FUSED_SURFACES | _LIT | _CENTRAL | _AMR; any other bit (4
+ * among them): GVT_HIP_ERR_INVALID ("allow" in the message), nothing changed.  Without GVT_HIP_FUSED_AMR the call is
+ * gvt_hip_volume_frame_fused_shaded in every respect, and samples_refined and amr_bricks are 0.  gvt_hip_volume_frame_fused_shaded
+ * goes on refusing bit 16.
+ * ELIGIBILITY, decided per call from the volumes' current state: GVT_HIP_FUSED_AMR drops the clause "no brick has subgrids" and nothing
+ * else -- one grid, table, matrix and voxel type, surfaces and lights equal as bits, the allow bits the frame needs and the gradient
+ * clauses stay.  Subgrids exist on float32 CELL volumes only and take surfaces and lit shading only when set with
+ * GVT_HIP_VOLUME_AMR_SHADED (the setters see to both).  A frame that MIXES bricks with and without subgrids is the normal case and is
+ * eligible.  A frame that reads a gradient (an isovalue, or effective lit shading) and mixes bricks with subgrids with CENTRAL bricks is
+ * a frame of mixed kinds: the loop, with every bit set.  An ineligible frame is not an error: the loop runs, fused = 0.  A frame in which
+ * no brick has subgrids launches exactly what gvt_hip_volume_frame_fused_shaded launches; features carries GVT_HIP_FUSED_AMR exactly
+ * when an AMR instantiation of the kernels ran.
+ * CONTRACT.  The fused frame's: for every eligible input at one sample per pixel the framebuffer equals gvt_hip_volume_frame's /
+ * _clipped's on the same arguments in every bit.  The visit of a brick that has subgrids is the AMR march's per-sample sequence ("AMR
+ * volumes" above): the skip bit from the brick's AMR cell word (with surfaces: from its per-cell word, built from the merged ranges),
+ * the descent between the skip decision and the gather, the gather, the corners and the spacing of the FINAL grid.  The visit of a
+ * brick without subgrids is what the fused kernels do today.  Between two visits the ray carries what it carries in the fused frames
+ * above; the descent adds no state to a ray.  The bricks' AMR tables are read from the volumes at every call: a _set_subgrids between
+ * two frames is seen by the next one.
+ * COUNTERS.  The bricks' own counters (gvt_hip_volume_info, _get_crossings, _get_shaded, and _get_amr_info's samples_refined and
+ * amr_marches) are not touched by a fused frame.  samples_refined below is the sum of what the loop would have added to the bricks'
+ * samples_refined for the same frame.
+ * OUT OF SCOPE.  The shadowed, fog-shadowed and mesh-shadowed frames and both bakes on bricks with subgrids (they go on refusing);
+ * CENTRAL gradients on AMR volumes; typed voxels with subgrids; in-place updates of AMR volumes; the Domain scheduler; fused as the default. */
+#define GVT_HIP_FUSED_AMR 16u       /* the fused kernels may take frames in which some or all bricks have subgrids */
+typedef struct {
+  uint32_t fused, features;  /* the fields of gvt_hip_volume_fused_shaded_stats, same order and meaning */
+  uint64_t samples_marched, samples_gathered, brick_visits, rays_deposited, adapter_calls;
+  uint64_t crossings_rendered, samples_shaded;
+  uint64_t samples_refined;  /* fused with GVT_HIP_FUSED_AMR in features: gathered samples whose final grid was a subgrid; 0 otherwise */
+  uint32_t amr_bricks;       /* ... and the bricks of the frame that had subgrids; 0 otherwise */
+  uint32_t pad;
+} gvt_hip_volume_fused_amr_stats;
+int gvt_hip_volume_frame_fused_amr(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                   const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
+                                   const gvt_hip_depth *depth /* may be NULL */, uint32_t allow,
+                                   gvt_hip_volume_fused_amr_stats *stats /* may be NULL */);
 
 /* ---- shadowed surfaces: shadow rays marched inside the fused frame (additive: the ABI revision stays 6, no entry point above changes) ----
  * gvt_hip_volume_frame_shadowed is the shaded fused frame in which a crossing is lit only by the light that reaches it.  A shadow ray

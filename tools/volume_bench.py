@@ -33,6 +33,13 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              table and rate of (d) above; three frames alternating in one process: the AMR volume with two
                                              isovalues and a light (--surfaces) or lit by one light (--shade), the same level-0 volume without
                                              subgrids under the same surfaces / shading, and the plain AMR frame; the two ratios beside them
+  python tools/volume_bench.py --fused --amr [--surfaces] [--shade] --bricks 1 8 64   the fused AMR frame (gvt_hip_volume_frame_fused_amr):
+                                             grid, table and rate of (d) above, the central eighth refined as eight level-1 subgrids cut
+                                             along the 4 x 4 x 4 brick faces (each lies in one brick of every bricking) with a ratio-4 child
+                                             in two of them; per bricking three tracers alternating frame by frame in one process: the loop,
+                                             the fused AMR frame, and the fused frame of the same level-0 grid without subgrids; median
+                                             [min .. max] of each, the loop's and the fused framebuffer compared in every bit once.  Without
+                                             --surfaces / --shade: the fog frame
   python tools/volume_bench.py --domains 1 2 4 8   volume domains across ranks: the "thin" 1080p frame of the 256^3 grid in 8 and in 64 bricks
                                              (round-robin owners) through scheduler.VolumeDomainTracer, W ranks as W threads of this process on
                                              ONE GPU over the stand-in transport of tests/fake_dist.py, one lock around library calls.  Per W and
@@ -636,6 +643,69 @@ def run_amr_shaded(n, steps, warmup, rate, what):
     return out
 
 
+def amr_bricked_scene(n):
+    """--fused --amr: the noise grid with its central eighth refined at ratio 2, given as EIGHT level-1 subgrids cut along the faces of
+    the 4 x 4 x 4 bricking (split_volume's even cuts), so that each lies in one brick of every bricking measured (1, 8 and 64); a ratio-4
+    child over the central cells of two of them (the first and the last)."""
+    vol = noise(n, "f32")
+    cells = n - 1
+    lo, hi = cells // 4, cells // 4 + cells // 2  # the central eighth, in cells: run_amr's
+    faces = [c for c in scenes._cuts(n, 4) if lo < c < hi]
+    edges = [lo] + faces + [hi]
+    boxes = [(a0, a1) for a0, a1 in zip(edges, edges[1:])]
+    level1 = []
+    for z0, z1 in boxes:
+        for y0, y1 in boxes:
+            for x0, x1 in boxes:
+                level1.append(scenes.refine(vol, (x0, y0, z0), (x1 - x0, y1 - y0, z1 - z0), 2, seed=1 + len(level1)))
+    for s in (level1[0], level1[-1]):
+        c = np.asarray(vol.subgrids[s].cells) * 2  # the subgrid's own cells per axis
+        scenes.refine(vol, tuple(int(v) // 4 for v in c), tuple(int(v) // 2 for v in c), 4, parent=s, seed=100 + s)
+    return vol
+
+
+def run_fused_amr(n, split, steps, warmup, rate, vol, shaded=None):
+    """--fused --amr [--surfaces] [--shade]: amr_bricked_scene in the bricking `split` under the "thin" table.  Three tracers alternate
+    frame by frame in one process: the loop over the AMR bricks, the fused AMR frame (gvt_hip_volume_frame_fused_amr) over the same
+    bricks, and the fused frame over the same level-0 grid without subgrids.  shaded: None (fog), "surfaces" (the "reached" isovalues,
+    opacity 0.3, one light) or "lit" (lit fog by one light).  The loop's and the fused AMR framebuffer are compared in every bit once."""
+    cam, t = camera(), transfer("thin")
+    plain = scenes.VolumeData(vol.data, vol.origin, vol.spacing)
+    bricks = vol if split == (1, 1, 1) else scenes.split_amr_volume(vol, *split)
+    bare = plain if split == (1, 1, 1) else scenes.split_volume(plain, *split)
+    trs = {"loop": VolumeTracer(bricks, cam, t, sampling_rate=rate, amr_shaded=True),
+           "fused": VolumeTracer(bricks, cam, t, sampling_rate=rate, amr_shaded=True, fused=True, fused_shaded=True, fused_amr=True),
+           "plain_fused": VolumeTracer(bare, cam, t, sampling_rate=rate, fused=True, fused_shaded=True)}
+    for tr in trs.values():
+        if shaded == "surfaces":
+            tr.set_surfaces(SURFACE_MODES["reached"], (), 0.3).set_lights([((3.0, 4.0, 5.0), (1.0, 1.0, 1.0))])
+        elif shaded == "lit":
+            tr.set_lights(SHADE_LIGHTS[:1]).set_shading(True)
+    ms = {k: [] for k in trs}
+    for i in range(warmup + steps):
+        for k, tr in trs.items():
+            ms[k].append(timed(tr.frame))
+    ms = {k: v[warmup:] for k, v in ms.items()}
+    same = bool((trs["loop"].framebuffer(False).view(np.uint32) == trs["fused"].framebuffer(False).view(np.uint32)).all())
+    st, pst = trs["fused"].stats(), trs["plain_fused"].stats()
+    out = {"mode": "fused_amr" if not shaded else "fused_amr_" + shaded, "n": n, "bricks": int(np.prod(split)), "sampling_rate": rate, "n_subgrids": len(vol.subgrids),
+           "loop_adapter_calls": int(trs["loop"].calls)}
+    for k, v in ms.items():
+        out.update({k + "_ms_median": med(v), k + "_ms_min": round(min(v), 3), k + "_ms_max": round(max(v), 3)})
+    out.update({"fused": int(st["fused"]), "features": int(st["features"]), "amr_bricks": int(st["amr_bricks"]), "brick_visits": int(st["brick_visits"]),
+                "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "samples_refined": int(st["samples_refined"]),
+                "crossings_per_frame": int(st["crossings_rendered"]), "samples_shaded": int(st["samples_shaded"]),
+                "plain_fused_features": int(pst["features"]), "plain_fused_samples_per_frame": int(pst["samples_marched"]),
+                "fused_over_loop": round(float(np.median(ms["fused"])) / float(np.median(ms["loop"])), 4),
+                "fused_over_plain_fused": round(float(np.median(ms["fused"])) / float(np.median(ms["plain_fused"])), 4),
+                "fused_median_below_loop_min": bool(float(np.median(ms["fused"])) < min(ms["loop"])), "same_bits": same,
+                "lit_pixels": int((trs["fused"].framebuffer(False)[..., 3] > 0).sum())})
+    for tr in trs.values():
+        for a in tr.adapters:
+            a.close()
+    return out
+
+
 def run_domains(n, split, world, steps, warmup, rate, kind, vol, per_queue, overlap):
     """One bricking at one world size: `world` threads, each a rank with its own HipVolumeBackend, frames started together."""
     import threading
@@ -853,7 +923,16 @@ def main():
                         out["runs"].append(r)
                         print(json.dumps(r), flush=True)
         a.sizes = []
-    if a.amr and (a.surfaces or a.shade):  # the shaded AMR frame against the plain volume's shaded frame and against the plain AMR frame
+    if a.fused and a.amr:  # the fused AMR frame against the loop and against the subgrid-free fused frame
+        for n in ([256] if a.sizes == [256, 512] else a.sizes):
+            vol = amr_bricked_scene(n)
+            for shaded in ([None] if not (a.surfaces or a.shade) else (["surfaces"] if a.surfaces else []) + (["lit"] if a.shade else [])):
+                for nb in a.bricks:
+                    r = run_fused_amr(n, FUSED_SPLITS[nb], a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate, vol, shaded)
+                    out["runs"].append(r)
+                    print(json.dumps(r), flush=True)
+        a.sizes = []
+    elif a.amr and (a.surfaces or a.shade):  # the shaded AMR frame against the plain volume's shaded frame and against the plain AMR frame
         for n in ([256] if a.sizes == [256, 512] else a.sizes):
             for what in (["surfaces"] if a.surfaces else []) + (["shade"] if a.shade else []):
                 r = run_amr_shaded(n, a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate, what)
