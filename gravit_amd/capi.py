@@ -126,7 +126,7 @@ class VolumeFusedAmrStats(C.Structure):
 
 
 class VolumeShadowParams(C.Structure):
-    """gvt_hip_volume_shadow_params: flags is 0 or VOLUME_ALLOW_CENTRAL; bias = the first shadow sample's lattice index, 1 .. 64."""
+    """gvt_hip_volume_shadow_params: flags is 0, or VOLUME_ALLOW_CENTRAL and VOLUME_ALLOW_AMR ORed; bias = the first shadow sample's lattice index, 1 .. 64."""
     _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
 
 
@@ -140,7 +140,7 @@ class VolumeShadowStats(C.Structure):
 
 
 class VolumeLightGridParams(C.Structure):
-    """gvt_hip_volume_light_grid_params: flags is 0 or VOLUME_ALLOW_CENTRAL; bias = the first sample of a vertex's shadow ray, 1 .. 64."""
+    """gvt_hip_volume_light_grid_params: flags is 0, or VOLUME_ALLOW_CENTRAL and VOLUME_ALLOW_AMR ORed; bias = the first sample of a vertex's shadow ray, 1 .. 64."""
     _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
 
 
@@ -170,7 +170,7 @@ class VolumeFogShadowStats(C.Structure):
 
 
 class VolumeOccluderParams(C.Structure):
-    """gvt_hip_volume_occluder_params: flags is 0 or VOLUME_ALLOW_CENTRAL."""
+    """gvt_hip_volume_occluder_params: flags is 0, or VOLUME_ALLOW_CENTRAL and VOLUME_ALLOW_AMR ORed."""
     _fields_ = [("flags", C.c_uint32), ("pad", C.c_uint32)]
 
 
@@ -204,6 +204,7 @@ FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bi
 FUSED_AMR = 16  # gvt_hip_volume_frame_fused_amr's further allow bit: frames in which some or all bricks have AMR subgrids may be fused
 FUSED_CENTRAL = 8  # ... and such frames whose bricks all shade with VOLUME_GRADIENT_CENTRAL (the kernel's CENTRAL instantiation; its bit in features)
 VOLUME_ALLOW_CENTRAL = 2  # flags of VolumeShadowParams, VolumeLightGridParams and VolumeOccluderParams: accept frames whose bricks are all CENTRAL
+VOLUME_ALLOW_AMR = 4  # ... the next bit of the same word: accept frames in which some or all bricks have AMR subgrids (the kernels' AMR instantiations)
 
 # volume ray flags (Ray::depth, actor/ORays.h) and gvt_hip_volume_create flags
 RAY_OPAQUE, RAY_BOUNDARY, RAY_EXTERNAL_BOUNDARY = 0x2, 0x4, 0x10

@@ -368,7 +368,7 @@ int set_device_u32(unsigned *p, unsigned v); // stream-ordered store of a host-k
 // The context's pinned staging block (Ctx::h_wire, PINNED_STAGE_BYTES, made on first use).  _begin: *h = the block, free to be written (it
 // waits for the stream to have read the last upload from it: an event, no stream synchronisation).  The caller fills it, enqueues ONE
 // hipMemcpyAsync from it on the context's stream and calls _end, which records the event behind that copy.
-#define PINNED_STAGE_BYTES (24 * 1024)
+#define PINNED_STAGE_BYTES (32 * 1024) // (the largest user: a fog- or mesh-shadowed AMR frame's three tables, 28 KiB -- volume.hip volume_frame_fused)
 int pinned_stage_begin(void **h);
 int pinned_stage_end();
 // one round's merged launch chain (no host round trip inside); `out` must have room for n_total * (1 + n_lights * passes) rays and

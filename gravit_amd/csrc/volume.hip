@@ -889,6 +889,7 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 #include "volume_fused_fog.inc" // k_volume_march_fused_fog
 #include "volume_occluder_grid.inc" // k_occluder_rays, k_occluder_fold, k_occluder_pack
 #include "volume_fused_mesh.inc" // k_volume_march_fused_mesh
+#include "volume_fused_shadow_amr.inc" // k_volume_march_fused_shadow_amr, _fog_amr, _mesh_amr, the lean two, k_volume_bake_light_amr
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
 
@@ -1776,15 +1777,48 @@ void launch_fused_mesh(uint32_t features, const gvt_hip_volume *V0, const gvt_hi
   else k_volume_march_fused_mesh<VT, false, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
 }
 
+// the shadowed AMR kernels' instantiation (GVT_HIP_FUSED_AMR is among the features; float32, CELL): the kernel of the shadowed, the
+// fog-shadowed (fog) or the mesh-shadowed (mesh) frame, clipped or not, lit fog or not, with surfaces or -- the lean kernels -- without.
+// d_grids: the bricks' planes (fog or mesh), else null
+template <typename... Args>
+void launch_fused_shadow_amr(uint32_t features, bool fog, bool mesh, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S,
+                             ShadowDev H, const FusedBrick *d_bricks, const AmrDev *d_amr, const MeshBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M,
+                             Args... args) {
+  const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
+  const float *d_t = depth ? depth->d_t : nullptr;
+  const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
+  if ((fog || mesh) && !(features & GVT_HIP_FUSED_SURFACES)) {
+    const LightDev L = light_dev(V0, M);
+    if (mesh && depth) k_volume_march_fused_mesh_lean_amr<true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else if (mesh) k_volume_march_fused_mesh_lean_amr<false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else if (depth) k_volume_march_fused_fog_lean_amr<true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else k_volume_march_fused_fog_lean_amr<false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+  } else if (mesh) {
+    if (depth && lit) k_volume_march_fused_mesh_amr<true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else if (depth) k_volume_march_fused_mesh_amr<true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else if (lit) k_volume_march_fused_mesh_amr<false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else k_volume_march_fused_mesh_amr<false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+  } else if (fog) {
+    if (depth) k_volume_march_fused_fog_amr<true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+    else k_volume_march_fused_fog_amr<false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
+  } else {
+    if (depth && lit) k_volume_march_fused_shadow_amr<true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
+    else if (depth) k_volume_march_fused_shadow_amr<true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
+    else if (lit) k_volume_march_fused_shadow_amr<false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
+    else k_volume_march_fused_shadow_amr<false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
+  }
+}
+
 // the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
 // features: fused_eligible's -- 0 launches k_volume_march_fused, anything else the shaded kernel with the table of volumes[0]
 // shadow (gvt_hip_volume_frame_shadowed; features has SURFACES then): the launch is k_volume_march_fused_shadow's, and shadow_out gets
 // its five further counter words, read back in the same wait.  fog (gvt_hip_volume_frame_fog_shadowed; shadow is given and features has
 // LIT): the launch is k_volume_march_fused_fog's, and the bricks' light grid planes travel in a second table beside the records.  mesh
 // (gvt_hip_volume_frame_mesh_shadowed; shadow is given): the launch is k_volume_march_fused_mesh's, and that table holds the occluder
-// grid's planes too (the light grid's only where fog is set as well).  GVT_HIP_FUSED_AMR in features (never with shadow, fog, mesh or
-// GVT_HIP_FUSED_CENTRAL: those callers do not allow the bit, and a brick with subgrids is CELL): the launch is the AMR kernels', the
-// bricks' AMR tables travel in a second table beside the records, read from the volumes NOW, and *refined_out gets the seventh counter
+// grid's planes too (the light grid's only where fog is set as well).  GVT_HIP_FUSED_AMR in features (never with
+// GVT_HIP_FUSED_CENTRAL: a brick with subgrids is CELL): the launch is the AMR kernels' -- with shadow, fog or mesh those of
+// volume_fused_shadow_amr.inc (GVT_HIP_VOLUME_ALLOW_AMR) -- the bricks' AMR tables travel in a further table beside the records and the
+// planes, read from the volumes NOW, and *refined_out gets the seventh counter (the shadowed kernels do not count it)
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
                        gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S, const ShadowDev *shadow = nullptr,
                        uint64_t *shadow_out = nullptr, bool fog = false, bool mesh = false, uint64_t *refined_out = nullptr) {
@@ -1819,20 +1853,21 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   AmrDev *d_amr = amr ? (AmrDev *)scratch_get(SCR_VOL_AMR, sizeof(AmrDev) * n_inst) : nullptr;
   if (amr && !d_amr) return GVT_HIP_ERR_DEVICE;
   static_assert((sizeof(FusedBrick) + sizeof(MeshBrick) + sizeof(void *)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table, the grids' and the ghosts' fit the staging block");
-  static_assert((sizeof(FusedBrick) + sizeof(AmrDev)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "... and so do the brick table and the AMR table, which takes the grids' and the ghosts' place (an AMR frame has neither)");
+  static_assert((sizeof(FusedBrick) + sizeof(MeshBrick) + sizeof(AmrDev)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "... and so do the brick table, the grids' and the AMR table, which takes the ghosts' place (an AMR frame is never CENTRAL)");
   void *stage = nullptr;
   if ((rc = pinned_stage_begin(&stage))) return rc;
   FusedBrick *h = (FusedBrick *)stage;
   FogBrick *hg = (FogBrick *)(h + VOL_DEST_MAX);
   MeshBrick *hm = (MeshBrick *)(h + VOL_DEST_MAX);
   const void **hf = (const void **)(hm + VOL_DEST_MAX);
-  AmrDev *ha = (AmrDev *)(h + VOL_DEST_MAX);
+  AmrDev *ha = (AmrDev *)(hm + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     FusedBrick R{};
     R.vox = B->d_vox;
     R.mc = (features & GVT_HIP_FUSED_SURFACES) ? (const uint8_t *)B->d_cells : B->d_mc; // (the surface visit reads the per-cell words, never the skip bytes)
     if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
+    else if (fog && amr) hm[i] = MeshBrick{ B->d_lgrid, nullptr };
     else if (fog) hg[i].grid = B->d_lgrid;
     if (central) hf[i] = B->d_ghost; // (null on a brick without an interior face: none of its layers is ever read)
     if (amr) ha[i] = B->sub.empty() ? AmrDev{ nullptr, nullptr, nullptr, nullptr } : AmrDev{ B->d_amr_mc, B->d_amr_list, B->d_amr_desc, B->d_amr_vox };
@@ -1841,7 +1876,7 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
     h[i] = R;
   }
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
-  if (mesh) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if (mesh || (fog && amr)) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   else if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (central) HIPCHK(hipMemcpyAsync(d_faces, hf, sizeof(void *) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (amr) HIPCHK(hipMemcpyAsync(d_amr, ha, sizeof(AmrDev) * n_inst, hipMemcpyHostToDevice, C.stream));
@@ -1854,7 +1889,10 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   const RayPlanes P = make_planes(q_cam->d_planes, q_cam->cap);
   const unsigned n_pix = (unsigned)(fb->w * fb->h);
   const FusedGhost HG{ d_faces, volumes[0]->gn[0], volumes[0]->gn[1], volumes[0]->gn[2] };
-  if (n && amr) { // (F32 and CELL: fused_eligible has compared the voxel types, and a brick with subgrids is F32)
+  if (n && amr && shadow) { // (the fog frame's table is a MeshBrick table here, its occluder pointers null)
+    launch_fused_shadow_amr(features, fog, mesh, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, (const AmrDev *)d_amr,
+                            (const MeshBrick *)d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work, d_stats);
+  } else if (n && amr) { // (F32 and CELL: fused_eligible has compared the voxel types, and a brick with subgrids is F32)
     if (depth) launch_fused_amr<true>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, (const AmrDev *)d_amr, T->dev(), P, (unsigned)n, M, depth->d_t,
                                       (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
     else launch_fused_amr<false>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, (const AmrDev *)d_amr, T->dev(), P, (unsigned)n, M,
@@ -2021,8 +2059,9 @@ int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip
   int rc;
   if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
   if (!params) { set_error("%s: null params", fn); return GVT_HIP_ERR_INVALID; }
-  if (params->flags & ~(uint32_t)GVT_HIP_VOLUME_ALLOW_CENTRAL) { set_error("%s: unknown flag bits %u", fn, params->flags); return GVT_HIP_ERR_INVALID; }
-  const uint32_t allow = GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | ((params->flags & GVT_HIP_VOLUME_ALLOW_CENTRAL) ? GVT_HIP_FUSED_CENTRAL : 0u);
+  if (params->flags & ~(uint32_t)(GVT_HIP_VOLUME_ALLOW_CENTRAL | GVT_HIP_VOLUME_ALLOW_AMR)) { set_error("%s: unknown flag bits %u", fn, params->flags); return GVT_HIP_ERR_INVALID; }
+  const uint32_t allow = GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | ((params->flags & GVT_HIP_VOLUME_ALLOW_CENTRAL) ? GVT_HIP_FUSED_CENTRAL : 0u) |
+                         ((params->flags & GVT_HIP_VOLUME_ALLOW_AMR) ? GVT_HIP_FUSED_AMR : 0u);
   if (params->bias < 1 || params->bias > 64) { set_error("%s: bias %d, 1 to 64 lattice steps are allowed", fn, params->bias); return GVT_HIP_ERR_INVALID; }
   bool any_surface = false, any_light = false, any_lit = false;
   for (size_t i = 0; i < n_inst; i++) {
@@ -2102,25 +2141,31 @@ extern "C" int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *T, gvt_hip_volume 
 namespace {
 
 // What both bakes (the light grids' and the occluder grids') ask of their arguments and of their bricks.  fn: the entry point's name in the
-// error texts.  bake_args: no null pointer, 1 to VOL_DEST_MAX bricks that have a table, flags 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL
+// error texts.  bake_args: no null pointer, 1 to VOL_DEST_MAX bricks that have a table, flags of GVT_HIP_VOLUME_ALLOW_CENTRAL and
+// GVT_HIP_VOLUME_ALLOW_AMR only
 int bake_args(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const uint32_t *flags) {
   if (!volumes || !m || !minv || !flags) { set_error("%s: null argument", fn); return GVT_HIP_ERR_INVALID; }
   if (n_inst < 1 || n_inst > VOL_DEST_MAX) { set_error("%s: %zu bricks, 1 to %d are allowed", fn, n_inst, VOL_DEST_MAX); return GVT_HIP_ERR_INVALID; }
   for (size_t i = 0; i < n_inst; i++)
     if (!volumes[i] || !volumes[i]->has_tf) { set_error("%s: brick %zu is null or has no transfer function", fn, i); return GVT_HIP_ERR_INVALID; }
-  if (*flags & ~(uint32_t)GVT_HIP_VOLUME_ALLOW_CENTRAL) { set_error("%s: unknown flag bits %u", fn, *flags); return GVT_HIP_ERR_INVALID; }
+  if (*flags & ~(uint32_t)(GVT_HIP_VOLUME_ALLOW_CENTRAL | GVT_HIP_VOLUME_ALLOW_AMR)) { set_error("%s: unknown flag bits %u", fn, *flags); return GVT_HIP_ERR_INVALID; }
   return 0;
 }
 
 // ... bake_bricks: bricks of one grid that tile it, under one matrix, with equal surfaces and lights, at least one usable light, no
-// subgrids, the CENTRAL clause (flags: the params' word -- with GVT_HIP_VOLUME_ALLOW_CENTRAL bricks that are all CENTRAL pass; the bake's
+// subgrids unless the flags have GVT_HIP_VOLUME_ALLOW_AMR (amr: does a brick have any?), the CENTRAL clause (flags: the params' word -- with
+// GVT_HIP_VOLUME_ALLOW_CENTRAL bricks that are all CENTRAL pass; the bake's
 // rays march with shading NONE and read no gradient, so the planes do not depend on the kind), at most 2^32 - 1 (vertex, light) pairs.
 // verts: the vertices summed over the bricks; usable: the lights' bits
-int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, uint32_t flags, uint64_t &verts, unsigned &usable) {
+int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, uint32_t flags, uint64_t &verts, unsigned &usable,
+                bool *amr = nullptr) {
   uint32_t features = 0;
   const char *why = "";
   const bool allow_central = (flags & GVT_HIP_VOLUME_ALLOW_CENTRAL) != 0;
-  if (!fused_eligible(volumes, minv, n_inst, GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | (allow_central ? GVT_HIP_FUSED_CENTRAL : 0u), features, &why)) {
+  const uint32_t allow = GVT_HIP_FUSED_SURFACES | GVT_HIP_FUSED_LIT | (allow_central ? GVT_HIP_FUSED_CENTRAL : 0u) | ((flags & GVT_HIP_VOLUME_ALLOW_AMR) ? GVT_HIP_FUSED_AMR : 0u);
+  const bool eligible = fused_eligible(volumes, minv, n_inst, allow, features, &why);
+  if (amr) *amr = (features & GVT_HIP_FUSED_AMR) != 0;
+  if (!eligible) {
     set_error("%s: the bricks are not eligible for the fused kernels: %s", fn, why);
     return GVT_HIP_ERR_INVALID;
   }
@@ -2167,7 +2212,8 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
   if (params->bias < 1 || params->bias > 64) { set_error("volume_light_grid_bake: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
   uint64_t verts = 0;
   unsigned usable = 0;
-  if ((rc = bake_bricks("volume_light_grid_bake", volumes, m, minv, n_inst, params->flags, verts, usable))) return rc;
+  bool amr = false; // a brick has subgrids (GVT_HIP_VOLUME_ALLOW_AMR): k_volume_bake_light_amr, and the bricks' AMR tables beside the records
+  if ((rc = bake_bricks("volume_light_grid_bake", volumes, m, minv, n_inst, params->flags, verts, usable, &amr))) return rc;
   const gvt_hip_volume *A = volumes[0];
   const ShadowDev H = shadow_dev(A, params->bias);
   const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
@@ -2188,6 +2234,7 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
   }
   FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
   LightGridBrick *d_parts = (LightGridBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(LightGridBrick) * n_inst);
+  AmrDev *d_amr = amr ? (AmrDev *)scratch_get(SCR_VOL_AMR, sizeof(AmrDev) * n_inst) : nullptr;
   unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -2199,13 +2246,14 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
     drop();
     return GVT_HIP_ERR_DEVICE;
   };
-  if (!d_bricks || !d_parts || !d_stats || !work) return fail("a scratch allocation");
+  if (!d_bricks || !d_parts || !d_stats || !work || (amr && !d_amr)) return fail("a scratch allocation");
   static_assert(VOL_BAKE_STATS <= VOL_FUSED_SHADOW_STATS, "the fused frames' counter words serve the bake");
-  static_assert((sizeof(FusedBrick) + sizeof(LightGridBrick)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "both tables fit the staging block");
+  static_assert((sizeof(FusedBrick) + sizeof(LightGridBrick) + sizeof(AmrDev)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the three tables fit the staging block");
   void *stage = nullptr;
   if (pinned_stage_begin(&stage)) return fail("the staging block");
   FusedBrick *h = (FusedBrick *)stage;
   LightGridBrick *hp = (LightGridBrick *)(h + VOL_DEST_MAX);
+  AmrDev *ha = (AmrDev *)(hp + VOL_DEST_MAX);
   unsigned first = 0;
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
@@ -2216,11 +2264,13 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
     for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
     h[i] = R;
     hp[i] = LightGridBrick{ fresh[i], first, 0u };
+    if (amr) ha[i] = B->sub.empty() ? AmrDev{ nullptr, nullptr, nullptr, nullptr } : AmrDev{ B->d_amr_mc, B->d_amr_list, B->d_amr_desc, B->d_amr_vox };
     first += (unsigned)((size_t)B->n[0] * B->n[1] * B->n[2]) * n_usable;
   }
   const unsigned n = first;
   bool ok = hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess &&
-            hipMemcpyAsync(d_parts, hp, sizeof(LightGridBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess;
+            hipMemcpyAsync(d_parts, hp, sizeof(LightGridBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess &&
+            (!amr || hipMemcpyAsync(d_amr, ha, sizeof(AmrDev) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess);
   if (pinned_stage_end() || !ok) return fail("the table upload");
   ok = hipMemsetAsync(work, 0, sizeof(unsigned), C.stream) == hipSuccess && hipMemsetAsync(d_stats, 0, VOL_BAKE_STATS * sizeof(unsigned long long), C.stream) == hipSuccess &&
        hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
@@ -2235,7 +2285,9 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
   for (int a = 0; a < 3; a++) { U.lo[a] = A->go[a] + (float)0 * A->sp[a]; U.hi[a] = A->go[a] + (float)(A->gn[a] - 1) * A->sp[a]; }
   const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
   ok = hipEventRecord(e0, C.stream) == hipSuccess;
-  if (ok)
+  if (ok && amr) // (F32: a brick with subgrids is, and fused_eligible has compared the voxel types)
+    k_volume_bake_light_amr<<<blocks, VOL_BLOCK, 0, C.stream>>>(U, surf_dev(A, Mi), H, d_bricks, (const AmrDev *)d_amr, d_parts, (unsigned)n_inst, n, M, Mi, work, d_stats);
+  else if (ok)
     with_voxel_type(A->vtype, [&](auto t) {
       using VT = decltype(t);
       k_volume_bake_light<VT><<<blocks, VOL_BLOCK, 0, C.stream>>>(U, surf_dev(A, Mi), H, d_bricks, d_parts, (unsigned)n_inst, n, M, Mi, work, d_stats);

@@ -562,7 +562,7 @@ class VolumeTracer:
     native: HipVolumeAdapter's (uint8 / int16 / uint16 bricks stored at their own width).
     amr_shaded: HipVolumeAdapter's -- the bricks' subgrids are set with capi.VOLUME_AMR_SHADED, so set_surfaces, set_lights and set_shading work
     on AMR bricks too (isovalues, slice planes and lit fog in the refined cells); such frames take the loop unless fused_amr is given (the
-    shadowed frames and the bakes refuse a brick with subgrids as ever).  Without it (the default) the setters are refused on a brick that has subgrids.
+    shadowed frames and the bakes refuse a brick with subgrids unless shadow_amr is given).  Without it (the default) the setters are refused on a brick that has subgrids.
     fused: frame() goes through gvt_hip_volume_frame_fused -- every brick in ONE march launch where the frame is eligible (plain bricks of
     one grid), the loop otherwise; the image is the loop's in every bit either way.  Default: the loop.
     fused_shaded (with fused): frame() goes through gvt_hip_volume_frame_fused_shaded with both bits (fused_allow), so frames with
@@ -574,7 +574,11 @@ class VolumeTracer:
     fused_amr (with fused; alone it raises ValueError): frame() goes through gvt_hip_volume_frame_fused_amr with capi.FUSED_AMR, plus
     FUSED_SURFACES | FUSED_LIT if fused_shaded, plus FUSED_CENTRAL if fused_central -- frames in which some or all bricks have subgrids
     are fused too (the kernels' AMR instantiations; the image is the loop's in every bit).  Without it (the default) such frames take the
-    loop, as ever.  shadows=True on bricks with subgrids stays refused.
+    loop, as ever.  shadows=True on bricks with subgrids stays refused unless shadow_amr is given.
+    shadow_amr (with shadows; alone it raises ValueError): every VolumeShadowParams, VolumeLightGridParams and VolumeOccluderParams the
+    tracer builds carries capi.VOLUME_ALLOW_AMR too -- the shadowed, fog-shadowed and mesh-shadowed frames and both bakes take bricks with
+    subgrids (the kernels' AMR instantiations; features carries capi.FUSED_AMR where one ran; the light and occluder grids stay at the
+    bricks' level-0 vertices).  Deliberately not derived from fused_amr: without it (the default) such frames and bakes are refused, as ever.
     shadows: frame() goes through gvt_hip_volume_frame_shadowed whatever fused says -- a crossing is lit only by the lights that reach it,
     a shadow ray per light marched inside the one launch; shadow_bias = the lattice index of a shadow ray's first sample (1 .. 64; 2 is
     a choice, not a measurement).  A frame that has surfaces and lights but cannot be fused is refused (GvtHipError): no loop renders
@@ -590,7 +594,7 @@ class VolumeTracer:
     again after the scene changed.  A frame that needs a grid and has none is refused (GvtHipError)."""
 
     def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2,
-                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False):
+                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False, shadow_amr=False):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -602,6 +606,8 @@ class VolumeTracer:
             raise ValueError("VolumeTracer: mesh_shadows needs shadows=True and fog_shadows=True (the mesh-shadowed frame is the fog-shadowed frame with one more change)")
         if fused_amr and not fused:
             raise ValueError("VolumeTracer: fused_amr needs fused=True (it is one more allow bit of the fused frame)")
+        if shadow_amr and not shadows:
+            raise ValueError("VolumeTracer: shadow_amr needs shadows=True (it is one more flag bit of the shadowed frames and their bakes)")
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         self.camera = camera
         self.m = capi.f32(mat_translate_scale((0, 0, 0), (1, 1, 1)) if m is None else m, 16)
@@ -623,7 +629,9 @@ class VolumeTracer:
         self.fused_amr = bool(fused_amr)
         # fused_amr=True: the allow word of gvt_hip_volume_frame_fused_amr
         self.fused_amr_allow = capi.FUSED_AMR | (capi.FUSED_SURFACES | capi.FUSED_LIT if self.fused_shaded else 0) | (capi.FUSED_CENTRAL if self.fused_central else 0)
-        self.param_flags = capi.VOLUME_ALLOW_CENTRAL if self.fused_central else 0  # the flags word of the shadowed frames' and the bakes' params
+        self.shadow_amr = bool(shadow_amr)
+        # the flags word of the shadowed frames' and the bakes' params
+        self.param_flags = (capi.VOLUME_ALLOW_CENTRAL if self.fused_central else 0) | (capi.VOLUME_ALLOW_AMR if self.shadow_amr else 0)
         self.fused_stats = None  # fused=True: gvt_hip_volume_fused_stats (fused_shaded: gvt_hip_volume_fused_shaded_stats; fused_amr: gvt_hip_volume_fused_amr_stats) of the last frame, as a dict
         self.shadows = bool(shadows)
         self.shadow_bias = int(shadow_bias)
@@ -831,7 +839,8 @@ class VolumeTracer:
         fused_amr=True adds amr_bricks (the bricks of the last frame that had subgrids; 0 unless an AMR instantiation ran), and where that
         frame was fused with capi.FUSED_AMR in features samples_refined is ITS count, like samples_marched; amr_marches goes on counting
         the LOOP's per-brick launches only.
-        shadows=True: the last frame's gvt_hip_volume_shadow_stats in fused_shaded's form (the camera rays' counters), and beside them
+        shadows=True: the last frame's gvt_hip_volume_shadow_stats in fused_shaded's form (the camera rays' counters; features carries
+        capi.FUSED_AMR where shadow_amr let an AMR instantiation run -- refined samples are not counted there), and beside them
         shadowed, shadow_rays, shadow_brick_visits, shadow_crossings, shadow_samples_marched and shadow_samples_gathered.
         fog_shadows=True adds fog_samples_shadowed of the last frame, light_bakes (bakes so far) and light_grid_rays / _bytes / _ms of the
         last bake (0 before the first).
@@ -1131,10 +1140,12 @@ class MixedTracer:
     takes either the mesh or the volume branch.  `camera` becomes the scene's (one sample per pixel).
     mesh_shadows (with shadows and fog_shadows): the meshes cast shadows into the volume (VolumeTracer's mesh_shadows).  frame() bakes the
     occluder grids before the first volume frame that needs them and again after update_scene() and set_lights(); rebake_occluders() is
-    explicit.  set_camera(), update() and set_surfaces() do not bake."""
+    explicit.  set_camera(), update() and set_surfaces() do not bake.
+    shadow_amr (with shadows): VolumeTracer's -- the shadowed frames and both bakes take bricks with AMR subgrids."""
 
     def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
-                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False):
+                 shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False,
+                 shadow_amr=False):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -1149,8 +1160,9 @@ class MixedTracer:
         self.depth = DepthPlane(camera.width, camera.height)
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
                                    fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias,
-                                   mesh_shadows=mesh_shadows, fused_central=fused_central, amr_shaded=amr_shaded, fused_amr=fused_amr)
-        # (amr_shaded: AMR bricks take surfaces and lit fog, in the clipped frame too; fused_amr: AMR bricks in the fused clipped frame too; fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; fused_central: with CENTRAL bricks too; shadows: the volume's surfaces shadowed by the
+                                   mesh_shadows=mesh_shadows, fused_central=fused_central, amr_shaded=amr_shaded, fused_amr=fused_amr,
+                                   shadow_amr=shadow_amr)
+        # (shadow_amr: the shadowed frames and the bakes take AMR bricks too, VolumeTracer's; amr_shaded: AMR bricks take surfaces and lit fog, in the clipped frame too; fused_amr: AMR bricks in the fused clipped frame too; fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; fused_central: with CENTRAL bricks too; shadows: the volume's surfaces shadowed by the
         # volume; fog_shadows: its lit fog too, from the baked light grids; mesh_shadows: both shadowed by the meshes as well, from the baked
         # occluder grids -- without it the meshes cast no shadow into the volume)
         self.mesh_shadows = bool(mesh_shadows)

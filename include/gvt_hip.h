@@ -880,8 +880,8 @@ int gvt_hip_volume_frame_fused_amr(gvt_hip_top *, gvt_hip_volume *const *volumes
  * REFUSED.  A frame that has a surface and a light but is not eligible for the shaded fused kernel under that allow word (subgrids;
  * GVT_HIP_VOLUME_GRADIENT_CENTRAL on a brick of a frame with an isovalue, unless flags allows it, below; bricks of different grids,
  * tables, matrices, surfaces or lights; more than 256 bricks): no loop renders shadows, so the call returns GVT_HIP_ERR_INVALID with a
- * message that names the clause.  A null params pointer, flag bits other than GVT_HIP_VOLUME_ALLOW_CENTRAL and a bias outside 1 .. 64
- * are refused likewise.
+ * message that names the clause.  A null params pointer, flag bits other than GVT_HIP_VOLUME_ALLOW_CENTRAL and GVT_HIP_VOLUME_ALLOW_AMR
+ * (the accepted words are 0, 2, 4 and 6; "flag" in the message) and a bias outside 1 .. 64 are refused likewise.
  * CENTRAL.  flags = GVT_HIP_VOLUME_ALLOW_CENTRAL (the first defined bit of the flags word of gvt_hip_volume_shadow_params,
  * gvt_hip_volume_light_grid_params and gvt_hip_volume_occluder_params; bit 0 stays undefined and refused) adds GVT_HIP_FUSED_CENTRAL
  * to the allow word of the three shadowed frames, the inert forward included: a frame whose bricks are ALL CENTRAL is accepted, a frame
@@ -923,11 +923,41 @@ int gvt_hip_volume_frame_fused_amr(gvt_hip_top *, gvt_hip_volume *const *volumes
  * shadow_crossings and shadow_samples_marched / _gathered are the fused frame's counters applied to the shadow rays.  They are kept
  * apart from the camera rays' counters, which equal those of the unshadowed frame whenever the two images agree.
  * OUT OF SCOPE.  Ambient occlusion; shadowed fog and geometry shadowing the volume (both below); the volume attenuating mesh shadow rays; the Domain
- * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR frames, and CENTRAL frames without
- * GVT_HIP_VOLUME_ALLOW_CENTRAL; shadows in the per-brick loop. */
+ * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR frames without GVT_HIP_VOLUME_ALLOW_AMR, and CENTRAL
+ * frames without GVT_HIP_VOLUME_ALLOW_CENTRAL; shadows in the per-brick loop.
+ *
+ * ---- shadows on AMR bricks (additive: one more flag bit; no struct changes size, no entry point is added, the ABI revision stays 6) ----
+ * flags | GVT_HIP_VOLUME_ALLOW_AMR (the second defined bit of the same word) adds GVT_HIP_FUSED_AMR to the allow word of the three
+ * shadowed frames, the inert forward included (which then is gvt_hip_volume_frame_fused_amr's path), and drops the clause "no brick has
+ * subgrids" -- and nothing else -- from the eligibility of the two bakes.  Without the bit every call answers as it did, message for
+ * message.  A frame in which no brick has subgrids launches exactly what it launches with the bit clear (flags 6 on an all-CENTRAL
+ * frame without subgrids is flags 2).  A brick with subgrids is float32 and CELL: a frame that reads a gradient and mixes such bricks
+ * with CENTRAL bricks is refused by the mixed-kinds clause ("central" in the message), whatever the flags.  features of
+ * gvt_hip_volume_shadow_stats carries GVT_HIP_FUSED_AMR exactly when an AMR instantiation ran.  Refined samples are NOT reported by the
+ * shadowed frames: the stats struct has no field for them (gvt_hip_volume_frame_fused_amr counts them for the unshadowed frame).
+ * CONTRACT.  T_j on AMR bricks is defined by the contract that exists: T_j = 1 - A_s, A_s the opacity the shadow ray would deposit as a
+ * camera ray of gvt_hip_volume_frame_fused_amr over the same bricks with the same surfaces and shading NONE.  The shadow ray therefore
+ * takes the AMR visit: the skip decision from the per-cell word built from the MERGED ranges (every level's vertices in the macro
+ * cell), then the descent, then the final grid's value.  The camera ray's crossing is shaded as the fused AMR frame shades it -- the
+ * final cell's corners, the descended fractions, the final grid's spacing -- with the one change above: ndl * T_j.
+ * LIGHT GRID.  G_j stays a float32 plane at the brick's own LEVEL-0 vertices: "a light grid never covers subgrids" remains true of its
+ * resolution.  Its rays start at level-0 vertices and are marched over the whole grid with all its subgrids as one brick, by the
+ * ownership walk of "shadowed fog", with the AMR visit on bricks that have subgrids.  The planes are the one brick's bits for every
+ * bricking that keeps each level-1 subgrid in one brick (the AMR sections' condition).
+ * Tg AND Og IN THE FRAME are interpolated at the sample's level-0 cell c with its level-0 fractions -- the fractions BEFORE the descent
+ * replaces them -- while the gradient that shades the sample is the final cell's.  DEVIATION: a shadow's edge on the fog is one LEVEL-0
+ * cell soft on an AMR brick too, however fine the cell that is shaded.
+ * OCCLUDER GRID.  The bake reads no sample; only its gate changes.  O stays at level-0 vertices.
+ * STALENESS is unchanged: gvt_hip_volume_set_subgrids makes both grids of the brick stale.
+ * CONSEQUENCES.  The same bits for every admissible bricking, and with or without macro-cell skipping.  With every T_j = 1 the bits are
+ * gvt_hip_volume_frame_fused_amr's.  Where every light is blocked the bits are the kd = 0 frame's.  With no mesh the mesh-shadowed
+ * frame has the fog-shadowed frame's bits.
+ * OUT OF SCOPE.  CENTRAL gradients, typed voxels or in-place updates on AMR volumes; light or occluder planes at subgrid resolution;
+ * refined-sample counters in the shadow stats; shadows across ranks. */
 #define GVT_HIP_VOLUME_ALLOW_CENTRAL 2u /* flags of the shadowed frames and the two bakes: accept frames whose bricks are all CENTRAL */
+#define GVT_HIP_VOLUME_ALLOW_AMR 4u     /* ... accept frames in which some or all bricks have AMR subgrids ("shadows on AMR bricks") */
 typedef struct {
-  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
+  uint32_t flags; /* 0, or GVT_HIP_VOLUME_ALLOW_CENTRAL and GVT_HIP_VOLUME_ALLOW_AMR ORed */
   int32_t bias;   /* 1 .. 64, lattice steps */
 } gvt_hip_volume_shadow_params;
 typedef struct {
@@ -997,7 +1027,7 @@ int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes,
  * Domain scheduler; AMR frames, and CENTRAL frames without GVT_HIP_VOLUME_ALLOW_CENTRAL ("shadowed surfaces", CENTRAL); moving the
  * crossings' shadow rays onto the grid. */
 typedef struct {
-  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
+  uint32_t flags; /* 0, or GVT_HIP_VOLUME_ALLOW_CENTRAL and GVT_HIP_VOLUME_ALLOW_AMR ORed */
   int32_t bias;   /* 1 .. 64, lattice steps */
 } gvt_hip_volume_light_grid_params;
 typedef struct {
@@ -1077,7 +1107,7 @@ int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *, gvt_hip_volume *const *volu
  * OUT OF SCOPE.  The fog attenuating mesh shadow rays; exact per-crossing mesh shadow rays; skipping volume shadow rays where O = 0;
  * the Domain scheduler; AMR frames, and CENTRAL frames without GVT_HIP_VOLUME_ALLOW_CENTRAL ("shadowed surfaces", CENTRAL). */
 typedef struct {
-  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
+  uint32_t flags; /* 0, or GVT_HIP_VOLUME_ALLOW_CENTRAL and GVT_HIP_VOLUME_ALLOW_AMR ORed */
   uint32_t pad;
 } gvt_hip_volume_occluder_params;
 typedef struct {

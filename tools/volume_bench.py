@@ -40,6 +40,11 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              the fused AMR frame, and the fused frame of the same level-0 grid without subgrids; median
                                              [min .. max] of each, the loop's and the fused framebuffer compared in every bit once.  Without
                                              --surfaces / --shade: the fog frame
+  python tools/volume_bench.py --fused --amr --surfaces --shade --shadows [--fog-shadows] [--mesh-shadows] --bricks 1 8 64   shadows on AMR
+                                             bricks (GVT_HIP_VOLUME_ALLOW_AMR): the same scene; per bricking and frame two tracers alternating
+                                             frame by frame in one process -- the shadowed (fog-shadowed, mesh-shadowed) frame over the AMR
+                                             bricks and the same frame over the same level-0 grid without subgrids -- and both tracers' bakes
+                                             (--fog-shadows: the light grids; --mesh-shadows: the occluder grids, the bunny inside the grid)
   python tools/volume_bench.py --domains 1 2 4 8   volume domains across ranks: the "thin" 1080p frame of the 256^3 grid in 8 and in 64 bricks
                                              (round-robin owners) through scheduler.VolumeDomainTracer, W ranks as W threads of this process on
                                              ONE GPU over the stand-in transport of tests/fake_dist.py, one lock around library calls.  Per W and
@@ -706,6 +711,65 @@ def run_fused_amr(n, split, steps, warmup, rate, vol, shaded=None):
     return out
 
 
+def run_shadow_amr(n, split, steps, warmup, rate, vol, frame, shape, first=None):
+    """--fused --amr with --shadows / --fog-shadows / --mesh-shadows: amr_bricked_scene in the bricking `split` under the "thin" table.
+    frame: "shadowed", "fog" or "mesh"; shape: "surf" (the "reached" isovalues, opacity 0.3, unlit fog), "lit" (lit fog alone: the lean
+    kernels) or "surf_lit"; one light.  Two tracers alternate frame by frame: the frame over the AMR bricks (shadow_amr=True) and the
+    same frame over the same level-0 grid without subgrids -- there is no loop to compare with.  The bakes of both are timed on their own
+    (the launches' event time).  first: the AMR framebuffer of another bricking, compared bitwise.  Returns (row, the AMR framebuffer)."""
+    t = transfer("thin")
+    scene = scenes.bunny_scene(1920, 1080) if frame == "mesh" else None
+    cam = scene.camera if scene is not None else camera()
+    if scene is not None:  # the bunny inside the grid: the subgrids are index boxes, they move with it
+        placed = scenes.mesh_in_volume(scene, vol, fill=0.6)
+        vol = scenes.VolumeData(placed.data, placed.origin, placed.spacing, vol.subgrids)
+    plain = scenes.VolumeData(vol.data, vol.origin, vol.spacing)
+    bricks = vol if split == (1, 1, 1) else scenes.split_amr_volume(vol, *split)
+    bare = plain if split == (1, 1, 1) else scenes.split_volume(plain, *split)
+    how = dict(sampling_rate=rate, shadows=True, fog_shadows=frame != "shadowed", mesh_shadows=frame == "mesh")
+    trs = {"amr": VolumeTracer(bricks, cam, t, amr_shaded=True, shadow_amr=True, **how), "plain": VolumeTracer(bare, cam, t, **how)}
+    for tr in trs.values():
+        if shape != "lit":
+            tr.set_surfaces(SURFACE_MODES["reached"], (), 0.3)
+        tr.set_lights(SHADE_LIGHTS[:1]).set_shading(shape != "surf")
+    bakes = {}
+    for k, tr in trs.items():
+        if frame != "shadowed" and shape != "surf":
+            bakes[k + "_light_bake"] = []
+            for i in range(warmup + steps):
+                tr.rebake()
+                bakes[k + "_light_bake"].append(tr.light_grid_stats["ms"])
+        if frame == "mesh":
+            bakes[k + "_occluder_bake"] = []
+            for i in range(warmup + steps):
+                tr.bake_occluders(scene)
+                bakes[k + "_occluder_bake"].append(tr.occluder_stats["ms"])
+    ms = {k: [] for k in trs}
+    for i in range(warmup + steps):
+        for k, tr in trs.items():
+            ms[k].append(timed(tr.frame))
+    ms = {k: v[warmup:] for k, v in ms.items()}
+    st, pst = trs["amr"].stats(), trs["plain"].stats()
+    fb = trs["amr"].framebuffer(False).copy()
+    out = {"mode": "shadow_amr_" + frame, "shape": shape, "n": n, "bricks": int(np.prod(split)), "sampling_rate": rate, "n_subgrids": len(vol.subgrids)}
+    for k, v in list(ms.items()) + [(k, v[warmup:]) for k, v in bakes.items()]:
+        out.update({k + "_ms_median": med(v), k + "_ms_min": round(min(v), 3), k + "_ms_max": round(max(v), 3)})
+    out["amr_over_plain"] = round(float(np.median(ms["amr"])) / float(np.median(ms["plain"])), 4)
+    for b in ("light_bake", "occluder_bake"):
+        if "amr_" + b in bakes:
+            out[b + "_amr_over_plain"] = round(float(np.median(bakes["amr_" + b][warmup:])) / float(np.median(bakes["plain_" + b][warmup:])), 4)
+    out.update({"shadowed": int(st["shadowed"]), "features": int(st["features"]), "plain_features": int(pst["features"]), "brick_visits": int(st["brick_visits"]),
+                "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "crossings_per_frame": int(st["crossings_rendered"]),
+                "samples_shaded": int(st["samples_shaded"]), "shadow_rays": int(st["shadow_rays"]), "shadow_samples": int(st["shadow_samples_marched"]),
+                "plain_samples_per_frame": int(pst["samples_marched"]), "plain_shadow_samples": int(pst["shadow_samples_marched"]),
+                "lit_pixels": int((fb[..., 3] > 0).sum()),
+                "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())})
+    for tr in trs.values():
+        for a in tr.adapters:
+            a.close()
+    return out, fb
+
+
 def run_domains(n, split, world, steps, warmup, rate, kind, vol, per_queue, overlap):
     """One bricking at one world size: `world` threads, each a rank with its own HipVolumeBackend, frames started together."""
     import threading
@@ -923,7 +987,23 @@ def main():
                         out["runs"].append(r)
                         print(json.dumps(r), flush=True)
         a.sizes = []
-    if a.fused and a.amr:  # the fused AMR frame against the loop and against the subgrid-free fused frame
+    if a.fused and a.amr and (a.shadows or a.fog_shadows or a.mesh_shadows):  # shadows on AMR bricks against the same frames without subgrids
+        if not (a.surfaces and a.shade):
+            ap.error("--amr with --shadows / --fog-shadows / --mesh-shadows goes with --fused --surfaces --shade")
+        frames = ([("shadowed", "surf")] if a.shadows else []) + ([("fog", "lit"), ("fog", "surf_lit")] if a.fog_shadows else [])
+        frames += [("mesh", "lit"), ("mesh", "surf_lit")] if a.mesh_shadows else []
+        for n in ([256] if a.sizes == [256, 512] else a.sizes):
+            vol = amr_bricked_scene(n)
+            for frame, shape in frames:
+                first = None
+                for nb in a.bricks:
+                    r, fb = run_shadow_amr(n, FUSED_SPLITS[nb], a.steps, a.warmup, 2.0 if a.rate == 1.0 else a.rate, vol, frame, shape, first)
+                    first = fb if first is None else first
+                    out["runs"].append(r)
+                    print(json.dumps(r), flush=True)
+        a.sizes = []
+        a.shadows = a.fog_shadows = a.mesh_shadows = False
+    elif a.fused and a.amr:  # the fused AMR frame against the loop and against the subgrid-free fused frame
         for n in ([256] if a.sizes == [256, 512] else a.sizes):
             vol = amr_bricked_scene(n)
             for shaded in ([None] if not (a.surfaces or a.shade) else (["surfaces"] if a.surfaces else []) + (["lit"] if a.shade else [])):
