@@ -162,8 +162,9 @@ __device__ inline void store_no_known(const RayPlanes &q, size_t i) { if (q.p5) 
 //   n0 = (c0.lo.x, c0.hi.x, c0.lo.y, c0.hi.y)   n1 = (c1.lo.x, c1.hi.x, c1.lo.y, c1.hi.y)
 //   n2 = (c0.lo.z, c0.hi.z, c1.lo.z, c1.hi.z)   n3 = (child0, child1, -, -) bit-cast ints
 // child >= 0: inner node index.  child < 0: leaf, ~child = (first_tri_slot << 3) | count (count <= 4).
-// Triangle slot (64 B = one line, leaf order): t0 = (v0.xyz, primID), t1 = (e1 = v0-v1, 0), t2 = (e2 = v2-v0, 0),
-// t3 = (Ng = e1 x e2, 0) -- all precomputed with the very float operations the test would perform.
+// Triangle slot (64 B = one line, leaf order): t0 = (v0.xyz, primID), t1 = (e1 = v0-v1, v1.x), t2 = (e2 = v2-v0, v1.y),
+// t3 = (v1.z, v2.xyz) -- the edges precomputed with the very float operations the test would perform, v1 and v2 as they are
+// for the shading kernel (lbvh.hip k_emit_tris; pinned bit for bit by tests/bvh_checker.py).
 // ---------------------------------------------------------------------------------------------
 struct BvhNode {
   float4 n0, n1, n2, n3;

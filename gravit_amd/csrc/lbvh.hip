@@ -9,7 +9,9 @@
 //   ->  collapse to 4-wide nodes, breadth first, child boxes quantised to 8 bits on a per-node grid (build_nodes4): the layout
 //       k_trace traverses.
 // Results of the closest/any-hit queries do not depend on the tree (conservative, padded boxes); only
-// speed does.
+// speed does.  The tree itself is specified by tests/bvh_checker.py (a numpy reference that predicts the
+// binary nodes and the slots bit for bit, and a validator of the 4-wide layout): a change to the key width,
+// the tie-break, the pad or the compaction order changes that file in the same commit.
 #include <string.h>
 #include <cstring>
 
@@ -1225,6 +1227,8 @@ int refit_lbvh(gvt_hip_mesh *M) {
       k_sah_sum<<<(unsigned)std::min<size_t>(2048, (M->nNodes + 255) / 256), 256, 0, st>>>(M->d_nodes, (unsigned)M->nNodes, 1.f / ra, sah_acc);
       HOK(hipMemcpyAsync(&sah_host, sah_acc, sizeof sah_host, hipMemcpyDeviceToHost, st));
       HOK(hipStreamSynchronize(st));
+    }
+    if (M->nNodes > 1) { // (as at build: a scene box without area -- a point, or extents whose products underflow -- leaves the empty sum, 1)
       M->sah_inner = 1.f + (float)((double)sah_host / 65536.0);
       M->packet_ok = M->sah_inner <= (float)C.packet_sah_max;
     }

@@ -1169,7 +1169,7 @@ int gvt_hip_wide_visit_stats(gvt_hip_mesh *, const float *org, const float *dir,
                              uint64_t *n_wide_nodes);
 /* measurement: the traversal layout as the kernels walk it -- (bytes_nodes / 64 - n_nodes) compressed 4-wide nodes of 64 bytes {origin.xyz, step.x | qlo.x[4], qhi.x[4],
  * qlo.y[4], qhi.y[4] | qlo.z[4], qhi.z[4], ref0, ref1 | ref2, ref3, step.y, step.z} (child box plane = origin + q * step; ref >= 0: node, < 0: leaf, ~ref =
- * first slot << 3 | triangles) and n_tris triangle slots of 64 bytes {v0, primID | e1 = v0 - v1, . | e2 = v2 - v0, . | .} in leaf order -- for the SIMD CPU
+ * first slot << 3 | triangles) and n_tris triangle slots of 64 bytes {v0, primID | e1 = v0 - v1, v1.x | e2 = v2 - v0, v1.y | v1.z, v2.xyz} in leaf order -- for the SIMD CPU
  * baseline of bench.py (oracle/simd_baseline.c) */
 int gvt_hip_mesh_download_wide(gvt_hip_mesh *, void *nodes4, size_t n_nodes4, void *slots, size_t n_slots);
 /* ... and the CLUSTER layout of the same nodes (built on first use; the Domain scheduler's small rounds, k_finish, walk it -- knob finish_clusters): a permutation of
