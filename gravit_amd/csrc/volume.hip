@@ -41,10 +41,23 @@
 // The contract (lattice, ownership, evaluation order, flags) is stated in include/gvt_hip.h; tests/volume_checker.py restates it in numpy.
 #include <algorithm>
 #include <cmath>
+#include <string>
 #include <type_traits>
 #include <vector>
 
 #include "gvt_internal.h"
+
+// What a brick remembers of the bake that filled its grid planes (the light grids' or the occluder grids'): planes, one per usable light
+// in the order of their bits; current: no call that makes the planes stale has touched the volume since; bake / index / count / m /
+// minv: which bake, and what it covered
+struct BakedGrids {
+  int planes = 0;
+  unsigned usable = 0;
+  bool current = false;
+  uint64_t bake = 0;
+  size_t index = 0, count = 0;
+  float m[16] = {}, minv[16] = {};
+};
 
 struct gvt_hip_volume {
   int n[3] = { 0, 0, 0 }, off[3] = { 0, 0, 0 };
@@ -95,26 +108,16 @@ struct gvt_hip_volume {
   unsigned ghost_mask = 0;       // bit 2 * axis + side: that face has a layer
   void *d_ghost = nullptr;
   uint64_t central_marches = 0;
-  // the light transmittance grids of the fog-shadowed frame (gvt_hip_volume_light_grid_bake; volume_light_grid.inc): lg_planes planes of
-  // the brick's vertices, one per usable light in the order of their bits.  lg_current: no call that changes what a shadow ray meets has
-  // touched the volume since the bake; lg_bake / lg_index / lg_count / lg_m / lg_minv: which bake, and what it covered
+  // the light transmittance grids of the fog-shadowed frame (gvt_hip_volume_light_grid_bake; volume_light_grid.inc): lg.planes planes of
+  // the brick's vertices.  lg.current: no call that changes what a shadow ray meets has touched the volume since the bake
   float *d_lgrid = nullptr;
-  int lg_planes = 0, lg_bias = 0;
-  unsigned lg_usable = 0;
-  bool lg_current = false;
-  uint64_t lg_bake = 0;
-  size_t lg_index = 0, lg_count = 0;
-  float lg_m[16] = {}, lg_minv[16] = {};
-  // the occluder grids of the mesh-shadowed frame (gvt_hip_volume_occluder_grid_bake; volume_occluder_grid.inc): og_planes uint8 planes of
-  // the brick's vertices, one per usable light in the order of their bits (1: no mesh between the vertex and the light, 0: one).
-  // og_current: neither the lights nor the subgrids were set since the bake; og_bake / og_index / og_count / og_m / og_minv: as lg_*
+  BakedGrids lg;
+  int lg_bias = 0;
+  // the occluder grids of the mesh-shadowed frame (gvt_hip_volume_occluder_grid_bake; volume_occluder_grid.inc): og.planes uint8 planes of
+  // the brick's vertices (1: no mesh between the vertex and the light, 0: one).  og.current: neither the lights nor the subgrids were
+  // set since the bake
   uint8_t *d_occ = nullptr;
-  int og_planes = 0;
-  unsigned og_usable = 0;
-  bool og_current = false;
-  uint64_t og_bake = 0;
-  size_t og_index = 0, og_count = 0;
-  float og_m[16] = {}, og_minv[16] = {};
+  BakedGrids og;
 };
 
 namespace {
@@ -1312,7 +1315,7 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   }
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
   HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
-  V->lg_current = false; // (a light grid baked under the old table is stale)
+  V->lg.current = false; // (a light grid baked under the old table is stale)
   for (int i = 0; i < 256; i++) { V->tf_a[i] = tf[i].w; V->tf_rgb[i][0] = tf[i].x; V->tf_rgb[i][1] = tf[i].y; V->tf_rgb[i][2] = tf[i].z; }
   V->tf_lo = value_lo; V->tf_hi = value_hi; V->has_tf = true;
   return rebuild_tables(V);
@@ -1337,7 +1340,7 @@ extern "C" int gvt_hip_volume_update_samples_typed(gvt_hip_volume *V, const void
   }
   hipStream_t st = gctx().stream;
   HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the samples)
-  V->lg_current = false; // (a light grid baked from the old samples is stale)
+  V->lg.current = false; // (a light grid baked from the old samples is stale)
   HIPCHK(hipMemcpyAsync(V->d_vox, samples, voxel_bytes(V->vtype) * total, (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
@@ -1377,7 +1380,7 @@ extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isova
     if (!finite || (p[0] == 0.f && p[1] == 0.f && p[2] == 0.f)) { set_error("volume_set_surfaces: slice %d has a zero or non-finite plane", i); return GVT_HIP_ERR_INVALID; }
   }
   V->n_iso = n_iso; V->n_pl = n_slices; V->surf_alpha = opacity;
-  V->lg_current = false; // (the surfaces cast shadows: a light grid baked under the old ones is stale)
+  V->lg.current = false; // (the surfaces cast shadows: a light grid baked under the old ones is stale)
   for (int i = 0; i < n_iso; i++) V->iso[i] = isovalues[i];
   for (int i = 0; i < n_slices; i++)
     for (int a = 0; a < 4; a++) V->plane[i][a] = slices[4 * i + a];
@@ -1392,8 +1395,8 @@ extern "C" int gvt_hip_volume_set_lights(gvt_hip_volume *V, const float *positio
   for (int i = 0; i < 3 * n; i++)
     if (!std::isfinite(positions[i]) || !std::isfinite(colours[i])) { set_error("volume_set_lights: light %d is not finite", i / 3); return GVT_HIP_ERR_INVALID; }
   V->n_lights = n; V->ka = ka; V->kd = kd;
-  V->lg_current = false; // (a light grid holds one plane per light of the old list)
-  V->og_current = false; // (... and so does an occluder grid)
+  V->lg.current = false; // (a light grid holds one plane per light of the old list)
+  V->og.current = false; // (... and so does an occluder grid)
   for (int j = 0; j < n; j++)
     for (int a = 0; a < 3; a++) { V->lpos[j][a] = positions[3 * j + a]; V->lcol[j][a] = colours[3 * j + a]; }
   return 0;
@@ -1710,103 +1713,115 @@ bool fused_eligible(gvt_hip_volume *const *volumes, const float *minv, size_t n_
   return true;
 }
 
-// the shaded fused kernel's instantiation for the frame's features (one of the three shaded combinations) and its by-value table.
-// CENTRAL (here and in the launchers below): the instantiation, decided by the caller from GVT_HIP_FUSED_CENTRAL in the features; the
-// argument list then ends in the ghost table (FusedGhost), else in NoGhost
-template <typename VT, bool CLIP, bool CENTRAL, typename... Args>
-void launch_fused_shaded(uint32_t features, unsigned blocks, hipStream_t st, const gvt_hip_volume *V0, const Mat4 &M, VolDev U, Args... args) {
-  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0, lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  if (surf && lit) k_volume_march_fused_shaded<VT, CLIP, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
-  else if (surf) k_volume_march_fused_shaded<VT, CLIP, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
-  else k_volume_march_fused_shaded<VT, CLIP, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
+// Runtime booleans as std::bool_constant arguments of a generic lambda: THE place a launcher turns flags into a kernel's boolean template
+// arguments.  A launcher names each instantiation once; which combinations exist is what its lambda spells, no more
+template <typename Fn>
+void with_bools(Fn f) { f(); }
+template <typename Fn, typename... Bools>
+void with_bools(Fn f, bool b, Bools... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-// the AMR kernels' instantiation for the frame's features (GVT_HIP_FUSED_AMR is among them): plain, or one of the three shaded combinations
-template <bool CLIP, typename... Args>
-void launch_fused_amr(uint32_t features, unsigned blocks, hipStream_t st, const gvt_hip_volume *V0, const Mat4 &M, VolDev U, Args... args) {
-  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0, lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  if (surf && lit) k_volume_march_fused_shaded_amr<CLIP, true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
-  else if (surf) k_volume_march_fused_shaded_amr<CLIP, true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), args...);
-  else if (lit) k_volume_march_fused_shaded_amr<CLIP, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), args...);
-  else k_volume_march_fused_amr<CLIP><<<blocks, VOL_BLOCK, 0, st>>>(U, args...);
+// the clip plane's two kernel arguments: the depth plane and its size, or none (the CLIP instantiations alone read them)
+struct ClipArgs { const float *d_t; unsigned n_clip; };
+ClipArgs clip_args(const gvt_hip_depth *depth) {
+  return depth ? ClipArgs{ depth->d_t, (unsigned)(depth->w * depth->h) } : ClipArgs{ nullptr, 0u };
 }
 
-// the shadowed kernel's instantiation: clipped or not, lit fog or not (surfaces are implied)
-template <typename VT, bool CENTRAL, typename... Args>
+// The launchers below: the kernel's instantiation for the frame's features, clipped (depth) or not, and its by-value tables.  CENTRAL: the
+// instantiation, decided by the caller from GVT_HIP_FUSED_CENTRAL in the features; the argument list (tail: the framebuffer, the work
+// counter, the counters) then ends in the ghost table (FusedGhost), else in NoGhost.
+// The shaded fused kernel: one of the three shaded combinations
+template <typename VT, bool CENTRAL, typename... Tail>
+void launch_fused_shaded(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, const FusedBrick *d_bricks,
+                         TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Tail... tail) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0;
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip, auto lit) {
+    if (surf) k_volume_march_fused_shaded<VT, clip.value, true, lit.value, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), d_bricks, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else k_volume_march_fused_shaded<VT, clip.value, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), d_bricks, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr, (features & GVT_HIP_FUSED_LIT) != 0);
+}
+
+// the AMR kernels (GVT_HIP_FUSED_AMR is among the features): plain, or one of the three shaded combinations
+template <typename... Tail>
+void launch_fused_amr(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, const FusedBrick *d_bricks,
+                      const AmrDev *d_amr, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Tail... tail) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0, lit = (features & GVT_HIP_FUSED_LIT) != 0;
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip, auto lit_c) {
+    if (surf) k_volume_march_fused_shaded_amr<clip.value, true, lit_c.value><<<blocks, VOL_BLOCK, 0, st>>>(U, surf_dev(V0, M), d_bricks, d_amr, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else if (lit) k_volume_march_fused_shaded_amr<clip.value, false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), d_bricks, d_amr, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else k_volume_march_fused_amr<clip.value><<<blocks, VOL_BLOCK, 0, st>>>(U, d_bricks, d_amr, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr, lit);
+}
+
+// the shadowed kernel: lit fog or not (surfaces are implied)
+template <typename VT, bool CENTRAL, typename... Tail>
 void launch_fused_shadow(uint32_t features, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H, const FusedBrick *d_bricks,
-                         TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
-  const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  const float *d_t = depth ? depth->d_t : nullptr;
-  const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
-  if (depth && lit) k_volume_march_fused_shadow<VT, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
-  else if (depth) k_volume_march_fused_shadow<VT, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
-  else if (lit) k_volume_march_fused_shadow<VT, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
-  else k_volume_march_fused_shadow<VT, false, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, d_t, n_clip, args...);
+                         TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Tail... tail) {
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip, auto lit) {
+    k_volume_march_fused_shadow<VT, clip.value, lit.value, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr, (features & GVT_HIP_FUSED_LIT) != 0);
 }
 
-// the fog-shadowed kernels' instantiation: clipped or not (lit fog is implied), with surfaces or -- the lean kernel -- without
-template <typename VT, bool CENTRAL, typename... Args>
+// the fog-shadowed kernels (lit fog is implied): with surfaces or -- the lean kernel -- without
+template <typename VT, bool CENTRAL, typename... Tail>
 void launch_fused_fog(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
-                      const FusedBrick *d_bricks, const FogBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
-  if (!(features & GVT_HIP_FUSED_SURFACES)) {
-    const LightDev L = light_dev(V0, M);
-    if (depth) k_volume_march_fused_fog_lean<VT, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
-    else k_volume_march_fused_fog_lean<VT, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
-    return;
-  }
-  if (depth) k_volume_march_fused_fog<VT, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, depth->d_t, (unsigned)(depth->w * depth->h), args...);
-  else k_volume_march_fused_fog<VT, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, (const float *)nullptr, 0u, args...);
+                      const FusedBrick *d_bricks, const FogBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Tail... tail) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0;
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip) {
+    if (surf) k_volume_march_fused_fog<VT, clip.value, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else k_volume_march_fused_fog_lean<VT, clip.value, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), H.usable, d_bricks, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr);
 }
 
-// the mesh-shadowed kernels' instantiation: clipped or not, lit fog or not, with surfaces or -- the lean kernel, lit fog implied -- without
-template <typename VT, bool CENTRAL, typename... Args>
+// the mesh-shadowed kernels: lit fog or not, with surfaces or -- the lean kernel, lit fog implied -- without
+template <typename VT, bool CENTRAL, typename... Tail>
 void launch_fused_mesh(uint32_t features, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
-                       const FusedBrick *d_bricks, const MeshBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Args... args) {
-  const float *d_t = depth ? depth->d_t : nullptr;
-  const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
-  if (!(features & GVT_HIP_FUSED_SURFACES)) {
-    const LightDev L = light_dev(V0, M);
-    if (depth) k_volume_march_fused_mesh_lean<VT, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else k_volume_march_fused_mesh_lean<VT, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-    return;
-  }
-  const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  if (depth && lit) k_volume_march_fused_mesh<VT, true, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-  else if (depth) k_volume_march_fused_mesh<VT, true, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-  else if (lit) k_volume_march_fused_mesh<VT, false, true, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
-  else k_volume_march_fused_mesh<VT, false, false, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, d_t, n_clip, args...);
+                       const FusedBrick *d_bricks, const MeshBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Tail... tail) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0;
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip, auto lit) {
+    if (surf) k_volume_march_fused_mesh<VT, clip.value, lit.value, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else k_volume_march_fused_mesh_lean<VT, clip.value, CENTRAL><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), H.usable, d_bricks, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr, (features & GVT_HIP_FUSED_LIT) != 0);
 }
 
-// the shadowed AMR kernels' instantiation (GVT_HIP_FUSED_AMR is among the features; float32, CELL): the kernel of the shadowed, the
-// fog-shadowed (fog) or the mesh-shadowed (mesh) frame, clipped or not, lit fog or not, with surfaces or -- the lean kernels -- without.
-// d_grids: the bricks' planes (fog or mesh), else null
-template <typename... Args>
+// the shadowed AMR kernels (GVT_HIP_FUSED_AMR is among the features; float32, CELL): the kernel of the shadowed, the fog-shadowed (fog) or
+// the mesh-shadowed (mesh) frame, lit fog or not, with surfaces or -- the lean kernels -- without.  d_grids: the bricks' planes (fog or
+// mesh), else null
+template <typename... Tail>
 void launch_fused_shadow_amr(uint32_t features, bool fog, bool mesh, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S,
                              ShadowDev H, const FusedBrick *d_bricks, const AmrDev *d_amr, const MeshBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M,
-                             Args... args) {
-  const bool lit = (features & GVT_HIP_FUSED_LIT) != 0;
-  const float *d_t = depth ? depth->d_t : nullptr;
-  const unsigned n_clip = depth ? (unsigned)(depth->w * depth->h) : 0u;
-  if ((fog || mesh) && !(features & GVT_HIP_FUSED_SURFACES)) {
-    const LightDev L = light_dev(V0, M);
-    if (mesh && depth) k_volume_march_fused_mesh_lean_amr<true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else if (mesh) k_volume_march_fused_mesh_lean_amr<false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else if (depth) k_volume_march_fused_fog_lean_amr<true><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else k_volume_march_fused_fog_lean_amr<false><<<blocks, VOL_BLOCK, 0, st>>>(U, L, H.usable, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-  } else if (mesh) {
-    if (depth && lit) k_volume_march_fused_mesh_amr<true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else if (depth) k_volume_march_fused_mesh_amr<true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else if (lit) k_volume_march_fused_mesh_amr<false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else k_volume_march_fused_mesh_amr<false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-  } else if (fog) {
-    if (depth) k_volume_march_fused_fog_amr<true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-    else k_volume_march_fused_fog_amr<false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, d_t, n_clip, args...);
-  } else {
-    if (depth && lit) k_volume_march_fused_shadow_amr<true, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
-    else if (depth) k_volume_march_fused_shadow_amr<true, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
-    else if (lit) k_volume_march_fused_shadow_amr<false, true><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
-    else k_volume_march_fused_shadow_amr<false, false><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, d_t, n_clip, args...);
-  }
+                             Tail... tail) {
+  const bool lean = (fog || mesh) && !(features & GVT_HIP_FUSED_SURFACES);
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip, auto lit) {
+    if (lean && mesh) k_volume_march_fused_mesh_lean_amr<clip.value><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), H.usable, d_bricks, d_amr, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else if (lean) k_volume_march_fused_fog_lean_amr<clip.value><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), H.usable, d_bricks, d_amr, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else if (mesh) k_volume_march_fused_mesh_amr<clip.value, lit.value><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else if (fog) k_volume_march_fused_fog_amr<clip.value><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else k_volume_march_fused_shadow_amr<clip.value, lit.value><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_amr, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr, (features & GVT_HIP_FUSED_LIT) != 0);
+}
+
+// a brick's record of the fused kernels' table (FusedBrick, volume_fused.inc).  cell_words: mc is the per-cell words of the surface visit,
+// which never reads the skip bytes (without surfaces the words hold the skip bit alone).  nb = (n - 1 + 7) / 8: the kernels recompute it
+FusedBrick fused_record(const gvt_hip_volume *B, bool cell_words) {
+  FusedBrick R{};
+  R.vox = B->d_vox;
+  R.mc = cell_words ? (const uint8_t *)B->d_cells : B->d_mc;
+  R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2];
+  for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
+  return R;
+}
+// ... and its four AMR pointers beside it (AmrDev, volume_fused_amr.inc): null on a brick without subgrids
+AmrDev amr_record(const gvt_hip_volume *B) {
+  return B->sub.empty() ? AmrDev{ nullptr, nullptr, nullptr, nullptr } : AmrDev{ B->d_amr_mc, B->d_amr_list, B->d_amr_desc, B->d_amr_vox };
 }
 
 // the frame in one launch: camera list, brick table (through the pinned staging block), march, ONE host wait (the counters' read-back).
@@ -1863,17 +1878,12 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   AmrDev *ha = (AmrDev *)(hm + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
-    FusedBrick R{};
-    R.vox = B->d_vox;
-    R.mc = (features & GVT_HIP_FUSED_SURFACES) ? (const uint8_t *)B->d_cells : B->d_mc; // (the surface visit reads the per-cell words, never the skip bytes)
+    h[i] = fused_record(B, (features & GVT_HIP_FUSED_SURFACES) != 0);
     if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
     else if (fog && amr) hm[i] = MeshBrick{ B->d_lgrid, nullptr };
     else if (fog) hg[i].grid = B->d_lgrid;
     if (central) hf[i] = B->d_ghost; // (null on a brick without an interior face: none of its layers is ever read)
-    if (amr) ha[i] = B->sub.empty() ? AmrDev{ nullptr, nullptr, nullptr, nullptr } : AmrDev{ B->d_amr_mc, B->d_amr_list, B->d_amr_desc, B->d_amr_vox };
-    R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2]; // (nb = (n - 1 + 7) / 8: the kernel recomputes it)
-    for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
-    h[i] = R;
+    if (amr) ha[i] = amr_record(B);
   }
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (mesh || (fog && amr)) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
@@ -1889,45 +1899,39 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   const RayPlanes P = make_planes(q_cam->d_planes, q_cam->cap);
   const unsigned n_pix = (unsigned)(fb->w * fb->h);
   const FusedGhost HG{ d_faces, volumes[0]->gn[0], volumes[0]->gn[1], volumes[0]->gn[2] };
-  if (n && amr && shadow) { // (the fog frame's table is a MeshBrick table here, its occluder pointers null)
-    launch_fused_shadow_amr(features, fog, mesh, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, (const AmrDev *)d_amr,
-                            (const MeshBrick *)d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work, d_stats);
-  } else if (n && amr) { // (F32 and CELL: fused_eligible has compared the voxel types, and a brick with subgrids is F32)
-    if (depth) launch_fused_amr<true>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, (const AmrDev *)d_amr, T->dev(), P, (unsigned)n, M, depth->d_t,
-                                      (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
-    else launch_fused_amr<false>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, (const AmrDev *)d_amr, T->dev(), P, (unsigned)n, M,
-                                 (const float *)nullptr, 0u, fb->d_rgba, n_pix, work, d_stats);
-  } else if (n)
-    with_voxel_type(volumes[0]->vtype, [&](auto t) {
+  const gvt_hip_volume *V0 = volumes[0];
+  if (n && amr && shadow) // (the fog frame's table is a MeshBrick table here, its occluder pointers null)
+    launch_fused_shadow_amr(features, fog, mesh, V0, depth, blocks, C.stream, vol_dev(V0), surf_dev(V0, M), *shadow, d_bricks, d_amr, d_mgrids, T->dev(), P, (unsigned)n, M,
+                            fb->d_rgba, n_pix, work, d_stats);
+  else if (n && amr) // (F32 and CELL: fused_eligible has compared the voxel types, and a brick with subgrids is F32)
+    launch_fused_amr(features, V0, depth, blocks, C.stream, vol_dev(V0), d_bricks, d_amr, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work, d_stats);
+  else if (n)
+    with_voxel_type(V0->vtype, [&](auto t) {
       using VT = decltype(t);
       // the shaded launches, for the kernels' CENTRAL instantiation (gh: FusedGhost) or the other (NoGhost)
       const auto shaded = [&](auto central_c, auto gh) {
         constexpr bool CENTRAL = decltype(central_c)::value;
         if (shadow && mesh)
-          launch_fused_mesh<VT, CENTRAL>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba,
-                                         n_pix, work, d_stats, gh);
+          launch_fused_mesh<VT, CENTRAL>(features, V0, depth, blocks, C.stream, vol_dev(V0), surf_dev(V0, M), *shadow, d_bricks, d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
+                                         work, d_stats, gh);
         else if (shadow && fog)
-          launch_fused_fog<VT, CENTRAL>(features, volumes[0], depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, d_grids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
+          launch_fused_fog<VT, CENTRAL>(features, V0, depth, blocks, C.stream, vol_dev(V0), surf_dev(V0, M), *shadow, d_bricks, d_grids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
                                         work, d_stats, gh);
         else if (shadow)
-          launch_fused_shadow<VT, CENTRAL>(features, depth, blocks, C.stream, vol_dev(volumes[0]), surf_dev(volumes[0], M), *shadow, d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba,
-                                           n_pix, work, d_stats, gh);
-        else if (depth)
-          launch_fused_shaded<VT, true, CENTRAL>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
-                                                 (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats, gh);
+          launch_fused_shadow<VT, CENTRAL>(features, depth, blocks, C.stream, vol_dev(V0), surf_dev(V0, M), *shadow, d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work,
+                                           d_stats, gh);
         else
-          launch_fused_shaded<VT, false, CENTRAL>(features, blocks, C.stream, volumes[0], M, vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, (const float *)nullptr, 0u,
-                                                  fb->d_rgba, n_pix, work, d_stats, gh);
+          launch_fused_shaded<VT, CENTRAL>(features, V0, depth, blocks, C.stream, vol_dev(V0), d_bricks, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix, work, d_stats, gh);
       };
       if (shadow || features) {
         if (central) shaded(std::true_type{}, HG);
         else shaded(std::false_type{}, NoGhost{});
         return;
       }
-      if (depth) k_volume_march_fused<VT, true><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, depth->d_t,
-                                                                                   (unsigned)(depth->w * depth->h), fb->d_rgba, n_pix, work, d_stats);
-      else k_volume_march_fused<VT, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(volumes[0]), d_bricks, T->dev(), P, (unsigned)n, M, nullptr, 0u, fb->d_rgba,
-                                                                               n_pix, work, d_stats);
+      const ClipArgs c = clip_args(depth);
+      with_bools([&](auto clip) {
+        k_volume_march_fused<VT, clip.value><<<blocks, VOL_BLOCK, 0, C.stream>>>(vol_dev(V0), d_bricks, T->dev(), P, (unsigned)n, M, c.d_t, c.n_clip, fb->d_rgba, n_pix, work, d_stats);
+      }, depth != nullptr);
     });
   HIPCHK(hipGetLastError());
   // (pinned words 16..27 of the context: six 64-bit counters, and 28..29 the AMR kernels' seventh; 30..31 are free, 32..41 the builder's; the shadowed frame's eleven are words 42..63)
@@ -2024,31 +2028,34 @@ ShadowDev shadow_dev(const gvt_hip_volume *A, int bias) {
   return H;
 }
 
-// Do these bricks, in this order and under these matrices, all hold a light grid of ONE bake that nothing has made stale since?
-bool light_grids_current(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, unsigned usable, const char **why) {
+// Do these bricks, in this order and under these matrices, all hold a grid (planes: d_lgrid or d_occ; grids: lg or og) of ONE bake that
+// nothing has made stale since?  what / bake_fn / stale_by: the three words in which the light grids' messages and the occluder grids' differ
+template <typename P>
+bool grids_current(P *gvt_hip_volume::*planes, BakedGrids gvt_hip_volume::*grids, const char *what, const char *bake_fn, const char *stale_by,
+                   gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, unsigned usable, std::string &why) {
+  const std::string w(what);
+  const BakedGrids &G0 = volumes[0]->*grids;
   for (size_t i = 0; i < n_inst; i++) {
-    const gvt_hip_volume *B = volumes[i];
-    if (!B->d_lgrid) { *why = "a brick holds no light grid (gvt_hip_volume_light_grid_bake)"; return false; }
-    if (!B->lg_current) { *why = "a brick's light grid is stale: its samples, table, surfaces, lights or subgrids were set after the bake"; return false; }
-    if (B->lg_bake != volumes[0]->lg_bake || B->lg_index != i || B->lg_count != n_inst) { *why = "the light grids were not baked over exactly these bricks in this order"; return false; }
-    if (!same_bits(B->lg_m, m + 16 * i, sizeof(B->lg_m)) || !same_bits(B->lg_minv, minv + 16 * i, sizeof(B->lg_minv))) { *why = "the light grids were baked under another matrix"; return false; }
-    if (B->lg_usable != usable || B->lg_planes != __builtin_popcount(usable)) { *why = "the light grids were baked for other lights"; return false; }
+    const BakedGrids &G = volumes[i]->*grids;
+    if (!(volumes[i]->*planes)) why = "a brick holds no " + w + " grid (" + bake_fn + ")";
+    else if (!G.current) why = "a brick's " + w + " grid is stale: its " + stale_by + " were set after the bake";
+    else if (G.bake != G0.bake || G.index != i || G.count != n_inst) why = "the " + w + " grids were not baked over exactly these bricks in this order";
+    else if (!same_bits(G.m, m + 16 * i, sizeof(G.m)) || !same_bits(G.minv, minv + 16 * i, sizeof(G.minv))) why = "the " + w + " grids were baked under another matrix";
+    else if (G.usable != usable || G.planes != __builtin_popcount(usable)) why = "the " + w + " grids were baked for other lights";
+    else continue;
+    return false;
   }
   return true;
 }
 
-// Do these bricks, in this order and under these matrices, all hold an occluder grid of ONE bake that nothing has made stale since?
-bool occluder_grids_current(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, unsigned usable, const char **why) {
-  for (size_t i = 0; i < n_inst; i++) {
-    const gvt_hip_volume *B = volumes[i];
-    if (!B->d_occ) { *why = "a brick holds no occluder grid (gvt_hip_volume_occluder_grid_bake)"; return false; }
-    if (!B->og_current) { *why = "a brick's occluder grid is stale: its lights or subgrids were set after the bake"; return false; }
-    if (B->og_bake != volumes[0]->og_bake || B->og_index != i || B->og_count != n_inst) { *why = "the occluder grids were not baked over exactly these bricks in this order"; return false; }
-    if (!same_bits(B->og_m, m + 16 * i, sizeof(B->og_m)) || !same_bits(B->og_minv, minv + 16 * i, sizeof(B->og_minv))) { *why = "the occluder grids were baked under another matrix"; return false; }
-    if (B->og_usable != usable || B->og_planes != __builtin_popcount(usable)) { *why = "the occluder grids were baked for other lights"; return false; }
-  }
-  return true;
+// a bake's commit on one brick (the planes' pointer is the caller's), and a release's reset
+void grids_commit(BakedGrids &G, unsigned usable, uint64_t bake, size_t index, size_t count, const float *m, const float *minv) {
+  G.planes = __builtin_popcount(usable); G.usable = usable; G.current = true;
+  G.bake = bake; G.index = index; G.count = count;
+  std::memcpy(G.m, m + 16 * index, sizeof(G.m));
+  std::memcpy(G.minv, minv + 16 * index, sizeof(G.minv));
 }
+void grids_reset(BakedGrids &G) { G.planes = 0; G.usable = 0; G.current = false; G.bake = 0; }
 
 // the shadowed frames.  fog: gvt_hip_volume_frame_fog_shadowed; mesh (with fog): gvt_hip_volume_frame_mesh_shadowed, *mesh_ran = did its
 // kernel run? (fn: the entry point's name in the error texts)
@@ -2085,14 +2092,17 @@ int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip
     }
     const ShadowDev H = shadow_dev(volumes[0], params->bias);
     fog_ran = fog && (features & GVT_HIP_FUSED_LIT) && H.usable; // (no lit fog: gvt_hip_volume_frame_shadowed in every bit; no usable light: every Tg = 1, nothing is read)
-    if (fog_ran && !light_grids_current(volumes, m, minv, n_inst, H.usable, &why)) {
-      set_error("%s: the frame has lit fog but its bricks do not all hold a current light grid: %s", fn, why);
+    std::string stale;
+    if (fog_ran && !grids_current(&gvt_hip_volume::d_lgrid, &gvt_hip_volume::lg, "light", "gvt_hip_volume_light_grid_bake", "samples, table, surfaces, lights or subgrids",
+                                  volumes, m, minv, n_inst, H.usable, stale)) {
+      set_error("%s: the frame has lit fog but its bricks do not all hold a current light grid: %s", fn, stale.c_str());
       return GVT_HIP_ERR_INVALID;
     }
     // (the mesh frame without a usable light is the fog-shadowed frame in every respect: no occluder grid is needed)
     const bool with_mesh = mesh && H.usable;
-    if (with_mesh && !occluder_grids_current(volumes, m, minv, n_inst, H.usable, &why)) {
-      set_error("%s: the frame has surfaces or lit fog but its bricks do not all hold a current occluder grid: %s", fn, why);
+    if (with_mesh && !grids_current(&gvt_hip_volume::d_occ, &gvt_hip_volume::og, "occluder", "gvt_hip_volume_occluder_grid_bake", "lights or subgrids", volumes, m, minv,
+                                    n_inst, H.usable, stale)) {
+      set_error("%s: the frame has surfaces or lit fog but its bricks do not all hold a current occluder grid: %s", fn, stale.c_str());
       return GVT_HIP_ERR_INVALID;
     }
     if (fog && (features & GVT_HIP_FUSED_LIT) && !(features & GVT_HIP_FUSED_SURFACES) && !H.usable) // (lit fog alone and no light casts a ray: the shaded fused frame)
@@ -2139,6 +2149,48 @@ extern "C" int gvt_hip_volume_frame_fog_shadowed(gvt_hip_top *T, gvt_hip_volume 
 }
 
 namespace {
+
+// What one bake owns until it commits: the bricks' fresh planes (P: float for the light grids, uint8_t for the occluder grids) and the two
+// events around its launches.  The destructor destroys the events and frees every plane that was not committed, so each failure path
+// is a return; a path with work in flight drains the stream first (fail does).  fn: the entry point's name in the error texts
+template <typename P>
+struct BakeScope {
+  const char *fn;
+  hipStream_t stream;
+  std::vector<P *> fresh;
+  uint64_t bytes = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  BakeScope(const char *fn_, hipStream_t st, size_t n_inst) : fn(fn_), stream(st), fresh(n_inst, nullptr) {}
+  BakeScope(const BakeScope &) = delete;
+  ~BakeScope() {
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    for (P *p : fresh) hipFree(p);
+  }
+  // the new planes, all before any brick changes: n_usable planes of each brick's vertices
+  int allocate(gvt_hip_volume *const *volumes, unsigned n_usable) {
+    for (size_t i = 0; i < fresh.size(); i++) {
+      const size_t nb = sizeof(P) * (size_t)volumes[i]->n[0] * volumes[i]->n[1] * volumes[i]->n[2] * n_usable;
+      if (hipMalloc((void **)&fresh[i], nb) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: no device memory for the planes of brick %zu (%zu bytes); the old grids are kept", fn, i, nb);
+        return GVT_HIP_ERR_CAPACITY;
+      }
+      bytes += nb;
+    }
+    return 0;
+  }
+  int fail(const char *what) {
+    set_error("%s: %s failed: %s; the old grids are kept", fn, what, hipGetErrorString(hipGetLastError()));
+    hipStreamSynchronize(stream);
+    return GVT_HIP_ERR_DEVICE;
+  }
+  P *commit(size_t i) { // (the brick owns the planes from here)
+    P *p = fresh[i];
+    fresh[i] = nullptr;
+    return p;
+  }
+};
 
 // What both bakes (the light grids' and the occluder grids') ask of their arguments and of their bricks.  fn: the entry point's name in the
 // error texts.  bake_args: no null pointer, 1 to VOL_DEST_MAX bricks that have a table, flags of GVT_HIP_VOLUME_ALLOW_CENTRAL and
@@ -2218,63 +2270,37 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
   const ShadowDev H = shadow_dev(A, params->bias);
   const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
   Ctx &C = gctx();
-  // the new planes, all before any brick changes
-  std::vector<float *> fresh(n_inst, nullptr);
-  const auto drop = [&]() { for (float *p : fresh) hipFree(p); };
-  uint64_t bytes = 0;
-  for (size_t i = 0; i < n_inst; i++) {
-    const size_t nb = sizeof(float) * (size_t)volumes[i]->n[0] * volumes[i]->n[1] * volumes[i]->n[2] * n_usable;
-    if (hipMalloc((void **)&fresh[i], nb) != hipSuccess) {
-      (void)hipGetLastError();
-      drop();
-      set_error("volume_light_grid_bake: no device memory for the planes of brick %zu (%zu bytes); the old grids are kept", i, nb);
-      return GVT_HIP_ERR_CAPACITY;
-    }
-    bytes += nb;
-  }
+  BakeScope<float> own("volume_light_grid_bake", C.stream, n_inst);
+  if ((rc = own.allocate(volumes, n_usable))) return rc;
   FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
   LightGridBrick *d_parts = (LightGridBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(LightGridBrick) * n_inst);
   AmrDev *d_amr = amr ? (AmrDev *)scratch_get(SCR_VOL_AMR, sizeof(AmrDev) * n_inst) : nullptr;
   unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const auto fail = [&](const char *what) {
-    set_error("volume_light_grid_bake: %s failed: %s; the old grids are kept", what, hipGetErrorString(hipGetLastError()));
-    hipStreamSynchronize(C.stream);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    drop();
-    return GVT_HIP_ERR_DEVICE;
-  };
-  if (!d_bricks || !d_parts || !d_stats || !work || (amr && !d_amr)) return fail("a scratch allocation");
+  if (!d_bricks || !d_parts || !d_stats || !work || (amr && !d_amr)) return own.fail("a scratch allocation");
   static_assert(VOL_BAKE_STATS <= VOL_FUSED_SHADOW_STATS, "the fused frames' counter words serve the bake");
   static_assert((sizeof(FusedBrick) + sizeof(LightGridBrick) + sizeof(AmrDev)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the three tables fit the staging block");
   void *stage = nullptr;
-  if (pinned_stage_begin(&stage)) return fail("the staging block");
+  if (pinned_stage_begin(&stage)) return own.fail("the staging block");
   FusedBrick *h = (FusedBrick *)stage;
   LightGridBrick *hp = (LightGridBrick *)(h + VOL_DEST_MAX);
   AmrDev *ha = (AmrDev *)(hp + VOL_DEST_MAX);
   unsigned first = 0;
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
-    FusedBrick R{};
-    R.vox = B->d_vox;
-    R.mc = (const uint8_t *)B->d_cells; // (the surface visit's per-cell words: without surfaces they hold the skip bit alone)
-    R.nx = B->n[0]; R.ny = B->n[1]; R.nz = B->n[2]; R.ox = B->off[0]; R.oy = B->off[1]; R.oz = B->off[2];
-    for (int a = 0; a < 3; a++) { R.lo[a] = B->lo[a]; R.hi[a] = B->hi[a]; }
-    h[i] = R;
-    hp[i] = LightGridBrick{ fresh[i], first, 0u };
-    if (amr) ha[i] = B->sub.empty() ? AmrDev{ nullptr, nullptr, nullptr, nullptr } : AmrDev{ B->d_amr_mc, B->d_amr_list, B->d_amr_desc, B->d_amr_vox };
+    h[i] = fused_record(B, true);
+    hp[i] = LightGridBrick{ own.fresh[i], first, 0u };
+    if (amr) ha[i] = amr_record(B);
     first += (unsigned)((size_t)B->n[0] * B->n[1] * B->n[2]) * n_usable;
   }
   const unsigned n = first;
   bool ok = hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess &&
             hipMemcpyAsync(d_parts, hp, sizeof(LightGridBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess &&
             (!amr || hipMemcpyAsync(d_amr, ha, sizeof(AmrDev) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess);
-  if (pinned_stage_end() || !ok) return fail("the table upload");
+  if (pinned_stage_end() || !ok) return own.fail("the table upload");
   ok = hipMemsetAsync(work, 0, sizeof(unsigned), C.stream) == hipSuccess && hipMemsetAsync(d_stats, 0, VOL_BAKE_STATS * sizeof(unsigned long long), C.stream) == hipSuccess &&
-       hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-  if (!ok) return fail("the launch's preparation");
+       hipEventCreate(&own.e0) == hipSuccess && hipEventCreate(&own.e1) == hipSuccess;
+  if (!ok) return own.fail("the launch's preparation");
   Mat4 M, Mi;
   for (int k = 0; k < 16; k++) { M.m[k] = m[k]; Mi.m[k] = minv[k]; }
   // the whole grid as one brick: offset 0, counts = the global counts, the global vertex box (gvt_hip_volume_create's expressions)
@@ -2284,7 +2310,7 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
   U.nbx = (A->gn[0] - 1 + 7) / 8; U.nby = (A->gn[1] - 1 + 7) / 8;
   for (int a = 0; a < 3; a++) { U.lo[a] = A->go[a] + (float)0 * A->sp[a]; U.hi[a] = A->go[a] + (float)(A->gn[a] - 1) * A->sp[a]; }
   const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
-  ok = hipEventRecord(e0, C.stream) == hipSuccess;
+  ok = hipEventRecord(own.e0, C.stream) == hipSuccess;
   if (ok && amr) // (F32: a brick with subgrids is, and fused_eligible has compared the voxel types)
     k_volume_bake_light_amr<<<blocks, VOL_BLOCK, 0, C.stream>>>(U, surf_dev(A, Mi), H, d_bricks, (const AmrDev *)d_amr, d_parts, (unsigned)n_inst, n, M, Mi, work, d_stats);
   else if (ok)
@@ -2294,26 +2320,23 @@ extern "C" int gvt_hip_volume_light_grid_bake(gvt_hip_volume *const *volumes, co
     });
   unsigned long long h_stats[VOL_BAKE_STATS] = {};
   float ms = 0.f;
-  ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(e1, C.stream) == hipSuccess &&
+  ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(own.e1, C.stream) == hipSuccess &&
        hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, C.stream) == hipSuccess && hipStreamSynchronize(C.stream) == hipSuccess &&
-       hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-  if (!ok) return fail("the bake kernel");
-  hipEventDestroy(e0); hipEventDestroy(e1);
+       hipEventElapsedTime(&ms, own.e0, own.e1) == hipSuccess;
+  if (!ok) return own.fail("the bake kernel");
   // commit: every brick at once
   static uint64_t bake_serial = 0;
   bake_serial++;
   for (size_t i = 0; i < n_inst; i++) {
     gvt_hip_volume *B = volumes[i];
     hipFree(B->d_lgrid);
-    B->d_lgrid = fresh[i];
-    B->lg_planes = (int)n_usable; B->lg_bias = params->bias; B->lg_usable = H.usable; B->lg_current = true;
-    B->lg_bake = bake_serial; B->lg_index = i; B->lg_count = n_inst;
-    std::memcpy(B->lg_m, m + 16 * i, sizeof(B->lg_m));
-    std::memcpy(B->lg_minv, minv + 16 * i, sizeof(B->lg_minv));
+    B->d_lgrid = own.commit(i);
+    B->lg_bias = params->bias;
+    grids_commit(B->lg, H.usable, bake_serial, i, n_inst, m, minv);
   }
   if (stats) {
     gvt_hip_volume_light_grid_stats O{};
-    O.rays = n; O.samples_marched = h_stats[0]; O.samples_gathered = h_stats[1]; O.crossings = h_stats[2]; O.bytes = bytes; O.ms = ms;
+    O.rays = n; O.samples_marched = h_stats[0]; O.samples_gathered = h_stats[1]; O.crossings = h_stats[2]; O.bytes = own.bytes; O.ms = ms;
     *stats = O;
   }
   return 0;
@@ -2323,12 +2346,12 @@ extern "C" int gvt_hip_volume_light_grid_download(gvt_hip_volume *V, int light, 
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!V || !out) { set_error("volume_light_grid_download: null argument"); return GVT_HIP_ERR_INVALID; }
   if (!V->d_lgrid) { set_error("volume_light_grid_download: the volume holds no light grid"); return GVT_HIP_ERR_INVALID; }
-  if (light < 0 || light >= GVT_HIP_VOLUME_MAX_LIGHTS || !((V->lg_usable >> light) & 1u)) {
+  if (light < 0 || light >= GVT_HIP_VOLUME_MAX_LIGHTS || !((V->lg.usable >> light) & 1u)) {
     set_error("volume_light_grid_download: light %d was not usable at the bake and has no grid (its transmittance is 1)", light);
     return GVT_HIP_ERR_INVALID;
   }
   const size_t n_vert = (size_t)V->n[0] * V->n[1] * V->n[2];
-  const int plane = __builtin_popcount(V->lg_usable & ((1u << light) - 1u));
+  const int plane = __builtin_popcount(V->lg.usable & ((1u << light) - 1u));
   HIPCHK(hipStreamSynchronize(gctx().stream));
   HIPCHK(hipMemcpy(out, V->d_lgrid + n_vert * (size_t)plane, sizeof(float) * n_vert, hipMemcpyDeviceToHost));
   return 0;
@@ -2338,10 +2361,10 @@ extern "C" int gvt_hip_volume_light_grid_info(gvt_hip_volume *V, gvt_hip_volume_
   if (!V || !out) { set_error("volume_light_grid_info: null argument"); return GVT_HIP_ERR_INVALID; }
   gvt_hip_volume_light_grid_state I{};
   I.present = V->d_lgrid ? 1u : 0u;
-  I.current = (V->d_lgrid && V->lg_current) ? 1u : 0u;
-  I.n_planes = V->d_lgrid ? V->lg_planes : 0;
+  I.current = (V->d_lgrid && V->lg.current) ? 1u : 0u;
+  I.n_planes = V->d_lgrid ? V->lg.planes : 0;
   I.bias = V->d_lgrid ? V->lg_bias : 0;
-  I.bytes = V->d_lgrid ? sizeof(float) * (uint64_t)V->n[0] * V->n[1] * V->n[2] * (uint64_t)V->lg_planes : 0;
+  I.bytes = V->d_lgrid ? sizeof(float) * (uint64_t)V->n[0] * V->n[1] * V->n[2] * (uint64_t)V->lg.planes : 0;
   *out = I;
   return 0;
 }
@@ -2353,7 +2376,8 @@ extern "C" int gvt_hip_volume_light_grid_release(gvt_hip_volume *V) {
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a frame in flight reads the planes)
   hipFree(V->d_lgrid);
   V->d_lgrid = nullptr;
-  V->lg_planes = 0; V->lg_bias = 0; V->lg_usable = 0; V->lg_current = false; V->lg_bake = 0;
+  grids_reset(V->lg);
+  V->lg_bias = 0;
   return 0;
 }
 
@@ -2394,20 +2418,8 @@ extern "C" int gvt_hip_volume_occluder_grid_bake(gvt_hip_volume *const *volumes,
   const ShadowDev H = shadow_dev(A, 1); // (the directions and their bits; the bias is the light grid's business)
   const unsigned n_usable = (unsigned)__builtin_popcount(H.usable);
   Ctx &C = gctx();
-  // the new planes, all before any brick changes
-  std::vector<uint8_t *> fresh(n_inst, nullptr);
-  const auto drop = [&]() { for (uint8_t *p : fresh) hipFree(p); };
-  uint64_t bytes = 0;
-  for (size_t i = 0; i < n_inst; i++) {
-    const size_t nb = (size_t)volumes[i]->n[0] * volumes[i]->n[1] * volumes[i]->n[2] * n_usable;
-    if (hipMalloc((void **)&fresh[i], nb) != hipSuccess) {
-      (void)hipGetLastError();
-      drop();
-      set_error("volume_occluder_grid_bake: no device memory for the planes of brick %zu (%zu bytes); the old grids are kept", i, nb);
-      return GVT_HIP_ERR_CAPACITY;
-    }
-    bytes += nb;
-  }
+  BakeScope<uint8_t> own("volume_occluder_grid_bake", C.stream, n_inst);
+  if ((rc = own.allocate(volumes, n_usable))) return rc;
   const unsigned n = (unsigned)(verts * n_usable);
   const unsigned chunk = std::min(n, C.occluder_chunk > 0 ? (unsigned)C.occluder_chunk : VOL_OCC_CHUNK);
   OccluderBrick *d_parts = (OccluderBrick *)scratch_get(SCR_VOL_GRIDS, sizeof(OccluderBrick) * n_inst);
@@ -2415,31 +2427,22 @@ extern "C" int gvt_hip_volume_occluder_grid_bake(gvt_hip_volume *const *volumes,
   uint8_t *d_O = (uint8_t *)scratch_get(SCR_VOL_OCC, chunk);
   int *d_flags = n_mesh_inst ? (int *)scratch_get(SCR_GENERAL, sizeof(int) * (size_t)chunk) : nullptr;
   unsigned long long *d_blocked = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const auto fail = [&](const char *what) {
-    set_error("volume_occluder_grid_bake: %s failed: %s; the old grids are kept", what, hipGetErrorString(hipGetLastError()));
-    hipStreamSynchronize(C.stream);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    drop();
-    return GVT_HIP_ERR_DEVICE;
-  };
-  if (!d_parts || !d_rays || !d_O || (n_mesh_inst && !d_flags) || !d_blocked) return fail("a scratch allocation");
+  if (!d_parts || !d_rays || !d_O || (n_mesh_inst && !d_flags) || !d_blocked) return own.fail("a scratch allocation");
   static_assert(sizeof(OccluderBrick) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the table fits the staging block");
   void *stage = nullptr;
-  if (pinned_stage_begin(&stage)) return fail("the staging block");
+  if (pinned_stage_begin(&stage)) return own.fail("the staging block");
   OccluderBrick *hp = (OccluderBrick *)stage;
   unsigned first = 0;
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
-    hp[i] = OccluderBrick{ fresh[i], first, B->n[0], B->n[1], B->n[2], B->off[0], B->off[1], B->off[2] };
+    hp[i] = OccluderBrick{ own.fresh[i], first, B->n[0], B->n[1], B->n[2], B->off[0], B->off[1], B->off[2] };
     first += (unsigned)((size_t)B->n[0] * B->n[1] * B->n[2]) * n_usable;
   }
   bool ok = hipMemcpyAsync(d_parts, hp, sizeof(OccluderBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess;
-  if (pinned_stage_end() || !ok) return fail("the table upload");
-  ok = hipMemsetAsync(d_blocked, 0, sizeof(unsigned long long), C.stream) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
-       hipEventRecord(e0, C.stream) == hipSuccess;
-  if (!ok) return fail("the launches' preparation");
+  if (pinned_stage_end() || !ok) return own.fail("the table upload");
+  ok = hipMemsetAsync(d_blocked, 0, sizeof(unsigned long long), C.stream) == hipSuccess && hipEventCreate(&own.e0) == hipSuccess && hipEventCreate(&own.e1) == hipSuccess &&
+       hipEventRecord(own.e0, C.stream) == hipSuccess;
+  if (!ok) return own.fail("the launches' preparation");
   Mat4 M;
   for (int k = 0; k < 16; k++) M.m[k] = m[k];
   RayPlanes P{};
@@ -2447,49 +2450,43 @@ extern "C" int gvt_hip_volume_occluder_grid_bake(gvt_hip_volume *const *volumes,
   uint64_t launches = 0;
   for (unsigned base = 0; base < n; base += chunk) {
     const unsigned nc = std::min(chunk, n - base);
-    if (hipMemsetAsync(d_O, 1, nc, C.stream) != hipSuccess) return fail("the chunk's clear");
+    if (hipMemsetAsync(d_O, 1, nc, C.stream) != hipSuccess) return own.fail("the chunk's clear");
     if (n_mesh_inst) {
       k_occluder_rays<<<blocks_of(nc), VOL_BLOCK, 0, C.stream>>>(A->go[0], A->go[1], A->go[2], A->sp[0], A->sp[1], A->sp[2], H, d_parts, (unsigned)n_inst, base, nc, M, P.p0, P.p1);
-      if (hipGetLastError() != hipSuccess) return fail("the ray kernel");
+      if (hipGetLastError() != hipSuccess) return own.fail("the ray kernel");
     }
     for (size_t i = 0; i < n_mesh_inst; i++) {
       Mat4 Mi;
       for (int k = 0; k < 16; k++) Mi.m[k] = mesh_minv[16 * i + k];
       if ((rc = launch_any_flags(meshes[i], P, nc, true, Mi, GVT_RAY_EPSILON, d_flags))) { // (its own message stands)
         hipStreamSynchronize(C.stream);
-        hipEventDestroy(e0); hipEventDestroy(e1);
-        drop();
         return rc;
       }
       launches++;
       k_occluder_fold<<<blocks_of(nc), VOL_BLOCK, 0, C.stream>>>(d_flags, nc, d_O);
-      if (hipGetLastError() != hipSuccess) return fail("the fold kernel");
+      if (hipGetLastError() != hipSuccess) return own.fail("the fold kernel");
     }
     k_occluder_pack<<<blocks_of(nc), VOL_BLOCK, 0, C.stream>>>(d_O, d_parts, (unsigned)n_inst, base, nc, d_blocked);
-    if (hipGetLastError() != hipSuccess) return fail("the pack kernel");
+    if (hipGetLastError() != hipSuccess) return own.fail("the pack kernel");
   }
   unsigned long long h_blocked = 0;
   float ms = 0.f;
-  ok = hipEventRecord(e1, C.stream) == hipSuccess && hipMemcpyAsync(&h_blocked, d_blocked, sizeof(h_blocked), hipMemcpyDeviceToHost, C.stream) == hipSuccess &&
-       (!n_mesh_inst || trav_overflow_fetch_async() == 0) && hipStreamSynchronize(C.stream) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-  if (!ok) return fail("the bake's last wait");
-  hipEventDestroy(e0); hipEventDestroy(e1);
-  if (n_mesh_inst && (rc = trav_overflow_result())) { drop(); return rc; } // (GVT_HIP_ERR_DEVICE: the flags are incomplete; the old grids are kept)
+  ok = hipEventRecord(own.e1, C.stream) == hipSuccess && hipMemcpyAsync(&h_blocked, d_blocked, sizeof(h_blocked), hipMemcpyDeviceToHost, C.stream) == hipSuccess &&
+       (!n_mesh_inst || trav_overflow_fetch_async() == 0) && hipStreamSynchronize(C.stream) == hipSuccess && hipEventElapsedTime(&ms, own.e0, own.e1) == hipSuccess;
+  if (!ok) return own.fail("the bake's last wait");
+  if (n_mesh_inst && (rc = trav_overflow_result())) return rc; // (GVT_HIP_ERR_DEVICE: the flags are incomplete; the old grids are kept)
   // commit: every brick at once
   static uint64_t bake_serial = 0;
   bake_serial++;
   for (size_t i = 0; i < n_inst; i++) {
     gvt_hip_volume *B = volumes[i];
     hipFree(B->d_occ);
-    B->d_occ = fresh[i];
-    B->og_planes = (int)n_usable; B->og_usable = H.usable; B->og_current = true;
-    B->og_bake = bake_serial; B->og_index = i; B->og_count = n_inst;
-    std::memcpy(B->og_m, m + 16 * i, sizeof(B->og_m));
-    std::memcpy(B->og_minv, minv + 16 * i, sizeof(B->og_minv));
+    B->d_occ = own.commit(i);
+    grids_commit(B->og, H.usable, bake_serial, i, n_inst, m, minv);
   }
   if (stats) {
     gvt_hip_volume_occluder_stats O{};
-    O.rays = n; O.rays_blocked = h_blocked; O.any_hit_launches = launches; O.bytes = bytes; O.ms = ms;
+    O.rays = n; O.rays_blocked = h_blocked; O.any_hit_launches = launches; O.bytes = own.bytes; O.ms = ms;
     *stats = O;
   }
   return 0;
@@ -2499,12 +2496,12 @@ extern "C" int gvt_hip_volume_occluder_grid_download(gvt_hip_volume *V, int ligh
   if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
   if (!V || !out) { set_error("volume_occluder_grid_download: null argument"); return GVT_HIP_ERR_INVALID; }
   if (!V->d_occ) { set_error("volume_occluder_grid_download: the volume holds no occluder grid"); return GVT_HIP_ERR_INVALID; }
-  if (light < 0 || light >= GVT_HIP_VOLUME_MAX_LIGHTS || !((V->og_usable >> light) & 1u)) {
+  if (light < 0 || light >= GVT_HIP_VOLUME_MAX_LIGHTS || !((V->og.usable >> light) & 1u)) {
     set_error("volume_occluder_grid_download: light %d was not usable at the bake and has no grid (its factor is 1)", light);
     return GVT_HIP_ERR_INVALID;
   }
   const size_t n_vert = (size_t)V->n[0] * V->n[1] * V->n[2];
-  const int plane = __builtin_popcount(V->og_usable & ((1u << light) - 1u));
+  const int plane = __builtin_popcount(V->og.usable & ((1u << light) - 1u));
   HIPCHK(hipStreamSynchronize(gctx().stream));
   HIPCHK(hipMemcpy(out, V->d_occ + n_vert * (size_t)plane, n_vert, hipMemcpyDeviceToHost));
   return 0;
@@ -2514,9 +2511,9 @@ extern "C" int gvt_hip_volume_occluder_grid_info(gvt_hip_volume *V, gvt_hip_volu
   if (!V || !out) { set_error("volume_occluder_grid_info: null argument"); return GVT_HIP_ERR_INVALID; }
   gvt_hip_volume_occluder_state I{};
   I.present = V->d_occ ? 1u : 0u;
-  I.current = (V->d_occ && V->og_current) ? 1u : 0u;
-  I.n_planes = V->d_occ ? V->og_planes : 0;
-  I.bytes = V->d_occ ? (uint64_t)V->n[0] * V->n[1] * V->n[2] * (uint64_t)V->og_planes : 0;
+  I.current = (V->d_occ && V->og.current) ? 1u : 0u;
+  I.n_planes = V->d_occ ? V->og.planes : 0;
+  I.bytes = V->d_occ ? (uint64_t)V->n[0] * V->n[1] * V->n[2] * (uint64_t)V->og.planes : 0;
   *out = I;
   return 0;
 }
@@ -2528,7 +2525,7 @@ extern "C" int gvt_hip_volume_occluder_grid_release(gvt_hip_volume *V) {
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a frame in flight reads the planes)
   hipFree(V->d_occ);
   V->d_occ = nullptr;
-  V->og_planes = 0; V->og_usable = 0; V->og_current = false; V->og_bake = 0;
+  grids_reset(V->og);
   return 0;
 }
 
@@ -2674,8 +2671,8 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   if (n == 0) {
     if (V->sub.empty()) return 0;
     HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the tables)
-    V->lg_current = false; // (a light grid never covers subgrids, and the ranges change)
-    V->og_current = false;
+    V->lg.current = false; // (a light grid never covers subgrids, and the ranges change)
+    V->og.current = false;
     amr_release(V);
     return amr_refresh_ranges(V);
   }
@@ -2715,8 +2712,8 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   if (!ok) return fail("the range kernel");
   hipFree(d_items); hipFree(d_out);
   // commit
-  V->lg_current = false;
-  V->og_current = false;
+  V->lg.current = false;
+  V->og.current = false;
   amr_release(V);
   V->d_amr_vox = d_vox; V->d_amr_mc = d_mc; V->d_amr_list = d_list; V->d_amr_desc = d_desc;
   V->sub.assign(grids, grids + n);

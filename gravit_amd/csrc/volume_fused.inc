@@ -8,8 +8,8 @@
 // What is uniform over the bricks of one grid (table, global origin, spacing, dt, value range, skip flag, minv) stays in the kernel's
 // VolDev argument, in scalar registers as in the plain march.  What differs per brick is a record of a device table indexed by instance
 // (the host fills it per call), loaded into vector registers when the lane enters the brick: four 16-byte loads per visit.  The macro
-// cells per axis are not in it: nbx and nby are (n - 1 + 7) / 8 of nx and ny, recomputed per sample (two shifts and adds against two
-// vector registers held through the march).
+// cells per axis are not in it: nbx and nby are (n - 1 + 7) / 8 of nx and ny, recomputed per sample (fused_macro_cell: two shifts and adds against
+// two vector registers held through the march).
 struct FusedBrick {
   const void *vox;     // the brick's samples
   const uint8_t *mc;   // its macro cells' skip bytes
@@ -45,6 +45,20 @@ __device__ __forceinline__ bool fused_clip(int id, const float *__restrict__ cli
     return t_clip < INFINITY;
   }
   return false;
+}
+
+// the macro cell of cell c in a brick of nx * ny * .. vertices: nby and nbx of THIS brick, (n - 1 + 7) / 8, recomputed (above).  Every
+// fused kernel and both light grid bakes index the skip bytes and the per-cell words through it
+__device__ __forceinline__ int fused_macro_cell(int nx, int ny, const int c[3]) {
+  return ((c[2] >> 3) * ((ny + 6) >> 3) + (c[1] >> 3)) * ((nx + 6) >> 3) + (c[0] >> 3);
+}
+
+// the end of a camera ray: its colour and opacity into its pixel (four atomic adds; a pixel id beyond the film deposits nothing)
+__device__ __forceinline__ void fused_deposit(float *__restrict__ fb, unsigned n_pix, int id, const float C[3], float A) {
+  if ((unsigned)id < n_pix) {
+    float *px = fb + (size_t)4 * (unsigned)id;
+    atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
+  }
 }
 
 template <typename T, bool CLIP>
@@ -106,10 +120,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused(VolDev U, cons
       } else {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -136,7 +147,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused(VolDev U, cons
         }
         k_last = k;
         n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         if (V.skip && !V.mc[bi]) { // an empty macro cell adds +0 per sample
           if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the ray arrived opaque: this sample adds +0 and ends it, as any sample does
           const int kj = vol_jump_target(V, o, d, k, k_hi, c);

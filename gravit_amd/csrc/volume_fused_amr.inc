@@ -85,10 +85,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_amr(VolDev U, 
       } else {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_amr(VolDev U, 
     n_visits += (unsigned)__popcll(ballot64(entered));
     n_deposits += (unsigned)__popcll(ballot64(deposited));
     // ---- the visit: volume_march_amr_body<false, false, CLIP>'s, step for step (KEEP IN STEP; `seen` there is k_last >= 0 here; nbx and
-    // nby are recomputed as in k_volume_march_fused), under the null-table rule above
+    // nby are recomputed: fused_macro_cell), under the null-table rule above
     if (active) {
       bool done = false;
       for (int s = 0; s < VOL_STEP; s++) {
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_amr(VolDev U, 
         }
         k_last = k;
         n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         uint2 word = make_uint2(0u, 0u);
         bool skip;
         if (Am.mc) { // empty by the union of every level's vertices in the macro cell: +0 per sample, whatever grid it is in
@@ -240,10 +237,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded_amr(Vol
       } else {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -258,7 +252,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded_amr(Vol
     n_visits += (unsigned)__popcll(ballot64(entered));
     n_deposits += (unsigned)__popcll(ballot64(deposited));
     // ---- the visit: volume_march_amr_body<SURF, LIT, CLIP>'s, step for step (KEEP IN STEP; `seen` there is k_last >= 0 here; nbx and nby
-    // are recomputed as in k_volume_march_fused_shaded), under the null-table rule above
+    // are recomputed: fused_macro_cell), under the null-table rule above
     if (active) {
       bool done = false;
       for (int s = 0; s < VOL_STEP; s++) {
@@ -274,7 +268,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shaded_amr(Vol
           if (k_last < 0 && k != k_carry) prev = -1;
         k_last = k;
         n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         uint2 word = make_uint2(0u, 0u);
         unsigned pl = 0u;
         bool skip;

@@ -7,7 +7,7 @@
 // KEEP IN STEP with k_volume_march_fused_shadow (and through it with k_volume_march_fused_shaded and volume_march_body): the kernel below
 // is that kernel restated, for the reason that one restates its parents -- the kernels that exist are to stay what they are, instruction
 // for instruction.  The differences: LIT is always on; the brick's grid pointer travels beside its record, in a parallel device table
-// loaded where the record is loaded (FusedBrick is unchanged); the camera ray's lit sample is vol_accumulate_lit_fog's.
+// loaded where the record is loaded (FusedBrick is unchanged); the camera ray's lit sample is vol_accumulate_lit_grids'.
 //   k_volume_march_fused_fog_lean<T, CLIP, CENTRAL>   the same change on k_volume_march_fused_shaded<T, CLIP, false, true, CENTRAL>, for a frame WITHOUT
 //                                   surfaces: no crossing exists, so no shadow ray is ever cast and the park, the modes and the side masks
 //                                   fall away with their registers and their LDS.  Measured before it existed (profiles/
@@ -23,32 +23,49 @@ struct FogBrick {
   const float *grid;
 };
 
-// vol_accumulate_lit<T, false> with the transmittance per light: ndl_s = ndl * Tg (an unusable light: Tg = 1, nothing read)
-template <typename T, bool CENTRAL, typename LT> // (LT: SurfDev or LightDev; CENTRAL: the gradient is vol_gradient_central's, from Hg)
-__device__ __forceinline__ unsigned vol_accumulate_lit_fog(const VolDev &V, const LT &L, const GhostTable<CENTRAL> &Hg, unsigned usable, const float *__restrict__ grid, const int c[3], float v,
-                                                           const VolCorners &G, const float f[3], float C[3], float &A) {
+// Og of the l-th usable light at cell c, fractions f: (float)O at the eight vertices of the occluder grid's plane (uint8, laid out as
+// the light grid's), in the nesting of Tg below
+__device__ __forceinline__ float occluder_lerp(const VolDev &V, const uint8_t *__restrict__ occ, int l, const int c[3], const float f[3]) {
+  const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny, plane = sz * (size_t)V.nz;
+  const uint8_t *p = occ + plane * (size_t)l + ((size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2]);
+  const float c00 = lerp_((float)p[0], (float)p[1], f[0]), c10 = lerp_((float)p[sy], (float)p[sy + 1], f[0]);
+  const float c01 = lerp_((float)p[sz], (float)p[sz + 1], f[0]), c11 = lerp_((float)p[sz + sy], (float)p[sz + sy + 1], f[0]);
+  return lerp_(lerp_(c00, c10, f[1]), lerp_(c01, c11, f[1]), f[2]);
+}
+
+// vol_accumulate_lit<T, false> with a factor per light from the bricks' planes: ndl_s = ndl * Tg, with MESH (the mesh-shadowed frames)
+// ndl * (Tg * Og) (an unusable light: 1, nothing read).  The planes are read at cell c of brick V with the fractions f0; the gradient
+// is taken from the corners G and fractions f at the spacing of Vf.  Outside an AMR visit Vf is V and f0 is f; in one
+// (volume_fused_shadow_amr.inc) G, f and Vf are the final cell's, c and f0 the level-0 cell's
+template <typename T, bool CENTRAL, bool MESH, typename LT> // (LT: SurfDev or LightDev; CENTRAL: the gradient is vol_gradient_central's, from Hg)
+__device__ __forceinline__ unsigned vol_accumulate_lit_grids(const VolDev &Vf, const VolDev &V, const LT &L, const GhostTable<CENTRAL> &Hg, unsigned usable,
+                                                             const float *__restrict__ grid, const uint8_t *__restrict__ occ, const int c[3], const float f0[3], float v,
+                                                             const VolCorners &G, const float f[3], float C[3], float &A) {
   const float4 tc = vol_lookup(V, v);
   float rgb[3] = { tc.x, tc.y, tc.z };
   const bool shaded = tc.w > 0.f; // (false for NaN)
   if (shaded) {
     float g[3], sum[3] = { 0.f, 0.f, 0.f };
     if constexpr (CENTRAL) vol_gradient_central<T>(V, Hg, c, G, f, g);
-    else vol_gradient(V, G, f, g);
+    else vol_gradient(Vf, G, f, g);
     const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
     if (len > 0.f && len < INFINITY) { // (false for NaN)
       const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
       const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny, plane = sz * (size_t)V.nz;
       const float *p = grid + ((size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2]);
+      int l = 0;
       for (int j = 0; j < L.n_lights; j++) {
         const float ndl = fabsf((n[0] * L.ldir[j][0] + n[1] * L.ldir[j][1]) + n[2] * L.ldir[j][2]);
-        float Tg = 1.f;
+        float Ts = 1.f;
         if ((usable >> j) & 1u) { // (wave-uniform)
-          const float c00 = lerp_(p[0], p[1], f[0]), c10 = lerp_(p[sy], p[sy + 1], f[0]);
-          const float c01 = lerp_(p[sz], p[sz + 1], f[0]), c11 = lerp_(p[sz + sy], p[sz + sy + 1], f[0]);
-          Tg = lerp_(lerp_(c00, c10, f[1]), lerp_(c01, c11, f[1]), f[2]);
+          const float c00 = lerp_(p[0], p[1], f0[0]), c10 = lerp_(p[sy], p[sy + 1], f0[0]);
+          const float c01 = lerp_(p[sz], p[sz + 1], f0[0]), c11 = lerp_(p[sz + sy], p[sz + sy + 1], f0[0]);
+          Ts = lerp_(lerp_(c00, c10, f0[1]), lerp_(c01, c11, f0[1]), f0[2]);
+          if constexpr (MESH) Ts = Ts * occluder_lerp(V, occ, l, c, f0);
           p += plane;
+          l++;
         }
-        const float ndl_s = ndl * Tg;
+        const float ndl_s = ndl * Ts;
         for (int a = 0; a < 3; a++) sum[a] = sum[a] + L.lcol[j][a] * ndl_s;
       }
     }
@@ -184,10 +201,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
       } else if (mode <= 0) {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -220,7 +234,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
         if (k_last < 0 && k != k_carry) prev = -1;
         k_last = k;
         if (mode > 0) s_marched++; else n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         float p[3];
         vol_point(V, o, d, k, p);
         const unsigned pl = surf_plane_sides(S, p);
@@ -322,7 +336,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
           if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the surface ends the ray: the sample itself adds nothing
         }
         if (mode > 0) vol_accumulate(V, v, C, A); // (shading NONE; the colour is dead)
-        else n_shaded += vol_accumulate_lit_fog<T, CENTRAL>(V, S, Hl, H.usable, grid, c, v, G, f, C, A);
+        else n_shaded += vol_accumulate_lit_grids<T, CENTRAL, false>(V, V, S, Hl, H.usable, grid, nullptr, c, f, v, G, f, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }
@@ -366,7 +380,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog(VolDev U, 
 }
 
 // KEEP IN STEP with k_volume_march_fused_shaded<T, CLIP, false, true>: that kernel restated, with the brick's planes loaded beside its
-// record and vol_accumulate_lit_fog in vol_accumulate_lit's place
+// record and vol_accumulate_lit_grids in vol_accumulate_lit's place
 template <typename T, bool CLIP, bool CENTRAL>
 __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDev U, LightDev S, unsigned usable, const FusedBrick *__restrict__ bricks,
                                                                            const FogBrick *__restrict__ grids, TopDev top, RayPlanes q, unsigned n, Mat4 minv,
@@ -431,10 +445,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDe
       } else {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -463,7 +474,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDe
         }
         k_last = k;
         n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         if (V.skip && !V.mc[bi]) { // an empty macro cell adds +0 per sample
           if (A >= GVT_HIP_VOLUME_OPAQUE_A) { k++; done = true; break; } // the ray arrived opaque: this sample adds +0 and ends it, as any sample does
           const int kj = vol_jump_target(V, o, d, k, k_hi, c);
@@ -478,7 +489,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_fog_lean(VolDe
         n_gathered++;
         VolCorners G;
         const float v = vol_gather<T>(V, c, f, G);
-        n_shaded += vol_accumulate_lit_fog<T, CENTRAL>(V, S, Hl, usable, grid, c, v, G, f, C, A);
+        n_shaded += vol_accumulate_lit_grids<T, CENTRAL, false>(V, V, S, Hl, usable, grid, nullptr, c, f, v, G, f, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }

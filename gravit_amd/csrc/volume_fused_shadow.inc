@@ -177,10 +177,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
       } else if (mode <= 0) {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -212,7 +209,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_shadow(VolDev 
         if (k_last < 0 && k != k_carry) prev = -1;
         k_last = k;
         if (mode > 0) s_marched++; else n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         float p[3];
         vol_point(V, o, d, k, p);
         const unsigned pl = surf_plane_sides(S, p);

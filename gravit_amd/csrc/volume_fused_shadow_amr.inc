@@ -34,47 +34,6 @@
 //
 // Termination: k_volume_march_fused_shadow's argument; the descent is bounded by the levels of a brick and adds no state to a ray.
 
-// vol_accumulate_lit_fog / _mesh (MESH) for a sample of an AMR visit: the gradient from the final cell's corners G and fractions f at the
-// fine spacing Vf; Tg (and Og) from the planes at the level-0 cell c of brick V with the level-0 fractions f0
-template <bool MESH, typename LT> // (LT: SurfDev or LightDev)
-__device__ __forceinline__ unsigned vol_accumulate_lit_grids_amr(const VolDev &Vf, const VolDev &V, const LT &L, unsigned usable, const float *__restrict__ grid,
-                                                                 const uint8_t *__restrict__ occ, const int c[3], const float f0[3], float v, const VolCorners &G,
-                                                                 const float f[3], float C[3], float &A) {
-  const float4 tc = vol_lookup(V, v);
-  float rgb[3] = { tc.x, tc.y, tc.z };
-  const bool shaded = tc.w > 0.f; // (false for NaN)
-  if (shaded) {
-    float g[3], sum[3] = { 0.f, 0.f, 0.f };
-    vol_gradient(Vf, G, f, g);
-    const float len = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
-    if (len > 0.f && len < INFINITY) { // (false for NaN)
-      const float n[3] = { g[0] / len, g[1] / len, g[2] / len };
-      const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * (size_t)V.ny, plane = sz * (size_t)V.nz;
-      const float *p = grid + ((size_t)c[0] + sy * (size_t)c[1] + sz * (size_t)c[2]);
-      int l = 0;
-      for (int j = 0; j < L.n_lights; j++) {
-        const float ndl = fabsf((n[0] * L.ldir[j][0] + n[1] * L.ldir[j][1]) + n[2] * L.ldir[j][2]);
-        float Ts = 1.f;
-        if ((usable >> j) & 1u) { // (wave-uniform)
-          const float c00 = lerp_(p[0], p[1], f0[0]), c10 = lerp_(p[sy], p[sy + 1], f0[0]);
-          const float c01 = lerp_(p[sz], p[sz + 1], f0[0]), c11 = lerp_(p[sz + sy], p[sz + sy + 1], f0[0]);
-          Ts = lerp_(lerp_(c00, c10, f0[1]), lerp_(c01, c11, f0[1]), f0[2]);
-          if constexpr (MESH) Ts = Ts * occluder_lerp(V, occ, l, c, f0);
-          p += plane;
-          l++;
-        }
-        const float ndl_s = ndl * Ts;
-        for (int a = 0; a < 3; a++) sum[a] = sum[a] + L.lcol[j][a] * ndl_s;
-      }
-    }
-    for (int a = 0; a < 3; a++) rgb[a] = rgb[a] * (L.ka + L.kd * sum[a]);
-  }
-  const float fr = (1.f - A) * tc.w;
-  C[0] = C[0] + fr * rgb[0]; C[1] = C[1] + fr * rgb[1]; C[2] = C[2] + fr * rgb[2];
-  A = A + fr;
-  return shaded ? 1u : 0u;
-}
-
 template <bool CLIP, bool LIT, int GRIDS>
 __device__ __forceinline__ void volume_shadow_amr_body(const VolDev &U, const SurfDev &S, const ShadowDev &H, const FusedBrick *__restrict__ bricks,
                                                        const AmrDev *__restrict__ amr, const MeshBrick *__restrict__ grids, const TopDev &top, RayPlanes q, unsigned n,
@@ -200,10 +159,7 @@ __device__ __forceinline__ void volume_shadow_amr_body(const VolDev &U, const Su
       } else if (mode <= 0) {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -237,7 +193,7 @@ __device__ __forceinline__ void volume_shadow_amr_body(const VolDev &U, const Su
         if (k_last < 0 && k != k_carry) prev = -1;
         k_last = k;
         if (mode > 0) s_marched++; else n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         float p[3];
         vol_point(V, o, d, k, p);
         const unsigned pl = surf_plane_sides(S, p);
@@ -329,7 +285,7 @@ __device__ __forceinline__ void volume_shadow_amr_body(const VolDev &U, const Su
         }
         if constexpr (LIT) {
           if (mode > 0) vol_accumulate(V, v, C, A); // (shading NONE; the colour is dead)
-          else if constexpr (GRIDS != 0) n_shaded += vol_accumulate_lit_grids_amr<GRIDS == 2>(amr_fine_spacing(V, log2_r), V, S, H.usable, grid.grid, grid.occ, c, f0, v, G, f, C, A);
+          else if constexpr (GRIDS != 0) n_shaded += vol_accumulate_lit_grids<float, false, GRIDS == 2>(amr_fine_spacing(V, log2_r), V, S, NoGhost{}, H.usable, grid.grid, grid.occ, c, f0, v, G, f, C, A);
           else n_shaded += vol_accumulate_lit<float, false>(amr_fine_spacing(V, log2_r), S, NoGhost{}, c, v, G, f, C, A);
         } else {
           vol_accumulate(V, v, C, A);
@@ -403,7 +359,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_march_fused_mesh_amr(VolDe
 
 // KEEP IN STEP with k_volume_march_fused_shaded_amr<CLIP, false, true> (the visit, the null-table rule: the skip bit of a brick with
 // subgrids is bit 31 of its AMR cell word, of a brick without its skip byte) and with k_volume_march_fused_fog_lean / _mesh_lean (the
-// planes loaded beside the record): that kernel restated, with vol_accumulate_lit_grids_amr in vol_accumulate_lit's place
+// planes loaded beside the record): that kernel restated, with vol_accumulate_lit_grids (volume_fused_fog.inc) in vol_accumulate_lit's place
 template <bool CLIP, bool MESH>
 __device__ __forceinline__ void volume_lean_amr_body(const VolDev &U, const LightDev &S, unsigned usable, const FusedBrick *__restrict__ bricks, const AmrDev *__restrict__ amr,
                                                      const MeshBrick *__restrict__ grids, const TopDev &top, RayPlanes q, unsigned n, const Mat4 &minv,
@@ -468,10 +424,7 @@ __device__ __forceinline__ void volume_lean_amr_body(const VolDev &U, const Ligh
       } else {
         if (brick >= 0) { // OPAQUE, or EXTERNAL: the ray leaves the volume (a camera ray that meets no brick deposits nothing)
           deposited = true;
-          if ((unsigned)id < n_pix) {
-            float *px = fb + (size_t)4 * (unsigned)id;
-            atomicAdd(px + 0, C[0]); atomicAdd(px + 1, C[1]); atomicAdd(px + 2, C[2]); atomicAdd(px + 3, A);
-          }
+          fused_deposit(fb, n_pix, id, C, A);
         }
         active = false;
         // (the lane's march state is dead now; saying so frees its registers for this block's temporaries)
@@ -500,7 +453,7 @@ __device__ __forceinline__ void volume_lean_amr_body(const VolDev &U, const Ligh
         }
         k_last = k;
         n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         uint2 word = make_uint2(0u, 0u);
         bool skip;
         if (Am.mc) { // empty by the union of every level's vertices in the macro cell: +0 per sample, whatever grid it is in
@@ -529,7 +482,7 @@ __device__ __forceinline__ void volume_lean_amr_body(const VolDev &U, const Ligh
         const float v = amr_gather(gp, sy, sz, f);
         VolCorners G;
         amr_corners(gp, sy, sz, G);
-        n_shaded += vol_accumulate_lit_grids_amr<MESH>(amr_fine_spacing(V, log2_r), V, S, usable, grid.grid, grid.occ, c, f0, v, G, f, C, A);
+        n_shaded += vol_accumulate_lit_grids<float, false, MESH>(amr_fine_spacing(V, log2_r), V, S, NoGhost{}, usable, grid.grid, grid.occ, c, f0, v, G, f, C, A);
         k++;
         if (A >= GVT_HIP_VOLUME_OPAQUE_A) { done = true; break; }
       }
@@ -660,7 +613,7 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_bake_light_amr(VolDev U, S
         }
         seen = true;
         n_marched++;
-        const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
+        const int bi = fused_macro_cell(V.nx, V.ny, c);
         float p[3];
         vol_point(V, o, d, k, p);
         const unsigned pl = surf_plane_sides(S, p);

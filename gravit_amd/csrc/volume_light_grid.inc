@@ -101,6 +101,8 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_volume_bake_light(VolDev U, SurfD
         }
         seen = true;
         n_marched++;
+        // (fused_macro_cell's expression, restated: through the function, by value or by reference, this kernel comes out two VGPRs
+        // larger -- profiles/volume_hoist.txt)
         const int bi = ((c[2] >> 3) * ((V.ny + 6) >> 3) + (c[1] >> 3)) * ((V.nx + 6) >> 3) + (c[0] >> 3); // (nby, nbx of this brick)
         float p[3];
         vol_point(V, o, d, k, p);
