@@ -453,6 +453,23 @@ class TransferFunction:
         return cls(cls.read_map(cmap_path, 4), cls.read_map(omap_path, 2), value_range)
 
 
+def subgrid_tree(subgrids):
+    """The tree of a list of scenes.Subgrid without its data: (parent, ratio, lo, cells) per entry, plain ints.  Needs no device."""
+    return [(int(s.parent), int(s.ratio), tuple(int(v) for v in s.lo), tuple(int(v) for v in s.cells)) for s in (subgrids or [])]
+
+
+def same_subgrid_tree(tree, subgrids, what="subgrids"):
+    """ValueError unless `subgrids` (scenes.Subgrid) have the tree `tree` (subgrid_tree's form): the same count and per entry the same
+    parent, ratio, lo and cells -- what gvt_hip_volume_update_amr takes for granted.  Needs no device."""
+    other = subgrid_tree(subgrids)
+    if len(other) != len(tree):
+        raise ValueError("%s: %d subgrids given, the brick has %d (another tree is set_subgrids)" % (what, len(other), len(tree)))
+    for i, (a, b) in enumerate(zip(tree, other)):
+        for name, x, y in zip(("parent", "ratio", "lo", "cells"), a, b):
+            if x != y:
+                raise ValueError("%s: entry %d has %s %s, the brick's has %s (another tree is set_subgrids)" % (what, i, name, y, x))
+
+
 class HipVolumeAdapter:
     """A volume brick on the device (gvt_hip_volume): the counterpart of the reference's volume adapters (OSPRayAdapter, PVolAdapter).
     `brick` is a scenes.Brick (or a scenes.VolumeData: the whole grid as one brick); its data may also be a torch tensor on the GPU.
@@ -472,6 +489,7 @@ class HipVolumeAdapter:
     def __init__(self, brick, sampling_rate=1.0, skip=True, native=False, amr_shaded=False):
         self.lib = capi.load()
         self.amr_shaded = bool(amr_shaded)
+        self.tree = []  # subgrid_tree of the current set (set_subgrids)
         if hasattr(brick, "global_counts"):
             counts, offset, gcounts = brick.counts, brick.offset, brick.global_counts
         else:
@@ -544,6 +562,74 @@ class HipVolumeAdapter:
         if self.amr_shaded if shaded is None else shaded:
             flags |= capi.VOLUME_AMR_SHADED
         capi.check(self.lib.gvt_hip_volume_set_subgrids(self.h, C.cast(pods, C.c_void_p), C.cast(ptrs, C.c_void_p), n, flags), "gvt_hip_volume_set_subgrids")
+        self.tree = subgrid_tree(subgrids)  # what update_amr and VolumeTracer.update(amr=True) compare a new step's subgrids with
+
+    def update_amr(self, data=None, subgrids=None):
+        """gvt_hip_volume_update_amr: the next time step of an AMR brick on the same subgrid tree, in place (every pointer a tracer borrowed
+        stays valid; transfer function, surfaces, lights and the occluder grid are kept, the light grid goes stale).  data: the level-0
+        samples, shape (nz, ny, nx), or None to keep them.  subgrids: None to keep them all, or a list as long as the brick's set whose
+        entries are scenes.Subgrid (its tree fields must be the stored ones), an array of that subgrid's shape, or None to keep that
+        subgrid.  Everything given is a numpy array, or everything a contiguous float32 torch tensor on the GPU (no host round trip).
+        ValueError for a shape or tree that is not the stored one, before anything changes.  Returns the device time of the update in ms."""
+        tree = getattr(self, "tree", [])
+        if not tree:
+            raise ValueError("update_amr: the brick has no subgrids (update_samples is its call)")
+        given = []  # (what, array) of everything that is not None, level 0 first
+        if data is not None:
+            shape = tuple(int(c) for c in self.counts[::-1])
+            if tuple(data.shape) != shape:
+                raise ValueError("update_amr: data of shape %s, the brick has %s" % (tuple(data.shape), shape))
+            given.append(("data", data))
+        entries = [None] * len(tree)
+        if subgrids is not None:
+            subgrids = list(subgrids)
+            if len(subgrids) != len(tree):
+                raise ValueError("update_amr: %d subgrids given, the brick has %d (another tree is set_subgrids)" % (len(subgrids), len(tree)))
+            for i, s in enumerate(subgrids):
+                if s is None:
+                    continue
+                if hasattr(s, "ratio"):  # a scenes.Subgrid: its tree fields must be the stored ones
+                    same_subgrid_tree([tree[i]], [s], "update_amr: subgrid %d" % i)
+                    s = s.data
+                parent, ratio, lo, cells = tree[i]
+                shape = tuple(c * ratio + 1 for c in cells[::-1])
+                if tuple(s.shape) != shape:
+                    raise ValueError("update_amr: subgrid %d has data of shape %s, its cells and ratio need %s" % (i, tuple(s.shape), shape))
+                entries[i] = s
+                given.append(("subgrid %d" % i, s))
+        if not given:
+            raise ValueError("update_amr: nothing given (neither data nor a subgrid)")
+        device = [hasattr(a, "data_ptr") and a.is_cuda for _, a in given]
+        if any(device) and not all(device):
+            raise ValueError("update_amr: the arrays must be all host arrays or all GPU tensors")
+        keep = []
+
+        def pointer(what, a):
+            if hasattr(a, "data_ptr") and a.is_cuda:
+                import torch
+
+                if not a.is_contiguous() or self.dtype_of(a) != "float32":
+                    raise ValueError("update_amr: %s: a device tensor must be contiguous float32" % what)
+                torch.cuda.current_stream(a.device).synchronize()  # (written on torch's stream, copied on the library's)
+                keep.append(a)
+                return a.data_ptr()
+            keep.append(np.ascontiguousarray(a.numpy() if hasattr(a, "data_ptr") else a, np.float32))
+            return keep[-1].ctypes.data
+
+        src = C.c_void_p(pointer("data", data)) if data is not None else None
+        ptrs = None
+        if subgrids is not None:
+            ptrs = (C.c_void_p * len(tree))()
+            for i, s in enumerate(entries):
+                if s is not None:
+                    ptrs[i] = pointer("subgrid %d" % i, s)
+        ms = C.c_float(0.0)
+        capi.check(self.lib.gvt_hip_volume_update_amr(self.h, src, C.c_size_t(int(np.prod(self.counts)) if data is not None else 0),
+                                                      None if ptrs is None else C.cast(ptrs, C.c_void_p), len(tree) if ptrs is not None else 0,
+                                                      C.c_uint32(1 if all(device) else 0), C.byref(ms)), "gvt_hip_volume_update_amr")
+        if data is not None:
+            self._data = keep[0]
+        return float(ms.value)
 
     GRADIENT_KINDS = {"cell": capi.VOLUME_GRADIENT_CELL, "central": capi.VOLUME_GRADIENT_CENTRAL}
 

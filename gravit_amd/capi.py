@@ -39,7 +39,7 @@ SYMBOLS = [
     "gvt_hip_volume_create_typed", "gvt_hip_volume_update_samples_typed", "gvt_hip_volume_get_voxel_type",
     "gvt_hip_depth_create", "gvt_hip_depth_destroy", "gvt_hip_depth_clear", "gvt_hip_depth_upload", "gvt_hip_depth_download", "gvt_hip_depth_render",
     "gvt_hip_volume_frame_clipped", "gvt_hip_fb_composite_over",
-    "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info",
+    "gvt_hip_volume_set_subgrids", "gvt_hip_volume_get_amr_info", "gvt_hip_volume_update_amr",
     "gvt_hip_volume_march_queue", "gvt_hip_volume_camera_filter", "gvt_hip_queues_export_wire", "gvt_hip_queues_append_wire",
     "gvt_hip_volume_set_ghosts", "gvt_hip_volume_set_gradient", "gvt_hip_volume_get_gradient",
     "gvt_hip_volume_frame_fused", "gvt_hip_volume_frame_fused_shaded", "gvt_hip_volume_frame_fused_amr",
@@ -263,6 +263,7 @@ def load():
         lib.gvt_hip_volume_get_voxel_type.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_set_subgrids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         lib.gvt_hip_volume_get_amr_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_update_amr.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
         lib.gvt_hip_volume_set_ghosts.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32]
         lib.gvt_hip_volume_set_gradient.argtypes = [C.c_void_p, C.c_int]
         lib.gvt_hip_volume_get_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

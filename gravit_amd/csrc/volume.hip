@@ -13,6 +13,7 @@
 //   k_vol_classify / k_vol_scatter          AbstractTrace::shuffleRays, volume branch, PRIMARY rays (algorithm/TracerBase.h:344-391), around
 //                                           the mesh shuffle's k_dest_scan (ordered_scan.inc)
 //   k_volume_march_amr / k_amr_ranges       AMR volumes (Volume::AddAMRGrid): nested refined subgrids inside a brick, volume_amr.inc
+//   k_amr_ranges_merge                      ... and their time steps in place (gvt_hip_volume_update_amr)
 //   k_volume_march_amr_surf / _lit / _surf_lit   ... with isovalues, slice planes and lit fog in the refined cells (GVT_HIP_VOLUME_AMR_SHADED)
 //   gvt_hip_volume_frame [_clipped]         Tracer<ImageScheduler>::operator() (algorithm/ImageTracer.h:127-269) over bricks; clipped: every camera
 //                                           ray ends at its pixel of a depth plane (depth.hip) -- geometry inside the volume
@@ -59,6 +60,11 @@ struct BakedGrids {
   float m[16] = {}, minv[16] = {};
 };
 
+namespace {
+struct AmrRangeItem;
+struct AmrMergeCell;
+} // namespace
+
 struct gvt_hip_volume {
   int n[3] = { 0, 0, 0 }, off[3] = { 0, 0, 0 };
   float go[3] = { 0, 0, 0 }, sp[3] = { 1, 1, 1 };
@@ -98,8 +104,13 @@ struct gvt_hip_volume {
   int *d_amr_list = nullptr;
   int4 *d_amr_desc = nullptr;
   std::vector<uint32_t> amr_first, amr_count; // per macro cell: its level-1 subgrids in d_amr_list (d_amr_mc without the skip bit)
-  std::vector<float> amr_min, amr_max;        // per macro cell: the subgrids' part of its value range (bmin / bmax / bnan hold the union)
-  std::vector<uint8_t> amr_nan;
+  // gvt_hip_volume_update_amr's tables (volume_amr.inc, k_amr_ranges_merge), built at the first update of a tree and freed with it: the
+  // range items grouped by macro cell, one AmrMergeCell per macro cell that has some; and every subgrid's place in d_amr_vox
+  AmrRangeItem *d_amr_items = nullptr;
+  AmrMergeCell *d_amr_cells = nullptr;
+  unsigned amr_n_cells = 0;
+  uint64_t amr_merge_bytes = 0;
+  std::vector<size_t> amr_offset, amr_samples;
   // smooth gradients (gvt_hip_volume_set_ghosts / _set_gradient): with GVT_HIP_VOLUME_GRADIENT_CENTRAL the shaded marches are the _central
   // entry points, which read the six face layers beyond the brick from d_ghost (one allocation: -x +x -y +y -z +z, a slab of a missing
   // face is never read)
@@ -883,7 +894,7 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
   }
 }
 
-#include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges
+#include "volume_amr.inc" // k_volume_march_amr, k_amr_ranges, k_amr_ranges_merge
 #include "volume_fused.inc" // k_volume_march_fused
 #include "volume_fused_shaded.inc" // k_volume_march_fused_shaded
 #include "volume_fused_amr.inc" // k_volume_march_fused_amr, k_volume_march_fused_shaded_amr
@@ -985,8 +996,9 @@ int upload_cells(gvt_hip_volume *V) {
 }
 
 // bmin / bmax / bnan and vmin / vmax from d_vox (stream-ordered behind whatever wrote it), then one host wait and the download: 9 bytes
-// per macro cell.  The grid itself never comes back to the host
-int volume_ranges(gvt_hip_volume *V) {
+// per macro cell.  The grid itself never comes back to the host.  amr_merge (gvt_hip_volume_update_amr; the volume's merge tables exist):
+// the subgrids' vertices are merged into the macro cells' ranges between the two kernels, so what comes down is the union
+int volume_ranges(gvt_hip_volume *V, bool amr_merge = false) {
   Ctx &C = gctx();
   const size_t nbk = (size_t)V->nb[0] * V->nb[1] * V->nb[2];
   char *d = (char *)scratch_get(SCR_VOL_RANGES, 9 * nbk + 2 * sizeof(float));
@@ -1006,6 +1018,8 @@ int volume_ranges(gvt_hip_volume *V) {
       else
         k_vol_ranges<T, false><<<blocks, VOL_BLOCK, 0, C.stream>>>(vox, (unsigned)V->n[0], (unsigned)V->n[1], (unsigned)V->n[2], (unsigned)V->nb[0], (unsigned)V->nb[1], runs, n_work, d_min, d_max, d_nan);
     });
+    if (amr_merge && V->amr_n_cells)
+      k_amr_ranges_merge<<<std::min(V->amr_n_cells, 1u << 20), VOL_BLOCK, 0, C.stream>>>(V->d_amr_vox, V->d_amr_items, V->d_amr_cells, V->amr_n_cells, d_min, d_max, d_nan);
     k_vol_range_total<<<1, VR_TOTAL_BLOCK, 0, C.stream>>>(d_min, d_max, nbk, d_tot);
   }
   HIPCHK(hipGetLastError());
@@ -1030,7 +1044,7 @@ int amr_upload_words(gvt_hip_volume *V) {
   return 0;
 }
 
-// the tables that depend on the samples AND the transfer function (gvt_hip_volume_set_transfer, gvt_hip_volume_update_samples): d_mc,
+// the tables that depend on the samples AND the transfer function (gvt_hip_volume_set_transfer, gvt_hip_volume_update_samples, _update_amr): d_mc,
 // n_empty and, through upload_cells, d_cells.  The one statement of the rule: a block may be skipped when every table entry its values
 // can reach -- one entry of margin either side for the rounding of the interpolation -- has a == 0: its samples then add exactly +0
 int rebuild_tables(gvt_hip_volume *V) {
@@ -1286,7 +1300,7 @@ extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
   hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost); hipFree(V->d_lgrid); hipFree(V->d_occ);
-  hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
+  hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc); hipFree(V->d_amr_items); hipFree(V->d_amr_cells);
   delete V;
 }
 
@@ -2631,20 +2645,30 @@ bool amr_plan(const gvt_hip_volume *V, const gvt_hip_subgrid *g, int n, AmrPlan 
 void amr_release(gvt_hip_volume *V) {
   hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc);
   V->d_amr_vox = nullptr; V->d_amr_mc = nullptr; V->d_amr_list = nullptr; V->d_amr_desc = nullptr;
-  V->sub.clear(); V->amr_first.clear(); V->amr_count.clear(); V->amr_min.clear(); V->amr_max.clear(); V->amr_nan.clear();
+  hipFree(V->d_amr_items); hipFree(V->d_amr_cells); // (the merge tables of gvt_hip_volume_update_amr belong to the tree)
+  V->d_amr_items = nullptr; V->d_amr_cells = nullptr; V->amr_n_cells = 0; V->amr_merge_bytes = 0;
+  V->amr_offset.clear(); V->amr_samples.clear();
+  V->sub.clear(); V->amr_first.clear(); V->amr_count.clear();
   V->amr_levels = 1; V->amr_bytes = 0; V->amr_flags = 0;
 }
 
+// the subgrids' part of the macro cells' value ranges, as gvt_hip_volume_set_subgrids has just reduced it (empty: no subgrids).  The volume
+// keeps no copy: bmin / bmax / bnan hold the union, and gvt_hip_volume_update_amr forms the next step's union on the device
+struct AmrHostRanges {
+  std::vector<float> mn, mx;
+  std::vector<uint8_t> wild;
+};
+
 // bmin / bmax / bnan, vmin / vmax: the level-0 ranges afresh from d_vox, then the subgrids' part merged in; the tables from the union
-int amr_refresh_ranges(gvt_hip_volume *V) {
+int amr_refresh_ranges(gvt_hip_volume *V, const AmrHostRanges &R) {
   int rc = volume_ranges(V);
   if (rc) return rc;
-  for (size_t b = 0; b < V->amr_min.size(); b++) {
-    if (V->amr_min[b] < V->bmin[b]) V->bmin[b] = V->amr_min[b];
-    if (V->amr_max[b] > V->bmax[b]) V->bmax[b] = V->amr_max[b];
-    V->bnan[b] |= V->amr_nan[b];
-    if (V->amr_min[b] < V->vmin) V->vmin = V->amr_min[b];
-    if (V->amr_max[b] > V->vmax) V->vmax = V->amr_max[b];
+  for (size_t b = 0; b < R.mn.size(); b++) {
+    if (R.mn[b] < V->bmin[b]) V->bmin[b] = R.mn[b];
+    if (R.mx[b] > V->bmax[b]) V->bmax[b] = R.mx[b];
+    V->bnan[b] |= R.wild[b];
+    if (R.mn[b] < V->vmin) V->vmin = R.mn[b];
+    if (R.mx[b] > V->vmax) V->vmax = R.mx[b];
   }
   return V->has_tf ? rebuild_tables(V) : 0;
 }
@@ -2674,7 +2698,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
     V->lg.current = false; // (a light grid never covers subgrids, and the ranges change)
     V->og.current = false;
     amr_release(V);
-    return amr_refresh_ranges(V);
+    return amr_refresh_ranges(V, AmrHostRanges{});
   }
   AmrPlan P;
   if (!amr_plan(V, grids, n, P)) return GVT_HIP_ERR_INVALID;
@@ -2721,16 +2745,98 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   V->amr_flags = flags & GVT_HIP_VOLUME_AMR_SHADED;
   V->amr_bytes = sizeof(float) * P.total + sizeof(uint2) * nbk + sizeof(int) * P.list.size() + sizeof(int4) * P.desc.size();
   V->amr_first.swap(P.first); V->amr_count.swap(P.cnt);
-  V->amr_min.assign(nbk, INFINITY); V->amr_max.assign(nbk, -INFINITY); V->amr_nan.assign(nbk, 0);
+  AmrHostRanges R;
+  R.mn.assign(nbk, INFINITY); R.mx.assign(nbk, -INFINITY); R.wild.assign(nbk, 0);
   for (size_t i = 0; i < n_items; i++) {
     const size_t b = P.item_cell[i];
-    if (out[i].mn < V->amr_min[b]) V->amr_min[b] = out[i].mn;
-    if (out[i].mx > V->amr_max[b]) V->amr_max[b] = out[i].mx;
-    V->amr_nan[b] |= (uint8_t)out[i].wild;
+    if (out[i].mn < R.mn[b]) R.mn[b] = out[i].mn;
+    if (out[i].mx > R.mx[b]) R.mx[b] = out[i].mx;
+    R.wild[b] |= (uint8_t)out[i].wild;
   }
   int rc = amr_upload_words(V); // (before a transfer function: no skip bit yet; rebuild_tables uploads them again)
   if (rc) return rc;
-  return amr_refresh_ranges(V);
+  return amr_refresh_ranges(V, R);
+}
+
+// ---- time-varying AMR volumes (the contract: include/gvt_hip.h, "time-varying AMR volumes")
+namespace {
+
+// k_amr_ranges_merge's tables, once per tree: amr_plan's range items of the stored subgrids in the order of their macro cells, one
+// AmrMergeCell per macro cell that has items, and every subgrid's place in d_amr_vox.  Nothing of the volume changes on failure
+int amr_merge_tables(gvt_hip_volume *V) {
+  if (V->d_amr_items) return 0;
+  AmrPlan P;
+  if (!amr_plan(V, V->sub.data(), (int)V->sub.size(), P)) return GVT_HIP_ERR_INVALID; // (not reached: _set_subgrids accepted this tree)
+  const size_t nbk = P.first.size(), n_items = P.items.size();
+  std::vector<unsigned> start(nbk + 1, 0u);
+  for (size_t i = 0; i < n_items; i++) start[P.item_cell[i] + 1]++;
+  for (size_t b = 0; b < nbk; b++) start[b + 1] += start[b];
+  std::vector<AmrMergeCell> cells;
+  for (size_t b = 0; b < nbk; b++)
+    if (start[b + 1] > start[b]) cells.push_back(AmrMergeCell{ (unsigned)b, start[b], start[b + 1] - start[b] });
+  std::vector<AmrRangeItem> items(n_items);
+  std::vector<unsigned> at(start.begin(), start.end() - 1);
+  for (size_t i = 0; i < n_items; i++) items[at[P.item_cell[i]]++] = P.items[i];
+  AmrRangeItem *d_items = nullptr;
+  AmrMergeCell *d_cells = nullptr;
+  const bool ok = hipMalloc((void **)&d_items, sizeof(AmrRangeItem) * n_items) == hipSuccess && hipMalloc((void **)&d_cells, sizeof(AmrMergeCell) * cells.size()) == hipSuccess &&
+                  hipMemcpy(d_items, items.data(), sizeof(AmrRangeItem) * n_items, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d_cells, cells.data(), sizeof(AmrMergeCell) * cells.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    set_error("volume_update_amr: the merge tables: %s", hipGetErrorString(hipGetLastError()));
+    hipFree(d_items); hipFree(d_cells);
+    return GVT_HIP_ERR_DEVICE;
+  }
+  V->d_amr_items = d_items; V->d_amr_cells = d_cells; V->amr_n_cells = (unsigned)cells.size();
+  V->amr_merge_bytes = sizeof(AmrRangeItem) * n_items + sizeof(AmrMergeCell) * cells.size();
+  V->amr_offset.swap(P.offset); V->amr_samples.swap(P.count);
+  return 0;
+}
+
+} // namespace
+
+extern "C" int gvt_hip_volume_update_amr(gvt_hip_volume *V, const float *samples, size_t n_samples, const float *const *subgrid_samples, int n_subgrids, uint32_t flags,
+                                         float *ms_out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V) { set_error("volume_update_amr: null volume"); return GVT_HIP_ERR_INVALID; }
+  if (flags & ~GVT_HIP_UPDATE_DEVICE) { set_error("volume_update_amr: unknown flags 0x%x", flags); return GVT_HIP_ERR_INVALID; }
+  if (V->sub.empty()) { set_error("volume_update_amr: the volume has no AMR subgrids (its time steps go through gvt_hip_volume_update_samples)"); return GVT_HIP_ERR_INVALID; }
+  const size_t total = (size_t)V->n[0] * V->n[1] * V->n[2];
+  if (n_samples != (samples ? total : 0)) {
+    set_error("volume_update_amr: %zu level-0 samples given, the brick has %zu (%d x %d x %d; 0 with NULL keeps them)", n_samples, total, V->n[0], V->n[1], V->n[2]);
+    return GVT_HIP_ERR_INVALID;
+  }
+  if (n_subgrids != (subgrid_samples ? (int)V->sub.size() : 0)) {
+    set_error("volume_update_amr: samples of %d subgrids given, the volume has %zu (0 with NULL keeps them all; another tree is gvt_hip_volume_set_subgrids)", n_subgrids, V->sub.size());
+    return GVT_HIP_ERR_INVALID;
+  }
+  bool any = samples != nullptr;
+  for (int i = 0; i < n_subgrids; i++) any = any || subgrid_samples[i] != nullptr;
+  if (!any) { set_error("volume_update_amr: no samples given, neither level 0's nor a subgrid's"); return GVT_HIP_ERR_INVALID; }
+  hipStream_t st = gctx().stream;
+  HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the samples)
+  int rc = amr_merge_tables(V);
+  if (rc) return rc;
+  V->lg.current = false; // (a light grid baked from the old samples is stale; the occluder grid reads meshes, lights and the tree: it stays)
+  const hipMemcpyKind kind = (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (samples) HIPCHK(hipMemcpyAsync(V->d_vox, samples, sizeof(float) * total, kind, st));
+  for (int i = 0; i < n_subgrids; i++)
+    if (subgrid_samples[i]) HIPCHK(hipMemcpyAsync(V->d_amr_vox + V->amr_offset[i], subgrid_samples[i], sizeof(float) * V->amr_samples[i], kind, st));
+  hipEvent_t e0, e1;
+  HIPCHK(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); set_error("volume_update_amr: hipEventCreate failed"); return GVT_HIP_ERR_DEVICE; }
+  rc = hipEventRecord(e0, st) == hipSuccess ? 0 : GVT_HIP_ERR_DEVICE;
+  if (!rc) rc = volume_ranges(V, true); // level 0, the subgrids merged in, the total: one download of the union
+  if (!rc && V->has_tf) rc = rebuild_tables(V); // (else: built when the transfer function arrives)
+  float ms = 0.f;
+  if (!rc && (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)) {
+    set_error("volume_update_amr: %s", hipGetErrorString(hipGetLastError()));
+    rc = GVT_HIP_ERR_DEVICE;
+  }
+  hipStreamSynchronize(st);
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  if (!rc && ms_out) *ms_out = ms;
+  return rc;
 }
 
 extern "C" int gvt_hip_volume_get_amr_info(gvt_hip_volume *V, gvt_hip_volume_amr_info *out) {

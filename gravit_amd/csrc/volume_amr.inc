@@ -4,6 +4,7 @@
 //   k_volume_march_amr_surf / _lit / _surf_lit <CLIP>   the same body with the surface and lit steps of volume_march_body, for volumes whose
 //                              subgrids were set with GVT_HIP_VOLUME_AMR_SHADED: crossings and shading read the FINAL grid's cell
 //   k_amr_ranges               every subgrid's vertices reduced into the level-0 macro cells whose closed box they lie in
+//   k_amr_ranges_merge         the same reduction per macro cell, merged into the level-0 ranges on the device (gvt_hip_volume_update_amr)
 // The contract is stated in include/gvt_hip.h ("AMR volumes"); tests/volume_amr_checker.py restates it in numpy.
 //
 // Device tables (built by amr_build on the host):
@@ -287,6 +288,47 @@ __global__ __launch_bounds__(VOL_BLOCK) void k_amr_ranges(const float *__restric
     if (threadIdx.x == 0) {
       for (int w = 1; w < WAVES; w++) vr_merge(r, VRange{ s_mn[w], s_mx[w], s_w[w] });
       out[it] = AmrRangeOut{ r.mn, r.mx, r.wild };
+    }
+    __syncthreads(); // (the next round writes the LDS again)
+  }
+}
+
+// ---- gvt_hip_volume_update_amr: the same reduction per time step, merged on the device.  The items of k_amr_ranges, grouped by macro
+// cell (built once per tree, amr_merge_tables); a block takes a macro cell that has items (grid-stride), reduces ALL of its rectangles
+// and merges the result into the level-0 range k_vol_ranges has just written for that cell: bmin / bmax / bnan then hold the union the
+// host used to form (amr_refresh_ranges), by the same rule (vr_merge).  ONE writer per macro cell, no atomics.
+// A rectangle is walked by rows: a wave per (y, z) row, its lanes along x, so neighbouring lanes read neighbouring floats and the row's
+// address costs one 32-bit division per row (the item is block-uniform: its words are scalar).  ext[1] * ext[2] fits 32 bits: a
+// rectangle lies in one macro cell, at most 8 * 512 + 1 vertices per axis.
+struct AmrMergeCell { unsigned cell, first, count; }; // the macro cell | its items in the grouped list
+
+__global__ __launch_bounds__(VOL_BLOCK) void k_amr_ranges_merge(const float *__restrict__ vox, const AmrRangeItem *__restrict__ items,
+                                                                const AmrMergeCell *__restrict__ cells, unsigned n_cells, float *__restrict__ bmin,
+                                                                float *__restrict__ bmax, uint8_t *__restrict__ bnan) {
+  constexpr unsigned WAVES = VOL_BLOCK / 64;
+  __shared__ float s_mn[WAVES], s_mx[WAVES];
+  __shared__ unsigned s_w[WAVES];
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (unsigned c = blockIdx.x; c < n_cells; c += gridDim.x) { // (block-uniform)
+    const AmrMergeCell M = cells[c];
+    VRange r = vr_none();
+    for (unsigned k = 0; k < M.count; k++) {
+      const AmrRangeItem I = items[M.first + k];
+      const float *g = vox + I.base + I.i0[0] + (size_t)I.nx * I.i0[1] + (size_t)I.nxy * I.i0[2];
+      const unsigned rows = I.ext[1] * I.ext[2];
+      for (unsigned row = wave; row < rows; row += WAVES) {
+        const unsigned z = row / I.ext[1], y = row - z * I.ext[1];
+        const float *p = g + (size_t)I.nx * y + (size_t)I.nxy * z;
+        for (unsigned x = lane; x < I.ext[0]; x += 64u) vr_add(r, p[x]);
+      }
+    }
+    r = vr_wave_all(r);
+    if (lane == 0u) { s_mn[wave] = r.mn; s_mx[wave] = r.mx; s_w[wave] = r.wild; }
+    __syncthreads();
+    if (threadIdx.x == 0) { // the one writer of this macro cell
+      for (unsigned w = 1; w < WAVES; w++) vr_merge(r, VRange{ s_mn[w], s_mx[w], s_w[w] });
+      vr_merge(r, VRange{ bmin[M.cell], bmax[M.cell], bnan[M.cell] });
+      bmin[M.cell] = r.mn; bmax[M.cell] = r.mx; bnan[M.cell] = (uint8_t)r.wild;
     }
     __syncthreads(); // (the next round writes the LDS again)
   }

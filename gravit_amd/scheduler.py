@@ -763,10 +763,13 @@ class VolumeTracer:
         return self
 
     @staticmethod
-    def _same_bricking(adapters, bricks):
+    def _same_bricking(adapters, bricks, amr=False):
         """Helper of update(), not part of the tracer's surface (static so that the check runs without a device): the bricks of another time
         step as a list, if they are the adapters' bricking (counts and offset per brick; a whole VolumeData has offset 0) and, for adapters
-        that name one (dtype_name), of their dtype; ValueError otherwise."""
+        that name one (dtype_name), of their dtype; with amr also of their subgrid tree (adapter.same_subgrid_tree against the adapter's
+        .tree); ValueError otherwise."""
+        from .adapter import same_subgrid_tree
+
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         if len(bricks) != len(adapters):
             raise ValueError("VolumeTracer.update: %d bricks given, the tracer has %d" % (len(bricks), len(adapters)))
@@ -779,15 +782,24 @@ class VolumeTracer:
             want, got = getattr(a, "dtype_name", None), str(b.data.dtype).replace("torch.", "")
             if want is not None and got != want:
                 raise ValueError("VolumeTracer.update: brick %d has %s data, the tracer's holds %s (another voxel type needs a new tracer)" % (i, got, want))
+            if amr:
+                same_subgrid_tree(getattr(a, "tree", []), getattr(b, "subgrids", None), "VolumeTracer.update: brick %d" % i)
         return bricks
 
-    def update(self, bricks):
+    def update(self, bricks, amr=False):
         """The next time step: the same bricking of the new data (scenes.split_volume with the same split, or one VolumeData), pushed into
-        the bricks in place (gvt_hip_volume_update_samples).  Transfer function, surfaces, lights, top level, queues and framebuffer stay."""
-        bricks = self._same_bricking(self.adapters, bricks)  # (all of them checked before the first one changes)
+        the bricks in place (gvt_hip_volume_update_samples).  Transfer function, surfaces, lights, top level, queues and framebuffer stay.
+        amr=True: the bricks may carry AMR subgrids (scenes.split_amr_volume with the same split) -- every brick's subgrid tree must be
+        its adapter's (ValueError before the first brick changes), and a brick that has subgrids goes through gvt_hip_volume_update_amr
+        with its level-0 data and all its subgrids' (the light grids go stale, the occluder grids do not).  Without it (the default) a
+        brick that has subgrids is refused by the library, as ever."""
+        bricks = self._same_bricking(self.adapters, bricks, amr)  # (all of them checked before the first one changes)
         self._grid_stale = True
         for a, b in zip(self.adapters, bricks):
-            a.update_samples(b.data)
+            if amr and getattr(b, "subgrids", None):
+                a.update_amr(b.data, b.subgrids)
+            else:
+                a.update_samples(b.data)
             if getattr(b, "ghosts", None) is not None:  # the new step's face layers travel with its bricks
                 a.set_ghosts(b.ghosts)
         return self
@@ -1189,8 +1201,9 @@ class MixedTracer:
         return self.mesh.backend.framebuffer(clamp)
 
     # the volume's controls
-    def update(self, bricks):
-        self.volume.update(bricks)
+    def update(self, bricks, amr=False):
+        """VolumeTracer.update: amr=True takes bricks with AMR subgrids in place (the occluder grids stay current)."""
+        self.volume.update(bricks, amr)
         return self
 
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):

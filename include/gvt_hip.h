@@ -651,8 +651,9 @@ int gvt_hip_fb_composite_over(gvt_hip_fb *front, const gvt_hip_fb *back, const g
  * and _set_shading with GVT_HIP_VOLUME_SHADE_GRADIENT return GVT_HIP_ERR_INVALID and change nothing, as _set_subgrids without the flag
  * does on a volume that has either.
  * OUT OF SCOPE, refused on every AMR volume, flagged or not, with GVT_HIP_ERR_INVALID and nothing changed: central gradients
- * (_set_gradient(CENTRAL), and _set_subgrids on a CENTRAL volume) and in-place updates (_update_samples / _update_samples_typed).  A new
- * time step of an AMR volume is _set_subgrids with n = 0, _update_samples and _set_subgrids again, or a new volume.  The
+ * (_set_gradient(CENTRAL), and _set_subgrids on a CENTRAL volume), and _update_samples / _update_samples_typed, which know one grid.  A
+ * new time step of an AMR volume on the same tree is gvt_hip_volume_update_amr ("time-varying AMR volumes" below), in place; a step
+ * whose tree changes is _set_subgrids (with n = 0, _update_samples and _set_subgrids again where level 0 changes too), or a new volume.  The
  * shadowed, fog-shadowed and mesh-shadowed frames and both bakes do not take bricks with subgrids (they refuse, as stated with each),
  * and neither do gvt_hip_volume_frame_fused and _fused_shaded (they fall back to the loop); gvt_hip_volume_frame_fused_amr with
  * GVT_HIP_FUSED_AMR marches such bricks in the fused frame ("fused frame: AMR bricks" below).  The clipped march (GVT_HIP_RAY_CLIP, gvt_hip_volume_frame_clipped) works on AMR volumes, shaded ones
@@ -687,6 +688,43 @@ typedef struct gvt_hip_volume_amr_info {
   uint64_t amr_marches;         /* marches that ran an AMR entry point, so far (0 on a volume that never had subgrids) */
 } gvt_hip_volume_amr_info;
 int gvt_hip_volume_get_amr_info(gvt_hip_volume *, gvt_hip_volume_amr_info *); /* synchronises */
+/* ---- time-varying AMR volumes (additive: the ABI revision stays 6, no entry point above changes its rule; _update_samples[_typed] go
+ *      on refusing a volume that has subgrids) ----
+ * The next time step of an AMR volume on the SAME subgrid tree (parents, ratios, lo, cells, and so every size), in place: new samples
+ * for the level-0 grid (samples; NULL with n_samples = 0 keeps them), for any of the subgrids (subgrid_samples[i], laid out as
+ * _set_subgrids takes them; an entry NULL keeps that subgrid, subgrid_samples NULL with n_subgrids = 0 keeps them all), or for both.
+ * flags: 0 (every pointer given is host memory) or GVT_HIP_UPDATE_DEVICE (every pointer given is device memory: no host round trip).
+ * After the call the volume answers exactly like a volume freshly created from the resident samples -- the new ones where given, the
+ * old ones elsewhere -- with the same _set_subgrids (same flags) and the same set_transfer / set_surfaces / set_lights / set_shading
+ * calls: every ray bit of gvt_hip_volume_trace, every framebuffer bit of gvt_hip_volume_frame, _clipped, _frame_fused_amr and the
+ * shadowed frames under GVT_HIP_VOLUME_ALLOW_AMR, value_min / value_max as numbers, n_blocks / n_blocks_empty.  Legal before any
+ * _set_transfer: the tables are then built when the transfer function arrives.  Samples need not be finite.
+ * WHAT STAYS.  Nothing a march reads is re-allocated: the level-0 samples, the subgrids' samples and tables, the skip table and the
+ * surface skip words keep their addresses, so tracers, tops, queues and fused frames built around the volume keep working.
+ * _get_amr_info reports the same n_subgrids, n_levels and subgrid_bytes; every counter goes on accumulating.
+ * WHAT GOES STALE.  The light grid (as with _update_samples: _get_light_grid says current = 0 and the fog-shadowed frames refuse until
+ * the next bake).  The occluder grid stays current: it depends on the meshes, the lights and the tree only.
+ * RANGES AND TABLES.  The macro cells' merged ranges ("MACRO CELLS" above) are recomputed from everything resident, on the device: the
+ * level-0 ranges by the kernel of _update_samples, then every subgrid's vertices merged into them by the min / max / not-finite rule of
+ * the level-0 ranges (a vertex on a macro-cell boundary counts for both cells), then one download of 9 bytes per macro cell; the skip
+ * table, the AMR cell words' skip bit and the surface skip words are rebuilt from them by the rule of _set_transfer and _set_surfaces.
+ * The volume keeps no other copy of the subgrids' ranges, so a later _set_subgrids(n = 0) gives the plain volume of the current
+ * level-0 samples.  The first update of a tree builds the merge's work list (freed with the tree; not part of subgrid_bytes).
+ * REFUSALS, GVT_HIP_ERR_INVALID, the volume exactly as it was, all checked before the first byte moves: a null volume; a volume without
+ * subgrids (its steps are gvt_hip_volume_update_samples'); samples with an n_samples that is not counts[0] * counts[1] * counts[2], or
+ * NULL with a non-zero n_samples; subgrid_samples with an n_subgrids that is not the volume's count, or NULL with a non-zero
+ * n_subgrids; nothing given at all (no level-0 samples and no subgrid entry); an unknown flag bit.
+ * GVT_HIP_ERR_DEVICE (a HIP call failed part way): samples may already be replaced while ranges and tables are not; the volume is then
+ * undefined until an update succeeds, and may only be updated again or destroyed.
+ * The call waits for the calling context's stream first and returns when it is done; the caller serialises it against frames that use
+ * the brick.  ms_out (may be NULL): time on the context's stream from the end of the uploads to the end of the update (ranges, their
+ * download, the tables' rebuild on the host and their upload), as for _update_samples.
+ * OUT OF SCOPE.  A step whose tree changes (regridding: _set_subgrids); typed voxels with subgrids; CENTRAL gradients on AMR volumes;
+ * the Domain scheduler's volume backend. */
+int gvt_hip_volume_update_amr(gvt_hip_volume *, const float *samples /* level 0; NULL: keep */, size_t n_samples /* the brick's vertex count, or 0 with NULL */,
+                              const float *const *subgrid_samples /* NULL: keep all; an entry NULL: keep that subgrid */,
+                              int n_subgrids /* the volume's subgrid count, or 0 with NULL */, uint32_t flags /* GVT_HIP_UPDATE_DEVICE: every pointer given is device memory */,
+                              float *ms_out /* may be NULL */);
 
 /* ---- volume domains across ranks: Tracer<DomainScheduler> taking the volume branch of shuffleRays (TracerBase.h:325-414,
  *      DomainTracer.h:148-496).  The bricks of one volume are spread over the ranks of a job (owner[brick] = rank); every rank holds a
@@ -855,7 +893,7 @@ int gvt_hip_volume_frame_fused_shaded(gvt_hip_top *, gvt_hip_volume *const *volu
  * amr_marches) are not touched by a fused frame.  samples_refined below is the sum of what the loop would have added to the bricks'
  * samples_refined for the same frame.
  * OUT OF SCOPE.  The shadowed, fog-shadowed and mesh-shadowed frames and both bakes on bricks with subgrids (they go on refusing);
- * CENTRAL gradients on AMR volumes; typed voxels with subgrids; in-place updates of AMR volumes; the Domain scheduler; fused as the default. */
+ * CENTRAL gradients on AMR volumes; typed voxels with subgrids; the Domain scheduler; fused as the default.  (In-place updates of AMR volumes: gvt_hip_volume_update_amr.) */
 #define GVT_HIP_FUSED_AMR 16u       /* the fused kernels may take frames in which some or all bricks have subgrids */
 typedef struct {
   uint32_t fused, features;  /* the fields of gvt_hip_volume_fused_shaded_stats, same order and meaning */
@@ -952,7 +990,7 @@ int gvt_hip_volume_frame_fused_amr(gvt_hip_top *, gvt_hip_volume *const *volumes
  * CONSEQUENCES.  The same bits for every admissible bricking, and with or without macro-cell skipping.  With every T_j = 1 the bits are
  * gvt_hip_volume_frame_fused_amr's.  Where every light is blocked the bits are the kd = 0 frame's.  With no mesh the mesh-shadowed
  * frame has the fog-shadowed frame's bits.
- * OUT OF SCOPE.  CENTRAL gradients, typed voxels or in-place updates on AMR volumes; light or occluder planes at subgrid resolution;
+ * OUT OF SCOPE.  CENTRAL gradients or typed voxels on AMR volumes; light or occluder planes at subgrid resolution;
  * refined-sample counters in the shadow stats; shadows across ranks. */
 #define GVT_HIP_VOLUME_ALLOW_CENTRAL 2u /* flags of the shadowed frames and the two bakes: accept frames whose bricks are all CENTRAL */
 #define GVT_HIP_VOLUME_ALLOW_AMR 4u     /* ... accept frames in which some or all bricks have AMR subgrids ("shadows on AMR bricks") */

@@ -7,8 +7,8 @@
 Each .hip is compiled with gravit_amd._build.FLAGS (of THIS tree) plus --offload-device-only -S, the two trees side by side.  Per kernel
 (every name that has a kernel descriptor) the lines between its label and its descriptor are compared, comments dropped and the
 local labels (.LBB*, .Ltmp*, .Lfunc_end*) replaced by one token, since a kernel added in front renumbers them.  Printed: the counts
-of identical, differing, new and vanished kernels, and for each differing kernel both instruction counts and the kernel info side by
-side.  Exit status 1 when a kernel differs or has vanished, else 0.  It is a diff: it knows no instruction.
+of identical, differing, new and vanished kernels, for each differing kernel both instruction counts and the kernel info side by
+side, and for each new kernel its own.  Exit status 1 when a kernel differs or has vanished, else 0.  It is a diff: it knows no instruction.
 """
 import argparse
 import os
@@ -95,6 +95,9 @@ def report(old, new, out=sys.stdout):
             print("  %-12s %10s %10s%s" % (title, a, b, "" if a == b else "   <--"), file=out)
     for k in fresh:
         print("new: %s" % k, file=out)
+        print("  %-12s %10d" % ("instructions", new[k]["insts"]), file=out)
+        for (title, _), b in zip(INFO, _row(new[k])):
+            print("  %-12s %10s" % (title, b), file=out)
     for k in gone:
         print("vanished: %s" % k, file=out)
     return 1 if differ or gone else 0

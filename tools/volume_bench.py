@@ -13,6 +13,12 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              range kernels (gvt_hip_profile's build class), ranges + download (an update of a volume without
                                              a transfer function), the rest = the host table rebuild and its upload.  --recreate-only: the
                                              first of these alone (it needs nothing the update added, so it also runs on an older tree)
+  python tools/volume_bench.py --update --amr   time-varying AMR volumes: two time steps of the --fused --amr scene (256^3, the central eighth
+                                             refined, ten subgrids) pushed alternately into one brick under the sparse table, samples in host
+                                             and in device memory: the wall time of the three-call route (set_subgrids([]), update_samples,
+                                             set_subgrids) and of gvt_hip_volume_update_amr, its ms_out and where that goes (range kernels,
+                                             ranges + download, the host table rebuild; wall - ms_out = the uploads).  --three-call-only: the
+                                             first of these alone (it needs nothing the in-place call added, so it also runs on an older tree)
   python tools/volume_bench.py --surfaces    the "thin" frames plain, with two isovalues the field never reaches (the per-sample cost of
                                              the side test alone) and with two it does (opacity 0.3, one light), each against the plain frame
   python tools/volume_bench.py --clip        geometry inside the volume: per grid size and bricking the "thin" frame plain and clipped at a depth
@@ -934,6 +940,62 @@ def run_update(n, device, steps, warmup, recreate_only, dtype="f32"):
     return out
 
 
+def run_amr_update(n, device, steps, warmup, three_call_only):
+    """--update --amr: two time steps of amr_bricked_scene(n) (step 2: every sample v of every level becomes 1 - v), pushed alternately into
+    one brick under the sparse table."""
+    from gravit_amd.adapter import HipVolumeAdapter
+
+    vol = amr_bricked_scene(n)
+    level0 = [vol.data, np.ascontiguousarray(F(1.0) - vol.data)]
+    subs = [list(vol.subgrids), [scenes.Subgrid(s.parent, s.ratio, s.lo, s.cells, np.ascontiguousarray(F(1.0) - s.data)) for s in vol.subgrids]]
+    sub_mb = 4.0 * sum(s.data.size for s in vol.subgrids) / 1e6
+    if device:
+        import torch
+
+        level0 = [torch.from_numpy(d).cuda() for d in level0]
+        subs = [[scenes.Subgrid(s.parent, s.ratio, s.lo, s.cells, torch.from_numpy(s.data).cuda()) for s in step] for step in subs]
+        torch.cuda.synchronize()
+    t = transfer("spikes", "f32")
+    ad = HipVolumeAdapter(vol, 2.0)
+    ad.set_transfer(t)
+    out = {"mode": "amr_update", "n": n, "samples": "device" if device else "host", "grid_mb": round(4.0 * n ** 3 / 1e6, 1), "subgrid_mb": round(sub_mb, 1),
+           "n_subgrids": len(vol.subgrids)}
+    wall = []
+    for i in range(warmup + steps):  # the documented route before the in-place call
+        k = (i + 1) % 2
+        t0 = time.perf_counter()
+        ad.set_subgrids([])
+        ad.update_samples(level0[k])
+        ad.set_subgrids(subs[k])
+        capi.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+    out["three_call_wall_ms"], out["three_call_wall_min_ms"] = med(wall[warmup:]), round(min(wall[warmup:]), 3)
+    out["n_blocks"], out["n_blocks_empty"] = ad.info()["n_blocks"], ad.info()["n_blocks_empty"]
+    if three_call_only:
+        return out
+    bare = HipVolumeAdapter(vol, 2.0)  # no transfer function: its update is ranges + download alone
+    wall, ms, ms_bare, ms_kernel = [], [], [], []
+    for i in range(warmup + steps):  # profiling off: the wall time and both ms_out
+        k = (i + 1) % 2
+        t0 = time.perf_counter()
+        ms.append(ad.update_amr(level0[k], subs[k]))
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms_bare.append(bare.update_amr(level0[k], subs[k]))
+    out["n_blocks_empty_in_place"] = ad.info()["n_blocks_empty"]  # (the same step as the three-call loop ended on: the same count)
+    capi.profile(1)
+    for i in range(warmup + steps):  # a pass of its own for the range kernels' event time
+        k0 = capi.stats()["ms_build"]
+        ad.update_amr(level0[(i + 1) % 2], subs[(i + 1) % 2])
+        ms_kernel.append(capi.stats()["ms_build"] - k0)
+    capi.profile(0)
+    w = warmup
+    out.update({"update_wall_ms": med(wall[w:]), "update_wall_min_ms": round(min(wall[w:]), 3), "update_wall_max_ms": round(max(wall[w:]), 3),
+                "update_ms_out": med(ms[w:]), "uploads_ms": med(np.array(wall[w:]) - np.array(ms[w:])), "range_kernels_ms": med(ms_kernel[w:]),
+                "ranges_and_download_ms": med(ms_bare[w:]), "table_rebuild_ms": med(np.array(ms[w:]) - np.array(ms_bare[w:])),
+                "three_call_over_update": round(out["three_call_wall_ms"] / max(float(np.median(wall[w:])), 1e-9), 1)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
@@ -951,6 +1013,7 @@ def main():
                          "bricks, fused against the loop, and with --shadows / --fog-shadows / --mesh-shadows the shadowed frames, CENTRAL against CELL")
     ap.add_argument("--amr", action="store_true")
     ap.add_argument("--recreate-only", action="store_true")
+    ap.add_argument("--three-call-only", action="store_true", help="with --update --amr: the three-call route alone")
     ap.add_argument("--domains", type=int, nargs="+", metavar="W")
     ap.add_argument("--per-queue", action="store_true")
     ap.add_argument("--overlap", action="store_true")
@@ -966,6 +1029,14 @@ def main():
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
     capi.init(0)
     out = {"source_hash": _build.source_hash(), "width": 1920, "height": 1080, "runs": []}
+    if a.update and a.amr:
+        for n in ([256] if a.sizes == [256, 512] else a.sizes):
+            for device in (False, True):
+                r = run_amr_update(n, device, a.steps, a.warmup, a.three_call_only)
+                out["runs"].append(r)
+                print(json.dumps(r), flush=True)
+        a.sizes = []
+        a.update = a.amr = False
     if a.update:
         for n in a.sizes:
             for device in (False, True):
