@@ -816,6 +816,22 @@ class HipVolumeAdapter:
     def occluder_grid_release(self):
         capi.check(self.lib.gvt_hip_volume_occluder_grid_release(self.h), "gvt_hip_volume_occluder_grid_release")
 
+    def ao_grid_info(self):
+        """present, current, n_dirs, bias, radius, bytes of the brick's ambient occlusion grid (gvt_hip_volume_ao_grid_info)."""
+        i = capi.VolumeAoState()
+        capi.check(self.lib.gvt_hip_volume_ao_grid_info(self.h, C.byref(i)), "gvt_hip_volume_ao_grid_info")
+        return i.as_dict()
+
+    def ao_grid(self):
+        """The baked ambient occlusion at the brick's vertices, (nz, ny, nx) float32, 1 = open (gvt_hip_volume_ao_grid_download); no grid:
+        GvtHipError."""
+        out = np.zeros(tuple(int(c) for c in self.counts[::-1]), np.float32)
+        capi.check(self.lib.gvt_hip_volume_ao_grid_download(self.h, capi.ptr(out)), "gvt_hip_volume_ao_grid_download")
+        return out
+
+    def ao_grid_release(self):
+        capi.check(self.lib.gvt_hip_volume_ao_grid_release(self.h), "gvt_hip_volume_ao_grid_release")
+
     def march_queue(self, queue, minv, may_clip=False):
         """gvt_hip_volume_march_queue: Adapter::trace on a device-resident RayQueue, in place and without a host wait; the rays keep
         their flags for the volume shuffle.  may_clip: the queue may hold rays that carry RAY_CLIP."""

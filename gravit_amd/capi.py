@@ -48,6 +48,8 @@ SYMBOLS = [
     "gvt_hip_volume_frame_fog_shadowed",
     "gvt_hip_volume_occluder_grid_bake", "gvt_hip_volume_occluder_grid_download", "gvt_hip_volume_occluder_grid_info", "gvt_hip_volume_occluder_grid_release",
     "gvt_hip_volume_frame_mesh_shadowed",
+    "gvt_hip_volume_ao_grid_bake", "gvt_hip_volume_ao_grid_download", "gvt_hip_volume_ao_grid_info", "gvt_hip_volume_ao_grid_release",
+    "gvt_hip_volume_frame_ao",
 ]
 
 
@@ -200,6 +202,48 @@ class VolumeMeshShadowStats(C.Structure):
         return out
 
 
+VOLUME_AO_MAX_DIRS = 32  # directions of one AO bake
+VOLUME_AO_MESH = 8  # flags of VolumeAoFrameParams only: the base frame is the mesh-shadowed frame
+
+
+class VolumeAoParams(C.Structure):
+    """gvt_hip_volume_ao_params: flags is 0 or VOLUME_ALLOW_CENTRAL; bias 1 .. 64; n_dirs 1 .. VOLUME_AO_MAX_DIRS world-space directions; radius > 0 (inf: no clip)."""
+    _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32), ("n_dirs", C.c_int32), ("radius", C.c_float), ("dirs", (C.c_float * 3) * VOLUME_AO_MAX_DIRS)]
+
+
+class VolumeAoStats(C.Structure):
+    """gvt_hip_volume_ao_stats: what gvt_hip_volume_ao_grid_bake reports of one bake (rays = vertices x n_dirs)."""
+    _fields_ = [("rays", C.c_uint64), ("samples_marched", C.c_uint64), ("samples_gathered", C.c_uint64), ("crossings", C.c_uint64), ("bytes", C.c_uint64),
+                ("ms", C.c_float), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class VolumeAoState(C.Structure):
+    """gvt_hip_volume_ao_state: what gvt_hip_volume_ao_grid_info reports of one volume."""
+    _fields_ = [("present", C.c_uint32), ("current", C.c_uint32), ("n_dirs", C.c_int32), ("bias", C.c_int32), ("radius", C.c_float), ("pad", C.c_uint32),
+                ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class VolumeAoFrameParams(C.Structure):
+    """gvt_hip_volume_ao_frame_params: flags is 0, VOLUME_ALLOW_CENTRAL, VOLUME_AO_MESH or both; bias = the crossings' shadow rays', 1 .. 64."""
+    _fields_ = [("flags", C.c_uint32), ("bias", C.c_int32)]
+
+
+class VolumeAoFrameStats(C.Structure):
+    """gvt_hip_volume_ao_frame_stats: the base frame's counters, then whether the AO kernel ran."""
+    _fields_ = [("base", VolumeMeshShadowStats), ("ao", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        out = self.base.as_dict()
+        out["ao"] = self.ao
+        return out
+
+
 FUSED_SURFACES, FUSED_LIT = 1, 2  # gvt_hip_volume_frame_fused_shaded's allow bits: frames with surfaces / with lit fog may be fused
 FUSED_AMR = 16  # gvt_hip_volume_frame_fused_amr's further allow bit: frames in which some or all bricks have AMR subgrids may be fused
 FUSED_CENTRAL = 8  # ... and such frames whose bricks all shade with VOLUME_GRADIENT_CENTRAL (the kernel's CENTRAL instantiation; its bit in features)
@@ -293,6 +337,11 @@ def load():
         lib.gvt_hip_volume_occluder_grid_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         lib.gvt_hip_volume_occluder_grid_info.argtypes = [C.c_void_p, C.c_void_p]
         lib.gvt_hip_volume_occluder_grid_release.argtypes = [C.c_void_p]
+        lib.gvt_hip_volume_ao_grid_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_ao_grid_download.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_ao_grid_info.argtypes = [C.c_void_p, C.c_void_p]
+        lib.gvt_hip_volume_ao_grid_release.argtypes = [C.c_void_p]
+        lib.gvt_hip_volume_frame_ao.argtypes = lib.gvt_hip_volume_frame_shadowed.argtypes
         lib.gvt_hip_fb_composite_over.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if lib.gvt_hip_abi_version() != ABI_VERSION:  # the out-structs below (MeshInfo, Stats, FrameStats) mirror ONE revision of include/gvt_hip.h
             raise GvtHipError("%s is ABI revision %d, this binding was written against %d: rebuild the library (python -m gravit_amd._build)" % (LIB_PATH, lib.gvt_hip_abi_version(), ABI_VERSION))
@@ -374,5 +423,5 @@ def stats_reset():
     check(load().gvt_hip_stats_reset(), "gvt_hip_stats_reset")
 
 
-__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeFusedAmrStats", "VolumeShadowParams", "VolumeShadowStats", "VolumeLightGridParams", "VolumeLightGridStats", "VolumeLightGridState", "VolumeFogShadowStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
+__all__ = ["load", "init", "check", "ptr", "f32", "GvtHipError", "MeshInfo", "VolumeInfo", "VolumeAmrInfo", "VolumeFusedStats", "VolumeFusedAmrStats", "VolumeShadowParams", "VolumeShadowStats", "VolumeLightGridParams", "VolumeLightGridStats", "VolumeLightGridState", "VolumeFogShadowStats", "VolumeAoParams", "VolumeAoStats", "VolumeAoState", "VolumeAoFrameParams", "VolumeAoFrameStats", "SubgridPod", "Stats", "SYMBOLS", "RAY_DTYPE", "HIT_DTYPE",
            "LIGHT_DTYPE", "MATERIAL_DTYPE"]

@@ -129,6 +129,13 @@ struct gvt_hip_volume {
   // set since the bake
   uint8_t *d_occ = nullptr;
   BakedGrids og;
+  // the AO grid of the AO frame (gvt_hip_volume_ao_grid_bake; volume_ao_grid.inc): ONE float32 plane of the brick's vertices (ag.planes is
+  // 1, ag.usable unused).  ag.current: no call that changes what an AO ray meets (samples, table, surfaces, subgrids) has touched the
+  // volume since the bake; the lights, the shading, the gradient kind and the ghosts do not matter to it
+  float *d_ao = nullptr;
+  BakedGrids ag;
+  int ag_dirs = 0, ag_bias = 0;
+  float ag_radius = 0.f;
 };
 
 namespace {
@@ -903,6 +910,8 @@ __global__ __launch_bounds__(VR_TOTAL_BLOCK) void k_vol_range_total(const float 
 #include "volume_fused_fog.inc" // k_volume_march_fused_fog
 #include "volume_occluder_grid.inc" // k_occluder_rays, k_occluder_fold, k_occluder_pack
 #include "volume_fused_mesh.inc" // k_volume_march_fused_mesh
+#include "volume_ao_grid.inc" // k_volume_bake_ao
+#include "volume_fused_ao.inc" // k_volume_march_fused_ao, k_volume_march_fused_ao_lean
 #include "volume_fused_shadow_amr.inc" // k_volume_march_fused_shadow_amr, _fog_amr, _mesh_amr, the lean two, k_volume_bake_light_amr
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + VOL_BLOCK - 1) / VOL_BLOCK); }
@@ -1299,7 +1308,7 @@ extern "C" int gvt_hip_volume_get_voxel_type(gvt_hip_volume *V, int *type_out, s
 extern "C" void gvt_hip_volume_destroy(gvt_hip_volume *V) {
   if (!V) return;
   if (gctx().ready) hipStreamSynchronize(gctx().stream);
-  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost); hipFree(V->d_lgrid); hipFree(V->d_occ);
+  hipFree(V->d_vox); hipFree(V->d_tf); hipFree(V->d_mc); hipFree(V->d_cells); hipFree(V->d_stats); hipFree(V->d_ghost); hipFree(V->d_lgrid); hipFree(V->d_occ); hipFree(V->d_ao);
   hipFree(V->d_amr_vox); hipFree(V->d_amr_mc); hipFree(V->d_amr_list); hipFree(V->d_amr_desc); hipFree(V->d_amr_items); hipFree(V->d_amr_cells);
   delete V;
 }
@@ -1330,6 +1339,7 @@ extern "C" int gvt_hip_volume_set_transfer(gvt_hip_volume *V, const float *cmap,
   HIPCHK(hipStreamSynchronize(gctx().stream)); // (a march in flight reads the tables)
   HIPCHK(hipMemcpy(V->d_tf, tf.data(), sizeof(float4) * 256, hipMemcpyHostToDevice));
   V->lg.current = false; // (a light grid baked under the old table is stale)
+  V->ag.current = false; // (... and so is an AO grid)
   for (int i = 0; i < 256; i++) { V->tf_a[i] = tf[i].w; V->tf_rgb[i][0] = tf[i].x; V->tf_rgb[i][1] = tf[i].y; V->tf_rgb[i][2] = tf[i].z; }
   V->tf_lo = value_lo; V->tf_hi = value_hi; V->has_tf = true;
   return rebuild_tables(V);
@@ -1355,6 +1365,7 @@ extern "C" int gvt_hip_volume_update_samples_typed(gvt_hip_volume *V, const void
   hipStream_t st = gctx().stream;
   HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the samples)
   V->lg.current = false; // (a light grid baked from the old samples is stale)
+  V->ag.current = false; // (... and so is an AO grid)
   HIPCHK(hipMemcpyAsync(V->d_vox, samples, voxel_bytes(V->vtype) * total, (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0));
@@ -1395,6 +1406,7 @@ extern "C" int gvt_hip_volume_set_surfaces(gvt_hip_volume *V, const float *isova
   }
   V->n_iso = n_iso; V->n_pl = n_slices; V->surf_alpha = opacity;
   V->lg.current = false; // (the surfaces cast shadows: a light grid baked under the old ones is stale)
+  V->ag.current = false; // (... and so is an AO grid)
   for (int i = 0; i < n_iso; i++) V->iso[i] = isovalues[i];
   for (int i = 0; i < n_slices; i++)
     for (int a = 0; a < 4; a++) V->plane[i][a] = slices[4 * i + a];
@@ -1805,6 +1817,19 @@ void launch_fused_mesh(uint32_t features, const gvt_hip_volume *V0, const gvt_hi
   }, depth != nullptr, (features & GVT_HIP_FUSED_LIT) != 0);
 }
 
+// the AO kernels (the AO frame: a usable light exists): lit fog or not, with surfaces or -- the lean kernel, lit fog implied -- without;
+// mesh: the base frame is the mesh-shadowed one
+template <typename VT, bool CENTRAL, typename... Tail>
+void launch_fused_ao(uint32_t features, bool mesh, const gvt_hip_volume *V0, const gvt_hip_depth *depth, unsigned blocks, hipStream_t st, VolDev U, SurfDev S, ShadowDev H,
+                     const FusedBrick *d_bricks, const AoBrick *d_grids, TopDev top, RayPlanes P, unsigned n, const Mat4 &M, Tail... tail) {
+  const bool surf = (features & GVT_HIP_FUSED_SURFACES) != 0;
+  const ClipArgs c = clip_args(depth);
+  with_bools([&](auto clip, auto lit, auto mesh_c) {
+    if (surf) k_volume_march_fused_ao<VT, clip.value, lit.value, CENTRAL, mesh_c.value><<<blocks, VOL_BLOCK, 0, st>>>(U, S, H, d_bricks, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+    else k_volume_march_fused_ao_lean<VT, clip.value, CENTRAL, mesh_c.value><<<blocks, VOL_BLOCK, 0, st>>>(U, light_dev(V0, M), H.usable, d_bricks, d_grids, top, P, n, M, c.d_t, c.n_clip, tail...);
+  }, depth != nullptr, (features & GVT_HIP_FUSED_LIT) != 0, mesh);
+}
+
 // the shadowed AMR kernels (GVT_HIP_FUSED_AMR is among the features; float32, CELL): the kernel of the shadowed, the fog-shadowed (fog) or
 // the mesh-shadowed (mesh) frame, lit fog or not, with surfaces or -- the lean kernels -- without.  d_grids: the bricks' planes (fog or
 // mesh), else null
@@ -1847,10 +1872,12 @@ AmrDev amr_record(const gvt_hip_volume *B) {
 // grid's planes too (the light grid's only where fog is set as well).  GVT_HIP_FUSED_AMR in features (never with
 // GVT_HIP_FUSED_CENTRAL: a brick with subgrids is CELL): the launch is the AMR kernels' -- with shadow, fog or mesh those of
 // volume_fused_shadow_amr.inc (GVT_HIP_VOLUME_ALLOW_AMR) -- the bricks' AMR tables travel in a further table beside the records and the
-// planes, read from the volumes NOW, and *refined_out gets the seventh counter (the shadowed kernels do not count it)
+// planes, read from the volumes NOW, and *refined_out gets the seventh counter (the shadowed kernels do not count it).  ao
+// (gvt_hip_volume_frame_ao; shadow is given with a usable light, never with GVT_HIP_FUSED_AMR): the launch is k_volume_march_fused_ao's, and
+// the table holds three pointers a brick (AoBrick): the light grid's where fog is set, the occluder grid's where mesh is, the AO grid's
 int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *minv, size_t n_inst, const gvt_hip_camera *cam, gvt_hip_queue *const *queues,
                        gvt_hip_fb *fb, const gvt_hip_depth *depth, uint32_t features, gvt_hip_volume_fused_shaded_stats &S, const ShadowDev *shadow = nullptr,
-                       uint64_t *shadow_out = nullptr, bool fog = false, bool mesh = false, uint64_t *refined_out = nullptr) {
+                       uint64_t *shadow_out = nullptr, bool fog = false, bool mesh = false, uint64_t *refined_out = nullptr, bool ao = false) {
   Ctx &C = gctx();
   int rc;
   if ((rc = gvt_hip_fb_clear(fb))) return rc;
@@ -1870,8 +1897,9 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
   if (!d_bricks || !d_stats || !work) return GVT_HIP_ERR_DEVICE;
   static_assert(sizeof(MeshBrick) >= sizeof(FogBrick), "one allocation serves either table");
-  void *d_planes = (fog || mesh) ? scratch_get(SCR_VOL_GRIDS, sizeof(MeshBrick) * n_inst) : nullptr;
-  if ((fog || mesh) && !d_planes) return GVT_HIP_ERR_DEVICE;
+  void *d_planes = ao ? scratch_get(SCR_VOL_GRIDS, sizeof(AoBrick) * n_inst) : (fog || mesh) ? scratch_get(SCR_VOL_GRIDS, sizeof(MeshBrick) * n_inst) : nullptr;
+  if ((ao || fog || mesh) && !d_planes) return GVT_HIP_ERR_DEVICE;
+  AoBrick *d_agrids = (AoBrick *)d_planes;
   FogBrick *d_grids = (FogBrick *)d_planes;
   MeshBrick *d_mgrids = (MeshBrick *)d_planes;
   // the CENTRAL instantiations' ghost table: the bricks' face pointers, beside the records (FusedGhost, volume_fused.inc)
@@ -1883,24 +1911,28 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
   if (amr && !d_amr) return GVT_HIP_ERR_DEVICE;
   static_assert((sizeof(FusedBrick) + sizeof(MeshBrick) + sizeof(void *)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "the brick table, the grids' and the ghosts' fit the staging block");
   static_assert((sizeof(FusedBrick) + sizeof(MeshBrick) + sizeof(AmrDev)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "... and so do the brick table, the grids' and the AMR table, which takes the ghosts' place (an AMR frame is never CENTRAL)");
+  static_assert((sizeof(FusedBrick) + sizeof(AoBrick) + sizeof(void *)) * VOL_DEST_MAX <= PINNED_STAGE_BYTES, "... and the AO frame's brick table, planes and ghosts");
   void *stage = nullptr;
   if ((rc = pinned_stage_begin(&stage))) return rc;
   FusedBrick *h = (FusedBrick *)stage;
   FogBrick *hg = (FogBrick *)(h + VOL_DEST_MAX);
   MeshBrick *hm = (MeshBrick *)(h + VOL_DEST_MAX);
-  const void **hf = (const void **)(hm + VOL_DEST_MAX);
+  AoBrick *ho = (AoBrick *)(h + VOL_DEST_MAX);
+  const void **hf = ao ? (const void **)(ho + VOL_DEST_MAX) : (const void **)(hm + VOL_DEST_MAX);
   AmrDev *ha = (AmrDev *)(hm + VOL_DEST_MAX);
   for (size_t i = 0; i < n_inst; i++) {
     const gvt_hip_volume *B = volumes[i];
     h[i] = fused_record(B, (features & GVT_HIP_FUSED_SURFACES) != 0);
-    if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
+    if (ao) ho[i] = AoBrick{ fog ? B->d_lgrid : nullptr, mesh ? B->d_occ : nullptr, B->d_ao };
+    else if (mesh) hm[i] = MeshBrick{ fog ? B->d_lgrid : nullptr, B->d_occ };
     else if (fog && amr) hm[i] = MeshBrick{ B->d_lgrid, nullptr };
     else if (fog) hg[i].grid = B->d_lgrid;
     if (central) hf[i] = B->d_ghost; // (null on a brick without an interior face: none of its layers is ever read)
     if (amr) ha[i] = amr_record(B);
   }
   HIPCHK(hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
-  if (mesh || (fog && amr)) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  if (ao) HIPCHK(hipMemcpyAsync(d_agrids, ho, sizeof(AoBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
+  else if (mesh || (fog && amr)) HIPCHK(hipMemcpyAsync(d_mgrids, hm, sizeof(MeshBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   else if (fog) HIPCHK(hipMemcpyAsync(d_grids, hg, sizeof(FogBrick) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (central) HIPCHK(hipMemcpyAsync(d_faces, hf, sizeof(void *) * n_inst, hipMemcpyHostToDevice, C.stream));
   if (amr) HIPCHK(hipMemcpyAsync(d_amr, ha, sizeof(AmrDev) * n_inst, hipMemcpyHostToDevice, C.stream));
@@ -1925,7 +1957,10 @@ int volume_frame_fused(gvt_hip_top *T, gvt_hip_volume *const *volumes, const flo
       // the shaded launches, for the kernels' CENTRAL instantiation (gh: FusedGhost) or the other (NoGhost)
       const auto shaded = [&](auto central_c, auto gh) {
         constexpr bool CENTRAL = decltype(central_c)::value;
-        if (shadow && mesh)
+        if (shadow && ao)
+          launch_fused_ao<VT, CENTRAL>(features, mesh, V0, depth, blocks, C.stream, vol_dev(V0), surf_dev(V0, M), *shadow, d_bricks, d_agrids, T->dev(), P, (unsigned)n, M, fb->d_rgba,
+                                       n_pix, work, d_stats, gh);
+        else if (shadow && mesh)
           launch_fused_mesh<VT, CENTRAL>(features, V0, depth, blocks, C.stream, vol_dev(V0), surf_dev(V0, M), *shadow, d_bricks, d_mgrids, T->dev(), P, (unsigned)n, M, fb->d_rgba, n_pix,
                                          work, d_stats, gh);
         else if (shadow && fog)
@@ -2072,11 +2107,11 @@ void grids_commit(BakedGrids &G, unsigned usable, uint64_t bake, size_t index, s
 void grids_reset(BakedGrids &G) { G.planes = 0; G.usable = 0; G.current = false; G.bake = 0; }
 
 // the shadowed frames.  fog: gvt_hip_volume_frame_fog_shadowed; mesh (with fog): gvt_hip_volume_frame_mesh_shadowed, *mesh_ran = did its
-// kernel run? (fn: the entry point's name in the error texts)
+// kernel run?; ao (with fog): gvt_hip_volume_frame_ao, *ao_ran likewise (fn: the entry point's name in the error texts)
 int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
                                const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth,
                                const gvt_hip_volume_shadow_params *params, gvt_hip_volume_shadow_stats &O, uint64_t &fog_samples, bool mesh = false,
-                               bool *mesh_ran = nullptr) {
+                               bool *mesh_ran = nullptr, bool ao = false, bool *ao_ran = nullptr) {
   int rc;
   if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
   if (!params) { set_error("%s: null params", fn); return GVT_HIP_ERR_INVALID; }
@@ -2119,11 +2154,19 @@ int volume_frame_shadowed_impl(const char *fn, bool fog, gvt_hip_top *T, gvt_hip
       set_error("%s: the frame has surfaces or lit fog but its bricks do not all hold a current occluder grid: %s", fn, stale.c_str());
       return GVT_HIP_ERR_INVALID;
     }
+    // (the AO frame without a usable light is its base frame in every respect: no AO grid is needed)
+    const bool with_ao = ao && H.usable;
+    if (with_ao && !grids_current(&gvt_hip_volume::d_ao, &gvt_hip_volume::ag, "ao", "gvt_hip_volume_ao_grid_bake", "samples, table, surfaces or subgrids", volumes, m, minv,
+                                  n_inst, 1u, stale)) {
+      set_error("%s: the frame has surfaces or lit fog but its bricks do not all hold a current ao grid: %s", fn, stale.c_str());
+      return GVT_HIP_ERR_INVALID;
+    }
     if (fog && (features & GVT_HIP_FUSED_LIT) && !(features & GVT_HIP_FUSED_SURFACES) && !H.usable) // (lit fog alone and no light casts a ray: the shaded fused frame)
       rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S);
     else
-      rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh, fog_ran, with_mesh);
+      rc = volume_frame_fused(T, volumes, minv, n_inst, cam, queues, fb, depth, features, S, &H, sh, fog_ran, with_mesh, nullptr, with_ao);
     if (!rc && mesh_ran) *mesh_ran = with_mesh;
+    if (!rc && ao_ran) *ao_ran = with_ao;
   }
   if (rc) return rc;
   O = gvt_hip_volume_shadow_stats{};
@@ -2222,9 +2265,10 @@ int bake_args(const char *fn, gvt_hip_volume *const *volumes, const float *m, co
 // subgrids unless the flags have GVT_HIP_VOLUME_ALLOW_AMR (amr: does a brick have any?), the CENTRAL clause (flags: the params' word -- with
 // GVT_HIP_VOLUME_ALLOW_CENTRAL bricks that are all CENTRAL pass; the bake's
 // rays march with shading NONE and read no gradient, so the planes do not depend on the kind), at most 2^32 - 1 (vertex, light) pairs.
-// verts: the vertices summed over the bricks; usable: the lights' bits
+// verts: the vertices summed over the bricks; usable: the lights' bits.  lights = false (the AO bake, which needs no light and compares
+// none): without the two light clauses, usable = 0
 int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, uint32_t flags, uint64_t &verts, unsigned &usable,
-                bool *amr = nullptr) {
+                bool *amr = nullptr, bool lights = true) {
   uint32_t features = 0;
   const char *why = "";
   const bool allow_central = (flags & GVT_HIP_VOLUME_ALLOW_CENTRAL) != 0;
@@ -2246,7 +2290,7 @@ int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, 
     // (fused_eligible compares surfaces and lights only where the frame renders them: the bake needs them equal whatever the shading)
     if (B->n_iso != A->n_iso || B->n_pl != A->n_pl || !same_bits(&B->surf_alpha, &A->surf_alpha, sizeof(float)) || !same_bits(B->iso, A->iso, sizeof(float) * (size_t)A->n_iso) ||
         !same_bits(B->plane, A->plane, sizeof(A->plane[0]) * (size_t)A->n_pl)) { set_error("%s: bricks with different surfaces", fn); return GVT_HIP_ERR_INVALID; }
-    if (B->n_lights != A->n_lights || !same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights)) { set_error("%s: bricks with different lights", fn); return GVT_HIP_ERR_INVALID; }
+    if (lights && (B->n_lights != A->n_lights || !same_bits(B->lpos, A->lpos, sizeof(A->lpos[0]) * (size_t)A->n_lights))) { set_error("%s: bricks with different lights", fn); return GVT_HIP_ERR_INVALID; }
     cells += (uint64_t)(B->n[0] - 1) * (uint64_t)(B->n[1] - 1) * (uint64_t)(B->n[2] - 1);
     verts += (uint64_t)B->n[0] * (uint64_t)B->n[1] * (uint64_t)B->n[2];
     for (size_t k = 0; k < i; k++) { // owned cells [off, off + n - 1) per axis: disjoint
@@ -2261,6 +2305,8 @@ int bake_bricks(const char *fn, gvt_hip_volume *const *volumes, const float *m, 
               (unsigned long long)((uint64_t)(A->gn[0] - 1) * (uint64_t)(A->gn[1] - 1) * (uint64_t)(A->gn[2] - 1)));
     return GVT_HIP_ERR_INVALID;
   }
+  usable = 0;
+  if (!lights) return 0;
   usable = shadow_dev(A, 1).usable;
   const unsigned n_usable = (unsigned)__builtin_popcount(usable);
   if (!n_usable) { set_error("%s: no usable light (none set, or every position is zero)", fn); return GVT_HIP_ERR_INVALID; }
@@ -2543,6 +2589,166 @@ extern "C" int gvt_hip_volume_occluder_grid_release(gvt_hip_volume *V) {
   return 0;
 }
 
+// ---- ambient occlusion (the contract: include/gvt_hip.h, "ambient occlusion"; volume_ao_grid.inc, volume_fused_ao.inc)
+extern "C" int gvt_hip_volume_ao_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_volume_ao_params *params,
+                                           gvt_hip_volume_ao_stats *stats) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  int rc;
+  if ((rc = bake_args("volume_ao_grid_bake", volumes, m, minv, n_inst, params ? &params->flags : nullptr))) return rc;
+  if (params->flags & GVT_HIP_VOLUME_ALLOW_AMR) { set_error("volume_ao_grid_bake: GVT_HIP_VOLUME_ALLOW_AMR is not accepted: an AO grid never covers subgrids"); return GVT_HIP_ERR_INVALID; }
+  if (params->bias < 1 || params->bias > 64) { set_error("volume_ao_grid_bake: bias %d, 1 to 64 lattice steps are allowed", params->bias); return GVT_HIP_ERR_INVALID; }
+  if (params->n_dirs < 1 || params->n_dirs > GVT_HIP_VOLUME_AO_MAX_DIRS) {
+    set_error("volume_ao_grid_bake: n_dirs %d, 1 to %d directions are allowed", params->n_dirs, GVT_HIP_VOLUME_AO_MAX_DIRS);
+    return GVT_HIP_ERR_INVALID;
+  }
+  if (!(params->radius > 0.f)) { set_error("volume_ao_grid_bake: radius %g, it must be positive (+Inf: no clip)", (double)params->radius); return GVT_HIP_ERR_INVALID; }
+  float h_dirs[GVT_HIP_VOLUME_AO_MAX_DIRS][3] = {};
+  for (int i = 0; i < params->n_dirs; i++) { // (normalised as shadow_dev normalises the lights)
+    const float x = params->dirs[i][0], y = params->dirs[i][1], z = params->dirs[i][2];
+    const float len = sqrtf((x * x + y * y) + z * z);
+    if (!(len > 0.f && std::isfinite(len))) { set_error("volume_ao_grid_bake: direction %d is zero or not finite", i); return GVT_HIP_ERR_INVALID; }
+    h_dirs[i][0] = x / len; h_dirs[i][1] = y / len; h_dirs[i][2] = z / len;
+  }
+  uint64_t verts = 0;
+  unsigned usable = 0;
+  if ((rc = bake_bricks("volume_ao_grid_bake", volumes, m, minv, n_inst, params->flags, verts, usable, nullptr, false))) return rc;
+  if (verts * (uint64_t)params->n_dirs > 0xffffffffull) {
+    set_error("volume_ao_grid_bake: %llu (vertex, direction) pairs, at most 2^32 - 1", (unsigned long long)(verts * (uint64_t)params->n_dirs));
+    return GVT_HIP_ERR_INVALID;
+  }
+  const gvt_hip_volume *A = volumes[0];
+  Ctx &C = gctx();
+  BakeScope<float> own("volume_ao_grid_bake", C.stream, n_inst);
+  if ((rc = own.allocate(volumes, 1u))) return rc;
+  // SCR_VOL_GRIDS: the per-brick table (VOL_DEST_MAX records), then the directions
+  const size_t table_bytes = sizeof(LightGridBrick) * VOL_DEST_MAX;
+  FusedBrick *d_bricks = (FusedBrick *)scratch_get(SCR_VOL_BRICKS, sizeof(FusedBrick) * n_inst);
+  char *d_table = (char *)scratch_get(SCR_VOL_GRIDS, table_bytes + sizeof(h_dirs));
+  unsigned long long *d_stats = (unsigned long long *)scratch_get(SCR_VOL_FUSED, VOL_FUSED_SHADOW_STATS * sizeof(unsigned long long));
+  unsigned *work = (unsigned *)scratch_get(SCR_VOL_WORK, sizeof(unsigned));
+  if (!d_bricks || !d_table || !d_stats || !work) return own.fail("a scratch allocation");
+  LightGridBrick *d_parts = (LightGridBrick *)d_table;
+  float *d_dirs = (float *)(d_table + table_bytes);
+  static_assert((sizeof(FusedBrick) + sizeof(LightGridBrick)) * VOL_DEST_MAX + sizeof(h_dirs) <= PINNED_STAGE_BYTES, "the two tables and the directions fit the staging block");
+  void *stage = nullptr;
+  if (pinned_stage_begin(&stage)) return own.fail("the staging block");
+  FusedBrick *h = (FusedBrick *)stage;
+  LightGridBrick *hp = (LightGridBrick *)(h + VOL_DEST_MAX);
+  std::memcpy(hp + VOL_DEST_MAX, h_dirs, sizeof(h_dirs));
+  unsigned first = 0;
+  for (size_t i = 0; i < n_inst; i++) {
+    const gvt_hip_volume *B = volumes[i];
+    h[i] = fused_record(B, true);
+    hp[i] = LightGridBrick{ own.fresh[i], first, 0u };
+    first += (unsigned)((size_t)B->n[0] * B->n[1] * B->n[2]);
+  }
+  const unsigned n = first; // (one work item a vertex)
+  bool ok = hipMemcpyAsync(d_bricks, h, sizeof(FusedBrick) * n_inst, hipMemcpyHostToDevice, C.stream) == hipSuccess &&
+            hipMemcpyAsync(d_table, hp, table_bytes + sizeof(h_dirs), hipMemcpyHostToDevice, C.stream) == hipSuccess;
+  if (pinned_stage_end() || !ok) return own.fail("the table upload");
+  ok = hipMemsetAsync(work, 0, sizeof(unsigned), C.stream) == hipSuccess && hipMemsetAsync(d_stats, 0, VOL_BAKE_STATS * sizeof(unsigned long long), C.stream) == hipSuccess &&
+       hipEventCreate(&own.e0) == hipSuccess && hipEventCreate(&own.e1) == hipSuccess;
+  if (!ok) return own.fail("the launch's preparation");
+  Mat4 M, Mi;
+  for (int k = 0; k < 16; k++) { M.m[k] = m[k]; Mi.m[k] = minv[k]; }
+  // the whole grid as one brick, as the light bake states it
+  VolDev U = vol_dev(A);
+  U.vox = nullptr; U.mc = nullptr;
+  U.nx = A->gn[0]; U.ny = A->gn[1]; U.nz = A->gn[2]; U.ox = 0; U.oy = 0; U.oz = 0;
+  U.nbx = (A->gn[0] - 1 + 7) / 8; U.nby = (A->gn[1] - 1 + 7) / 8;
+  for (int a = 0; a < 3; a++) { U.lo[a] = A->go[a] + (float)0 * A->sp[a]; U.hi[a] = A->go[a] + (float)(A->gn[a] - 1) * A->sp[a]; }
+  const float t0 = (float)(params->bias - 1) * A->dt;
+  const unsigned blocks = std::min(blocks_of(n), (unsigned)(std::max(C.n_cu, 1) * 8));
+  ok = hipEventRecord(own.e0, C.stream) == hipSuccess;
+  if (ok)
+    with_voxel_type(A->vtype, [&](auto t) {
+      using VT = decltype(t);
+      k_volume_bake_ao<VT><<<blocks, VOL_BLOCK, 0, C.stream>>>(U, surf_dev(A, Mi), d_bricks, d_parts, (unsigned)n_inst, n, M, Mi, d_dirs, params->n_dirs, t0, params->radius, work,
+                                                              d_stats);
+    });
+  unsigned long long h_stats[VOL_BAKE_STATS] = {};
+  float ms = 0.f;
+  ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(own.e1, C.stream) == hipSuccess &&
+       hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, C.stream) == hipSuccess && hipStreamSynchronize(C.stream) == hipSuccess &&
+       hipEventElapsedTime(&ms, own.e0, own.e1) == hipSuccess;
+  if (!ok) return own.fail("the bake kernel");
+  // commit: every brick at once
+  static uint64_t bake_serial = 0;
+  bake_serial++;
+  for (size_t i = 0; i < n_inst; i++) {
+    gvt_hip_volume *B = volumes[i];
+    hipFree(B->d_ao);
+    B->d_ao = own.commit(i);
+    B->ag_dirs = params->n_dirs; B->ag_bias = params->bias; B->ag_radius = params->radius;
+    grids_commit(B->ag, 1u, bake_serial, i, n_inst, m, minv);
+  }
+  if (stats) {
+    gvt_hip_volume_ao_stats O{};
+    O.rays = (uint64_t)n * (uint64_t)params->n_dirs; O.samples_marched = h_stats[0]; O.samples_gathered = h_stats[1]; O.crossings = h_stats[2]; O.bytes = own.bytes; O.ms = ms;
+    *stats = O;
+  }
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_ao_grid_download(gvt_hip_volume *V, float *out) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V || !out) { set_error("volume_ao_grid_download: null argument"); return GVT_HIP_ERR_INVALID; }
+  if (!V->d_ao) { set_error("volume_ao_grid_download: the volume holds no ao grid"); return GVT_HIP_ERR_INVALID; }
+  HIPCHK(hipStreamSynchronize(gctx().stream));
+  HIPCHK(hipMemcpy(out, V->d_ao, sizeof(float) * (size_t)V->n[0] * V->n[1] * V->n[2], hipMemcpyDeviceToHost));
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_ao_grid_info(gvt_hip_volume *V, gvt_hip_volume_ao_state *out) {
+  if (!V || !out) { set_error("volume_ao_grid_info: null argument"); return GVT_HIP_ERR_INVALID; }
+  gvt_hip_volume_ao_state I{};
+  I.present = V->d_ao ? 1u : 0u;
+  I.current = (V->d_ao && V->ag.current) ? 1u : 0u;
+  I.n_dirs = V->d_ao ? V->ag_dirs : 0;
+  I.bias = V->d_ao ? V->ag_bias : 0;
+  I.radius = V->d_ao ? V->ag_radius : 0.f;
+  I.bytes = V->d_ao ? sizeof(float) * (uint64_t)V->n[0] * V->n[1] * V->n[2] : 0;
+  *out = I;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_ao_grid_release(gvt_hip_volume *V) {
+  if (ensure_init()) return GVT_HIP_ERR_NODEVICE;
+  if (!V) { set_error("volume_ao_grid_release: null"); return GVT_HIP_ERR_INVALID; }
+  if (!V->d_ao) return 0;
+  HIPCHK(hipStreamSynchronize(gctx().stream)); // (a frame in flight reads the plane)
+  hipFree(V->d_ao);
+  V->d_ao = nullptr;
+  grids_reset(V->ag);
+  V->ag_dirs = 0; V->ag_bias = 0; V->ag_radius = 0.f;
+  return 0;
+}
+
+extern "C" int gvt_hip_volume_frame_ao(gvt_hip_top *T, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst, const gvt_hip_camera *cam,
+                                       gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth, const gvt_hip_volume_ao_frame_params *params,
+                                       gvt_hip_volume_ao_frame_stats *stats) {
+  int rc;
+  if ((rc = volume_frame_args(T, volumes, m, minv, n_inst, cam, queues, fb, depth))) return rc;
+  if (!params) { set_error("volume_frame_ao: null params"); return GVT_HIP_ERR_INVALID; }
+  if (params->flags & GVT_HIP_VOLUME_ALLOW_AMR) { set_error("volume_frame_ao: GVT_HIP_VOLUME_ALLOW_AMR is not accepted: an AO grid never covers subgrids"); return GVT_HIP_ERR_INVALID; }
+  if (params->flags & ~(uint32_t)(GVT_HIP_VOLUME_ALLOW_CENTRAL | GVT_HIP_VOLUME_AO_MESH)) { set_error("volume_frame_ao: unknown flag bits %u", params->flags); return GVT_HIP_ERR_INVALID; }
+  const bool mesh = (params->flags & GVT_HIP_VOLUME_AO_MESH) != 0;
+  const gvt_hip_volume_shadow_params base{ params->flags & GVT_HIP_VOLUME_ALLOW_CENTRAL, params->bias };
+  gvt_hip_volume_shadow_stats O{};
+  uint64_t fog_samples = 0;
+  bool mesh_ran = false, ao_ran = false;
+  rc = volume_frame_shadowed_impl("volume_frame_ao", true, T, volumes, m, minv, n_inst, cam, queues, fb, depth, &base, O, fog_samples, mesh, &mesh_ran, true, &ao_ran);
+  if (!rc && stats) {
+    gvt_hip_volume_ao_frame_stats F{};
+    F.base.fog.frame = O;
+    F.base.fog.fog_samples_shadowed = fog_samples;
+    F.base.mesh_shadowed = mesh_ran ? 1u : 0u;
+    F.ao = ao_ran ? 1u : 0u;
+    *stats = F;
+  }
+  return rc;
+}
+
 // ---- AMR volumes: the host side of volume_amr.inc (the contract: include/gvt_hip.h, "AMR volumes")
 namespace {
 
@@ -2697,6 +2903,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
     HIPCHK(hipStreamSynchronize(st)); // (a march in flight reads the tables)
     V->lg.current = false; // (a light grid never covers subgrids, and the ranges change)
     V->og.current = false;
+    V->ag.current = false;
     amr_release(V);
     return amr_refresh_ranges(V, AmrHostRanges{});
   }
@@ -2738,6 +2945,7 @@ extern "C" int gvt_hip_volume_set_subgrids(gvt_hip_volume *V, const gvt_hip_subg
   // commit
   V->lg.current = false;
   V->og.current = false;
+  V->ag.current = false;
   amr_release(V);
   V->d_amr_vox = d_vox; V->d_amr_mc = d_mc; V->d_amr_list = d_list; V->d_amr_desc = d_desc;
   V->sub.assign(grids, grids + n);
@@ -2818,6 +3026,7 @@ extern "C" int gvt_hip_volume_update_amr(gvt_hip_volume *V, const float *samples
   int rc = amr_merge_tables(V);
   if (rc) return rc;
   V->lg.current = false; // (a light grid baked from the old samples is stale; the occluder grid reads meshes, lights and the tree: it stays)
+  V->ag.current = false; // (... and so is an AO grid)
   const hipMemcpyKind kind = (flags & GVT_HIP_UPDATE_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (samples) HIPCHK(hipMemcpyAsync(V->d_vox, samples, sizeof(float) * total, kind, st));
   for (int i = 0; i < n_subgrids; i++)

@@ -691,6 +691,17 @@ def mesh_in_volume(scene, vol, fill=0.6):
     return VolumeData(vol.data, origin, spacing)
 
 
+def ao_directions(n):
+    """The direction set of an ambient occlusion bake (gvt_hip_volume_ao_grid_bake): the n points of the Fibonacci sphere, i = arange(n) +
+    0.5, z = 1 - 2 i / n, r = sqrt(1 - z^2), phi = i pi (3 - sqrt 5), computed in float64 and returned as float32 (n, 3).  The library
+    normalises them again."""
+    i = np.arange(int(n), dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * i / float(n)
+    r = np.sqrt(1.0 - z * z)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1).astype(F)
+
+
 # ------------------------------------------------------------------ AMR volumes (Volume::AddAMRGrid; api::addAmrSubgrid; apps/render/AmrApp.cpp)
 def subgrid_geometry(vol, index):
     """Origin (the position of vertex 0) and vertex spacing of subgrid `index` of vol (-1: the level-0 grid), in float64."""

@@ -591,10 +591,16 @@ class VolumeTracer:
     mesh_shadows (with shadows and fog_shadows; otherwise ValueError): frame() goes through gvt_hip_volume_frame_mesh_shadowed -- meshes
     cast shadows into the volume, from occluder grids baked at the vertices (gvt_hip_volume_occluder_grid_bake).  bake_occluders(scene)
     bakes them; frame() bakes again from the same scene after set_lights().  The library cannot see a mesh move: call bake_occluders
-    again after the scene changed.  A frame that needs a grid and has none is refused (GvtHipError)."""
+    again after the scene changed.  A frame that needs a grid and has none is refused (GvtHipError).
+    ao (with shadows and fog_shadows, without shadow_amr; otherwise ValueError): frame() goes through gvt_hip_volume_frame_ao -- with
+    capi.VOLUME_AO_MESH when mesh_shadows is set -- so the ambient term is ka times the ambient occlusion interpolated from a grid baked at
+    the vertices (gvt_hip_volume_ao_grid_bake).  ao_dirs: a count (scenes.ao_directions) or an (n, 3) array of world-space directions;
+    ao_radius: the AO rays' length (None: 16 lattice steps); ao_bias: the bake's bias.  frame() bakes on the first frame that needs the
+    grid and again after update(), set_surfaces() and set_transfer(), not after set_lights(); rebake_ao() is explicit."""
 
     def __init__(self, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, fused=False, fused_shaded=False, shadows=False, shadow_bias=2,
-                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False, shadow_amr=False):
+                 fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False, shadow_amr=False,
+                 ao=False, ao_dirs=16, ao_radius=None, ao_bias=1):
         import ctypes as C
 
         from .adapter import HipVolumeAdapter
@@ -606,6 +612,10 @@ class VolumeTracer:
             raise ValueError("VolumeTracer: mesh_shadows needs shadows=True and fog_shadows=True (the mesh-shadowed frame is the fog-shadowed frame with one more change)")
         if fused_amr and not fused:
             raise ValueError("VolumeTracer: fused_amr needs fused=True (it is one more allow bit of the fused frame)")
+        if ao and not (shadows and fog_shadows):
+            raise ValueError("VolumeTracer: ao needs shadows=True and fog_shadows=True (the AO frame is the fog-shadowed frame with one more change)")
+        if ao and shadow_amr:
+            raise ValueError("VolumeTracer: ao does not take shadow_amr (an AO grid never covers subgrids)")
         if shadow_amr and not shadows:
             raise ValueError("VolumeTracer: shadow_amr needs shadows=True (it is one more flag bit of the shadowed frames and their bakes)")
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
@@ -647,6 +657,19 @@ class VolumeTracer:
         self._occluder_source = None  # the scene or backend of the last bake_occluders: what frame() bakes from again
         self._occluder_stale = True  # nothing baked yet, or set_lights since the last bake
         self._occluder_kept = None  # adapter.scene_instances' third result: the mesh adapters made here for a scenes.Scene
+        self.ao = bool(ao)
+        if isinstance(ao_dirs, (int, np.integer)):
+            from .scenes import ao_directions
+
+            ao_dirs = ao_directions(int(ao_dirs))
+        self.ao_dirs = np.ascontiguousarray(ao_dirs, np.float32).reshape(-1, 3)
+        if self.ao and not 1 <= len(self.ao_dirs) <= capi.VOLUME_AO_MAX_DIRS:
+            raise ValueError("VolumeTracer: %d AO directions, 1 to %d are allowed" % (len(self.ao_dirs), capi.VOLUME_AO_MAX_DIRS))
+        self.ao_radius = None if ao_radius is None else float(ao_radius)  # None: 16 lattice steps, taken from the first brick at the bake
+        self.ao_bias = int(ao_bias)
+        self.ao_bakes = 0
+        self.ao_stats = None  # ao=True: gvt_hip_volume_ao_stats of the last bake, as a dict
+        self._ao_stale = True  # nothing baked yet, or update / set_surfaces / set_transfer since the last bake
         self._surfaces = False  # set_surfaces with at least one isovalue or slice plane?
         self._lit = False  # set_shading(True)?
         self._usable_lights = 0  # lights of set_lights that cast shadow rays
@@ -663,7 +686,21 @@ class VolumeTracer:
         m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
         minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
         calls = C.c_uint64(0)
-        if self.mesh_shadows:
+        if self.ao and self.shadows and self.fog_shadows:
+            if self._grid_stale and self._lit and self._usable_lights:
+                self.rebake()
+            if self.mesh_shadows and self._occluder_stale and self._occluder_source is not None and self._usable_lights and (self._lit or self._surfaces):
+                self.bake_occluders(self._occluder_source)
+            if self._ao_stale and self._usable_lights and (self._lit or self._surfaces):
+                self.rebake_ao()
+            st = capi.VolumeAoFrameStats()
+            params = capi.VolumeAoFrameParams(self.param_flags | (capi.VOLUME_AO_MESH if self.mesh_shadows else 0), self.shadow_bias)
+            capi.check(capi.load().gvt_hip_volume_frame_ao(self.top.h, self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst),
+                                                           C.byref(pod), self._arr(self.queues), self.fb.h, None if depth is None else depth.h,
+                                                           C.byref(params), C.byref(st)), "gvt_hip_volume_frame_ao")
+            self.shadow_stats = st.as_dict()
+            calls = C.c_uint64(st.base.fog.adapter_calls)
+        elif self.mesh_shadows:
             if self._grid_stale and self._lit and self._usable_lights:
                 self.rebake()
             if self._occluder_stale and self._occluder_source is not None and self._usable_lights and (self._lit or self._surfaces):
@@ -739,6 +776,24 @@ class VolumeTracer:
         self._grid_stale = False
         return self
 
+    def rebake_ao(self):
+        """gvt_hip_volume_ao_grid_bake over the tracer's bricks under its matrix: the AO grid of the AO frame."""
+        import ctypes as C
+
+        m = np.ascontiguousarray(np.tile(self.m, self.n_inst), np.float32)
+        minv = np.ascontiguousarray(np.tile(self.minv, self.n_inst), np.float32)
+        radius = 16.0 * float(self.adapters[0].info()["dt"]) if self.ao_radius is None else self.ao_radius
+        params = capi.VolumeAoParams(self.param_flags, self.ao_bias, len(self.ao_dirs), radius)
+        for i, d in enumerate(self.ao_dirs):
+            params.dirs[i][:] = [float(x) for x in d]
+        st = capi.VolumeAoStats()
+        capi.check(capi.load().gvt_hip_volume_ao_grid_bake(self._arr(self.adapters), capi.ptr(m), capi.ptr(minv), C.c_size_t(self.n_inst), C.byref(params),
+                                                           C.byref(st)), "gvt_hip_volume_ao_grid_bake")
+        self.ao_stats = st.as_dict()
+        self.ao_bakes += 1
+        self._ao_stale = False
+        return self
+
     def bake_occluders(self, scene_or_backend):
         """gvt_hip_volume_occluder_grid_bake over the tracer's bricks under its matrix: which vertices the meshes of scene_or_backend (a
         scenes.Scene or a scheduler.HipBackend, taken as adapter.DepthPlane.render takes them) shadow from each usable light."""
@@ -795,6 +850,7 @@ class VolumeTracer:
         brick that has subgrids is refused by the library, as ever."""
         bricks = self._same_bricking(self.adapters, bricks, amr)  # (all of them checked before the first one changes)
         self._grid_stale = True
+        self._ao_stale = True
         for a, b in zip(self.adapters, bricks):
             if amr and getattr(b, "subgrids", None):
                 a.update_amr(b.data, b.subgrids)
@@ -807,9 +863,18 @@ class VolumeTracer:
     def set_surfaces(self, isovalues=(), slices=(), opacity=1.0):
         """The volume's isosurfaces and slice planes (object space), on every brick."""
         self._grid_stale = True
+        self._ao_stale = True
         self._surfaces = bool(len(isovalues) or len(slices))
         for a in self.adapters:
             a.set_surfaces(isovalues, slices, opacity)
+        return self
+
+    def set_transfer(self, tf):
+        """Another transfer function on every brick (HipVolumeAdapter.set_transfer): the light grids and the AO grid are baked again."""
+        self._grid_stale = True
+        self._ao_stale = True
+        for a in self.adapters:
+            a.set_transfer(tf)
         return self
 
     def set_lights(self, lights, ka=0.4, kd=0.6):
@@ -857,8 +922,13 @@ class VolumeTracer:
         fog_shadows=True adds fog_samples_shadowed of the last frame, light_bakes (bakes so far) and light_grid_rays / _bytes / _ms of the
         last bake (0 before the first).
         mesh_shadows=True adds mesh_shadowed of the last frame, occluder_bakes (bakes so far) and occluder_rays / _rays_blocked / _bytes /
-        _ms of the last bake (0 before the first)."""
+        _ms of the last bake (0 before the first).
+        ao=True adds ao of the last frame (1: the AO kernel ran), ao_bakes (bakes so far) and ao_rays / _bytes / _ms of the last bake."""
         out = self._brick_stats()
+        if self.ao:
+            g = self.ao_stats or {"rays": 0, "bytes": 0, "ms": 0.0}
+            out.update(ao_bakes=self.ao_bakes, ao_rays=g["rays"], ao_bytes=g["bytes"], ao_ms=g["ms"],
+                       ao=0 if self.shadow_stats is None else self.shadow_stats.get("ao", 0))
         if self.mesh_shadows:
             g = self.occluder_stats or {"rays": 0, "rays_blocked": 0, "bytes": 0, "ms": 0.0}
             out.update(occluder_bakes=self.occluder_bakes, occluder_rays=g["rays"], occluder_rays_blocked=g["rays_blocked"], occluder_bytes=g["bytes"],
@@ -1077,7 +1147,7 @@ class VolumeDomainTracer(DomainTracer):
     ray ends; the sum-reduce and the rows_only rectangles add it to zeros."""
 
     def __init__(self, bricks, owner, camera, tf, dist, torch, comm_device, m=None, sampling_rate=1.0, skip=True, native=False, backend=None, overlap=False,
-                 shadows=False, fog_shadows=False, mesh_shadows=False):
+                 shadows=False, fog_shadows=False, mesh_shadows=False, ao=False):
         from types import SimpleNamespace
 
         if shadows:  # (a shadow ray is marched to its end by the lane that needs it: a rank does not hold the foreign bricks it crosses)
@@ -1086,6 +1156,8 @@ class VolumeDomainTracer(DomainTracer):
             raise ValueError("VolumeDomainTracer: fog_shadows need every brick of the volume on one device (VolumeTracer(shadows=True, fog_shadows=True))")
         if mesh_shadows:  # (the mesh-shadowed frame is the fog-shadowed frame with one more change)
             raise ValueError("VolumeDomainTracer: mesh_shadows need every brick of the volume on one device (VolumeTracer(shadows=True, fog_shadows=True, mesh_shadows=True))")
+        if ao:  # (the AO frame is the fog-shadowed frame with one more change, and a vertex's AO rays cross foreign bricks)
+            raise ValueError("VolumeDomainTracer: ao needs every brick of the volume on one device (VolumeTracer(shadows=True, fog_shadows=True, ao=True))")
 
         bricks = list(bricks) if isinstance(bricks, (list, tuple)) else [bricks]
         if m is not None:  # (whatever backend marches the bricks: the next-brick rule is the same)
@@ -1153,11 +1225,12 @@ class MixedTracer:
     mesh_shadows (with shadows and fog_shadows): the meshes cast shadows into the volume (VolumeTracer's mesh_shadows).  frame() bakes the
     occluder grids before the first volume frame that needs them and again after update_scene() and set_lights(); rebake_occluders() is
     explicit.  set_camera(), update() and set_surfaces() do not bake.
-    shadow_amr (with shadows): VolumeTracer's -- the shadowed frames and both bakes take bricks with AMR subgrids."""
+    shadow_amr (with shadows): VolumeTracer's -- the shadowed frames and both bakes take bricks with AMR subgrids.
+    ao, ao_dirs, ao_radius, ao_bias: VolumeTracer's -- the volume frame is the AO frame (meshes do not occlude ambient light)."""
 
     def __init__(self, scene, bricks, camera, tf, m=None, sampling_rate=1.0, skip=True, native=False, normal_mode=NORMALS_FLAT, fused=False, fused_shaded=False,
                  shadows=False, shadow_bias=2, fog_shadows=False, fog_bias=1, mesh_shadows=False, fused_central=False, amr_shaded=False, fused_amr=False,
-                 shadow_amr=False):
+                 shadow_amr=False, ao=False, ao_dirs=16, ao_radius=None, ao_bias=1):
         from dataclasses import replace
 
         from .adapter import DepthPlane
@@ -1173,7 +1246,7 @@ class MixedTracer:
         self.volume = VolumeTracer(bricks, camera, tf, m=m, sampling_rate=sampling_rate, skip=skip, native=native, fused=fused,
                                    fused_shaded=fused_shaded, shadows=shadows, shadow_bias=shadow_bias, fog_shadows=fog_shadows, fog_bias=fog_bias,
                                    mesh_shadows=mesh_shadows, fused_central=fused_central, amr_shaded=amr_shaded, fused_amr=fused_amr,
-                                   shadow_amr=shadow_amr)
+                                   shadow_amr=shadow_amr, ao=ao, ao_dirs=ao_dirs, ao_radius=ao_radius, ao_bias=ao_bias)
         # (shadow_amr: the shadowed frames and the bakes take AMR bricks too, VolumeTracer's; amr_shaded: AMR bricks take surfaces and lit fog, in the clipped frame too; fused_amr: AMR bricks in the fused clipped frame too; fused: its clipped frame in one launch; fused_shaded: with surfaces or lit fog too; fused_central: with CENTRAL bricks too; shadows: the volume's surfaces shadowed by the
         # volume; fog_shadows: its lit fog too, from the baked light grids; mesh_shadows: both shadowed by the meshes as well, from the baked
         # occluder grids -- without it the meshes cast no shadow into the volume)

@@ -960,7 +960,7 @@ int gvt_hip_volume_frame_fused_amr(gvt_hip_top *, gvt_hip_volume *const *volumes
  * COUNTERS.  shadow_rays = (samples with at least one rendered crossing) x (lights with a usable ws_j); shadow_brick_visits,
  * shadow_crossings and shadow_samples_marched / _gathered are the fused frame's counters applied to the shadow rays.  They are kept
  * apart from the camera rays' counters, which equal those of the unshadowed frame whenever the two images agree.
- * OUT OF SCOPE.  Ambient occlusion; shadowed fog and geometry shadowing the volume (both below); the volume attenuating mesh shadow rays; the Domain
+ * OUT OF SCOPE.  Ambient occlusion in this frame (see "ambient occlusion" below); shadowed fog and geometry shadowing the volume (both below); the volume attenuating mesh shadow rays; the Domain
  * scheduler (a rank does not hold the foreign bricks a shadow ray needs); AMR frames without GVT_HIP_VOLUME_ALLOW_AMR, and CENTRAL
  * frames without GVT_HIP_VOLUME_ALLOW_CENTRAL; shadows in the per-brick loop.
  *
@@ -1061,7 +1061,7 @@ int gvt_hip_volume_frame_shadowed(gvt_hip_top *, gvt_hip_volume *const *volumes,
  * frames count them; bytes = the planes' size; ms = the launch's event time.  Frame: gvt_hip_volume_shadow_stats, and
  * fog_samples_shadowed = samples_shaded when the fog kernel ran (else 0).
  * A volume that holds a grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees the grid.
- * OUT OF SCOPE.  A coarser or compressed grid; pruning vertices no sample reads; ambient occlusion; the
+ * OUT OF SCOPE.  A coarser or compressed grid; pruning vertices no sample reads; ambient occlusion in this frame (see "ambient occlusion" below); the
  * Domain scheduler; AMR frames, and CENTRAL frames without GVT_HIP_VOLUME_ALLOW_CENTRAL ("shadowed surfaces", CENTRAL); moving the
  * crossings' shadow rays onto the grid. */
 typedef struct {
@@ -1174,6 +1174,96 @@ int gvt_hip_volume_frame_mesh_shadowed(gvt_hip_top *, gvt_hip_volume *const *vol
                                        const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb,
                                        const gvt_hip_depth *depth /* may be NULL */, const gvt_hip_volume_shadow_params *params,
                                        gvt_hip_volume_mesh_shadow_stats *stats /* may be NULL */);
+
+/* ---- ambient occlusion: AO grids baked on the device, read in-frame (additive: the ABI revision stays 6, no entry point above changes) ----
+ * The ambient term of the shadowed frames stops being a constant: how open a point of the volume is to its surroundings is computed
+ * ONCE at every grid vertex (gvt_hip_volume_ao_grid_bake), kept beside the samples as one float32 plane and interpolated wherever ka is
+ * used (gvt_hip_volume_frame_ao).
+ * THE GRID.  For a frame of bricks of ONE grid, every global vertex I has one float32 value AO(I):
+ *   wp     = the vertex in world space, exactly as "shadowed fog" computes it (p[a] = origin[a] + (float)I[a] * spacing[a]; m as a point)
+ *   d_i    = the caller's direction i of n_dirs (1 .. GVT_HIP_VOLUME_AO_MAX_DIRS, world space), normalised by the host in float32 the way
+ *            the lights are: d / sqrtf((x * x + y * y) + z * z); a zero or non-finite direction is refused
+ *   ray i: origin wp, direction d_i, t_min = (float)(bias - 1) * dt, no colour, no opacity, flag GVT_HIP_RAY_CLIP with t_max = radius
+ *          (sample k is taken while (float)k * dt < radius); with radius = +Inf no flag and no clip
+ *   A_i    = the opacity this ray deposits when marched over the WHOLE grid as ONE brick with the frame's surfaces and shading NONE: the
+ *            definition of G_j ("shadowed fog") with the clip added, nothing else -- the side mask is carried, the arrives-opaque rule
+ *            holds, GVT_HIP_VOLUME_OPAQUE_A ends the ray
+ *   AO(I)  : s = 0.f; for i = 0 .. n_dirs - 1 in order: s = s + (1.f - A_i); AO = s / (float)n_dirs   (the order is part of the contract)
+ * A brick stores AO at its own vertices, at the samples' own index, in one plane; shared layers twice with the same bits.  The bits are
+ * the one brick's for every bricking: the walk is the light bake's walk by sample ownership, not the next-brick rule, so directions that
+ * run in a brick face, axis-parallel ones included, are legal.
+ * THE BAKE.  Eligibility is gvt_hip_volume_light_grid_bake's without its two light clauses (an AO bake needs no light and compares
+ * none): flags 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL (GVT_HIP_VOLUME_ALLOW_AMR is refused, and so are bricks with subgrids); bias 1 .. 64;
+ * n_dirs 1 .. 32; radius > 0 and not NaN; at most 2^32 - 1 (vertex, direction) pairs.  Refusals: GVT_HIP_ERR_INVALID, the message names
+ * the clause.  A plane that cannot be allocated: GVT_HIP_ERR_CAPACITY.  A HIP call that fails: GVT_HIP_ERR_DEVICE.  In every failing
+ * case each brick keeps the AO grid it had.  The call waits for its launch.  One lane per vertex walks the vertex's rays one after
+ * another (volume_ao_grid.inc).
+ * CURRENT.  A frame's AO grids are current if ONE bake covered exactly these volumes in this order with the same m and minv bits and
+ * since then no brick has had _update_samples[_typed], _update_amr, _set_transfer, _set_surfaces or _set_subgrids.  _set_lights,
+ * _set_shading, _set_gradient and _set_ghosts do NOT make them stale.
+ * THE FRAME.  gvt_hip_volume_frame_ao is its BASE frame -- gvt_hip_volume_frame_fog_shadowed, or with GVT_HIP_VOLUME_AO_MESH in the flags
+ * gvt_hip_volume_frame_mesh_shadowed: same arguments, same refusals, crossings lit through exact in-kernel shadow rays, the fog through
+ * Tg (and Og) -- with ONE more change.  At a sample whose cell is c and whose fractions are f
+ *     AOg  = trilinear interpolation of AO at the cell's eight vertices (the sample's c and f; nesting x, then y, then z, as Tg)
+ *     ka_s = ka * AOg
+ *     shaded lit fog sample (tc.w > 0):  rgb[a] = tc.rgb[a] * (ka_s + kd * sum[a])     (a NaN or zero gradient: tc.rgb * ka_s)
+ *     crossing at sample k:              the same ka_s in ka's place, AOg from sample k's own cell, shared by all its crossings
+ * AO is read only where ka is used; A never depends on it and no ray is cast or skipped because of it, so every counter of `base`
+ * equals the base frame's, skipping stays exact against GVT_HIP_VOLUME_NO_SKIP and the image is the same bits for every bricking.
+ * INERT.  No usable light, or neither surfaces nor effective lit shading: the call is the base frame in every respect; ao = 0 and no AO
+ * grid is needed.
+ * REFUSED (GVT_HIP_ERR_INVALID, the message names the clause, nothing changed, the framebuffer not cleared): everything the base frame
+ * refuses; unknown flag bits; GVT_HIP_VOLUME_ALLOW_AMR; a frame that is not inert and whose bricks do not all hold a CURRENT AO grid
+ * ("ao grid").
+ * CONSEQUENCES.  With AO = 1 at every vertex the bits are the base frame's (ka * 1.f is ka); radius <= dt with bias 1 gives that grid
+ * (t_min = 0 puts the ray's first sample at k = 1, and (float)1 * dt < radius fails: no sample, A_i = 0).  With ka = 0 the bits are the
+ * base frame's at ka = 0.
+ * DEVIATIONS.  (1) AO is interpolated from level-0 vertices: one cell soft, and a vertex just behind a sheet sees the sheet; bias is the
+ * remedy, as for shadows.  (2) Meshes do not occlude ambient light, and the mesh frame is untouched.  (3) The direction set is fixed per
+ * bake and not rotated per vertex: with few directions banding follows the set.
+ * COUNTERS.  Bake: rays = (vertices summed over the bricks) x n_dirs; samples_marched / _gathered / crossings as the light bake's;
+ * bytes = the planes' size; ms = the event time around the launch.  Frame: the base frame's, and ao = 1 when the AO kernel ran.
+ * A volume that holds an AO grid renders through every other entry point with the bits it had.  gvt_hip_volume_destroy frees it.
+ * OUT OF SCOPE.  AMR bricks; AO in the unshadowed fused frames and in the per-brick loop; uint8 or coarser planes; the Domain scheduler. */
+#define GVT_HIP_VOLUME_AO_MAX_DIRS 32
+#define GVT_HIP_VOLUME_AO_MESH 8u /* flags of gvt_hip_volume_ao_frame_params only: the base frame is the mesh-shadowed frame */
+typedef struct {
+  uint32_t flags; /* 0 or GVT_HIP_VOLUME_ALLOW_CENTRAL */
+  int32_t bias;   /* the first sample of a vertex's AO rays, 1 .. 64 */
+  int32_t n_dirs; /* 1 .. GVT_HIP_VOLUME_AO_MAX_DIRS */
+  float radius;   /* > 0; +Inf: no clip */
+  float dirs[GVT_HIP_VOLUME_AO_MAX_DIRS][3];
+} gvt_hip_volume_ao_params;
+typedef struct {
+  uint64_t rays, samples_marched, samples_gathered, crossings, bytes; /* rays = vertices x n_dirs */
+  float ms;
+  uint32_t pad;
+} gvt_hip_volume_ao_stats;
+typedef struct {
+  uint32_t present, current; /* a grid is held | ... and no call has made it stale since its bake */
+  int32_t n_dirs, bias;      /* of the bake */
+  float radius;
+  uint32_t pad;
+  uint64_t bytes;
+} gvt_hip_volume_ao_state;
+typedef struct {
+  uint32_t flags; /* 0, GVT_HIP_VOLUME_ALLOW_CENTRAL, GVT_HIP_VOLUME_AO_MESH, or both */
+  int32_t bias;   /* the crossings' shadow rays', 1 .. 64 */
+} gvt_hip_volume_ao_frame_params;
+typedef struct {
+  gvt_hip_volume_mesh_shadow_stats base; /* the base frame's counters, same meaning */
+  uint32_t ao, pad;                      /* ao = 1: the AO kernel ran */
+} gvt_hip_volume_ao_frame_stats;
+int gvt_hip_volume_ao_grid_bake(gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                                const gvt_hip_volume_ao_params *params, gvt_hip_volume_ao_stats *stats /* may be NULL */);
+/* out: host memory, counts[0] * counts[1] * counts[2] floats at i + nx * (j + ny * k).  No grid: GVT_HIP_ERR_INVALID.  A stale grid
+ * can still be downloaded. */
+int gvt_hip_volume_ao_grid_download(gvt_hip_volume *, float *out);
+int gvt_hip_volume_ao_grid_info(gvt_hip_volume *, gvt_hip_volume_ao_state *out);
+int gvt_hip_volume_ao_grid_release(gvt_hip_volume *); /* frees the plane; a volume without a grid: 0 */
+int gvt_hip_volume_frame_ao(gvt_hip_top *, gvt_hip_volume *const *volumes, const float *m, const float *minv, size_t n_inst,
+                            const gvt_hip_camera *cam, gvt_hip_queue *const *queues, gvt_hip_fb *fb, const gvt_hip_depth *depth /* may be NULL */,
+                            const gvt_hip_volume_ao_frame_params *params, gvt_hip_volume_ao_frame_stats *stats /* may be NULL */);
 
 /* ---- framebuffer: IceTComposite (composite/IceTComposite.cpp:79-157) ---- */
 gvt_hip_fb *gvt_hip_fb_create(int width, int height);

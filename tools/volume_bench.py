@@ -69,6 +69,9 @@ Kernel times come from a separate run under `rocprofv3 --kernel-trace --stats` (
                                              and the samples shaded per frame, and the two framebuffers compared bitwise after every pair
   python tools/volume_bench.py --fused --shade --fog-shadows  shadowed fog (gvt_hip_volume_frame_fog_shadowed): the lit fused frame, the same
                                                         frame with the fog shadowed from the light grids, and the bake
+  python tools/volume_bench.py --fused --shade --fog-shadows --ao [--mesh-shadows] [--surfaces] [--gradient central]  ambient occlusion
+                                             (gvt_hip_volume_frame_ao): per bricking the AO bake's ms beside the light grids' bake, the AO
+                                             frame against its base frame in the same run, the brickings' framebuffers compared bitwise
   python tools/volume_bench.py --fused --shade --fog-shadows --mesh-shadows  meshes shadowing the volume (gvt_hip_volume_frame_mesh_shadowed):
                                                         the bunny of scenes.bunny_scene inside the grid (scenes.mesh_in_volume); the bake of the
                                                         occluder grids and its share spent in any-hit launches; the fog-shadowed frame and the
@@ -394,6 +397,62 @@ def run_mesh_shadows(n, split, steps, warmup, rate, kind, vol, shape, dtype="f32
            "fog_ms_median": med(fog), "fog_ms_min": round(min(fog), 3), "fog_ms_max": round(max(fog), 3),
            "mesh_ms_median": med(mesh), "mesh_ms_min": round(min(mesh), 3), "mesh_ms_max": round(max(mesh), 3),
            "mesh_over_fog": round(float(np.median(mesh)) / float(np.median(fog)), 4), "mesh_shadowed": int(st["mesh_shadowed"]),
+           "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "samples_shaded": int(st["samples_shaded"]),
+           "crossings_per_frame": int(st["crossings_rendered"]), "shadow_rays": int(st["shadow_rays"]),
+           "counters_same": bool(all(st[k] == ps[k] for k in ("samples_marched", "samples_gathered", "samples_shaded", "brick_visits", "rays_deposited", "shadow_rays",
+                                                              "shadow_samples_marched"))),
+           "same_bits_as_first": None if first is None else bool((first.view(np.uint32) == fb.view(np.uint32)).all())}
+    return row, fb
+
+
+def run_ao(n, split, steps, warmup, rate, kind, vol, shape, dtype="f32", first=None, mesh=False, central=False, dirs=16):
+    """Ambient occlusion: the base frame (fog-shadowed; mesh: mesh-shadowed, the bunny inside the grid) against the AO frame
+    (gvt_hip_volume_frame_ao), alternating frame by frame on one tracer (VolumeTracer.ao switches the entry point); the AO bake (`dirs`
+    Fibonacci directions, 16 lattice steps) timed on its own beside the light grids' bake on the same bricks in the same run -- both a
+    cost per change, not per frame.  shape: "lit" or "surf_lit".  central: CENTRAL bricks under the flag.  Returns (row, the AO framebuffer)."""
+    scene = scenes.bunny_scene(1920, 1080) if mesh else None
+    placed = scenes.mesh_in_volume(scene, vol, fill=0.6) if mesh else vol
+    bricks = placed if split == (1, 1, 1) and not central else scenes.split_volume(placed, *split, ghosts=True)
+    tr = VolumeTracer(bricks, scene.camera if mesh else camera(), transfer(kind, dtype), sampling_rate=rate, native=dtype != "f32", fused=True, fused_shaded=True,
+                      shadows=True, fog_shadows=True, mesh_shadows=mesh, fused_central=central, ao=True, ao_dirs=dirs)
+    _, lo, hi = DTYPES[dtype]
+    if shape != "lit":
+        tr.set_surfaces(tuple(lo + v * (hi - lo) for v in SURFACE_MODES["reached"]), (), 0.3)
+    tr.set_lights(SHADE_LIGHTS[:1]).set_shading(True)
+    if central:
+        tr.set_gradient("central")
+    if mesh:
+        tr.bake_occluders(scene)
+    bake, light = [], []
+    for i in range(warmup + steps):
+        tr.rebake_ao()
+        bake.append(tr.ao_stats["ms"])
+        tr.rebake()
+        light.append(tr.light_grid_stats["ms"])
+    bake, light = bake[warmup:], light[warmup:]
+    g = tr.ao_stats
+    base, ao = [], []
+
+    def frame(flag):
+        tr.ao = flag
+        tr.frame()
+
+    for i in range(warmup + steps):
+        base.append(timed(lambda: frame(False)))
+        ps = tr.stats()
+        ao.append(timed(lambda: frame(True)))
+    base, ao = base[warmup:], ao[warmup:]
+    st = tr.stats()
+    fb = tr.framebuffer(False).copy()
+    row = {"mode": "fused_ao", "shape": shape, "base": "mesh_shadowed" if mesh else "fog_shadowed", "gradient": "central" if central else "cell", "n": n, "dtype": dtype,
+           "tf": kind, "bricks": int(np.prod(split)), "sampling_rate": rate, "ao_dirs": int(dirs), "ao_radius_steps": 16,
+           "bake_ms_median": med(bake), "bake_ms_min": round(min(bake), 3), "bake_ms_max": round(max(bake), 3), "bake_rays": int(g["rays"]),
+           "bake_mrays_per_s": round(g["rays"] / float(np.median(bake)) / 1e3, 1), "bake_samples": int(g["samples_marched"]),
+           "bake_samples_interpolated": int(g["samples_gathered"]), "grid_bytes": int(g["bytes"]), "light_bake_ms_median": med(light),
+           "bake_over_light_bake": round(float(np.median(bake)) / float(np.median(light)), 3),
+           "base_ms_median": med(base), "base_ms_min": round(min(base), 3), "base_ms_max": round(max(base), 3),
+           "ao_ms_median": med(ao), "ao_ms_min": round(min(ao), 3), "ao_ms_max": round(max(ao), 3),
+           "ao_over_base": round(float(np.median(ao)) / float(np.median(base)), 4), "ao": int(st["ao"]),
            "samples_per_frame": int(st["samples_marched"]), "samples_interpolated": int(st["samples_gathered"]), "samples_shaded": int(st["samples_shaded"]),
            "crossings_per_frame": int(st["crossings_rendered"]), "shadow_rays": int(st["shadow_rays"]),
            "counters_same": bool(all(st[k] == ps[k] for k in ("samples_marched", "samples_gathered", "samples_shaded", "brick_visits", "rays_deposited", "shadow_rays",
@@ -1024,6 +1083,9 @@ def main():
     ap.add_argument("--bias", type=int, default=2, help="with --shadows: the first shadow sample's lattice index")
     ap.add_argument("--fog-shadows", action="store_true", help="with --fused --shade: the lit fused frame against the fog-shadowed frame, and the bake of its light grids")
     ap.add_argument("--mesh-shadows", action="store_true", help="with --fused --shade --fog-shadows: the fog-shadowed frame against the mesh-shadowed frame, and the bake of its occluder grids")
+    ap.add_argument("--ao", action="store_true", help="with --fused --shade --fog-shadows [--mesh-shadows] [--surfaces] [--gradient central]: the base frame against the AO frame, "
+                                                      "and the bake of the AO grid beside the light grids'")
+    ap.add_argument("--ao-dirs", type=int, default=16, help="with --ao: directions of the bake (Fibonacci sphere)")
     a = ap.parse_args()
     if a.update or a.domains:
         import torch  # noqa: F401  (the device samples; imported before the library initialises the device)
@@ -1102,6 +1164,19 @@ def main():
         ap.error("--fog-shadows goes with --fused --shade")
     if a.mesh_shadows and not a.fog_shadows:
         ap.error("--mesh-shadows goes with --fused --shade --fog-shadows")
+    if a.ao:  # ambient occlusion: its own rows, and nothing else
+        if not (a.fused and a.shade and a.fog_shadows):
+            ap.error("--ao goes with --fused --shade --fog-shadows")
+        for n in a.sizes:
+            vol = noise(n, a.dtype)
+            for shape, kind in [("lit", k) for k in a.tf] + ([("surf_lit", "thin")] if a.surfaces else []):
+                first = None
+                for nb in a.bricks:
+                    r, fb = run_ao(n, FUSED_SPLITS[nb], a.steps, a.warmup, a.rate, kind, vol, shape, a.dtype, first, a.mesh_shadows, a.gradient == "central", a.ao_dirs)
+                    first = fb if first is None else first
+                    out["runs"].append(r)
+                    print(json.dumps(r), flush=True)
+        a.sizes = []
     if a.fused and a.gradient == "central":  # the CENTRAL rows, ahead of the rows the other flags print: fused against the loop, and the shadowed frames asked for against their CELL frames
         for n in a.sizes:
             vol = noise(n, a.dtype)
